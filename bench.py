@@ -520,6 +520,32 @@ def device_identity(torch, local_rank, stub):
         return f"cuda:{local_rank}"
 
 
+def dump_outputs(out_dir, groups, rank, world, stub, budget=48 << 20):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as DIR/<name>.npy (float64 / float32).
+    Every robot's PlanResult (findBestPath's answer), and the master costmaps (updateMap's answer) of a fixed, seeded sample
+    of robots, whole: all of them would not fit the budget.  The arrays are read after the timed region has ended."""
+    from navigation_amd._lib import PlanResult
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"rank{rank}_" if world > 1 else ""
+    res = np.concatenate([g.rview for g in groups])
+    for name, _ in PlanResult._fields_:
+        if name != "reserved":
+            np.save(os.path.join(out_dir, f"{tag}plan_{name}.npy"), np.asarray(res[name], np.float64))
+    if stub:
+        return
+    n = len(res)
+    ny, nx = groups[0].fl.ny, groups[0].fl.nx
+    k = max(1, min(n, 32, budget // (ny * nx * 4)))
+    pick = np.sort(np.random.RandomState(20261015).choice(n, k, replace=False))
+    maps, first = [], 0
+    for g in groups:
+        for i in pick[(pick >= first) & (pick < first + g.n)]:
+            maps.append(g.fl.master(int(i - first), 1)[0])
+        first += g.n
+    np.save(os.path.join(out_dir, f"{tag}costmap_master_robots.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{tag}costmap_master.npy"), np.stack(maps).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -543,6 +569,8 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-process rehearsal on a box with ONE GPU: every rank uses device 0, collectives over gloo")
     ap.add_argument("--stub-fleet", action="store_true", help="host-only stand-in for the fleet (CPU tests of the N > 1 code path; computes nothing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (plan results, a seeded sample of master costmaps) as DIR/<name>.npy")
     args = ap.parse_args()
 
     # ---- N ranks.  Nothing above or below this block has touched torch / HIP yet.
@@ -706,6 +734,8 @@ def main():
         dom_n += cnt
         g.fl.profile(False)
         g.fl.profile_select(None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, groups, rank, world, stub)
     boxes = np.concatenate([g.fl.bounds() for g in groups])
     win_cells = int(((boxes[:, 1] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 2])).sum())
     wb = np.concatenate([g.fl.wavefront_boxes() for g in groups]).astype(np.int64)

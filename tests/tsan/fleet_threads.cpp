@@ -5,6 +5,8 @@
 // No application lock: the library's per-fleet mutex is all that orders them.  TSAN aborts the run on any data race.
 // A cycle's result must come from ONE configuration (best_index and n_scored agree): a configure that landed inside
 // a cycle's launch sequence would show as a mixed pair.
+// Each helper thread does at most one operation per finished cycle: the fleet mutex is not fair, and helpers that
+// re-lock it straight away can starve thread A for minutes under TSAN.  They still land anywhere inside a cycle.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -51,9 +53,17 @@ int main(int argc, char** argv) {
 
   std::atomic<bool> stop{false};
   std::atomic<long> n_cfg{0}, n_aux{0}, n_read{0};
+  std::atomic<int> cycles_done{0};
+  auto pace = [&](int& seen) {  // wait (without the lock) until thread A has finished another cycle
+    while (!stop.load() && cycles_done.load() == seen) std::this_thread::yield();
+    seen = cycles_done.load();
+  };
   std::thread tb([&] {
     bool which = false;
+    int seen = -1;
     while (!stop.load()) {
+      pace(seen);
+      if (stop.load()) break;
       which = !which;
       CK(navgpu_planner_configure(f, which ? &cb : &ca));
       ++n_cfg;
@@ -62,7 +72,10 @@ int main(int argc, char** argv) {
   });
   std::thread tc([&] {
     int k = 0;
+    int seen = -1;
     while (!stop.load()) {
+      pace(seen);
+      if (stop.load()) break;
       navgpu_inflation_params q = ip;
       q.inflation_radius = (k & 1) ? 0.55 : 0.40;
       CK(navgpu_inflation_configure(f, &q));
@@ -79,7 +92,10 @@ int main(int argc, char** argv) {
   std::thread td([&] {
     std::vector<int32_t> boxes(4 * n);
     std::vector<uint32_t> lv(3 * n);
+    int seen = -1;
     while (!stop.load()) {
+      pace(seen);
+      if (stop.load()) break;
       CK(navgpu_costmap_bounds(f, 0, n, boxes.data()));
       CK(navgpu_planner_wavefront_levels(f, 0, n, lv.data()));
       int rc = navgpu_planner_wavefront_boxes(f, 0, n, boxes.data());
@@ -120,6 +136,7 @@ int main(int argc, char** argv) {
       float p[9] = {1.6f, 1.6f, 0, 1.6f, 1.6f, 0.1f, 1.6f, 1.6f, 0.2f}, v[9] = {0.2f, 0, 0, 0.2f, 0, 0, 0.2f, 0, 0};
       CK(navgpu_planner_stage_poses(f, 0, n, p, v));
     }
+    ++cycles_done;
   }
   stop.store(true);
   tb.join(); tc.join(); td.join();
