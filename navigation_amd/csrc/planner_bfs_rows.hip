@@ -26,77 +26,70 @@ __host__ __device__ inline size_t bfs_rows_lds_words(uint32_t nx, uint32_t ny) {
   const uint32_t nw = bfs_rows_waves(ny);
   return (((size_t)nw * kRowsPerWave * ((nx + 31) >> 5) + 3) & ~(size_t)3) + (size_t)kCareRows * kCareWords + (size_t)(nw + 2) * 2 * kRowsHalo * (2 * Wp + kRowsRecordPad);
 }
-// One group of four words (A B C D, left neighbour word L, right neighbour word R) of one level, skipped as a whole when
-// bit g of the wave's active mask is clear.  Per word:
-//   x = (f << 1 | left >> 31) | (f >> 1 | right << 31) | up | down;   cand = x & ~blocked;   blocked |= x
-// (six vector instructions: two v_alignbit, two v_or with the DPP row shift folded in, v_bitop3, v_or3)
-// cand* leave in h* (the words are written back by rowsCommit4 once every group has read the old frontier).
-// nz: bit g set when any lane has new cells in the group; lo / hi: when its first / last word has (the neighbouring
-// group borders them next level).
-__device__ __forceinline__ void rowsGroup4(const int g, const uint32_t aw, uint32_t& nz, uint32_t& lo, uint32_t& hi,
-                                           uint32_t& bA, uint32_t& bB, uint32_t& bC, uint32_t& bD, const uint32_t fL, const uint32_t fA,
-                                           const uint32_t fB, const uint32_t fC, const uint32_t fD, const uint32_t fR, uint32_t& hA, uint32_t& hB,
-                                           uint32_t& hC, uint32_t& hD) {
-  uint32_t tA, tB, tC, tD, uA, uB, uC, uD, st;
+// One group of four words f[0..3] of one level, updated in place, skipped as a whole when bit g of the wave's active mask is
+// clear.  Per word:
+//   x = (f << 1 | left >> 31) | (f >> 1 | right << 31) | up | down;   new f = x & ~blocked;   blocked |= x
+// (six vector instructions: two v_alignbit, two v_or with the DPP row shift folded in, v_bitop3, v_or3).  The new frontier is
+// written over f once every neighbour in the group has been read.  The old last word goes to p before the skip, live or not:
+// it is the next group's left neighbour L, so the caller alternates two registers (a group that is not live holds no frontier
+// cell, and its last word is that).  R: the next group's first word, still old.
+// nz: bit g set when any lane has new cells in the group; lo / hi: when its first / last word has (the neighbouring group
+// borders them next level).  The three tests are compares into SGPR pairs combined by scalar ops after the vector work: no
+// vcc -> branch round trip in the group's path.
+__device__ __forceinline__ void rowsGroup4(const int g, const uint32_t aw, uint32_t& nz, uint32_t& lo, uint32_t& hi, uint32_t* __restrict__ b,
+                                           uint32_t* __restrict__ f, const uint32_t L, const uint32_t R, uint32_t& p) {
+  uint32_t u0, u1, u2, u3, t0, t1, t2, t3, st;
+  uint64_t c0, c1, c2;
+#define NAVGPU_ROWS_DPP " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
   asm volatile(
+      "v_mov_b32 %[p], %[f3]\n\t"
       "s_bitcmp1_b32 %[aw], %[g]\n\t"
       "s_cbranch_scc0 1f\n\t"
-      "v_alignbit_b32 %[uA], %[fA], %[fL], 31\n\t"
-      "v_alignbit_b32 %[uB], %[fB], %[fA], 31\n\t"
-      "v_alignbit_b32 %[uC], %[fC], %[fB], 31\n\t"
-      "v_alignbit_b32 %[uD], %[fD], %[fC], 31\n\t"
-      "v_alignbit_b32 %[hA], %[fB], %[fA], 1\n\t"
-      "v_alignbit_b32 %[hB], %[fC], %[fB], 1\n\t"
-      "v_alignbit_b32 %[hC], %[fD], %[fC], 1\n\t"
-      "v_alignbit_b32 %[hD], %[fR], %[fD], 1\n\t"
-      "v_or_b32_dpp %[tA], %[fA], %[uA] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[tB], %[fB], %[uB] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[tC], %[fC], %[uC] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[tD], %[fD], %[uD] wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[uA], %[fA], %[hA] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[uB], %[fB], %[hB] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[uC], %[fC], %[hC] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_or_b32_dpp %[uD], %[fD], %[hD] wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-      "v_bitop3_b32 %[hA], %[tA], %[bA], %[uA] bitop3:0x32\n\t"
-      "v_bitop3_b32 %[hB], %[tB], %[bB], %[uB] bitop3:0x32\n\t"
-      "v_bitop3_b32 %[hC], %[tC], %[bC], %[uC] bitop3:0x32\n\t"
-      "v_bitop3_b32 %[hD], %[tD], %[bD], %[uD] bitop3:0x32\n\t"
-      "v_or3_b32 %[bA], %[bA], %[tA], %[uA]\n\t"
-      "v_or3_b32 %[bB], %[bB], %[tB], %[uB]\n\t"
-      "v_or3_b32 %[bC], %[bC], %[tC], %[uC]\n\t"
-      "v_or3_b32 %[bD], %[bD], %[tD], %[uD]\n\t"
-      "v_or3_b32 %[tA], %[hA], %[hB], %[hC]\n\t"
-      "v_or_b32_e32 %[tA], %[tA], %[hD]\n\t"
-      "v_cmp_ne_u32_e32 vcc, 0, %[tA]\n\t"
-      "s_cbranch_vccz 1f\n\t"
-      "s_bitset1_b32 %[nz], %[g]\n\t"
-      "v_cmp_ne_u32_e32 vcc, 0, %[hA]\n\t"
-      "s_cbranch_vccz 3f\n\t"
-      "s_bitset1_b32 %[lo], %[g]\n\t"
-      "3:\n\t"
-      "v_cmp_ne_u32_e32 vcc, 0, %[hD]\n\t"
-      "s_cbranch_vccz 1f\n\t"
-      "s_bitset1_b32 %[hi], %[g]\n\t"
+      "v_alignbit_b32 %[u0], %[f0], %[L], 31\n\t"
+      "v_alignbit_b32 %[u1], %[f1], %[f0], 31\n\t"
+      "v_alignbit_b32 %[u2], %[f2], %[f1], 31\n\t"
+      "v_alignbit_b32 %[u3], %[f3], %[f2], 31\n\t"
+      "v_alignbit_b32 %[t0], %[f1], %[f0], 1\n\t"
+      "v_alignbit_b32 %[t1], %[f2], %[f1], 1\n\t"
+      "v_alignbit_b32 %[t2], %[f3], %[f2], 1\n\t"
+      "v_alignbit_b32 %[t3], %[R], %[f3], 1\n\t"
+      "v_or_b32_dpp %[u0], %[f0], %[u0] wave_shr:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[u1], %[f1], %[u1] wave_shr:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[u2], %[f2], %[u2] wave_shr:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[u3], %[f3], %[u3] wave_shr:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[t0], %[f0], %[t0] wave_shl:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[t1], %[f1], %[t1] wave_shl:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[t2], %[f2], %[t2] wave_shl:1" NAVGPU_ROWS_DPP
+      "v_or_b32_dpp %[t3], %[f3], %[t3] wave_shl:1" NAVGPU_ROWS_DPP
+      "v_bitop3_b32 %[f0], %[u0], %[b0], %[t0] bitop3:0x32\n\t"
+      "v_bitop3_b32 %[f1], %[u1], %[b1], %[t1] bitop3:0x32\n\t"
+      "v_bitop3_b32 %[f2], %[u2], %[b2], %[t2] bitop3:0x32\n\t"
+      "v_bitop3_b32 %[f3], %[u3], %[b3], %[t3] bitop3:0x32\n\t"
+      "v_or3_b32 %[b0], %[b0], %[u0], %[t0]\n\t"
+      "v_or3_b32 %[b1], %[b1], %[u1], %[t1]\n\t"
+      "v_or3_b32 %[b2], %[b2], %[u2], %[t2]\n\t"
+      "v_or3_b32 %[b3], %[b3], %[u3], %[t3]\n\t"
+      "v_or3_b32 %[u0], %[f0], %[f1], %[f2]\n\t"
+      "v_cmp_ne_u32_e64 %[c1], 0, %[f0]\n\t"
+      "v_or_b32_e32 %[u0], %[u0], %[f3]\n\t"
+      "v_cmp_ne_u32_e64 %[c2], 0, %[f3]\n\t"
+      "v_cmp_ne_u32_e64 %[c0], 0, %[u0]\n\t"
+      "s_cmp_lg_u64 %[c1], 0\n\t"
+      "s_cselect_b32 %[st], %[bit], 0\n\t"
+      "s_or_b32 %[lo], %[lo], %[st]\n\t"
+      "s_cmp_lg_u64 %[c2], 0\n\t"
+      "s_cselect_b32 %[st], %[bit], 0\n\t"
+      "s_or_b32 %[hi], %[hi], %[st]\n\t"
+      "s_cmp_lg_u64 %[c0], 0\n\t"
+      "s_cselect_b32 %[st], %[bit], 0\n\t"
+      "s_or_b32 %[nz], %[nz], %[st]\n\t"
       "1:\n\t"
-      : [bA] "+v"(bA), [bB] "+v"(bB), [bC] "+v"(bC), [bD] "+v"(bD), [hA] "=&v"(hA), [hB] "=&v"(hB), [hC] "=&v"(hC), [hD] "=&v"(hD), [nz] "+s"(nz),
-        [lo] "+s"(lo), [hi] "+s"(hi), [tA] "=&v"(tA), [tB] "=&v"(tB), [tC] "=&v"(tC), [tD] "=&v"(tD),
-        [uA] "=&v"(uA), [uB] "=&v"(uB), [uC] "=&v"(uC), [uD] "=&v"(uD), [st] "=&s"(st)
-      : [aw] "s"(aw), [g] "n"(g), [fL] "v"(fL), [fA] "v"(fA), [fB] "v"(fB), [fC] "v"(fC), [fD] "v"(fD), [fR] "v"(fR)
-      : "vcc", "scc");
-}
-__device__ __forceinline__ void rowsCommit4(const int g, const uint32_t aw, uint32_t& fA, uint32_t& fB, uint32_t& fC, uint32_t& fD, const uint32_t hA,
-                                            const uint32_t hB, const uint32_t hC, const uint32_t hD) {
-  asm volatile(
-      "s_bitcmp1_b32 %[aw], %[g]\n\t"
-      "s_cbranch_scc0 2f\n\t"
-      "v_mov_b32 %[fA], %[hA]\n\t"
-      "v_mov_b32 %[fB], %[hB]\n\t"
-      "v_mov_b32 %[fC], %[hC]\n\t"
-      "v_mov_b32 %[fD], %[hD]\n\t"
-      "2:\n\t"
-      : [fA] "+v"(fA), [fB] "+v"(fB), [fC] "+v"(fC), [fD] "+v"(fD)
-      : [aw] "s"(aw), [g] "n"(g), [hA] "v"(hA), [hB] "v"(hB), [hC] "v"(hC), [hD] "v"(hD)
+      : [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [b3] "+v"(b[3]), [f0] "+v"(f[0]), [f1] "+v"(f[1]), [f2] "+v"(f[2]), [f3] "+v"(f[3]),
+        [p] "=&v"(p), [u0] "=&v"(u0), [u1] "=&v"(u1), [u2] "=&v"(u2), [u3] "=&v"(u3), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
+        [t3] "=&v"(t3), [nz] "+s"(nz), [lo] "+s"(lo), [hi] "+s"(hi), [c0] "=&s"(c0), [c1] "=&s"(c1), [c2] "=&s"(c2), [st] "=&s"(st)
+      : [aw] "s"(aw), [g] "n"(g), [bit] "n"(1 << g), [L] "v"(L), [R] "v"(R)
       : "scc");
+#undef NAVGPU_ROWS_DPP
 }
 // The seed cells of wavefront `which` of robot `inst`, from its plan (as bfsWaveGrid; map_grid.cpp:160-187, 190-233): every
 // lane of the workgroup takes a slice of the plan, `set(mx, my)` is called once per seed cell.
@@ -300,21 +293,13 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
         // One group = one asm statement that carries its own wave-uniform skip, so the compiler sees straight-line code
         // with in-place (tied) updates of `blocked` and `fr`.  (Written as C++ branches the same loop made it rename both
         // arrays per word: register copies in the path of every SKIPPED word and a dozen more at the loop's back edge.)
-        // A group's new frontier waits in h[] until the NEXT group has read the old words (its left neighbour), then goes back.
-        uint32_t h[2][4];
+        // p[q & 1] carries group q's old last word to group q + 1.
+        uint32_t p[2];
         const uint32_t zero = 0;
 #pragma unroll
-        for (int q = 0; q < NG; ++q) {
-          rowsGroup4(q, aw, nz, lo, hi, blocked[4 * q], blocked[4 * q + 1], blocked[4 * q + 2], blocked[4 * q + 3],
-                     q > 0 ? fr[q > 0 ? 4 * q - 1 : 0] : zero, fr[4 * q], fr[4 * q + 1], fr[4 * q + 2], fr[4 * q + 3],
-                     q + 1 < NG ? fr[q + 1 < NG ? 4 * q + 4 : 0] : zero, h[q & 1][0], h[q & 1][1], h[q & 1][2], h[q & 1][3]);
-          if (q > 0) {
-            const int p = q > 0 ? q - 1 : 0;
-            rowsCommit4(p, aw, fr[4 * p], fr[4 * p + 1], fr[4 * p + 2], fr[4 * p + 3], h[p & 1][0], h[p & 1][1], h[p & 1][2], h[p & 1][3]);
-          }
-        }
-        rowsCommit4(NG - 1, aw, fr[4 * (NG - 1)], fr[4 * (NG - 1) + 1], fr[4 * (NG - 1) + 2], fr[4 * (NG - 1) + 3], h[(NG - 1) & 1][0], h[(NG - 1) & 1][1],
-                    h[(NG - 1) & 1][2], h[(NG - 1) & 1][3]);
+        for (int q = 0; q < NG; ++q)
+          rowsGroup4(q, aw, nz, lo, hi, &blocked[4 * q], &fr[4 * q], q > 0 ? p[(q + 1) & 1] : zero, q + 1 < NG ? fr[q + 1 < NG ? 4 * q + 4 : 0] : zero,
+                     p[q & 1]);
         BFS_STAMP(ts2);
         BFS_ACC(1, ts2 - ts1);
         // the new cells of the robot's region get their distance now, from the lane that owns the row
