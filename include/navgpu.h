@@ -15,7 +15,7 @@
  * reference's bool / negative-cost error channel); the caller owns every buffer it passes.
  * There is NO CPU fallback: without a usable HIP device `navgpu_fleet_create` fails.
  *
- * Threading: every entry point that takes a fleet (or a navgpu_navfn handle) holds that handle's
+ * Threading: every entry point that takes a fleet (or a navgpu_navfn / navgpu_amcl handle) holds that handle's
  * own recursive mutex for its whole body and makes the handle's GPU current on the calling thread,
  * so calls on ONE handle from several host threads are serialised inside the library: a
  * reconfigure (navgpu_planner_configure, navgpu_inflation_configure, navgpu_obstacle_configure,
@@ -29,7 +29,7 @@
  * adapters do (navgpu::DWAPlannerROS::configuration_mutex_, the layers' gpu_access_ /
  * inflation_access_), next to the master-costmap mutex the reference already holds around both
  * virtual calls (costmap_2d/src/layered_costmap.cpp:83, move_base/src/move_base.cpp:947).
- * navgpu_fleet_destroy / navgpu_navfn_destroy must not race any other call on the same handle.
+ * navgpu_fleet_destroy / navgpu_navfn_destroy / navgpu_amcl_destroy must not race any other call on the same handle.
  * Distinct handles are independent.  navgpu_last_error is per thread.
  */
 #ifndef NAVGPU_H_
@@ -662,6 +662,111 @@ int navgpu_global_planner_plan(navgpu_navfn* nav, uint32_t first, uint32_t count
  * the same code as in navgpu_global_planner_plan.  use_dijkstra must be 1.  results[k].cycles = rounds run. */
 int navgpu_global_planner_plan_wavefront(navgpu_navfn* nav, uint32_t first, uint32_t count, const navgpu_global_planner_params* params,
                                          const double* starts_xy, const double* goals_xy, const int32_t* goal_cells_xy, navgpu_navfn_result* results);
+
+/* ------------------------------------------------------------------------------------------ */
+/* amcl::AMCLLaser - the laser sensor update of a batch of particle filters (one per robot)   */
+/* ------------------------------------------------------------------------------------------ */
+/* A handle holds n_filters independent particle filters ("filters") on one device: per filter a map (map_t), a sample set
+ * (pf_sample_set_t: up to max_samples poses and weights and the converged flag), the pf_t running averages w_slow / w_fast
+ * and the laser pose.  Filter k's samples live at k * max_samples in every sample array.  One laser model configuration
+ * (navgpu_amcl_laser_configure) serves every filter of the handle.  All arithmetic is fp64 with the reference's operation
+ * order; the device's libm (sin / cos / atan2 / exp / log) may differ from the host's by an ulp.  Coordinates are metres,
+ * cells are map_t's (origin at the map centre, map.h:139-147).  Motion model, resampling and the kd-tree stay with the
+ * reference (they draw from drand48 / pf_ran_gaussian). */
+typedef struct navgpu_amcl navgpu_amcl;
+#define NAVGPU_AMCL_MODEL_BEAM 0                     /* laser_model_t, amcl_laser.h:42-48 */
+#define NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD 1
+#define NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB 2
+#define NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_GOMPERTZ 3
+typedef struct {
+  int32_t model_type;  /* NAVGPU_AMCL_MODEL_*                                                                              */
+  int32_t max_beams;   /* AMCLLaser(max_beams, map); < 2: update_sensor returns updated = 0 and touches nothing             */
+  /* SetModelBeam (amcl_laser.cpp:65-81) */
+  double z_hit, z_short, z_max, z_rand, sigma_hit, lambda_short, chi_outlier;
+  /* SetModelLikelihoodFieldProb (:100-120): the beam-skip parameters (z_hit, z_rand, sigma_hit as above; the max_occ_dist
+   * argument of every SetModelLikelihoodField* is a property of the map: navgpu_amcl_set_map) */
+  int32_t do_beamskip;
+  int32_t reserved;
+  double beam_skip_distance, beam_skip_threshold, beam_skip_error_threshold;
+  /* SetModelLikelihoodFieldGompertz (:122-147) */
+  double gompertz_a, gompertz_b, gompertz_c, input_shift, input_scale, output_shift;
+  /* SetMapFactors (:149-156); the constructor's defaults are 1.0 / 1.0 / 0.0 (:51-53) */
+  double off_map_factor, non_free_space_factor, non_free_space_radius;
+  /* pf_alloc(..., alpha_slow, alpha_fast, ...) (pf.c:48-90) */
+  double alpha_slow, alpha_fast;
+} navgpu_amcl_laser_params;
+/* replaces: pf_alloc / AMCLLaser::AMCLLaser (pf.c:48-90, amcl_laser.cpp:42-56) for n_filters filters.  max_beams is the
+ * largest laser_params.max_beams the handle accepts (<= 1024); n_filters <= 65535 (NAVGPU_ERR_CAPACITY above). */
+int navgpu_amcl_create(uint32_t n_filters, uint32_t max_samples, uint32_t max_beams, int32_t device, navgpu_amcl** out);
+int navgpu_amcl_destroy(navgpu_amcl* amcl);
+/* replaces: AmclNode::convertMap (amcl_node.cpp:1062-1093) + the map_update_cspace(map, max_occ_dist) call of
+ * SetModelLikelihoodField* (amcl_laser.cpp:98,119,146).  occupancy = OccupancyGrid data, height x width (count of them, or
+ * ONE map stored once for the whole slice when shared != 0); 0 -> free (-1), 100 -> occupied (+1), anything else -> unknown
+ * (0); scale_up_factor in 1..16 (amcl_node.cpp:369-374) gives size = width * f x height * f, scale = resolution / f, and
+ * origin_xy = {origin.position.x, .y} of the message (the same for every map of the call) is shifted to the map centre as
+ * there.  size_x, size_y <= 16384.  The distance map is computed on the device as the EXACT capped Euclidean distance
+ * transform: with D = the smallest squared cell distance (dx^2 + dy^2) to an occupied cell and R = (int)(max_occ_dist /
+ * scale), a cell holds (float)max_occ_dist when sqrt((double)D) > R (or there is no occupied cell) and
+ * (float)(sqrt((double)D) * scale) otherwise.  The reference's brushfire carries the source of whichever neighbour left its
+ * priority queue first, which is order-dependent; it is never below the exact transform and above it on a few per cent of
+ * cells (DESIGN "amcl").  navgpu_amcl_set_distance_map uploads the reference's own bytes. */
+int navgpu_amcl_set_map(navgpu_amcl* amcl, uint32_t first, uint32_t count, const int8_t* occupancy, uint32_t width, uint32_t height,
+                        double resolution, const double* origin_xy, int32_t scale_up_factor, int32_t shared, double max_occ_dist);
+/* The same from a map_t as it stands (what an amcl::AMCLLaser holds): occ_state = size_y x size_x occ_state values (-1 free,
+ * 0 unknown, +1 occupied) stored as given, scale and origin_x / origin_y (the map centre, map.h:63-67) taken as they are.
+ * The distance map is computed as by navgpu_amcl_set_map. */
+int navgpu_amcl_set_map_cells(navgpu_amcl* amcl, uint32_t first, uint32_t count, const int8_t* occ_state, uint32_t size_x, uint32_t size_y,
+                              double scale, double origin_x, double origin_y, int32_t shared, double max_occ_dist);
+/* map_t::distances as the caller computed them (e.g. the reference's map_update_cspace): size_y x size_x floats per filter
+ * of the slice, or one array for all when shared != 0.  A map stored once for several filters of the slice takes the data
+ * given for the last of them.  NAVGPU_ERR_STATE when a filter of the slice has no map. */
+int navgpu_amcl_set_distance_map(navgpu_amcl* amcl, uint32_t first, uint32_t count, const float* distances, int32_t shared);
+/* map_t::distances of one filter's map (size_y x size_x floats); NAVGPU_ERR_STATE when it has none */
+int navgpu_amcl_distance_map(navgpu_amcl* amcl, uint32_t filter, float* out);
+/* replaces: AMCLLaser::SetModelBeam / SetModelLikelihoodField / SetModelLikelihoodFieldProb / SetModelLikelihoodFieldGompertz /
+ * SetMapFactors (amcl_laser.cpp:65-156) and pf_alloc's alpha_slow / alpha_fast.  All or nothing: an invalid struct
+ * (model_type outside 0..3, max_beams outside 0..capacity - NAVGPU_ERR_CAPACITY above it -, do_beamskip not 0 / 1, a NaN
+ * parameter) leaves the previous configuration in force. */
+int navgpu_amcl_laser_configure(navgpu_amcl* amcl, const navgpu_amcl_laser_params* params);
+/* replaces: AMCLLaser::SetLaserPose (amcl_laser.h:118): xyth = count x {x, y, theta} of the laser in the robot frame */
+int navgpu_amcl_set_laser_pose(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* xyth);
+/* pf_t::sets[current_set] of the slice: sample_counts[count] (<= max_samples, NAVGPU_ERR_CAPACITY above), poses = count x
+ * max_samples x {x, y, theta} (pf_vector_t), weights = count x max_samples, converged[count].  Entries past a filter's
+ * sample_count are stored and returned as given but take no part in an update.  get: any output pointer may be NULL. */
+int navgpu_amcl_set_samples(navgpu_amcl* amcl, uint32_t first, uint32_t count, const int32_t* sample_counts, const double* poses,
+                            const double* weights, const int32_t* converged);
+int navgpu_amcl_get_samples(navgpu_amcl* amcl, uint32_t first, uint32_t count, int32_t* sample_counts, double* poses, double* weights,
+                            int32_t* converged);
+/* pf_t::w_slow, w_fast (pf.h:133): w = count x {w_slow, w_fast} */
+int navgpu_amcl_set_filter_state(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* w);
+int navgpu_amcl_get_filter_state(navgpu_amcl* amcl, uint32_t first, uint32_t count, double* w);
+/* replaces: AMCLLaser::UpdateSensor -> pf_update_sensor(pf, ApplyModelToSampleSet, data) (amcl_laser.cpp:160-236, pf.c:270-316)
+ * for every filter of the slice: the configured model, then (when its total is > 0) the map-factor pass, then normalisation
+ * and the w_slow / w_fast running averages; weights become uniform when the total is 0.  The boundary is AMCLLaserData:
+ * ranges_xy holds, filter after filter, range_counts[k] pairs {range, bearing} (laserReceived's ranges[i][0..1]),
+ * range_max[k] per filter.  updated[k] = 1 where the update ran, 0 where the reference returns false (max_beams < 2; the
+ * filter is untouched).  Sample totals are summed in a fixed order (not the reference's serial one: weights agree to a
+ * relative 1e-12) that does not depend on the other filters.  Defined where the reference is not:
+ * - the beam model's step (range_count - 1) / (max_beams - 1) is 0 for 1 <= range_count < max_beams and the reference's loop
+ *   never ends (amcl_laser.cpp:265): such a filter gets updated[k] = NAVGPU_ERR_INVALID and is untouched, the others run and
+ *   the call returns NAVGPU_ERR_INVALID;
+ * - in the likelihood-field-prob model's beam skipping, the error branch (skipped beams >= max_beams * error threshold)
+ *   integrates temp_obs[j][beam] for every beam < max_beams, including entries this update did not write (max-range / NaN
+ *   beams and indices past the last subsampled beam: stale or uninitialised memory there).  Here only the entries written in
+ *   this update are integrated, in both branches;
+ * - the map factors read map_occ_dist even for the beam model, which needs no distances (the reference reads a NULL
+ *   map_t::distances there unless something called map_update_cspace): here every map set by navgpu_amcl_set_map /
+ *   _set_map_cells carries its exact distance map, whatever the model, so the factors are always defined.
+ * NAVGPU_ERR_STATE for a filter without a map or before navgpu_amcl_laser_configure; nothing runs then.  A range_count above
+ * INT32_MAX (AMCLLaserData::range_count is an int) is NAVGPU_ERR_INVALID. */
+int navgpu_amcl_update_sensor(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* ranges_xy, const uint32_t* range_counts,
+                              const double* range_max, int32_t* updated);
+/* The likelihood-field-prob beam skipping of the last update of one filter (amcl_laser.cpp:543-566), arrays of the handle's
+ * max_beams (navgpu_amcl_create) entries indexed by beam_ind: obs_count (particles whose beam end lies on the map closer than
+ * beam_skip_distance to an obstacle), obs_mask (1: beam integrated) and *error (1: too many beams skipped, every written beam
+ * integrated).  *active = 0 where the last update did not skip beams (do_beamskip off, set not converged, another model); the
+ * rest is then zero.  Any output pointer may be NULL. */
+int navgpu_amcl_beam_skip_state(navgpu_amcl* amcl, uint32_t filter, int32_t* obs_count, uint8_t* obs_mask, int32_t* error, int32_t* active);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,37 @@ class GlobalPlannerParams(C.Structure):
             setattr(self, k, v)
 
 
+AMCL_MODEL_BEAM, AMCL_MODEL_LIKELIHOOD_FIELD, AMCL_MODEL_LIKELIHOOD_FIELD_PROB, AMCL_MODEL_LIKELIHOOD_FIELD_GOMPERTZ = range(4)
+
+
+class AmclLaserParams(C.Structure):
+    """Mirror of navgpu_amcl_laser_params (include/navgpu.h).  Defaults: amcl_node.cpp's parameter defaults (likelihood field,
+    max_beams 30, laser_z_* 0.95 / 0.1 / 0.05 / 0.05, laser_sigma_hit 0.2, laser_lambda_short 0.1, beam skip 0.5 / 0.3 / 0.9,
+    alpha_slow / alpha_fast 0.001 / 0.1) and SetMapFactors' constructor values 1.0 / 1.0 / 0.0."""
+    _fields_ = [("model_type", C.c_int32), ("max_beams", C.c_int32)] + [(n, C.c_double) for n in (
+        "z_hit", "z_short", "z_max", "z_rand", "sigma_hit", "lambda_short", "chi_outlier")] + [
+        ("do_beamskip", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_double) for n in (
+            "beam_skip_distance", "beam_skip_threshold", "beam_skip_error_threshold", "gompertz_a", "gompertz_b", "gompertz_c",
+            "input_shift", "input_scale", "output_shift", "off_map_factor", "non_free_space_factor", "non_free_space_radius",
+            "alpha_slow", "alpha_fast")]
+
+    DEFAULTS = dict(model_type=AMCL_MODEL_LIKELIHOOD_FIELD, max_beams=30, z_hit=0.95, z_short=0.1, z_max=0.05, z_rand=0.05, sigma_hit=0.2,
+                    lambda_short=0.1, chi_outlier=0.0, do_beamskip=0, reserved=0, beam_skip_distance=0.5, beam_skip_threshold=0.3,
+                    beam_skip_error_threshold=0.9, gompertz_a=1.0, gompertz_b=1.0, gompertz_c=1.0, input_shift=0.0, input_scale=1.0,
+                    output_shift=0.0, off_map_factor=1.0, non_free_space_factor=1.0, non_free_space_radius=0.0, alpha_slow=0.001,
+                    alpha_fast=0.1)
+
+    def __init__(self, **kw):
+        super().__init__()
+        d = dict(self.DEFAULTS)
+        d.update(kw)
+        for k, v in d.items():
+            setattr(self, k, v)
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -273,6 +304,20 @@ SYMBOLS = [
     ("navgpu_profile_read", C.c_int, [vp, i32, C.POINTER(dbl), C.POINTER(C.c_uint64)]),
     ("navgpu_kernel_name", C.c_char_p, [i32]),
     ("navgpu_device_sincos", C.c_int, [i32, vp, u32, vp, vp]),
+    ("navgpu_amcl_create", C.c_int, [u32, u32, u32, i32, C.POINTER(vp)]),
+    ("navgpu_amcl_destroy", C.c_int, [vp]),
+    ("navgpu_amcl_set_map", C.c_int, [vp, u32, u32, vp, u32, u32, dbl, vp, i32, i32, dbl]),
+    ("navgpu_amcl_set_map_cells", C.c_int, [vp, u32, u32, vp, u32, u32, dbl, dbl, dbl, i32, dbl]),
+    ("navgpu_amcl_set_distance_map", C.c_int, [vp, u32, u32, vp, i32]),
+    ("navgpu_amcl_distance_map", C.c_int, [vp, u32, vp]),
+    ("navgpu_amcl_laser_configure", C.c_int, [vp, C.POINTER(AmclLaserParams)]),
+    ("navgpu_amcl_set_laser_pose", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_set_samples", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+    ("navgpu_amcl_get_samples", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+    ("navgpu_amcl_set_filter_state", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_get_filter_state", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_update_sensor", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+    ("navgpu_amcl_beam_skip_state", C.c_int, [vp, u32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
 ]
 
 

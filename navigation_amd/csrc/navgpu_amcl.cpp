@@ -1,0 +1,422 @@
+// navgpu_amcl_*: host side of the amcl laser update for a batch of particle filters (see amcl_kernels.hip and include/navgpu.h).
+#include <memory>
+
+#include "navgpu_amcl.h"
+#include "navgpu_fleet.h"
+
+namespace {
+// One map_t on the device; several filters may hold the same one (set_map with shared != 0)
+struct AmclMap {
+  int8_t* occ = nullptr;
+  float* dist = nullptr;
+  int sx = 0, sy = 0;
+  double scale = 0, ox = 0, oy = 0, max_occ_dist = 0;
+  ~AmclMap() {
+    if (occ) hipFree(occ);
+    if (dist) hipFree(dist);
+  }
+};
+}  // namespace
+
+struct navgpu_amcl {
+  AmclDev d{};
+  uint32_t n = 0;
+  int device = 0;
+  std::recursive_mutex mu;
+  hipStream_t stream = nullptr;
+  std::vector<void*> allocs;
+  std::vector<std::shared_ptr<AmclMap>> maps;  // [n]
+  std::vector<AmclMapDev> map_desc;            // [n] mirror of d.maps
+  std::vector<int32_t> sample_count, converged;
+  std::vector<double> laser;                   // [n][3]
+  navgpu_amcl_laser_params params{};
+  bool configured = false;
+  AmclFilterDev* d_filters = nullptr;          // [n]
+  double* d_beams = nullptr;                   // [n][2 * max_beams][2] subsampled {range, bearing}
+  template <class T>
+  int alloc(T** p, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    if (hipMalloc(&q, bytes) != hipSuccess) {
+      g_last_error = "hipMalloc failed (amcl)";
+      return NAVGPU_ERR_HIP;
+    }
+    hipMemsetAsync(q, 0, bytes, stream);
+    allocs.push_back(q);
+    *p = static_cast<T*>(q);
+    return NAVGPU_OK;
+  }
+  bool rangeOk(uint32_t first, uint32_t count) const { return count > 0 && first < n && count <= n - first; }
+  int uploadMaps() {
+    HIP_TRY(hipMemcpyAsync(d.maps, map_desc.data(), sizeof(AmclMapDev) * n, hipMemcpyHostToDevice, stream));
+    HIP_TRY(waitStream(stream));
+    return NAVGPU_OK;
+  }
+};
+
+namespace {
+struct AmclGuard {
+  std::lock_guard<std::recursive_mutex> lk;
+  explicit AmclGuard(navgpu_amcl* h) : lk(h->mu) { (void)hipSetDevice(h->device); }
+};
+
+bool isFinite(double v) { return std::isfinite(v); }
+
+bool paramsValid(const navgpu_amcl_laser_params& p) {
+  if (p.model_type < NAVGPU_AMCL_MODEL_BEAM || p.model_type > NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_GOMPERTZ) return false;
+  if (p.max_beams < 0 || (p.do_beamskip != 0 && p.do_beamskip != 1)) return false;
+  const double v[] = {p.z_hit, p.z_short, p.z_max, p.z_rand, p.sigma_hit, p.lambda_short, p.chi_outlier, p.beam_skip_distance,
+                      p.beam_skip_threshold, p.beam_skip_error_threshold, p.gompertz_a, p.gompertz_b, p.gompertz_c, p.input_shift,
+                      p.input_scale, p.output_shift, p.off_map_factor, p.non_free_space_factor, p.non_free_space_radius, p.alpha_slow,
+                      p.alpha_fast};
+  for (double x : v)
+    if (x != x) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int navgpu_amcl_create(uint32_t n_filters, uint32_t max_samples, uint32_t max_beams, int32_t device, navgpu_amcl** out) {
+  if (!out || !n_filters || !max_samples || !max_beams) return NAVGPU_ERR_INVALID;
+  // filters sit on a grid dimension of the launches (<= 65535); sample indices and counts are int32
+  if (max_beams > (uint32_t)kAmclMaxBeams || n_filters > (uint32_t)kAmclMaxFilters || max_samples > (uint32_t)INT32_MAX ||
+      (uint64_t)n_filters * max_samples > (1ull << 28))
+    return NAVGPU_ERR_CAPACITY;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+    g_last_error = "no usable HIP device (navgpu has no CPU fallback)";
+    return NAVGPU_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+  navgpu_amcl* h = new navgpu_amcl();
+  h->n = n_filters;
+  h->device = device;
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete h;
+    g_last_error = "hipStreamCreate failed";
+    return NAVGPU_ERR_HIP;
+  }
+  h->maps.resize(n_filters);
+  h->map_desc.assign(n_filters, AmclMapDev{});
+  h->sample_count.assign(n_filters, 0);
+  h->converged.assign(n_filters, 0);
+  h->laser.assign((size_t)n_filters * 3, 0.0);
+  AmclDev& d = h->d;
+  d.max_samples = max_samples;
+  d.max_beams = max_beams;
+  int rc = 0;
+#define A(ptr, cnt) \
+  if (!rc) rc = h->alloc(&(ptr), (size_t)(cnt));
+  A(d.poses, (size_t)n_filters * max_samples * 3);
+  A(d.weights, (size_t)n_filters * max_samples);
+  A(d.w, (size_t)n_filters * 2);
+  A(d.maps, n_filters);
+  A(d.obs_count, (size_t)n_filters * max_beams);
+  A(d.obs_mask, (size_t)n_filters * max_beams);
+  A(d.skip_info, (size_t)n_filters * 2);
+  A(h->d_filters, n_filters);
+  A(h->d_beams, (size_t)n_filters * 2 * max_beams * 2);
+#undef A
+  if (!rc && waitStream(h->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;
+  if (rc) {
+    navgpu_amcl_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_destroy(navgpu_amcl* h) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  (void)hipSetDevice(h->device);
+  if (h->stream) waitStream(h->stream);
+  h->maps.clear();
+  for (void* p : h->allocs) hipFree(p);
+  if (h->stream) hipStreamDestroy(h->stream);
+  delete h;
+  return NAVGPU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// Maps of a slice: `src` is OccupancyGrid data (height x width, scaled up by `factor` on the device) or, with `cells`, map_t
+// occ_state values copied as they are (factor 1); scale and the centre origin (ox, oy) are map_t's own.
+int setMaps(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* src, uint32_t width, uint32_t height, int factor, bool cells,
+            double scale, double ox, double oy, int32_t shared, double max_occ_dist) {
+  const uint64_t sx = (uint64_t)width * factor, sy = (uint64_t)height * factor;
+  AmclGuard guard_(h);
+  // map_update_cspace: CachedDistanceMap::cell_radius_ = max_dist / scale, an int
+  const double rd = max_occ_dist / scale;
+  const int radius = rd >= 2147483647.0 ? 2147483647 : (int)rd;
+  const size_t msg_cells = (size_t)width * height, cells_n = (size_t)(sx * sy);
+  int8_t* d_msg = nullptr;
+  int32_t* d_g = nullptr;
+  HIP_TRY(hipMalloc(&d_msg, msg_cells));
+  if (hipMalloc(&d_g, cells_n * sizeof(int32_t)) != hipSuccess) {
+    hipFree(d_msg);
+    g_last_error = "hipMalloc failed (amcl map)";
+    return NAVGPU_ERR_HIP;
+  }
+  int rc = NAVGPU_OK;
+  std::vector<std::shared_ptr<AmclMap>> made;
+  const uint32_t n_maps = shared ? 1u : count;
+  for (uint32_t k = 0; k < n_maps && !rc; ++k) {
+    auto m = std::make_shared<AmclMap>();
+    m->sx = (int)sx;
+    m->sy = (int)sy;
+    m->scale = scale;
+    m->ox = ox;
+    m->oy = oy;
+    m->max_occ_dist = max_occ_dist;
+    if (hipMalloc(&m->occ, cells_n) != hipSuccess || hipMalloc(&m->dist, cells_n * sizeof(float)) != hipSuccess) {
+      g_last_error = "hipMalloc failed (amcl map)";
+      rc = NAVGPU_ERR_HIP;
+      break;
+    }
+    if (hipMemcpyAsync(cells ? m->occ : d_msg, src + k * msg_cells, msg_cells, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+      rc = NAVGPU_ERR_HIP;
+      break;
+    }
+    if (!cells) launch_amcl_convert(d_msg, width, height, factor, m->occ, m->sx, m->sy, h->stream);
+    launch_amcl_cspace(m->occ, m->sx, m->sy, radius, scale, max_occ_dist, d_g, m->dist, h->stream);
+    if (!rc) rc = checkLaunch();
+    if (waitStream(h->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;  // the staging buffers are reused by the next map
+    made.push_back(m);
+  }
+  hipFree(d_msg);
+  hipFree(d_g);
+  if (rc) return rc;
+  for (uint32_t k = 0; k < count; ++k) {
+    const auto& m = made[shared ? 0 : k];
+    h->maps[first + k] = m;
+    h->map_desc[first + k] = AmclMapDev{m->occ, m->dist, m->sx, m->sy, m->scale, m->ox, m->oy, m->max_occ_dist};
+  }
+  return h->uploadMaps();
+}
+}  // namespace
+
+extern "C" {
+
+int navgpu_amcl_set_map(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* occupancy, uint32_t width, uint32_t height,
+                        double resolution, const double* origin_xy, int32_t scale_up_factor, int32_t shared, double max_occ_dist) {
+  if (!h || !occupancy || !origin_xy || !h->rangeOk(first, count) || !width || !height || !(resolution > 0) || !isFinite(resolution) ||
+      scale_up_factor < 1 || scale_up_factor > 16 || !(max_occ_dist >= 0) || !isFinite(max_occ_dist) || !isFinite(origin_xy[0]) ||
+      !isFinite(origin_xy[1]))
+    return NAVGPU_ERR_INVALID;
+  const uint64_t sx = (uint64_t)width * scale_up_factor, sy = (uint64_t)height * scale_up_factor;
+  if (sx > (uint64_t)kAmclMaxMapSide || sy > (uint64_t)kAmclMaxMapSide) return NAVGPU_ERR_CAPACITY;
+  // AmclNode::convertMap: size = msg size * f, scale = resolution / f, origin moved to the map centre
+  const double scale = resolution / scale_up_factor;
+  const double ox = origin_xy[0] + (int)(sx / 2) * scale, oy = origin_xy[1] + (int)(sy / 2) * scale;
+  return setMaps(h, first, count, occupancy, width, height, scale_up_factor, false, scale, ox, oy, shared, max_occ_dist);
+}
+
+int navgpu_amcl_set_map_cells(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* occ_state, uint32_t size_x, uint32_t size_y,
+                              double scale, double origin_x, double origin_y, int32_t shared, double max_occ_dist) {
+  if (!h || !occ_state || !h->rangeOk(first, count) || !size_x || !size_y || !(scale > 0) || !isFinite(scale) || !(max_occ_dist >= 0) ||
+      !isFinite(max_occ_dist) || !isFinite(origin_x) || !isFinite(origin_y))
+    return NAVGPU_ERR_INVALID;
+  if (size_x > (uint32_t)kAmclMaxMapSide || size_y > (uint32_t)kAmclMaxMapSide) return NAVGPU_ERR_CAPACITY;
+  return setMaps(h, first, count, occ_state, size_x, size_y, 1, true, scale, origin_x, origin_y, shared, max_occ_dist);
+}
+
+int navgpu_amcl_set_distance_map(navgpu_amcl* h, uint32_t first, uint32_t count, const float* distances, int32_t shared) {
+  if (!h || !distances || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  for (uint32_t k = 0; k < count; ++k)
+    if (!h->maps[first + k]) {
+      g_last_error = "navgpu_amcl_set_distance_map: filter without a map";
+      return NAVGPU_ERR_STATE;
+    }
+  if (shared)
+    for (uint32_t k = 1; k < count; ++k)
+      if (h->maps[first + k]->sx != h->maps[first]->sx || h->maps[first + k]->sy != h->maps[first]->sy) return NAVGPU_ERR_INVALID;
+  size_t off = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    const AmclMap& m = *h->maps[first + k];
+    const size_t cells = (size_t)m.sx * m.sy;
+    HIP_TRY(hipMemcpyAsync(m.dist, distances + off, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (!shared) off += cells;
+  }
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_distance_map(navgpu_amcl* h, uint32_t filter, float* out) {
+  if (!h || !out || filter >= h->n) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  const auto& m = h->maps[filter];
+  if (!m) return NAVGPU_ERR_STATE;
+  HIP_TRY(hipMemcpyAsync(out, m->dist, (size_t)m->sx * m->sy * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_laser_configure(navgpu_amcl* h, const navgpu_amcl_laser_params* p) {
+  if (!h || !p || !paramsValid(*p)) return NAVGPU_ERR_INVALID;
+  if ((uint32_t)p->max_beams > h->d.max_beams) return NAVGPU_ERR_CAPACITY;
+  AmclGuard guard_(h);
+  h->params = *p;
+  h->configured = true;
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_set_laser_pose(navgpu_amcl* h, uint32_t first, uint32_t count, const double* xyth) {
+  if (!h || !xyth || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  std::copy(xyth, xyth + 3 * (size_t)count, h->laser.begin() + 3 * (size_t)first);
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_set_samples(navgpu_amcl* h, uint32_t first, uint32_t count, const int32_t* sample_counts, const double* poses,
+                            const double* weights, const int32_t* converged) {
+  if (!h || !sample_counts || !poses || !weights || !converged || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  for (uint32_t k = 0; k < count; ++k) {
+    if (sample_counts[k] < 0) return NAVGPU_ERR_INVALID;
+    if ((uint32_t)sample_counts[k] > h->d.max_samples) return NAVGPU_ERR_CAPACITY;
+  }
+  AmclGuard guard_(h);
+  const size_t ms = h->d.max_samples;
+  HIP_TRY(hipMemcpyAsync(h->d.poses + first * ms * 3, poses, sizeof(double) * count * ms * 3, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d.weights + first * ms, weights, sizeof(double) * count * ms, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  for (uint32_t k = 0; k < count; ++k) {
+    h->sample_count[first + k] = sample_counts[k];
+    h->converged[first + k] = converged[k] ? 1 : 0;
+  }
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_get_samples(navgpu_amcl* h, uint32_t first, uint32_t count, int32_t* sample_counts, double* poses, double* weights,
+                            int32_t* converged) {
+  if (!h || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  const size_t ms = h->d.max_samples;
+  if (poses) HIP_TRY(hipMemcpyAsync(poses, h->d.poses + first * ms * 3, sizeof(double) * count * ms * 3, hipMemcpyDeviceToHost, h->stream));
+  if (weights) HIP_TRY(hipMemcpyAsync(weights, h->d.weights + first * ms, sizeof(double) * count * ms, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  for (uint32_t k = 0; k < count; ++k) {
+    if (sample_counts) sample_counts[k] = h->sample_count[first + k];
+    if (converged) converged[k] = h->converged[first + k];
+  }
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_set_filter_state(navgpu_amcl* h, uint32_t first, uint32_t count, const double* w) {
+  if (!h || !w || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  HIP_TRY(hipMemcpyAsync(h->d.w + 2 * (size_t)first, w, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_get_filter_state(navgpu_amcl* h, uint32_t first, uint32_t count, double* w) {
+  if (!h || !w || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  HIP_TRY(hipMemcpyAsync(w, h->d.w + 2 * (size_t)first, sizeof(double) * 2 * count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_update_sensor(navgpu_amcl* h, uint32_t first, uint32_t count, const double* ranges_xy, const uint32_t* range_counts,
+                              const double* range_max, int32_t* updated) {
+  if (!h || !range_counts || !range_max || !updated || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  if (!h->configured) {
+    g_last_error = "navgpu_amcl_update_sensor before navgpu_amcl_laser_configure";
+    return NAVGPU_ERR_STATE;
+  }
+  const navgpu_amcl_laser_params& P = h->params;
+  uint64_t total_ranges = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    if (range_counts[k] > (uint32_t)INT32_MAX) {  // AMCLLaserData::range_count is an int
+      g_last_error = "navgpu_amcl_update_sensor: range_count above INT32_MAX";
+      return NAVGPU_ERR_INVALID;
+    }
+    total_ranges += range_counts[k];
+  }
+  if (total_ranges && !ranges_xy) return NAVGPU_ERR_INVALID;
+  if (P.max_beams < 2) {  // AMCLLaser::UpdateSensor returns false (amcl_laser.cpp:163-164)
+    std::fill(updated, updated + count, 0);
+    return NAVGPU_OK;
+  }
+  for (uint32_t k = 0; k < count; ++k) {  // every map carries its distance map (set_map computes it), so a map is all it needs
+    if (!h->maps[first + k]) {
+      g_last_error = "navgpu_amcl_update_sensor: a filter has no map";
+      return NAVGPU_ERR_STATE;
+    }
+  }
+  // Subsample every filter's scan with the model's step (amcl_laser.cpp:265, 334-338, 417-421, 637-641)
+  std::vector<AmclFilterDev> fd(count);
+  std::vector<double> beams;
+  beams.reserve((size_t)count * 4 * P.max_beams);
+  int rc = NAVGPU_OK, max_samples = 0, max_nb = 0;
+  const double* src = ranges_xy;
+  for (uint32_t k = 0; k < count; ++k) {
+    const int rcount = (int)range_counts[k];
+    const uint32_t f = first + k;
+    int step;
+    if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB) {
+      step = (int)ceil(rcount / static_cast<double>(P.max_beams));
+      if (step < 1) step = 1;
+    } else {
+      step = (rcount - 1) / (P.max_beams - 1);
+      if (step < 1 && P.model_type != NAVGPU_AMCL_MODEL_BEAM) step = 1;
+    }
+    AmclFilterDev& e = fd[k];
+    e.sample_count = h->sample_count[f];
+    e.converged = h->converged[f];
+    e.range_max = range_max[k];
+    std::copy(&h->laser[3 * (size_t)f], &h->laser[3 * (size_t)f] + 3, e.laser);
+    e.beam_off = (uint32_t)(beams.size() / 2);
+    e.active = 1;
+    if (step < 1 && rcount > 0) {  // the beam model's loop would never end
+      e.active = 0;
+      updated[k] = NAVGPU_ERR_INVALID;
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_update_sensor: beam model with 1 <= range_count < max_beams (the reference loops forever)";
+    } else {
+      updated[k] = 1;
+      for (int i = 0; i < rcount; i += step) {
+        beams.push_back(src[2 * (size_t)i]);
+        beams.push_back(src[2 * (size_t)i + 1]);
+      }
+      e.n_beams = (int)(beams.size() / 2 - e.beam_off);
+      max_samples = std::max(max_samples, e.sample_count);
+      max_nb = std::max(max_nb, e.n_beams);
+    }
+    src += 2 * (size_t)rcount;
+  }
+  if (beams.size() > (size_t)h->n * 2 * h->d.max_beams * 2) return NAVGPU_ERR_CAPACITY;  // cannot happen: < 2 max_beams per filter
+  if (!beams.empty())
+    HIP_TRY(hipMemcpyAsync(h->d_beams, beams.data(), sizeof(double) * beams.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_filters, fd.data(), sizeof(AmclFilterDev) * count, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemsetAsync(h->d.obs_count + (size_t)first * h->d.max_beams, 0, sizeof(int32_t) * count * h->d.max_beams, h->stream));
+  HIP_TRY(hipMemsetAsync(h->d.obs_mask + (size_t)first * h->d.max_beams, 0, (size_t)count * h->d.max_beams, h->stream));
+  HIP_TRY(hipMemsetAsync(h->d.skip_info + 2 * (size_t)first, 0, sizeof(int32_t) * 2 * count, h->stream));
+  if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB && P.do_beamskip)
+    launch_amcl_laser(h->d, P, first, count, h->d_filters, h->d_beams, max_samples, max_nb, 1, h->stream);
+  launch_amcl_laser(h->d, P, first, count, h->d_filters, h->d_beams, max_samples, max_nb, 0, h->stream);
+  launch_amcl_normalize(h->d, P, first, count, h->d_filters, h->stream);
+  const int lrc = checkLaunch();
+  HIP_TRY(waitStream(h->stream));
+  return lrc ? lrc : rc;
+}
+
+int navgpu_amcl_beam_skip_state(navgpu_amcl* h, uint32_t filter, int32_t* obs_count, uint8_t* obs_mask, int32_t* error, int32_t* active) {
+  if (!h || filter >= h->n) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  const size_t mb = h->d.max_beams;
+  int32_t info[2];
+  HIP_TRY(hipMemcpyAsync(info, h->d.skip_info + 2 * (size_t)filter, sizeof(info), hipMemcpyDeviceToHost, h->stream));
+  if (obs_count) HIP_TRY(hipMemcpyAsync(obs_count, h->d.obs_count + filter * mb, sizeof(int32_t) * mb, hipMemcpyDeviceToHost, h->stream));
+  if (obs_mask) HIP_TRY(hipMemcpyAsync(obs_mask, h->d.obs_mask + filter * mb, mb, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  if (active) *active = info[0];
+  if (error) *error = info[1];
+  return NAVGPU_OK;
+}
+
+}  // extern "C"

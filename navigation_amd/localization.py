@@ -1,0 +1,147 @@
+"""AmclLaser: thin Python handle over navgpu_amcl_* — amcl's laser sensor update for a batch of particle filters on one GPU.
+
+  set_map            AmclNode::convertMap + map_update_cspace      (amcl_node.cpp:1062-1093, map_cspace.cpp)
+  set_map_cells      the same from a map_t's occ_state / scale / origin as they stand
+  set_distance_map   map_t::distances as computed elsewhere (e.g. the reference's own map_update_cspace)
+  configure          AMCLLaser::SetModel* / SetMapFactors, pf_alloc's alpha_slow / alpha_fast
+  update_sensor      AMCLLaser::UpdateSensor -> pf_update_sensor    (amcl_laser.cpp:160-236, pf.c:270-316)
+All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
+"""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import AmclLaserParams, check, lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class AmclLaser:
+    def __init__(self, n_filters, max_samples, max_beams=30, device=0):
+        self.L = lib()
+        self.n, self.max_samples, self.max_beams = n_filters, max_samples, max_beams
+        h = C.c_void_p()
+        check(self.L.navgpu_amcl_create(n_filters, max_samples, max_beams, device, C.byref(h)), "navgpu_amcl_create")
+        self.h = h
+        self.map_shape = [None] * n_filters
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.navgpu_amcl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _count(self, first, count):
+        return (self.n - first) if count is None else count
+
+    def set_map(self, occupancy, resolution, origin_xy=(0.0, 0.0), max_occ_dist=2.0, scale_up_factor=1, first=0, count=None):
+        """occupancy: OccupancyGrid data (height, width) int8 shared by `count` filters, or (count, height, width)."""
+        a = np.ascontiguousarray(occupancy, np.int8)
+        shared = a.ndim == 2
+        count = self._count(first, count)
+        if not shared:
+            assert a.shape[0] == count
+        h, w = a.shape[-2:]
+        org = np.ascontiguousarray(origin_xy, np.float64)
+        check(self.L.navgpu_amcl_set_map(self.h, first, count, _p(a), w, h, float(resolution), _p(org), int(scale_up_factor), int(shared),
+                                         float(max_occ_dist)), "amcl_set_map")
+        for k in range(first, first + count):
+            self.map_shape[k] = (h * scale_up_factor, w * scale_up_factor)
+
+    def set_map_cells(self, occ_state, scale, origin_xy, max_occ_dist=2.0, first=0, count=None):
+        """occ_state: map_t occ_state values (size_y, size_x) shared by `count` filters, or (count, size_y, size_x); origin_xy: map_t's
+        origin_x / origin_y (the map centre)."""
+        a = np.ascontiguousarray(occ_state, np.int8)
+        shared = a.ndim == 2
+        count = self._count(first, count)
+        if not shared:
+            assert a.shape[0] == count
+        sy, sx = a.shape[-2:]
+        check(self.L.navgpu_amcl_set_map_cells(self.h, first, count, _p(a), sx, sy, float(scale), float(origin_xy[0]), float(origin_xy[1]),
+                                               int(shared), float(max_occ_dist)), "amcl_set_map_cells")
+        for k in range(first, first + count):
+            self.map_shape[k] = (sy, sx)
+
+    def set_distance_map(self, distances, first=0, count=None):
+        """distances: (size_y, size_x) float32 for every filter of the slice, or (count, size_y, size_x)."""
+        a = np.ascontiguousarray(distances, np.float32)
+        count = self._count(first, count)
+        shared = a.ndim == 2
+        check(self.L.navgpu_amcl_set_distance_map(self.h, first, count, _p(a), int(shared)), "amcl_set_distance_map")
+
+    def distance_map(self, filter=0):
+        out = np.zeros(self.map_shape[filter], np.float32)
+        check(self.L.navgpu_amcl_distance_map(self.h, filter, _p(out)), "amcl_distance_map")
+        return out
+
+    def configure(self, params=None, **kw):
+        p = params if params is not None else AmclLaserParams(**kw)
+        check(self.L.navgpu_amcl_laser_configure(self.h, C.byref(p)), "amcl_laser_configure")
+        return p
+
+    def set_laser_pose(self, xyth, first=0):
+        a = np.ascontiguousarray(xyth, np.float64).reshape(-1, 3)
+        check(self.L.navgpu_amcl_set_laser_pose(self.h, first, len(a), _p(a)), "amcl_set_laser_pose")
+
+    def set_samples(self, poses, weights, sample_counts=None, converged=None, first=0):
+        """poses: (count, max_samples, 3) or (count, n, 3) with n <= max_samples; weights likewise (count, n)."""
+        poses = np.asarray(poses, np.float64)
+        count, n = poses.shape[0], poses.shape[1]
+        if n > self.max_samples:
+            raise ValueError(f"{n} samples per filter > max_samples {self.max_samples}")
+        P = np.zeros((count, self.max_samples, 3))
+        W = np.zeros((count, self.max_samples))
+        P[:, :n] = poses
+        W[:, :n] = np.asarray(weights, np.float64).reshape(count, n)
+        sc = np.ascontiguousarray(np.full(count, n) if sample_counts is None else sample_counts, np.int32)
+        cv = np.ascontiguousarray(np.zeros(count) if converged is None else converged, np.int32)
+        check(self.L.navgpu_amcl_set_samples(self.h, first, count, _p(sc), _p(P), _p(W), _p(cv)), "amcl_set_samples")
+
+    def get_samples(self, first=0, count=None):
+        """-> (sample_counts, poses (count, max_samples, 3), weights (count, max_samples), converged)"""
+        count = self._count(first, count)
+        sc = np.zeros(count, np.int32)
+        cv = np.zeros(count, np.int32)
+        P = np.zeros((count, self.max_samples, 3))
+        W = np.zeros((count, self.max_samples))
+        check(self.L.navgpu_amcl_get_samples(self.h, first, count, _p(sc), _p(P), _p(W), _p(cv)), "amcl_get_samples")
+        return sc, P, W, cv
+
+    def set_filter_state(self, w_slow_fast, first=0):
+        a = np.ascontiguousarray(w_slow_fast, np.float64).reshape(-1, 2)
+        check(self.L.navgpu_amcl_set_filter_state(self.h, first, len(a), _p(a)), "amcl_set_filter_state")
+
+    def get_filter_state(self, first=0, count=None):
+        count = self._count(first, count)
+        a = np.zeros((count, 2))
+        check(self.L.navgpu_amcl_get_filter_state(self.h, first, count, _p(a)), "amcl_get_filter_state")
+        return a
+
+    def update_sensor(self, scans, range_max, first=0, raise_on_error=True):
+        """scans: a list of (range_count, 2) arrays {range, bearing}, one per filter of the slice; range_max: scalar or per filter.
+        -> (status, updated[count])"""
+        count = len(scans)
+        rc_ = np.ascontiguousarray([len(s) for s in scans], np.uint32)
+        flat = [np.asarray(s, np.float64).reshape(-1, 2) for s in scans]
+        xy = np.ascontiguousarray(np.concatenate(flat) if rc_.sum() else np.zeros((1, 2)), np.float64)
+        rm = np.ascontiguousarray(np.broadcast_to(np.asarray(range_max, np.float64), (count,)))
+        upd = np.zeros(count, np.int32)
+        st = self.L.navgpu_amcl_update_sensor(self.h, first, count, _p(xy), _p(rc_), _p(rm), _p(upd))
+        if raise_on_error:
+            check(st, "amcl_update_sensor")
+        return st, upd
+
+    def beam_skip_state(self, filter=0):
+        """-> (obs_count[max_beams], obs_mask[max_beams], error, active) of the last update"""
+        oc = np.zeros(self.max_beams, np.int32)
+        om = np.zeros(self.max_beams, np.uint8)
+        err, act = C.c_int32(), C.c_int32()
+        check(self.L.navgpu_amcl_beam_skip_state(self.h, filter, _p(oc), _p(om), C.byref(err), C.byref(act)), "amcl_beam_skip_state")
+        return oc, om.astype(bool), err.value, act.value
