@@ -671,8 +671,8 @@ int navgpu_global_planner_plan_wavefront(navgpu_navfn* nav, uint32_t first, uint
  * and the laser pose.  Filter k's samples live at k * max_samples in every sample array.  One laser model configuration
  * (navgpu_amcl_laser_configure) serves every filter of the handle.  All arithmetic is fp64 with the reference's operation
  * order; the device's libm (sin / cos / atan2 / exp / log) may differ from the host's by an ulp.  Coordinates are metres,
- * cells are map_t's (origin at the map centre, map.h:139-147).  Motion model, resampling and the kd-tree stay with the
- * reference (they draw from drand48 / pf_ran_gaussian). */
+ * cells are map_t's (origin at the map centre, map.h:139-147).  Resampling, the kd-tree histogram and the cluster statistics
+ * run on the device too (navgpu_amcl_update_resample below); the motion model stays with the reference (pf_ran_gaussian). */
 typedef struct navgpu_amcl navgpu_amcl;
 #define NAVGPU_AMCL_MODEL_BEAM 0                     /* laser_model_t, amcl_laser.h:42-48 */
 #define NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD 1
@@ -732,7 +732,8 @@ int navgpu_amcl_laser_configure(navgpu_amcl* amcl, const navgpu_amcl_laser_param
 int navgpu_amcl_set_laser_pose(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* xyth);
 /* pf_t::sets[current_set] of the slice: sample_counts[count] (<= max_samples, NAVGPU_ERR_CAPACITY above), poses = count x
  * max_samples x {x, y, theta} (pf_vector_t), weights = count x max_samples, converged[count].  Entries past a filter's
- * sample_count are stored and returned as given but take no part in an update.  get: any output pointer may be NULL. */
+ * sample_count are stored and returned as given but take no part in an update.  get: any output pointer may be NULL.
+ * set also sets each filter's kd-tree leaf count from its uploaded poses (navgpu_amcl_set_kd_leaf_counts). */
 int navgpu_amcl_set_samples(navgpu_amcl* amcl, uint32_t first, uint32_t count, const int32_t* sample_counts, const double* poses,
                             const double* weights, const int32_t* converged);
 int navgpu_amcl_get_samples(navgpu_amcl* amcl, uint32_t first, uint32_t count, int32_t* sample_counts, double* poses, double* weights,
@@ -767,6 +768,69 @@ int navgpu_amcl_update_sensor(navgpu_amcl* amcl, uint32_t first, uint32_t count,
  * integrated).  *active = 0 where the last update did not skip beams (do_beamskip off, set not converged, another model); the
  * rest is then zero.  Any output pointer may be NULL. */
 int navgpu_amcl_beam_skip_state(navgpu_amcl* amcl, uint32_t filter, int32_t* obs_count, uint8_t* obs_mask, int32_t* error, int32_t* active);
+
+/* ---- amcl resampling: pf_update_resample, the kd-tree histogram, pf_cluster_stats, pf_update_converged ---- */
+#define NAVGPU_AMCL_RESAMPLE_MULTINOMIAL 0 /* pf_resample_model_t, pf.h */
+#define NAVGPU_AMCL_RESAMPLE_SYSTEMATIC 1
+#define NAVGPU_AMCL_DRAW_SUPPLIED 0 /* the caller's uniform draws and random poses (parity with the reference) */
+#define NAVGPU_AMCL_DRAW_DEVICE 1   /* a counter-based generator on the device, seeded per call; nothing is uploaded */
+typedef struct {
+  int32_t resample_model; /* NAVGPU_AMCL_RESAMPLE_*                       pf_set_resample_model (pf.c:116-119)          */
+  int32_t min_samples;    /* pf_alloc's min_samples (0 .. max_samples)                                                  */
+  double pop_err, pop_z;  /* KLD bound, pf_alloc's 0.01 / 3 (pf.c:72-73; amcl_node's kld_err / kld_z)                  */
+  double dist_threshold;  /* pf_update_converged's, 0.5 in pf_alloc (pf.c:74)                                          */
+} navgpu_amcl_resample_params;
+/* replaces: pf_set_resample_model and the pf_alloc fields above; max_samples is the handle's.  All or nothing: an invalid
+ * struct (model not 0 / 1, min_samples outside 0..max_samples, pop_err not > 0, NaN) leaves the previous one in force. */
+int navgpu_amcl_resample_configure(navgpu_amcl* amcl, const navgpu_amcl_resample_params* params);
+/* replaces: pf_update_resample(pf) (pf.c:512-562) for every filter of the slice: draw set b from the current set, weights 1 / total,
+ * w_slow = w_fast = 0 where w_diff > 0, the kd-tree histogram's leaf count, pf_cluster_stats and pf_update_converged (get_samples
+ * returns the new set and its converged flag, get_clusters its clusters, get_kd_leaf_counts its leaf count).
+ * draw_source NAVGPU_AMCL_DRAW_SUPPLIED: the reference's drand48() stream as values -
+ *   multinomial: u = count x max_samples x {u_flag, u_pick}: candidate k is random when u_flag < w_diff, else the sample whose
+ *     [c[i], c[i+1]) holds u_pick (u_pick of a random candidate is not read);
+ *   systematic: systematic_start[count], systematic_sample_start;
+ *   both: random_poses = the pools of the slice's filters one after the other, random_pose_counts[k] poses {x, y, theta} each,
+ *     consumed in order (pf_t::random_pose_fn).  A pool shorter than the filter needs gives status[k] = NAVGPU_ERR_INVALID and
+ *     the filter is untouched.  seed is not read.
+ * draw_source NAVGPU_AMCL_DRAW_DEVICE: Philox4x32-10 keyed by `seed`, counter {draw, filter, the filter's call counter}; the
+ *   call counter of every filter of the slice goes up by one per call (navgpu_amcl_set_rng_counters).  Random poses follow
+ *   AmclNode::randomFreeSpacePose (amcl_node.cpp:1200-1212): a uniform index into the filter's map's free cells (occ_state -1,
+ *   x-major, kept by navgpu_amcl_set_map*), the cell centre, theta = u * 2 pi - pi.  u, systematic_start, random_poses and
+ *   random_pose_counts are not read.
+ * The histogram key is floor(pose / {0.5, 0.5, 10 deg}) (pf_kdtree.c:72-74,116-118); the multinomial draw stops after candidate k
+ * (1-based) once k > pf_resample_limit(leaf count of the first k); systematic draws pf_resample_limit(leaf count of the current
+ * set AT ITS CREATION: set_samples / the previous resample / set_kd_leaf_counts) * (1 + w_diff) samples, the first
+ * (int)(w_diff * new_count) of them random.  w_diff = 1 - w_fast / w_slow, clamped at 0.  Defined where the reference is not:
+ * - a draw no interval [c[i], c[i+1]) holds (a systematic target in [c[n], 1.0] loops forever at pf.c:378-386, a multinomial
+ *   u_pick >= c[n] reads samples[n] at pf.c:474-483; also u < 0 or NaN) picks the LAST SAMPLE WITH POSITIVE WEIGHT (sample n-1
+ *   when no weight is positive);
+ * - n_rand == new_count (w_diff == 1) makes every sample random; delta = 1 / 0 is never used;
+ * - w_slow == 0 (0 / 0 or -inf after a reset) gives w_diff = 0, as the multinomial comparison with NaN does;
+ * - a filter with sample_count 0, a random candidate without a pose (pool exhausted, a map without free cells), or a set b pose
+ *   with a non-finite coordinate or |bin| > 2^20 - 2 gives status[k] = NAVGPU_ERR_INVALID and leaves that filter untouched.
+ * Weights of set a must be >= 0 (as update_sensor leaves them).  Clusters are numbered by their lowest sample index (the
+ * reference numbers them in kd-tree node order, which depends on the insertion history); none is dropped.  Sums run in
+ * sample order in one lane, so two runs give identical bytes.  Returns NAVGPU_ERR_INVALID when any filter failed (the others
+ * ran), NAVGPU_ERR_STATE before navgpu_amcl_resample_configure or for device draws on a filter without a map. */
+int navgpu_amcl_update_resample(navgpu_amcl* amcl, uint32_t first, uint32_t count, int32_t draw_source, const double* u,
+                                const double* systematic_start, const double* random_poses, const uint32_t* random_pose_counts, uint64_t seed,
+                                int32_t* status);
+/* replaces: pf_get_cluster_stats (pf.c:760-779) and the set's cluster_count read at amcl_node.cpp:1590-1597 for the current set
+ * of one filter after a resample: *cluster_count, then for the first min(cluster_count, capacity) clusters counts[k], weights[k],
+ * means[k][3], covs[k][3][3]; set_mean[3], set_cov[9] are pf_sample_set_t::mean / cov.  Any array may be NULL.
+ * NAVGPU_ERR_CAPACITY when cluster_count > capacity (the first `capacity` are written); NAVGPU_ERR_STATE (cluster_count 0)
+ * before the filter's first resample. */
+int navgpu_amcl_get_clusters(navgpu_amcl* amcl, uint32_t filter, int32_t* cluster_count, uint32_t capacity, int32_t* counts,
+                             double* weights, double* means, double* covs, double* set_mean, double* set_cov);
+/* pf_kdtree_t::leaf_count of each filter's current set as it was created, what systematic resampling sizes set b from
+ * (pf.c:342).  navgpu_amcl_set_samples sets it from the uploaded poses, as pf_init_model's inserts do (pf.c:180-205);
+ * update_resample sets it to the new set's. */
+int navgpu_amcl_set_kd_leaf_counts(navgpu_amcl* amcl, uint32_t first, uint32_t count, const int32_t* leaf_counts);
+int navgpu_amcl_get_kd_leaf_counts(navgpu_amcl* amcl, uint32_t first, uint32_t count, int32_t* leaf_counts);
+/* The device generator's per-filter call counters (0 at create); with the same seed, counter and set a call repeats its draws. */
+int navgpu_amcl_set_rng_counters(navgpu_amcl* amcl, uint32_t first, uint32_t count, const uint64_t* counters);
+int navgpu_amcl_get_rng_counters(navgpu_amcl* amcl, uint32_t first, uint32_t count, uint64_t* counters);
 
 #ifdef __cplusplus
 }

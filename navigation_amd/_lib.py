@@ -210,6 +210,25 @@ class AmclLaserParams(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+AMCL_RESAMPLE_MULTINOMIAL, AMCL_RESAMPLE_SYSTEMATIC = range(2)
+AMCL_DRAW_SUPPLIED, AMCL_DRAW_DEVICE = range(2)
+
+
+class AmclResampleParams(C.Structure):
+    """Mirror of navgpu_amcl_resample_params (include/navgpu.h).  Defaults: pf_alloc's pop_err 0.01, pop_z 3, dist_threshold 0.5
+    (pf.c:72-74), amcl_node's min_particles 100 and its default multinomial resample_model."""
+    _fields_ = [("resample_model", C.c_int32), ("min_samples", C.c_int32), ("pop_err", C.c_double), ("pop_z", C.c_double),
+                ("dist_threshold", C.c_double)]
+    DEFAULTS = dict(resample_model=AMCL_RESAMPLE_MULTINOMIAL, min_samples=100, pop_err=0.01, pop_z=3.0, dist_threshold=0.5)
+
+    def __init__(self, **kw):
+        super().__init__()
+        d = dict(self.DEFAULTS)
+        d.update(kw)
+        for k, v in d.items():
+            setattr(self, k, v)
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -318,6 +337,13 @@ SYMBOLS = [
     ("navgpu_amcl_get_filter_state", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_amcl_update_sensor", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
     ("navgpu_amcl_beam_skip_state", C.c_int, [vp, u32, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
+    ("navgpu_amcl_resample_configure", C.c_int, [vp, C.POINTER(AmclResampleParams)]),
+    ("navgpu_amcl_update_resample", C.c_int, [vp, u32, u32, i32, vp, vp, vp, vp, C.c_uint64, vp]),
+    ("navgpu_amcl_get_clusters", C.c_int, [vp, u32, C.POINTER(i32), u32, vp, vp, vp, vp, vp, vp]),
+    ("navgpu_amcl_set_kd_leaf_counts", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_get_kd_leaf_counts", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_set_rng_counters", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_get_rng_counters", C.c_int, [vp, u32, u32, vp]),
 ]
 
 

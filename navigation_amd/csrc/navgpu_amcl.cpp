@@ -1,19 +1,26 @@
 // navgpu_amcl_*: host side of the amcl laser update for a batch of particle filters (see amcl_kernels.hip and include/navgpu.h).
+#include <algorithm>
+#include <cmath>
 #include <memory>
 
 #include "navgpu_amcl.h"
 #include "navgpu_fleet.h"
+
+#include <array>
 
 namespace {
 // One map_t on the device; several filters may hold the same one (set_map with shared != 0)
 struct AmclMap {
   int8_t* occ = nullptr;
   float* dist = nullptr;
+  int32_t* free_cells = nullptr;  // occ_state == -1, x-major (AmclNode::free_space_indices, amcl_node.cpp:1028-1033)
+  int n_free = 0;
   int sx = 0, sy = 0;
   double scale = 0, ox = 0, oy = 0, max_occ_dist = 0;
   ~AmclMap() {
     if (occ) hipFree(occ);
     if (dist) hipFree(dist);
+    if (free_cells) hipFree(free_cells);
   }
 };
 }  // namespace
@@ -33,6 +40,16 @@ struct navgpu_amcl {
   bool configured = false;
   AmclFilterDev* d_filters = nullptr;          // [n]
   double* d_beams = nullptr;                   // [n][2 * max_beams][2] subsampled {range, bearing}
+  // resampling (navgpu_amcl_update_resample); the workspace is allocated by the first call
+  navgpu_amcl_resample_params rparams{};
+  bool rconfigured = false;
+  AmclResampleDev rs{};
+  bool rs_ready = false;
+  AmclResampleFilterDev* d_rfilters = nullptr;  // [n]
+  std::vector<int32_t> leaf, cluster_count;     // kd-tree leaf count of the current set at its creation; its cluster count
+  std::vector<uint64_t> rng_ctr;                // device draws: calls made per filter
+  void* d_upload = nullptr;                     // supplied draws of the last call
+  size_t upload_bytes = 0;
   template <class T>
   int alloc(T** p, size_t count) {
     void* q = nullptr;
@@ -102,6 +119,9 @@ int navgpu_amcl_create(uint32_t n_filters, uint32_t max_samples, uint32_t max_be
   h->sample_count.assign(n_filters, 0);
   h->converged.assign(n_filters, 0);
   h->laser.assign((size_t)n_filters * 3, 0.0);
+  h->leaf.assign(n_filters, 0);
+  h->cluster_count.assign(n_filters, 0);
+  h->rng_ctr.assign(n_filters, 0);
   AmclDev& d = h->d;
   d.max_samples = max_samples;
   d.max_beams = max_beams;
@@ -117,6 +137,7 @@ int navgpu_amcl_create(uint32_t n_filters, uint32_t max_samples, uint32_t max_be
   A(d.skip_info, (size_t)n_filters * 2);
   A(h->d_filters, n_filters);
   A(h->d_beams, (size_t)n_filters * 2 * max_beams * 2);
+  A(h->d_rfilters, n_filters);
 #undef A
   if (!rc && waitStream(h->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;
   if (rc) {
@@ -133,6 +154,7 @@ int navgpu_amcl_destroy(navgpu_amcl* h) {
   if (h->stream) waitStream(h->stream);
   h->maps.clear();
   for (void* p : h->allocs) hipFree(p);
+  if (h->d_upload) hipFree(h->d_upload);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
   return NAVGPU_OK;
@@ -141,6 +163,38 @@ int navgpu_amcl_destroy(navgpu_amcl* h) {
 }  // extern "C"
 
 namespace {
+// The free-cell list of a map for random poses: cells with occ_state == -1 in AmclNode's x-major order (amcl_node.cpp:1028-1033,
+// with its default laser_non_free_space_radius 0 every free cell passes map_occ_dist > radius)
+int freeCells(AmclMap& m, hipStream_t s) {
+  std::vector<int8_t> occ((size_t)m.sx * m.sy);
+  HIP_TRY(hipMemcpyAsync(occ.data(), m.occ, occ.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(waitStream(s));
+  std::vector<int32_t> list;
+  for (int i = 0; i < m.sx; ++i)
+    for (int j = 0; j < m.sy; ++j)
+      if (occ[i + (size_t)j * m.sx] == -1) list.push_back(i + j * m.sx);
+  m.n_free = (int)list.size();
+  if (list.empty()) return NAVGPU_OK;
+  HIP_TRY(hipMalloc(&m.free_cells, list.size() * sizeof(int32_t)));
+  HIP_TRY(hipMemcpyAsync(m.free_cells, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(waitStream(s));
+  return NAVGPU_OK;
+}
+
+// pf_kdtree_insert's leaf count (pf_kdtree.c:110-120): distinct floor(pose / {0.5, 0.5, 10 deg}) keys of a set, as pf_init_model
+// leaves it.  Non-finite bins all count as one key.
+int32_t leafCount(const double* poses, int n) {
+  std::vector<std::array<double, 3>> keys((size_t)n);
+  const double size[3] = {0.50, 0.50, (10 * M_PI / 180)};
+  for (int i = 0; i < n; ++i)
+    for (int a = 0; a < 3; ++a) {
+      const double b = std::floor(poses[3 * (size_t)i + a] / size[a]);
+      keys[i][a] = std::isfinite(b) ? b : INFINITY;
+    }
+  std::sort(keys.begin(), keys.end());
+  return (int32_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
+}
+
 // Maps of a slice: `src` is OccupancyGrid data (height x width, scaled up by `factor` on the device) or, with `cells`, map_t
 // occ_state values copied as they are (factor 1); scale and the centre origin (ox, oy) are map_t's own.
 int setMaps(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* src, uint32_t width, uint32_t height, int factor, bool cells,
@@ -183,6 +237,7 @@ int setMaps(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* src, u
     launch_amcl_cspace(m->occ, m->sx, m->sy, radius, scale, max_occ_dist, d_g, m->dist, h->stream);
     if (!rc) rc = checkLaunch();
     if (waitStream(h->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;  // the staging buffers are reused by the next map
+    if (!rc) rc = freeCells(*m, h->stream);
     made.push_back(m);
   }
   hipFree(d_msg);
@@ -191,7 +246,7 @@ int setMaps(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* src, u
   for (uint32_t k = 0; k < count; ++k) {
     const auto& m = made[shared ? 0 : k];
     h->maps[first + k] = m;
-    h->map_desc[first + k] = AmclMapDev{m->occ, m->dist, m->sx, m->sy, m->scale, m->ox, m->oy, m->max_occ_dist};
+    h->map_desc[first + k] = AmclMapDev{m->occ, m->dist, m->free_cells, m->n_free, m->sx, m->sy, m->scale, m->ox, m->oy, m->max_occ_dist};
   }
   return h->uploadMaps();
 }
@@ -285,6 +340,7 @@ int navgpu_amcl_set_samples(navgpu_amcl* h, uint32_t first, uint32_t count, cons
   for (uint32_t k = 0; k < count; ++k) {
     h->sample_count[first + k] = sample_counts[k];
     h->converged[first + k] = converged[k] ? 1 : 0;
+    h->leaf[first + k] = leafCount(poses + (size_t)k * ms * 3, sample_counts[k]);
   }
   return NAVGPU_OK;
 }
@@ -417,6 +473,192 @@ int navgpu_amcl_beam_skip_state(navgpu_amcl* h, uint32_t filter, int32_t* obs_co
   if (active) *active = info[0];
   if (error) *error = info[1];
   return NAVGPU_OK;
+}
+
+int navgpu_amcl_resample_configure(navgpu_amcl* h, const navgpu_amcl_resample_params* p) {
+  if (!h || !p) return NAVGPU_ERR_INVALID;
+  if ((p->resample_model != NAVGPU_AMCL_RESAMPLE_MULTINOMIAL && p->resample_model != NAVGPU_AMCL_RESAMPLE_SYSTEMATIC) ||
+      p->min_samples < 0 || (uint32_t)p->min_samples > h->d.max_samples || !(p->pop_err > 0) || !isFinite(p->pop_err) ||
+      !isFinite(p->pop_z) || p->dist_threshold != p->dist_threshold)
+    return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  h->rparams = *p;
+  h->rconfigured = true;
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_set_kd_leaf_counts(navgpu_amcl* h, uint32_t first, uint32_t count, const int32_t* leaf_counts) {
+  if (!h || !leaf_counts || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  for (uint32_t k = 0; k < count; ++k)
+    if (leaf_counts[k] < 0) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  std::copy(leaf_counts, leaf_counts + count, h->leaf.begin() + first);
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_get_kd_leaf_counts(navgpu_amcl* h, uint32_t first, uint32_t count, int32_t* leaf_counts) {
+  if (!h || !leaf_counts || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  std::copy(h->leaf.begin() + first, h->leaf.begin() + first + count, leaf_counts);
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_set_rng_counters(navgpu_amcl* h, uint32_t first, uint32_t count, const uint64_t* counters) {
+  if (!h || !counters || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  std::copy(counters, counters + count, h->rng_ctr.begin() + first);
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_get_rng_counters(navgpu_amcl* h, uint32_t first, uint32_t count, uint64_t* counters) {
+  if (!h || !counters || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  std::copy(h->rng_ctr.begin() + first, h->rng_ctr.begin() + first + count, counters);
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_update_resample(navgpu_amcl* h, uint32_t first, uint32_t count, int32_t draw_source, const double* u,
+                                const double* systematic_start, const double* random_poses, const uint32_t* random_pose_counts, uint64_t seed,
+                                int32_t* status) {
+  if (!h || !status || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  if (draw_source != NAVGPU_AMCL_DRAW_SUPPLIED && draw_source != NAVGPU_AMCL_DRAW_DEVICE) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  if (!h->rconfigured) {
+    g_last_error = "navgpu_amcl_update_resample before navgpu_amcl_resample_configure";
+    return NAVGPU_ERR_STATE;
+  }
+  const navgpu_amcl_resample_params& R = h->rparams;
+  const bool sys = R.resample_model == NAVGPU_AMCL_RESAMPLE_SYSTEMATIC, dev = draw_source == NAVGPU_AMCL_DRAW_DEVICE;
+  const size_t ms = h->d.max_samples;
+  uint64_t pool_total = 0;
+  if (!dev) {
+    if (!random_pose_counts || (!sys && !u) || (sys && !systematic_start)) return NAVGPU_ERR_INVALID;
+    for (uint32_t k = 0; k < count; ++k) pool_total += random_pose_counts[k];
+    if (pool_total && !random_poses) return NAVGPU_ERR_INVALID;
+    if (pool_total > (uint64_t)INT32_MAX) return NAVGPU_ERR_CAPACITY;
+  } else {
+    for (uint32_t k = 0; k < count; ++k)
+      if (!h->maps[first + k]) {
+        g_last_error = "navgpu_amcl_update_resample: device draws for a filter without a map";
+        return NAVGPU_ERR_STATE;
+      }
+  }
+  AmclResampleDev& r = h->rs;
+  if (!h->rs_ready) {
+    uint32_t P = 1;
+    while (P < ms) P <<= 1;
+    r.P = P;
+    const size_t n = h->n;
+    int rc = 0;
+#define A(ptr, cnt) \
+  if (!rc) rc = h->alloc(&(ptr), (size_t)(cnt));
+    A(r.c, n * (ms + 1));
+    A(r.cand, n * ms * 3);
+    A(r.cs, n * ms * 2);
+    A(r.skey, n * P);
+    A(r.sidx, n * P);
+    A(r.a, n * P);
+    A(r.b, n * P);
+    A(r.label, n * ms);
+    A(r.ukey, n * ms);
+    A(r.cstart, n * ms);
+    A(r.cl_count, n * ms);
+    A(r.cl_stats, n * ms * 13);
+    A(r.set_stats, n * 12);
+#undef A
+    if (rc) return rc;
+    HIP_TRY(waitStream(h->stream));
+    h->rs_ready = true;
+  }
+  // supplied draws: {u_flag, u_pick} pairs (multinomial) then the random-pose pool, in one upload
+  const size_t u_doubles = (!dev && !sys) ? (size_t)count * ms * 2 : 0, bytes = sizeof(double) * (u_doubles + 3 * pool_total);
+  r.u = nullptr;
+  r.pool = nullptr;
+  if (bytes) {
+    if (bytes > h->upload_bytes) {
+      if (h->d_upload) hipFree(h->d_upload);
+      h->d_upload = nullptr;
+      h->upload_bytes = 0;
+      HIP_TRY(hipMalloc(&h->d_upload, bytes));
+      h->upload_bytes = bytes;
+    }
+    double* up = static_cast<double*>(h->d_upload);
+    if (u_doubles) HIP_TRY(hipMemcpyAsync(up, u, sizeof(double) * u_doubles, hipMemcpyHostToDevice, h->stream));
+    if (pool_total)
+      HIP_TRY(hipMemcpyAsync(up + u_doubles, random_poses, sizeof(double) * 3 * pool_total, hipMemcpyHostToDevice, h->stream));
+    r.u = up;
+    r.pool = up + u_doubles;
+  }
+  std::vector<AmclResampleFilterDev> fd(count);
+  uint64_t pool_off = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    AmclResampleFilterDev& e = fd[k];
+    const uint32_t f = first + k;
+    e.sample_count = h->sample_count[f];
+    e.leaf_in = h->leaf[f];
+    e.pool_count = dev ? 0 : (int32_t)random_pose_counts[k];
+    e.pool_off = pool_off;
+    pool_off += dev ? 0 : random_pose_counts[k];
+    e.rng_ctr = h->rng_ctr[f];
+    e.sys_start = (!dev && sys) ? systematic_start[k] : 0.0;
+    e.active = 1;
+    e.status = NAVGPU_ERR_INVALID;
+  }
+  HIP_TRY(hipMemcpyAsync(h->d_rfilters, fd.data(), sizeof(AmclResampleFilterDev) * count, hipMemcpyHostToDevice, h->stream));
+  const AmclResampleParamsDev P{R.resample_model, R.min_samples, (int32_t)ms, dev ? 1 : 0, R.pop_err, R.pop_z, R.dist_threshold, seed};
+  launch_amcl_resample(h->d, r, P, first, count, h->d_rfilters, h->stream);
+  const int lrc = checkLaunch();
+  if (lrc) return lrc;
+  HIP_TRY(hipMemcpyAsync(fd.data(), h->d_rfilters, sizeof(AmclResampleFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  int rc = NAVGPU_OK;
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t f = first + k;
+    const AmclResampleFilterDev& e = fd[k];
+    status[k] = e.status;
+    if (dev) ++h->rng_ctr[f];
+    if (e.status != NAVGPU_OK) {
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_update_resample: a filter has no samples, too few supplied random poses, no free cell or a pose "
+                     "outside the histogram's range";
+      continue;
+    }
+    h->sample_count[f] = e.count;
+    h->leaf[f] = e.leaf_out;
+    h->converged[f] = e.converged;
+    h->cluster_count[f] = e.cluster_count;
+  }
+  return rc;
+}
+
+int navgpu_amcl_get_clusters(navgpu_amcl* h, uint32_t filter, int32_t* cluster_count, uint32_t capacity, int32_t* counts, double* weights,
+                             double* means, double* covs, double* set_mean, double* set_cov) {
+  if (!h || !cluster_count || filter >= h->n) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  const int32_t C = h->cluster_count[filter];
+  *cluster_count = C;
+  if (!h->rs_ready || C == 0) {
+    g_last_error = "navgpu_amcl_get_clusters: the filter has not been resampled";
+    return NAVGPU_ERR_STATE;
+  }
+  const size_t ms = h->d.max_samples, fo = (size_t)filter * ms, nc = std::min<size_t>((size_t)C, capacity);
+  std::vector<int32_t> cnt(nc);
+  std::vector<double> st(nc * 13), ss(12);
+  if (nc) {
+    HIP_TRY(hipMemcpyAsync(cnt.data(), h->rs.cl_count + fo, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), h->rs.cl_stats + fo * 13, sizeof(double) * nc * 13, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(ss.data(), h->rs.set_stats + 12 * (size_t)filter, sizeof(double) * 12, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  for (size_t k = 0; k < nc; ++k) {
+    if (counts) counts[k] = cnt[k];
+    if (weights) weights[k] = st[13 * k];
+    if (means) std::copy(&st[13 * k + 1], &st[13 * k + 4], means + 3 * k);
+    if (covs) std::copy(&st[13 * k + 4], &st[13 * k + 13], covs + 9 * k);
+  }
+  if (set_mean) std::copy(ss.begin(), ss.begin() + 3, set_mean);
+  if (set_cov) std::copy(ss.begin() + 3, ss.end(), set_cov);
+  return (size_t)C > capacity ? NAVGPU_ERR_CAPACITY : NAVGPU_OK;
 }
 
 }  // extern "C"

@@ -5,13 +5,20 @@
   set_distance_map   map_t::distances as computed elsewhere (e.g. the reference's own map_update_cspace)
   configure          AMCLLaser::SetModel* / SetMapFactors, pf_alloc's alpha_slow / alpha_fast
   update_sensor      AMCLLaser::UpdateSensor -> pf_update_sensor    (amcl_laser.cpp:160-236, pf.c:270-316)
+  configure_resample pf_set_resample_model and pf_alloc's KLD / convergence parameters
+  update_resample    pf_update_resample: resampling, kd-tree histogram, pf_cluster_stats, pf_update_converged (pf.c:222-720)
+  clusters           pf_get_cluster_stats / the set's cluster_count and mean / cov
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
-from ._lib import AmclLaserParams, check, lib
+from ._lib import AMCL_DRAW_DEVICE, AMCL_DRAW_SUPPLIED, AMCL_RESAMPLE_SYSTEMATIC, AmclLaserParams, AmclResampleParams, check, lib
+
+# pf_sample_set_t's clusters and overall statistics: count (C,), weight (C,), mean (C, 3), cov (C, 3, 3), set_mean (3,), set_cov (3, 3)
+AmclClusters = namedtuple("AmclClusters", "count weight mean cov set_mean set_cov")
 
 
 def _p(a):
@@ -145,3 +152,70 @@ class AmclLaser:
         err, act = C.c_int32(), C.c_int32()
         check(self.L.navgpu_amcl_beam_skip_state(self.h, filter, _p(oc), _p(om), C.byref(err), C.byref(act)), "amcl_beam_skip_state")
         return oc, om.astype(bool), err.value, act.value
+
+    def configure_resample(self, params=None, **kw):
+        """navgpu_amcl_resample_params fields: resample_model, min_samples, pop_err, pop_z, dist_threshold."""
+        p = params if params is not None else AmclResampleParams(**kw)
+        check(self.L.navgpu_amcl_resample_configure(self.h, C.byref(p)), "amcl_resample_configure")
+        self.resample_params = p
+        return p
+
+    def update_resample(self, draws=None, seed=None, first=0, count=None, raise_on_error=True):
+        """draws=None: the device generator with `seed`.  Supplied draws, a dict for the `count` filters of the slice:
+          u:                (count, n_u, 2) {u_flag, u_pick} per candidate (multinomial; padded to max_samples with 1.0, i.e.
+                            never random and never a valid pick - pad generously, the KLD limit stops early);
+          systematic_start: (count,) (systematic);
+          random_poses:     a list of (k_i, 3) pools, one per filter, consumed in order.
+        -> (status, status[count])"""
+        count = self._count(first, count) if draws is None else len(draws["random_poses"])
+        st = np.zeros(count, np.int32)
+        if draws is None:
+            rc = self.L.navgpu_amcl_update_resample(self.h, first, count, AMCL_DRAW_DEVICE, None, None, None, None,
+                                                    int(0 if seed is None else seed) & (2 ** 64 - 1), _p(st))
+        else:
+            pools = [np.asarray(q, np.float64).reshape(-1, 3) for q in draws["random_poses"]]
+            pc = np.ascontiguousarray([len(q) for q in pools], np.uint32)
+            pool = np.ascontiguousarray(np.concatenate(pools) if pc.sum() else np.zeros((1, 3)))
+            u = np.ones((count, self.max_samples, 2))
+            if draws.get("u") is not None:
+                uu = np.asarray(draws["u"], np.float64).reshape(count, -1, 2)
+                u[:, :uu.shape[1]] = uu[:, :self.max_samples]
+            ss = np.ascontiguousarray(np.broadcast_to(np.asarray(draws.get("systematic_start", 0.0), np.float64), (count,)))
+            rc = self.L.navgpu_amcl_update_resample(self.h, first, count, AMCL_DRAW_SUPPLIED, _p(u), _p(ss), _p(pool), _p(pc), 0, _p(st))
+        if raise_on_error:
+            check(rc, "amcl_update_resample")
+        return rc, st
+
+    def clusters(self, filter=0):
+        """-> AmclClusters of the filter's current set after a resample (clusters numbered by their lowest sample index)."""
+        n = C.c_int32()
+        rc = self.L.navgpu_amcl_get_clusters(self.h, filter, C.byref(n), 0, None, None, None, None, None, None)
+        if rc < 0 and n.value <= 0:
+            check(rc, "amcl_get_clusters")
+        k = n.value
+        cnt, w = np.zeros(k, np.int32), np.zeros(k)
+        mean, cov = np.zeros((k, 3)), np.zeros((k, 3, 3))
+        sm, sc = np.zeros(3), np.zeros((3, 3))
+        check(self.L.navgpu_amcl_get_clusters(self.h, filter, C.byref(n), k, _p(cnt), _p(w), _p(mean), _p(cov), _p(sm), _p(sc)),
+              "amcl_get_clusters")
+        return AmclClusters(cnt, w, mean, cov, sm, sc)
+
+    def kd_leaf_counts(self, first=0, count=None):
+        count = self._count(first, count)
+        a = np.zeros(count, np.int32)
+        check(self.L.navgpu_amcl_get_kd_leaf_counts(self.h, first, count, _p(a)), "amcl_get_kd_leaf_counts")
+        return a
+
+    def set_kd_leaf_counts(self, leaf_counts, first=0):
+        a = np.ascontiguousarray(leaf_counts, np.int32).ravel()
+        check(self.L.navgpu_amcl_set_kd_leaf_counts(self.h, first, len(a), _p(a)), "amcl_set_kd_leaf_counts")
+
+    def rng_counters(self, first=0, count=None):
+        count = self._count(first, count)
+        a = np.zeros(count, np.uint64)
+        check(self.L.navgpu_amcl_get_rng_counters(self.h, first, count, _p(a)), "amcl_get_rng_counters")
+        return a
+
+    def set_rng_counters(self, counters, first=0):
+        a = np.ascontiguousarray(counters, np.uint64).ravel()
+        check(self.L.navgpu_amcl_set_rng_counters(self.h, first, len(a), _p(a)), "amcl_set_rng_counters")
