@@ -672,7 +672,8 @@ int navgpu_global_planner_plan_wavefront(navgpu_navfn* nav, uint32_t first, uint
  * (navgpu_amcl_laser_configure) serves every filter of the handle.  All arithmetic is fp64 with the reference's operation
  * order; the device's libm (sin / cos / atan2 / exp / log) may differ from the host's by an ulp.  Coordinates are metres,
  * cells are map_t's (origin at the map centre, map.h:139-147).  Resampling, the kd-tree histogram and the cluster statistics
- * run on the device too (navgpu_amcl_update_resample below); the motion model stays with the reference (pf_ran_gaussian). */
+ * run on the device too (navgpu_amcl_update_resample below), and so does the odometry motion model (navgpu_amcl_update_action),
+ * so a filter's set can stay on the device from one cycle to the next. */
 typedef struct navgpu_amcl navgpu_amcl;
 #define NAVGPU_AMCL_MODEL_BEAM 0                     /* laser_model_t, amcl_laser.h:42-48 */
 #define NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD 1
@@ -831,6 +832,52 @@ int navgpu_amcl_get_kd_leaf_counts(navgpu_amcl* amcl, uint32_t first, uint32_t c
 /* The device generator's per-filter call counters (0 at create); with the same seed, counter and set a call repeats its draws. */
 int navgpu_amcl_set_rng_counters(navgpu_amcl* amcl, uint32_t first, uint32_t count, const uint64_t* counters);
 int navgpu_amcl_get_rng_counters(navgpu_amcl* amcl, uint32_t first, uint32_t count, uint64_t* counters);
+
+/* ---- amcl odometry motion model: AMCLOdom::UpdateAction -> pf_update_action ---- */
+#define NAVGPU_AMCL_ODOM_DIFF 0 /* odom_model_t, amcl_odom.h:38-45, same order */
+#define NAVGPU_AMCL_ODOM_OMNI 1
+#define NAVGPU_AMCL_ODOM_DIFF_CORRECTED 2
+#define NAVGPU_AMCL_ODOM_OMNI_CORRECTED 3
+#define NAVGPU_AMCL_ODOM_GAUSSIAN 4
+#define NAVGPU_AMCL_DRAW_DRAND48 2 /* the reference's drand48() stream, regenerated on the device from its state */
+typedef struct {
+  int32_t model_type;                         /* NAVGPU_AMCL_ODOM_*                                                    */
+  int32_t reserved;
+  double alpha1, alpha2, alpha3, alpha4, alpha5; /* SetModel's drift parameters (alpha5: omni and Gaussian only)       */
+} navgpu_amcl_odom_params;
+/* replaces: AMCLOdom::SetModelDiff / SetModelOmni / SetModelGaussian / SetModel (amcl_odom.cpp:68-125).  All or nothing: a
+ * model outside 0..4 or a NaN alpha leaves the previous configuration in force.  Negative alphas are accepted as in the reference:
+ * the uncorrected models then draw with a negative "stddev", the corrected ones with sqrt of a negative (NaN). */
+int navgpu_amcl_odom_configure(navgpu_amcl* amcl, const navgpu_amcl_odom_params* params);
+/* replaces: AMCLOdom::UpdateAction(pf, data) (amcl_odom.cpp:128-379) for every filter of the slice.  odom = count x 9 doubles:
+ * AMCLOdomData's pose[3], delta[3], absolute_motion[3] as amcl_node.cpp:1444-1464 fills them (absolute_motion is read by the
+ * Gaussian model only).  Every sample < sample_count of each filter moves in place; nothing else changes: weights, converged,
+ * w_slow / w_fast, the clusters of the last resample, the kd-tree leaf count (pf_update_action rebuilds no tree, and systematic
+ * resampling sizes from the count "as created") and the entries past sample_count.  theta is not normalised (as in the
+ * reference).  Everything that depends on the odometry alone (delta_rot1 / delta_trans / delta_rot2, the *_noise terms, the
+ * stddevs, angle_diff(atan2(dy, dx), old_theta), normalize(delta_rot1 / delta_rot2)) is computed on the host with the host's
+ * libm in the reference's own expressions; per particle the device's sin / cos / atan2 / log may differ from the host's by an ulp
+ * (angle_diff and normalize are atan2(sin(z), cos(z)), so a 1-ulp difference can wrap a result near +-pi by 2 pi).
+ * A Gaussian deviate is pf_ran_gaussian's (pf_pdf.c:132-146), multiplied left to right as C parses it:
+ *   (sigma * x2) * sqrt(-2.0*log(w)/w).
+ * draw_source NAVGPU_AMCL_DRAW_DRAND48 (parity with the reference): drand48_state[k] is filter k's 48-bit LCG state X, in and
+ *   out (after srand48(s) it is (s & 0xFFFFFFFF) << 16 | 0x330E; the next drand48() is ((0x5DEECE66D X + 0xB) mod 2^48) / 2^48).
+ *   Each filter draws 3 deviates per sample in sample order and in each model's own order (diff: rot1, trans, rot2; omni: trans,
+ *   rot, strafe; Gaussian: trans, strafe, rot): values equal to 0.0 are skipped, the others are paired consecutively as
+ *   (x1, x2) = 2 r - 1, and a pair is accepted when 0 < w = x1*x1 + x2*x2 <= 1.  The state comes back advanced by exactly the
+ *   number of values the reference's loop consumes.  A state >= 2^48 gives status[k] = NAVGPU_ERR_INVALID and leaves that filter
+ *   (and its state) untouched.  seed is not read.
+ * draw_source NAVGPU_AMCL_DRAW_DEVICE: Philox4x32-10 keyed by `seed` (see update_resample), counter {draw, filter | 2 << 16,
+ *   the filter's call counter}: sample i takes the two double pairs (u0, u1) of draw 2 i and (u2, u3) of draw 2 i + 1 (53-bit
+ *   doubles in [0, 1)) and its three deviates, in the model's order, are
+ *     r0 = sqrt(-2 log(1 - u0)), z0 = r0 * cos(2 pi u1), z1 = r0 * sin(2 pi u1), z2 = sqrt(-2 log(1 - u2)) * cos(2 pi u3),
+ *   each used as pf_ran_gaussian's value: sigma * z.  The call counter is the one update_resample uses and goes up by one per
+ *   call for every filter of the slice, so consecutive motion and resample calls never repeat draws.  drand48_state is not read.
+ * Any other draw_source (NAVGPU_AMCL_DRAW_SUPPLIED included) is NAVGPU_ERR_INVALID.  NAVGPU_ERR_STATE before
+ * navgpu_amcl_odom_configure (no map is needed); NAVGPU_ERR_INVALID for a NULL odom or a NULL drand48_state in drand48 mode, and
+ * when any filter failed (the others ran). */
+int navgpu_amcl_update_action(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* odom, int32_t draw_source,
+                              uint64_t* drand48_state, uint64_t seed, int32_t* status);
 
 #ifdef __cplusplus
 }

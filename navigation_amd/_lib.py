@@ -229,6 +229,25 @@ class AmclResampleParams(C.Structure):
             setattr(self, k, v)
 
 
+AMCL_ODOM_DIFF, AMCL_ODOM_OMNI, AMCL_ODOM_DIFF_CORRECTED, AMCL_ODOM_OMNI_CORRECTED, AMCL_ODOM_GAUSSIAN = range(5)
+AMCL_DRAW_DRAND48 = 2
+
+
+class AmclOdomParams(C.Structure):
+    """Mirror of navgpu_amcl_odom_params (include/navgpu.h): odom_model_t and AMCLOdom's alpha1..alpha5.  Defaults: amcl_node's
+    odom_model_type "diff" and odom_alpha1..5 0.2 (amcl_node.cpp)."""
+    _fields_ = [("model_type", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_double) for n in (
+        "alpha1", "alpha2", "alpha3", "alpha4", "alpha5")]
+    DEFAULTS = dict(model_type=AMCL_ODOM_DIFF, reserved=0, alpha1=0.2, alpha2=0.2, alpha3=0.2, alpha4=0.2, alpha5=0.2)
+
+    def __init__(self, **kw):
+        super().__init__()
+        d = dict(self.DEFAULTS)
+        d.update(kw)
+        for k, v in d.items():
+            setattr(self, k, v)
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -344,6 +363,8 @@ SYMBOLS = [
     ("navgpu_amcl_get_kd_leaf_counts", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_amcl_set_rng_counters", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_amcl_get_rng_counters", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_odom_configure", C.c_int, [vp, C.POINTER(AmclOdomParams)]),
+    ("navgpu_amcl_update_action", C.c_int, [vp, u32, u32, vp, i32, vp, C.c_uint64, vp]),
 ]
 
 

@@ -24,30 +24,6 @@ constexpr double kKeyLimit = (double)(kKeyBias - 2);  // |bin| <= 2^20 - 2: the 
 constexpr uint64_t kNoKey = ~0ull;
 constexpr uint32_t kStartDraw = 0xFFFFFFFFu;  // draw index of systematic_sample_start (device draws)
 
-// Philox4x32-10 (Salmon et al., SC'11): counter {draw index, filter | stream << 16, call counter lo, hi}, key = seed
-__device__ __forceinline__ void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-// two doubles in [0, 1) with 53 random bits each
-__device__ __forceinline__ void draw2(const AmclResampleParamsDev& p, uint32_t filter, uint64_t call, uint32_t index, uint32_t stream,
-                                      double& u0, double& u1) {
-  uint32_t c[4] = {index, filter | (stream << 16), (uint32_t)call, (uint32_t)(call >> 32)};
-  philox(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-  const double s = 1.0 / 9007199254740992.0;
-  u0 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6)) * s;
-  u1 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6)) * s;
-}
-
 // AmclNode::randomFreeSpacePose (amcl_node.cpp:1200-1212) with u_cell, u_theta in place of its two drand48() calls
 __device__ bool freePose(const AmclMapDev& m, double u_cell, double u_theta, double* out) {
   if (m.n_free <= 0 || !m.free_cells) return false;
@@ -208,7 +184,7 @@ __global__ __launch_bounds__(kRsThreads) void k_amcl_resample(AmclDev d, AmclRes
       nrand = (int)(w_diff * new_count);
       const int nsys = new_count - nrand;
       double start = F->sys_start, u1;
-      if (dev) draw2(p, f, call, kStartDraw, 0, start, u1);
+      if (dev) draw2(p.seed, f, call, kStartDraw, 0, start, u1);
       if (nsys > 0) {  // nsys == 0 (w_diff == 1): every sample is random and delta = 1 / 0 is never used
         const double delta = 1.0 / nsys;
         double target = start;
@@ -239,7 +215,7 @@ __global__ __launch_bounds__(kRsThreads) void k_amcl_resample(AmclDev d, AmclRes
     for (int k = t; k < M; k += nt) {
       double uf, up;
       if (dev)
-        draw2(p, f, call, k, 0, uf, up);
+        draw2(p.seed, f, call, k, 0, uf, up);
       else
         uf = r.u[(blockIdx.x * (size_t)ms + k) * 2];
       a[k] = uf < w_diff;
@@ -265,7 +241,7 @@ __global__ __launch_bounds__(kRsThreads) void k_amcl_resample(AmclDev d, AmclRes
     } else {
       double uf, up;
       if (dev)
-        draw2(p, f, call, k, 0, uf, up);
+        draw2(p.seed, f, call, k, 0, uf, up);
       else {
         uf = r.u[(blockIdx.x * (size_t)ms + k) * 2];
         up = r.u[(blockIdx.x * (size_t)ms + k) * 2 + 1];
@@ -279,7 +255,7 @@ __global__ __launch_bounds__(kRsThreads) void k_amcl_resample(AmclDev d, AmclRes
     if (random) {
       if (dev) {
         double uc, ut;
-        draw2(p, f, call, k, 1, uc, ut);
+        draw2(p.seed, f, call, k, 1, uc, ut);
         ok = freePose(map, uc, ut, pose);
       } else if (q < F->pool_count) {
         pose[0] = pool[3 * (size_t)q];

@@ -50,6 +50,11 @@ struct navgpu_amcl {
   std::vector<uint64_t> rng_ctr;                // device draws: calls made per filter
   void* d_upload = nullptr;                     // supplied draws of the last call
   size_t upload_bytes = 0;
+  // motion model (navgpu_amcl_update_action); the record workspace is allocated by the first configure
+  navgpu_amcl_odom_params oparams{};
+  bool oconfigured = false;
+  double2* d_records = nullptr;                 // [n][3 max_samples] drand48 Gaussian records {x2, s}
+  AmclOdomFilterDev* d_ofilters = nullptr;      // [n]
   template <class T>
   int alloc(T** p, size_t count) {
     void* q = nullptr;
@@ -659,6 +664,163 @@ int navgpu_amcl_get_clusters(navgpu_amcl* h, uint32_t filter, int32_t* cluster_c
   if (set_mean) std::copy(ss.begin(), ss.begin() + 3, set_mean);
   if (set_cov) std::copy(ss.begin() + 3, ss.end(), set_cov);
   return (size_t)C > capacity ? NAVGPU_ERR_CAPACITY : NAVGPU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// amcl_odom.cpp's normalize / angle_diff (:35-56), evaluated with the host's libm as the reference evaluates them
+double normalizeAngle(double z) { return atan2(sin(z), cos(z)); }
+double angleDiff(double a, double b) {
+  a = normalizeAngle(a);
+  b = normalizeAngle(b);
+  const double d1 = a - b;
+  double d2 = 2 * M_PI - fabs(d1);
+  if (d1 > 0) d2 *= -1.0;
+  if (fabs(d1) < fabs(d2)) return d1;
+  return d2;
+}
+
+// What AMCLOdom::UpdateAction computes from the odometry alone (amcl_odom.cpp:128-379), in its own expressions; the per-particle
+// part is k_amcl_odom.  The diff models evaluate their stddevs inside the sample loop: the same value for every sample.
+void odomConstants(const navgpu_amcl_odom_params& P, const double* o, double* k) {
+  const double* pose = o;
+  const double* delta = o + 3;
+  const double* absm = o + 6;
+  const double old_theta = pose[2] - delta[2];  // pf_vector_sub(ndata->pose, ndata->delta).v[2]
+  const double a1 = P.alpha1, a2 = P.alpha2, a3 = P.alpha3, a4 = P.alpha4, a5 = P.alpha5;
+  std::fill(k, k + kAmclOdomConsts, 0.0);
+  switch (P.model_type) {
+    case NAVGPU_AMCL_ODOM_OMNI:
+    case NAVGPU_AMCL_ODOM_OMNI_CORRECTED: {
+      const double delta_trans = sqrt(delta[0] * delta[0] + delta[1] * delta[1]);
+      const double delta_rot = delta[2];
+      double trans_sd = (a3 * (delta_trans * delta_trans) + a1 * (delta_rot * delta_rot));
+      double rot_sd = (a4 * (delta_rot * delta_rot) + a2 * (delta_trans * delta_trans));
+      double strafe_sd = (a1 * (delta_rot * delta_rot) + a5 * (delta_trans * delta_trans));
+      if (P.model_type == NAVGPU_AMCL_ODOM_OMNI_CORRECTED) {
+        trans_sd = sqrt(trans_sd);
+        rot_sd = sqrt(rot_sd);
+        strafe_sd = sqrt(strafe_sd);
+      }
+      k[0] = angleDiff(atan2(delta[1], delta[0]), old_theta);
+      k[1] = delta_trans;
+      k[2] = delta_rot;
+      k[3] = trans_sd;
+      k[4] = rot_sd;
+      k[5] = strafe_sd;
+      break;
+    }
+    case NAVGPU_AMCL_ODOM_DIFF:
+    case NAVGPU_AMCL_ODOM_DIFF_CORRECTED: {
+      double delta_rot1;
+      if (sqrt(delta[1] * delta[1] + delta[0] * delta[0]) < 0.01)
+        delta_rot1 = 0.0;
+      else
+        delta_rot1 = angleDiff(atan2(delta[1], delta[0]), old_theta);
+      const double delta_trans = sqrt(delta[0] * delta[0] + delta[1] * delta[1]);
+      const double delta_rot2 = angleDiff(delta[2], delta_rot1);
+      const double n1 = std::min(fabs(angleDiff(delta_rot1, 0.0)), fabs(angleDiff(delta_rot1, M_PI)));
+      const double n2 = std::min(fabs(angleDiff(delta_rot2, 0.0)), fabs(angleDiff(delta_rot2, M_PI)));
+      double rot1_sd = a1 * n1 * n1 + a2 * delta_trans * delta_trans;
+      double trans_sd = a3 * delta_trans * delta_trans + a4 * n1 * n1 + a4 * n2 * n2;
+      double rot2_sd = a1 * n2 * n2 + a2 * delta_trans * delta_trans;
+      if (P.model_type == NAVGPU_AMCL_ODOM_DIFF_CORRECTED) {
+        rot1_sd = sqrt(rot1_sd);
+        trans_sd = sqrt(trans_sd);
+        rot2_sd = sqrt(rot2_sd);
+      }
+      k[0] = normalizeAngle(delta_rot1);  // angle_diff(delta_rot1, .)'s first step, the same for every sample
+      k[1] = normalizeAngle(delta_rot2);
+      k[2] = delta_trans;
+      k[3] = rot1_sd;
+      k[4] = trans_sd;
+      k[5] = rot2_sd;
+      break;
+    }
+    default: {  // NAVGPU_AMCL_ODOM_GAUSSIAN
+      const double delta_trans = sqrt(delta[0] * delta[0] + delta[1] * delta[1]);
+      const double delta_rot = delta[2];
+      const double t2 = absm[0] * absm[0], s2 = absm[1] * absm[1], r2 = absm[2] * absm[2];
+      k[0] = angleDiff(atan2(delta[1], delta[0]), old_theta);
+      k[1] = delta_trans;
+      k[2] = delta_rot;
+      k[3] = delta[2] / 2;
+      k[4] = sqrt(a3 * t2 + a4 * r2);  // trans
+      k[5] = sqrt(a4 * r2 + a5 * s2);  // strafe
+      k[6] = sqrt(a1 * r2 + a2 * t2);  // rot
+      break;
+    }
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int navgpu_amcl_odom_configure(navgpu_amcl* h, const navgpu_amcl_odom_params* p) {
+  if (!h || !p) return NAVGPU_ERR_INVALID;
+  if (p->model_type < NAVGPU_AMCL_ODOM_DIFF || p->model_type > NAVGPU_AMCL_ODOM_GAUSSIAN) return NAVGPU_ERR_INVALID;
+  const double v[] = {p->alpha1, p->alpha2, p->alpha3, p->alpha4, p->alpha5};
+  for (double x : v)
+    if (x != x) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  if (!h->d_records) {
+    int rc = 0;
+    if (!rc) rc = h->alloc(&h->d_records, (size_t)h->n * 3 * h->d.max_samples);
+    if (!rc) rc = h->alloc(&h->d_ofilters, h->n);
+    if (rc) return rc;
+    HIP_TRY(waitStream(h->stream));
+  }
+  h->oparams = *p;
+  h->oconfigured = true;
+  return NAVGPU_OK;
+}
+
+int navgpu_amcl_update_action(navgpu_amcl* h, uint32_t first, uint32_t count, const double* odom, int32_t draw_source,
+                              uint64_t* drand48_state, uint64_t seed, int32_t* status) {
+  if (!h || !status || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  if (draw_source != NAVGPU_AMCL_DRAW_DRAND48 && draw_source != NAVGPU_AMCL_DRAW_DEVICE) return NAVGPU_ERR_INVALID;
+  const bool dev = draw_source == NAVGPU_AMCL_DRAW_DEVICE;
+  if (!odom || (!dev && !drand48_state)) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  if (!h->oconfigured) {
+    g_last_error = "navgpu_amcl_update_action before navgpu_amcl_odom_configure";
+    return NAVGPU_ERR_STATE;
+  }
+  std::vector<AmclOdomFilterDev> fd(count);
+  int rc = NAVGPU_OK, max_count = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    AmclOdomFilterDev& e = fd[k];
+    const uint32_t f = first + k;
+    e.sample_count = h->sample_count[f];
+    e.active = 1;
+    e.state = dev ? 0 : drand48_state[k];
+    e.rng_ctr = h->rng_ctr[f];
+    odomConstants(h->oparams, odom + 9 * (size_t)k, e.k);
+    status[k] = NAVGPU_OK;
+    if (!dev && drand48_state[k] > kAmclDrand48Mask) {
+      e.active = 0;
+      status[k] = NAVGPU_ERR_INVALID;
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_update_action: a drand48 state >= 2^48";
+      continue;
+    }
+    max_count = std::max(max_count, e.sample_count);
+  }
+  HIP_TRY(hipMemcpyAsync(h->d_ofilters, fd.data(), sizeof(AmclOdomFilterDev) * count, hipMemcpyHostToDevice, h->stream));
+  if (!dev) launch_amcl_drand48_gauss(h->d_records, h->d.max_samples, count, h->d_ofilters, h->stream);
+  launch_amcl_odom(h->d, h->oparams.model_type, dev ? 1 : 0, seed, h->d_records, first, count, max_count, h->d_ofilters, h->stream);
+  const int lrc = checkLaunch();
+  if (lrc) return lrc;
+  if (!dev) HIP_TRY(hipMemcpyAsync(fd.data(), h->d_ofilters, sizeof(AmclOdomFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  for (uint32_t k = 0; k < count; ++k) {
+    if (dev)
+      ++h->rng_ctr[first + k];
+    else if (fd[k].active)
+      drand48_state[k] = fd[k].state;
+  }
+  return rc;
 }
 
 }  // extern "C"

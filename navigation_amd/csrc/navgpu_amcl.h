@@ -8,6 +8,7 @@
 // Resampling (amcl_resample_kernels.hip) adds a per-filter workspace (AmclResampleDev) and the cluster statistics of the
 // current set: cl_count int32 [n][max_samples], cl_stats double [n][max_samples][13] {weight, mean[3], cov[9]},
 // set_stats double [n][12] {mean[3], cov[9]}.
+// The motion model (amcl_motion_kernels.hip) adds, in drand48 mode, a record workspace: double2 [n][3 max_samples] {x2, s}.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -95,8 +96,54 @@ struct AmclResampleDev {
   double* set_stats;
 };
 
+// Philox4x32-10 (Salmon et al., SC'11): counter {draw index, filter | stream << 16, call counter lo, hi}, key = seed.  Streams:
+// 0 and 1 resampling (amcl_resample_kernels.hip), 2 the motion model (amcl_motion_kernels.hip).
+__device__ __forceinline__ void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+// two doubles in [0, 1) with 53 random bits each
+__device__ __forceinline__ void draw2(uint64_t seed, uint32_t filter, uint64_t call, uint32_t index, uint32_t stream,
+                                      double& u0, double& u1) {
+  uint32_t c[4] = {index, filter | (stream << 16), (uint32_t)call, (uint32_t)(call >> 32)};
+  philox(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const double s = 1.0 / 9007199254740992.0;
+  u0 = ((double)(c[0] >> 5) * 67108864.0 + (double)(c[1] >> 6)) * s;
+  u1 = ((double)(c[2] >> 5) * 67108864.0 + (double)(c[3] >> 6)) * s;
+}
+
 void launch_amcl_resample(const AmclDev& d, const AmclResampleDev& r, const AmclResampleParamsDev& p, uint32_t first, uint32_t count,
                           AmclResampleFilterDev* filters, hipStream_t s);
+
+// One filter of an update_action call (AMCLOdom::UpdateAction, amcl_odom.cpp:128-379).  k[] holds what depends on the odometry
+// alone, computed on the host in the reference's own expressions (navgpu_amcl.cpp, odomConstants):
+//   diff / diff-corrected: {normalize(delta_rot1), normalize(delta_rot2), delta_trans, sd_rot1, sd_trans, sd_rot2}
+//   omni / omni-corrected: {bearing, delta_trans, delta_rot, sd_trans, sd_rot, sd_strafe}
+//   Gaussian:              {bearing, delta_trans, delta_rot, delta.v[2] / 2, sd_trans, sd_strafe, sd_rot}
+// with bearing = angle_diff(atan2(delta.v[1], delta.v[0]), old_pose.v[2]).
+struct AmclOdomFilterDev {
+  int32_t sample_count;
+  int32_t active;        // 0: the filter is skipped (invalid drand48 state)
+  uint64_t state;        // drand48 mode: the 48-bit LCG state, in and out
+  uint64_t rng_ctr;      // device mode: the filter's call counter
+  double k[7];
+};
+
+constexpr int kAmclOdomConsts = 7;
+constexpr uint64_t kAmclDrand48Mask = (1ull << 48) - 1;  // drand48's state is 48 bits
+
+void launch_amcl_drand48_gauss(double2* records, uint32_t max_samples, uint32_t count, AmclOdomFilterDev* filters, hipStream_t s);
+void launch_amcl_odom(const AmclDev& d, int32_t model, int32_t draw_device, uint64_t seed, const double2* records, uint32_t first,
+                      uint32_t count, int max_sample_count, const AmclOdomFilterDev* filters, hipStream_t s);
 
 void launch_amcl_convert(const int8_t* msg, uint32_t width, uint32_t height, int factor, int8_t* occ, int sx, int sy, hipStream_t s);
 void launch_amcl_cspace(const int8_t* occ, int sx, int sy, int radius, double scale, double max_occ_dist, int32_t* g, float* dist,

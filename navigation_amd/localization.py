@@ -8,6 +8,8 @@
   configure_resample pf_set_resample_model and pf_alloc's KLD / convergence parameters
   update_resample    pf_update_resample: resampling, kd-tree histogram, pf_cluster_stats, pf_update_converged (pf.c:222-720)
   clusters           pf_get_cluster_stats / the set's cluster_count and mean / cov
+  configure_odom     AMCLOdom::SetModel*                              (amcl_odom.cpp:68-125)
+  update_action      AMCLOdom::UpdateAction -> pf_update_action: the odometry motion model (amcl_odom.cpp:128-379)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -15,7 +17,8 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import AMCL_DRAW_DEVICE, AMCL_DRAW_SUPPLIED, AMCL_RESAMPLE_SYSTEMATIC, AmclLaserParams, AmclResampleParams, check, lib
+from ._lib import (AMCL_DRAW_DEVICE, AMCL_DRAW_DRAND48, AMCL_DRAW_SUPPLIED, AMCL_RESAMPLE_SYSTEMATIC, AmclLaserParams, AmclOdomParams,
+                   AmclResampleParams, check, lib)
 
 # pf_sample_set_t's clusters and overall statistics: count (C,), weight (C,), mean (C, 3), cov (C, 3, 3), set_mean (3,), set_cov (3, 3)
 AmclClusters = namedtuple("AmclClusters", "count weight mean cov set_mean set_cov")
@@ -23,6 +26,11 @@ AmclClusters = namedtuple("AmclClusters", "count weight mean cov set_mean set_co
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def drand48_state(seed):
+    """drand48's 48-bit state after srand48(seed): the low 32 bits of seed, then 0x330E."""
+    return ((int(seed) & 0xFFFFFFFF) << 16) | 0x330E
 
 
 class AmclLaser:
@@ -219,3 +227,28 @@ class AmclLaser:
     def set_rng_counters(self, counters, first=0):
         a = np.ascontiguousarray(counters, np.uint64).ravel()
         check(self.L.navgpu_amcl_set_rng_counters(self.h, first, len(a), _p(a)), "amcl_set_rng_counters")
+
+    def configure_odom(self, model, alpha1=0.2, alpha2=0.2, alpha3=0.2, alpha4=0.2, alpha5=0.2):
+        """AMCLOdom::SetModel(model, alpha1..alpha5); model: AMCL_ODOM_* (odom_model_t)."""
+        p = AmclOdomParams(model_type=int(model), alpha1=alpha1, alpha2=alpha2, alpha3=alpha3, alpha4=alpha4, alpha5=alpha5)
+        check(self.L.navgpu_amcl_odom_configure(self.h, C.byref(p)), "amcl_odom_configure")
+        self.odom_params = p
+        return p
+
+    def update_action(self, odom, drand48_state=None, seed=None, first=0, raise_on_error=True):
+        """odom: (count, 9) {pose[3], delta[3], absolute_motion[3]} per filter of the slice (AMCLOdomData).
+        drand48_state: (count,) 48-bit states, the reference's drand48() stream (parity); otherwise the device generator with `seed`.
+        -> (status, status[count], the advanced drand48 states or None)"""
+        o = np.ascontiguousarray(odom, np.float64).reshape(-1, 9)
+        count = len(o)
+        st = np.zeros(count, np.int32)
+        if drand48_state is not None:
+            x = np.array(np.broadcast_to(np.asarray(drand48_state, np.uint64), (count,)))  # a copy: the caller's states stay as given
+            rc = self.L.navgpu_amcl_update_action(self.h, first, count, _p(o), AMCL_DRAW_DRAND48, _p(x), 0, _p(st))
+        else:
+            x = None
+            rc = self.L.navgpu_amcl_update_action(self.h, first, count, _p(o), AMCL_DRAW_DEVICE, None,
+                                                  int(0 if seed is None else seed) & (2 ** 64 - 1), _p(st))
+        if raise_on_error:
+            check(rc, "amcl_update_action")
+        return rc, st, x
