@@ -18,16 +18,13 @@ constexpr uint8_t kNoInfo = 255, kLethal = 254, kInscribed = 253, kFree = 0;
 constexpr int kMaxFootprint = 32;
 constexpr int kCareRows = 128, kCareWords = 4;  // bounded wavefronts: extent of the per-robot pocket mask (k_samples)
 #ifndef NAVGPU_SCORE_TAB_THREADS
-#define NAVGPU_SCORE_TAB_THREADS 256  // samples per k_score_tab workgroup (512 with a 52 KB image: 0.523 ms; 256 with 26 KB: 0.516 ms, configs[4] 2.17 -> 1.82 ms)
+#define NAVGPU_SCORE_TAB_THREADS 256  // samples per k_score_sweep workgroup (as for round 2's table kernel - 512 with a 52 KB image: 0.523 ms; 256 with 26 KB: 0.516 ms, configs[4] 2.17 -> 1.82 ms)
 #endif
 #ifndef NAVGPU_SCORE_TAB_LDS_KB
-#define NAVGPU_SCORE_TAB_LDS_KB 14    // first LDS budget tried for a k_score_tab workgroup's image (window + screens + table rows): 3 v_theta rows at configs[2] (26 KB = 9 rows: k_score 0.526 -> 0.506 ms)
+#define NAVGPU_SCORE_TAB_LDS_KB 14    // first LDS budget score_table_rows tries for a k_score_sweep workgroup's image (window + screens + its row group's table rows): 3 v_theta rows at configs[2] (round 2's table kernel, 26 KB = 9 rows: 0.526 -> 0.506 ms)
 #endif
 #ifndef NAVGPU_SCORE_PREP_THREADS
 #define NAVGPU_SCORE_PREP_THREADS 256  // threads of the workgroup that builds a robot's image (k_score_prep_*): alone 512 is 3 us faster, but beside the other stream groups' kernels its 8 waves and 53 KB wait longer for a CU (0.872 -> 0.862 ms per step)
-#endif
-#ifndef NAVGPU_SCORE_TAB_WAVES
-#define NAVGPU_SCORE_TAB_WAVES 6      // waves per SIMD k_score_tab is compiled for (6: 80 registers)
 #endif
 #ifndef NAVGPU_SCORE_THREADS
 #define NAVGPU_SCORE_THREADS 256
@@ -154,18 +151,17 @@ struct PlannerDev {
   uint32_t fp_rcells;         // Chebyshev radius (cells) that contains every footprint cell around the centre cell
   uint8_t fp_halfw[32];       // by |dy| <= fp_rcells: the largest |dx| at which a footprint cell can lie dy rows from the centre cell (a disc, planWindow); 0xFF: no such row
   uint32_t fp_chunk;          // cells of the longest footprint edge (+1): picks the k_score<CHUNK> instantiation
-  uint32_t use_tables, tab_steps, tab_nfp, tab_nth;
+  uint32_t use_tables, tab_steps, tab_nfp, tab_nth;  // use_tables (planWindow): the prep image carries the heading tables and k_score_sweep scores
   // MapGridCostFunction options beyond DWAPlanner's own wiring (navgpu_planner_set_map_grid_options), indexed
   // 0 path, 1 goal, 2 goal_front, 3 alignment: aggregation 0 Last | 1 Sum | 2 Product, sideways shift in metres
   int32_t mg_agg[4];
   double mg_yshift[4];
   int32_t mg_generic;         // any of them set: the scoring launches take the general step (score_body<AGG>)
-  uint32_t tab_rows;          // v_theta rows per row group = rows of the tables a k_score_tab workgroup keeps in LDS
-  uint32_t tab_bytes;         // score_table_bytes(): the tables' share of the LDS image (0 without tables)
+  uint32_t tab_rows;          // v_theta rows per row group = rows of the tables a k_score_sweep workgroup keeps in LDS
+  uint32_t tab_bytes;         // score_table_bytes(): the tables' share of the image k_score_prep_tab builds (set by launch_score for that launch)
   double tab_dt;              // sim_time / tab_steps
   uint8_t* prep;              // [n][prep_stride] LDS image of k_score (window, reach bitmaps, heading tables), built per cycle by k_score_prep*
   uint32_t prep_stride, prep_bytes;
-  // k_score<TABLES>: shared per-(v_theta, step) tables in LDS
   double* sample_cost;        // [n][max_samples] or null
   int32_t* sample_status;     // [n][max_samples] or null
   double* part_cost;          // [n][score_blocks]

@@ -763,7 +763,8 @@ static void planWindow(const navgpu_fleet* f, PlannerDev& pl, const std::vector<
     }
     pl.fp_chunk = (uint32_t)ceil(max_edge / pl.res) + 1;
   }
-  // shared heading tables (k_score<TABLES>): constant velocity + fixed step count only
+  // shared heading tables in the prep image, scored by k_score_sweep: constant velocity + fixed step count only, and no more
+  // steps than the sweep's 7-bit step tag holds (127); everything else is scored by k_score_gen
   uint32_t max_nfp = 0;
   for (uint32_t v : fp_n) max_nfp = std::max(max_nfp, v);
   pl.use_tables = 0;
@@ -772,7 +773,7 @@ static void planWindow(const navgpu_fleet* f, PlannerDev& pl, const std::vector<
     pl.tab_dt = c.sim_time / (int)pl.tab_steps;
     pl.tab_nfp = max_nfp;
     pl.tab_nth = (uint32_t)std::max(c.vth_samples, 2) + 1;
-    pl.tab_rows = pl.tab_steps >= 1 && pl.tab_steps <= pl.max_sim_steps ? score_table_rows(pl, win) : 0;
+    pl.tab_rows = pl.tab_steps >= 1 && pl.tab_steps <= pl.max_sim_steps && pl.tab_steps <= 127 ? score_table_rows(pl, win) : 0;
     if (pl.tab_rows >= 1) pl.use_tables = 1;
   }
 }
@@ -1162,8 +1163,8 @@ int navgpu_planner_configure(navgpu_fleet* f, const navgpu_dwa_config* c) {
   const uint32_t ax = (uint32_t)(std::max(cfg.vx_samples, 2) + 1), ay = (uint32_t)(std::max(cfg.vy_samples, 2) + 1),
                  at = (uint32_t)(std::max(cfg.vth_samples, 2) + 1);
   const uint32_t max_samples = ax * ay * at;
-  // capacity of the per-workgroup partial results: the 256-thread launch, and the table launch's row groups (each
-  // rounds its share up to whole workgroups: at most one more per v_theta value, planner_score*.hip)
+  // capacity of the per-workgroup partial results: the 256-thread launch, and the sweep launch's row groups (each
+  // rounds its share up to whole workgroups: at most one more per v_theta value, planner_score_sweep.hip)
   const uint32_t score_blocks = 2 * ((max_samples + std::min(kScoreThreads, NAVGPU_SCORE_TAB_THREADS) - 1) / std::min(kScoreThreads, NAVGPU_SCORE_TAB_THREADS)) + at + 2;
   // All-or-nothing (the threading contract of navgpu.h: a reconfigure that fails leaves the previous configuration in force, and
   // the control thread may run the next cycle on it): the new configuration is put together in a COPY of the planner state, its

@@ -5,20 +5,19 @@
 
 namespace navgpu {
 
-// TABLES (use_dwa && discretize_by_time): the heading sequence theta_k of a sample depends only on its
-// v_theta and the step (theta += v_theta*dt, rounded to float each step), so sincos(theta_k),
-// sincos(pi/2+theta_k), the rotated footprint vertices and the forward-point offset are computed once
-// per (v_theta sample, step) by the workgroup into LDS and shared by all (vx, vy) samples, and lanes
-// are mapped so that a wave shares one v_theta: identical edge shapes => convergent Bresenham loops.
-// The arithmetic per value is unchanged (same operations, same rounding), only deduplicated.
+// TABLES (use_tables: use_dwa && discretize_by_time, k_score_prep_tab only): the heading sequence theta_k of a sample
+// depends only on its v_theta and the step (theta += v_theta*dt, rounded to float each step), so sincos(theta_k),
+// sincos(pi/2+theta_k) and the rotated footprint vertices are computed once per (v_theta sample, step) into the robot's
+// image, and k_score_sweep shares them among all (vx, vy) samples.  The arithmetic per value is unchanged (same
+// operations, same rounding), only deduplicated.
 __host__ __device__ inline size_t score_bits_bytes(int win) {  // [win][nw][4] words (part of the LDS image), 16-byte aligned
   return (((size_t)4 * win * ((win + 31) >> 5) * 4) + 15) & ~(size_t)15;
 }
 // the two [win][nw][2] word arrays the dilation passes work in: behind the image, only where the image is BUILT (PREP != 2)
 __host__ __device__ inline size_t score_scratch_bytes(int win) { return score_bits_bytes(win); }
-// PREP: 0 = build the LDS image (window, bitmaps, tables) in this workgroup; 1 = build it and store it to
-// pl.prep (k_score_prep*, one workgroup per robot); 2 = load the stored image (the scoring workgroups of
-// a robot all use the same one: 74 of them in the 32x32x16 configuration)
+// PREP: 0 = build the LDS image (window, bitmaps) in this workgroup (k_score_explicit*); 1 = build it and store it to
+// pl.prep (k_score_prep*, one workgroup per robot; with TABLES the tables too); 2 = load the stored image (the k_score_gen
+// workgroups of a robot all use the same one)
 // CHUNK: cells of a footprint edge fetched per LDS round trip; the launcher picks the smallest of 6 / 9 / 12 / 16 that
 // covers the longest edge (a 0.4 m square at 0.05 m: 9), longer edges take several chunks
 // AGG: the MapGridCostFunction options DWAPlanner itself never sets - aggregation Sum / Product and a sideways shift
@@ -44,7 +43,7 @@ __host__ __device__ inline uint32_t score_prep_reject_bytes(const PlannerDev& pl
 __host__ __device__ inline uint32_t score_prep_reject_offset(const PlannerDev& pl) { return pl.prep_stride - score_prep_reject_bytes(pl); }
 size_t score_table_row_bytes(const PlannerDev& pl);
 size_t score_table_lds_bytes(const PlannerDev& pl);
-// k_score_sweep (planner_score_sweep.hip): the launch for use_dwa && discretize_by_time with DWAPlanner's own MapGrid options
+// k_score_sweep (planner_score_sweep.hip): the launch for use_tables with DWAPlanner's own MapGrid options
 bool score_sweep_applies(const PlannerDev& pl);
 uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s);  // returns blocks per instance
 

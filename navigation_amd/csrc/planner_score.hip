@@ -39,6 +39,7 @@ __device__ unsigned long long g_prep_stats[16];
 #endif
 template <bool EXPLICIT, bool TABLES, int THREADS, int PREP = 0, int CHUNK = 12, bool AGG = false>
 __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first, const float* explicit_sample) {
+  static_assert(!TABLES || PREP == 1, "the tables are built into a stored image only (k_score_prep_tab)");
   extern __shared__ __align__(16) uint8_t s_dyn[];
   uint8_t* s_win = s_dyn;
   __shared__ double s_fp[2 * kMaxFootprint];
@@ -257,36 +258,15 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
       if (cc >= 254) s_win[i] = cc ^ 1u;
     }
   }
-  // ---- TABLES: per-(v_theta sample, step) heading, trig, rotated footprint, forward-point offset
-  const int K = TABLES ? (int)pl.tab_steps : 0;
-  const int tnfp = TABLES ? (int)pl.tab_nfp : 0;
-  const int nth_s = TABLES ? cnt[2] : 0;
-  // rows of the tables in LDS: all tab_nth where they are built (PREP 1); the scoring launch (PREP 2) keeps only the
-  // tab_rows v_theta rows of its workgroup's row group (see the lane mapping below)
-  const int lrows = TABLES ? (PREP == 2 ? (int)pl.tab_rows : (int)pl.tab_nth) : 0;
-  double* s_trig = reinterpret_cast<double*>(s_dyn + win_bytes + score_bits_bytes(win));  // [rows][K][4] cs, sn, cs2, sn2
-  double* s_rot = s_trig + (size_t)lrows * K * 4;                                 // [rows][K][tnfp][2]
-  float* s_th = reinterpret_cast<float*>(s_rot + (size_t)lrows * K * tnfp * 2);       // [rows][K]
-  // TABLES lane mapping.  Lanes are v_theta-major so that a wave shares one heading sequence.  The v_theta rows are cut
-  // into groups of tab_rows (what the LDS budget holds: all of them for configs[2]'s 17, 17 of configs[4]'s 33); a
-  // group takes bpg consecutive workgroups, which enumerate its rows x (vx, vy) pairs.  Blocks past the last group idle.
-  int t_row_base = 0, t_rows = 0, t_li0 = 0;
-  if (TABLES && PREP == 2) {
-    const int nxy = max(cnt[0] * cnt[1], 1), R = (int)pl.tab_rows;
-    const int bpg = (nxy * R + (int)blockDim.x - 1) / (int)blockDim.x;
-    const int gi = (int)blockIdx.x / bpg;
-    t_row_base = gi * R;
-    t_rows = min(max(cnt[2] - t_row_base, 0), R);
-    t_li0 = ((int)blockIdx.x - gi * bpg) * (int)blockDim.x;
-    if (t_li0 >= t_rows * nxy) {  // no sample for this workgroup (the last group's share is rounded up to the largest): no image either
-      if (tid == 0) {
-        pl.part_cost[(size_t)inst * pl.score_blocks + blockIdx.x] = 1.0e300;
-        pl.part_index[(size_t)inst * pl.score_blocks + blockIdx.x] = 0x7FFFFFFF;
-      }
-      return;
-    }
-  }
-  if (TABLES && PREP != 2) {
+  // ---- TABLES: per-(v_theta sample, step) heading, trig and rotated footprint, all tab_nth v_theta rows
+  if (TABLES) {
+    const int K = (int)pl.tab_steps;
+    const int tnfp = (int)pl.tab_nfp;
+    const int nth_s = cnt[2];
+    const int lrows = (int)pl.tab_nth;
+    double* s_trig = reinterpret_cast<double*>(s_dyn + win_bytes + score_bits_bytes(win));  // [rows][K][4] cs, sn, cs2, sn2
+    double* s_rot = s_trig + (size_t)lrows * K * 4;                                 // [rows][K][tnfp][2]
+    float* s_th = reinterpret_cast<float*>(s_rot + (size_t)lrows * K * tnfp * 2);       // [rows][K]
     __syncthreads();  // s_axis, s_fp staged
     PREP_STAMP(4);  // MapGrid screens (+ walk-order swap)
     const double dt_t = c.sim_time / K;
@@ -400,50 +380,13 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
       }
       return;
     }
-    if (!TABLES) {
-      for (uint32_t i = tid; i < n16; i += blockDim.x) lds[i] = img[i];
-      if (PREP == 2) {
-        if (tid < 2 * nfp) s_fp[tid] = pre_fp;
+    // PREP 2: the stored image, and the footprint / axis samples loaded into registers above
+    for (uint32_t i = tid; i < n16; i += blockDim.x) lds[i] = img[i];
+    if (tid < 2 * nfp) s_fp[tid] = pre_fp;
 #pragma unroll
-        for (int u = 0; u < kAxisChunks; ++u) {
-          const uint32_t i = tid + (uint32_t)u * THREADS;
-          if (i < 3u * kMaxAxis) s_axis[i / kMaxAxis][i % kMaxAxis] = pre_axis[u];
-        }
-      }
-    } else {
-      // window + screens, and of the tables only the v_theta rows this workgroup's samples use (lanes are
-      // v_theta-major: 512 lanes of a 33 x 33 (vx, vy) grid span two of the 17 rows), at their usual place
-      // r0..r1: rows of the group (relative to its first) that this workgroup's lanes use
-      const int nxy = max(cnt[0] * cnt[1], 1), last = max(t_rows, 1) - 1;
-      const int r0 = min(t_li0 / nxy, last);
-      const int r1 = min((t_li0 + (int)blockDim.x - 1) / nxy, last);
-      const int n16w = (int)((win_bytes + score_bits_bytes(win)) >> 4);
-      const int ncopy = t_rows > 0 ? r1 - r0 + 1 : 0;                // (a workgroup past the last row group has no rows)
-      const int n_trig = ncopy * K * 2, n_rot = ncopy * K * tnfp;  // 32 B per entry, 16 B per vertex
-      const int l_trig = n16w + r0 * K * 2, g_trig = n16w + (t_row_base + r0) * K * 2;
-      const int l_rot = n16w + lrows * K * 2 + r0 * K * tnfp, g_rot = n16w + (int)pl.tab_nth * K * 2 + (t_row_base + r0) * K * tnfp;
-      const int n16t = n16w + n_trig + n_rot;
-      const float* g_th = reinterpret_cast<const float*>(img + n16w + (size_t)pl.tab_nth * K * (2 + tnfp)) + t_row_base * K;
-      auto srcOf = [&](int i) { return i < n16w ? i : (i < n16w + n_trig ? g_trig + (i - n16w) : g_rot + (i - n16w - n_trig)); };
-      auto dstOf = [&](int i) { return i < n16w ? i : (i < n16w + n_trig ? l_trig + (i - n16w) : l_rot + (i - n16w - n_trig)); };
-      constexpr int kBatch = 4;  // 16-byte loads a lane has in flight (4 x 256 lanes x 16 B = 16 KB: a configs[2] image whole)
-      uint4 v[kBatch];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u) v[u] = img[srcOf(min((int)tid + u * THREADS, n16t - 1))];
-      const int th_i = r0 * K + (int)tid, th_n = (r0 + ncopy) * K;
-      const float th_v = g_th[min(th_i, max(th_n - 1, 0))];
-#pragma unroll
-      for (int u = 0; u < kBatch; ++u)
-        if ((int)tid + u * THREADS < n16t) lds[dstOf((int)tid + u * THREADS)] = v[u];
-      if (th_i < th_n) s_th[th_i] = th_v;
-      if (tid < 2 * nfp) s_fp[tid] = pre_fp;
-#pragma unroll
-      for (int u = 0; u < kAxisChunks; ++u) {
-        const uint32_t i = tid + (uint32_t)u * THREADS;
-        if (i < 3u * kMaxAxis) s_axis[i / kMaxAxis][i % kMaxAxis] = pre_axis[u];
-      }
-      for (int i = (int)tid + kBatch * THREADS; i < n16t; i += blockDim.x) lds[dstOf(i)] = img[srcOf(i)];  // larger images: the rest
-      for (int i = th_i + (int)blockDim.x; i < th_n; i += blockDim.x) s_th[i] = g_th[i];
+    for (int u = 0; u < kAxisChunks; ++u) {
+      const uint32_t i = tid + (uint32_t)u * THREADS;
+      if (i < 3u * kMaxAxis) s_axis[i / kMaxAxis][i % kMaxAxis] = pre_axis[u];
     }
     __syncthreads();
   }
@@ -487,20 +430,9 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
   };
   const uint8_t fail_span = (pl.cfg.allow_unknown != 0) ? 0 : 1;  // pointCost: 254, and 255 unless allow_unknown
 
-  // lane -> sample slot.  TABLES: v_theta-major so that a wave shares one heading sequence; the slot
-  // index (x-outer, y, theta-inner, as the reference enumerates) is what results are keyed by.
-  const int lin = blockIdx.x * blockDim.x + tid;
-  bool in_range = lin < n_samples;
-  int sidx = lin, t_ith = 0, t_r = 0, t_row = 0;
-  if (TABLES) {
-    const int nxy = max(cnt[0] * cnt[1], 1);
-    const int li = t_li0 + (int)tid;
-    t_row = divSmall(li, nxy);   // row within the group = row of the tables in LDS
-    t_r = li - t_row * nxy;      // index of the (vx, vy) pair, x-outer
-    t_ith = t_row_base + t_row;
-    in_range = n_samples > 0 && t_row < t_rows;
-    sidx = t_r * cnt[2] + t_ith;
-  }
+  // lane -> sample slot: the slot index (x-outer, y, theta-inner, as the reference enumerates) is what results are keyed by
+  const int sidx = blockIdx.x * blockDim.x + tid;
+  const bool in_range = sidx < n_samples;
   double total = -1.0;
   int status = NAVGPU_SAMPLE_REJECTED;
 
@@ -512,17 +444,10 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
       vs[2] = explicit_sample[2];
     } else {
       const int nth = cnt[2], nyv = cnt[1];
-      int ix, iy, ith;
-      if (TABLES) {  // sidx = (ix * nyv + iy) * nth + ith with ith = t_ith: one division instead of two
-        ix = divSmall(t_r, nyv);
-        iy = t_r - ix * nyv;
-        ith = t_ith;
-      } else {
-        ix = sidx / (nyv * nth);
-        const int rem = sidx - ix * (nyv * nth);
-        iy = rem / nth;
-        ith = rem - iy * nth;
-      }
+      const int ix = sidx / (nyv * nth);
+      const int rem = sidx - ix * (nyv * nth);
+      const int iy = rem / nth;
+      const int ith = rem - iy * nth;
       vs[0] = s_axis[0][ix];
       vs[1] = s_axis[1][iy];
       vs[2] = s_axis[2][ith];
@@ -536,9 +461,7 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     int num_steps = 0;
     if (!reject) {
       double ns;
-      if (TABLES) {
-        ns = (double)K;  // = ceil(sim_time / sim_granularity), evaluated once on the host (the tables exist for discretize_by_time only)
-      } else if (c.discretize_by_time) {
+      if (c.discretize_by_time) {
         ns = ceil(c.sim_time / c.sim_granularity);
       } else {
         double sim_time_distance = vmag * c.sim_time;
@@ -557,8 +480,8 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     }
     if (!reject) {
       status = NAVGPU_SAMPLE_SCORED;
-      const double dt = TABLES ? pl.tab_dt : c.sim_time / num_steps;  // (tab_dt = sim_time / tab_steps, the same division, once on the host)
-      const bool continued = TABLES ? false : !c.use_dwa;  // (the tables exist for use_dwa only)
+      const double dt = c.sim_time / num_steps;
+      const bool continued = !c.use_dwa;
       float px = st.pos[0], py = st.pos[1], pth = st.pos[2];
       float lv[3] = {vs[0], vs[1], vs[2]};
       const float acc[3] = {(float)c.acc_lim_x, (float)c.acc_lim_y, (float)c.acc_lim_theta};
@@ -628,16 +551,9 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
       } else {
         for (int step = 0; step < num_steps; ++step) {
           if (first_fail <= min_order) break;
-          const int te = TABLES ? t_row * K + step : 0;
-          if (TABLES) pth = s_th[te];
           const double x = px, y = py, th = pth;
           double sn, cs;
-          if (TABLES) {
-            cs = s_trig[4 * te];
-            sn = s_trig[4 * te + 1];
-          } else {
-            sincos(th, &sn, &cs);
-          }
+          sincos(th, &sn, &cs);
           uint32_t cx = 0, cy = 0;
           const bool ok_c = w2m(x, y, cx, cy);
           // ---- screen: on every point but the last a critic can only FAIL (its value is overwritten: aggregation
@@ -658,12 +574,7 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
             lv[2] = t1[2];
           }
           double sn2 = 0.0, cs2 = 0.0;
-          if (TABLES) {
-            cs2 = s_trig[4 * te + 2];
-            sn2 = s_trig[4 * te + 3];
-          } else if (lv[1] != 0.0f) {
-            sincos(M_PI_2 + th, &sn2, &cs2);
-          }
+          if (lv[1] != 0.0f) sincos(M_PI_2 + th, &sn2, &cs2);
           // (rollout_trig 1: cos(pos[2]) names the float function and vel[0] * cos(pos[2]) is a float product - navgpu.h; its value is
           // taken as the double function's, rounded to float)
           const double tx = c.rollout_trig ? (double)(lv[0] * (float)cs) : lv[0] * cs, ty = c.rollout_trig ? (double)(lv[0] * (float)sn) : lv[0] * sn;
@@ -735,15 +646,8 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
                 for (uint32_t v = 0; v <= nfp && !bad; ++v) {
                   int vx, vy;
                   if (v < nfp) {
-                    double wx, wy;
-                    if (TABLES) {
-                      wx = x + s_rot[(te * tnfp + v) * 2];
-                      wy = y + s_rot[(te * tnfp + v) * 2 + 1];
-                    } else {
-                      const double sx = s_fp[2 * v], sy = s_fp[2 * v + 1];
-                      wx = x + (sx * cs - sy * sn);
-                      wy = y + (sx * sn + sy * cs);
-                    }
+                    const double sx = s_fp[2 * v], sy = s_fp[2 * v + 1];
+                    const double wx = x + (sx * cs - sy * sn), wy = y + (sx * sn + sy * cs);
                     uint32_t ux, uy;
                     if (!w2m(wx, wy, ux, uy)) {
                       bad = true;
@@ -1035,14 +939,7 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
   }
 }
 
-// three entry points over the same body: the table variant is compiled for 6 waves/SIMD (80 VGPRs) in 256-thread
-// workgroups whose image (window + screens + the v_theta rows of their row group) stays below 26 KB: 6 per CU = 24 waves
-constexpr int kScoreThreadsTab = NAVGPU_SCORE_TAB_THREADS;
 constexpr int kScorePrepThreads = NAVGPU_SCORE_PREP_THREADS;  // the workgroup that builds a robot's image
-template <int CHUNK>
-__global__ __launch_bounds__(kScoreThreadsTab, NAVGPU_SCORE_TAB_WAVES) void k_score_tab(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  score_body<false, true, kScoreThreadsTab, 2, CHUNK>(pl, first, explicit_sample);
-}
 template <int CHUNK>
 __global__ __launch_bounds__(kScoreThreads) void k_score_gen(PlannerDev pl, uint32_t first, const float* explicit_sample) {
   score_body<false, false, kScoreThreads, 2, CHUNK>(pl, first, explicit_sample);
@@ -1071,7 +968,7 @@ size_t score_table_row_bytes(const PlannerDev& pl) { return (size_t)pl.tab_steps
 size_t score_table_bytes(const PlannerDev& pl) {  // all v_theta rows: the image k_score_prep_tab builds
   return ((size_t)pl.tab_nth * score_table_row_bytes(pl) + 15) & ~(size_t)15;
 }
-size_t score_table_lds_bytes(const PlannerDev& pl) {  // the tab_rows rows of one row group: what a k_score_tab workgroup holds
+size_t score_table_lds_bytes(const PlannerDev& pl) {  // the tab_rows rows of one row group: what a k_score_sweep workgroup holds
   return ((size_t)pl.tab_rows * score_table_row_bytes(pl) + 15) & ~(size_t)15;
 }
 // v_theta rows per row group and the LDS budget they were sized for; 0 = no tables.  A workgroup's image (window +
@@ -1095,11 +992,8 @@ size_t score_prep_slot_bytes(const PlannerDev& pl) {  // a robot's slot of pl.pr
 }
 uint32_t launch_score(const PlannerDev& pl_in, uint32_t first, uint32_t count, const float* explicit_sample, hipStream_t s) {
   PlannerDev pl = pl_in;
-  // A/B switch for the per-(v_theta, step) tables (tools/probe_score.py)
-  if (NAVGPU_DEBUG_ENV("NAVGPU_DEBUG_NO_TABLES") && atoi(NAVGPU_DEBUG_ENV("NAVGPU_DEBUG_NO_TABLES"))) pl.use_tables = 0;  // tool builds only
   const size_t win_bytes = score_window_bytes(pl.win);
   const size_t scratch = score_scratch_bytes((int)pl.win);  // only where the image is built
-  pl.tab_bytes = 0;
   if (explicit_sample) {
     const size_t lds_x = win_bytes + scratch;
     if (pl.mg_generic) {
@@ -1111,32 +1005,18 @@ uint32_t launch_score(const PlannerDev& pl_in, uint32_t first, uint32_t count, c
     hipLaunchKernelGGL(k_score_explicit, dim3(1, count), dim3(kScoreThreads), lds_x, s, pl, first, explicit_sample);
     return 1;
   }
-  if (pl.mg_generic) pl.use_tables = 0;  // (the general step has no table variant)
-  pl.prep_bytes = (uint32_t)score_prep_bytes(pl);  // (after the debug override of use_tables)
-  if (pl.use_tables) {
-    // the prep launch builds all rows (its LDS holds the whole image); a scoring workgroup holds one row group
+  if (score_sweep_applies(pl)) {
+    // the prep launch builds all table rows (its LDS holds the whole image); a sweep workgroup loads one row group
     pl.tab_bytes = (uint32_t)score_table_bytes(pl);
+    pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
     const size_t lds_prep = win_bytes + score_table_bytes(pl) + scratch;
     if (lds_prep > 48 * 1024) hipFuncSetAttribute((const void*)k_score_prep_tab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep);
     hipLaunchKernelGGL(k_score_prep_tab, dim3(1, count), dim3(kScorePrepThreads), lds_prep, s, pl, first);
-    pl.tab_bytes = (uint32_t)score_table_lds_bytes(pl);
-    if (score_sweep_applies(pl) && !NAVGPU_DEBUG_ENV("NAVGPU_DEBUG_NO_SWEEP")) return launch_score_sweep(pl, first, count, s);
-    const size_t lds = win_bytes + score_table_lds_bytes(pl);
-    // row groups x workgroups per group, for the largest (vx, vy) grid the configuration can produce
-    const uint32_t max_nxy = pl.max_samples / std::max(pl.tab_nth, 1u), groups = (pl.tab_nth + pl.tab_rows - 1) / pl.tab_rows;
-    const uint32_t blocks = std::min(groups * ((max_nxy * pl.tab_rows + kScoreThreadsTab - 1) / kScoreThreadsTab), pl.score_blocks);
-#define NAVGPU_SCORE_TAB(C)                                                                                              \
-  {                                                                                                                      \
-    if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k_score_tab<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(k_score_tab<C>, dim3(blocks, count), dim3(kScoreThreadsTab), lds, s, pl, first, explicit_sample);  \
+    return launch_score_sweep(pl, first, count, s);
   }
-    if (pl.fp_chunk <= 6) NAVGPU_SCORE_TAB(6)
-    else if (pl.fp_chunk <= 9) NAVGPU_SCORE_TAB(9)
-    else if (pl.fp_chunk <= 12) NAVGPU_SCORE_TAB(12)
-    else NAVGPU_SCORE_TAB(16)
-#undef NAVGPU_SCORE_TAB
-    return blocks;
-  }
+  // the general path (no tables, or mg_generic: the general step has no table variant)
+  pl.use_tables = 0;
+  pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
   const uint32_t gen_blocks = (pl.max_samples + kScoreThreads - 1) / kScoreThreads;  // (score_blocks is the capacity of the partial results)
   if (win_bytes + scratch > 48 * 1024) hipFuncSetAttribute((const void*)k_score_prep_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(win_bytes + scratch));
   hipLaunchKernelGGL(k_score_prep_gen, dim3(1, count), dim3(kScoreThreads), win_bytes + scratch, s, pl, first);

@@ -12,7 +12,7 @@
 // Why two phases.  One lane rolls one sample out.  89 % of the trajectory points pass the per-cell screens of the robot's
 // LDS image (planner_score.hip builds it: nothing in reach of the footprint can fail, the path / goal grids hold a distance
 // here) in ~60 vector instructions; the others have to walk the footprint's outline through the costmap window, ~1 000
-// instructions with a few dozen dependent LDS round trips.  Walked where they come up (rounds 1-3: k_score_tab), a wave pays
+// instructions with a few dozen dependent LDS round trips.  Walked where they come up (rounds 1-3, as k_score_gen does), a wave pays
 // for a walk whenever one of its lanes needs one - 11 % of the wave-steps, at 57 % lane density - and its 20 steps are serial.
 // Here the sweep only DECIDES: a point that needs its footprint walked is appended to a queue in LDS (pose, owner lane, step)
 // and the lane moves on.  Every kSweepBlockSteps steps the workgroup meets, all 256 lanes take queue entries - whoever
@@ -27,6 +27,7 @@
 namespace navgpu {
 
 constexpr int kSweepThreads = NAVGPU_SCORE_TAB_THREADS;
+constexpr int kSweepWaves = 6;  // waves per SIMD k_score_sweep is compiled for (6: 80 registers)
 #ifndef NAVGPU_SWEEP_BLOCK_STEPS
 #define NAVGPU_SWEEP_BLOCK_STEPS 4  // A/B over 3..5 x 512..1024 on configs[2] and configs[4]: tools/ab_variants.sh, tools/ab_configs4.sh
 #endif
@@ -58,7 +59,7 @@ __device__ unsigned long long g_sweep_stats[16];
 // TRIGF: navgpu_dwa_config::rollout_trig = 1 - computeNewPositions' cos(pos[2]) / sin(pos[2]) name the float functions and
 // vel[0] * cos(pos[2]) is a float product (its value: the table's double, rounded to float)
 template <int CHUNK, bool TRIGF>
-__global__ __launch_bounds__(kSweepThreads, NAVGPU_SCORE_TAB_WAVES) void k_score_sweep(PlannerDev pl, uint32_t first) {
+__global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(PlannerDev pl, uint32_t first) {
   constexpr int THREADS = kSweepThreads;
   extern __shared__ __align__(16) uint8_t s_dyn[];
   uint8_t* s_win = s_dyn;
@@ -747,14 +748,17 @@ __global__ __launch_bounds__(kSweepThreads, NAVGPU_SCORE_TAB_WAVES) void k_score
 #endif
 }
 
-// The sweep takes every launch of the table variant (use_dwa, discretize_by_time, DWAPlanner's own MapGrid options): its tags
-// hold 10 bits of lane, 7 of step and 14 of table row.
+// The sweep takes every launch with tables (use_tables: use_dwa, discretize_by_time, at most 127 steps - planWindow) and
+// DWAPlanner's own MapGrid options.  Its tags hold 10 bits of lane, 7 of step and 14 of table row (tab_rows <= tab_nth <= 128:
+// navgpu_configure_planner's max_axis).  The capacity check always holds: groups * ceil(nxy * R / 256) <= 2 * ceil(max_samples
+// / 256) + at + 2 = score_blocks, since groups * R < tab_nth + R <= 2 * tab_nth and groups <= tab_nth = at.
+static_assert(kSweepThreads <= 1024, "10 bits of lane in the walk queue's tags");
 static uint32_t score_sweep_blocks(const PlannerDev& pl) {
   const uint32_t max_nxy = pl.max_samples / std::max(pl.tab_nth, 1u), groups = (pl.tab_nth + std::max(pl.tab_rows, 1u) - 1) / std::max(pl.tab_rows, 1u);
   return groups * ((max_nxy * pl.tab_rows + kSweepThreads - 1) / kSweepThreads);
 }
 bool score_sweep_applies(const PlannerDev& pl) {
-  return pl.use_tables && !pl.mg_generic && score_sweep_blocks(pl) <= pl.score_blocks && pl.tab_steps >= 1 && pl.tab_steps <= 127 && pl.tab_rows < (1u << 14) && kSweepThreads <= 1024;
+  return pl.use_tables && !pl.mg_generic && score_sweep_blocks(pl) <= pl.score_blocks;
 }
 uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) {
   const size_t lds = score_window_bytes(pl.win) + score_table_lds_bytes(pl);

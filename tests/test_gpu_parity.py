@@ -257,13 +257,14 @@ def _inflated_instance(orc, n, idx, synth):
 
 
 def _check_planner(nav, orc, n, cfg_kw, n_inst=2, footprint=None, allow_unknown=1, unknown_frac=0.0, cycles=1, seed0=0,
-                   plan_len=None, near_obstacles=0, map_grid_options=()):
+                   plan_len=None, near_obstacles=0, map_grid_options=(), max_sim_steps=128):
     from navigation_amd import synth
     N = L(nav)
     fp = synth.FOOTPRINT if footprint is None else footprint
     cfg = nav.DwaConfig(allow_unknown=allow_unknown, **cfg_kw)
     ocfg = orc.DwaConfig(**cfg.as_dict())
-    fl = nav.Fleet(n_inst, n, n, synth.RES, layers=N.LAYER_OBSTACLE, keep_sample_costs=True, max_sim_steps=128, max_plan=256)
+    fl = nav.Fleet(n_inst, n, n, synth.RES, layers=N.LAYER_OBSTACLE, keep_sample_costs=True, max_sim_steps=max_sim_steps,
+                   max_plan=256)
     fl.configure_planner(cfg)
     fl.set_footprint(fp)
     insts = [_inflated_instance(orc, n, seed0 + i, synth) for i in range(n_inst)]
@@ -361,6 +362,14 @@ def test_planner_sum_scores_and_zero_scales(nav, orc):
                                        discretize_by_time=1, sum_scores=1, occdist_scale=0.02), n_inst=2, seed0=20)
     _check_planner(nav, orc, 160, dict(vx_samples=6, vy_samples=5, vth_samples=7, sim_time=1.2, sim_granularity=0.1,
                                        discretize_by_time=1, occdist_scale=0.0, forward_point_distance=0.0), n_inst=2, seed0=22)
+
+
+def test_planner_tables_more_than_127_steps(nav, orc):
+    # use_dwa + discretize_by_time with 150 steps: more than k_score_sweep's 7-bit step tag holds, so the general kernel
+    # scores it.  A 4-vertex footprint and 4 v_theta rows keep the heading tables within the prep image's LDS budget, i.e.
+    # the configuration is one the tables would otherwise cover.
+    _check_planner(nav, orc, 160, dict(vx_samples=6, vy_samples=5, vth_samples=3, sim_time=1.5, sim_granularity=0.01,
+                                       discretize_by_time=1), n_inst=2, seed0=30, cycles=2, near_obstacles=6, max_sim_steps=160)
 
 
 def test_planner_oscillation_flags_persist(nav, orc):
