@@ -156,7 +156,7 @@ struct PlannerDev {
   // 0 path, 1 goal, 2 goal_front, 3 alignment: aggregation 0 Last | 1 Sum | 2 Product, sideways shift in metres
   int32_t mg_agg[4];
   double mg_yshift[4];
-  int32_t mg_generic;         // any of them set: the scoring launches take the general step (score_body<AGG>)
+  int32_t mg_generic;         // any of them set: the scoring launches take the general step (scoreSamples<..., AGG>)
   uint32_t tab_rows;          // v_theta rows per row group = rows of the tables a k_score_sweep workgroup keeps in LDS
   uint32_t tab_bytes;         // score_table_bytes(): the tables' share of the image k_score_prep_tab builds (set by launch_score for that launch)
   double tab_dt;              // sim_time / tab_steps

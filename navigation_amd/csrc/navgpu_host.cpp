@@ -1368,7 +1368,7 @@ int navgpu_planner_wavefront_boxes(navgpu_fleet* f, uint32_t first, uint32_t cou
   return NAVGPU_OK;
 }
 
-#ifdef NAVGPU_SCORE_STATS  // experiment builds only: the LDS image k_score_prep* stored for one robot
+#ifdef NAVGPU_DEBUG_SWITCHES  // tool builds only (tools/probe_goal_window.py): the LDS image k_score_prep* stored for one robot
 extern "C" int navgpu_debug_prep_image(navgpu_fleet* f, uint32_t inst, uint8_t* out, uint32_t cap, uint32_t* win, uint32_t* bytes) {
   waitStream(f->stream);
   const uint32_t n = std::min<uint32_t>(cap, f->pl.prep_stride);

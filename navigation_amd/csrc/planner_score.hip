@@ -21,136 +21,110 @@ namespace navgpu {
 // The costmap window the trajectories can reach is staged in LDS; cells outside it (never needed
 // with a correctly sized window) fall back to a global load, so results never depend on it.
 // ------------------------------------------------------------------------------------------------
-#if defined(NAVGPU_SCORE_TIMING) && !defined(NAVGPU_SCORE_STATS)  // phase stamps only (no counters in the loop)
-__device__ unsigned long long g_score_stats[24];
-#endif
-#ifdef NAVGPU_SCORE_STATS  // experiment builds only (make EXTRA=-DNAVGPU_SCORE_STATS, tools/probe_score_stats.py)
-__device__ unsigned long long g_score_stats[24];  // lane-steps, unscreened lanes, wave-steps, waves with an unscreened lane, walk lanes, waves with a walk, last-step waves
-#define SCORE_STAT(i, v) atomicAdd(&g_score_stats[i], (unsigned long long)(v))
-#else
-#define SCORE_STAT(i, v)
-#endif
 #ifdef NAVGPU_PREP_TIMING  // experiment builds only (tools/probe_prep_timing.py): where k_score_prep_tab's time goes (one workgroup in 16 reports)
 __device__ unsigned long long g_prep_stats[16];
-#define PREP_STAMP(i) \
-  if (PREP == 1) prep_t[i] = wall_clock64()
+#define PREP_STAMP(i) prep_t[i] = wall_clock64()
 #else
 #define PREP_STAMP(i)
 #endif
-template <bool EXPLICIT, bool TABLES, int THREADS, int PREP = 0, int CHUNK = 12, bool AGG = false>
-__device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first, const float* explicit_sample) {
-  static_assert(!TABLES || PREP == 1, "the tables are built into a stored image only (k_score_prep_tab)");
-  extern __shared__ __align__(16) uint8_t s_dyn[];
-  uint8_t* s_win = s_dyn;
-  __shared__ double s_fp[2 * kMaxFootprint];
-  __shared__ float s_axis[3][kMaxAxis];
-  __shared__ double s_rc[THREADS / 64];
-  __shared__ int s_ri[THREADS / 64];
-  __shared__ int s_cnt[2];
 
-  const uint32_t inst = first + blockIdx.y;
+// The robot a workgroup works on (blockIdx.y) and its costmap window in LDS: win x win cells from map cell (wx0, wy0)
+struct ScoreRobot {
+  uint32_t inst;
+  Geom g;
+  navgpu_robot_state st;
+  const uint8_t* master;
+  const uint32_t *dpath, *dgoal, *dfront;
+  const int32_t* cnt;
+  uint32_t nfp;
+  int win, wx0, wy0;
+  int win_bytes, nw;  // the window's bytes rounded up to 16, 32-cell words per window row
+};
+__device__ __forceinline__ ScoreRobot scoreRobot(const PlannerDev& pl, uint32_t inst) {
+  ScoreRobot r;
+  r.inst = inst;
+  r.g = geomOf(pl, inst);
+  r.st = pl.state[inst];
+  r.master = pl.master + (size_t)inst * pl.cells_padded;
+  r.dpath = pl.path + (size_t)inst * pl.cells;
+  r.dgoal = pl.goal + (size_t)inst * pl.cells;
+  r.dfront = pl.goal_front + (size_t)inst * pl.cells;
+  r.cnt = pl.axis_count + 4 * inst;
+  r.nfp = pl.fp_n[inst];
+  r.win = (int)pl.win;
+  r.win_bytes = (r.win * r.win + 15) & ~15;
+  r.nw = (r.win + 31) >> 5;
+  return r;
+}
+// the window's origin: robot cell (floor of the map coordinate, also valid when the robot is off the map) - win / 2
+__device__ __forceinline__ void placeWindow(ScoreRobot& r) {
+  double fx = floor(((double)r.st.pos[0] - r.g.ox) / r.g.res), fy = floor(((double)r.st.pos[1] - r.g.oy) / r.g.res);
+  fx = fmin(fmax(fx, -1.0e6), 1.0e6);
+  fy = fmin(fmax(fy, -1.0e6), 1.0e6);
+  r.wx0 = (int)fx - r.win / 2;
+  r.wy0 = (int)fy - r.win / 2;
+}
+
+// ---- stage: footprint and per-axis samples (not for an explicit sample) to LDS, the workgroup's counters cleared, the
+// window placed and its bytes staged
+template <bool EXPLICIT>
+__device__ __forceinline__ void stageInputs(const PlannerDev& pl, ScoreRobot& r, double* s_fp, float (*s_axis)[kMaxAxis], int* s_cnt, uint8_t* s_win) {
   const uint32_t tid = threadIdx.x;
-#ifdef NAVGPU_PREP_TIMING
-  unsigned long long prep_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  PREP_STAMP(0);
-#ifdef NAVGPU_SCORE_TIMING
-  const unsigned long long ts0 = wall_clock64();
-#endif
-  // A scoring workgroup's prologue (a few dependent loads, the image copy, barriers) is a handful of instructions, but its
-  // waves are the YOUNGEST on their SIMDs and lose every issue arbitration against the five older workgroups in their
-  // rollout loops: measured 40 % of a workgroup's residence before its first trajectory point.  Raised priority until the
-  // image is in place gets it out of the way.
-  if (PREP == 2) __builtin_amdgcn_s_setprio(3);
-  const navgpu_dwa_config& c = pl.cfg;
-  const Geom g = geomOf(pl, inst);
-  const navgpu_robot_state st = pl.state[inst];
-  const uint8_t* master = pl.master + (size_t)inst * pl.cells_padded;
-  const uint32_t* dpath = pl.path + (size_t)inst * pl.cells;
-  const uint32_t* dgoal = pl.goal + (size_t)inst * pl.cells;
-  const uint32_t* dfront = pl.goal_front + (size_t)inst * pl.cells;
-  const int32_t* cnt = pl.axis_count + 4 * inst;
-  const int n_samples = EXPLICIT ? 1 : cnt[3];
-  const uint32_t nfp = pl.fp_n[inst];
-  const int win = (int)pl.win;
-
-  // ---- stage: footprint, per-axis samples, costmap window around the robot
-  // A scoring workgroup (PREP 2) keeps what it loads here in registers and writes it to LDS together with its image
-  // further down: ONE batch of loads in flight and one barrier instead of five dependent round trips and three barriers
-  // (a load takes several microseconds while 24 waves per CU gather from the distance grids; measured 40 % of a
-  // workgroup's residence was spent before its first trajectory point).
-  constexpr int kAxisChunks = (3 * kMaxAxis + THREADS - 1) / THREADS;
-  double pre_fp = 0.0;
-  float pre_axis[kAxisChunks];
-  if (PREP == 2) {
-    pre_fp = pl.fp_spec[(size_t)inst * kMaxFootprint * 2 + (tid < 2 * nfp ? tid : 0)];
-#pragma unroll
-    for (int u = 0; u < kAxisChunks; ++u) {
-      const uint32_t i = min(tid + (uint32_t)u * THREADS, 3u * kMaxAxis - 1), a = i / kMaxAxis, k = i - a * kMaxAxis;
-      pre_axis[u] = pl.axis_samples[((size_t)inst * 3 + a) * pl.max_axis + min(k, pl.max_axis - 1)];
-      if (k >= pl.max_axis) pre_axis[u] = 0.f;
-    }
-  } else {
-    if (tid < 2 * nfp) s_fp[tid] = pl.fp_spec[(size_t)inst * kMaxFootprint * 2 + tid];
-    if (!EXPLICIT) {
-      for (uint32_t i = tid; i < 3 * kMaxAxis; i += blockDim.x) {
-        uint32_t a = i / kMaxAxis, k = i - a * kMaxAxis;
-        s_axis[a][k] = k < pl.max_axis ? pl.axis_samples[((size_t)inst * 3 + a) * pl.max_axis + k] : 0.f;
-      }
+  const Geom& g = r.g;
+  if (tid < 2 * r.nfp) s_fp[tid] = pl.fp_spec[(size_t)r.inst * kMaxFootprint * 2 + tid];
+  if (!EXPLICIT) {
+    for (uint32_t i = tid; i < 3 * kMaxAxis; i += blockDim.x) {
+      uint32_t a = i / kMaxAxis, k = i - a * kMaxAxis;
+      s_axis[a][k] = k < pl.max_axis ? pl.axis_samples[((size_t)r.inst * 3 + a) * pl.max_axis + k] : 0.f;
     }
   }
   if (tid == 0) s_cnt[0] = s_cnt[1] = 0;
-  int wx0 = 0, wy0 = 0;
-  {
-    // window origin: robot cell (floor of the map coordinate, also valid when the robot is off the map)
-    double fx = floor(((double)st.pos[0] - g.ox) / g.res), fy = floor(((double)st.pos[1] - g.oy) / g.res);
-    fx = fmin(fmax(fx, -1.0e6), 1.0e6);
-    fy = fmin(fmax(fy, -1.0e6), 1.0e6);
-    wx0 = (int)fx - win / 2;
-    wy0 = (int)fy - win / 2;
-    // (eight loads of a lane in flight at a time - unconditional, clamped: a conditional load in a rolled loop is waited
-    // for on its own, nine latencies in a row for a 65 x 65 window)
-    for (int i0 = tid; PREP != 2 && i0 < win * win; i0 += 8 * (int)blockDim.x) {
-      uint8_t v[8];
-      bool in_map[8];
+  placeWindow(r);
+  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0;
+  // (eight loads of a lane in flight at a time - unconditional, clamped: a conditional load in a rolled loop is waited
+  // for on its own, nine latencies in a row for a 65 x 65 window)
+  for (int i0 = tid; i0 < win * win; i0 += 8 * (int)blockDim.x) {
+    uint8_t v[8];
+    bool in_map[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int ic = min(i0 + u * (int)blockDim.x, win * win - 1);
-        const int ly = ic / win, lx = ic - ly * win;
-        const int gx = wx0 + lx, gy = wy0 + ly;
-        in_map[u] = gx >= 0 && gy >= 0 && gx < (int)g.nx && gy < (int)g.ny;
-        v[u] = master[min(max(gy, 0), (int)g.ny - 1) * g.nx + min(max(gx, 0), (int)g.nx - 1)];
-      }
+    for (int u = 0; u < 8; ++u) {
+      const int ic = min(i0 + u * (int)blockDim.x, win * win - 1);
+      const int ly = ic / win, lx = ic - ly * win;
+      const int gx = wx0 + lx, gy = wy0 + ly;
+      in_map[u] = gx >= 0 && gy >= 0 && gx < (int)g.nx && gy < (int)g.ny;
+      v[u] = r.master[min(max(gy, 0), (int)g.ny - 1) * g.nx + min(max(gx, 0), (int)g.nx - 1)];
+    }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int i = i0 + u * (int)blockDim.x;
-        if (i < win * win) s_win[i] = in_map[u] ? v[u] : (uint8_t)0;
-      }
+    for (int u = 0; u < 8; ++u) {
+      const int i = i0 + u * (int)blockDim.x;
+      if (i < win * win) s_win[i] = in_map[u] ? v[u] : (uint8_t)0;
     }
   }
-  // ---- per-cell screens of the window, four bitmaps interleaved per 32-cell word: s_fb[(y * nw + j) * 4 + k]
-  // Footprint shortcuts: the cells a footprint with centre cell c can touch lie within the Chebyshev radius
-  // fp_rcells of c (>= circumscribed radius in cells + 1).  Two bitmaps of the window, dilated by that radius, are
-  // built once per robot (bit-parallel: rows of 32-cell words, shifts for the horizontal pass, word ORs for the
-  // vertical one; everything outside the window or off the map counts as set):
-  //   k = 0: some cell in reach is not FREE_SPACE  -> clear = the point's footprint cost is exactly 0
-  //   k = 1: some cell in reach fails pointCost    -> clear = the point is legal (cost not needed)
-  // MapGrid screens (not dilated): a trajectory point only has to NOT be an obstacle / unreachable cell of the path and
-  // goal grids unless it is the last one (aggregation Last, map_grid_cost_function.cpp:92-127):
-  //   k = 2: path grid holds obstacleCosts() or unreachableCellCosts() here    k = 3: the goal grid does
-  const int win_bytes = (win * win + 15) & ~15;
-  const int nw = (win + 31) >> 5;
-  uint32_t* s_fb = reinterpret_cast<uint32_t*>(s_dyn + win_bytes);  // [win][nw][4]
-  // build scratch behind the image (window + bitmaps + tables): [win][nw][2] raw, [win][nw][2] after the horizontal pass
-  uint32_t* s_ba = reinterpret_cast<uint32_t*>(s_dyn + win_bytes + score_bits_bytes(win) + (TABLES ? pl.tab_bytes : 0u));
+}
+
+// ---- stage: per-cell screens of the window, four bitmaps interleaved per 32-cell word: s_fb[(y * nw + j) * 4 + k]
+// Footprint shortcuts: the cells a footprint with centre cell c can touch lie within the Chebyshev radius
+// fp_rcells of c (>= circumscribed radius in cells + 1).  Two bitmaps of the window, dilated by that radius, are
+// built once per robot (bit-parallel: rows of 32-cell words, shifts for the horizontal pass, word ORs for the
+// vertical one; everything outside the window or off the map counts as set):
+//   k = 0: some cell in reach is not FREE_SPACE  -> clear = the point's footprint cost is exactly 0
+//   k = 1: some cell in reach fails pointCost    -> clear = the point is legal (cost not needed)
+// MapGrid screens (not dilated): a trajectory point only has to NOT be an obstacle / unreachable cell of the path and
+// goal grids unless it is the last one (aggregation Last, map_grid_cost_function.cpp:92-127):
+//   k = 2: path grid holds obstacleCosts() or unreachableCellCosts() here    k = 3: the goal grid does
+// s_ba: build scratch behind the image (window + bitmaps + tables): [win][nw][2] raw, [win][nw][2] after the horizontal pass.
+// The LDS window is kept in "walk order": with allow_unknown the bytes 254 (LETHAL) and 255 (NO_INFORMATION)
+// are swapped, so that in both modes a footprint cell fails pointCost iff its stored byte >= walk_fail and the
+// polygon walk needs nothing but a running maximum per cell (cellCost() undoes the swap).
+__device__ __forceinline__ void buildScreens(const PlannerDev& pl, const ScoreRobot& r, uint8_t* s_dyn, uint32_t* s_ba) {
+  const uint32_t tid = threadIdx.x;
+  const Geom& g = r.g;
+  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0, nw = r.nw;
+  const uint32_t *dpath = r.dpath, *dgoal = r.dgoal;
+  uint8_t* s_win = s_dyn;
+  uint32_t* s_fb = reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes);  // [win][nw][4]
   const int rc = (int)pl.fp_rcells;
   const uint8_t fail_span_w = (pl.cfg.allow_unknown != 0) ? 0 : 1;
-  if (PREP != 2) __syncthreads();
-  PREP_STAMP(1);  // staged: footprint, axis samples, window bytes
-#ifdef NAVGPU_SCORE_TIMING
-  const unsigned long long ts0a = wall_clock64();
-#endif
-  if (PREP != 2) {
   {  // the raw bits: 64 consecutive cells of a (padded) window row per wave step, packed by ballot
     const int row_cells = nw * 32;
     const bool obst_off = pl.scale_obstacle == 0;  // obstacle critic off (scale 0: skipped, simple_scored_sampling_planner.cpp:55-57): nothing to screen
@@ -176,7 +150,6 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     }
   }
   __syncthreads();
-  PREP_STAMP(2);  // raw bits
   // The dilation: a DISC (PlannerDev::fp_halfw: per row offset dy the largest |dx| an outline cell can have), not the Chebyshev
   // square around it - a fifth to a quarter fewer cells, and every cell less is trajectory points that need not be looked at.
   // Grouped by dx: the rows that contribute at |dx| = d are |dy| <= Y(d) (the half widths fall with |dy|), so the rows are OR-ed
@@ -201,7 +174,6 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     }
     s_fb[4 * cell + (it & 1)] = m;
   }
-  PREP_STAMP(3);  // dilation
   {  // MapGrid screens: 64 consecutive cells of a (padded) window row per wave step, packed by ballot
     const uint32_t n_obst = pl.cells, n_unreach = pl.cells + 1;
     const int row_cells = nw * 32;
@@ -245,156 +217,191 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
       }
     }
   }
-  }
-  // The LDS window is kept in "walk order": with allow_unknown the bytes 254 (LETHAL) and 255 (NO_INFORMATION)
-  // are swapped, so that in both modes a footprint cell fails pointCost iff its stored byte >= walk_fail and the
-  // polygon walk needs nothing but a running maximum per cell (cellCost() undoes the swap).
-  const bool walk_swap = pl.cfg.allow_unknown != 0;
-  const uint32_t walk_fail = walk_swap ? 255u : 254u;
-  if (PREP != 2 && walk_swap) {
+  if (pl.cfg.allow_unknown != 0) {  // walk order
     __syncthreads();
     for (int i = tid; i < win * win; i += blockDim.x) {
       const uint8_t cc = s_win[i];
       if (cc >= 254) s_win[i] = cc ^ 1u;
     }
   }
-  // ---- TABLES: per-(v_theta sample, step) heading, trig and rotated footprint, all tab_nth v_theta rows
-  if (TABLES) {
-    const int K = (int)pl.tab_steps;
-    const int tnfp = (int)pl.tab_nfp;
-    const int nth_s = cnt[2];
-    const int lrows = (int)pl.tab_nth;
-    double* s_trig = reinterpret_cast<double*>(s_dyn + win_bytes + score_bits_bytes(win));  // [rows][K][4] cs, sn, cs2, sn2
-    double* s_rot = s_trig + (size_t)lrows * K * 4;                                 // [rows][K][tnfp][2]
-    float* s_th = reinterpret_cast<float*>(s_rot + (size_t)lrows * K * tnfp * 2);       // [rows][K]
-    __syncthreads();  // s_axis, s_fp staged
-    PREP_STAMP(4);  // MapGrid screens (+ walk-order swap)
-    const double dt_t = c.sim_time / K;
-    if ((int)tid < nth_s) {
-      float pth = st.pos[2];
-      const float vth = s_axis[2][tid];
-      for (int k = 0; k < K; ++k) {
-        s_th[tid * K + k] = pth;
-        pth = (float)(pth + vth * dt_t);  // computeNewPositions :258
-      }
-    }
-    __syncthreads();
-    PREP_STAMP(5);  // heading sequences
-    for (int e = tid; e < nth_s * K; e += blockDim.x) {
-      const double th = s_th[e];
-      double sn, cs, sn2, cs2;
-      sincos(th, &sn, &cs);
-      sincos(M_PI_2 + th, &sn2, &cs2);
-      s_trig[4 * e] = cs;
-      s_trig[4 * e + 1] = sn;
-      s_trig[4 * e + 2] = cs2;
-      s_trig[4 * e + 3] = sn2;
-      for (int v = 0; v < (int)nfp && v < tnfp; ++v) {
-        const double sx = s_fp[2 * v], sy = s_fp[2 * v + 1];
-        s_rot[(e * tnfp + v) * 2] = sx * cs - sy * sn;      // world_model.h:72-73
-        s_rot[(e * tnfp + v) * 2 + 1] = sx * sn + sy * cs;
-      }
-    }
-  }
-  if (PREP != 2) __syncthreads();
-  PREP_STAMP(6);  // trig + rotated footprints
-#ifdef NAVGPU_SCORE_TIMING
-  const unsigned long long ts0b = wall_clock64();
-#endif
-  if (PREP != 0) {  // the LDS image as 16-byte words: [0, prep_bytes)
-    uint4* img = reinterpret_cast<uint4*>(pl.prep + (size_t)inst * pl.prep_stride);
-    uint4* lds = reinterpret_cast<uint4*>(s_dyn);
-    const uint32_t n16 = pl.prep_bytes >> 4;
-    if (PREP == 1) {
-      for (uint32_t i = tid; i < n16; i += blockDim.x) img[i] = lds[i];
-      if (TABLES) {
-        // What every lane of the sweep launch would otherwise work out again: the robot's scalars (two fp64 divisions, a ceil)
-        // and the generator's reject tests of the (vx, vy) pairs (a compensated fp64 square root each) - behind the image.
-        uint8_t* rej = pl.prep + (size_t)inst * pl.prep_stride + score_prep_reject_offset(pl);
-        int32_t* aux = reinterpret_cast<int32_t*>(rej - kScoreAuxBytes);
-        // d0: how far (Euclidean, cells, rounded down) from the robot's own cell - the window's centre - the nearest cell lies at which ANY screen is
-        // set (or the window ends).  A trajectory point fewer cells away than that passes every screen whatever else: the sweep skips
-        // its worldToMap and look-up for as many steps as the sample's speed cannot cover d0 cells in (k_score_sweep).
-        // The path / goal screen at the robot's own cell decides those critics for EVERY sample at step 0 (all rollouts start there):
-        // start_fail = 4 (the path critic fails there; the goal critic, later in the list, no longer counts either) or 5 (the goal
-        // critic does - e.g. a goal inside an inflated wall, 17 % of the benchmark's robots) or 0.  The distance is taken over the
-        // screens that still count after that.
-        const int c0 = win / 2;
-        const uint32_t w_c0 = (uint32_t)(c0 * nw + (c0 >> 5));
-        const int start_fail = ((s_fb[4 * w_c0 + 2] >> (c0 & 31)) & 1u) ? 4 : (((s_fb[4 * w_c0 + 3] >> (c0 & 31)) & 1u) ? 5 : 0);
-        if (tid == 0) s_cnt[0] = (win / 2) * (win / 2);  // (squared: the distance is Euclidean - a pose moves |v| dt whatever its bearing)
-        __syncthreads();
-        PREP_STAMP(7);  // image stored
-        {
-          int dmin = win * win;
-          for (int it = tid; it < win * nw; it += blockDim.x) {
-            const int y = it / nw, j = it - y * nw;
-            uint32_t m = (c.sum_scores ? s_fb[4 * it] : s_fb[4 * it + 1]) | (start_fail == 4 ? 0u : s_fb[4 * it + 2]) | (start_fail != 0 ? 0u : s_fb[4 * it + 3]);
-            const int dy = y > c0 ? y - c0 : c0 - y;
-            // the set cell nearest to column c0: the lowest set bit at or right of it, the highest left of it (no loop over the bits)
-            const int p = c0 - 32 * j;  // c0's bit position in this word (may lie outside it)
-            const uint32_t right = p <= 0 ? m : (p >= 32 ? 0u : m & (0xFFFFFFFFu << p)), left = m & ~right;
-            if (right) dmin = min(dmin, (32 * j + __ffs(right) - 1 - c0) * (32 * j + __ffs(right) - 1 - c0) + dy * dy);
-            if (left) dmin = min(dmin, (c0 - (32 * j + 31 - __clz(left))) * (c0 - (32 * j + 31 - __clz(left))) + dy * dy);
-          }
-          atomicMin(&s_cnt[0], dmin);
-        }
-        __syncthreads();
-        if (tid == 0) {
-          const double inv_res = pl.inv_res, fpd = c.forward_point_distance;
-          const bool en_fwd = pl.scale_goal != 0 || (pl.align_on[inst] && pl.scale_path != 0);  // goal_front or alignment critic on
-          // the forward point (x + fpd cos, y + fpd sin) stays on the map whenever the centre cell is this many cells away from
-          // every border; only then may a step skip its worldToMap
-          const uint32_t fwd_margin = (uint32_t)fmin(ceil(fabs(fpd) * inv_res) + 1.0, 1.0e6);
-          const bool fwd_screen = !en_fwd || (2u * fwd_margin < g.nx && 2u * fwd_margin < g.ny);
-          const uint32_t fwd_lo = en_fwd ? fwd_margin : 0u, fwd_nx = g.nx - 2u * fwd_lo, fwd_ny = g.ny - 2u * fwd_lo;
-          // the forward-margin test is only needed when the LDS window reaches into the margin band of the map
-          const bool need_margin = !((uint32_t)wx0 - fwd_lo < fwd_nx && (uint32_t)(wx0 + win - 1) - fwd_lo < fwd_nx && (uint32_t)wy0 - fwd_lo < fwd_ny &&
-                                     (uint32_t)(wy0 + win - 1) - fwd_lo < fwd_ny);
-          aux[0] = wx0;
-          aux[1] = wy0;
-          aux[2] = (int32_t)fwd_lo;
-          aux[3] = (int32_t)fwd_nx;
-          aux[4] = (int32_t)fwd_ny;
-          aux[5] = need_margin ? 1 : 0;
-          aux[6] = fwd_screen ? 1 : 0;
-          aux[7] = (int)floor(sqrt((double)s_cnt[0]));
-          aux[8] = start_fail;
-        }
-        // generateTrajectory's reject tests (simple_trajectory_generator.cpp:193-200), the part that depends on (vx, vy) only:
-        // bit 0: vmag + eps < min_trans_vel (rejects together with the v_theta half), bit 1: vmag - eps > max_trans_vel
-        const int nyv = max(cnt[1], 1), nxyv = cnt[0] * cnt[1];
-        for (int i = tid; i < nxyv; i += blockDim.x) {
-          const int ix = i / nyv, iy = i - ix * nyv;
-          const double vmag = hyp2((double)s_axis[0][ix], (double)s_axis[1][iy]);
-          const double eps = 1e-4;
-          rej[i] = (uint8_t)(((c.min_trans_vel >= 0 && vmag + eps < c.min_trans_vel) ? 1 : 0) | ((c.max_trans_vel >= 0 && vmag - eps > c.max_trans_vel) ? 2 : 0));
-        }
-#ifdef NAVGPU_PREP_TIMING
-        PREP_STAMP(8);  // free distance, scalars, reject bytes
-        if (PREP == 1 && tid == 0 && (blockIdx.y & 15u) == 3u) {
-          for (int i = 0; i < 8; ++i) atomicAdd(&g_prep_stats[i], prep_t[i + 1] - prep_t[i]);
-          atomicAdd(&g_prep_stats[15], 1ull);
-        }
-#endif
-      }
-      return;
-    }
-    // PREP 2: the stored image, and the footprint / axis samples loaded into registers above
-    for (uint32_t i = tid; i < n16; i += blockDim.x) lds[i] = img[i];
-    if (tid < 2 * nfp) s_fp[tid] = pre_fp;
-#pragma unroll
-    for (int u = 0; u < kAxisChunks; ++u) {
-      const uint32_t i = tid + (uint32_t)u * THREADS;
-      if (i < 3u * kMaxAxis) s_axis[i / kMaxAxis][i % kMaxAxis] = pre_axis[u];
-    }
-    __syncthreads();
-  }
+}
 
-  if (PREP == 2) __builtin_amdgcn_s_setprio(0);
-#ifdef NAVGPU_SCORE_TIMING
-  const unsigned long long ts1 = wall_clock64();
-#endif
+// ---- stage (the tables, use_tables: use_dwa && discretize_by_time, k_score_prep_tab only): per-(v_theta sample, step) heading, trig and
+// rotated footprint, all tab_nth v_theta rows, behind the screens
+__device__ __forceinline__ void buildTables(const PlannerDev& pl, const ScoreRobot& r, const double* s_fp, const float (*s_axis)[kMaxAxis], uint8_t* s_dyn) {
+  const uint32_t tid = threadIdx.x;
+  const navgpu_dwa_config& c = pl.cfg;
+  const navgpu_robot_state& st = r.st;
+  const uint32_t nfp = r.nfp;
+  const int K = (int)pl.tab_steps;
+  const int tnfp = (int)pl.tab_nfp;
+  const int nth_s = r.cnt[2];
+  const int lrows = (int)pl.tab_nth;
+  double* s_trig = reinterpret_cast<double*>(s_dyn + r.win_bytes + score_bits_bytes(r.win));  // [rows][K][4] cs, sn, cs2, sn2
+  double* s_rot = s_trig + (size_t)lrows * K * 4;                                              // [rows][K][tnfp][2]
+  float* s_th = reinterpret_cast<float*>(s_rot + (size_t)lrows * K * tnfp * 2);                // [rows][K]
+  __syncthreads();  // s_axis, s_fp staged
+  const double dt_t = c.sim_time / K;
+  if ((int)tid < nth_s) {
+    float pth = st.pos[2];
+    const float vth = s_axis[2][tid];
+    for (int k = 0; k < K; ++k) {
+      s_th[tid * K + k] = pth;
+      pth = (float)(pth + vth * dt_t);  // computeNewPositions :258
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < nth_s * K; e += blockDim.x) {
+    const double th = s_th[e];
+    double sn, cs, sn2, cs2;
+    sincos(th, &sn, &cs);
+    sincos(M_PI_2 + th, &sn2, &cs2);
+    s_trig[4 * e] = cs;
+    s_trig[4 * e + 1] = sn;
+    s_trig[4 * e + 2] = cs2;
+    s_trig[4 * e + 3] = sn2;
+    for (int v = 0; v < (int)nfp && v < tnfp; ++v) {
+      const double sx = s_fp[2 * v], sy = s_fp[2 * v + 1];
+      s_rot[(e * tnfp + v) * 2] = sx * cs - sy * sn;      // world_model.h:72-73
+      s_rot[(e * tnfp + v) * 2 + 1] = sx * sn + sy * cs;
+    }
+  }
+}
+
+// ---- stage: the LDS image as 16-byte words, [0, prep_bytes), to the robot's slot of pl.prep
+__device__ __forceinline__ void storeImage(const PlannerDev& pl, const ScoreRobot& r, const uint8_t* s_dyn) {
+  uint4* img = reinterpret_cast<uint4*>(pl.prep + (size_t)r.inst * pl.prep_stride);
+  const uint4* lds = reinterpret_cast<const uint4*>(s_dyn);
+  const uint32_t n16 = pl.prep_bytes >> 4;
+  for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) img[i] = lds[i];
+}
+
+// ---- stage (k_score_prep_tab only): the sweep's per-robot scalars and the reject bytes of the (vx, vy) pairs, behind the image
+__device__ __forceinline__ void storeSweepScalars(const PlannerDev& pl, const ScoreRobot& r, const float (*s_axis)[kMaxAxis], int* s_cnt,
+                                                  const uint8_t* s_dyn) {
+  const uint32_t tid = threadIdx.x;
+  const navgpu_dwa_config& c = pl.cfg;
+  const Geom& g = r.g;
+  const int32_t* cnt = r.cnt;
+  const uint32_t inst = r.inst;
+  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0, nw = r.nw;
+  const uint32_t* s_fb = reinterpret_cast<const uint32_t*>(s_dyn + r.win_bytes);
+  // What every lane of the sweep launch would otherwise work out again: the robot's scalars (two fp64 divisions, a ceil)
+  // and the generator's reject tests of the (vx, vy) pairs (a compensated fp64 square root each) - behind the image.
+  uint8_t* rej = pl.prep + (size_t)inst * pl.prep_stride + score_prep_reject_offset(pl);
+  int32_t* aux = reinterpret_cast<int32_t*>(rej - kScoreAuxBytes);
+  // d0: how far (Euclidean, cells, rounded down) from the robot's own cell - the window's centre - the nearest cell lies at which ANY screen is
+  // set (or the window ends).  A trajectory point fewer cells away than that passes every screen whatever else: the sweep skips
+  // its worldToMap and look-up for as many steps as the sample's speed cannot cover d0 cells in (k_score_sweep).
+  // The path / goal screen at the robot's own cell decides those critics for EVERY sample at step 0 (all rollouts start there):
+  // start_fail = 4 (the path critic fails there; the goal critic, later in the list, no longer counts either) or 5 (the goal
+  // critic does - e.g. a goal inside an inflated wall, 17 % of the benchmark's robots) or 0.  The distance is taken over the
+  // screens that still count after that.
+  const int c0 = win / 2;
+  const uint32_t w_c0 = (uint32_t)(c0 * nw + (c0 >> 5));
+  const int start_fail = ((s_fb[4 * w_c0 + 2] >> (c0 & 31)) & 1u) ? 4 : (((s_fb[4 * w_c0 + 3] >> (c0 & 31)) & 1u) ? 5 : 0);
+  if (tid == 0) s_cnt[0] = (win / 2) * (win / 2);  // (squared: the distance is Euclidean - a pose moves |v| dt whatever its bearing)
+  __syncthreads();
+  {
+    int dmin = win * win;
+    for (int it = tid; it < win * nw; it += blockDim.x) {
+      const int y = it / nw, j = it - y * nw;
+      uint32_t m = (c.sum_scores ? s_fb[4 * it] : s_fb[4 * it + 1]) | (start_fail == 4 ? 0u : s_fb[4 * it + 2]) | (start_fail != 0 ? 0u : s_fb[4 * it + 3]);
+      const int dy = y > c0 ? y - c0 : c0 - y;
+      // the set cell nearest to column c0: the lowest set bit at or right of it, the highest left of it (no loop over the bits)
+      const int p = c0 - 32 * j;  // c0's bit position in this word (may lie outside it)
+      const uint32_t right = p <= 0 ? m : (p >= 32 ? 0u : m & (0xFFFFFFFFu << p)), left = m & ~right;
+      if (right) dmin = min(dmin, (32 * j + __ffs(right) - 1 - c0) * (32 * j + __ffs(right) - 1 - c0) + dy * dy);
+      if (left) dmin = min(dmin, (c0 - (32 * j + 31 - __clz(left))) * (c0 - (32 * j + 31 - __clz(left))) + dy * dy);
+    }
+    atomicMin(&s_cnt[0], dmin);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double inv_res = pl.inv_res, fpd = c.forward_point_distance;
+    const bool en_fwd = pl.scale_goal != 0 || (pl.align_on[inst] && pl.scale_path != 0);  // goal_front or alignment critic on
+    // the forward point (x + fpd cos, y + fpd sin) stays on the map whenever the centre cell is this many cells away from
+    // every border; only then may a step skip its worldToMap
+    const uint32_t fwd_margin = (uint32_t)fmin(ceil(fabs(fpd) * inv_res) + 1.0, 1.0e6);
+    const bool fwd_screen = !en_fwd || (2u * fwd_margin < g.nx && 2u * fwd_margin < g.ny);
+    const uint32_t fwd_lo = en_fwd ? fwd_margin : 0u, fwd_nx = g.nx - 2u * fwd_lo, fwd_ny = g.ny - 2u * fwd_lo;
+    // the forward-margin test is only needed when the LDS window reaches into the margin band of the map
+    const bool need_margin = !((uint32_t)wx0 - fwd_lo < fwd_nx && (uint32_t)(wx0 + win - 1) - fwd_lo < fwd_nx && (uint32_t)wy0 - fwd_lo < fwd_ny &&
+                               (uint32_t)(wy0 + win - 1) - fwd_lo < fwd_ny);
+    aux[0] = wx0;
+    aux[1] = wy0;
+    aux[2] = (int32_t)fwd_lo;
+    aux[3] = (int32_t)fwd_nx;
+    aux[4] = (int32_t)fwd_ny;
+    aux[5] = need_margin ? 1 : 0;
+    aux[6] = fwd_screen ? 1 : 0;
+    aux[7] = (int)floor(sqrt((double)s_cnt[0]));
+    aux[8] = start_fail;
+  }
+  // generateTrajectory's reject tests (simple_trajectory_generator.cpp:193-200), the part that depends on (vx, vy) only:
+  // bit 0: vmag + eps < min_trans_vel (rejects together with the v_theta half), bit 1: vmag - eps > max_trans_vel
+  const int nyv = max(cnt[1], 1), nxyv = cnt[0] * cnt[1];
+  for (int i = tid; i < nxyv; i += blockDim.x) {
+    const int ix = i / nyv, iy = i - ix * nyv;
+    const double vmag = hyp2((double)s_axis[0][ix], (double)s_axis[1][iy]);
+    const double eps = 1e-4;
+    rej[i] = (uint8_t)(((c.min_trans_vel >= 0 && vmag + eps < c.min_trans_vel) ? 1 : 0) | ((c.max_trans_vel >= 0 && vmag - eps > c.max_trans_vel) ? 2 : 0));
+  }
+}
+
+// ---- stage (k_score_gen*): the footprint and the axis samples, loaded into registers before the image copy
+struct ScoreInputs {
+  static constexpr int kAxisChunks = (3 * kMaxAxis + kScoreThreads - 1) / kScoreThreads;
+  double fp;
+  float axis[kAxisChunks];
+};
+__device__ __forceinline__ ScoreInputs loadInputs(const PlannerDev& pl, const ScoreRobot& r) {
+  const uint32_t tid = threadIdx.x;
+  ScoreInputs in;
+  in.fp = pl.fp_spec[(size_t)r.inst * kMaxFootprint * 2 + (tid < 2 * r.nfp ? tid : 0)];
+#pragma unroll
+  for (int u = 0; u < ScoreInputs::kAxisChunks; ++u) {
+    const uint32_t i = min(tid + (uint32_t)u * kScoreThreads, 3u * kMaxAxis - 1), a = i / kMaxAxis, k = i - a * kMaxAxis;
+    in.axis[u] = pl.axis_samples[((size_t)r.inst * 3 + a) * pl.max_axis + min(k, pl.max_axis - 1)];
+    if (k >= pl.max_axis) in.axis[u] = 0.f;
+  }
+  return in;
+}
+// ---- stage (k_score_gen*): the stored image to LDS, with the footprint / axis samples loadInputs holds; one barrier
+__device__ __forceinline__ void loadImage(const PlannerDev& pl, const ScoreRobot& r, const ScoreInputs& in, double* s_fp, float (*s_axis)[kMaxAxis],
+                                          uint8_t* s_dyn) {
+  const uint32_t tid = threadIdx.x;
+  const uint4* img = reinterpret_cast<const uint4*>(pl.prep + (size_t)r.inst * pl.prep_stride);
+  uint4* lds = reinterpret_cast<uint4*>(s_dyn);
+  const uint32_t n16 = pl.prep_bytes >> 4;
+  for (uint32_t i = tid; i < n16; i += blockDim.x) lds[i] = img[i];
+  if (tid < 2 * r.nfp) s_fp[tid] = in.fp;
+#pragma unroll
+  for (int u = 0; u < ScoreInputs::kAxisChunks; ++u) {
+    const uint32_t i = tid + (uint32_t)u * kScoreThreads;
+    if (i < 3u * kMaxAxis) s_axis[i / kMaxAxis][i % kMaxAxis] = in.axis[u];
+  }
+  __syncthreads();
+}
+
+// ---- stage: one lane per velocity sample - rollout, critics, the sample's outputs - and the workgroup's partial argmin
+// CHUNK: cells of a footprint edge fetched per LDS round trip (see planner_score.h); AGG: the general MapGrid step
+template <bool EXPLICIT, int CHUNK, bool AGG>
+__device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRobot& r, const double* s_fp, const float (*s_axis)[kMaxAxis],
+                                             const uint8_t* s_dyn, double* s_rc, int* s_ri, int* s_cnt, const float* explicit_sample) {
+  const uint32_t tid = threadIdx.x;
+  const navgpu_dwa_config& c = pl.cfg;
+  const Geom& g = r.g;
+  const navgpu_robot_state& st = r.st;
+  const uint8_t* master = r.master;
+  const uint32_t *dpath = r.dpath, *dgoal = r.dgoal, *dfront = r.dfront;
+  const int32_t* cnt = r.cnt;
+  const uint32_t inst = r.inst, nfp = r.nfp;
+  const int n_samples = EXPLICIT ? 1 : cnt[3];
+  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0, win_bytes = r.win_bytes, nw = r.nw;
+  const uint8_t* s_win = s_dyn;
+  const bool walk_swap = pl.cfg.allow_unknown != 0;  // the window bytes are in walk order (buildScreens)
+  const uint32_t walk_fail = walk_swap ? 255u : 254u;
   // NOTE: the LDS read is unconditional (clamped index) and the global fallback sits in its own
   // rarely-taken branch; a `cond ? lds[i] : global[j]` form makes hipcc merge both into one FLAT load.
   auto inWin = [&](int x, int y) { return (unsigned)(x - wx0) < (unsigned)win && (unsigned)(y - wy0) < (unsigned)win; };
@@ -407,27 +414,7 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     return (uint8_t)v;
   };
   const double inv_res = pl.inv_res;
-  // Costmap2D::worldToMap with the two fp64 divisions replaced by a multiply; exact: whenever the
-  // product is not clear of an integer by 1e-7 (error bound 5e-10 below 1e6 cells) the division is redone.
-  // Straight-line: the only branch is the rare redo.
-  auto w2m = [&](double wx, double wy, uint32_t& mx, uint32_t& my) -> bool {
-    const double dx = wx - g.ox, dy = wy - g.oy;
-    const double qx = dx * inv_res, qy = dy * inv_res;
-    double fx = floor(qx), fy = floor(qy);
-    const double rx = qx - fx, ry = qy - fy;
-    if (__builtin_expect(fmin(rx, ry) < 1.0e-7 || fmax(rx, ry) > 1.0 - 1.0e-7, 0)) {
-      fx = !(dx >= 0.0) ? -1.0 : (qx >= 1.0e6 ? 1.0e6 : (double)(int)(dx / g.res));  // wx < origin -> false (costmap_2d.cpp:210)
-      fy = !(dy >= 0.0) ? -1.0 : (qy >= 1.0e6 ? 1.0e6 : (double)(int)(dy / g.res));
-    }
-    // v_cvt_i32_f64 saturates (a point left of / below the origin floors to a negative cell, one far beyond the grid to
-    // INT_MAX: both fail the size test as unsigned numbers), which a C++ cast does not promise
-    int ix, iy;
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(ix) : "v"(fx));
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(iy) : "v"(fy));
-    mx = (uint32_t)ix;
-    my = (uint32_t)iy;
-    return mx < g.nx && my < g.ny;
-  };
+  const WorldToMapFast w2m{g, inv_res};
   const uint8_t fail_span = (pl.cfg.allow_unknown != 0) ? 0 : 1;  // pointCost: 254, and 255 unless allow_unknown
 
   // lane -> sample slot: the slot index (x-outer, y, theta-inner, as the reference enumerates) is what results are keyed by
@@ -585,30 +572,6 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
           const uint32_t any = (scr_sum ? fbw.x : fbw.y) | (fbw.z & scr_z) | (fbw.w & scr_w);
           const bool margin_ok = !need_margin || ((cx - fwd_lo < fwd_nx) && (cy - fwd_lo < fwd_ny));
           const bool screened = screen_on && step != num_steps - 1 && in_w && !((any >> (lxw & 31)) & 1u) && margin_ok;
-#ifdef NAVGPU_SCORE_STATS
-          if (screen_on && step != num_steps - 1 && in_w) {
-            SCORE_STAT(8, (fbw.y >> (lxw & 31)) & 1u);
-            SCORE_STAT(9, (fbw.z >> (lxw & 31)) & 1u);
-            SCORE_STAT(10, (fbw.w >> (lxw & 31)) & 1u);
-            SCORE_STAT(11, !((cx - fwd_lo < fwd_nx) && (cy - fwd_lo < fwd_ny)));
-          } else if (step != num_steps - 1) {
-            SCORE_STAT(12, !ok_c);
-            SCORE_STAT(13, ok_c && !inWin((int)cx, (int)cy));
-            SCORE_STAT(14, !screen_on);
-          }
-#endif
-#ifdef NAVGPU_SCORE_STATS
-          {
-            const unsigned long long act = __ballot(true), uns = __ballot(!screened);
-            if (__ffsll((long long)act) - 1 == (int)(tid & 63)) {
-              SCORE_STAT(0, __popcll(act));
-              SCORE_STAT(1, __popcll(uns));
-              SCORE_STAT(2, 1);
-              SCORE_STAT(3, uns != 0);
-              SCORE_STAT(6, step == num_steps - 1);
-            }
-          }
-#endif
           if (!screened) {
           const bool live_obs = en_obs && 1 < first_fail;
           // all_free: every cell the footprint can touch is FREE_SPACE -> the step costs exactly 0.
@@ -622,15 +585,6 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
           if (live_obs && all_free) {
             v_obs = c.sum_scores ? v_obs + 0.0 : 0.0;
           } else if (live_obs) {
-#ifdef NAVGPU_SCORE_STATS
-            {
-              const unsigned long long wk = __ballot(ok_c && nfp >= 3);
-              if (__ffsll((long long)__ballot(true)) - 1 == (int)(tid & 63)) {
-                SCORE_STAT(4, __popcll(wk));
-                SCORE_STAT(5, wk != 0);
-              }
-            }
-#endif
             double f_cost = 0.0;
             bool bad = !ok_c;  // CostmapModel::footprintCost: centre off the map -> -1
             if (!bad) {
@@ -867,17 +821,11 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
         if (first_fail < 6) {
           total = fail_code;
         } else {
-          auto add = [&](bool en, double value, double scale) {
-            if (!en) return;
-            double cost = value;
-            if (cost != 0) cost *= scale;
-            total += cost;
-          };
-          add(en_obs, v_obs, sc_obs);
-          add(en_gf, v_gf, sc_gf);
-          add(en_al, v_al, sc_al);
-          add(en_path, v_path, sc_path);
-          add(en_goal, v_goal, sc_goal);
+          addCritic(total, en_obs, v_obs, sc_obs);
+          addCritic(total, en_gf, v_gf, sc_gf);
+          addCritic(total, en_al, v_al, sc_al);
+          addCritic(total, en_path, v_path, sc_path);
+          addCritic(total, en_goal, v_goal, sc_goal);
         }
       }
     }
@@ -887,9 +835,6 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     }
   }
 
-#ifdef NAVGPU_SCORE_TIMING
-  const unsigned long long ts2 = wall_clock64();
-#endif
   // ---- workgroup argmin (lowest index wins ties == first strict minimum of the sequential loop)
   const bool valid = in_range && status == NAVGPU_SAMPLE_SCORED && total >= 0.0;
   double bc = valid ? total : 1.0e300;
@@ -911,23 +856,8 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
     atomicAdd(&s_cnt[1], __popcll(m_valid));
   }
   __syncthreads();
-#ifdef NAVGPU_SCORE_TIMING
-  // (one workgroup in 256 reports: with every wave adding to the same few words the atomics themselves stretched the launch sixfold
-  // and made the prologue look like 39 % of a workgroup's residence; sampled, it is 6 %)
-  if (PREP == 2 && (tid & 63) == 0 && (blockIdx.x & 15) == 3 && (blockIdx.y & 15) == 5) {
-    const unsigned long long ts3 = wall_clock64();
-    atomicAdd(&g_score_stats[16], ts1 - ts0);  // image load, per wave
-    atomicAdd(&g_score_stats[22], ts0a - ts0);  // ... of which: staging of footprint / axis samples up to the first barrier
-    atomicAdd(&g_score_stats[23], ts0b - ts0a); // ... lane mapping up to the second barrier
-    atomicAdd(&g_score_stats[17], ts2 - ts1);  // sample setup + rollout, per wave
-    atomicAdd(&g_score_stats[18], ts3 - ts2);  // reduction + wait for the slowest wave of the workgroup
-    atomicAdd(&g_score_stats[19], 1ull);
-    if (tid == 0) atomicAdd(&g_score_stats[20], ts3 - ts0);  // workgroup residence
-    if (tid == 0) atomicAdd(&g_score_stats[21], 1ull);
-  }
-#endif
   if (tid == 0) {
-    for (int w = 1; w < THREADS / 64; ++w)
+    for (int w = 1; w < kScoreThreads / 64; ++w)
       if (s_rc[w] < bc || (s_rc[w] == bc && s_ri[w] < bi)) {
         bc = s_rc[w];
         bi = s_ri[w];
@@ -940,25 +870,103 @@ __device__ __forceinline__ void score_body(const PlannerDev& pl, uint32_t first,
 }
 
 constexpr int kScorePrepThreads = NAVGPU_SCORE_PREP_THREADS;  // the workgroup that builds a robot's image
+
+// k_score_prep_tab: a robot's image with the heading tables, and what k_score_sweep reads behind it
+__global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev pl, uint32_t first) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ int s_cnt[2];
+#ifdef NAVGPU_PREP_TIMING
+  unsigned long long prep_t[6];
+#endif
+  PREP_STAMP(0);
+  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  stageInputs<false>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
+  __syncthreads();
+  PREP_STAMP(1);
+  buildScreens(pl, r, s_dyn, reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes + score_bits_bytes(r.win) + pl.tab_bytes));
+  PREP_STAMP(2);
+  buildTables(pl, r, s_fp, s_axis, s_dyn);
+  __syncthreads();
+  PREP_STAMP(3);
+  storeImage(pl, r, s_dyn);
+  PREP_STAMP(4);
+  storeSweepScalars(pl, r, s_axis, s_cnt, s_dyn);
+#ifdef NAVGPU_PREP_TIMING
+  PREP_STAMP(5);
+  if (threadIdx.x == 0 && (blockIdx.y & 15u) == 3u) {
+    for (int i = 0; i < 5; ++i) atomicAdd(&g_prep_stats[i], prep_t[i + 1] - prep_t[i]);
+    atomicAdd(&g_prep_stats[15], 1ull);
+  }
+#endif
+}
+// k_score_prep_gen: a robot's image (window and screens) for the k_score_gen* workgroups
+__global__ __launch_bounds__(kScoreThreads) void k_score_prep_gen(PlannerDev pl, uint32_t first) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ int s_cnt[2];
+  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  stageInputs<false>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
+  __syncthreads();
+  buildScreens(pl, r, s_dyn, reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes + score_bits_bytes(r.win)));
+  __syncthreads();
+  storeImage(pl, r, s_dyn);
+}
+// k_score_gen<CHUNK> / k_score_gen_agg: the samples of a robot, from the image k_score_prep_gen stored
+template <int CHUNK, bool AGG>
+__device__ __forceinline__ void scoreGen(const PlannerDev& pl, uint32_t first) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ double s_rc[kScoreThreads / 64];
+  __shared__ int s_ri[kScoreThreads / 64];
+  __shared__ int s_cnt[2];
+  // A scoring workgroup's prologue (a few dependent loads, the image copy, barriers) is a handful of instructions, but its
+  // waves are the YOUNGEST on their SIMDs and lose every issue arbitration against the five older workgroups in their
+  // rollout loops: measured 40 % of a workgroup's residence before its first trajectory point.  Raised priority until the
+  // image is in place gets it out of the way.
+  __builtin_amdgcn_s_setprio(3);
+  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  // The footprint and axis samples stay in registers until the image is copied, and go to LDS with it: ONE batch of
+  // loads in flight and one barrier instead of five dependent round trips and three barriers (a load takes several
+  // microseconds while 24 waves per CU gather from the distance grids).
+  const ScoreInputs in = loadInputs(pl, r);
+  if (threadIdx.x == 0) s_cnt[0] = s_cnt[1] = 0;
+  placeWindow(r);
+  loadImage(pl, r, in, s_fp, s_axis, s_dyn);
+  __builtin_amdgcn_s_setprio(0);
+  scoreSamples<false, CHUNK, AGG>(pl, r, s_fp, s_axis, s_dyn, s_rc, s_ri, s_cnt, nullptr);
+}
+// k_score_explicit(_agg): checkTrajectory's one sample, on an image built in the workgroup itself
+template <bool AGG>
+__device__ __forceinline__ void scoreExplicit(const PlannerDev& pl, uint32_t first, const float* explicit_sample) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ double s_rc[kScoreThreads / 64];
+  __shared__ int s_ri[kScoreThreads / 64];
+  __shared__ int s_cnt[2];
+  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  stageInputs<true>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
+  __syncthreads();
+  buildScreens(pl, r, s_dyn, reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes + score_bits_bytes(r.win)));
+  __syncthreads();
+  scoreSamples<true, 12, AGG>(pl, r, s_fp, s_axis, s_dyn, s_rc, s_ri, s_cnt, explicit_sample);
+}
 template <int CHUNK>
 __global__ __launch_bounds__(kScoreThreads) void k_score_gen(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  score_body<false, false, kScoreThreads, 2, CHUNK>(pl, first, explicit_sample);
+  scoreGen<CHUNK, false>(pl, first);
 }
-__global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev pl, uint32_t first) {
-  score_body<false, true, kScorePrepThreads, 1>(pl, first, nullptr);
-}
-__global__ __launch_bounds__(kScoreThreads) void k_score_prep_gen(PlannerDev pl, uint32_t first) {
-  score_body<false, false, kScoreThreads, 1>(pl, first, nullptr);
+__global__ __launch_bounds__(kScoreThreads) void k_score_gen_agg(PlannerDev pl, uint32_t first, const float* explicit_sample) {
+  scoreGen<16, true>(pl, first);
 }
 __global__ __launch_bounds__(kScoreThreads) void k_score_explicit(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  score_body<true, false, kScoreThreads>(pl, first, explicit_sample);
-}
-// the same two entry points with the general MapGridCostFunction step (aggregation Sum / Product, sideways shift)
-__global__ __launch_bounds__(kScoreThreads) void k_score_gen_agg(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  score_body<false, false, kScoreThreads, 2, 16, true>(pl, first, explicit_sample);
+  scoreExplicit<false>(pl, first, explicit_sample);
 }
 __global__ __launch_bounds__(kScoreThreads) void k_score_explicit_agg(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  score_body<true, false, kScoreThreads, 0, 12, true>(pl, first, explicit_sample);
+  scoreExplicit<true>(pl, first, explicit_sample);
 }
 
 size_t score_window_bytes(uint32_t win) {  // costmap window + the four per-cell screens
@@ -995,46 +1003,28 @@ uint32_t launch_score(const PlannerDev& pl_in, uint32_t first, uint32_t count, c
   const size_t win_bytes = score_window_bytes(pl.win);
   const size_t scratch = score_scratch_bytes((int)pl.win);  // only where the image is built
   if (explicit_sample) {
-    const size_t lds_x = win_bytes + scratch;
-    if (pl.mg_generic) {
-      if (lds_x > 48 * 1024) hipFuncSetAttribute((const void*)k_score_explicit_agg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
-      hipLaunchKernelGGL(k_score_explicit_agg, dim3(1, count), dim3(kScoreThreads), lds_x, s, pl, first, explicit_sample);
-      return 1;
-    }
-    if (lds_x > 48 * 1024) hipFuncSetAttribute((const void*)k_score_explicit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_x);
-    hipLaunchKernelGGL(k_score_explicit, dim3(1, count), dim3(kScoreThreads), lds_x, s, pl, first, explicit_sample);
+    launchScore(pl.mg_generic ? k_score_explicit_agg : k_score_explicit, dim3(1, count), kScoreThreads, win_bytes + scratch, s, pl, first,
+                explicit_sample);
     return 1;
   }
   if (score_sweep_applies(pl)) {
     // the prep launch builds all table rows (its LDS holds the whole image); a sweep workgroup loads one row group
     pl.tab_bytes = (uint32_t)score_table_bytes(pl);
     pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
-    const size_t lds_prep = win_bytes + score_table_bytes(pl) + scratch;
-    if (lds_prep > 48 * 1024) hipFuncSetAttribute((const void*)k_score_prep_tab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep);
-    hipLaunchKernelGGL(k_score_prep_tab, dim3(1, count), dim3(kScorePrepThreads), lds_prep, s, pl, first);
+    launchScore(k_score_prep_tab, dim3(1, count), kScorePrepThreads, win_bytes + score_table_bytes(pl) + scratch, s, pl, first);
     return launch_score_sweep(pl, first, count, s);
   }
   // the general path (no tables, or mg_generic: the general step has no table variant)
   pl.use_tables = 0;
   pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
   const uint32_t gen_blocks = (pl.max_samples + kScoreThreads - 1) / kScoreThreads;  // (score_blocks is the capacity of the partial results)
-  if (win_bytes + scratch > 48 * 1024) hipFuncSetAttribute((const void*)k_score_prep_gen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(win_bytes + scratch));
-  hipLaunchKernelGGL(k_score_prep_gen, dim3(1, count), dim3(kScoreThreads), win_bytes + scratch, s, pl, first);
-#define NAVGPU_SCORE_GEN(C)                                                                                                    \
-  {                                                                                                                            \
-    if (win_bytes > 48 * 1024) hipFuncSetAttribute((const void*)k_score_gen<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_bytes); \
-    hipLaunchKernelGGL(k_score_gen<C>, dim3(gen_blocks, count), dim3(kScoreThreads), win_bytes, s, pl, first, explicit_sample);          \
-  }
-  if (pl.mg_generic) {
-    if (win_bytes > 48 * 1024) hipFuncSetAttribute((const void*)k_score_gen_agg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_bytes);
-    hipLaunchKernelGGL(k_score_gen_agg, dim3(gen_blocks, count), dim3(kScoreThreads), win_bytes, s, pl, first, explicit_sample);
-    return gen_blocks;
-  }
-  if (pl.fp_chunk <= 6) NAVGPU_SCORE_GEN(6)
-  else if (pl.fp_chunk <= 9) NAVGPU_SCORE_GEN(9)
-  else if (pl.fp_chunk <= 12) NAVGPU_SCORE_GEN(12)
-  else NAVGPU_SCORE_GEN(16)
-#undef NAVGPU_SCORE_GEN
+  launchScore(k_score_prep_gen, dim3(1, count), kScoreThreads, win_bytes + scratch, s, pl, first);
+  auto gen = pl.mg_generic        ? k_score_gen_agg
+             : pl.fp_chunk <= 6  ? k_score_gen<6>
+             : pl.fp_chunk <= 9  ? k_score_gen<9>
+             : pl.fp_chunk <= 12 ? k_score_gen<12>
+                                 : k_score_gen<16>;
+  launchScore(gen, dim3(gen_blocks, count), kScoreThreads, win_bytes, s, pl, first, explicit_sample);
   return gen_blocks;
 }
 
@@ -1044,16 +1034,6 @@ extern "C" int navgpu_debug_prep_stats(unsigned long long* out16, int reset) {
   if (reset) {
     unsigned long long z[16] = {0};
     hipMemcpyToSymbol(HIP_SYMBOL(g_prep_stats), z, sizeof(z));
-  }
-  return 0;
-}
-#endif
-#if defined(NAVGPU_SCORE_STATS) || defined(NAVGPU_SCORE_TIMING)
-extern "C" int navgpu_debug_score_stats(unsigned long long* out8, int reset) {
-  if (out8) hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_score_stats), sizeof(unsigned long long) * 24);
-  if (reset) {
-    unsigned long long z[24] = {0};
-    hipMemcpyToSymbol(HIP_SYMBOL(g_score_stats), z, sizeof(z));
   }
   return 0;
 }

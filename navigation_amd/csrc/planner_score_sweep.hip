@@ -190,26 +190,7 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
     return (uint8_t)v;
   };
   const double inv_res = pl.inv_res;
-  // Costmap2D::worldToMap (costmap_2d.cpp:208-220) with the two fp64 divisions replaced by a multiply; exact: whenever the
-  // product is not clear of an integer by 1e-7 (error bound 5e-10 below 1e6 cells) the division is redone.
-  auto w2m = [&](double wx, double wy, uint32_t& mx, uint32_t& my) -> bool {
-    const double dx = wx - g.ox, dy = wy - g.oy;
-    const double qx = dx * inv_res, qy = dy * inv_res;
-    double fx = floor(qx), fy = floor(qy);
-    const double rx = qx - fx, ry = qy - fy;
-    if (__builtin_expect(fmin(rx, ry) < 1.0e-7 || fmax(rx, ry) > 1.0 - 1.0e-7, 0)) {
-      fx = !(dx >= 0.0) ? -1.0 : (qx >= 1.0e6 ? 1.0e6 : (double)(int)(dx / g.res));  // wx < origin -> false (costmap_2d.cpp:210)
-      fy = !(dy >= 0.0) ? -1.0 : (qy >= 1.0e6 ? 1.0e6 : (double)(int)(dy / g.res));
-    }
-    // v_cvt_i32_f64 saturates (a point left of / below the origin floors to a negative cell, one far beyond the grid to
-    // INT_MAX: both fail the size test as unsigned numbers), which a C++ cast does not promise
-    int ix, iy;
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(ix) : "v"(fx));
-    asm("v_cvt_i32_f64 %0, %1" : "=v"(iy) : "v"(fy));
-    mx = (uint32_t)ix;
-    my = (uint32_t)iy;
-    return mx < g.nx && my < g.ny;
-  };
+  const WorldToMapFast w2m{g, inv_res};
 
   // ---- CostmapModel::footprintCost at pose (x, y) with the rotated vertices of table entry te (costmap_model.cpp:50-142):
   // returns true when some vertex is off the map (footprint_cost = -1); else mx = the largest byte on the outline, in walk
@@ -688,17 +669,11 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
     } else {
       // scoreTrajectory's sum in critic order (a term that is 0 is not scaled: `if (cost != 0) cost *= scale`)
       total = 0.0;
-      auto add = [&](bool en, double value, double scale) {
-        if (!en) return;
-        double cost = value;
-        if (cost != 0) cost *= scale;
-        total += cost;
-      };
-      add(en_obs, (double)(s_obs[tid] & ~kWalkFailed), sc_obs);
-      add(en_gf, (double)d_gf, sc_gf);
-      add(en_al, (double)d_al, sc_al);
-      add(en_path, (double)d_path, sc_path);
-      add(en_goal, (double)d_goal, sc_goal);
+      addCritic(total, en_obs, (double)(s_obs[tid] & ~kWalkFailed), sc_obs);
+      addCritic(total, en_gf, (double)d_gf, sc_gf);
+      addCritic(total, en_al, (double)d_al, sc_al);
+      addCritic(total, en_path, (double)d_path, sc_path);
+      addCritic(total, en_goal, (double)d_goal, sc_goal);
     }
   }
   if (in_range && pl.sample_cost) {
@@ -753,36 +728,30 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
 // navgpu_configure_planner's max_axis).  The capacity check always holds: groups * ceil(nxy * R / 256) <= 2 * ceil(max_samples
 // / 256) + at + 2 = score_blocks, since groups * R < tab_nth + R <= 2 * tab_nth and groups <= tab_nth = at.
 static_assert(kSweepThreads <= 1024, "10 bits of lane in the walk queue's tags");
-static uint32_t score_sweep_blocks(const PlannerDev& pl) {
-  const uint32_t max_nxy = pl.max_samples / std::max(pl.tab_nth, 1u), groups = (pl.tab_nth + std::max(pl.tab_rows, 1u) - 1) / std::max(pl.tab_rows, 1u);
-  return groups * ((max_nxy * pl.tab_rows + kSweepThreads - 1) / kSweepThreads);
+// row groups x workgroups per group, for the largest (vx, vy) grid the configuration can produce
+static dim3 score_sweep_grid(const PlannerDev& pl, uint32_t count) {
+  const uint32_t rows = std::max(pl.tab_rows, 1u);
+  const uint32_t max_nxy = pl.max_samples / std::max(pl.tab_nth, 1u), groups = (pl.tab_nth + rows - 1) / rows;
+  return dim3((max_nxy * pl.tab_rows + kSweepThreads - 1) / kSweepThreads, groups, count);
 }
 bool score_sweep_applies(const PlannerDev& pl) {
-  return pl.use_tables && !pl.mg_generic && score_sweep_blocks(pl) <= pl.score_blocks;
+  const dim3 grid = score_sweep_grid(pl, 1);
+  return pl.use_tables && !pl.mg_generic && grid.x * grid.y <= pl.score_blocks;
 }
 uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) {
   const size_t lds = score_window_bytes(pl.win) + score_table_lds_bytes(pl);
-  // row groups x workgroups per group, for the largest (vx, vy) grid the configuration can produce
-  const uint32_t max_nxy = pl.max_samples / std::max(pl.tab_nth, 1u), groups = (pl.tab_nth + pl.tab_rows - 1) / pl.tab_rows;
-  const uint32_t bpg = (max_nxy * pl.tab_rows + kSweepThreads - 1) / kSweepThreads;
-  const uint32_t blocks = groups * bpg;  // (<= score_blocks: score_sweep_applies)
-#define NAVGPU_SCORE_SWEEP(C)                                                                                                             \
-  {                                                                                                                                       \
-    if (lds > 40 * 1024) {                                                                                                                \
-      hipFuncSetAttribute((const void*)k_score_sweep<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                     \
-      hipFuncSetAttribute((const void*)k_score_sweep<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-    }                                                                                                                                     \
-    if (pl.cfg.rollout_trig)                                                                                                              \
-      hipLaunchKernelGGL((k_score_sweep<C, true>), dim3(bpg, groups, count), dim3(kSweepThreads), lds, s, pl, first);                      \
-    else                                                                                                                                  \
-      hipLaunchKernelGGL((k_score_sweep<C, false>), dim3(bpg, groups, count), dim3(kSweepThreads), lds, s, pl, first);                     \
-  }
-  if (pl.fp_chunk <= 6) NAVGPU_SCORE_SWEEP(6)
-  else if (pl.fp_chunk <= 9) NAVGPU_SCORE_SWEEP(9)
-  else if (pl.fp_chunk <= 12) NAVGPU_SCORE_SWEEP(12)
-  else NAVGPU_SCORE_SWEEP(16)
-#undef NAVGPU_SCORE_SWEEP
-  return blocks;
+  const dim3 grid = score_sweep_grid(pl, count);  // (grid.x * grid.y <= score_blocks: score_sweep_applies)
+  // (allowed from 40 KB: beside the dynamic LDS the kernel holds 10 KB of static LDS, the walk queue)
+  const bool trigf = pl.cfg.rollout_trig != 0;
+  if (pl.fp_chunk <= 6)
+    launchScore<40 * 1024>(trigf ? k_score_sweep<6, true> : k_score_sweep<6, false>, grid, kSweepThreads, lds, s, pl, first);
+  else if (pl.fp_chunk <= 9)
+    launchScore<40 * 1024>(trigf ? k_score_sweep<9, true> : k_score_sweep<9, false>, grid, kSweepThreads, lds, s, pl, first);
+  else if (pl.fp_chunk <= 12)
+    launchScore<40 * 1024>(trigf ? k_score_sweep<12, true> : k_score_sweep<12, false>, grid, kSweepThreads, lds, s, pl, first);
+  else
+    launchScore<40 * 1024>(trigf ? k_score_sweep<16, true> : k_score_sweep<16, false>, grid, kSweepThreads, lds, s, pl, first);
+  return grid.x * grid.y;
 }
 
 #ifdef NAVGPU_SWEEP_COUNTS

@@ -312,7 +312,7 @@ __global__ __launch_bounds__(64) void k_stage_poses(PoseChunk c) {
 }
 void launch_stage_poses(const PoseChunk& c, hipStream_t s) { hipLaunchKernelGGL(k_stage_poses, dim3(1), dim3(64), 0, s, c); }
 
-// sin / cos of the headings as score_body evaluates them (navgpu_device_sincos: the floating-point contract, checkable)
+// sin / cos of the headings as scoreSamples evaluates them (navgpu_device_sincos: the floating-point contract, checkable)
 __global__ void k_sincos(const double* th, uint32_t n, double* sn, double* cs) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) sincos(th[i], &sn[i], &cs[i]);

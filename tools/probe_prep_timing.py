@@ -21,8 +21,8 @@ for g in groups:
 fn(out, 0)
 groups_n = G
 n = max(out[15], 1)
-names = ["stage footprint / samples / window bytes", "raw bits", "dilation", "MapGrid screens", "heading sequences", "trig + rotated footprints",
-         "image store", "free distance, scalars, reject bytes"]
+names = ["stageInputs: footprint / samples / window bytes", "buildScreens: raw bits, dilation, MapGrid screens", "buildTables: headings, trig, rotated footprints",
+         "storeImage", "storeSweepScalars: free distance, scalars, reject bytes"]
 tot = 0.0
 for i, nm in enumerate(names):
     us = out[i] / n * 10.0 / 1e3  # wall_clock64: 100 MHz
