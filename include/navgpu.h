@@ -879,6 +879,55 @@ int navgpu_amcl_odom_configure(navgpu_amcl* amcl, const navgpu_amcl_odom_params*
 int navgpu_amcl_update_action(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* odom, int32_t draw_source,
                               uint64_t* drand48_state, uint64_t seed, int32_t* status);
 
+/* ---- amcl filter initialisation: pf_init and pf_init_model (global localisation) ---- */
+/* Both calls leave each filter's set as pf_init leaves it: sample_count = the handle's max_samples, every weight 1.0 / max_samples,
+ * w_slow = w_fast = 0, converged 0, the kd-tree leaf count = the number of distinct histogram bins of the new set, and the
+ * clusters and set mean / cov of pf_cluster_stats, numbered by lowest sample index as after update_resample (get_clusters is
+ * valid right after an init).  draw_source is NAVGPU_AMCL_DRAW_DRAND48 or NAVGPU_AMCL_DRAW_DEVICE, with update_action's
+ * conventions: drand48_state[k] in and out (not read in device mode), the device call counter +1 per call for every filter
+ * that ran (shared with update_action / update_resample).  status[k] per filter; a filter that fails is untouched, its drand48
+ * state included, and so are the filters outside the slice.  A pose that is not finite or has |bin| > 2^20 - 2 fails the filter
+ * with NAVGPU_ERR_INVALID (a negative eigenvalue of cov, whose sqrt the reference takes, gives NaN poses). */
+/* replaces: pf_init(pf, mean, cov) (pf.c:138-176) with pf_pdf_gaussian_alloc / _sample (pf_pdf.c:46-126).  mean = count x 3,
+ * cov = count x 9 (row-major).  The host decomposes cov as pf_matrix_unitary does (Householder tridiagonalisation and QL
+ * iteration, fp64, the same operation order): rotation cr and cd[j] = sqrt(eigenvalue j), eigenvalues ascending.  Per sample
+ * r[j] = pf_ran_gaussian(cd[j]) for j = 0, 1, 2, then x[i] = mean[i] + cr[i][0] r[0] + cr[i][1] r[1] + cr[i][2] r[2], left to right.
+ * drand48: the 3 max_samples deviates of update_action's drand48 mode, in sample order; pass the state srand48(++pf_pdf_seed)
+ *   leaves, (seed << 16) | 0x330E.  Device: Philox stream 3, counter {draw, filter | 3 << 16, call counter}; sample i takes draws
+ *   2 i and 2 i + 1 and update_action's Box-Muller deviates z0, z1, z2, each scaled as cd[j] * z.
+ * NAVGPU_ERR_INVALID for NULL arguments or when any filter failed (a non-finite mean or cov, a state >= 2^48, a bad pose). */
+int navgpu_amcl_init_gaussian(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* mean, const double* cov,
+                              int32_t draw_source, uint64_t* drand48_state, uint64_t seed, int32_t* status);
+typedef struct {
+  double starting_weight_threshold; /* uniform_pose_starting_weight_threshold                                        */
+  double deweight_multiplier;       /* uniform_pose_deweight_multiplier                                              */
+  uint64_t max_candidates;          /* per filter per call; 0 = 100 x max_samples; at most 2^40, 2^32 with device draws */
+} navgpu_amcl_uniform_params;
+/* replaces: pf_init_model(pf, AmclNode::uniformPoseGenerator, node) (pf.c:180-213, amcl_node.cpp:1200-1263).  A candidate is
+ * randomFreeSpacePose over the filter's free cells: cells with occ_state -1 and map_occ_dist > the configured
+ * non_free_space_radius (0 before navgpu_amcl_laser_configure), x-major as amcl_node.cpp:1026-1033 lists them; the cell centre
+ * and theta = u * 2 pi - pi.  Candidates are scored only when a scan is given (ranges_xy, range_counts and range_max as in
+ * update_sensor; ranges_xy == NULL && range_counts == NULL means last_laser_data_ == NULL), starting_weight_threshold > 0 and
+ * 0 <= deweight_multiplier < 1 (amcl_node.cpp:1253).  The score is scorePose's: the configured laser model on a one-sample set of
+ * weight 1.0, converged 0 (no beam skipping), subsampled as update_sensor does, with the filter's laser pose; then the map
+ * factors when it is > 0.  A sample retries while score < gw, gw *= deweight_multiplier after every retry; gw restarts at the
+ * threshold for every sample; a NaN score accepts.
+ * drand48: candidate j of a filter takes values 2 j (cell) and 2 j + 1 (theta) of its stream (no zero skipping); the state comes
+ *   back advanced by 2 x candidates_used[k].  Device: Philox stream 4, counter {sample, filter | 4 << 16, call counter (its low 32
+ *   bits), retry}: each sample runs its own retry sequence, distributed as the reference's draws, not its stream.
+ *   Every candidate drawn counts towards the filter's total at once, and all its samples stop when the total passes
+ *   max_candidates, so a call draws at most about max_candidates + max_samples candidates per filter.
+ * candidates_used[k] (may be NULL): the candidates drawn (max_samples when unscored).  Defined where the reference is not:
+ * - a map without free cells gives status[k] = NAVGPU_ERR_INVALID;
+ * - a filter that needs more than max_candidates candidates gets status[k] = NAVGPU_ERR_CAPACITY.  The reference loops as long as
+ *   it takes (forever when no candidate can reach the decayed threshold, e.g. with negative scores);
+ * - the beam model with 1 <= range_count < max_beams (the reference's loop never ends) gives NAVGPU_ERR_INVALID.
+ * Returns NAVGPU_ERR_CAPACITY when a filter hit the cap, else NAVGPU_ERR_INVALID when any filter failed (the others ran);
+ * NAVGPU_ERR_STATE for a filter without a map or a scan before navgpu_amcl_laser_configure (nothing runs then). */
+int navgpu_amcl_init_uniform(navgpu_amcl* amcl, uint32_t first, uint32_t count, const navgpu_amcl_uniform_params* params,
+                             const double* ranges_xy, const uint32_t* range_counts, const double* range_max, int32_t draw_source,
+                             uint64_t* drand48_state, uint64_t seed, uint64_t* candidates_used, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

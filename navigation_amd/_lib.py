@@ -233,6 +233,12 @@ AMCL_ODOM_DIFF, AMCL_ODOM_OMNI, AMCL_ODOM_DIFF_CORRECTED, AMCL_ODOM_OMNI_CORRECT
 AMCL_DRAW_DRAND48 = 2
 
 
+class AmclUniformParams(C.Structure):
+    """Mirror of navgpu_amcl_uniform_params (include/navgpu.h): uniform_pose_starting_weight_threshold,
+    uniform_pose_deweight_multiplier and the per-filter candidate cap (0: 100 x max_samples)."""
+    _fields_ = [("starting_weight_threshold", C.c_double), ("deweight_multiplier", C.c_double), ("max_candidates", C.c_uint64)]
+
+
 class AmclOdomParams(C.Structure):
     """Mirror of navgpu_amcl_odom_params (include/navgpu.h): odom_model_t and AMCLOdom's alpha1..alpha5.  Defaults: amcl_node's
     odom_model_type "diff" and odom_alpha1..5 0.2 (amcl_node.cpp)."""
@@ -365,6 +371,8 @@ SYMBOLS = [
     ("navgpu_amcl_get_rng_counters", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_amcl_odom_configure", C.c_int, [vp, C.POINTER(AmclOdomParams)]),
     ("navgpu_amcl_update_action", C.c_int, [vp, u32, u32, vp, i32, vp, C.c_uint64, vp]),
+    ("navgpu_amcl_init_gaussian", C.c_int, [vp, u32, u32, vp, vp, i32, vp, C.c_uint64, vp]),
+    ("navgpu_amcl_init_uniform", C.c_int, [vp, u32, u32, C.POINTER(AmclUniformParams), vp, vp, vp, i32, vp, C.c_uint64, vp, vp]),
 ]
 
 

@@ -12,42 +12,12 @@
 // sequential loop of one lane where the reference's order decides the result.
 #include <hip/hip_runtime.h>
 
-#include "navgpu_amcl.h"
+#include "amcl_pf_stages.h"
 
 namespace navgpu {
 
 namespace {
-constexpr int kRsThreads = 1024;
-constexpr int kKeyBits = 21;
-constexpr int64_t kKeyBias = 1 << 20;
-constexpr double kKeyLimit = (double)(kKeyBias - 2);  // |bin| <= 2^20 - 2: the +-1 neighbours of a bin stay inside its field
-constexpr uint64_t kNoKey = ~0ull;
 constexpr uint32_t kStartDraw = 0xFFFFFFFFu;  // draw index of systematic_sample_start (device draws)
-
-// AmclNode::randomFreeSpacePose (amcl_node.cpp:1200-1212) with u_cell, u_theta in place of its two drand48() calls
-__device__ bool freePose(const AmclMapDev& m, double u_cell, double u_theta, double* out) {
-  if (m.n_free <= 0 || !m.free_cells) return false;
-  const unsigned idx = (unsigned)(u_cell * (double)m.n_free);
-  if (idx >= (unsigned)m.n_free) return false;
-  const int cell = m.free_cells[idx], i = cell % m.sx, j = cell / m.sx;
-  out[0] = m.ox + (i - m.sx / 2) * m.scale;  // MAP_WXGX / MAP_WYGY (map.h:133-134)
-  out[1] = m.oy + (j - m.sy / 2) * m.scale;
-  out[2] = u_theta * 2 * M_PI - M_PI;
-  return true;
-}
-
-// pf_kdtree_insert's key (pf_kdtree.c:116-118) packed as three biased 21-bit fields; false for a non-finite pose or |bin| > 2^20 - 2
-__device__ __forceinline__ bool binKey(const double* pose, uint64_t& key) {
-  const double size[3] = {0.50, 0.50, (10 * M_PI / 180)};
-  uint64_t k = 0;
-  for (int a = 0; a < 3; ++a) {
-    const double b = floor(pose[a] / size[a]);
-    if (!(b >= -kKeyLimit && b <= kKeyLimit)) return false;
-    k = (k << kKeyBits) | (uint64_t)((int64_t)b + kKeyBias);
-  }
-  key = k;
-  return true;
-}
 
 // pf_resample_limit (pf.c:567-588); n above max_samples (where the reference's int conversion could overflow) is max_samples
 __device__ int kldLimit(const AmclResampleParamsDev& p, int k) {
@@ -76,62 +46,6 @@ __device__ __forceinline__ int pickIndex(const double* c, int n, double r, int f
       lo = mid + 1;
   }
   return lo;
-}
-
-__device__ __forceinline__ int findKey(const uint64_t* keys, int n, uint64_t k) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (keys[mid] < k)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return lo < n && keys[lo] == k ? lo : -1;
-}
-
-// exclusive prefix sum of a[0, n) in place; every thread of the workgroup calls it; returns the total
-__device__ int blockScan(int* a, int n, int* sh) {
-  int carry = 0;
-  const int t = threadIdx.x, nt = blockDim.x;
-  for (int base = 0; base < n; base += nt) {
-    const int i = base + t;
-    const int v = i < n ? a[i] : 0;
-    sh[t] = v;
-    __syncthreads();
-    for (int off = 1; off < nt; off <<= 1) {
-      const int x = t >= off ? sh[t - off] : 0;
-      __syncthreads();
-      sh[t] += x;
-      __syncthreads();
-    }
-    if (i < n) a[i] = carry + sh[t] - v;
-    carry += sh[nt - 1];
-    __syncthreads();
-  }
-  return carry;
-}
-
-// ascending bitonic sort of the pairs (key, idx) over P (a power of two) slots
-__device__ void bitonicSort(uint64_t* key, uint32_t* idx, uint32_t P) {
-  for (uint32_t k = 2; k <= P; k <<= 1)
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t i = threadIdx.x; i < P; i += blockDim.x) {
-        const uint32_t l = i ^ j;
-        if (l > i) {
-          const uint64_t ki = key[i], kl = key[l];
-          const uint32_t ii = idx[i], il = idx[l];
-          const bool gt = ki > kl || (ki == kl && ii > il);
-          if (gt == ((i & k) == 0)) {
-            key[i] = kl;
-            key[l] = ki;
-            idx[i] = il;
-            idx[l] = ii;
-          }
-        }
-      }
-      __syncthreads();
-    }
 }
 
 __global__ __launch_bounds__(kRsThreads) void k_amcl_resample(AmclDev d, AmclResampleDev r, AmclResampleParamsDev p, uint32_t first,
@@ -323,122 +237,13 @@ __global__ __launch_bounds__(kRsThreads) void k_amcl_resample(AmclDev d, AmclRes
   }
   const int count = s_count;
 
-  // 6. occupied bins of set b (runs of the sorted keys whose first sample is < count), ascending, and each sample's bin
-  for (int q = t; q < (int)P; q += nt)
-    a[q] = skey[q] != kNoKey && (int)sidx[q] < count && (q == 0 || skey[q] != skey[q - 1]);
-  __syncthreads();
-  const int U = blockScan(a, P, sh);
-  for (int q = t; q < (int)P; q += nt) {
-    if (skey[q] == kNoKey || (int)sidx[q] >= count) continue;
-    const bool start = q == 0 || skey[q] != skey[q - 1];
-    const int u = start ? a[q] : a[q] - 1;
-    b[sidx[q]] = u;
-    if (start) {
-      ukey[u] = skey[q];
-      label[u] = (int)sidx[q];
-    }
-  }
-  __syncthreads();
-
-  // 7. connected components over the 26-neighbourhood, no angular wrap (pf_kdtree.c:407-437): every bin takes the smallest label
-  //    of its neighbours and of its label's own bin until nothing changes; the fixed point is the component's lowest sample index
-  for (;;) {
-    if (t == 0) s_changed = 0;
-    __syncthreads();
-    for (int u = t; u < U; u += nt) {
-      const uint64_t key = ukey[u];
-      int l = label[u];
-      for (int o = 0; o < 27; ++o) {
-        if (o == 13) continue;
-        const int64_t dx = o / 9 - 1, dy = (o % 9) / 3 - 1, dt = o % 3 - 1;
-        const uint64_t nk = key + (uint64_t)((dx << (2 * kKeyBits)) + (dy << kKeyBits) + dt);
-        const int v = findKey(ukey, U, nk);
-        if (v >= 0) l = min(l, label[v]);
-      }
-      l = min(l, label[b[l]]);
-      if (l < label[u]) {
-        label[u] = l;
-        s_changed = 1;
-      }
-    }
-    __syncthreads();
-    if (!s_changed) break;
-    __syncthreads();
-  }
-
-  // 8. clusters numbered by their lowest sample index; cos / sin of every angle
-  for (int i = t; i < count; i += nt) {
-    a[i] = label[b[i]] == i;
-    cs[2 * (size_t)i] = cos(cand[3 * (size_t)i + 2]);
-    cs[2 * (size_t)i + 1] = sin(cand[3 * (size_t)i + 2]);
-  }
-  __syncthreads();
-  const int C = blockScan(a, count, sh);
-  for (int q = t; q < (int)P; q += nt) {
-    if (q < count) {
-      skey[q] = (uint64_t)a[label[b[q]]];
-      sidx[q] = (uint32_t)q;
-    } else {
-      skey[q] = kNoKey;
-      sidx[q] = 0xFFFFFFFFu;
-    }
-  }
-  __syncthreads();
-  bitonicSort(skey, sidx, P);
-  for (int q = t; q < count; q += nt)
-    if (q == 0 || skey[q] != skey[q - 1]) cstart[skey[q]] = q;
-  __syncthreads();
-
-  // 9. pf_cluster_stats (pf.c:592-720): per cluster in one lane, summed in sample order
-  const double total = (double)count, w = 1.0 / total;
-  int* cl_count = r.cl_count + fo;
-  double* cl = r.cl_stats + fo * 13;
-  for (int k = t; k < C; k += nt) {
-    const int s = cstart[k], e = k + 1 < C ? cstart[k + 1] : count;
-    double weight = 0.0, m[4] = {0.0, 0.0, 0.0, 0.0}, cc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-    for (int q = s; q < e; ++q) {
-      const size_t i = sidx[q];
-      const double v[2] = {cand[3 * i], cand[3 * i + 1]};
-      weight += w;
-      m[0] += w * v[0];
-      m[1] += w * v[1];
-      m[2] += w * cs[2 * i];
-      m[3] += w * cs[2 * i + 1];
-      for (int j = 0; j < 2; j++)
-        for (int l = 0; l < 2; l++) cc[j][l] += w * v[j] * v[l];
-    }
-    double* o = cl + 13 * (size_t)k;
-    const double mean[3] = {m[0] / weight, m[1] / weight, atan2(m[3], m[2])};
-    o[0] = weight;
-    o[1] = mean[0];
-    o[2] = mean[1];
-    o[3] = mean[2];
-    for (int j = 0; j < 9; ++j) o[4 + j] = 0.0;
-    for (int j = 0; j < 2; j++)
-      for (int l = 0; l < 2; l++) o[4 + 3 * j + l] = cc[j][l] / weight - mean[j] * mean[l];
-    o[4 + 8] = -2 * log(sqrt(m[2] * m[2] + m[3] * m[3]));
-    cl_count[k] = e - s;
-  }
-  if (t == 0) {  // the set's statistics
-    double weight = 0.0, m[4] = {0.0, 0.0, 0.0, 0.0}, cc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-    for (int i = 0; i < count; ++i) {
-      const double v[2] = {cand[3 * (size_t)i], cand[3 * (size_t)i + 1]};
-      weight += w;
-      m[0] += w * v[0];
-      m[1] += w * v[1];
-      m[2] += w * cs[2 * (size_t)i];
-      m[3] += w * cs[2 * (size_t)i + 1];
-      for (int j = 0; j < 2; j++)
-        for (int l = 0; l < 2; l++) cc[j][l] += w * v[j] * v[l];
-    }
-    double* o = r.set_stats + 12 * (size_t)f;
-    const double mean[3] = {m[0] / weight, m[1] / weight, atan2(m[3], m[2])};
-    for (int j = 0; j < 3; ++j) o[j] = mean[j];
-    for (int j = 0; j < 9; ++j) o[3 + j] = 0.0;
-    for (int j = 0; j < 2; j++)
-      for (int l = 0; l < 2; l++) o[3 + 3 * j + l] = cc[j][l] / weight - mean[j] * mean[l];
-    o[3 + 8] = -2 * log(sqrt(m[2] * m[2] + m[3] * m[3]));
-  }
+  // 6-9. occupied bins of set b, their components, the clusters and their statistics (amcl_pf_stages.h)
+  const SetWork sw{cand, cs, skey, sidx, a, b, label, ukey, cstart, P};
+  const int U = occupiedBins(sw, count, sh);
+  connectComponents(sw, U, &s_changed);
+  const int C = numberClusters(sw, count, sh);
+  clusterStats(sw, count, C, r.cl_count + fo, r.cl_stats + fo * 13, r.set_stats + 12 * (size_t)f);
+  const double total = (double)count;
   if (t == 64) {  // pf_update_converged's means (pf.c:230-240), in another wave
     double mx = 0, my = 0;
     for (int i = 0; i < count; ++i) {

@@ -15,12 +15,18 @@ struct AmclMap {
   float* dist = nullptr;
   int32_t* free_cells = nullptr;  // occ_state == -1, x-major (AmclNode::free_space_indices, amcl_node.cpp:1028-1033)
   int n_free = 0;
+  // the same restricted to map_occ_dist > radius, as the node builds it (init_uniform); rebuilt when the radius or distances change
+  int32_t* free_r = nullptr;
+  int n_free_r = 0;
+  double free_r_radius = 0;
+  bool free_r_valid = false;
   int sx = 0, sy = 0;
   double scale = 0, ox = 0, oy = 0, max_occ_dist = 0;
   ~AmclMap() {
     if (occ) hipFree(occ);
     if (dist) hipFree(dist);
     if (free_cells) hipFree(free_cells);
+    if (free_r) hipFree(free_r);
   }
 };
 }  // namespace
@@ -55,6 +61,7 @@ struct navgpu_amcl {
   bool oconfigured = false;
   double2* d_records = nullptr;                 // [n][3 max_samples] drand48 Gaussian records {x2, s}
   AmclOdomFilterDev* d_ofilters = nullptr;      // [n]
+  AmclInitFilterDev* d_ifilters = nullptr;      // [n] init calls (navgpu_amcl_init_*)
   template <class T>
   int alloc(T** p, size_t count) {
     void* q = nullptr;
@@ -69,6 +76,36 @@ struct navgpu_amcl {
     return NAVGPU_OK;
   }
   bool rangeOk(uint32_t first, uint32_t count) const { return count > 0 && first < n && count <= n - first; }
+  // the resampling workspace (also the init's), allocated by the first call that needs it
+  int resampleWorkspace() {
+    if (rs_ready) return NAVGPU_OK;
+    const size_t ms = d.max_samples, n = this->n;
+    AmclResampleDev& r = rs;
+    uint32_t P = 1;
+    while (P < ms) P <<= 1;
+    r.P = P;
+    int rc = 0;
+#define A(ptr, cnt) \
+  if (!rc) rc = alloc(&(ptr), (size_t)(cnt));
+    A(r.c, n * (ms + 1));
+    A(r.cand, n * ms * 3);
+    A(r.cs, n * ms * 2);
+    A(r.skey, n * P);
+    A(r.sidx, n * P);
+    A(r.a, n * P);
+    A(r.b, n * P);
+    A(r.label, n * ms);
+    A(r.ukey, n * ms);
+    A(r.cstart, n * ms);
+    A(r.cl_count, n * ms);
+    A(r.cl_stats, n * ms * 13);
+    A(r.set_stats, n * 12);
+#undef A
+    if (rc) return rc;
+    HIP_TRY(waitStream(stream));
+    rs_ready = true;
+    return NAVGPU_OK;
+  }
   int uploadMaps() {
     HIP_TRY(hipMemcpyAsync(d.maps, map_desc.data(), sizeof(AmclMapDev) * n, hipMemcpyHostToDevice, stream));
     HIP_TRY(waitStream(stream));
@@ -200,6 +237,20 @@ int32_t leafCount(const double* poses, int n) {
   return (int32_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
 }
 
+// The models' subsampling step of a scan (amcl_laser.cpp:265, 334-338, 417-421, 637-641); < 1 where the beam model's loop would
+// never end.  max_beams >= 2.
+int beamStep(const navgpu_amcl_laser_params& P, int rcount) {
+  int step;
+  if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB) {
+    step = (int)ceil(rcount / static_cast<double>(P.max_beams));
+    if (step < 1) step = 1;
+  } else {
+    step = (rcount - 1) / (P.max_beams - 1);
+    if (step < 1 && P.model_type != NAVGPU_AMCL_MODEL_BEAM) step = 1;
+  }
+  return step;
+}
+
 // Maps of a slice: `src` is OccupancyGrid data (height x width, scaled up by `factor` on the device) or, with `cells`, map_t
 // occ_state values copied as they are (factor 1); scale and the centre origin (ox, oy) are map_t's own.
 int setMaps(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* src, uint32_t width, uint32_t height, int factor, bool cells,
@@ -298,6 +349,7 @@ int navgpu_amcl_set_distance_map(navgpu_amcl* h, uint32_t first, uint32_t count,
     const AmclMap& m = *h->maps[first + k];
     const size_t cells = (size_t)m.sx * m.sy;
     HIP_TRY(hipMemcpyAsync(m.dist, distances + off, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    h->maps[first + k]->free_r_valid = false;
     if (!shared) off += cells;
   }
   HIP_TRY(waitStream(h->stream));
@@ -418,14 +470,7 @@ int navgpu_amcl_update_sensor(navgpu_amcl* h, uint32_t first, uint32_t count, co
   for (uint32_t k = 0; k < count; ++k) {
     const int rcount = (int)range_counts[k];
     const uint32_t f = first + k;
-    int step;
-    if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB) {
-      step = (int)ceil(rcount / static_cast<double>(P.max_beams));
-      if (step < 1) step = 1;
-    } else {
-      step = (rcount - 1) / (P.max_beams - 1);
-      if (step < 1 && P.model_type != NAVGPU_AMCL_MODEL_BEAM) step = 1;
-    }
+    const int step = beamStep(P, rcount);
     AmclFilterDev& e = fd[k];
     e.sample_count = h->sample_count[f];
     e.converged = h->converged[f];
@@ -549,32 +594,7 @@ int navgpu_amcl_update_resample(navgpu_amcl* h, uint32_t first, uint32_t count, 
       }
   }
   AmclResampleDev& r = h->rs;
-  if (!h->rs_ready) {
-    uint32_t P = 1;
-    while (P < ms) P <<= 1;
-    r.P = P;
-    const size_t n = h->n;
-    int rc = 0;
-#define A(ptr, cnt) \
-  if (!rc) rc = h->alloc(&(ptr), (size_t)(cnt));
-    A(r.c, n * (ms + 1));
-    A(r.cand, n * ms * 3);
-    A(r.cs, n * ms * 2);
-    A(r.skey, n * P);
-    A(r.sidx, n * P);
-    A(r.a, n * P);
-    A(r.b, n * P);
-    A(r.label, n * ms);
-    A(r.ukey, n * ms);
-    A(r.cstart, n * ms);
-    A(r.cl_count, n * ms);
-    A(r.cl_stats, n * ms * 13);
-    A(r.set_stats, n * 12);
-#undef A
-    if (rc) return rc;
-    HIP_TRY(waitStream(h->stream));
-    h->rs_ready = true;
-  }
+  if (int rc = h->resampleWorkspace()) return rc;
   // supplied draws: {u_flag, u_pick} pairs (multinomial) then the random-pose pool, in one upload
   const size_t u_doubles = (!dev && !sys) ? (size_t)count * ms * 2 : 0, bytes = sizeof(double) * (u_doubles + 3 * pool_total);
   r.u = nullptr;
@@ -819,6 +839,405 @@ int navgpu_amcl_update_action(navgpu_amcl* h, uint32_t first, uint32_t count, co
       ++h->rng_ctr[first + k];
     else if (fd[k].active)
       drand48_state[k] = fd[k].state;
+  }
+  return rc;
+}
+
+}  // extern "C"
+
+namespace {
+// pf_matrix_unitary (pf_vector.c:222-276): the eigen-decomposition of a symmetric 3 x 3 matrix by Householder reduction to
+// tridiagonal form, then the implicit-shift QL iteration, eigenvalues ascending (the EISPACK tred2 / tql2 pair as JAMA states
+// it).  Every operation keeps the order of that formulation, so the host's IEEE fp64 (no contraction) reproduces the
+// reference's rotation and eigenvalues bit for bit.  false when the iteration does not settle (a non-finite matrix).
+bool symmetricEigen3(const double a[9], double vec[3][3], double val[3]) {
+  double* const dg = val;  // the diagonal as the reduction and the iteration go on
+  double off[3];           // the sub-diagonal
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) vec[r][c] = a[3 * r + c];
+  for (int c = 0; c < 3; ++c) dg[c] = vec[2][c];
+  // 1. Householder: row `row` of the remaining block is folded onto the sub-diagonal, rows 2 then 1
+  for (int row = 2; row >= 1; --row) {
+    double norm1 = 0.0, hh = 0.0;
+    for (int k = 0; k < row; ++k) norm1 = norm1 + fabs(dg[k]);
+    if (norm1 == 0.0) {
+      off[row] = dg[row - 1];
+      for (int c = 0; c < row; ++c) {
+        dg[c] = vec[row - 1][c];
+        vec[row][c] = 0.0;
+        vec[c][row] = 0.0;
+      }
+      dg[row] = hh;
+      continue;
+    }
+    for (int k = 0; k < row; ++k) {
+      dg[k] /= norm1;
+      hh += dg[k] * dg[k];
+    }
+    double lead = dg[row - 1], root = sqrt(hh);
+    if (lead > 0) root = -root;
+    off[row] = norm1 * root;
+    hh = hh - lead * root;
+    dg[row - 1] = lead - root;
+    for (int c = 0; c < row; ++c) off[c] = 0.0;
+    for (int c = 0; c < row; ++c) {
+      const double u = dg[c];
+      vec[c][row] = u;
+      double acc = off[c] + vec[c][c] * u;
+      for (int k = c + 1; k <= row - 1; ++k) {
+        acc += vec[k][c] * dg[k];
+        off[k] += vec[k][c] * u;
+      }
+      off[c] = acc;
+    }
+    double dot = 0.0;
+    for (int c = 0; c < row; ++c) {
+      off[c] /= hh;
+      dot += off[c] * dg[c];
+    }
+    const double half = dot / (hh + hh);
+    for (int c = 0; c < row; ++c) off[c] -= half * dg[c];
+    for (int c = 0; c < row; ++c) {
+      const double u = dg[c], q = off[c];
+      for (int k = c; k <= row - 1; ++k) vec[k][c] -= (u * off[k] + q * dg[k]);
+      dg[c] = vec[row - 1][c];
+      vec[row][c] = 0.0;
+    }
+    dg[row] = hh;
+  }
+  // 2. the accumulated transformation
+  for (int c = 0; c < 2; ++c) {
+    vec[2][c] = vec[c][c];
+    vec[c][c] = 1.0;
+    const double hh = dg[c + 1];
+    if (hh != 0.0) {
+      for (int k = 0; k <= c; ++k) dg[k] = vec[k][c + 1] / hh;
+      for (int j = 0; j <= c; ++j) {
+        double acc = 0.0;
+        for (int k = 0; k <= c; ++k) acc += vec[k][c + 1] * vec[k][j];
+        for (int k = 0; k <= c; ++k) vec[k][j] -= acc * dg[k];
+      }
+    }
+    for (int k = 0; k <= c; ++k) vec[k][c + 1] = 0.0;
+  }
+  for (int c = 0; c < 3; ++c) {
+    dg[c] = vec[2][c];
+    vec[2][c] = 0.0;
+  }
+  vec[2][2] = 1.0;
+  off[0] = 0.0;
+  // 3. QL with implicit shifts on the tridiagonal (dg, off)
+  off[0] = off[1];
+  off[1] = off[2];
+  off[2] = 0.0;
+  double shift = 0.0, bound = 0.0;
+  const double eps = 0x1p-52;
+  for (int l = 0; l < 3; ++l) {
+    const double here = fabs(dg[l]) + fabs(off[l]);
+    bound = bound > here ? bound : here;
+    int m = l;
+    while (m < 2 && !(fabs(off[m]) <= eps * bound)) ++m;  // off[2] == 0 always stops the search
+    if (m > l) {
+      int iter = 0;
+      do {
+        if (++iter > 64) return false;
+        const double g0 = dg[l];
+        double p = (dg[l + 1] - g0) / (2.0 * off[l]);
+        double r = sqrt(p * p + 1.0 * 1.0);
+        if (p < 0) r = -r;
+        dg[l] = off[l] / (p + r);
+        dg[l + 1] = off[l] * (p + r);
+        const double next = dg[l + 1];
+        double h = g0 - dg[l];
+        for (int i = l + 2; i < 3; ++i) dg[i] -= h;
+        shift = shift + h;
+        p = dg[m];
+        double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
+        const double el1 = off[l + 1];
+        for (int i = m - 1; i >= l; --i) {
+          c3 = c2;
+          c2 = c;
+          s2 = s;
+          const double g = c * off[i];
+          h = c * p;
+          r = sqrt(p * p + off[i] * off[i]);
+          off[i + 1] = s * r;
+          s = off[i] / r;
+          c = p / r;
+          p = c * dg[i] - s * g;
+          dg[i + 1] = h + s * (c * g + s * dg[i]);
+          for (int k = 0; k < 3; ++k) {
+            const double v1 = vec[k][i + 1];
+            vec[k][i + 1] = s * vec[k][i] + c * v1;
+            vec[k][i] = c * vec[k][i] - s * v1;
+          }
+        }
+        p = -s * s2 * c3 * el1 * off[l] / next;
+        off[l] = s * p;
+        dg[l] = c * p;
+      } while (fabs(off[l]) > eps * bound);
+    }
+    dg[l] = dg[l] + shift;
+    off[l] = 0.0;
+  }
+  // 4. ascending order, columns with them (selection of the smallest, as the reference)
+  for (int i = 0; i < 2; ++i) {
+    int k = i;
+    double p = dg[i];
+    for (int j = i + 1; j < 3; ++j)
+      if (dg[j] < p) {
+        k = j;
+        p = dg[j];
+      }
+    if (k != i) {
+      dg[k] = dg[i];
+      dg[i] = p;
+      for (int j = 0; j < 3; ++j) std::swap(vec[j][i], vec[j][k]);
+    }
+  }
+  return true;
+}
+
+// 48-bit LCG state advanced k steps (drand48's a = 0x5DEECE66D, c = 0xB)
+uint64_t drand48Advance(uint64_t x, uint64_t k) {
+  uint64_t a = 1, c = 0, ba = 0x5DEECE66Dull, bc = 0xB;
+  while (k) {
+    if (k & 1) {
+      a = (ba * a) & kAmclDrand48Mask;
+      c = (ba * c + bc) & kAmclDrand48Mask;
+    }
+    bc = (ba * bc + bc) & kAmclDrand48Mask;
+    ba = (ba * ba) & kAmclDrand48Mask;
+    k >>= 1;
+  }
+  return (a * x + c) & kAmclDrand48Mask;
+}
+
+constexpr uint64_t kInitDefaultCandidatesPerSample = 100;  // max_candidates = 0: 100 x max_samples per filter
+
+// The free cells of map m with map_occ_dist > radius (amcl_node.cpp:1026-1033), kept on the map until the radius or its
+// distances change
+int freeCellsBeyond(AmclMap& m, double radius, hipStream_t s) {
+  if (m.free_r_valid && m.free_r_radius == radius) return NAVGPU_OK;
+  const size_t cells = (size_t)m.sx * m.sy;
+  std::vector<int8_t> occ(cells);
+  std::vector<float> dist(cells);
+  HIP_TRY(hipMemcpyAsync(occ.data(), m.occ, cells, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(dist.data(), m.dist, cells * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(waitStream(s));
+  std::vector<int32_t> list;
+  for (int i = 0; i < m.sx; ++i)
+    for (int j = 0; j < m.sy; ++j) {
+      const size_t c = i + (size_t)j * m.sx;
+      if (occ[c] == -1 && (double)dist[c] > radius) list.push_back((int32_t)c);
+    }
+  if (m.free_r) hipFree(m.free_r);
+  m.free_r = nullptr;
+  m.n_free_r = (int)list.size();
+  m.free_r_valid = false;
+  if (!list.empty()) {
+    HIP_TRY(hipMalloc(&m.free_r, list.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemcpyAsync(m.free_r, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(waitStream(s));
+  }
+  m.free_r_radius = radius;
+  m.free_r_valid = true;
+  return NAVGPU_OK;
+}
+
+// Launch an init over the slice and commit what succeeded: the set is max_samples poses of weight 1 / max_samples, w_slow =
+// w_fast = 0, unconverged, with its leaf count and clusters
+int runInit(navgpu_amcl* h, uint32_t first, uint32_t count, const AmclInitParamsDev& p, std::vector<AmclInitFilterDev>& fd,
+            const std::vector<double>& beams, int max_nb) {
+  if (int rc = h->resampleWorkspace()) return rc;
+  if (p.gaussian && !p.draw_device && !h->d_records) {
+    if (int rc = h->alloc(&h->d_records, (size_t)h->n * 3 * h->d.max_samples)) return rc;
+  }
+  if (!h->d_ifilters) {
+    if (int rc = h->alloc(&h->d_ifilters, h->n)) return rc;
+  }
+  if (!beams.empty())
+    HIP_TRY(hipMemcpyAsync(h->d_beams, beams.data(), sizeof(double) * beams.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_ifilters, fd.data(), sizeof(AmclInitFilterDev) * count, hipMemcpyHostToDevice, h->stream));
+  launch_amcl_init(h->d, h->rs, p, h->params, h->d_beams, max_nb, h->d_records, first, count, h->d_ifilters, h->stream);
+  const int lrc = checkLaunch();
+  if (lrc) return lrc;
+  HIP_TRY(hipMemcpyAsync(fd.data(), h->d_ifilters, sizeof(AmclInitFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t f = first + k;
+    if (!fd[k].active || fd[k].status != NAVGPU_OK) continue;
+    h->sample_count[f] = (int32_t)h->d.max_samples;
+    h->converged[f] = 0;
+    h->leaf[f] = fd[k].leaf_out;
+    h->cluster_count[f] = fd[k].cluster_count;
+  }
+  return NAVGPU_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int navgpu_amcl_init_gaussian(navgpu_amcl* h, uint32_t first, uint32_t count, const double* mean, const double* cov, int32_t draw_source,
+                              uint64_t* drand48_state, uint64_t seed, int32_t* status) {
+  if (!h || !status || !mean || !cov || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  if (draw_source != NAVGPU_AMCL_DRAW_DRAND48 && draw_source != NAVGPU_AMCL_DRAW_DEVICE) return NAVGPU_ERR_INVALID;
+  const bool dev = draw_source == NAVGPU_AMCL_DRAW_DEVICE;
+  if (!dev && !drand48_state) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  std::vector<AmclInitFilterDev> fd(count);
+  int rc = NAVGPU_OK;
+  for (uint32_t k = 0; k < count; ++k) {
+    AmclInitFilterDev& e = fd[k];
+    e = AmclInitFilterDev{};
+    e.active = 1;
+    e.status = NAVGPU_OK;
+    e.state = dev ? 0 : drand48_state[k];
+    e.rng_ctr = h->rng_ctr[first + k];
+    status[k] = NAVGPU_OK;
+    double vec[3][3], val[3];
+    bool ok = dev || drand48_state[k] <= kAmclDrand48Mask;
+    for (int a = 0; a < 3; ++a) ok = ok && isFinite(mean[3 * (size_t)k + a]);
+    for (int a = 0; a < 9; ++a) ok = ok && isFinite(cov[9 * (size_t)k + a]);
+    ok = ok && symmetricEigen3(cov + 9 * (size_t)k, vec, val);
+    if (!ok) {
+      e.active = 0;
+      status[k] = NAVGPU_ERR_INVALID;
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_init_gaussian: a drand48 state >= 2^48 or a non-finite mean or covariance";
+      continue;
+    }
+    for (int a = 0; a < 3; ++a) {
+      e.mean[a] = mean[3 * (size_t)k + a];
+      e.cd[a] = sqrt(val[a]);  // pf_pdf_gaussian_alloc (pf_pdf.c:60-62); NaN for a negative eigenvalue
+      for (int b = 0; b < 3; ++b) e.cr[3 * a + b] = vec[a][b];
+    }
+  }
+  AmclInitParamsDev p{};
+  p.gaussian = 1;
+  p.draw_device = dev ? 1 : 0;
+  p.seed = seed;
+  const int irc = runInit(h, first, count, p, fd, {}, 0);
+  if (irc) return irc;
+  for (uint32_t k = 0; k < count; ++k) {
+    if (!fd[k].active) continue;
+    if (dev) ++h->rng_ctr[first + k];
+    if (fd[k].status != NAVGPU_OK) {
+      status[k] = fd[k].status;
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_init_gaussian: a non-finite pose or a pose outside the histogram's range";
+    } else if (!dev) {
+      drand48_state[k] = fd[k].state;
+    }
+  }
+  return rc;
+}
+
+int navgpu_amcl_init_uniform(navgpu_amcl* h, uint32_t first, uint32_t count, const navgpu_amcl_uniform_params* params, const double* ranges_xy,
+                             const uint32_t* range_counts, const double* range_max, int32_t draw_source, uint64_t* drand48_state,
+                             uint64_t seed, uint64_t* candidates_used, int32_t* status) {
+  if (!h || !params || !status || !h->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  if (draw_source != NAVGPU_AMCL_DRAW_DRAND48 && draw_source != NAVGPU_AMCL_DRAW_DEVICE) return NAVGPU_ERR_INVALID;
+  const bool dev = draw_source == NAVGPU_AMCL_DRAW_DEVICE;
+  if (!dev && !drand48_state) return NAVGPU_ERR_INVALID;
+  const bool scan = ranges_xy || range_counts;  // both NULL: no scan yet (last_laser_data_ == NULL)
+  if (scan && (!range_counts || !range_max)) return NAVGPU_ERR_INVALID;
+  const double thr = params->starting_weight_threshold, mult = params->deweight_multiplier;
+  if (thr != thr || mult != mult) return NAVGPU_ERR_INVALID;
+  AmclGuard guard_(h);
+  const size_t ms = h->d.max_samples;
+  const uint64_t cap = params->max_candidates ? params->max_candidates
+                                              : std::min<uint64_t>(kInitDefaultCandidatesPerSample * ms, dev ? (1ull << 32) : (1ull << 40));
+  if (cap > (1ull << 40) || (dev && cap > (1ull << 32))) return NAVGPU_ERR_INVALID;  // device retries are numbered in 32 bits
+  for (uint32_t k = 0; k < count; ++k)
+    if (!h->maps[first + k]) {
+      g_last_error = "navgpu_amcl_init_uniform: a filter has no map";
+      return NAVGPU_ERR_STATE;
+    }
+  if (scan && !h->configured) {
+    g_last_error = "navgpu_amcl_init_uniform: a scan before navgpu_amcl_laser_configure";
+    return NAVGPU_ERR_STATE;
+  }
+  const navgpu_amcl_laser_params& P = h->params;
+  const bool scored = scan && thr > 0.0 && mult < 1.0 && mult >= 0.0;  // amcl_node.cpp:1253
+  const double radius = h->configured ? P.non_free_space_radius : 0.0;
+  std::vector<AmclInitFilterDev> fd(count);
+  std::vector<double> beams;
+  int rc = NAVGPU_OK, max_nb = 0;
+  const double* src = ranges_xy;
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t f = first + k;
+    AmclInitFilterDev& e = fd[k];
+    e = AmclInitFilterDev{};
+    e.active = 1;
+    e.status = NAVGPU_OK;
+    e.state = dev ? 0 : drand48_state[k];
+    e.rng_ctr = h->rng_ctr[f];
+    status[k] = NAVGPU_OK;
+    AmclMap& m = *h->maps[f];
+    if (int frc = freeCellsBeyond(m, radius, h->stream)) return frc;
+    e.free_cells = m.free_r;
+    e.n_free = m.n_free_r;
+    const int rcount = scan ? (int)std::min<uint32_t>(range_counts[k], (uint32_t)INT32_MAX) : 0;
+    if (scan && range_counts[k] > (uint32_t)INT32_MAX) return NAVGPU_ERR_INVALID;
+    if (scored) {
+      if (rcount && !ranges_xy) return NAVGPU_ERR_INVALID;
+      std::copy(&h->laser[3 * (size_t)f], &h->laser[3 * (size_t)f] + 3, e.laser);
+      e.range_max = range_max[k];
+      e.beam_off = (uint32_t)(beams.size() / 2);
+      const int step = P.max_beams < 2 ? 1 : beamStep(P, rcount);
+      if (step < 1 && rcount > 0) {
+        e.active = 0;
+        status[k] = NAVGPU_ERR_INVALID;
+        if (rc != NAVGPU_ERR_CAPACITY) rc = NAVGPU_ERR_INVALID;
+        g_last_error = "navgpu_amcl_init_uniform: beam model with 1 <= range_count < max_beams (the reference loops forever)";
+      } else if (P.max_beams >= 2) {
+        for (int i = 0; i < rcount; i += step) {
+          beams.push_back(src[2 * (size_t)i]);
+          beams.push_back(src[2 * (size_t)i + 1]);
+        }
+      }
+      e.n_beams = (int)(beams.size() / 2 - e.beam_off);
+      max_nb = std::max(max_nb, e.n_beams);
+      src += 2 * (size_t)rcount;
+    }
+    if (e.active && (e.n_free <= 0 || (!dev && drand48_state[k] > kAmclDrand48Mask))) {
+      e.active = 0;
+      status[k] = NAVGPU_ERR_INVALID;
+      if (rc != NAVGPU_ERR_CAPACITY) rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_init_uniform: a map without free cells or a drand48 state >= 2^48";
+    }
+    if (e.active && !scored && cap < ms) {
+      e.active = 0;
+      status[k] = NAVGPU_ERR_CAPACITY;
+      rc = NAVGPU_ERR_CAPACITY;
+    }
+  }
+  if (beams.size() > (size_t)h->n * 2 * h->d.max_beams * 2) return NAVGPU_ERR_CAPACITY;  // cannot happen: < 2 max_beams per filter
+  AmclInitParamsDev p{};
+  p.draw_device = dev ? 1 : 0;
+  p.scored = scored ? 1 : 0;
+  p.threshold = thr;
+  p.multiplier = mult;
+  p.max_candidates = cap;
+  p.seed = seed;
+  const int irc = runInit(h, first, count, p, fd, beams, max_nb);
+  if (irc) return irc;
+  for (uint32_t k = 0; k < count; ++k) {
+    if (!fd[k].active) {
+      if (candidates_used) candidates_used[k] = 0;
+      continue;
+    }
+    const uint64_t used = scored ? fd[k].used : ms;
+    if (candidates_used) candidates_used[k] = used;
+    if (dev) ++h->rng_ctr[first + k];
+    if (fd[k].status != NAVGPU_OK) {
+      status[k] = fd[k].status;
+      if (rc == NAVGPU_OK || fd[k].status == NAVGPU_ERR_CAPACITY) rc = fd[k].status;
+      g_last_error = "navgpu_amcl_init_uniform: a filter needed more than max_candidates candidates, or a pose outside the histogram";
+    } else if (!dev) {
+      drand48_state[k] = drand48Advance(drand48_state[k], 2 * used);
+    }
   }
   return rc;
 }

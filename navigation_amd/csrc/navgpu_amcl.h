@@ -9,6 +9,7 @@
 // current set: cl_count int32 [n][max_samples], cl_stats double [n][max_samples][13] {weight, mean[3], cov[9]},
 // set_stats double [n][12] {mean[3], cov[9]}.
 // The motion model (amcl_motion_kernels.hip) adds, in drand48 mode, a record workspace: double2 [n][3 max_samples] {x2, s}.
+// The init (amcl_init_kernels.hip) uses the resampling workspace and, for the Gaussian in drand48 mode, the record workspace.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -97,7 +98,8 @@ struct AmclResampleDev {
 };
 
 // Philox4x32-10 (Salmon et al., SC'11): counter {draw index, filter | stream << 16, call counter lo, hi}, key = seed.  Streams:
-// 0 and 1 resampling (amcl_resample_kernels.hip), 2 the motion model (amcl_motion_kernels.hip).
+// 0 and 1 resampling (amcl_resample_kernels.hip), 2 the motion model (amcl_motion_kernels.hip), 3 the Gaussian init and 4 the
+// uniform init (amcl_init_kernels.hip; stream 4 puts the retry number where the counter's high word would be).
 __device__ __forceinline__ void philox(uint32_t c[4], uint32_t k0, uint32_t k1) {
   for (int r = 0; r < 10; ++r) {
     const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
@@ -144,6 +146,35 @@ constexpr uint64_t kAmclDrand48Mask = (1ull << 48) - 1;  // drand48's state is 4
 void launch_amcl_drand48_gauss(double2* records, uint32_t max_samples, uint32_t count, AmclOdomFilterDev* filters, hipStream_t s);
 void launch_amcl_odom(const AmclDev& d, int32_t model, int32_t draw_device, uint64_t seed, const double2* records, uint32_t first,
                       uint32_t count, int max_sample_count, const AmclOdomFilterDev* filters, hipStream_t s);
+
+// One filter of an init call (pf_init / pf_init_model)
+struct AmclInitFilterDev {
+  int32_t active;        // 0: the filter is skipped
+  int32_t status;        // in: NAVGPU_OK; out: NAVGPU_ERR_INVALID (bad bin), NAVGPU_ERR_CAPACITY (candidate cap); nothing written then
+  uint64_t state;        // drand48 mode: the 48-bit LCG state (the Gaussian records advance it)
+  uint64_t rng_ctr;      // device mode: the filter's call counter
+  uint64_t used;         // uniform, scored: candidates drawn (out)
+  const int32_t* free_cells;  // uniform: the free cells of this call
+  int32_t n_free;
+  int32_t n_beams;       // scored: subsampled beams of the scan
+  uint32_t beam_off;     // scored: first {range, bearing} pair in the beam buffer
+  int32_t leaf_out, cluster_count;  // out
+  int32_t pad;
+  double mean[3], cr[9], cd[3];     // Gaussian: pf_pdf_gaussian_alloc's x, cr (row-major) and cd
+  double laser[3];       // scored: laser pose in the robot frame
+  double range_max;
+};
+
+struct AmclInitParamsDev {
+  int32_t gaussian, draw_device, scored, pad;
+  double threshold, multiplier;   // scored: uniform_pose_starting_weight_threshold, uniform_pose_deweight_multiplier
+  uint64_t max_candidates;        // per filter (scored)
+  uint64_t seed;
+};
+
+void launch_amcl_init(const AmclDev& d, const AmclResampleDev& r, const AmclInitParamsDev& p, const navgpu_amcl_laser_params& P,
+                      const double* beams, int max_n_beams, double2* records, uint32_t first, uint32_t count, AmclInitFilterDev* filters,
+                      hipStream_t s);
 
 void launch_amcl_convert(const int8_t* msg, uint32_t width, uint32_t height, int factor, int8_t* occ, int sx, int sy, hipStream_t s);
 void launch_amcl_cspace(const int8_t* occ, int sx, int sy, int radius, double scale, double max_occ_dist, int32_t* g, float* dist,

@@ -10,6 +10,8 @@
   clusters           pf_get_cluster_stats / the set's cluster_count and mean / cov
   configure_odom     AMCLOdom::SetModel*                              (amcl_odom.cpp:68-125)
   update_action      AMCLOdom::UpdateAction -> pf_update_action: the odometry motion model (amcl_odom.cpp:128-379)
+  init_gaussian      pf_init: a Gaussian set                             (pf.c:138-176)
+  init_uniform       pf_init_model with AmclNode::uniformPoseGenerator (global localisation, amcl_node.cpp:1200-1263)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -18,7 +20,7 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import (AMCL_DRAW_DEVICE, AMCL_DRAW_DRAND48, AMCL_DRAW_SUPPLIED, AMCL_RESAMPLE_SYSTEMATIC, AmclLaserParams, AmclOdomParams,
-                   AmclResampleParams, check, lib)
+                   AmclResampleParams, AmclUniformParams, check, lib)
 
 # pf_sample_set_t's clusters and overall statistics: count (C,), weight (C,), mean (C, 3), cov (C, 3, 3), set_mean (3,), set_cov (3, 3)
 AmclClusters = namedtuple("AmclClusters", "count weight mean cov set_mean set_cov")
@@ -252,3 +254,49 @@ class AmclLaser:
         if raise_on_error:
             check(rc, "amcl_update_action")
         return rc, st, x
+
+    def init_gaussian(self, mean, cov, drand48_state=None, seed=None, first=0, count=None, raise_on_error=True):
+        """pf_init(pf, mean, cov) for every filter of the slice.  mean: (3,) or (count, 3); cov: (3, 3) or (count, 3, 3).
+        drand48_state: (count,) 48-bit states (parity: (pf_pdf_seed << 16) | 0x330E); otherwise the device generator with `seed`.
+        -> (status, status[count], the advanced drand48 states or None)"""
+        count = self._count(first, count)
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(mean, np.float64).reshape(-1, 3), (count, 3)))
+        c = np.ascontiguousarray(np.broadcast_to(np.asarray(cov, np.float64).reshape(-1, 9), (count, 9)))
+        st = np.zeros(count, np.int32)
+        x, src, sd = self._draws(drand48_state, seed, count)
+        rc = self.L.navgpu_amcl_init_gaussian(self.h, first, count, _p(m), _p(c), src, None if x is None else _p(x), sd, _p(st))
+        if raise_on_error:
+            check(rc, "amcl_init_gaussian")
+        return rc, st, x
+
+    def init_uniform(self, scans=None, range_max=None, threshold=0.0, deweight_multiplier=0.0, max_candidates=0, drand48_state=None,
+                     seed=None, first=0, count=None, raise_on_error=True):
+        """pf_init_model(pf, uniformPoseGenerator) for every filter of the slice.  scans: None (no scan yet) or a list of
+        (range_count, 2) arrays {range, bearing} per filter, with range_max (scalar or per filter), as update_sensor takes them.
+        threshold / deweight_multiplier: uniform_pose_starting_weight_threshold / uniform_pose_deweight_multiplier (amcl_node's
+        defaults 0 and 0: no scoring).  -> (status, status[count], the advanced drand48 states or None, candidates_used[count])"""
+        count = self._count(first, count) if scans is None else len(scans)
+        p = AmclUniformParams(starting_weight_threshold=threshold, deweight_multiplier=deweight_multiplier,
+                              max_candidates=int(max_candidates))
+        st = np.zeros(count, np.int32)
+        used = np.zeros(count, np.uint64)
+        x, src, sd = self._draws(drand48_state, seed, count)
+        flat = rc_ = rm = None
+        if scans is not None:
+            rc_ = np.ascontiguousarray([len(s) for s in scans], np.uint32)
+            parts = [np.asarray(s, np.float64).reshape(-1, 2) for s in scans]
+            flat = np.ascontiguousarray(np.concatenate(parts) if rc_.sum() else np.zeros((1, 2)))
+            rm = np.ascontiguousarray(np.broadcast_to(np.asarray(range_max, np.float64), (count,)))
+        rc = self.L.navgpu_amcl_init_uniform(self.h, first, count, C.byref(p), None if flat is None else _p(flat),
+                                             None if rc_ is None else _p(rc_), None if rm is None else _p(rm), src,
+                                             None if x is None else _p(x), sd, _p(used), _p(st))
+        if raise_on_error:
+            check(rc, "amcl_init_uniform")
+        return rc, st, x, used
+
+    @staticmethod
+    def _draws(drand48_state, seed, count):
+        """update_action's draw-source handling -> (a copy of the states or None, draw_source, seed)"""
+        if drand48_state is not None:
+            return np.array(np.broadcast_to(np.asarray(drand48_state, np.uint64), (count,))), AMCL_DRAW_DRAND48, 0
+        return None, AMCL_DRAW_DEVICE, int(0 if seed is None else seed) & (2 ** 64 - 1)
