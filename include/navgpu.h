@@ -554,6 +554,80 @@ int navgpu_tp_get_state(navgpu_fleet* fleet, uint32_t first, uint32_t count, nav
 int navgpu_tp_set_state(navgpu_fleet* fleet, uint32_t first, uint32_t count, const navgpu_tp_state* states);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Footprint-cost queries, rotate_recovery::RotateRecovery, carrot_planner::CarrotPlanner       */
+/* ------------------------------------------------------------------------------------------ */
+/* replaces: WorldModel::footprintCost(x, y, theta, footprint_spec) -> CostmapModel::footprintCost
+ * (base_local_planner/include/base_local_planner/world_model.h:65-86, base_local_planner/src/costmap_model.cpp:50-142)
+ * called directly - "is this footprint legal at these poses" - against the RESIDENT master grid, origin and footprint
+ * (navgpu_set_footprint) of every robot in [first, first+count).  query_counts = count run lengths (0 is legal);
+ * poses_xyth = sum(query_counts) x {x, y, theta} doubles in the world frame, robot after robot.  costs_out = one double per
+ * query: -1.0 when the centre or an oriented vertex is off the map, or an outline cell is LETHAL, or NO_INFORMATION with
+ * allow_unknown = 0; else the largest cell cost over the outline (LineIterator cells of every edge, the closing one
+ * included).  With fewer than 3 vertices: the centre cell's cost, and INSCRIBED fails too (:60-67).  allow_unknown is explicit
+ * (CostmapModel derives it from the costmap's default value, :45-48).  first_illegal_out (or NULL) = per robot
+ * the index within its run of the first query with a negative cost, -1 when there is none; found on the device.
+ * A pose that is not finite is NAVGPU_ERR_INVALID, here as in the two calls below.
+ * Ordered on the fleet's stream behind whatever was queued before (a navgpu_costmap_update, say); returns when the results
+ * are on the host.  NAVGPU_ERR_STATE while a staged rolling-window origin has not been applied by an update yet. */
+int navgpu_footprint_cost(navgpu_fleet* fleet, uint32_t first, uint32_t count, const uint32_t* query_counts, const double* poses_xyth,
+                          int32_t allow_unknown, double* costs_out, int32_t* first_illegal_out);
+
+/* RotateRecovery's parameters (rotate_recovery/src/rotate_recovery.cpp:60-66): sim_granularity 0.017, and from
+ * ~/TrajectoryPlannerROS acc_lim_th 3.2, max_rotational_vel 1.0, min_in_place_rotational_vel 0.4, yaw_goal_tolerance 0.10.
+ * (frequency, 20.0, is the caller's: one navgpu_rotate_recovery_step per tick.)  allow_unknown: what
+ * CostmapModel(*local_costmap_->getCostmap()) derives from the costmap's default value (:68, costmap_model.cpp:45-48),
+ * explicit here. */
+typedef struct {
+  double sim_granularity;
+  double acc_lim_th;
+  double max_rotational_vel;
+  double min_in_place_rotational_vel;
+  double yaw_goal_tolerance;
+  int32_t allow_unknown;
+  int32_t reserved;
+} navgpu_rotate_recovery_params;
+/* capacity: headings of one robot's sweep in one step.  A sweep covers less than 2 pi, so sim_granularity must be at least
+ * 2 pi / (NAVGPU_ROTATE_RECOVERY_MAX_SWEEP - 1) (about 0.00154 rad) */
+#define NAVGPU_ROTATE_RECOVERY_MAX_SWEEP 4096
+
+/* the locals of RotateRecovery::runBehavior that live across iterations of its loop (:100-104), per robot */
+typedef struct {
+  double start_offset;  /* 0 - normalize_angle(yaw) at the first step of a run                                            */
+  int32_t got_180;
+  int32_t started;      /* 0: the next step begins a run (sets start_offset, clears got_180); cleared again by DONE / BLOCKED */
+  int32_t swept;        /* out: headings the last step checked - the whole sweep, or up to and including the illegal one   */
+  int32_t reserved;
+} navgpu_rotate_recovery_state;
+
+typedef enum {
+  NAVGPU_ROTATE_RUNNING = 0, /* cmd_wz published, loop continues (:137-152)                                               */
+  NAVGPU_ROTATE_DONE = 1,    /* cmd_wz published, then got_180 && current_angle >= -tolerance (:148-150)                  */
+  NAVGPU_ROTATE_BLOCKED = 2  /* a swept heading has negative footprint cost: the early return of :123-126, cmd_wz = 0    */
+} navgpu_rotate_status;
+
+/* replaces: RotateRecovery::initialize's parameter reads (:55-66).  NAVGPU_ERR_INVALID for a sim_granularity that is not
+ * positive, NAVGPU_ERR_CAPACITY for one below the bound above; a call that fails changes nothing. */
+int navgpu_rotate_recovery_configure(navgpu_fleet* fleet, const navgpu_rotate_recovery_params* params);
+/* replaces: one pass of the while(n.ok()) body of RotateRecovery::runBehavior (:105-153) for every robot of
+ * [first, first+count).  poses_xyth = count x {x, y, yaw}: local_costmap_->getRobotPose.  The headings yaw + sim_angle, with
+ * sim_angle grown by repeated += sim_granularity from 0 while < dist_left (:117-129), of all robots are checked in one
+ * k_footprint_cost launch; cmd_wz_out = min(max(sqrt(2 * acc_lim_th * dist_left), min_in_place_rotational_vel),
+ * max_rotational_vel) (:131-135), status_out = navgpu_rotate_status.  The caller publishes cmd_wz and steps again after
+ * 1 / frequency while the status is RUNNING.  angles::normalize_angle: the fmod form of navgpu_shortest_angular_distance. */
+int navgpu_rotate_recovery_step(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* poses_xyth,
+                                navgpu_rotate_recovery_state* state_inout, double* cmd_wz_out, int32_t* status_out);
+
+/* replaces: CarrotPlanner::makePlan's search (carrot_planner/src/carrot_planner.cpp:116-169) for one plan per robot of
+ * [first, first+count), on the costmaps this fleet holds.  starts_xyth, goals_xyth = count x {x, y, yaw}.  The candidates
+ * start + scale * (goal - start), yaw normalize_angle(start_yaw + scale * normalize_angle(goal_yaw - start_yaw)), with scale
+ * from 1.0 by repeated -= 0.01 until it is negative (:131-153), of all plans are evaluated in one k_footprint_cost launch.
+ * targets_xyth_out = the first legal candidate in that order; found_out = the number of candidates tried up to and
+ * including it (1: the goal itself), or 0 with the target set to the start when none is legal (:136-143).  A robot with
+ * fewer than 3 footprint vertices finds nothing (CarrotPlanner::footprintCost, :76-79). */
+int navgpu_carrot_plan(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* starts_xyth, const double* goals_xyth,
+                       int32_t allow_unknown, double* targets_xyth_out, int32_t* found_out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* measurement                                                                                */
 /* ------------------------------------------------------------------------------------------ */
 typedef enum {
@@ -563,7 +637,8 @@ typedef enum {
   NAVGPU_K_BFS = 3,      /* MapGrid wavefronts                            */
   NAVGPU_K_SCORE = 4,    /* rollout + critics                             */
   NAVGPU_K_SELECT = 5,   /* argmin + result + oscillation update          */
-  NAVGPU_K_COUNT = 6
+  NAVGPU_K_FOOTPRINT = 6,/* batched footprint-cost queries                */
+  NAVGPU_K_COUNT = 7
 } navgpu_kernel_id;
 /* HIP-event timing of the kernels on the fleet's stream.  While enabled every launch of the
  * listed kernels is bracketed by two hipEventRecord calls; read() synchronises and returns the

@@ -11,8 +11,8 @@ _LIB = None
 LAYER_STATIC, LAYER_OBSTACLE, LAYER_VOXEL, LAYER_INFLATION = 1, 2, 4, 8
 GRID_MASTER, GRID_STATIC, GRID_OBSTACLE, GRID_VOXEL, GRID_PATH, GRID_GOAL, GRID_GOAL_FRONT = range(7)
 OBS_MARKING, OBS_CLEARING = 1, 2
-K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT = range(6)
-KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select")
+K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT = range(7)
+KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost")
 
 
 class NavgpuError(RuntimeError):
@@ -156,6 +156,30 @@ class TpResult(C.Structure):
 
 class TpSample(C.Structure):
     _fields_ = [("vx", C.c_double), ("vy", C.c_double), ("vtheta", C.c_double), ("cost", C.c_double), ("n_points", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+ROTATE_RUNNING, ROTATE_DONE, ROTATE_BLOCKED = range(3)
+ROTATE_RECOVERY_MAX_SWEEP = 4096
+
+
+class RotateRecoveryParams(C.Structure):
+    """navgpu_rotate_recovery_params; defaults are the reference's (rotate_recovery.cpp:60-66)."""
+    _fields_ = [(n, C.c_double) for n in ("sim_granularity", "acc_lim_th", "max_rotational_vel", "min_in_place_rotational_vel",
+                                          "yaw_goal_tolerance")] + [("allow_unknown", C.c_int32), ("reserved", C.c_int32)]
+    DEFAULTS = dict(sim_granularity=0.017, acc_lim_th=3.2, max_rotational_vel=1.0, min_in_place_rotational_vel=0.4,
+                    yaw_goal_tolerance=0.10, allow_unknown=0, reserved=0)
+
+    def __init__(self, **kw):
+        super().__init__()
+        d = dict(self.DEFAULTS)
+        d.update(kw)
+        for k, v in d.items():
+            setattr(self, k, v)
+
+
+class RotateRecoveryState(C.Structure):
+    _fields_ = [("start_offset", C.c_double), ("got_180", C.c_int32), ("started", C.c_int32), ("swept", C.c_int32),
                 ("reserved", C.c_int32)]
 
 
@@ -328,6 +352,10 @@ SYMBOLS = [
     ("navgpu_tp_score_trajectory", C.c_int, [vp, u32, vp, vp, vp, C.POINTER(dbl)]),
     ("navgpu_tp_get_state", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_tp_set_state", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_footprint_cost", C.c_int, [vp, u32, u32, vp, vp, i32, vp, vp]),
+    ("navgpu_rotate_recovery_configure", C.c_int, [vp, C.POINTER(RotateRecoveryParams)]),
+    ("navgpu_rotate_recovery_step", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+    ("navgpu_carrot_plan", C.c_int, [vp, u32, u32, vp, vp, i32, vp, vp]),
     ("navgpu_navfn_create", C.c_int, [u32, u32, u32, i32, C.POINTER(vp)]),
     ("navgpu_navfn_destroy", C.c_int, [vp]),
     ("navgpu_navfn_set_costmap", C.c_int, [vp, u32, u32, vp, i32, i32, i32]),

@@ -198,6 +198,22 @@ struct TpDev {
 void launch_tp_within(const PlannerDev& pl, const TpDev& tp, uint32_t first, uint32_t count, hipStream_t s);
 void launch_tp_rollout(const PlannerDev& pl, const TpDev& tp, uint32_t first, uint32_t count, int store_points, hipStream_t s);
 
+// batched CostmapModel::footprintCost queries (footprint_kernels.hip): runs of poses per robot of a launch, packed
+struct FootprintDev {
+  uint32_t nx, ny, cells_padded;
+  double res;
+  const double* origin;     // [n][2]
+  const uint8_t* master;    // [n][cells_padded]
+  const double* fp_spec;    // [n][kMaxFootprint][2] robot-frame footprint (navgpu_set_footprint)
+  const uint32_t* fp_n;     // [n]
+  const uint32_t* q_off;    // [count + 1] first query of robot first + k in poses / costs
+  const double* poses;      // [queries][3] x, y, theta in the world frame
+  double* costs;            // [queries]
+  uint32_t* first_hit;      // [count] preset to 0xFFFFFFFF (= -1): the robot's first query that fails (seek_legal: that is legal); or null
+  int32_t allow_unknown, seek_legal;
+};
+void launch_footprint_cost(const FootprintDev& d, uint32_t first, uint32_t count, const uint32_t* h_counts, const uint32_t* h_fp_n, hipStream_t s);
+
 // ---- launchers (defined in the .hip files) ---------------------------------------------------
 void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const double* bounds_in, int only_bounds,
                      hipStream_t s);

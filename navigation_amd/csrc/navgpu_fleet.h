@@ -1,6 +1,7 @@
 // Internal to libnavgpu.so: the fleet object behind the opaque navgpu_fleet handle and the helpers the host
 // translation units share (navgpu_host.cpp: lifetime / costmap layers / DWA planner / measurement,
-// navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner).
+// navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner,
+// navgpu_recovery.cpp: footprint-cost queries, RotateRecovery, CarrotPlanner).
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -126,6 +127,13 @@ struct navgpu_fleet {
   std::vector<TpOut> tp_h_out;
   std::vector<uint32_t> tp_h_nsamples, tp_h_within, tp_h_within_count;
   std::vector<int32_t> tp_h_winner;
+  // footprint-cost queries, rotate recovery, carrot planner (navgpu_recovery.cpp): query staging, grown on demand
+  struct FootprintQueries {
+    uint32_t cap = 0;             // queries the buffers hold
+    double *d_poses = nullptr, *d_costs = nullptr, *h_poses = nullptr, *h_costs = nullptr;  // [cap][3], [cap]; h_: pinned
+    uint32_t *d_off = nullptr, *d_first = nullptr, *h_off = nullptr, *h_first = nullptr;    // [n + 1], [n]
+  } fq;
+  navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers
   double* d_bounds_tmp = nullptr;               // [n][4]
   int32_t* d_boxes_tmp = nullptr;               // [n][4]
@@ -181,6 +189,12 @@ struct navgpu_fleet {
     auto it = std::find(allocs.begin(), allocs.end(), q);
     if (it != allocs.end()) allocs.erase(it);
     hipFree(q);
+  }
+  void releasePinned(void* q) {
+    if (!q) return;
+    auto it = std::find(pinned.begin(), pinned.end(), q);
+    if (it != pinned.end()) pinned.erase(it);
+    hipHostFree(q);
   }
   bool rangeOk(uint32_t first, uint32_t count) const { return count > 0 && first < desc.n_instances && count <= desc.n_instances - first; }
 

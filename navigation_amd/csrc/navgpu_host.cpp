@@ -30,7 +30,7 @@ int navgpu_device_count(void) {
   return n;
 }
 const char* navgpu_kernel_name(int32_t k) {
-  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select"};
+  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost"};
   return (k >= 0 && k < NAVGPU_K_COUNT) ? names[k] : "?";
 }
 

@@ -5,7 +5,7 @@
 //                  createTrajectories, fp64 state as in the reference; second pass stores the winner's points
 // The two MapGrid wavefronts are the k_bfs* kernels of planner_kernels.hip (bfs_grids = 2, `within` set).
 // Compiled with -ffp-contract=off.
-#include "navgpu_device.h"
+#include "costmap_model_dev.h"
 
 namespace navgpu {
 
@@ -27,52 +27,8 @@ void launch_tp_within(const PlannerDev& pl, const TpDev& tp, uint32_t first, uin
   hipLaunchKernelGGL(k_tp_within, dim3(4, count), dim3(256), 0, s, pl, tp, first);
 }
 
-// CostmapModel::pointCost / lineCost / footprintCost (costmap_model.cpp:50-142) on the global costmap
-struct TpWorld {
-  const uint8_t* master;
-  Geom g;
-  bool allow_unknown;
-  __device__ double pointCost(int x, int y) const {
-    const uint8_t cost = master[(uint32_t)y * g.nx + (uint32_t)x];
-    if (cost == kLethal || (cost == kNoInfo && !allow_unknown)) return -1;
-    return cost;
-  }
-  // The cells of base_local_planner::LineIterator (line_iterator.h:38-139) from (x0, y0) to (x1, y1), both ends included:
-  // the longer axis advances with every cell, the shorter one whenever the running remainder - which starts at half the
-  // long extent - passes it.  visit(x, y) returns false to end the walk; the return value says whether it ran to the end.
-  template <class Visit>
-  __device__ static bool forEachLineCell(int x0, int y0, int x1, int y1, Visit&& visit) {
-    const int ex = x1 >= x0 ? x1 - x0 : x0 - x1, ey = y1 >= y0 ? y1 - y0 : y0 - y1;
-    const int sx = x1 >= x0 ? 1 : -1, sy = y1 >= y0 ? 1 : -1;
-    const bool along_x = ex >= ey;
-    const int long_ext = along_x ? ex : ey, short_ext = along_x ? ey : ex;
-    int rem = long_ext / 2, x = x0, y = y0;
-    for (int k = 0; k <= long_ext; ++k) {
-      if (!visit(x, y)) return false;
-      rem += short_ext;
-      const bool side = rem >= long_ext;
-      if (side) rem -= long_ext;
-      x += along_x ? sx : (side ? sx : 0);
-      y += along_x ? (side ? sy : 0) : sy;
-    }
-    return true;
-  }
-  // maximum cost over the line's cells, -1 as soon as one of them fails `fails(cost)`
-  template <class Fails>
-  __device__ double lineMax(int x0, int y0, int x1, int y1, Fails&& fails) const {
-    double worst = 0.0;
-    const bool clear = forEachLineCell(x0, y0, x1, y1, [&](int x, int y) {
-      const uint8_t cost = master[(uint32_t)y * g.nx + (uint32_t)x];
-      if (fails(cost)) return false;
-      if (worst < (double)cost) worst = (double)cost;
-      return true;
-    });
-    return clear ? worst : -1.0;
-  }
-  // CostmapModel::lineCost (costmap_model.cpp:104-125): a cell fails like pointCost
-  __device__ double lineCost(int x0, int x1, int y0, int y1) const {
-    return lineMax(x0, y0, x1, y1, [&](uint8_t cost) { return cost == kLethal || (cost == kNoInfo && !allow_unknown); });
-  }
+// CostmapModel on the global costmap (costmap_model_dev.h) + the planner's own ray walk for heading scoring
+struct TpWorld : CostmapModelDev {
   // TrajectoryPlanner::pointCost / lineCost (trajectory_planner.cpp:388-472): the planner's own ray walk for headingDiff;
   // unlike CostmapModel::pointCost it fails on INSCRIBED cells too
   __device__ double planLineCost(int x0, int x1, int y0, int y1) const {
@@ -94,43 +50,6 @@ struct TpWorld {
       }
     }
     return 1.7976931348623157e308;  // DBL_MAX
-  }
-  // WorldModel::footprintCost(x, y, theta, spec) (world_model.h:65-86) + CostmapModel::footprintCost
-  __device__ double footprintCost(double x, double y, double theta, const double* spec, uint32_t nfp) const {
-    const double cos_th = cos(theta), sin_th = sin(theta);
-    uint32_t cell_x, cell_y;
-    if (!worldToMap(g, x, y, cell_x, cell_y)) return -1.0;
-    if (nfp < 3) {
-      const uint8_t cost = master[cell_y * g.nx + cell_x];
-      if (cost == kLethal || cost == kInscribed || (cost == kNoInfo && !allow_unknown)) return -1.0;
-      return cost;
-    }
-    double footprint_cost = 0.0;
-    uint32_t fx = 0, fy = 0, px = 0, py = 0;
-    for (uint32_t v = 0; v <= nfp; ++v) {
-      uint32_t vx, vy;
-      if (v < nfp) {
-        const double sx = spec[2 * v], sy = spec[2 * v + 1];
-        const double wx = x + (sx * cos_th - sy * sin_th), wy = y + (sx * sin_th + sy * cos_th);
-        if (!worldToMap(g, wx, wy, vx, vy)) return -1.0;
-        if (v == 0) {
-          fx = vx;
-          fy = vy;
-          px = vx;
-          py = vy;
-          continue;
-        }
-      } else {  // closing edge: last -> first
-        vx = fx;
-        vy = fy;
-      }
-      const double line_cost = lineCost((int)px, (int)vx, (int)py, (int)vy);
-      footprint_cost = fmax(line_cost, footprint_cost);
-      if (line_cost < 0) return -1.0;
-      px = vx;
-      py = vy;
-    }
-    return footprint_cost;
   }
 };
 

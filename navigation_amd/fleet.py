@@ -7,6 +7,9 @@ Method names follow the reference interfaces they front:
   set_plan              DWAPlanner::setPlan                  (dwa_local_planner/src/dwa_planner.cpp:204-207)
   find_best_path        DWAPlanner::updatePlanAndLocalCosts + findBestPath (dwa_planner.cpp:240-371)
   check_trajectory      DWAPlanner::checkTrajectory          (dwa_planner.cpp:213-237)
+  footprint_cost        CostmapModel::footprintCost          (base_local_planner/src/costmap_model.cpp:50-142)
+  rotate_recovery_step  RotateRecovery::runBehavior, one pass (rotate_recovery/src/rotate_recovery.cpp:105-153)
+  carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -444,6 +447,43 @@ class Fleet:
     def tp_set_state(self, states, first=0):
         arr = (N.TpState * len(states))(*states)
         check(self.L.navgpu_tp_set_state(self.h, first, len(states), arr), "tp_set_state")
+
+    # ---------------------------------------------------------------- footprint queries, rotate recovery, carrot planner
+    def footprint_cost(self, poses, first=0, allow_unknown=True, want_first_illegal=True):
+        """CostmapModel::footprintCost of runs of poses: `poses` is one (q_k, 3) array of x, y, theta per robot from `first` on
+        (empty runs allowed).  Returns (list of cost arrays, first illegal index per robot or -1)."""
+        runs = [np.asarray(p, np.float64).reshape(-1, 3) for p in poses]
+        counts = np.array([len(r) for r in runs], np.uint32)
+        packed = np.ascontiguousarray(np.concatenate(runs) if runs else np.zeros((0, 3)))
+        costs = np.zeros(len(packed), np.float64)
+        fi = np.zeros(len(runs), np.int32)
+        check(self.L.navgpu_footprint_cost(self.h, first, len(runs), _ptr(counts), _ptr(packed), int(allow_unknown), _ptr(costs),
+                                           _ptr(fi) if want_first_illegal else None), "footprint_cost")
+        off = np.concatenate([[0], np.cumsum(counts)]).astype(int)
+        return [costs[off[k]:off[k + 1]] for k in range(len(runs))], fi
+
+    def configure_rotate_recovery(self, params=None, **kw):
+        p = params if params is not None else N.RotateRecoveryParams(**kw)
+        check(self.L.navgpu_rotate_recovery_configure(self.h, C.byref(p)), "rotate_recovery_configure")
+
+    def rotate_recovery_step(self, poses, states, first=0):
+        """One pass of RotateRecovery::runBehavior's loop for len(poses) robots.  `states` is a ctypes array of
+        RotateRecoveryState, updated in place (zero-initialised states begin a run).  Returns (cmd_wz, status)."""
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        wz = np.zeros(len(p), np.float64)
+        status = np.zeros(len(p), np.int32)
+        check(self.L.navgpu_rotate_recovery_step(self.h, first, len(p), _ptr(p), C.cast(states, C.c_void_p), _ptr(wz), _ptr(status)),
+              "rotate_recovery_step")
+        return wz, status
+
+    def carrot_plan(self, starts, goals, first=0, allow_unknown=True):
+        """CarrotPlanner::makePlan's search for len(starts) plans -> (targets (n, 3), found (n,): candidates tried, 0 = none legal)."""
+        s = np.ascontiguousarray(starts, np.float64).reshape(-1, 3)
+        g = np.ascontiguousarray(goals, np.float64).reshape(-1, 3)
+        targets = np.zeros_like(s)
+        found = np.zeros(len(s), np.int32)
+        check(self.L.navgpu_carrot_plan(self.h, first, len(s), _ptr(s), _ptr(g), int(allow_unknown), _ptr(targets), _ptr(found)), "carrot_plan")
+        return targets, found
 
     # ---------------------------------------------------------------- measurement
     def profile(self, enable=True):
