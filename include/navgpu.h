@@ -628,6 +628,44 @@ int navgpu_carrot_plan(navgpu_fleet* fleet, uint32_t first, uint32_t count, cons
                        int32_t allow_unknown, double* targets_xyth_out, int32_t* found_out);
 
 /* ------------------------------------------------------------------------------------------ */
+/* VoxelLayer debug outputs: voxel clouds and clearing endpoints from the resident grid         */
+/* ------------------------------------------------------------------------------------------ */
+#define NAVGPU_VOXEL_UNKNOWN 1 /* voxel_grid::UNKNOWN */
+#define NAVGPU_VOXEL_MARKED 2  /* voxel_grid::MARKED  */
+
+/* replaces: the loops of costmap_2d_cloud's voxelCallback (costmap_2d/src/costmap_2d_cloud.cpp:85-122; float xyz, a
+ * geometry_msgs::Point32 per voxel) and costmap_2d_markers' (costmap_2d/src/costmap_2d_markers.cpp:84-108; as_double = 1,
+ * a geometry_msgs::Point per voxel) over the voxel_grid message, on the RESIDENT voxel grid (NAVGPU_GRID_VOXEL) of every
+ * robot in [first, first+count).  Returned per robot: every voxel (x, y, z), z < z_voxels, whose VoxelGrid::getVoxel
+ * (voxel_grid/include/voxel_grid/voxel_grid.h:183-206) equals `status` - bits z and z + 16 of the column both set: MARKED,
+ * exactly one: UNKNOWN, neither: FREE, never returned - in the reference's loop order, y outer, then x, z inner.  The
+ * coordinates are mapToWorld3D (costmap_2d_cloud.cpp:36-42), origin + (m + 0.5) * resolution in double, with the robot's
+ * current origin and the fleet resolution for x / y and origin_z / z_resolution of navgpu_obstacle_configure for z;
+ * as_double = 0 narrows them to float as the assignment to a Point32 does.
+ * xyz = count x capacity x 3 floats or doubles, robot r's points from r * capacity * 3; counts[r] is always the true
+ * number, points beyond `capacity` are not written, and nothing is written behind a robot's last point.  xyz = NULL with
+ * capacity = 0 counts only.  The positions come from a prefix sum, not from atomics: two calls give identical bytes.
+ * NAVGPU_ERR_INVALID for a fleet without NAVGPU_LAYER_VOXEL, a status other than the two above, a range outside the fleet
+ * (or of more than 65535 robots), xyz = NULL with a capacity; NAVGPU_ERR_STATE while a staged rolling-window origin has not
+ * been applied by an update yet (as navgpu_footprint_cost).  Ordered on the fleet's stream behind whatever was queued
+ * before; returns when the results are in the caller's buffers. */
+int navgpu_voxel_points(navgpu_fleet* fleet, uint32_t first, uint32_t count, int status, int as_double, uint32_t capacity, void* xyz,
+                        uint32_t* counts);
+
+/* replaces: the clearing_endpoints cloud of VoxelLayer::raytraceFreespace (costmap_2d/plugins/voxel_layer.cpp:286-381).
+ * For every robot of the range, the clearing observations its last navgpu_costmap_stage staged, in staging order; for each,
+ * its points in cloud order; for every point that passes worldToMap3DFloat at :353 the clipped ray end (float)wpx,
+ * (float)wpy, (float)wpz of :297-372 - the same fp64 sequence k_obstacle walks its rays with.  An observation without
+ * points, or whose sensor origin fails worldToMap3DFloat (:277-284), yields none; so does every observation while the layer
+ * is disabled (:121-122).  counts[r] = the robot's total; obs_counts = count x max_observations entries, one per staged
+ * observation of the robot in staging order (0 for marking-only ones and beyond the staged ones), so a caller can publish
+ * one cloud per observation as the reference does.  xyz, capacity and the errors are those of navgpu_voxel_points.
+ * Valid once navgpu_costmap_update or navgpu_obstacle_update_bounds has consumed the staging - the reference clips with the
+ * origin AFTER updateOrigin (:119-120) - and until the next stage: NAVGPU_ERR_STATE otherwise. */
+int navgpu_voxel_clearing_endpoints(navgpu_fleet* fleet, uint32_t first, uint32_t count, uint32_t capacity, float* xyz,
+                                    uint32_t* obs_counts, uint32_t* counts);
+
+/* ------------------------------------------------------------------------------------------ */
 /* measurement                                                                                */
 /* ------------------------------------------------------------------------------------------ */
 typedef enum {
@@ -638,7 +676,8 @@ typedef enum {
   NAVGPU_K_SCORE = 4,    /* rollout + critics                             */
   NAVGPU_K_SELECT = 5,   /* argmin + result + oscillation update          */
   NAVGPU_K_FOOTPRINT = 6,/* batched footprint-cost queries                */
-  NAVGPU_K_COUNT = 7
+  NAVGPU_K_VOXEL_EXPORT = 7, /* voxel points / clearing endpoints: count, scan and emit launches */
+  NAVGPU_K_COUNT = 8
 } navgpu_kernel_id;
 /* HIP-event timing of the kernels on the fleet's stream.  While enabled every launch of the
  * listed kernels is bracketed by two hipEventRecord calls; read() synchronises and returns the

@@ -11,8 +11,9 @@ _LIB = None
 LAYER_STATIC, LAYER_OBSTACLE, LAYER_VOXEL, LAYER_INFLATION = 1, 2, 4, 8
 GRID_MASTER, GRID_STATIC, GRID_OBSTACLE, GRID_VOXEL, GRID_PATH, GRID_GOAL, GRID_GOAL_FRONT = range(7)
 OBS_MARKING, OBS_CLEARING = 1, 2
-K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT = range(7)
-KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost")
+VOXEL_UNKNOWN, VOXEL_MARKED = 1, 2  # voxel_grid::VoxelStatus
+K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT, K_VOXEL_EXPORT = range(8)
+KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export")
 
 
 class NavgpuError(RuntimeError):
@@ -356,6 +357,8 @@ SYMBOLS = [
     ("navgpu_rotate_recovery_configure", C.c_int, [vp, C.POINTER(RotateRecoveryParams)]),
     ("navgpu_rotate_recovery_step", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
     ("navgpu_carrot_plan", C.c_int, [vp, u32, u32, vp, vp, i32, vp, vp]),
+    ("navgpu_voxel_points", C.c_int, [vp, u32, u32, C.c_int, C.c_int, u32, vp, vp]),
+    ("navgpu_voxel_clearing_endpoints", C.c_int, [vp, u32, u32, u32, vp, vp, vp]),
     ("navgpu_navfn_create", C.c_int, [u32, u32, u32, i32, C.POINTER(vp)]),
     ("navgpu_navfn_destroy", C.c_int, [vp]),
     ("navgpu_navfn_set_costmap", C.c_int, [vp, u32, u32, vp, i32, i32, i32]),

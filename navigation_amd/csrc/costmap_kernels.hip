@@ -378,37 +378,14 @@ __global__ __launch_bounds__(256) void k_obstacle(CostmapDev cm, uint32_t first,
             b.touch(ox + dx * scale, oy + dy * scale);
           }
         } else {
-          if (obs.n_points == 0) continue;
-          const double ox = obs.ox, oy = obs.oy, oz = obs.oz;
-          // worldToMap3DFloat (voxel_layer.h:107-118)
-          if (ox < g.ox || oy < g.oy || oz < cm.origin_z) continue;
-          const double sensor_x = (ox - g.ox) / g.res, sensor_y = (oy - g.oy) / g.res, sensor_z = (oz - cm.origin_z) / cm.z_resolution;
-          if (!(sensor_x < g.nx && sensor_y < g.ny && sensor_z < size_z)) continue;
-          const double map_end_x = g.ox + (g.nx - 1 + 0.5) * g.res;  // origin + getSizeInMetersX()
-          const double map_end_y = g.oy + (g.ny - 1 + 0.5) * g.res;
+          VoxelRay ray;  // the sensor test and the clip of voxel_layer.cpp:269-353 (navgpu_device.h)
+          if (!voxelRayBegin(g, cm, size_z, obs, ray)) continue;
+          const double ox = ray.ox, oy = ray.oy;
+          const double sensor_x = ray.sensor_x, sensor_y = ray.sensor_y, sensor_z = ray.sensor_z;
           const uint32_t cell_range = cellDistance(obs.raytrace_range, g.res);
           for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
-            double wpx = pts[3 * p], wpy = pts[3 * p + 1], wpz = pts[3 * p + 2];
-            double distance = sqrt((ox - wpx) * (ox - wpx) + (oy - wpy) * (oy - wpy) + (oz - wpz) * (oz - wpz));
-            double scaling_fact = fmax(fmin(1.0, (distance - 2 * g.res) / distance), 0.0);
-            wpx = scaling_fact * (wpx - ox) + ox;
-            wpy = scaling_fact * (wpy - oy) + oy;
-            wpz = scaling_fact * (wpz - oz) + oz;
-            double a = wpx - ox, bb = wpy - oy, c = wpz - oz, t = 1.0;
-            if (wpz > cm.max_obstacle_height)
-              t = fmax(0.0, fmin(t, (cm.max_obstacle_height - 0.01 - oz) / c));
-            else if (wpz < cm.origin_z)
-              t = fmin(t, (cm.origin_z - oz) / c);
-            if (wpx < g.ox) t = fmin(t, (g.ox - ox) / a);
-            if (wpy < g.oy) t = fmin(t, (g.oy - oy) / bb);
-            if (wpx > map_end_x) t = fmin(t, (map_end_x - ox) / a);
-            if (wpy > map_end_y) t = fmin(t, (map_end_y - oy) / bb);
-            wpx = ox + a * t;
-            wpy = oy + bb * t;
-            wpz = oz + c * t;
-            if (wpx < g.ox || wpy < g.oy || wpz < cm.origin_z) continue;
-            double px = (wpx - g.ox) / g.res, py = (wpy - g.oy) / g.res, pz = (wpz - cm.origin_z) / cm.z_resolution;
-            if (!(px < g.nx && py < g.ny && pz < size_z)) continue;
+            double wpx, wpy, wpz, px, py, pz;
+            if (!voxelRayEnd(g, cm, size_z, ray, pts + 3 * p, wpx, wpy, wpz, px, py, pz)) continue;
             // clearVoxelLineInMap endpoint check (voxel_grid.cpp:131-136) is implied by the two tests above
             if (pass == 0) {
               raytrace3d(g.nx, sensor_x, sensor_y, sensor_z, px, py, pz, cell_range,

@@ -214,6 +214,27 @@ struct FootprintDev {
 };
 void launch_footprint_cost(const FootprintDev& d, uint32_t first, uint32_t count, const uint32_t* h_counts, const uint32_t* h_fp_n, hipStream_t s);
 
+// voxel-layer debug outputs (voxel_export_kernels.hip): per-launch view of the fleet's export scratch
+struct VoxelExportDev {
+  uint32_t* totals;      // [count][stride] per-chunk totals of launch (a), their exclusive prefix after (b)
+  uint32_t stride;
+  uint32_t* counts;      // [count]
+  uint32_t* obs_counts;  // [count][max_obs] (clearing endpoints)
+  void* xyz;             // [count][capacity][3] float or double, or null while counting
+  uint32_t capacity;     // points per robot in xyz
+  int32_t status, as_double;  // NAVGPU_VOXEL_UNKNOWN / _MARKED; doubles instead of floats (voxel points)
+};
+constexpr uint32_t kVxThreads = 256;                    // lanes of every export workgroup
+constexpr uint32_t kVxPerLane = 4;                      // consecutive columns of a lane: one 16-byte load
+constexpr uint32_t kVxChunk = kVxThreads * kVxPerLane;  // columns of a chunk (1000 x 1000: 977 chunks)
+constexpr uint32_t kClearChunk = kVxThreads;            // points of a chunk: one per lane (the predicate is ~40 fp64 operations)
+inline uint32_t voxel_export_chunks(uint32_t cells) { return (cells + kVxChunk - 1) / kVxChunk; }                  // chunk totals per robot: voxel points
+inline uint32_t clear_export_chunks(uint32_t max_points) { return (max_points + kClearChunk - 1) / kClearChunk; }  // ... per observation: clearing endpoints
+void launch_voxel_points_count(const CostmapDev& cm, const VoxelExportDev& v, uint32_t first, uint32_t count, hipStream_t s);
+void launch_voxel_points_emit(const CostmapDev& cm, const VoxelExportDev& v, uint32_t first, uint32_t count, hipStream_t s);
+void launch_clear_endpoints_count(const CostmapDev& cm, const VoxelExportDev& v, uint32_t first, uint32_t count, hipStream_t s);
+void launch_clear_endpoints_emit(const CostmapDev& cm, const VoxelExportDev& v, uint32_t first, uint32_t count, hipStream_t s);
+
 // ---- launchers (defined in the .hip files) ---------------------------------------------------
 void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const double* bounds_in, int only_bounds,
                      hipStream_t s);
@@ -285,6 +306,61 @@ __device__ __forceinline__ double hyp2(double x, double y) {
   double e = (a - (s - bb)) + (b - bb);
   double r = __builtin_fma(-h, h, s);
   return h + (r + e) / (2.0 * h);
+}
+
+// VoxelLayer::raytraceFreespace (voxel_layer.cpp:266-372) without the ray walk: what an observation fixes, and the clipped
+// end of one point's ray.  k_obstacle<true> walks the ray to that end, k_clear_count / k_clear_emit (voxel_export_kernels.hip)
+// return the end itself (the clearing_endpoints cloud); fp64 in the reference's statement order, -ffp-contract=off.
+struct VoxelRay {
+  double ox, oy, oz;                    // sensor origin
+  double sensor_x, sensor_y, sensor_z;  // the same in cells (worldToMap3DFloat, voxel_layer.h:107-118)
+  double map_end_x, map_end_y;          // origin + getSizeInMetersX / Y
+};
+// false: the observation clears nothing (no points, :269-270; sensor origin off the map, :277-284).  size_z = min(z_voxels, 16)
+__device__ __forceinline__ bool voxelRayBegin(const Geom& g, const CostmapDev& cm, uint32_t size_z, const ObsCsr& obs, VoxelRay& r) {
+  if (obs.n_points == 0) return false;
+  r.ox = obs.ox;
+  r.oy = obs.oy;
+  r.oz = obs.oz;
+  if (r.ox < g.ox || r.oy < g.oy || r.oz < cm.origin_z) return false;
+  r.sensor_x = (r.ox - g.ox) / g.res;
+  r.sensor_y = (r.oy - g.oy) / g.res;
+  r.sensor_z = (r.oz - cm.origin_z) / cm.z_resolution;
+  if (!(r.sensor_x < g.nx && r.sensor_y < g.ny && r.sensor_z < size_z)) return false;
+  r.map_end_x = g.ox + (g.nx - 1 + 0.5) * g.res;
+  r.map_end_y = g.oy + (g.ny - 1 + 0.5) * g.res;
+  return true;
+}
+// :297-353 for the point pt[0..2]: (wpx, wpy, wpz) the clipped end in the world, (px, py, pz) in cells; false when it fails
+// worldToMap3DFloat at :353 (no ray, no endpoint)
+__device__ __forceinline__ bool voxelRayEnd(const Geom& g, const CostmapDev& cm, uint32_t size_z, const VoxelRay& r, const float* pt, double& wpx,
+                                            double& wpy, double& wpz, double& px, double& py, double& pz) {
+  const double ox = r.ox, oy = r.oy, oz = r.oz;
+  wpx = pt[0];
+  wpy = pt[1];
+  wpz = pt[2];
+  double distance = sqrt((ox - wpx) * (ox - wpx) + (oy - wpy) * (oy - wpy) + (oz - wpz) * (oz - wpz));
+  double scaling_fact = fmax(fmin(1.0, (distance - 2 * g.res) / distance), 0.0);
+  wpx = scaling_fact * (wpx - ox) + ox;
+  wpy = scaling_fact * (wpy - oy) + oy;
+  wpz = scaling_fact * (wpz - oz) + oz;
+  double a = wpx - ox, bb = wpy - oy, c = wpz - oz, t = 1.0;
+  if (wpz > cm.max_obstacle_height)
+    t = fmax(0.0, fmin(t, (cm.max_obstacle_height - 0.01 - oz) / c));
+  else if (wpz < cm.origin_z)
+    t = fmin(t, (cm.origin_z - oz) / c);
+  if (wpx < g.ox) t = fmin(t, (g.ox - ox) / a);
+  if (wpy < g.oy) t = fmin(t, (g.oy - oy) / bb);
+  if (wpx > r.map_end_x) t = fmin(t, (r.map_end_x - ox) / a);
+  if (wpy > r.map_end_y) t = fmin(t, (r.map_end_y - oy) / bb);
+  wpx = ox + a * t;
+  wpy = oy + bb * t;
+  wpz = oz + c * t;
+  if (wpx < g.ox || wpy < g.oy || wpz < cm.origin_z) return false;
+  px = (wpx - g.ox) / g.res;
+  py = (wpy - g.oy) / g.res;
+  pz = (wpz - cm.origin_z) / cm.z_resolution;
+  return px < g.nx && py < g.ny && pz < size_z;
 }
 
 // navfn::NavFn arrays of a batch of plans (navfn_kernels.hip, navgpu_navfn.cpp)

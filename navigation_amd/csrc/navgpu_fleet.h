@@ -1,7 +1,8 @@
 // Internal to libnavgpu.so: the fleet object behind the opaque navgpu_fleet handle and the helpers the host
 // translation units share (navgpu_host.cpp: lifetime / costmap layers / DWA planner / measurement,
 // navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner,
-// navgpu_recovery.cpp: footprint-cost queries, RotateRecovery, CarrotPlanner).
+// navgpu_recovery.cpp: footprint-cost queries, RotateRecovery, CarrotPlanner, navgpu_voxel_export.cpp: voxel-layer debug
+// outputs).
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -133,6 +134,16 @@ struct navgpu_fleet {
     double *d_poses = nullptr, *d_costs = nullptr, *h_poses = nullptr, *h_costs = nullptr;  // [cap][3], [cap]; h_: pinned
     uint32_t *d_off = nullptr, *d_first = nullptr, *h_off = nullptr, *h_first = nullptr;    // [n + 1], [n]
   } fq;
+  // voxel-layer debug outputs (navgpu_voxel_export.cpp): chunk totals and counts, sized at creation for a voxel fleet; the
+  // point buffer grows on demand
+  struct VoxelExport {
+    uint32_t stride = 0;          // chunk totals per robot: the larger of the two exports' needs
+    uint32_t *d_totals = nullptr, *d_counts = nullptr, *d_obs_counts = nullptr;  // [n][stride], [n], [n][max_obs]
+    uint32_t *h_counts = nullptr, *h_obs_counts = nullptr;                       // pinned
+    void* d_xyz = nullptr;
+    size_t xyz_bytes = 0;
+  } vx;
+  std::vector<uint8_t> obs_consumed;            // [n] an update has run on what navgpu_costmap_stage staged last
   navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers
   double* d_bounds_tmp = nullptr;               // [n][4]

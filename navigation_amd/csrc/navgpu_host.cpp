@@ -30,7 +30,7 @@ int navgpu_device_count(void) {
   return n;
 }
 const char* navgpu_kernel_name(int32_t k) {
-  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost"};
+  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export"};
   return (k >= 0 && k < NAVGPU_K_COUNT) ? names[k] : "?";
 }
 
@@ -146,6 +146,12 @@ int navgpu_fleet_create(const navgpu_fleet_desc* d, navgpu_fleet** out) {
     if (cm.voxel) A(cm.voxel_alt, (size_t)n * cm.cells_padded);
   }
   if (cm.voxel) A(cm.mark_seq, (size_t)n * cm.max_points);
+  if (cm.voxel) {  // navgpu_voxel_points / navgpu_voxel_clearing_endpoints: one total per chunk of columns / of an observation's points
+    f->vx.stride = std::max(voxel_export_chunks(cm.cells), clear_export_chunks(cm.max_points) * cm.max_obs);
+    A(f->vx.d_totals, (size_t)n * f->vx.stride);
+    A(f->vx.d_counts, n);
+    A(f->vx.d_obs_counts, (size_t)n * cm.max_obs);
+  }
 #define AP(ptr, cnt)                              \
   if ((rc = f->allocPinned(&(ptr), (cnt))) != 0) { \
     navgpu_fleet_destroy(f);                       \
@@ -154,6 +160,10 @@ int navgpu_fleet_create(const navgpu_fleet_desc* d, navgpu_fleet** out) {
   AP(f->hp_used, n);
   AP(f->hp_shift, (size_t)n * 2);
   AP(f->hp_result, (size_t)n * 2);  // two slots: navgpu_planner_set_cycles_in_flight
+  if (cm.voxel) {
+    AP(f->vx.h_counts, n);
+    AP(f->vx.h_obs_counts, (size_t)n * cm.max_obs);
+  }
   f->pl.result = f->hp_result;  // k_select writes results straight into pinned host memory (72 B per robot)
 #undef AP
   A(f->d_bounds_tmp, (size_t)n * 4);
@@ -226,6 +236,7 @@ int navgpu_fleet_create(const navgpu_fleet_desc* d, navgpu_fleet** out) {
   f->h_fp_spec.assign((size_t)n * kMaxFootprint * 2, 0.0);
   f->h_fp_n.assign(n, 0);
   f->grid_partial.assign(n, 0);
+  f->obs_consumed.assign(n, 0);
   f->bounded_grids = true;  // navgpu_planner_set_bounded_map_grids
   f->h_box.assign((size_t)n * 4, 0);
   f->inputs_gen.assign(n, 0);
@@ -850,6 +861,7 @@ int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
   if (f->desc.rolling_window) f->touchInputs(first, count);  // the origins move now
   HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
   for (uint32_t li = 0; li < count; ++li) f->hp_cnt[first + li] = f->hp_used[first + li] = 0;
+  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 0);
   for (uint32_t k = 0; k < n_obs; ++k) {
     const navgpu_observation& o = obs[k];
     if (o.instance < first || o.instance >= first + count) return NAVGPU_ERR_INVALID;
@@ -956,6 +968,7 @@ int navgpu_costmap_update(navgpu_fleet* f, uint32_t first, uint32_t count) {
     if (rc) return rc;
   }
   PROFILED(f, NAVGPU_K_OBSTACLE, launch_obstacle(cm, first, count, nullptr, 0, f->stream));
+  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 1);
   PROFILED(f, NAVGPU_K_MERGE, launch_merge(cm, first, count, nullptr, f->stream));
   if (cm.layers & NAVGPU_LAYER_INFLATION) PROFILED(f, NAVGPU_K_INFLATE, launch_inflate(cm, first, count, nullptr, f->stream));
   return checkLaunch();
@@ -997,6 +1010,7 @@ int navgpu_obstacle_update_bounds(navgpu_fleet* f, uint32_t first, uint32_t coun
   }
   HIP_TRY(hipMemcpyAsync(f->d_bounds_tmp, bounds, sizeof(double) * 4 * count, hipMemcpyHostToDevice, f->stream));
   PROFILED(f, NAVGPU_K_OBSTACLE, launch_obstacle(f->cm, first, count, f->d_bounds_tmp, 1, f->stream));
+  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 1);
   HIP_TRY(hipMemcpyAsync(bounds, f->d_bounds_tmp, sizeof(double) * 4 * count, hipMemcpyDeviceToHost, f->stream));
   HIP_TRY(waitStream(f->stream));
   return checkLaunch();

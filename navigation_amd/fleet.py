@@ -10,6 +10,8 @@ Method names follow the reference interfaces they front:
   footprint_cost        CostmapModel::footprintCost          (base_local_planner/src/costmap_model.cpp:50-142)
   rotate_recovery_step  RotateRecovery::runBehavior, one pass (rotate_recovery/src/rotate_recovery.cpp:105-153)
   carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
+  voxel_points          costmap_2d_cloud / costmap_2d_markers voxelCallback (costmap_2d/src/costmap_2d_cloud.cpp:85-122)
+  voxel_clearing_endpoints  VoxelLayer::raytraceFreespace's clearing_endpoints cloud (plugins/voxel_layer.cpp:286-381)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -484,6 +486,36 @@ class Fleet:
         found = np.zeros(len(s), np.int32)
         check(self.L.navgpu_carrot_plan(self.h, first, len(s), _ptr(s), _ptr(g), int(allow_unknown), _ptr(targets), _ptr(found)), "carrot_plan")
         return targets, found
+
+    # ---------------------------------------------------------------- voxel layer debug outputs
+    def voxel_points(self, status, as_double=False, first=0, count=None):
+        """The voxels whose VoxelGrid::getVoxel equals `status` (N.VOXEL_UNKNOWN / N.VOXEL_MARKED) as world coordinates of
+        their centres, in the reference's loop order (y, x, z): one (k, 3) float32 / float64 array per robot.  Counts first,
+        then sizes the buffer from the largest count."""
+        first, count = self._range(first, count)
+        counts = np.zeros(count, np.uint32)
+        check(self.L.navgpu_voxel_points(self.h, first, count, int(status), int(as_double), 0, None, _ptr(counts)), "voxel_points")
+        cap = int(counts.max())
+        xyz = np.zeros((count, cap, 3), np.float64 if as_double else np.float32)
+        if cap:
+            check(self.L.navgpu_voxel_points(self.h, first, count, int(status), int(as_double), cap, _ptr(xyz), _ptr(counts)), "voxel_points")
+        return [xyz[k, :counts[k]] for k in range(count)]
+
+    def voxel_clearing_endpoints(self, first=0, count=None):
+        """The clearing_endpoints clouds of the last staged and updated cycle: per robot a list with one (k, 3) float32 array
+        per staged observation, in staging order (empty for marking-only ones)."""
+        first, count = self._range(first, count)
+        max_obs = max(1, self.desc.max_observations)
+        counts = np.zeros(count, np.uint32)
+        per_obs = np.zeros((count, max_obs), np.uint32)
+        check(self.L.navgpu_voxel_clearing_endpoints(self.h, first, count, 0, None, _ptr(per_obs), _ptr(counts)), "voxel_clearing_endpoints")
+        cap = int(counts.max())
+        xyz = np.zeros((count, cap, 3), np.float32)
+        if cap:
+            check(self.L.navgpu_voxel_clearing_endpoints(self.h, first, count, cap, _ptr(xyz), _ptr(per_obs), _ptr(counts)),
+                  "voxel_clearing_endpoints")
+        off = np.concatenate([np.zeros((count, 1), np.int64), np.cumsum(per_obs, axis=1, dtype=np.int64)], axis=1)
+        return [[xyz[k, off[k, o]:off[k, o + 1]] for o in range(max_obs)] for k in range(count)]
 
     # ---------------------------------------------------------------- measurement
     def profile(self, enable=True):

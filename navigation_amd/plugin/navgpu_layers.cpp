@@ -91,6 +91,29 @@ bool LayerBridge::updateCosts(costmap_2d::Costmap2D& master, int min_i, int min_
   return true;
 }
 
+bool LayerBridge::voxelGrid(std::vector<uint32_t>* data) {
+  return navgpu_grid_download(fleet_, NAVGPU_GRID_VOXEL, 0, 1, &(*data)[0]) == NAVGPU_OK;
+}
+
+bool LayerBridge::clearingEndpoints(size_t n_clearing, std::vector<std::vector<geometry_msgs::Point32> >* clouds) {
+  const uint32_t max_obs = 16;  // d.max_observations of create()
+  uint32_t per_obs[max_obs], total = 0;
+  if (navgpu_voxel_clearing_endpoints(fleet_, 0, 1, 0, NULL, per_obs, &total) != NAVGPU_OK) return false;
+  std::vector<float> xyz((size_t)total * 3 + 1);
+  if (total && navgpu_voxel_clearing_endpoints(fleet_, 0, 1, total, &xyz[0], per_obs, &total) != NAVGPU_OK) return false;
+  clouds->assign(n_clearing, std::vector<geometry_msgs::Point32>());
+  size_t at = 0;
+  for (size_t k = 0; k < n_clearing && k < max_obs; ++k) {
+    (*clouds)[k].resize(per_obs[k]);
+    for (uint32_t i = 0; i < per_obs[k]; ++i, ++at) {
+      (*clouds)[k][i].x = xyz[3 * at];
+      (*clouds)[k][i].y = xyz[3 * at + 1];
+      (*clouds)[k][i].z = xyz[3 * at + 2];
+    }
+  }
+  return true;
+}
+
 // ----------------------------------------------------------------------------- InflationBounds
 InflationBounds::InflationBounds() : last_min_x(-std::numeric_limits<float>::max()), last_min_y(-std::numeric_limits<float>::max()),
                                      last_max_x(std::numeric_limits<float>::max()), last_max_y(std::numeric_limits<float>::max()) {}
@@ -254,7 +277,54 @@ bool ObstacleLayer::gpuUpdateBounds(double rx, double ry, double ryaw, double* m
   *max_x = b[2];
   *max_y = b[3];
   costmap_2d::transformFootprint(rx, ry, ryaw, getFootprint(), transformed_footprint_);  // updateFootprint :415-425
+  publishDebugTopics(clearing);
   return true;
+}
+void ObstacleLayer::advertiseVoxelTopics(ros::NodeHandle& nh) {  // voxel_layer.cpp:55-65
+  nh.param("publish_voxel_map", publish_voxel_, false);
+  if (publish_voxel_) voxel_pub_ = nh.advertise<costmap_2d::VoxelGrid>("voxel_grid", 1);
+  clearing_endpoints_pub_ = nh.advertise<sensor_msgs::PointCloud>("clearing_endpoints", 1);
+}
+void ObstacleLayer::publishVoxelTopics(const std::vector<costmap_2d::Observation>& clearing, int z_voxels, double origin_z, double z_resolution) {
+  if (clearing_endpoints_pub_.getNumSubscribers() > 0 && !clearing.empty()) {  // voxel_layer.cpp:286-291, :375-381
+    std::vector<std::vector<geometry_msgs::Point32> > clouds;
+    if (!gpu_.clearingEndpoints(clearing.size(), &clouds)) {
+      ROS_ERROR_THROTTLE(1.0, "navgpu_voxel_clearing_endpoints: %s", navgpu_last_error());
+    } else {
+      for (size_t k = 0; k < clearing.size(); ++k) {
+        // the reference publishes nothing for an observation without points or with its sensor off the map (:269-284)
+        if (clearing[k].cloud_->points.empty() || clouds[k].empty()) continue;
+        sensor_msgs::PointCloud msg;
+        msg.points.swap(clouds[k]);
+        msg.header.frame_id = global_frame_;
+        // pcl_conversions::fromPCL(header).stamp: the PCL stamp is microseconds (whole seconds and a multiple of 1000 ns: both exact)
+        const uint64_t stamp_us = clearing[k].cloud_->header.stamp;
+        msg.header.stamp = ros::Time((double)(stamp_us / 1000000ull)) + ros::Duration((double)((stamp_us % 1000000ull) * 1000ull) * 1e-9);
+        msg.header.seq = clearing[k].cloud_->header.seq;
+        clearing_endpoints_pub_.publish(msg);
+      }
+    }
+  }
+  if (publish_voxel_) {  // voxel_layer.cpp:190-209
+    costmap_2d::VoxelGrid grid_msg;
+    grid_msg.size_x = size_x_;
+    grid_msg.size_y = size_y_;
+    grid_msg.size_z = z_voxels;
+    grid_msg.data.resize((size_t)size_x_ * size_y_);
+    if (grid_msg.data.empty() || !gpu_.voxelGrid(&grid_msg.data)) {
+      ROS_ERROR_THROTTLE(1.0, "navgpu voxel grid download: %s", navgpu_last_error());
+      return;
+    }
+    grid_msg.origin.x = origin_x_;
+    grid_msg.origin.y = origin_y_;
+    grid_msg.origin.z = origin_z;
+    grid_msg.resolutions.x = resolution_;
+    grid_msg.resolutions.y = resolution_;
+    grid_msg.resolutions.z = z_resolution;
+    grid_msg.header.frame_id = global_frame_;
+    grid_msg.header.stamp = ros::Time::now();
+    voxel_pub_.publish(grid_msg);
+  }
 }
 void ObstacleLayer::updateBounds(double rx, double ry, double ryaw, double* min_x, double* min_y, double* max_x, double* max_y) {
   gpuUpdateBounds(rx, ry, ryaw, min_x, min_y, max_x, max_y);
@@ -270,6 +340,11 @@ void ObstacleLayer::updateCosts(costmap_2d::Costmap2D& master, int min_i, int mi
 
 // ----------------------------------------------------------------------------- VoxelLayer
 VoxelLayer::~VoxelLayer() { delete voxel_dsrv_; }
+void VoxelLayer::onInitialize() {  // voxel_layer.cpp:55-65
+  ObstacleLayer::onInitialize();
+  ros::NodeHandle private_nh("~/" + name_);
+  advertiseVoxelTopics(private_nh);
+}
 void VoxelLayer::setupDynamicReconfigure(ros::NodeHandle& nh) {  // voxel_layer.cpp:63-69
   voxel_dsrv_ = new dynamic_reconfigure::Server<costmap_2d::VoxelPluginConfig>(nh);
   voxel_dsrv_->setCallback(boost::bind(&VoxelLayer::reconfigureCB, this, _1, _2));
@@ -327,6 +402,7 @@ void GpuLayers::onInitialize() {
   ip_.priority_queue_order = pq;
   need_reinflation_ = true;
   ObstacleLayer::onInitialize();
+  if (voxel_) advertiseVoxelTopics(nh);
 }
 void GpuLayers::pushObstacleParams() {
   vp_.enabled = enabled_;

@@ -21,7 +21,9 @@
 #include <costmap_2d/layer.h>
 #include <costmap_2d/layered_costmap.h>
 #include <costmap_2d/obstacle_layer.h>
+#include <costmap_2d/VoxelGrid.h>
 #include <dynamic_reconfigure/server.h>
+#include <sensor_msgs/PointCloud.h>
 
 #include <boost/thread.hpp>
 
@@ -47,6 +49,11 @@ class LayerBridge {
   // updateCosts of the obstacle-type layer and / or the inflation layer on the master grid handed in
   bool updateCosts(costmap_2d::Costmap2D& master, int min_i, int min_j, int max_i, int max_j, bool merge, bool inflate,
                    unsigned char* layer_grid_out);
+  // VoxelLayer's debug outputs from the resident grid, valid after updateBounds: the columns of the voxel_grid message
+  // (voxel_layer.cpp:190-209), and one clearing_endpoints cloud per clearing observation of that updateBounds, in its order
+  // (:286-381; updateBounds stages the clearing observations first)
+  bool voxelGrid(std::vector<uint32_t>* data);
+  bool clearingEndpoints(size_t n_clearing, std::vector<std::vector<geometry_msgs::Point32> >* clouds);
 
  private:
   navgpu_fleet* fleet_;
@@ -97,7 +104,7 @@ class InflationLayer : public costmap_2d::Layer {
 // hot virtuals.
 class ObstacleLayer : public costmap_2d::ObstacleLayer {
  public:
-  ObstacleLayer() {}
+  ObstacleLayer() : publish_voxel_(false) {}
   virtual ~ObstacleLayer() {}
   virtual void onInitialize();
   virtual void matchSize();
@@ -111,6 +118,13 @@ class ObstacleLayer : public costmap_2d::ObstacleLayer {
   virtual int gpuLayers() const { return NAVGPU_LAYER_OBSTACLE; }
   virtual void pushObstacleParams();
   bool gpuUpdateBounds(double rx, double ry, double ryaw, double* min_x, double* min_y, double* max_x, double* max_y);
+  // what VoxelLayer::onInitialize advertises (voxel_layer.cpp:55-65) and what its updateBounds / raytraceFreespace publish
+  // (:190-209, :375-381), for the adapters that run a voxel fleet; called at the end of gpuUpdateBounds
+  void advertiseVoxelTopics(ros::NodeHandle& nh);
+  void publishVoxelTopics(const std::vector<costmap_2d::Observation>& clearing, int z_voxels, double origin_z, double z_resolution);
+  virtual void publishDebugTopics(const std::vector<costmap_2d::Observation>& clearing) {}
+  ros::Publisher voxel_pub_, clearing_endpoints_pub_;
+  bool publish_voxel_;
   LayerBridge gpu_;
   // The reference's obstacle / voxel layers take no lock in their reconfigure callbacks (a VoxelLayer reconfigure runs
   // matchSize from the spinner thread, voxel_layer.cpp:77-91).  Here matchSize destroys and recreates the fleet handle,
@@ -119,18 +133,24 @@ class ObstacleLayer : public costmap_2d::ObstacleLayer {
 };
 
 // costmap_2d::VoxelLayer's members are private, so this adapter derives from ObstacleLayer like VoxelLayer itself does
-// and re-reads VoxelPluginConfig with its own dynamic_reconfigure server (voxel_layer.cpp:63-91).  The voxel_grid /
-// clearing_endpoints debug topics of the reference are not published (visualisation, out of scope).
+// and re-reads VoxelPluginConfig with its own dynamic_reconfigure server (voxel_layer.cpp:63-91).  It publishes what the
+// reference class publishes: voxel_grid when publish_voxel_map is set, from navgpu_grid_download(NAVGPU_GRID_VOXEL), and
+// one clearing_endpoints cloud per clearing observation while that topic has subscribers, from
+// navgpu_voxel_clearing_endpoints (ObstacleLayer::publishVoxelTopics).
 class VoxelLayer : public ObstacleLayer {
  public:
   VoxelLayer() : voxel_dsrv_(NULL), z_voxels_(10), unknown_threshold_(15), mark_threshold_(0), origin_z_(0.0), z_resolution_(0.2) {}
   virtual ~VoxelLayer();
   virtual bool isDiscretized() { return true; }
+  virtual void onInitialize();
 
  protected:
   virtual void setupDynamicReconfigure(ros::NodeHandle& nh);
   virtual int gpuLayers() const { return NAVGPU_LAYER_VOXEL; }
   virtual void pushObstacleParams();
+  virtual void publishDebugTopics(const std::vector<costmap_2d::Observation>& clearing) {
+    publishVoxelTopics(clearing, z_voxels_, origin_z_, z_resolution_);
+  }
 
  private:
   void reconfigureCB(costmap_2d::VoxelPluginConfig& config, uint32_t level);
@@ -157,6 +177,9 @@ class GpuLayers : public ObstacleLayer {
   virtual void onFootprintChanged();
   virtual int gpuLayers() const { return (voxel_ ? NAVGPU_LAYER_VOXEL : NAVGPU_LAYER_OBSTACLE) | NAVGPU_LAYER_INFLATION; }
   virtual void pushObstacleParams();
+  virtual void publishDebugTopics(const std::vector<costmap_2d::Observation>& clearing) {
+    if (voxel_) publishVoxelTopics(clearing, vp_.z_voxels, vp_.origin_z, vp_.z_resolution);
+  }
 
  private:
   bool voxel_;
