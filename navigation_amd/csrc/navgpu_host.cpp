@@ -1037,7 +1037,7 @@ int navgpu_obstacle_update_costs(navgpu_fleet* f, uint32_t first, uint32_t count
 // all within `reach` of the robot: speed bound x sim_time + forward_point_distance.  Every axis velocity a sample can
 // take lies between the robot's velocity and the limits (simple_trajectory_generator.cpp:77-110, velocity_iterator.h;
 // computeNewVelocities moves from the one towards the other), so |v_axis| <= max(|min|, |max|, |v|).  k_samples turns
-// the reach into the robot's box and a wavefront stops once that box is settled (k_bfs_wave); what it leaves open is
+// the reach into the robot's box and a wavefront stops once that box is settled (k_bfs_rows, k_bfs_rows2, k_bfs_global); what it leaves open is
 // completed by ensureCompleteGrids before anybody else reads the grid.
 static const int kBoxMarginCells = 4;  // cell rounding of pose and points, the touched-obstacle ring, slack
 static double reachMetres(const navgpu_dwa_config& c, const float vel[3], const float* sample) {

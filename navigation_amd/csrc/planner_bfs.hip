@@ -1,11 +1,11 @@
 // MapGrid wavefronts (gfx950): k_free_bits, k_bfs_global (maps beyond the register-resident sweeps of planner_bfs_rows.hip)
 // and launch_bfs, which picks the kernel for a map.
-#include "planner_common.h"
+#include "planner_bfs_common.h"
 
 namespace navgpu {
 
 // k_free_bits: the traversable-cell bitmap of every robot's costmap, [ny][W] words, once per launch for the two or three
-// wavefronts of a robot (each reads its rows twice).  Inside k_bfs_wave the same 160 KB of cost bytes took 14 wide loads
+// wavefronts of a robot (each reads its rows twice).  Read inside a sweep, the same 160 KB of cost bytes took 14 wide loads
 // per lane that the register budget of the sweep serialises: 16 us per read, against 7 dword loads now.
 __global__ __launch_bounds__(256) void k_free_bits(PlannerDev pl, uint32_t first) {
   const uint32_t W = (pl.nx + 31) >> 5, words = pl.ny * W;
@@ -53,53 +53,10 @@ __global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, uint32_t fir
     nxt[w] = 0;
   }
   __syncthreads();
-  {
-    const uint32_t n = pl.plan_count[inst];
-    const double* P = pl.plan + (size_t)inst * pl.max_plan * 2;
-    const bool ovr = which == 2;
-    const double lx = pl.front_last[2 * inst], ly = pl.front_last[2 * inst + 1];
-    const uint32_t chunk = (n + blockDim.x - 1) / blockDim.x;
-    const uint32_t i0 = min(n, tid * chunk), i1 = min(n, i0 + chunk);
-    uint32_t mine = 0;
-    for (uint32_t i = i0; i < i1; ++i) mine += adjustedPoints(P, i, lx, ly, ovr, n, g.res, true, [](uint32_t, double, double) {});
-    uint32_t total;
-    const uint32_t bs = blockExclusiveScan1024(mine, s_wave, &total);
-    auto valid = [&](double x, double y, uint32_t& cell) {
-      uint32_t mx, my;
-      if (!worldToMap(g, x, y, mx, my)) return false;
-      cell = my * nx + mx;
-      return master[cell] != kNoInfo;
-    };
-    uint32_t fmin_ = 0xFFFFFFFFu, b = bs;
-    for (uint32_t i = i0; i < i1; ++i)
-      b += adjustedPoints(P, i, lx, ly, ovr, n, g.res, false, [&](uint32_t k, double x, double y) {
-        uint32_t cell;
-        if (valid(x, y, cell)) fmin_ = min(fmin_, b + k);
-      });
-    const uint32_t f = blockMin1024(fmin_, s_wave);
-    if (f != 0xFFFFFFFFu) {
-      uint32_t emin = total;
-      b = bs;
-      for (uint32_t i = i0; i < i1; ++i)
-        b += adjustedPoints(P, i, lx, ly, ovr, n, g.res, false, [&](uint32_t k, double x, double y) {
-          uint32_t cell;
-          if (b + k > f && !valid(x, y, cell)) emin = min(emin, b + k);
-        });
-      const uint32_t e = blockMin1024(emin, s_wave);
-      b = bs;
-      for (uint32_t i = i0; i < i1; ++i)
-        b += adjustedPoints(P, i, lx, ly, ovr, n, g.res, false, [&](uint32_t k, double x, double y) {
-          const uint32_t idx = b + k;
-          const bool seed = (which == 0) ? (idx >= f && idx < e) : (idx == e - 1);
-          if (!seed) return;
-          uint32_t cell;
-          if (!valid(x, y, cell)) return;
-          const uint32_t my = cell / nx, mx = cell - my * nx;
-          atomicOr(&cur[my * W + (mx >> 5)], 1u << (mx & 31));
-          dist[cell] = 0;
-        });
-    }
-  }
+  bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
+    atomicOr(&cur[my * W + (mx >> 5)], 1u << (mx & 31));
+    dist[my * nx + mx] = 0;
+  });
   __syncthreads();
   for (uint32_t w = tid; w < words; w += blockDim.x) vis[w] |= cur[w];
   // Activity-driven levels: the map is cut into tiles of 4 words x 16 rows (128 x 16 cells, one wave each; tile
@@ -120,19 +77,9 @@ __global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, uint32_t fir
   const uint32_t lane = tid & 63u, wave = tid >> 6;
   const uint32_t lr = lane >> 2, lc = lane & 3u;
   uint32_t level = 0, buf = 0;  // buf: which flag set belongs to `cur`
-  // bounded search (see k_bfs_wave): the robot's region, its pocket mask, and the words of the bitmaps that cover it
-  int gx0 = 0, gx1 = -1, gy0 = 0, gy1 = -1, care_ok = 0;
-  if (pl.bfs_bounded && pl.bfs_grids == 3) {
-    const int* bb = pl.bfs_box + (size_t)inst * 8;
-    gx0 = bb[0];
-    gx1 = bb[1];
-    gy0 = bb[2];
-    gy1 = bb[3];
-    care_ok = bb[4];
-  }
-  const bool bounded = gx1 >= gx0 && gy1 >= gy0;
-  const uint32_t rg_w0 = (uint32_t)(gx0 >> 5), rg_nw = bounded ? (uint32_t)(gx1 >> 5) - rg_w0 + 1 : 0u;
-  const uint32_t rg_words = bounded ? (uint32_t)(gy1 - gy0 + 1) * rg_nw : 0u;
+  // the robot's region (the whole map unless the search is bounded), its pocket mask, and the words of the bitmaps that cover it
+  const BfsRegion rg = bfsRegion(pl, inst);
+  const uint32_t rg_nw = (uint32_t)(rg.w1 - rg.w0 + 1), rg_words = (uint32_t)(rg.y1 - rg.y0 + 1) * rg_nw;
   const uint32_t* care = pl.bfs_care + (size_t)inst * kCareRows * kCareWords;
   while (true) {
     int any = 0;
@@ -191,22 +138,12 @@ __global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, uint32_t fir
         if (q.in) {
           const uint32_t cand = ((q.fc << 1) | (q.l >> 31) | (q.fc >> 1) | (q.r << 31) | q.u | q.d) & ~q.v;
           nf = cand & q.fb;
-          uint32_t no = cand & ~q.fb;
           nxt[q.w] = nf;
           if (cand) {
             vis[q.w] = q.v | cand;
             uint32_t* drow = dist + q.row * nx + q.wi * 32;
-            uint32_t qq = nf;
-            while (qq) {
-              const int bpos = __ffs(qq) - 1;
-              qq &= qq - 1;
-              drow[bpos] = level + 1;
-            }
-            while (no) {
-              const int bpos = __ffs(no) - 1;
-              no &= no - 1;
-              drow[bpos] = N_obst;
-            }
+            bfsStoreCells(drow, nf, level + 1, false);
+            bfsStoreCells(drow, cand & ~q.fb, N_obst, false);
           }
         }
         const uint64_t nz = __builtin_amdgcn_ballot_w64(nf != 0);
@@ -234,32 +171,21 @@ __global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, uint32_t fir
     nxt = t;
     buf ^= 1u;
     ++level;
-    if (bounded && (level & 7u) == 0) {  // stop once no cell of the box is open and no frontier cell is in the region
+    if (rg.bounded && (level & 7u) == 0) {  // stop once no cell of the box is open and no frontier cell is in the region
       int open = 0;
       for (uint32_t i = tid; i < rg_words; i += blockDim.x) {
-        const uint32_t rr = i / rg_nw, ww = i - rr * rg_nw, wi = rg_w0 + ww, w = ((uint32_t)gy0 + rr) * W + wi;
-        const int c_lo = max(gx0 - (int)(wi * 32), 0), c_hi = min(gx1 - (int)(wi * 32), 31);
-        const uint32_t cm = (0xFFFFFFFFu >> (31 - c_hi)) & (0xFFFFFFFFu << c_lo);
-        const uint32_t cw = care_ok ? (ww < (uint32_t)kCareWords ? care[rr * kCareWords + ww] : 0u) : 0xFFFFFFFFu;
-        if ((((~vis[w] & fre[w] & cw) | cur[w]) & cm) != 0) open = 1;
+        const uint32_t rr = i / rg_nw, ww = i - rr * rg_nw, wi = (uint32_t)rg.w0 + ww, w = ((uint32_t)rg.y0 + rr) * W + wi;
+        const uint32_t cw = rg.care_ok ? (ww < (uint32_t)kCareWords ? care[rr * kCareWords + ww] : 0u) : 0xFFFFFFFFu;
+        if ((((~vis[w] & fre[w] & cw) | cur[w]) & bfsColMask(rg.x0, rg.x1, (int)wi)) != 0) open = 1;
       }
       if (!__syncthreads_or(open)) break;
     }
   }
   if (tid == 0 && pl.bfs_grids == 3) pl.bfs_levels[(size_t)inst * 3 + which] = level;
   // (a bounded search is only ever read inside its region: the rest of the grid is left as it is)
-  for (uint32_t i = tid; i < (bounded ? rg_words : words); i += blockDim.x) {
-    const uint32_t w = bounded ? ((uint32_t)gy0 + i / rg_nw) * W + rg_w0 + (i - (i / rg_nw) * rg_nw) : i;
-    uint32_t t = ~vis[w];
-    if (t) {
-      const uint32_t row = w / W, wi = w - row * W;
-      uint32_t* drow = dist + row * nx + wi * 32;
-      while (t) {
-        const int bpos = __ffs(t) - 1;
-        t &= t - 1;
-        drow[bpos] = N_unreach;
-      }
-    }
+  for (uint32_t i = tid; i < rg_words; i += blockDim.x) {
+    const uint32_t rr = i / rg_nw, row = (uint32_t)rg.y0 + rr, wi = (uint32_t)rg.w0 + (i - rr * rg_nw);
+    bfsStoreCells(dist + row * nx + wi * 32, ~vis[row * W + wi], N_unreach, false);
   }
 }
 // per-instance scratch words of the wavefront launches: none for maps the one-row-per-lane sweep takes, else twelve bitmaps

@@ -2,7 +2,7 @@
 // k_bfs_rows2 (two rows per lane, up to 1024 x 1344).  MapGridCostFunction::prepare (map_grid_cost_function.cpp:59-68) =
 //   MapGrid::resetPathDist + adjustPlanResolution (map_grid.cpp:135-171) + setTargetCells (:174-213) | setLocalGoal
 //   (:216-258) + computeTargetDistance (:262-310) with updatePathCell (:103-122).
-#include "planner_common.h"
+#include "planner_bfs_common.h"
 
 namespace navgpu {
 
@@ -91,84 +91,21 @@ __device__ __forceinline__ void rowsGroup4(const int g, const uint32_t aw, uint3
       : "scc");
 #undef NAVGPU_ROWS_DPP
 }
-// The seed cells of wavefront `which` of robot `inst`, from its plan (as bfsWaveGrid; map_grid.cpp:160-187, 190-233): every
-// lane of the workgroup takes a slice of the plan, `set(mx, my)` is called once per seed cell.
-template <typename Set>
-__device__ __forceinline__ void rowsPlanSeeds(const PlannerDev& pl, const uint32_t inst, const int which, const Geom& g, const uint8_t* master,
-                                              const uint32_t nx, const uint32_t tid, uint32_t* s_wave, Set&& set) {
-  const uint32_t n = pl.plan_count[inst];
-  const double* P = pl.plan + (size_t)inst * pl.max_plan * 2;
-  const bool ovr = which == 2;
-  const double lx = pl.front_last[2 * inst], ly = pl.front_last[2 * inst + 1];
-  const uint32_t chunk = (n + blockDim.x - 1) / blockDim.x;
-  const uint32_t i0 = min(n, tid * chunk), i1 = min(n, i0 + chunk);
-  uint32_t mine = 0;
-  for (uint32_t i = i0; i < i1; ++i) mine += adjustedPoints(P, i, lx, ly, ovr, n, g.res, true, [](uint32_t, double, double) {});
-  uint32_t total;
-  const uint32_t base = blockExclusiveScan1024(mine, s_wave, &total);
-  auto valid = [&](double x, double y, uint32_t& cell) {
-    uint32_t mx, my;
-    if (!worldToMap(g, x, y, mx, my)) return false;
-    cell = my * nx + mx;
-    return master[cell] != kNoInfo;
-  };
-  uint32_t fmin_ = 0xFFFFFFFFu, b = base;
-  for (uint32_t i = i0; i < i1; ++i)
-    b += adjustedPoints(P, i, lx, ly, ovr, n, g.res, false, [&](uint32_t k, double x, double y) {
-      uint32_t cell;
-      if (valid(x, y, cell)) fmin_ = min(fmin_, b + k);
-    });
-  const uint32_t f = blockMin1024(fmin_, s_wave);
-  if (f == 0xFFFFFFFFu) return;  // (uniform over the workgroup)
-  uint32_t emin = total;
-  b = base;
-  for (uint32_t i = i0; i < i1; ++i)
-    b += adjustedPoints(P, i, lx, ly, ovr, n, g.res, false, [&](uint32_t k, double x, double y) {
-      uint32_t cell;
-      if (b + k > f && !valid(x, y, cell)) emin = min(emin, b + k);
-    });
-  const uint32_t e = blockMin1024(emin, s_wave);
-  b = base;
-  for (uint32_t i = i0; i < i1; ++i)
-    b += adjustedPoints(P, i, lx, ly, ovr, n, g.res, false, [&](uint32_t k, double x, double y) {
-      const uint32_t idx = b + k;
-      const bool seed = (which == 0) ? (idx >= f && idx < e) : (idx == e - 1);
-      if (!seed) return;
-      uint32_t cell;
-      if (!valid(x, y, cell)) return;
-      const uint32_t my = cell / nx;
-      set(cell - my * nx, my);
-    });
-}
 template <int W>
 __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t inst, const int which, const uint32_t item) {
   constexpr int NG = (W + 3) / 4;         // groups of four words
   constexpr int WP = NG * 4;              // words kept per row: W rounded up (the extra ones are blocked everywhere)
   constexpr int D = kRowsHalo;
-  int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1, care_ok = 0;  // the robot's region (box + 2 cells) and whether its pockets are known
-  if (pl.bfs_bounded) {
-    const int4 bb = reinterpret_cast<const int4*>(pl.bfs_box)[2 * inst];
-    bx0 = __builtin_amdgcn_readfirstlane(bb.x);
-    bx1 = __builtin_amdgcn_readfirstlane(bb.y);
-    by0 = __builtin_amdgcn_readfirstlane(bb.z);
-    by1 = __builtin_amdgcn_readfirstlane(bb.w);
-    care_ok = __builtin_amdgcn_readfirstlane(pl.bfs_box[8 * inst + 4]);
-  }
-  if (!(bx1 >= bx0 && by1 >= by0)) {  // (uniform over the workgroup) a whole-grid search: the region is the map, nothing is ever "settled"
-    bx0 = 0;
-    by0 = 0;
-    bx1 = (int)pl.nx - 1;
-    by1 = (int)pl.ny - 1;
-    care_ok = 0;
-  }
+  const BfsRegion rg = bfsRegion(pl, inst);
+  const int bx0 = rg.x0, bx1 = rg.x1, by0 = rg.y0, by1 = rg.y1, care_ok = rg.care_ok;  // (box + 2 cells; are its pockets known)
   extern __shared__ __align__(16) uint32_t sm[];
   __shared__ uint32_t s_wave[16];
   __shared__ uint32_t s_flag[3];  // rotating by exchange: something new was reached since the last one
   __shared__ uint32_t s_open[3];  //                       something of the robot's box is still open
   uint32_t tid_ = threadIdx.x, nx_ = pl.nx, ny_ = pl.ny;
-  asm volatile("" : "+v"(tid_), "+s"(nx_), "+s"(ny_));  // opaque per item, as in bfsWaveGrid
+  asm volatile("" : "+v"(tid_), "+s"(nx_), "+s"(ny_));  // opaque per item (nothing worked out from them is carried from one search of the item loop to the next)
   const uint32_t tid = tid_;
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8] = wall_clock64();
+  bfsStamp(pl, tid, item, 0);
   const Geom g = geomOf(pl, inst);
   const uint32_t nx = nx_, ny = ny_, Wr = (nx + 31) >> 5;  // Wr <= W words really exist
   const uint32_t nw = blockDim.x >> 6;
@@ -195,17 +132,17 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   for (uint32_t i = tid; i < seed_words + kCareRows * kCareWords + edge_words; i += blockDim.x) sm[i] = 0;
   if (tid < 3) s_flag[tid] = s_open[tid] = 0;
   __syncthreads();
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 4] = wall_clock64();
+  bfsStamp(pl, tid, item, 4);
   if (care_ok) {  // the pocket mask of the robot's box: by region row, four words from the region's first (k_samples)
     const uint32_t* care = pl.bfs_care + (size_t)inst * kCareRows * kCareWords;
     for (uint32_t i = tid; i < (uint32_t)(kCareRows * kCareWords); i += blockDim.x) care_l[i] = care[i];
   }
   // --- seeds from the plan
-  rowsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
+  bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
     atomicOr(&seedm[my * Wr + (mx >> 5)], 1u << (mx & 31));  // a few hundred seeds, once
   });
   __syncthreads();
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 5] = wall_clock64();
+  bfsStamp(pl, tid, item, 5);
 
   uint32_t blocked[WP], fr[WP];
 #pragma unroll
@@ -220,31 +157,10 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   // the region in this lane's terms
   const bool wave_in_box = (int)(wave_id * kRowsPerWave) <= by1 && (int)((wave_id + 1) * kRowsPerWave) > by0;  // wave-uniform
   const bool row_in_box = owner && row_i >= by0 && row_i <= by1;
-  const int w0 = bx0 >> 5, w1 = bx1 >> 5;
-  uint32_t region_groups = 0;  // groups that hold words of the region
-  for (int jr = w0; jr <= w1; ++jr) region_groups |= 1u << (jr >> 2);
+  const int w0 = rg.w0, w1 = rg.w1;
+  const uint32_t region_groups = bfsRegionGroups(rg);
   uint32_t* drow = dist + (size_t)row * nx;
-  // distances of the cells `cells` of word j of this lane's row.  Two plain bit loops (every lane runs the longest one, so
-  // their bodies are kept to a find-first-bit, an address and a store): whole aligned groups of four first - fronts that
-  // run along a row reach 32 cells of a word at once - then what is left, cell by cell
-  auto storeCells = [&](int j, uint32_t cells, uint32_t value) {
-    uint32_t* dw = drow + j * 32;
-    if (aligned4) {
-      uint32_t full = cells & (cells >> 1) & (cells >> 2) & (cells >> 3) & 0x11111111u;
-      cells &= ~(full * 15u);
-      const uint4 v4 = make_uint4(value, value, value, value);
-      while (full) {
-        const uint32_t bpos = (uint32_t)__ffs(full) - 1u;
-        *reinterpret_cast<uint4*>(dw + bpos) = v4;
-        full &= full - 1;
-      }
-    }
-    while (cells) {
-      const uint32_t bpos = (uint32_t)__ffs(cells) - 1u;
-      dw[bpos] = value;
-      cells &= cells - 1;
-    }
-  };
+  auto storeCells = [&](int j, uint32_t cells, uint32_t value) { bfsStoreCells(drow + j * 32, cells, value, aligned4); };
   // LDS offsets (words) of the 2 * WP-word row record this lane publishes / takes in at an exchange:
   //   own rows 0 .. D-1 (lanes D .. 2D-1) -> this wave's TOP record, read by the wave above into its lanes 64-D .. 63;
   //   own rows 50-D .. 49 (lanes 64-2D .. 63-D) -> BOTTOM record, read by the wave below into its lanes 0 .. D-1
@@ -275,7 +191,7 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   }
   uint32_t a_own = activity();
   uint32_t level = 0, xch = 0, any_blk = 0;
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 2] = wall_clock64();
+  bfsStamp(pl, tid, item, 2);
   bool done = false;
 #ifdef NAVGPU_BFS_STATS
   unsigned long long bst[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -390,7 +306,7 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   if (lane == 0)
     for (int k = 0; k < 9; ++k) atomicAdd(&g_bfs_stats[k], bst[k]);
 #endif
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 3] = wall_clock64();
+  bfsStamp(pl, tid, item, 3);
 
   // --- the rest of the region: obstacle cells an expanded cell touched -> obstacleCosts(), everything else that was not
   // reached -> unreachableCellCosts().  Expanded = reached free cells + seeds.  (The halo lanes next to the own rows are
@@ -430,11 +346,7 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
       }
     }
   }
-  if (pl.bfs_trace && tid == 0) {
-    pl.bfs_trace[(size_t)item * 8 + 6] = wall_clock64();
-    pl.bfs_trace[(size_t)item * 8 + 1] = wall_clock64() | ((unsigned long long)level << 48);
-  }
-  if (tid == 0 && pl.bfs_grids == 3) pl.bfs_levels[(size_t)inst * 3 + which] = level;  // next cycle's dispatch order
+  bfsFinish(pl, tid, inst, which, item, level);
 }
 template <int W>
 __global__ __launch_bounds__(1024, 6) void k_bfs_rows(PlannerDev pl, uint32_t first, uint32_t count, uint32_t* next_item, const uint32_t* order) {
@@ -591,30 +503,16 @@ __device__ __forceinline__ void rows2Level(const uint32_t aw, uint32_t& nz, uint
 }
 __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_t inst, const int which, const uint32_t item, uint32_t* seedw) {
   constexpr int W = kRows2Words, NG = W / 4, D = kRows2Levels, HL = kRows2HaloLanes;
-  int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1, care_ok = 0;  // the robot's region (box + 2 cells) and whether its pockets are known
-  if (pl.bfs_bounded) {
-    const int4 bb = reinterpret_cast<const int4*>(pl.bfs_box)[2 * inst];
-    bx0 = __builtin_amdgcn_readfirstlane(bb.x);
-    bx1 = __builtin_amdgcn_readfirstlane(bb.y);
-    by0 = __builtin_amdgcn_readfirstlane(bb.z);
-    by1 = __builtin_amdgcn_readfirstlane(bb.w);
-    care_ok = __builtin_amdgcn_readfirstlane(pl.bfs_box[8 * inst + 4]);
-  }
-  if (!(bx1 >= bx0 && by1 >= by0)) {  // (uniform over the workgroup) a whole-grid search: the region is the map
-    bx0 = 0;
-    by0 = 0;
-    bx1 = (int)pl.nx - 1;
-    by1 = (int)pl.ny - 1;
-    care_ok = 0;
-  }
+  const BfsRegion rg = bfsRegion(pl, inst);
+  const int bx0 = rg.x0, bx1 = rg.x1, by0 = rg.y0, by1 = rg.y1, care_ok = rg.care_ok;  // (box + 2 cells; are its pockets known)
   extern __shared__ __align__(16) uint32_t sm[];
   __shared__ uint32_t s_wave[16];
   __shared__ uint32_t s_flag[3];
   __shared__ uint32_t s_open[3];
   uint32_t tid_ = threadIdx.x, nx_ = pl.nx, ny_ = pl.ny;
-  asm volatile("" : "+v"(tid_), "+s"(nx_), "+s"(ny_));  // opaque per item, as in bfsWaveGrid
+  asm volatile("" : "+v"(tid_), "+s"(nx_), "+s"(ny_));  // opaque per item (nothing worked out from them is carried from one search of the item loop to the next)
   const uint32_t tid = tid_;
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8] = wall_clock64();
+  bfsStamp(pl, tid, item, 0);
   const Geom g = geomOf(pl, inst);
   const uint32_t nx = nx_, ny = ny_, Wr = (nx + 31) >> 5;  // Wr <= 32 words really exist
   const uint32_t nw = blockDim.x >> 6;
@@ -639,16 +537,16 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   for (uint32_t i = tid; i < ny * Wr; i += blockDim.x) seedw[i] = 0;
   if (tid < 3) s_flag[tid] = s_open[tid] = 0;
   __syncthreads();
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 4] = wall_clock64();
+  bfsStamp(pl, tid, item, 4);
   if (care_ok) {  // the pocket mask of the robot's box: by region row, four words from the region's first (k_samples)
     const uint32_t* care = pl.bfs_care + (size_t)inst * kCareRows * kCareWords;
     for (uint32_t i = tid; i < (uint32_t)(kCareRows * kCareWords); i += blockDim.x) care_l[i] = care[i];
   }
-  rowsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
+  bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
     atomicOr(&seedw[my * Wr + (mx >> 5)], 1u << (mx & 31));
   });
   __syncthreads();
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 5] = wall_clock64();
+  bfsStamp(pl, tid, item, 5);
   // The seed words were zeroed and set by other lanes of this workgroup and read by an earlier item: drop this CU's stale L1
   // lines, then plain loads see what the atomics left in L2.
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -693,26 +591,10 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   }
   const bool wave_in_box = (int)(wave_id * kRows2PerWave) <= by1 && (int)((wave_id + 1) * kRows2PerWave) > by0;  // wave-uniform
   const bool inA = ownerA && rowA_i >= by0 && rowA_i <= by1, inB = ownerB && rowB_i >= by0 && rowB_i <= by1;
-  const int w0 = bx0 >> 5, w1 = bx1 >> 5;
-  uint32_t region_groups = 0;
-  for (int jr = w0; jr <= w1; ++jr) region_groups |= 1u << (jr >> 2);
-  auto storeCells = [&](const uint32_t row, int j, uint32_t cells, uint32_t value) {  // as bfsRowsGrid's (the row's address is worked out here: registers)
-    uint32_t* dw = dist + (size_t)row * nx + j * 32;
-    if (aligned4) {
-      uint32_t full = cells & (cells >> 1) & (cells >> 2) & (cells >> 3) & 0x11111111u;
-      cells &= ~(full * 15u);
-      const uint4 v4 = make_uint4(value, value, value, value);
-      while (full) {
-        const uint32_t bpos = (uint32_t)__ffs(full) - 1u;
-        *reinterpret_cast<uint4*>(dw + bpos) = v4;
-        full &= full - 1;
-      }
-    }
-    while (cells) {
-      const uint32_t bpos = (uint32_t)__ffs(cells) - 1u;
-      dw[bpos] = value;
-      cells &= cells - 1;
-    }
+  const int w0 = rg.w0, w1 = rg.w1;
+  const uint32_t region_groups = bfsRegionGroups(rg);
+  auto storeCells = [&](const uint32_t row, int j, uint32_t cells, uint32_t value) {  // (the row's address is worked out here: registers)
+    bfsStoreCells(dist + (size_t)row * nx + j * 32, cells, value, aligned4);
   };
   // LDS offsets (words) of the 4 * W-word record (both rows) this lane publishes / takes in at an exchange:
   //   lanes HL .. 2 HL - 1 -> this wave's TOP record, read by the wave above into its lanes 64 - HL .. 63;
@@ -746,7 +628,7 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   }
   uint32_t a_own = activity();
   uint32_t level = 0, xch = 0, any_blk = 0;
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 2] = wall_clock64();
+  bfsStamp(pl, tid, item, 2);
   bool done = false;
 #ifdef NAVGPU_BFS_STATS
   unsigned long long bst[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -819,8 +701,7 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
       for (int j = 0; j < W; ++j) {
         if (j >= w0 && j <= w1) {  // wave-uniform
           const uint32_t cw_i = (uint32_t)(j - w0);
-          const int c_lo = max(bx0 - j * 32, 0), c_hi = min(bx1 - j * 32, 31);
-          const uint32_t cm = c_hi >= c_lo ? ((0xFFFFFFFFu >> (31 - c_hi)) & (0xFFFFFFFFu << c_lo)) : 0u;
+          const uint32_t cm = bfsColMask(bx0, bx1, j);
           if (inA) {
             const uint32_t care = (care_ok != 0 && cw_i < (uint32_t)kCareWords && rrA < (uint32_t)kCareRows) ? care_l[rrA * kCareWords + cw_i] : (care_ok ? 0u : 0xFFFFFFFFu);
             open_any |= ((~blA[j] & care) | frA[j]) & cm;
@@ -867,7 +748,7 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   if (lane == 0)
     for (int k = 0; k < 9; ++k) atomicAdd(&g_bfs_stats[k], bst[k]);
 #endif
-  if (pl.bfs_trace && tid == 0) pl.bfs_trace[(size_t)item * 8 + 3] = wall_clock64();
+  bfsStamp(pl, tid, item, 3);
 
   // --- the rest of the region: obstacle cells an expanded cell touched -> obstacleCosts(), everything else that was not
   // reached -> unreachableCellCosts().  Expanded = reached free cells + seeds.  (The own rows have moved on since the last
@@ -933,11 +814,7 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
       }
     }
   }
-  if (pl.bfs_trace && tid == 0) {
-    pl.bfs_trace[(size_t)item * 8 + 6] = wall_clock64();
-    pl.bfs_trace[(size_t)item * 8 + 1] = wall_clock64() | ((unsigned long long)level << 48);
-  }
-  if (tid == 0 && pl.bfs_grids == 3) pl.bfs_levels[(size_t)inst * 3 + which] = level;  // next cycle's dispatch order
+  bfsFinish(pl, tid, inst, which, item, level);
 }
 __global__ __launch_bounds__(768, 3) void k_bfs_rows2(PlannerDev pl, uint32_t first, uint32_t count, uint32_t* next_item, const uint32_t* order, uint32_t* scratch) {
   __shared__ uint32_t s_item;

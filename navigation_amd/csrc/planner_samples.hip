@@ -32,7 +32,7 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint
   if (blockIdx.x >= count) {
     const uint32_t robot = blockIdx.x - count, inst = first + robot;
     if (wv == 0) {
-      // dispatch order of this launch's wavefronts (k_bfs_wave takes items off a counter): longest first, predicted by
+      // dispatch order of this launch's wavefronts (the row sweeps take items off a counter): longest first, predicted by
       // the level count of the robot's previous cycle.  item = g * count + robot, g = 0 goal_front, 1 goal, 2 path;
       // every robot ranks its three items among all of them (count * 3 keys: a dozen loads per lane)
       const uint32_t total = 3 * count;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint
   }
   const uint32_t inst = first + blockIdx.x;
   const navgpu_robot_state st = pl.state[inst];
-  // Bounded wavefronts (k_bfs_wave).  The box = every cell a MapGrid look-up of this robot's samples can fall in: the
+  // Bounded wavefronts (bfsRegion, planner_bfs_common.h).  The box = every cell a MapGrid look-up of this robot's samples can fall in: the
   // staged reach around the robot's cell.  The region = the box grown by two cells, clipped to the map.  A search may
   // stop when (a) no cell of the box that it could still reach is open and (b) no frontier cell is inside the region.
   // "Could still reach" leaves out the POCKETS: free cells that no 4-connected chain of free cells joins to the rim of

@@ -1069,7 +1069,7 @@ def test_trajectory_planner_cycles(nav, orc, holonomic, dwa):
 
 
 def test_trajectory_planner_edge_cases(nav, orc):
-    """Other wavefront kernels (600x600 -> k_bfs<12>, 1000x1000 -> k_bfs_global) with within_robot, a circular
+    """Other wavefront kernels (600x600 -> k_bfs_rows<20>, 1000x1000 -> k_bfs_rows2) with within_robot, a circular
     (2-vertex) footprint, an empty plan, a robot next to the map border, unsupported options."""
     from navigation_amd import synth
     N = L(nav)
@@ -1115,7 +1115,7 @@ def test_trajectory_planner_edge_cases(nav, orc):
 
 def test_mapgrid_fleet_soak(nav, orc):
     """Many wavefront workgroups in flight at once (384 per launch, more than the chip has CUs), several cycles with moving robots: every
-    grid against the oracle.  Guards the barrier-less neighbour-wave synchronisation of k_bfs_wave under load."""
+    grid against the oracle.  Guards the exchange between neighbouring waves of k_bfs_rows (400 x 400: k_bfs_rows<13>) under load."""
     from navigation_amd import synth
     N = L(nav)
     n, n_inst, cycles = 400, 128, 5
@@ -1321,7 +1321,7 @@ def test_bounded_map_grids_reconfigure_between_stage_and_cycle(nav, orc):
     fl.close()
 
 
-@pytest.mark.parametrize("sizes,rounds", [((160, 250, 400), 40), ((600,), 3), ((800,), 3)])  # k_bfs_wave<7>, <13>, k_bfs_global
+@pytest.mark.parametrize("sizes,rounds", [((160, 250, 400), 40), ((600,), 3), ((800,), 3)])  # k_bfs_rows<7>, <13>; <20>; k_bfs_rows2
 def test_bounded_map_grids_random_stress(nav, orc, sizes, rounds):
     """Seeded random clutter, poses, velocities, limits and plans (some through obstacles, some ending near the robot): the
     bounded and the whole-grid searches must give every sample the same cost, and the completed grids must be equal."""
@@ -1388,3 +1388,118 @@ def test_bounded_map_grids_random_stress(nav, orc, sizes, rounds):
         total += out[1][3].size
         fl.close()
     assert shorter > total // 3, (shorter, total)  # the comparison is not vacuous: many of the searches did stop early
+
+
+# ---- every wavefront kernel on the smallest maps that select it.  The kernel follows from the words of a row and the wave
+# count, not from the area: up to 640 cells across k_bfs_rows (<20> from 417), 641 .. 1024 k_bfs_rows2, beyond k_bfs_global
+def _walled_map(nx, ny, seam_rows, rs):
+    """Random blobs, a wall with gaps on each of `seam_rows` (the rows either side of two waves' blocks) and a two-cell wall
+    with gaps across a word boundary of the bitmaps (cells 319 | 320)."""
+    m = np.zeros((ny, nx), np.uint8)
+    for _ in range(nx * ny // 900):
+        cx, cy, r = rs.randint(0, nx), rs.randint(0, ny), rs.randint(1, 4)
+        m[max(0, cy - r):cy + r + 1, max(0, cx - r):cx + r + 1] = LETHAL
+    m[rs.random_sample(m.shape) < 0.01] = NOINFO
+    m[:, 319:321] = LETHAL
+    m[3::7, 319:321] = 0
+    for k, row in enumerate(seam_rows):
+        m[row, :] = LETHAL
+        for x0 in range(5 + 31 * k, nx, 97 - 36 * k):  # (gaps of the two rows coincide in places and lie on word boundaries in others)
+            m[row, x0:x0 + 2] = 0
+        m[row, 31:33] = 0
+    return m
+
+
+@pytest.mark.parametrize("nx,ny,seam_rows", [(672, 49, ()), (1024, 113, (111, 112)), (640, 51, (49, 50))])
+def test_row_sweeps_smallest_maps(nav, orc, nx, ny, seam_rows):
+    """k_bfs_rows2 at 672 x 49 (21 words: rows are no whole 16-byte units, so the word-by-word row loads; an odd row count; one
+    wave) and at 1024 x 113 (two waves of 112 rows: one exchange seam, rows 111 | 112); k_bfs_rows<20> at 640 x 51 (two waves of
+    50 rows, seam 49 | 50).  All three grids against the oracle, bounded search and completion both (_mapgrid_case)."""
+    from navigation_amd import synth
+    res = synth.RES
+    m = _walled_map(nx, ny, seam_rows, np.random.RandomState(nx + ny))
+    sx, sy = nx * res, ny * res
+    plan = np.stack([np.linspace(0.1 * sx, 0.9 * sx, 60), np.linspace(0.2 * sy, 0.95 * sy, 60)], 1)
+    for px, py in plan:  # keep the plan itself traversable
+        m[int(py / res), int(px / res)] = 0
+    _mapgrid_case(nav, orc, m, plan, [0.5 * sx, 0.5 * sy, 0.3])
+
+
+def test_bfs_global_bounded_equals_complete(nav, orc):
+    """k_bfs_global (1056 cells across: 33 words) with its bounded stop rule against its complete search: one robot in the
+    middle, a plan across the right half, and inside the robot's box an enclosed ring off the plan, one on it and a one-cell
+    pocket (as test_bounded_map_grids_pockets).  A download completes a bounded grid, so what the bounded search left inside
+    the box is checked through its readers: every sample's cost and status, which come from look-ups inside the box only,
+    against the complete run and against the oracle; the completed grids against both as well."""
+    from navigation_amd import synth
+    N = L(nav)
+    nx, ny, rx, ry = 1056, 64, 528, 32
+    res = synth.RES
+    m = np.zeros((ny, nx), np.uint8)
+    for cx, cy in ((rx + 12, ry + 12), (rx + 22, ry)):
+        m[cy - 4:cy + 5, cx - 4:cx + 5] = LETHAL
+        m[cy - 2:cy + 3, cx - 2:cx + 3] = 0
+    m[ry - 3:ry, rx + 3:rx + 6] = INSCRIBED
+    m[ry - 2, rx + 4] = 0
+    m[10:64, 800] = LETHAL  # the goal wavefront comes round this wall
+    cfg = nav.DwaConfig(vx_samples=9, vy_samples=7, vth_samples=9, sim_time=1.7, sim_granularity=0.085, discretize_by_time=1, max_vel_y=0.3, min_vel_y=-0.3)
+    plan = np.stack([(rx + 0.5) * res + 0.04 * np.arange(600), np.full(600, (ry + 0.5) * res)], 1)
+    pos, vel = [(rx + 0.5) * res, (ry + 0.5) * res, 0.2], [0.3, 0.0, 0.1]
+    out = {}
+    for bounded in (1, 0):
+        fl = nav.Fleet(1, nx, ny, res, layers=N.LAYER_OBSTACLE, keep_sample_costs=True, max_sim_steps=64, max_plan=640)
+        fl.configure_planner(cfg)
+        fl.set_footprint(synth.FOOTPRINT)
+        fl.set_bounded_map_grids(bounded)
+        fl.upload(N.GRID_MASTER, m)
+        fl.set_plan()
+        r = fl.find_best_path([pos], [vel], [plan])[0]
+        lv = np.asarray(fl.wavefront_levels()).reshape(-1)[:3].copy()
+        cost, status, _ = fl.samples(0)
+        grids = [fl.download(g, 0, 1)[0].copy() for g in (N.GRID_PATH, N.GRID_GOAL, N.GRID_GOAL_FRONT)]  # completes the bounded ones
+        out[bounded] = (r, lv, cost.copy(), status.copy(), grids)
+        fl.close()
+    (rb, lb, cb, sb, gb), (rc, lc, cc, sc, gc) = out[1], out[0]
+    print("wavefront levels bounded", lb, "complete", lc)
+    assert (rb.best_index, rb.n_valid, rb.n_scored, rb.cost) == (rc.best_index, rc.n_valid, rc.n_scored, rc.cost)
+    assert np.array_equal(cb, cc) and np.array_equal(sb, sc)
+    for a, b in zip(gb, gc):
+        assert np.array_equal(a, b)
+    assert (lb <= lc).all() and (lb < lc).any(), (lb, lc)
+    p = orc.DwaPlanner(m, res, 0.0, 0.0, orc.DwaConfig(**cfg.as_dict()))
+    p.set_plan()
+    o, _, _, cfull, ost = p.cycle(np.asarray(pos, np.float32), np.asarray(vel, np.float32), plan, synth.FOOTPRINT)
+    scored = ost == 1
+    assert np.array_equal(sb, ost) and rb.best_index == o.best_index
+    assert np.array_equal(cb[scored] < 0, cfull[scored] < 0)
+    assert np.allclose(cb[scored][cfull[scored] >= 0], cfull[scored][cfull[scored] >= 0], rtol=0, atol=1e-5)
+    for which in range(3):
+        assert np.array_equal(gb[which].astype(np.float64).reshape(-1), np.asarray(p.grid(which)).reshape(-1)), which
+
+
+def test_bfs_global_legacy_two_grids(nav, orc):
+    """k_bfs_global in the legacy planner's two-grid launch (bfs_grids = 2, path_map_ with the within_robot bits) at 1056 x 64:
+    a lethal block under the robot, which the path wavefront passes through and the goal wavefront does not."""
+    from navigation_amd import synth
+    N = L(nav)
+    nx, ny, rx, ry = 1056, 64, 528, 32
+    res = synth.RES
+    rs = np.random.RandomState(3)
+    m = np.zeros((ny, nx), np.uint8)
+    for _ in range(60):
+        cx, cy, r = rs.randint(0, nx), rs.randint(0, ny), rs.randint(1, 4)
+        if abs(cy - ry) > 8:
+            m[max(0, cy - r):cy + r + 1, max(0, cx - r):cx + r + 1] = LETHAL
+    m[ry - 2:ry + 3, rx - 2:rx + 3] = LETHAL  # an obstacle under the robot: within_robot lets the wavefront through
+    cfg = N.TpConfig(vx_samples=4, vtheta_samples=5, sim_time=1.0, sim_granularity=0.05, angular_sim_granularity=0.05)
+    fl = nav.Fleet(1, nx, ny, res, layers=N.LAYER_OBSTACLE, max_sim_steps=64, max_plan=256, max_footprint=16)
+    fl.set_footprint(synth.FOOTPRINT)
+    fl.upload(N.GRID_MASTER, m)
+    fl.configure_trajectory_planner(cfg)
+    o = orc.TrajectoryPlanner(m, res, cfg, synth.FOOTPRINT)
+    plan = np.stack([(rx + 0.5) * res + 0.1 * np.arange(200), np.full(200, (ry + 0.5) * res)], 1)
+    fl.tp_update_plan(0, plan)
+    o.update_plan(plan)
+    pos = np.array([[(rx + 0.5) * res, (ry + 0.5) * res, 0.7]], np.float32)
+    _tp_compare_cycle(fl, N, [o], pos, np.zeros((1, 3), np.float32))
+    fl.close()

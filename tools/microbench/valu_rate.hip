@@ -1,5 +1,5 @@
 // Micro-benchmark: VALU issue rate per SIMD on gfx950 as a function of waves per SIMD and instruction kind,
-// to price "VALU-bound" kernels (k_score, k_bfs_wave) against a measured instruction roofline.
+// to price "VALU-bound" kernels (k_score_sweep, k_bfs_rows) against a measured instruction roofline.
 //   hipcc --offload-arch=gfx950 -O3 valu_rate.hip -o valu_rate && ./valu_rate
 // One workgroup per CU, W waves per SIMD (threads = 256 * W); every wave runs N independent instructions of one kind
 // on 8 private registers; cycles per instruction per SIMD = elapsed / (N * W).

@@ -1,4 +1,4 @@
-"""TEMP: per-workgroup start/end of k_bfs_wave in the bench fleet"""
+"""TEMP: per-workgroup start/end of the row sweeps (k_bfs_rows, k_bfs_rows2) in the bench fleet"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
