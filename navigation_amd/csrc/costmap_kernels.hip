@@ -228,13 +228,37 @@ __device__ __forceinline__ uint32_t cellDistance(double world_dist, double res) 
 // VoxelGrid::bitsBelowThreshold (voxel_grid.h:151-164) == popcount(n) <= thr
 __device__ __forceinline__ bool bitsBelowThreshold(uint32_t n, uint32_t thr) { return (uint32_t)__popc(n) <= thr; }
 
+// A world-frame box that only grows.  Its lower corner grows in two spellings, as the reference's std::min calls come in two
+// argument orders; they differ for NaN and for -0.0 against 0.0, and every call site keeps the one it has always had:
+//   touch   : min = (min < x) ? min : x   CostmapLayer::touch (costmap_layer.cpp:6-12): ray ends, marked points, the footprint
+//   include : min = (x < min) ? x : min   StaticLayer::updateBounds (static_layer.cpp:277-282), add / useExtraBounds (costmap_layer.cpp:23-26,
+//             :51-54), InflationLayer::updateBounds (inflation_layer.cpp:153-156, the cycle's box INTO last cycle's), the workgroup reduction
+// The upper corner is max = (max < x) ? x : max in both.
 struct BoundsAcc {
   double min_x, min_y, max_x, max_y;
-  __device__ __forceinline__ void touch(double x, double y) {  // CostmapLayer::touch: std::min(x, *min_x) ...
+  __device__ __forceinline__ void touch(double x, double y) {
     min_x = (min_x < x) ? min_x : x;
     min_y = (min_y < y) ? min_y : y;
     max_x = (max_x < x) ? x : max_x;
     max_y = (max_y < y) ? y : max_y;
+  }
+  __device__ __forceinline__ void include(double x0, double y0, double x1, double y1) {
+    min_x = (x0 < min_x) ? x0 : min_x;
+    min_y = (y0 < min_y) ? y0 : min_y;
+    max_x = (max_x < x1) ? x1 : max_x;
+    max_y = (max_y < y1) ? y1 : max_y;
+  }
+  __device__ __forceinline__ void load(const double* p) {  // min_x, min_y, max_x, max_y
+    min_x = p[0];
+    min_y = p[1];
+    max_x = p[2];
+    max_y = p[3];
+  }
+  __device__ __forceinline__ void store(double* p) const {
+    p[0] = min_x;
+    p[1] = min_y;
+    p[2] = max_x;
+    p[3] = max_y;
   }
 };
 
@@ -253,376 +277,389 @@ __device__ __forceinline__ void enforceBounds(const Geom& g, double wx, double w
     my = (int)((wy - g.oy) / g.res);
 }
 
+// ---- the stages of k_obstacle, in the order the kernel runs them ----
+struct ObstacleGrids {  // the obstacle / voxel layer of one robot
+  Geom g;
+  uint8_t* layer;                          // its 2-D grid
+  uint32_t* vox;                           // its columns (voxel layer), else null
+  uint32_t size_z, unknown_thr, mark_thr;  // voxel layer: min(z_voxels, 16), voxel_layer.cpp:89, mark_threshold; else 0
+};
+
+// boundsSeed (thread 0): what the box holds before any observation - the caller's bounds when it passes them ([robot of the launch][4]),
+// StaticLayer::updateBounds (static_layer.cpp:263-283) and useExtraBounds (obstacle_layer.cpp:347, voxel_layer.cpp:123; costmap_layer.cpp:46-60)
+__device__ __forceinline__ void boundsSeed(const CostmapDev& cm, const Geom& g, InstCostmapState* st, const double* bounds_in, int only_bounds,
+                                           bool has_obs_layer, BoundsAcc& b) {
+  if (bounds_in) b.load(bounds_in + 4 * blockIdx.x);
+  if (!only_bounds && (cm.layers & NAVGPU_LAYER_STATIC) && st->static_has_updated_data) {
+    // mapToWorld(x_, y_) and (x_+width_, y_+height_) with the whole map as the updated window
+    b.include(g.ox + (0 + 0.5) * g.res, g.oy + (0 + 0.5) * g.res, g.ox + (g.nx + 0.5) * g.res, g.oy + (g.ny + 0.5) * g.res);
+    st->static_has_updated_data = 0;
+  }
+  if (!only_bounds && cm.stat_roll) {
+    // rolling window: StaticLayer::updateBounds has no early return (static_layer.cpp:265-268) and adds the extent
+    // of the LAYER's grid - the static map's own geometry - every cycle
+    b.include(cm.stat_ox + (0 + 0.5) * cm.stat_res, cm.stat_oy + (0 + 0.5) * cm.stat_res, cm.stat_ox + (cm.stat_nx + 0.5) * cm.stat_res,
+              cm.stat_oy + (cm.stat_ny + 0.5) * cm.stat_res);
+  }
+  if (has_obs_layer && st->has_extra_bounds) {
+    b.include(st->extra[0], st->extra[1], st->extra[2], st->extra[3]);
+    st->extra[0] = st->extra[1] = 1e6;
+    st->extra[2] = st->extra[3] = -1e6;
+    st->has_extra_bounds = 0;
+  }
+}
+
+// ObstacleLayer::updateRaytraceBounds (obstacle_layer.cpp:602-610): the ray from (ox, oy) towards (wx, wy) touches the bounds
+// where it ends, at most `range` away
+__device__ __forceinline__ void rangeTouch(BoundsAcc& b, double ox, double oy, double wx, double wy, double range) {
+  double dx = wx - ox, dy = wy - oy;
+  double full = hyp2(dx, dy);
+  double scale = fmin(1.0, range / full);
+  b.touch(ox + dx * scale, oy + dy * scale);
+}
+
+// The clip of ObstacleLayer::raytraceFreespace (obstacle_layer.cpp:529-560): the ray from (ox, oy) to (wx, wy) is cut at the map's
+// edges, one after the other, each cut starting from the original direction.  (Its 3-D counterpart is voxelRayEnd, navgpu_device.h.)
+__device__ __forceinline__ void clipRay2D(const Geom& g, double map_end_x, double map_end_y, double ox, double oy, double& wx, double& wy) {
+  double a = wx - ox, bb = wy - oy;
+  if (wx < g.ox) {
+    double t = (g.ox - ox) / a;
+    wx = g.ox;
+    wy = oy + bb * t;
+  }
+  if (wy < g.oy) {
+    double t = (g.oy - oy) / bb;
+    wx = ox + a * t;
+    wy = g.oy;
+  }
+  if (wx > map_end_x) {
+    double t = (map_end_x - ox) / a;
+    wx = map_end_x - .001;
+    wy = oy + bb * t;
+  }
+  if (wy > map_end_y) {
+    double t = (map_end_y - oy) / bb;
+    wx = ox + a * t;
+    wy = map_end_y - .001;
+  }
+}
+
+// clearRays2D: ObstacleLayer::raytraceFreespace (obstacle_layer.cpp:498-576) for one clearing observation, a ray per lane
+__device__ __forceinline__ void clearRays2D(const ObstacleGrids& L, const ObsCsr& obs, const float* pts, uint32_t tid, BoundsAcc& b) {
+  const Geom& g = L.g;
+  uint32_t x0, y0;
+  if (!worldToMap(g, obs.ox, obs.oy, x0, y0)) return;  // sensor origin off the map (:506-513)
+  const double map_end_x = g.ox + g.nx * g.res, map_end_y = g.oy + g.ny * g.res;
+  if (tid == 0) b.touch(obs.ox, obs.oy);
+  const uint32_t cell_range = cellDistance(obs.raytrace_range, g.res);
+  for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
+    double wx = pts[3 * p], wy = pts[3 * p + 1];
+    clipRay2D(g, map_end_x, map_end_y, obs.ox, obs.oy, wx, wy);
+    uint32_t x1, y1;
+    if (!worldToMap(g, wx, wy, x1, y1)) continue;
+    raytrace2d(g.nx, x0, y0, x1, y1, cell_range, [&](uint32_t off) { L.layer[off] = kFree; });
+    rangeTouch(b, obs.ox, obs.oy, wx, wy, obs.raytrace_range);
+  }
+}
+
+// clearRaysVoxel: VoxelLayer::raytraceFreespace (voxel_layer.cpp:266-383) for one clearing observation; the sensor test and the clip are
+// voxelRayBegin / voxelRayEnd (navgpu_device.h).  Pass 0 clears the column bits of every ray and touches the bounds, pass 1 (after a
+// barrier) walks the same rays and sets the 2-D byte of each column from its final state (ClearVoxelInMap, voxel_grid.h:349).
+__device__ __forceinline__ void clearRaysVoxel(const CostmapDev& cm, const ObstacleGrids& L, const ObsCsr& obs, const float* pts, int pass,
+                                               uint32_t tid, BoundsAcc& b) {
+  const Geom& g = L.g;
+  VoxelRay ray;
+  if (!voxelRayBegin(g, cm, L.size_z, obs, ray)) return;
+  const uint32_t cell_range = cellDistance(obs.raytrace_range, g.res);
+  for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
+    double wpx, wpy, wpz, px, py, pz;
+    if (!voxelRayEnd(g, cm, L.size_z, ray, pts + 3 * p, wpx, wpy, wpz, px, py, pz)) continue;
+    // clearVoxelLineInMap's endpoint check (voxel_grid.cpp:131-136) is implied by the two tests above
+    if (pass == 0) {
+      raytrace3d(g.nx, ray.sensor_x, ray.sensor_y, ray.sensor_z, px, py, pz, cell_range,
+                 [&](uint32_t off, uint32_t zm) { atomicAnd(&L.vox[off], ~zm); });
+      rangeTouch(b, ray.ox, ray.oy, wpx, wpy, obs.raytrace_range);
+    } else {
+      raytrace3d(g.nx, ray.sensor_x, ray.sensor_y, ray.sensor_z, px, py, pz, cell_range, [&](uint32_t off, uint32_t) {
+        uint32_t col = L.vox[off];
+        uint32_t unknown_bits = (uint16_t)(col >> 16) ^ (uint16_t)col;
+        uint32_t marked_bits = col >> 16;
+        if (bitsBelowThreshold(marked_bits, L.mark_thr))
+          L.layer[off] = bitsBelowThreshold(unknown_bits, L.unknown_thr) ? kFree : kNoInfo;
+      });
+    }
+  }
+}
+
+// The height and range test every marking loop starts with (obstacle_layer.cpp:378-396, voxel_layer.cpp:155-165); the point as doubles
+__device__ __forceinline__ bool acceptMark(const CostmapDev& cm, const ObsCsr& obs, double sq_obstacle_range, const float* pt, double& px,
+                                           double& py, double& pz) {
+  px = pt[0];
+  py = pt[1];
+  pz = pt[2];
+  if (pz > cm.max_obstacle_height) return false;
+  double sq_dist = (px - obs.ox) * (px - obs.ox) + (py - obs.oy) * (py - obs.oy) + (pz - obs.oz) * (pz - obs.oz);
+  return !(sq_dist >= sq_obstacle_range);
+}
+// The column and the level an accepted point marks: the floor clamp of voxel_layer.cpp:169-173, VoxelLayer::worldToMap3D (voxel_layer.h:120-133,
+// against size_z_ as configured; the < 2^31 guards as in worldToMap) and VoxelGrid::markVoxelInMap's own bound (voxel_grid.h:102)
+__device__ __forceinline__ bool voxelCellOf(const CostmapDev& cm, const ObstacleGrids& L, double px, double py, double pz, uint32_t& cell,
+                                            uint32_t& mz) {
+  const Geom& g = L.g;
+  double wz = (pz < cm.origin_z) ? cm.origin_z : pz;
+  if (px < g.ox || py < g.oy || wz < cm.origin_z) return false;
+  double fxm = (px - g.ox) / g.res, fym = (py - g.oy) / g.res, fzm = (wz - cm.origin_z) / cm.z_resolution;
+  if (!(fxm < 2147483648.0) || !(fym < 2147483648.0) || !(fzm < 2147483648.0)) return false;
+  uint32_t mx = (uint32_t)(int)fxm, my = (uint32_t)(int)fym;
+  mz = (uint32_t)(int)fzm;
+  if (!(mx < g.nx && my < g.ny && mz < (uint32_t)cm.z_voxels)) return false;
+  if (mz >= L.size_z) return false;
+  cell = my * g.nx + mx;
+  return true;
+}
+
+// markPoints: the marking loop of ObstacleLayer::updateBounds (obstacle_layer.cpp:368-410) or VoxelLayer::updateBounds (voxel_layer.cpp:144-188)
+// for one marking observation, in one pass.  The voxel form is exact with mark_threshold == 0: every accepted point is marked whatever the order.
+template <bool VOXEL>
+__device__ __forceinline__ void markPoints(const CostmapDev& cm, const ObstacleGrids& L, const ObsCsr& obs, const float* pts, uint32_t tid,
+                                           BoundsAcc& b) {
+  const double sq_obstacle_range = obs.obstacle_range * obs.obstacle_range;
+  for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
+    double px, py, pz;
+    if (!acceptMark(cm, obs, sq_obstacle_range, pts + 3 * p, px, py, pz)) continue;
+    if (!VOXEL) {
+      uint32_t mx, my;
+      if (!worldToMap(L.g, px, py, mx, my)) continue;
+      L.layer[my * L.g.nx + mx] = kLethal;
+      b.touch(px, py);
+    } else {
+      uint32_t cell, mz;
+      if (!voxelCellOf(cm, L, px, py, pz, cell, mz)) continue;
+      uint32_t full_mask = ((uint32_t)1 << mz << 16) | (1u << mz);
+      uint32_t old = atomicOr(&L.vox[cell], full_mask);
+      uint32_t marked_bits = (old | full_mask) >> 16;
+      if (!bitsBelowThreshold(marked_bits, L.mark_thr)) {
+        L.layer[cell] = kLethal;
+        b.touch(px, py);
+      }
+    }
+  }
+}
+
+// markPointsOrdered: the voxel layer's marking loop over ALL marking observations, mark_threshold > 0.  VoxelGrid::markVoxelInMap reports
+// "marked" from the column's bit count AT THAT POINT of the sequential loop (voxel_grid.h:100-117), so which points touch the
+// bounds depends on the point order.  Exact two-step form: (1) every point records its cell, z and the column bits before any
+// marking; (2) a point is marked iff those bits, the bits of the EARLIER points of the same cell and its own exceed the threshold.
+__device__ __forceinline__ void markPointsOrdered(const CostmapDev& cm, const ObstacleGrids& L, uint32_t ob, uint32_t oe,
+                                                       const float* inst_points, uint2* seq, uint32_t tid, BoundsAcc& b) {
+  uint32_t n_seq = 0;
+  for (uint32_t o = ob; o < oe; ++o) n_seq = max(n_seq, cm.obs[o].first_point + cm.obs[o].n_points);
+  for (uint32_t s = tid; s < n_seq; s += blockDim.x) seq[s] = make_uint2(0u, 0u);
+  __syncthreads();
+  for (uint32_t o = ob; o < oe; ++o) {
+    const ObsCsr obs = cm.obs[o];
+    if (!(obs.flags & NAVGPU_OBS_MARKING)) continue;
+    const float* pts = inst_points + (size_t)obs.first_point * 3;
+    const double sq_obstacle_range = obs.obstacle_range * obs.obstacle_range;
+    for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
+      double px, py, pz;
+      if (!acceptMark(cm, obs, sq_obstacle_range, pts + 3 * p, px, py, pz)) continue;
+      uint32_t cell, mz;
+      if (!voxelCellOf(cm, L, px, py, pz, cell, mz)) continue;
+      seq[obs.first_point + p] = make_uint2(cell, 0x80000000u | ((L.vox[cell] >> 16) << 8) | mz);
+    }
+  }
+  __syncthreads();
+  for (uint32_t s = tid; s < n_seq; s += blockDim.x) {
+    const uint2 e = seq[s];
+    if (!(e.y & 0x80000000u)) continue;
+    const uint32_t mz = e.y & 0xFFu;
+    uint32_t acc = ((e.y >> 8) & 0xFFFFu) | (1u << mz);
+    for (uint32_t q = 0; q < s; ++q) {
+      const uint2 f = seq[q];
+      if ((f.y & 0x80000000u) && f.x == e.x) acc |= 1u << (f.y & 0xFFu);
+    }
+    atomicOr(&L.vox[e.x], ((uint32_t)1 << mz << 16) | (1u << mz));
+    if (!bitsBelowThreshold(acc, L.mark_thr)) {
+      L.layer[e.x] = kLethal;
+      const float* pt = inst_points + (size_t)s * 3;  // touched with the point's own coordinates (voxel_layer.cpp:185)
+      b.touch((double)pt[0], (double)pt[1]);
+    }
+  }
+}
+
+// footprintTouch: ObstacleLayer::updateFootprint (obstacle_layer.cpp:415-425), a vertex of the transformed footprint per lane
+__device__ __forceinline__ void footprintTouch(const CostmapDev& cm, uint32_t inst, uint32_t tid, BoundsAcc& b) {
+  if (!cm.footprint_clearing) return;
+  const uint32_t nfp = cm.fp_n[inst];
+  if (tid < nfp) b.touch(cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2], cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2 + 1]);
+}
+
+// reduceBounds: the workgroup's box into thread 0 (min / max are exact and order-free): wave shuffles, then the waves' rows of `red`.  Holds a barrier.
+__device__ __forceinline__ void reduceBounds(BoundsAcc& b, double (&red)[4][4], uint32_t tid) {
+  for (int off = 32; off > 0; off >>= 1)
+    b.include(__shfl_down(b.min_x, off), __shfl_down(b.min_y, off), __shfl_down(b.max_x, off), __shfl_down(b.max_y, off));
+  if ((tid & 63) == 0) b.store(red[tid >> 6]);
+  __syncthreads();
+  if (tid == 0)
+    for (int w = 1; w < 4; ++w) b.include(red[w][0], red[w][1], red[w][2], red[w][3]);
+}
+
+// finishBounds (thread 0): where the reduced box goes; returns whether a box is left to update.  only_bounds hands it back to the caller
+// (layer-granular use by costmap_2d::Layer adapters); else InflationLayer::updateBounds (inflation_layer.cpp:125-158) and the bounds -> cell
+// box of LayeredCostmap::updateMap (layered_costmap.cpp:113-135) into the robot's state, where k_merge and the inflation kernels find it.
+__device__ __forceinline__ int finishBounds(const CostmapDev& cm, const Geom& g, InstCostmapState* st, BoundsAcc& b, double* bounds_out,
+                                            int only_bounds) {
+  if (only_bounds) {
+    // 1: the footprint polygon is cleared in this launch, ahead of the navgpu_obstacle_update_costs that the host's LayeredCostmap
+    // issues next (updateFootprint has put the polygon into the bounds, so that call always follows)
+    b.store(bounds_out + 4 * blockIdx.x);
+    return 1;
+  }
+  if (cm.layers & NAVGPU_LAYER_INFLATION) {
+    BoundsAcc u{st->last_min_x, st->last_min_y, st->last_max_x, st->last_max_y};  // tmp_min_x .. tmp_max_y (:145-148)
+    st->last_min_x = b.min_x;
+    st->last_min_y = b.min_y;
+    st->last_max_x = b.max_x;
+    st->last_max_y = b.max_y;
+    if (st->need_reinflation) {
+      const double kFloatMax = 3.4028234663852886e38;  // std::numeric_limits<float>::max()
+      b = BoundsAcc{-kFloatMax, -kFloatMax, kFloatMax, kFloatMax};
+      st->need_reinflation = 0;
+    } else {
+      u.include(b.min_x, b.min_y, b.max_x, b.max_y);  // std::min(tmp_min_x, *min_x) .. (:153-156)
+      const double r = cm.inflation_radius;
+      b = BoundsAcc{u.min_x - r, u.min_y - r, u.max_x + r, u.max_y + r};
+    }
+  }
+  b.store(st->bounds);
+  int x0, xn, y0, yn;
+  enforceBounds(g, b.min_x, b.min_y, x0, y0);
+  enforceBounds(g, b.max_x, b.max_y, xn, yn);
+  x0 = x0 > 0 ? x0 : 0;
+  xn = ((int)g.nx < xn + 1) ? (int)g.nx : xn + 1;
+  y0 = y0 > 0 ? y0 : 0;
+  yn = ((int)g.ny < yn + 1) ? (int)g.ny : yn + 1;
+  st->box[0] = x0;
+  st->box[1] = xn;
+  st->box[2] = y0;
+  st->box[3] = yn;
+  st->box_valid = !(xn < x0 || yn < y0);
+  return st->box_valid;
+}
+
+// clearFootprintPolygon: the head of ObstacleLayer::updateCosts (obstacle_layer.cpp:432-435) - the robot's footprint polygon becomes
+// FREE_SPACE in the layer grid.  Costmap2D::setConvexPolygonCost (costmap_2d.cpp:315-428) == per column x, every cell between the lowest
+// and the highest outline cell of that column (the bubble sort + pairwise walk of convexFillCells yields exactly this because each outline
+// column holds >= 2 entries of a closed outline; tests/test_polygon_fill).  Holds barriers: the whole workgroup calls it.
+__device__ __forceinline__ void clearFootprintPolygon(const CostmapDev& cm, const Geom& g, uint32_t inst, uint8_t* layer, uint32_t tid,
+                                                      uint32_t* s_vx, uint32_t* s_vy, uint32_t* colmin, uint32_t* colmax, int* s_poly_ok) {
+  const uint32_t nfp = cm.fp_n[inst];
+  if (tid == 0) *s_poly_ok = nfp >= 3;
+  __syncthreads();
+  if (tid < nfp) {
+    uint32_t mx, my;
+    bool ok = worldToMap(g, cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2], cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2 + 1], mx, my);
+    s_vx[tid] = mx;
+    s_vy[tid] = my;
+    if (!ok) atomicAnd(s_poly_ok, 0);
+  }
+  __syncthreads();
+  if (!*s_poly_ok) return;
+  uint32_t minx = 0xFFFFFFFFu, maxx = 0;
+  for (uint32_t i = 0; i < nfp; ++i) {
+    minx = s_vx[i] < minx ? s_vx[i] : minx;
+    maxx = s_vx[i] > maxx ? s_vx[i] : maxx;
+  }
+  const uint32_t span = maxx - minx + 1;
+  if (span > 1024) return;
+  for (uint32_t c = tid; c < span; c += blockDim.x) {
+    colmin[c] = 0xFFFFFFFFu;
+    colmax[c] = 0;
+  }
+  __syncthreads();
+  if (tid < nfp) {
+    uint32_t e1 = (tid + 1 == nfp) ? 0 : tid + 1;
+    raytrace2d(g.nx, s_vx[tid], s_vy[tid], s_vx[e1], s_vy[e1], 0xFFFFFFFFu, [&](uint32_t off) {
+      uint32_t y = off / g.nx, x = off - y * g.nx;
+      atomicMin(&colmin[x - minx], y);
+      atomicMax(&colmax[x - minx], y);
+    });
+  }
+  __syncthreads();
+  for (uint32_t c = tid >> 4; c < span; c += blockDim.x >> 4) {
+    uint32_t lo = colmin[c], hi = colmax[c];
+    if (lo == 0xFFFFFFFFu) continue;
+    for (uint32_t y = lo + (tid & 15); y <= hi; y += 16) layer[y * g.nx + minx + c] = kFree;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
-// k_obstacle: one 256-thread workgroup per robot instance.
-//   ObstacleLayer::updateBounds   plugins/obstacle_layer.cpp:340-413 (+ raytraceFreespace :498-576,
-//                                 updateRaytraceBounds :602-610, updateFootprint :415-425)
-//   VoxelLayer::updateBounds      plugins/voxel_layer.cpp:116-213 (+ raytraceFreespace :266-383)
-//   StaticLayer::updateBounds     plugins/static_layer.cpp:263-283
-//   InflationLayer::updateBounds  plugins/inflation_layer.cpp:125-158
-//   LayeredCostmap::updateMap     src/layered_costmap.cpp:96-135 (bounds -> cell box)
-//   ObstacleLayer::updateCosts    plugins/obstacle_layer.cpp:432-435 (footprint polygon clearing,
-//                                 Costmap2D::setConvexPolygonCost src/costmap_2d.cpp:315-428)
-// Ordering kept from the reference: every clearing ray before any mark (workgroup barrier
-// between the phases); all rays write FREE_SPACE so write-write races are benign.  The voxel
-// clear phase is split in two (column bits with atomics, then the dependent 2-D byte from the
-// final column state) which is equivalent because bits only ever get cleared during the phase.
+// k_obstacle: one 256-thread workgroup per robot instance takes its obstacle / voxel layer through a cycle, up to the cell box that
+// k_merge and the inflation kernels work on.  The stages (above; each names the reference lines it restates):
+//   boundsSeed              the caller's bounds, StaticLayer::updateBounds, useExtraBounds (thread 0)
+//   clearRays2D | clearRaysVoxel pass 0, barrier, pass 1    ObstacleLayer / VoxelLayer::raytraceFreespace, per clearing observation
+//   barrier                 every clearing ray before any mark, as in the reference's updateBounds
+//   markPoints<VOXEL> per marking observation | markPointsOrdered (voxel layer with mark_threshold > 0)
+//   footprintTouch          ObstacleLayer::updateFootprint
+//   reduceBounds            the workgroup's box into thread 0
+//   finishBounds            only_bounds write-back, or InflationLayer::updateBounds + LayeredCostmap::updateMap's cell box (thread 0)
+//   clearFootprintPolygon   the setConvexPolygonCost of ObstacleLayer::updateCosts
+// All rays write FREE_SPACE, so write-write races between them are benign.  The voxel clear phase in two passes equals the
+// reference's ray-by-ray order because bits only ever get cleared during the phase.
 // ------------------------------------------------------------------------------------------------
 template <bool VOXEL>
 __global__ __launch_bounds__(256) void k_obstacle(CostmapDev cm, uint32_t first, const double* bounds_io_in, double* bounds_io_out,
                                                   int only_bounds) {
-  const uint32_t inst = first + blockIdx.x;
-  const uint32_t tid = threadIdx.x;
-  Geom g{cm.origin[2 * inst], cm.origin[2 * inst + 1], cm.res, cm.nx, cm.ny};
-  uint8_t* layer = cm.obst + (size_t)inst * cm.cells_padded;
-  uint32_t* vox = VOXEL ? cm.voxel + (size_t)inst * cm.cells_padded : nullptr;
+  const uint32_t inst = first + blockIdx.x, tid = threadIdx.x;
+  ObstacleGrids L;
+  L.g = Geom{cm.origin[2 * inst], cm.origin[2 * inst + 1], cm.res, cm.nx, cm.ny};
+  L.layer = cm.obst + (size_t)inst * cm.cells_padded;
+  L.vox = VOXEL ? cm.voxel + (size_t)inst * cm.cells_padded : nullptr;
+  L.size_z = VOXEL ? (uint32_t)(cm.z_voxels > 16 ? 16 : cm.z_voxels) : 0;
+  L.unknown_thr = VOXEL ? (uint32_t)(cm.unknown_threshold + (16 - cm.z_voxels)) : 0;  // voxel_layer.cpp:89
+  L.mark_thr = VOXEL ? (uint32_t)cm.mark_threshold : 0;
   InstCostmapState* st = cm.state + inst;
-
   __shared__ double red[4][4];
   __shared__ int s_box_valid;
   __shared__ uint32_t colmin[1024], colmax[1024];
   __shared__ uint32_t s_vx[kMaxFootprint], s_vy[kMaxFootprint];
   __shared__ int s_poly_ok;
 
-  BoundsAcc b{1e30, 1e30, -1e30, -1e30};
-  if (tid == 0) {
-    if (bounds_io_in) {
-      b.min_x = bounds_io_in[4 * blockIdx.x + 0];
-      b.min_y = bounds_io_in[4 * blockIdx.x + 1];
-      b.max_x = bounds_io_in[4 * blockIdx.x + 2];
-      b.max_y = bounds_io_in[4 * blockIdx.x + 3];
-    }
-    if (!only_bounds && (cm.layers & NAVGPU_LAYER_STATIC) && st->static_has_updated_data) {
-      // mapToWorld(x_, y_) and (x_+width_, y_+height_) with the whole map as the updated window
-      double wx = g.ox + (0 + 0.5) * g.res, wy = g.oy + (0 + 0.5) * g.res;
-      b.min_x = (wx < b.min_x) ? wx : b.min_x;  // std::min(wx, *min_x)
-      b.min_y = (wy < b.min_y) ? wy : b.min_y;
-      wx = g.ox + (g.nx + 0.5) * g.res;
-      wy = g.oy + (g.ny + 0.5) * g.res;
-      b.max_x = (b.max_x < wx) ? wx : b.max_x;
-      b.max_y = (b.max_y < wy) ? wy : b.max_y;
-      st->static_has_updated_data = 0;
-    }
-    if (!only_bounds && cm.stat_roll) {
-      // rolling window: StaticLayer::updateBounds has no early return (static_layer.cpp:265-268) and adds the extent
-      // of the LAYER's grid - the static map's own geometry - every cycle
-      double wx = cm.stat_ox + (0 + 0.5) * cm.stat_res, wy = cm.stat_oy + (0 + 0.5) * cm.stat_res;
-      b.min_x = (wx < b.min_x) ? wx : b.min_x;
-      b.min_y = (wy < b.min_y) ? wy : b.min_y;
-      wx = cm.stat_ox + (cm.stat_nx + 0.5) * cm.stat_res;
-      wy = cm.stat_oy + (cm.stat_ny + 0.5) * cm.stat_res;
-      b.max_x = (b.max_x < wx) ? wx : b.max_x;
-      b.max_y = (b.max_y < wy) ? wy : b.max_y;
-    }
-  }
-
   const bool has_obs_layer = (cm.layers & (NAVGPU_LAYER_OBSTACLE | NAVGPU_LAYER_VOXEL)) && cm.obs_enabled;
-  if (tid == 0 && has_obs_layer && st->has_extra_bounds) {  // useExtraBounds (obstacle_layer.cpp:347, voxel_layer.cpp:123; costmap_layer.cpp:46-60)
-    b.min_x = (st->extra[0] < b.min_x) ? st->extra[0] : b.min_x;
-    b.min_y = (st->extra[1] < b.min_y) ? st->extra[1] : b.min_y;
-    b.max_x = (b.max_x < st->extra[2]) ? st->extra[2] : b.max_x;
-    b.max_y = (b.max_y < st->extra[3]) ? st->extra[3] : b.max_y;
-    st->extra[0] = st->extra[1] = 1e6;
-    st->extra[2] = st->extra[3] = -1e6;
-    st->has_extra_bounds = 0;
-  }
-  const uint32_t ob = inst * cm.max_obs, oe = ob + cm.obs_count[inst];
-  const float* inst_points = cm.points + (size_t)inst * cm.max_points * 3;
-  const uint32_t unknown_thr = VOXEL ? (uint32_t)(cm.unknown_threshold + (16 - cm.z_voxels)) : 0;  // voxel_layer.cpp:89
-  const uint32_t mark_thr = VOXEL ? (uint32_t)cm.mark_threshold : 0;
-  const uint32_t size_z = VOXEL ? (uint32_t)(cm.z_voxels > 16 ? 16 : cm.z_voxels) : 0;
+  BoundsAcc b{1e30, 1e30, -1e30, -1e30};
+  if (tid == 0) boundsSeed(cm, L.g, st, bounds_io_in, only_bounds, has_obs_layer, b);
 
   if (has_obs_layer) {
-    // ---------------- phase 1: clearing observations
+    const uint32_t ob = inst * cm.max_obs, oe = ob + cm.obs_count[inst];
+    const float* inst_points = cm.points + (size_t)inst * cm.max_points * 3;
     for (int pass = 0; pass < (VOXEL ? 2 : 1); ++pass) {
       for (uint32_t o = ob; o < oe; ++o) {
         const ObsCsr obs = cm.obs[o];
         if (!(obs.flags & NAVGPU_OBS_CLEARING)) continue;
-        const float* pts = inst_points + (size_t)obs.first_point * 3;
-        if (!VOXEL) {
-          uint32_t x0, y0;
-          if (!worldToMap(g, obs.ox, obs.oy, x0, y0)) continue;
-          const double map_end_x = g.ox + g.nx * g.res, map_end_y = g.oy + g.ny * g.res;
-          if (tid == 0) b.touch(obs.ox, obs.oy);
-          const uint32_t cell_range = cellDistance(obs.raytrace_range, g.res);
-          for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
-            double wx = pts[3 * p], wy = pts[3 * p + 1];
-            const double ox = obs.ox, oy = obs.oy;
-            double a = wx - ox, bb = wy - oy;
-            if (wx < g.ox) {
-              double t = (g.ox - ox) / a;
-              wx = g.ox;
-              wy = oy + bb * t;
-            }
-            if (wy < g.oy) {
-              double t = (g.oy - oy) / bb;
-              wx = ox + a * t;
-              wy = g.oy;
-            }
-            if (wx > map_end_x) {
-              double t = (map_end_x - ox) / a;
-              wx = map_end_x - .001;
-              wy = oy + bb * t;
-            }
-            if (wy > map_end_y) {
-              double t = (map_end_y - oy) / bb;
-              wx = ox + a * t;
-              wy = map_end_y - .001;
-            }
-            uint32_t x1, y1;
-            if (!worldToMap(g, wx, wy, x1, y1)) continue;
-            raytrace2d(g.nx, x0, y0, x1, y1, cell_range, [&](uint32_t off) { layer[off] = kFree; });
-            double dx = wx - ox, dy = wy - oy;
-            double full = hyp2(dx, dy);
-            double scale = fmin(1.0, obs.raytrace_range / full);
-            b.touch(ox + dx * scale, oy + dy * scale);
-          }
-        } else {
-          VoxelRay ray;  // the sensor test and the clip of voxel_layer.cpp:269-353 (navgpu_device.h)
-          if (!voxelRayBegin(g, cm, size_z, obs, ray)) continue;
-          const double ox = ray.ox, oy = ray.oy;
-          const double sensor_x = ray.sensor_x, sensor_y = ray.sensor_y, sensor_z = ray.sensor_z;
-          const uint32_t cell_range = cellDistance(obs.raytrace_range, g.res);
-          for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
-            double wpx, wpy, wpz, px, py, pz;
-            if (!voxelRayEnd(g, cm, size_z, ray, pts + 3 * p, wpx, wpy, wpz, px, py, pz)) continue;
-            // clearVoxelLineInMap endpoint check (voxel_grid.cpp:131-136) is implied by the two tests above
-            if (pass == 0) {
-              raytrace3d(g.nx, sensor_x, sensor_y, sensor_z, px, py, pz, cell_range,
-                         [&](uint32_t off, uint32_t zm) { atomicAnd(&vox[off], ~zm); });
-              double dx = wpx - ox, dy = wpy - oy;
-              double full = hyp2(dx, dy);
-              double scale = fmin(1.0, obs.raytrace_range / full);
-              b.touch(ox + dx * scale, oy + dy * scale);
-            } else {
-              raytrace3d(g.nx, sensor_x, sensor_y, sensor_z, px, py, pz, cell_range, [&](uint32_t off, uint32_t) {
-                uint32_t col = vox[off];
-                uint32_t unknown_bits = (uint16_t)(col >> 16) ^ (uint16_t)col;
-                uint32_t marked_bits = col >> 16;
-                if (bitsBelowThreshold(marked_bits, mark_thr))
-                  layer[off] = bitsBelowThreshold(unknown_bits, unknown_thr) ? kFree : kNoInfo;
-              });
-            }
-          }
-        }
+        if (!VOXEL)
+          clearRays2D(L, obs, inst_points + (size_t)obs.first_point * 3, tid, b);
+        else
+          clearRaysVoxel(cm, L, obs, inst_points + (size_t)obs.first_point * 3, pass, tid, b);
       }
       __syncthreads();
     }
-    // ---------------- phase 2: marking observations
-    // VoxelGrid::markVoxelInMap reports "marked" from the column's bit count AT THAT POINT of the sequential loop
-    // (voxel_grid.h:100-117), so with mark_threshold > 0 which points touch the bounds depends on the point
-    // order.  Exact two-step form: (1) every point records its cell, z and the column bits before any marking;
-    // (2) a point is marked iff those bits, the bits of the EARLIER points of the same cell and its own exceed
-    // the threshold.  (mark_threshold == 0: every accepted point is marked, the one-pass form below is exact.)
-    if (VOXEL && mark_thr > 0) {
-      uint2* seq = cm.mark_seq + (size_t)inst * cm.max_points;
-      uint32_t n_seq = 0;
-      for (uint32_t o = ob; o < oe; ++o) n_seq = max(n_seq, cm.obs[o].first_point + cm.obs[o].n_points);
-      for (uint32_t s = tid; s < n_seq; s += blockDim.x) seq[s] = make_uint2(0u, 0u);
-      __syncthreads();
+    if (VOXEL && L.mark_thr > 0)
+      markPointsOrdered(cm, L, ob, oe, inst_points, cm.mark_seq + (size_t)inst * cm.max_points, tid, b);
+    else
       for (uint32_t o = ob; o < oe; ++o) {
         const ObsCsr obs = cm.obs[o];
         if (!(obs.flags & NAVGPU_OBS_MARKING)) continue;
-        const float* pts = inst_points + (size_t)obs.first_point * 3;
-        const double sq_obstacle_range = obs.obstacle_range * obs.obstacle_range;
-        for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
-          const float fx = pts[3 * p], fy = pts[3 * p + 1], fz = pts[3 * p + 2];
-          double px = fx, py = fy, pz = fz;
-          if (pz > cm.max_obstacle_height) continue;
-          double sq_dist = (px - obs.ox) * (px - obs.ox) + (py - obs.oy) * (py - obs.oy) + (pz - obs.oz) * (pz - obs.oz);
-          if (sq_dist >= sq_obstacle_range) continue;
-          double wz = (pz < cm.origin_z) ? cm.origin_z : pz;
-          if (px < g.ox || py < g.oy || wz < cm.origin_z) continue;
-          double fxm = (px - g.ox) / g.res, fym = (py - g.oy) / g.res, fzm = (wz - cm.origin_z) / cm.z_resolution;
-          if (!(fxm < 2147483648.0) || !(fym < 2147483648.0) || !(fzm < 2147483648.0)) continue;
-          uint32_t mx = (uint32_t)(int)fxm, my = (uint32_t)(int)fym, mz = (uint32_t)(int)fzm;
-          if (!(mx < g.nx && my < g.ny && mz < (uint32_t)cm.z_voxels)) continue;
-          if (mz >= size_z) continue;
-          const uint32_t cell = my * g.nx + mx;
-          seq[obs.first_point + p] = make_uint2(cell, 0x80000000u | ((vox[cell] >> 16) << 8) | mz);
-        }
+        markPoints<VOXEL>(cm, L, obs, inst_points + (size_t)obs.first_point * 3, tid, b);
       }
-      __syncthreads();
-      for (uint32_t s = tid; s < n_seq; s += blockDim.x) {
-        const uint2 e = seq[s];
-        if (!(e.y & 0x80000000u)) continue;
-        const uint32_t mz = e.y & 0xFFu;
-        uint32_t acc = ((e.y >> 8) & 0xFFFFu) | (1u << mz);
-        for (uint32_t q = 0; q < s; ++q) {
-          const uint2 f = seq[q];
-          if ((f.y & 0x80000000u) && f.x == e.x) acc |= 1u << (f.y & 0xFFu);
-        }
-        atomicOr(&vox[e.x], ((uint32_t)1 << mz << 16) | (1u << mz));
-        if (!bitsBelowThreshold(acc, mark_thr)) {
-          layer[e.x] = kLethal;
-          const float* pt = inst_points + (size_t)s * 3;  // touched with the point's own coordinates (voxel_layer.cpp:181)
-          b.touch((double)pt[0], (double)pt[1]);
-        }
-      }
-    } else
-    for (uint32_t o = ob; o < oe; ++o) {
-      const ObsCsr obs = cm.obs[o];
-      if (!(obs.flags & NAVGPU_OBS_MARKING)) continue;
-      const float* pts = inst_points + (size_t)obs.first_point * 3;
-      const double sq_obstacle_range = obs.obstacle_range * obs.obstacle_range;
-      for (uint32_t p = tid; p < obs.n_points; p += blockDim.x) {
-        const float fx = pts[3 * p], fy = pts[3 * p + 1], fz = pts[3 * p + 2];
-        double px = fx, py = fy, pz = fz;
-        if (pz > cm.max_obstacle_height) continue;
-        double sq_dist = (px - obs.ox) * (px - obs.ox) + (py - obs.oy) * (py - obs.oy) + (pz - obs.oz) * (pz - obs.oz);
-        if (sq_dist >= sq_obstacle_range) continue;
-        if (!VOXEL) {
-          uint32_t mx, my;
-          if (!worldToMap(g, px, py, mx, my)) continue;
-          layer[my * g.nx + mx] = kLethal;
-          b.touch(px, py);
-        } else {
-          double wz = (pz < cm.origin_z) ? cm.origin_z : pz;  // voxel_layer.cpp:169-173
-          if (px < g.ox || py < g.oy || wz < cm.origin_z) continue;
-          double fxm = (px - g.ox) / g.res, fym = (py - g.oy) / g.res, fzm = (wz - cm.origin_z) / cm.z_resolution;
-          if (!(fxm < 2147483648.0) || !(fym < 2147483648.0) || !(fzm < 2147483648.0)) continue;
-          uint32_t mx = (uint32_t)(int)fxm, my = (uint32_t)(int)fym, mz = (uint32_t)(int)fzm;
-          if (!(mx < g.nx && my < g.ny && mz < (uint32_t)cm.z_voxels)) continue;  // worldToMap3D uses size_z_ as configured
-          if (mz >= size_z) continue;                                             // VoxelGrid::markVoxelInMap bound (voxel_grid.h:102)
-          uint32_t full_mask = ((uint32_t)1 << mz << 16) | (1u << mz);
-          uint32_t old = atomicOr(&vox[my * g.nx + mx], full_mask);
-          uint32_t marked_bits = (old | full_mask) >> 16;
-          if (!bitsBelowThreshold(marked_bits, mark_thr)) {
-            layer[my * g.nx + mx] = kLethal;
-            b.touch(px, py);
-          }
-        }
-      }
-    }
-    // ---------------- updateFootprint: touch the transformed footprint
-    if (cm.footprint_clearing) {
-      uint32_t nfp = cm.fp_n[inst];
-      if (tid < nfp) b.touch(cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2], cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2 + 1]);
-    }
+    footprintTouch(cm, inst, tid, b);
   }
 
-  // ---------------- workgroup reduction of the bounds (min/max are exact, order-free)
-  for (int off = 32; off > 0; off >>= 1) {
-    double o0 = __shfl_down(b.min_x, off), o1 = __shfl_down(b.min_y, off), o2 = __shfl_down(b.max_x, off), o3 = __shfl_down(b.max_y, off);
-    b.min_x = (o0 < b.min_x) ? o0 : b.min_x;
-    b.min_y = (o1 < b.min_y) ? o1 : b.min_y;
-    b.max_x = (b.max_x < o2) ? o2 : b.max_x;
-    b.max_y = (b.max_y < o3) ? o3 : b.max_y;
-  }
-  if ((tid & 63) == 0) {
-    red[tid >> 6][0] = b.min_x;
-    red[tid >> 6][1] = b.min_y;
-    red[tid >> 6][2] = b.max_x;
-    red[tid >> 6][3] = b.max_y;
-  }
+  reduceBounds(b, red, tid);
+  if (tid == 0) s_box_valid = finishBounds(cm, L.g, st, b, bounds_io_out, only_bounds);
   __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) {
-      b.min_x = (red[w][0] < b.min_x) ? red[w][0] : b.min_x;
-      b.min_y = (red[w][1] < b.min_y) ? red[w][1] : b.min_y;
-      b.max_x = (b.max_x < red[w][2]) ? red[w][2] : b.max_x;
-      b.max_y = (b.max_y < red[w][3]) ? red[w][3] : b.max_y;
-    }
-    if (only_bounds) {
-      bounds_io_out[4 * blockIdx.x + 0] = b.min_x;
-      bounds_io_out[4 * blockIdx.x + 1] = b.min_y;
-      bounds_io_out[4 * blockIdx.x + 2] = b.max_x;
-      bounds_io_out[4 * blockIdx.x + 3] = b.max_y;
-      // layer-granular use (costmap_2d::Layer adapters): the footprint polygon is cleared here, ahead of the
-      // navgpu_obstacle_update_costs that the host's LayeredCostmap issues next (ObstacleLayer::updateCosts :431-434;
-      // updateFootprint has put the polygon into the bounds, so that call always follows)
-      s_box_valid = 1;
-    } else {
-      if (cm.layers & NAVGPU_LAYER_INFLATION) {  // InflationLayer::updateBounds
-        if (st->need_reinflation) {
-          st->last_min_x = b.min_x;
-          st->last_min_y = b.min_y;
-          st->last_max_x = b.max_x;
-          st->last_max_y = b.max_y;
-          b.min_x = -3.4028234663852886e38;  // -std::numeric_limits<float>::max()
-          b.min_y = -3.4028234663852886e38;
-          b.max_x = 3.4028234663852886e38;
-          b.max_y = 3.4028234663852886e38;
-          st->need_reinflation = 0;
-        } else {
-          double tminx = st->last_min_x, tminy = st->last_min_y, tmaxx = st->last_max_x, tmaxy = st->last_max_y;
-          st->last_min_x = b.min_x;
-          st->last_min_y = b.min_y;
-          st->last_max_x = b.max_x;
-          st->last_max_y = b.max_y;
-          b.min_x = ((b.min_x < tminx) ? b.min_x : tminx) - cm.inflation_radius;  // std::min(tmp_min_x, *min_x)
-          b.min_y = ((b.min_y < tminy) ? b.min_y : tminy) - cm.inflation_radius;
-          b.max_x = ((tmaxx < b.max_x) ? b.max_x : tmaxx) + cm.inflation_radius;
-          b.max_y = ((tmaxy < b.max_y) ? b.max_y : tmaxy) + cm.inflation_radius;
-        }
-      }
-      st->bounds[0] = b.min_x;
-      st->bounds[1] = b.min_y;
-      st->bounds[2] = b.max_x;
-      st->bounds[3] = b.max_y;
-      int x0, xn, y0, yn;
-      enforceBounds(g, b.min_x, b.min_y, x0, y0);
-      enforceBounds(g, b.max_x, b.max_y, xn, yn);
-      x0 = x0 > 0 ? x0 : 0;
-      xn = ((int)g.nx < xn + 1) ? (int)g.nx : xn + 1;
-      y0 = y0 > 0 ? y0 : 0;
-      yn = ((int)g.ny < yn + 1) ? (int)g.ny : yn + 1;
-      st->box[0] = x0;
-      st->box[1] = xn;
-      st->box[2] = y0;
-      st->box[3] = yn;
-      st->box_valid = !(xn < x0 || yn < y0);
-      s_box_valid = st->box_valid;
-    }
-  }
-  __syncthreads();
-
-  // ---------------- ObstacleLayer::updateCosts head: clear the robot footprint polygon in the layer grid.
-  // setConvexPolygonCost == per column x, every cell between the lowest and the highest outline
-  // cell of that column (the bubble sort + pairwise walk of convexFillCells yields exactly this
-  // because each outline column holds >= 2 entries of a closed outline; tests/test_polygon_fill).
-  if (has_obs_layer && cm.footprint_clearing && s_box_valid) {
-    const uint32_t nfp = cm.fp_n[inst];
-    if (tid == 0) s_poly_ok = nfp >= 3;
-    __syncthreads();
-    if (tid < nfp) {
-      uint32_t mx, my;
-      bool ok = worldToMap(g, cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2], cm.fp_world[((size_t)inst * kMaxFootprint + tid) * 2 + 1], mx, my);
-      s_vx[tid] = mx;
-      s_vy[tid] = my;
-      if (!ok) atomicAnd(&s_poly_ok, 0);
-    }
-    __syncthreads();
-    if (s_poly_ok) {
-      uint32_t minx = 0xFFFFFFFFu, maxx = 0;
-      for (uint32_t i = 0; i < nfp; ++i) {
-        minx = s_vx[i] < minx ? s_vx[i] : minx;
-        maxx = s_vx[i] > maxx ? s_vx[i] : maxx;
-      }
-      const uint32_t span = maxx - minx + 1;
-      if (span <= 1024) {
-        for (uint32_t c = tid; c < span; c += blockDim.x) {
-          colmin[c] = 0xFFFFFFFFu;
-          colmax[c] = 0;
-        }
-        __syncthreads();
-        if (tid < nfp) {
-          uint32_t e1 = (tid + 1 == nfp) ? 0 : tid + 1;
-          raytrace2d(g.nx, s_vx[tid], s_vy[tid], s_vx[e1], s_vy[e1], 0xFFFFFFFFu, [&](uint32_t off) {
-            uint32_t y = off / g.nx, x = off - y * g.nx;
-            atomicMin(&colmin[x - minx], y);
-            atomicMax(&colmax[x - minx], y);
-          });
-        }
-        __syncthreads();
-        for (uint32_t c = tid >> 4; c < span; c += blockDim.x >> 4) {
-          uint32_t lo = colmin[c], hi = colmax[c];
-          if (lo == 0xFFFFFFFFu) continue;
-          for (uint32_t y = lo + (tid & 15); y <= hi; y += 16) layer[y * g.nx + minx + c] = kFree;
-        }
-      }
-    }
-  }
+  if (has_obs_layer && cm.footprint_clearing && s_box_valid)
+    clearFootprintPolygon(cm, L.g, inst, L.layer, tid, s_vx, s_vy, colmin, colmax, &s_poly_ok);
 }
 
 // k_reset_bounding_box: CostmapLayer::resetBoundingBox (costmap_layer.cpp:30-43) on the obstacle / voxel layer's 2-D grid:
@@ -647,6 +684,8 @@ __global__ __launch_bounds__(256) void k_reset_bounding_box(CostmapDev cm, uint3
       st->extra[0] = st->extra[1] = 1e6;
       st->extra[2] = st->extra[3] = -1e6;
     }
+    // addExtraBounds (costmap_layer.cpp:21-28).  Keep these four lines in step with BoundsAcc::include, whose spelling they are:
+    // through a BoundsAcc the kernel holds all eight doubles at once (18 VGPRs instead of 16)
     st->extra[0] = (bw[0] < st->extra[0]) ? bw[0] : st->extra[0];
     st->extra[1] = (bw[1] < st->extra[1]) ? bw[1] : st->extra[1];
     st->extra[2] = (st->extra[2] < bw[2]) ? bw[2] : st->extra[2];
@@ -665,6 +704,32 @@ void launch_reset_window(uint8_t* grid, size_t stride, uint32_t count, uint32_t 
 }
 void launch_reset_bounding_box(const CostmapDev& cm, uint32_t first, uint32_t count, const double* boxes_world, hipStream_t s) {
   hipLaunchKernelGGL(k_reset_bounding_box, dim3(count), dim3(256), 0, s, cm, first, boxes_world);
+}
+
+// The cell box [x0, xn) x [y0, yn) a cycle's k_merge and inflation kernels work on (LayeredCostmap::updateMap,
+// layered_costmap.cpp:113-135).
+struct UpdateBox {
+  int x0, y0, xn, yn;
+};
+// Robot `inst`'s box, the k-th of its launch: the caller's when it passes `boxes` ([k][4], ordered x0, y0, xn, yn as updateCosts takes
+// them), else the one finishBounds left in the robot's state - InstCostmapState::box, ordered x0, xn, y0, yn as updateMap declares
+// them.  false: that box is empty (layered_costmap.cpp:128-135), nothing to update.
+__device__ __forceinline__ bool updateBox(const CostmapDev& cm, const int32_t* boxes, uint32_t k, uint32_t inst, UpdateBox& box) {
+  if (boxes) {
+    box = UpdateBox{boxes[4 * k + 0], boxes[4 * k + 1], boxes[4 * k + 2], boxes[4 * k + 3]};
+    return true;
+  }
+  const InstCostmapState* st = cm.state + inst;
+  if (!st->box_valid) return false;
+  box.x0 = st->box[0];
+  box.xn = st->box[1];
+  box.y0 = st->box[2];
+  box.yn = st->box[3];
+  return true;
+}
+// InflationLayer::updateCosts' seed box (inflation_layer.cpp:200-211): grown by the inflation radius R, clamped to the nx x ny grid
+__device__ __forceinline__ UpdateBox inflateBox(const UpdateBox& box, int R, uint32_t nx, uint32_t ny) {
+  return UpdateBox{max(0, box.x0 - R), max(0, box.y0 - R), min((int)nx, box.xn + R), min((int)ny, box.yn + R)};
 }
 
 void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const double* bounds_in, int only_bounds, hipStream_t s) {
@@ -686,20 +751,9 @@ void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_merge(CostmapDev cm, uint32_t first, const int32_t* boxes, int static_received, int layer_only) {
   const uint32_t inst = first + blockIdx.y;
-  int x0, xn, y0, yn;
-  if (boxes) {
-    x0 = boxes[4 * blockIdx.y + 0];
-    y0 = boxes[4 * blockIdx.y + 1];
-    xn = boxes[4 * blockIdx.y + 2];
-    yn = boxes[4 * blockIdx.y + 3];
-  } else {
-    const InstCostmapState* st = cm.state + inst;
-    if (!st->box_valid) return;
-    x0 = st->box[0];
-    xn = st->box[1];
-    y0 = st->box[2];
-    yn = st->box[3];
-  }
+  UpdateBox box;
+  if (!updateBox(cm, boxes, blockIdx.y, inst, box)) return;
+  const int x0 = box.x0, y0 = box.y0, xn = box.xn, yn = box.yn;
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;  // 16-cell group
   const uint32_t base = q * 16;
   if (base >= cm.cells) return;
@@ -801,25 +855,10 @@ __global__ __launch_bounds__(256) void k_inflate(CostmapDev cm, uint32_t first, 
   extern __shared__ __align__(16) uint8_t lds[];
   const uint32_t inst = first + blockIdx.z;
   const int R = (int)cm.R;
-  int min_i, min_j, max_i, max_j;
-  if (boxes) {
-    min_i = boxes[4 * blockIdx.z + 0];
-    min_j = boxes[4 * blockIdx.z + 1];
-    max_i = boxes[4 * blockIdx.z + 2];
-    max_j = boxes[4 * blockIdx.z + 3];
-  } else {
-    const InstCostmapState* st = cm.state + inst;
-    if (!st->box_valid) return;
-    min_i = st->box[0];
-    max_i = st->box[1];
-    min_j = st->box[2];
-    max_j = st->box[3];
-  }
-  // grown + clamped box (:205-213)
-  min_i = max(0, min_i - R);
-  min_j = max(0, min_j - R);
-  max_i = min((int)cm.nx, max_i + R);
-  max_j = min((int)cm.ny, max_j + R);
+  UpdateBox box;
+  if (!updateBox(cm, boxes, blockIdx.z, inst, box)) return;
+  box = inflateBox(box, R, cm.nx, cm.ny);
+  const int min_i = box.x0, min_j = box.y0, max_i = box.xn, max_j = box.yn;
   const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
   // seeds that can reach this tile lie in [tx0-R, tx0+kTile+R) x [ty0-R, ty0+kTile+R)
   if (tx0 - R >= max_i || tx0 + kTile + R <= min_i || ty0 - R >= max_j || ty0 + kTile + R <= min_j) return;
@@ -906,24 +945,10 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
   if (rz >= count) return;
   const uint32_t inst = first + rz;
   const int R = RT > 0 ? RT : (int)cm.R;
-  int min_i, min_j, max_i, max_j;
-  if (boxes) {
-    min_i = boxes[4 * rz + 0];
-    min_j = boxes[4 * rz + 1];
-    max_i = boxes[4 * rz + 2];
-    max_j = boxes[4 * rz + 3];
-  } else {
-    const InstCostmapState* st = cm.state + inst;
-    if (!st->box_valid) return;
-    min_i = st->box[0];
-    max_i = st->box[1];
-    min_j = st->box[2];
-    max_j = st->box[3];
-  }
-  min_i = max(0, min_i - R);
-  min_j = max(0, min_j - R);
-  max_i = min((int)cm.nx, max_i + R);
-  max_j = min((int)cm.ny, max_j + R);
+  UpdateBox box;
+  if (!updateBox(cm, boxes, rz, inst, box)) return;
+  box = inflateBox(box, R, cm.nx, cm.ny);
+  const int min_i = box.x0, min_j = box.y0, max_i = box.xn, max_j = box.yn;
   const int tx0 = (int)tbx * kBX, ty0 = (int)tby * kBY;
   if (tx0 - R >= max_i || tx0 + kBX + R <= min_i || ty0 - R >= max_j || ty0 + kBY + R <= min_j) return;
 
@@ -1100,30 +1125,16 @@ __global__ __launch_bounds__(64) void k_inflate_pq(CostmapDev cm, uint32_t first
   extern __shared__ __align__(16) uint8_t pq_sm[];
   const uint32_t inst = first + blockIdx.x;
   const uint32_t tid = threadIdx.x;
-  int min_i, min_j, max_i, max_j;
-  if (boxes) {
-    min_i = boxes[4 * blockIdx.x + 0];
-    min_j = boxes[4 * blockIdx.x + 1];
-    max_i = boxes[4 * blockIdx.x + 2];
-    max_j = boxes[4 * blockIdx.x + 3];
-  } else {
-    const InstCostmapState* st = cm.state + inst;
-    if (!st->box_valid) return;
-    min_i = st->box[0];
-    max_i = st->box[1];
-    min_j = st->box[2];
-    max_j = st->box[3];
-  }
+  UpdateBox box;
+  if (!updateBox(cm, boxes, blockIdx.x, inst, box)) return;
   uint8_t* master = cm.master + (size_t)inst * cm.cells_padded;
   uint8_t* seen_g = cm.pq_seen + (size_t)inst * cm.cells_padded;
   PqCell* heap_g = cm.pq_heap + (size_t)inst * cm.pq_cap;
   const uint32_t size_x = cm.nx, size_y = cm.ny;
   const int R = (int)cm.R;
   const uint32_t n = cm.R + 2;  // stride of the caches
-  min_i = max(0, min_i - R);  // :204-212
-  min_j = max(0, min_j - R);
-  max_i = min((int)size_x, max_i + R);
-  max_j = min((int)size_y, max_j + R);
+  box = inflateBox(box, R, size_x, size_y);
+  const int min_i = box.x0, min_j = box.y0, max_i = box.xn, max_j = box.yn;
   if (max_i <= min_i || max_j <= min_j) return;  // (uniform) no seed row / column: the loops below never run
   // everything the walk can touch
   const int wx0 = max(0, min_i - R - 1), wy0 = max(0, min_j - R - 1), wx1 = min((int)size_x, max_i + R + 1), wy1 = min((int)size_y, max_j + R + 1);

@@ -6,7 +6,7 @@
 //                       classify: popc counts, a bit scan emits.
 //   clearing endpoints: voxel_layer.cpp:286-381 - the clipped ray end of every point of every staged clearing observation that
 //                       passes worldToMap3DFloat, in staging then cloud order; the predicate and the end are voxelRayBegin /
-//                       voxelRayEnd of navgpu_device.h, which k_obstacle<true> walks its rays to.
+//                       voxelRayEnd of navgpu_device.h, which k_obstacle<true>'s clearRaysVoxel walks its rays to.
 // Both are three launches over fixed-size chunks of the input:
 //   (a) count : a workgroup per (chunk, robot) - per (chunk of points, observation, robot) for the endpoints - writes ONE total
 //   (b) scan  : a workgroup per robot scans its totals exclusively, in tiles of 256 with a carry, and writes the robot's count

@@ -809,6 +809,96 @@ def test_costmap_edge_cases(nav, orc):
     fl.close()
 
 
+def test_obstacle_rays_leave_through_every_edge(nav, orc):
+    """Clearing rays that leave the map through each edge and each corner (two clips in sequence), 2-D and voxel, first with
+    a raytrace range that reaches the edge, then (twice: InflationLayer merges the previous cycle's box) with one that ends
+    inside the map, where updateRaytraceBounds' scale < 1 decides the box."""
+    from navigation_amd import synth
+    N = L(nav)
+    n = 40
+    size = n * synth.RES  # 2 m
+    sensor = (1.02, 0.98, 0.5)
+    pose = [sensor[0], sensor[1], 0.3]
+    insc = synth.inscribed_radius(synth.FOOTPRINT)
+    outward = [[3.0, 1.1], [-1.0, 0.9], [1.1, 3.0], [0.9, -1.0],      # beyond the +x, -x, +y, -y edge
+               [3.0, 3.2], [-1.0, 3.1], [-1.0, -1.2], [3.1, -0.9]]    # beyond the four corners
+    inside = [1.31, 1.22]
+    cloud = np.array([p + [0.3] for p in outward + [inside]], np.float32)
+
+    def first_cut(p):  # the first cut of obstacle_layer.cpp:535-560 that applies to p, alone
+        ox, oy = sensor[0], sensor[1]
+        a, b = p[0] - ox, p[1] - oy
+        if p[0] < 0.0:
+            return 0.0, oy + b * (0.0 - ox) / a
+        if p[1] < 0.0:
+            return ox + a * (0.0 - oy) / b, 0.0
+        if p[0] > size:
+            return size - .001, oy + b * (size - ox) / a
+        return ox + a * (size - oy) / b, size - .001
+
+    for p in outward[4:]:  # every corner ray needs a second cut: the first one leaves its end outside the map
+        cx, cy = first_cut(p)
+        assert not (0.0 <= cx <= size and 0.0 <= cy <= size), ("one cut is enough for this corner", p, cx, cy)
+
+    def exit_cell(p):  # the cell in which the ray from the sensor towards p leaves the map
+        dx, dy = p[0] - sensor[0], p[1] - sensor[1]
+        t = min(((size if d > 0 else 0.0) - s) / d for s, d in ((sensor[0], dx), (sensor[1], dy)))
+        return tuple(min(n - 1, max(0, int((s + d * t) / synth.RES))) for s, d in ((sensor[0], dx), (sensor[1], dy)))
+
+    for voxel in (False, True):
+        pts = cloud
+        if voxel:  # one point above max_obstacle_height, one below the floor
+            pts = np.concatenate([cloud, np.array([[1.42, 0.72, 2.4], [0.62, 1.38, -0.2]], np.float32)])
+        fl = nav.Fleet(1, n, n, synth.RES, layers=(N.LAYER_VOXEL if voxel else N.LAYER_OBSTACLE) | N.LAYER_INFLATION,
+                       track_unknown=True, max_points=16, max_observations=1)
+        o = orc.LayeredCostmap(True)
+        o.resize(n, n, synth.RES, 0, 0)
+        o.set_footprint(synth.FOOTPRINT)
+        if voxel:
+            fl.configure_obstacle(z_voxels=10, origin_z=0.0, z_resolution=0.2, mark_threshold=0, max_obstacle_height=2.0)
+            o.add_voxel(z_voxels=10, origin_z=0.0, z_resolution=0.2, mark_threshold=0, max_obstacle_height=2.0)
+        else:
+            fl.configure_obstacle()
+            o.add_obstacle()
+        fl.set_footprint(synth.FOOTPRINT)
+        fl.configure_inflation(synth.INFLATION_RADIUS, synth.COST_SCALING, insc)
+        o.add_inflation(synth.INFLATION_RADIUS, synth.COST_SCALING, exact=True)
+        o.set_footprint(synth.FOOTPRINT)
+
+        def cycle(observations):
+            o.clear_observations()
+            for ob in observations:
+                o.add_observation(ob["points"], origin=ob["origin"], obstacle_range=ob["obstacle_range"], raytrace_range=ob["raytrace_range"])
+            o.update_map(*pose)
+            fl.stage_observations([pose], observations)
+            fl.update_map()
+            assert np.array_equal(fl.bounds()[0], o.bounds()), ("box", voxel)
+            assert np.array_equal(fl.download(N.GRID_OBSTACLE)[0], o.layer(2)), ("layer 2-D grid", voxel)
+            assert np.array_equal(fl.master()[0], o.master()), ("master", voxel)
+            if voxel:
+                assert np.array_equal(fl.download(N.GRID_VOXEL)[0], o.voxels()), ("voxel columns", voxel)
+
+        cycle([])
+        before = o.layer(2).copy()
+        cycle([dict(instance=0, points=pts, origin=sensor, obstacle_range=2.5, raytrace_range=5.0)])
+        after = o.layer(2)
+        # the oracle itself: every outward ray cleared cells that were unknown where it leaves the map, the inner point is marked
+        for p in outward:
+            cx, cy = exit_cell(p)
+            win = (slice(max(0, cy - 1), cy + 2), slice(max(0, cx - 1), cx + 2))
+            assert np.all(before[win] == NOINFO) and np.any(after[win] == FREE), ("ray clears nothing at its edge", voxel, p)
+        assert after[int(inside[1] / synth.RES), int(inside[0] / synth.RES)] == LETHAL, ("inner point not marked", voxel)
+        if voxel:  # the point below the floor marks level 0 of its column, the one above max_obstacle_height marks nothing
+            cols = o.voxels()
+            assert (cols[int(1.38 / synth.RES), int(0.62 / synth.RES)] >> 16) == 1, "below-floor point"
+            assert (cols[int(0.72 / synth.RES), int(1.42 / synth.RES)] >> 16) == 0, "point above max_obstacle_height"
+        for _ in range(2):
+            cycle([dict(instance=0, points=pts, origin=sensor, obstacle_range=2.5, raytrace_range=0.3)])
+        x0, xn, y0, yn = o.bounds()
+        assert 0 < x0 and xn < n and 0 < y0 and yn < n, ("the short rays' box should lie inside the map", voxel, o.bounds())
+        fl.close()
+
+
 # ----------------------------------------------------------------------------------------------
 # MapGrid wavefronts: searches longer than one level epoch (> 1023 levels), odd and non-square sizes
 # ----------------------------------------------------------------------------------------------
