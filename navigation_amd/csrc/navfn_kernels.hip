@@ -15,18 +15,13 @@
 // costmaps already resident in HBM) is where the device is used.
 #include <hip/hip_runtime.h>
 
+#include "navfn_rules.h"
 #include "navgpu_device.h"
 
 namespace navgpu {
 
 namespace {
 constexpr int kCostUnknownRos = 255, kCostObs = 254, kCostObsRos = 253, kCostNeutral = 50;  // navfn.h:49-67
-constexpr float kPotHigh = 1.0e10f;                                                          // navfn.h:77
-// `int minp = potarr[stc]` (navfn.cpp:895, gradient_path.cpp:119) with potarr[stc] == POT_HIGH is out of int range; the
-// amd64 builds of the reference get cvttss2si's 0x80000000 there (so no neighbour is lower and the trace ends with "high
-// potential"); v_cvt_i32_f32 would saturate to INT_MAX and walk on, so the amd64 value is restated.
-__device__ __forceinline__ int truncX86(float v) { return (v >= -2147483648.f && v < 2147483648.f) ? (int)v : (int)0x80000000; }
-constexpr int kPriorityBufSize = 10000;                                                      // navfn.h:80
 }  // namespace
 
 // NavFn::setCostmap: cost_mode 0 = the bytes ARE costarr, 1 = isROS, 2 = plain PGM (borders of 7 cells stay obstacles)
@@ -57,8 +52,7 @@ __global__ __launch_bounds__(256) void k_navfn_costmap(NavfnDev nv, uint32_t fir
 }
 
 // NavFn::calcPath / gradCell (:811-1056) over one plan's potential array, one lane: the interpolated gradient descent from the
-// start cell, its result record included.  Shared by the two expansions (reference order: k_navfn_plan; tiled wavefront:
-// k_navfn_wf_path).
+// start cell, its result record included (the tiled wavefront's walk by one wave is k_navfn_wf_path).
 __device__ void navfnCalcPath(const NavfnDev& nv, uint32_t plan, const float* potarr, int goal0, int goal1, int start0, int start1, int n_max,
                               int cycle) {
   const int nx = nv.nx, ny = nv.ny, ns = nv.ns;
@@ -67,41 +61,22 @@ __device__ void navfnCalcPath(const NavfnDev& nv, uint32_t plan, const float* po
   float* pathx = nv.path + (size_t)plan * 2 * nv.path_cap;
   float* pathy = pathx + nv.path_cap;
   const int startCell = start1 * nx + start0;
-  // ---- gradCell (:1001-1056)
-  auto gradCell = [&](int n) {
-    if (gradx[n] + grady[n] > 0.0) return;
-    if (n < nx || n > ns - nx) return;
-    const float cv = potarr[n];
-    float dx = 0.0f, dy = 0.0f;
-    if (cv >= kPotHigh) {
-      if (potarr[n - 1] < kPotHigh)
-        dx = -kCostObs;
-      else if (potarr[n + 1] < kPotHigh)
-        dx = kCostObs;
-      if (potarr[n - nx] < kPotHigh)
-        dy = -kCostObs;
-      else if (potarr[nx + 1] < kPotHigh)  // as written in the reference (:1020)
-        dy = kCostObs;
-    } else {
-      if (potarr[n - 1] < kPotHigh) dx += potarr[n - 1] - cv;
-      if (potarr[n + 1] < kPotHigh) dx += cv - potarr[n + 1];
-      if (potarr[n - nx] < kPotHigh) dy += potarr[n - nx] - cv;
-      if (potarr[n + nx] < kPotHigh) dy += cv - potarr[n + nx];
-    }
-    float norm = (float)hypot((double)dx, (double)dy);
-    if (norm > 0) {
-      norm = (float)(1.0 / norm);
-      gradx[n] = norm * dx;
-      grady[n] = norm * dy;
-    }
-  };
-  // ---- calcPath (:811-985)
-  const float pathStep = 0.5f;
+  const float pot_nx1 = potarr[nx + 1];
   int stc = startCell, npath = 0, found = 0;
   float dx = 0, dy = 0;
-  for (int i = 0; i < n_max && i < (int)nv.path_cap; i++) {
+  auto pot = [&](int ox, int oy) -> float { return potarr[stc + ox + oy * nx]; };
+  auto gradCell = [&](int qx, int qy) {  // NavFn tests the memo first: gradx[n] is read for whichever n the walker asks
+    const int n = stc + qx + qy * nx;
+    if (gradx[n] + grady[n] > 0.0) return;
+    float gx, gy;
+    if (cellGradient(pot, qx, qy, n, nx, ns, pot_nx1, (float)kCostObs, gx, gy)) {
+      gradx[n] = gx;
+      grady[n] = gy;
+    }
+  };
+  for (int i = 0; i < n_max && i < (int)nv.path_cap; i++) {  // (NavFn's walk stops at the buffer's end; GradientPath's counts on)
     const int nearest_point = max(0, min(nx * ny - 1, stc + (int)round((double)dx) + (int)(nx * round((double)dy))));
-    if (potarr[nearest_point] < (float)kCostNeutral) {
+    if (potarr[nearest_point] < (float)kCostNeutral) {  // NavFn's end test: a potential below COST_NEUTRAL is the goal's
       pathx[npath] = (float)goal0;
       pathy[npath] = (float)goal1;
       ++npath;
@@ -112,44 +87,23 @@ __device__ void navfnCalcPath(const NavfnDev& nv, uint32_t plan, const float* po
     pathx[npath] = (float)(stc % nx) + dx;
     pathy[npath] = (float)(stc / nx) + dy;
     npath++;
-    bool oscillation_detected = false;
-    if (npath > 2 && pathx[npath - 1] == pathx[npath - 3] && pathy[npath - 1] == pathy[npath - 3]) oscillation_detected = true;
-    const int stcnx = stc + nx, stcpx = stc - nx;
-    if (potarr[stc] >= kPotHigh || potarr[stc + 1] >= kPotHigh || potarr[stc - 1] >= kPotHigh || potarr[stcnx] >= kPotHigh ||
-        potarr[stcnx + 1] >= kPotHigh || potarr[stcnx - 1] >= kPotHigh || potarr[stcpx] >= kPotHigh || potarr[stcpx + 1] >= kPotHigh ||
-        potarr[stcpx - 1] >= kPotHigh || oscillation_detected) {
-      // potential-function boundary: follow the grid to the lowest of the eight neighbours (:893-925; minp is an int there)
-      int minc = stc;
-      int minp = truncX86(potarr[stc]);
-      const int nb[8] = {stcpx - 1, stcpx, stcpx + 1, stc - 1, stc + 1, stcnx - 1, stcnx, stcnx + 1};
-      for (int q = 0; q < 8; ++q)
-        if (potarr[nb[q]] < (float)minp) {
-          minp = (int)potarr[nb[q]];
-          minc = nb[q];
-        }
-      stc = minc;
+    const bool oscillation_detected = npath > 2 && pathx[npath - 1] == pathx[npath - 3] && pathy[npath - 1] == pathy[npath - 3];
+    if (highAmongNine(pot) || oscillation_detected) {
+      int mox, moy;
+      lowestOfEight(pot, mox, moy);
+      stc += mox + moy * nx;
       dx = 0;
       dy = 0;
       if (potarr[stc] >= kPotHigh) break;
     } else {
-      gradCell(stc);
-      gradCell(stc + 1);
-      gradCell(stcnx);
-      gradCell(stcnx + 1);
-      const float x1 = (float)((1.0 - dx) * gradx[stc] + dx * gradx[stc + 1]);
-      const float x2 = (float)((1.0 - dx) * gradx[stcnx] + dx * gradx[stcnx + 1]);
-      const float x = (float)((1.0 - dy) * x1 + dy * x2);
-      const float y1 = (float)((1.0 - dx) * grady[stc] + dx * grady[stc + 1]);
-      const float y2 = (float)((1.0 - dx) * grady[stcnx] + dx * grady[stcnx + 1]);
-      const float y = (float)((1.0 - dy) * y1 + dy * y2);
-      if (x == 0.0 && y == 0.0) break;  // zero gradient
-      const float ss = (float)(pathStep / hypot((double)x, (double)y));
-      dx += x * ss;
-      dy += y * ss;
-      if (dx > 1.0) { stc++; dx = (float)(dx - 1.0); }
-      if (dx < -1.0) { stc--; dx = (float)(dx + 1.0); }
-      if (dy > 1.0) { stc += nx; dy = (float)(dy - 1.0); }
-      if (dy < -1.0) { stc -= nx; dy = (float)(dy + 1.0); }
+      gradCell(0, 0);
+      gradCell(1, 0);
+      gradCell(0, 1);
+      gradCell(1, 1);
+      const int stcnx = stc + nx;
+      const float gx[4] = {gradx[stc], gradx[stc + 1], gradx[stcnx], gradx[stcnx + 1]};
+      const float gy[4] = {grady[stc], grady[stc + 1], grady[stcnx], grady[stcnx + 1]};
+      if (!gradientStep(gx, gy, nx, stc, dx, dy)) break;  // zero gradient
     }
   }
   navgpu_navfn_result r;
@@ -160,109 +114,56 @@ __device__ void navfnCalcPath(const NavfnDev& nv, uint32_t plan, const float* po
   nv.results[plan] = r;
 }
 
-__global__ __launch_bounds__(256) void k_navfn_plan(NavfnDev nv, uint32_t first, const int32_t* goals, const int32_t* starts, int astar,
-                                                    int at_start) {
-  const uint32_t plan = first + blockIdx.x;
-  const int nx = nv.nx, ny = nv.ny, ns = nv.ns;
-  uint8_t* costarr = nv.costarr + (size_t)plan * nv.ns_padded;
-  uint8_t* pending = nv.pending + (size_t)plan * nv.ns_padded;
-  float* potarr = nv.potarr + (size_t)plan * nv.ns_padded;
-  float* gradx = nv.gradx + (size_t)plan * nv.ns_padded;
-  float* grady = nv.grady + (size_t)plan * nv.ns_padded;
-  const int goal0 = goals[2 * blockIdx.x], goal1 = goals[2 * blockIdx.x + 1];
-  const int start0 = starts[2 * blockIdx.x], start1 = starts[2 * blockIdx.x + 1];
-  // ---- setupNavFn(keepit = true) (:379-440), all lanes
-  for (int i = threadIdx.x; i < ns; i += blockDim.x) {
-    potarr[i] = kPotHigh;
-    gradx[i] = 0.0f;
-    grady[i] = 0.0f;
-    pending[i] = 0;
+// setupNavFn(keepit = true) (:379-440), all lanes of the block
+__device__ __forceinline__ void navfnSetup(const NavfnDev& nv, uint32_t plan) {
+  const int nx = nv.nx, ny = nv.ny;
+  const size_t base = (size_t)plan * nv.ns_padded;
+  for (int i = threadIdx.x; i < nv.ns; i += blockDim.x) {
+    nv.potarr[base + i] = kPotHigh;
+    nv.gradx[base + i] = 0.0f;
+    nv.grady[base + i] = 0.0f;
+    nv.pending[base + i] = 0;
     const int y = i / nx, x = i - y * nx;
-    if (y == 0 || y == ny - 1 || x == 0 || x == nx - 1) costarr[i] = (uint8_t)kCostObs;  // outer bounds of the cost array
+    if (y == 0 || y == ny - 1 || x == 0 || x == nx - 1) nv.costarr[base + i] = (uint8_t)kCostObs;  // outer bounds of the cost array
   }
   __syncthreads();
-  if (threadIdx.x != 0) return;
+}
 
-  int* curP = nv.pb + (size_t)plan * 3 * kPriorityBufSize;
-  int* nextP = curP + kPriorityBufSize;
-  int* overP = nextP + kPriorityBufSize;
-  int curPe = 0, nextPe = 0, overPe = 0;
+// initCost (:445-453), then propNavFnDijkstra / propNavFnAstar over updateCell / updateCellAstar (:466-791), one lane: the cycles used
+__device__ int navfnPropagate(const NavfnDev& nv, uint32_t plan, int goal0, int goal1, int start0, int start1, int astar, int at_start) {
+  const int nx = nv.nx, ny = nv.ny;
+  const uint8_t* costarr = nv.costarr + (size_t)plan * nv.ns_padded;
+  float* potarr = nv.potarr + (size_t)plan * nv.ns_padded;
+  PriorityBuffers pb(nv.pb + (size_t)plan * 3 * kPriorityBufSize, nv.pending + (size_t)plan * nv.ns_padded, nv.ns);
   float curT = (float)kCostObs;
   const float priInc = 2 * kCostNeutral;
-  auto pushable = [&](int n) { return n >= 0 && n < ns && !pending[n] && costarr[n] < kCostObs; };
-  auto push_cur = [&](int n) {  // :367-375
-    if (pushable(n) && curPe < kPriorityBufSize) {
-      curP[curPe++] = n;
-      pending[n] = 1;
-    }
-  };
-  auto push_next = [&](int n) {
-    if (pushable(n) && nextPe < kPriorityBufSize) {
-      nextP[nextPe++] = n;
-      pending[n] = 1;
-    }
-  };
-  auto push_over = [&](int n) {
-    if (pushable(n) && overPe < kPriorityBufSize) {
-      overP[overPe++] = n;
-      pending[n] = 1;
-    }
-  };
-  {  // initCost(goal, 0) (:445-453)
+  auto pushable = [&](int n) { return costarr[n] < kCostObs; };
+  {
     const int k = goal0 + goal1 * nx;
     potarr[k] = 0.0f;
-    push_cur(k + 1);
-    push_cur(k - 1);
-    push_cur(k - nx);
-    push_cur(k + nx);
+    pb.pushCur(k + 1, pushable);
+    pb.pushCur(k - 1, pushable);
+    pb.pushCur(k - nx, pushable);
+    pb.pushCur(k + nx, pushable);
   }
-  // ---- updateCell / updateCellAstar (:466-620)
   auto updateCell = [&](int n) {
     const float l = potarr[n - 1], r = potarr[n + 1], u = potarr[n - nx], d = potarr[n + nx];
-    float ta, tc;
-    if (l < r) tc = l; else tc = r;
-    if (u < d) ta = u; else ta = d;
-    if (costarr[n] < kCostObs) {  // don't propagate into obstacles
-      const float hf = (float)costarr[n];
-      float dc = tc - ta;
-      if (dc < 0) {
-        dc = -dc;
-        ta = tc;
+    if (costarr[n] >= kCostObs) return;  // don't propagate into obstacles
+    float pot = interpolatePotential(l < r ? l : r, u < d ? u : d, (float)costarr[n]);
+    if (pot < potarr[n]) {
+      const float le = (float)(0.707106781 * (float)costarr[n - 1]);
+      const float re = (float)(0.707106781 * (float)costarr[n + 1]);
+      const float ue = (float)(0.707106781 * (float)costarr[n - nx]);
+      const float de = (float)(0.707106781 * (float)costarr[n + nx]);
+      potarr[n] = pot;
+      if (astar) {  // updateCellAstar adds the distance to the start AFTER the store: only the threshold and push tests see it
+        const int x = n % nx, y = n / nx;
+        const float dist = (float)(hypot((double)(x - start0), (double)(y - start1)) * (float)kCostNeutral);
+        pot += dist;
       }
-      float pot;
-      if (dc >= hf)
-        pot = ta + hf;
-      else {  // two-neighbour interpolation; the polynomial's literals are doubles
-        const float dd = dc / hf;
-        const float v = (float)(-0.2301 * dd * dd + 0.5307 * dd + 0.7040);
-        pot = ta + hf * v;
-      }
-      if (pot < potarr[n]) {
-        const float le = (float)(0.707106781 * (float)costarr[n - 1]);
-        const float re = (float)(0.707106781 * (float)costarr[n + 1]);
-        const float ue = (float)(0.707106781 * (float)costarr[n - nx]);
-        const float de = (float)(0.707106781 * (float)costarr[n + nx]);
-        potarr[n] = pot;
-        if (astar) {
-          const int x = n % nx, y = n / nx;
-          const float dist = (float)(hypot((double)(x - start0), (double)(y - start1)) * (float)kCostNeutral);
-          pot += dist;
-        }
-        if (pot < curT) {  // low-cost buffer block
-          if (l > pot + le) push_next(n - 1);
-          if (r > pot + re) push_next(n + 1);
-          if (u > pot + ue) push_next(n - nx);
-          if (d > pot + de) push_next(n + nx);
-        } else {  // overflow block
-          if (l > pot + le) push_over(n - 1);
-          if (r > pot + re) push_over(n + 1);
-          if (u > pot + ue) push_over(n - nx);
-          if (d > pot + de) push_over(n + nx);
-        }
-      }
+      pb.pushNeighbours(pot < curT, n, nx, pot, l, r, u, d, le, re, ue, de, pushable);
     }
   };
-  // ---- propNavFnDijkstra / propNavFnAstar (:633-791)
   const int cycles = max(nx * ny / 20, nx + ny);
   int cycle = 0;
   if (astar) {
@@ -271,26 +172,25 @@ __global__ __launch_bounds__(256) void k_navfn_plan(NavfnDev nv, uint32_t first,
   }
   const int startCell = start1 * nx + start0;
   for (; cycle < cycles; cycle++) {
-    if (curPe == 0 && nextPe == 0) break;
-    for (int i = 0; i < curPe; i++) pending[curP[i]] = 0;
-    for (int i = 0; i < curPe; i++) updateCell(curP[i]);
-    curPe = nextPe;
-    nextPe = 0;
-    int* pb = curP;
-    curP = nextP;
-    nextP = pb;
-    if (curPe == 0) {
-      curT += priInc;
-      curPe = overPe;
-      overPe = 0;
-      pb = curP;
-      curP = overP;
-      overP = pb;
-    }
-    if (astar || at_start)
+    if (pb.cur_end == 0 && pb.next_end == 0) break;
+    pb.beginBlock();
+    for (int i = 0; i < pb.cur_end; i++) updateCell(pb.cur[i]);
+    pb.endBlock(curT, priInc);
+    if (astar || at_start)  // (NavFn stops at the start cell only when asked to; DijkstraExpansion always stops at its goal)
       if (potarr[startCell] < kPotHigh) break;
   }
-  navfnCalcPath(nv, plan, potarr, goal0, goal1, start0, start1, astar ? nx * 4 : nx * ny / 2, cycle);
+  return cycle;
+}
+
+__global__ __launch_bounds__(256) void k_navfn_plan(NavfnDev nv, uint32_t first, const int32_t* goals, const int32_t* starts, int astar,
+                                                    int at_start) {
+  const uint32_t plan = first + blockIdx.x;
+  const int goal0 = goals[2 * blockIdx.x], goal1 = goals[2 * blockIdx.x + 1];
+  const int start0 = starts[2 * blockIdx.x], start1 = starts[2 * blockIdx.x + 1];
+  navfnSetup(nv, plan);
+  if (threadIdx.x != 0) return;
+  const int cycle = navfnPropagate(nv, plan, goal0, goal1, start0, start1, astar, at_start);
+  navfnCalcPath(nv, plan, nv.potarr + (size_t)plan * nv.ns_padded, goal0, goal1, start0, start1, astar ? nv.nx * 4 : nv.nx * nv.ny / 2, cycle);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -322,13 +222,8 @@ constexpr uint32_t kWfCopy = 1u, kWfCompute = 2u;
 // (dijkstra.cpp:178-185)
 __device__ __forceinline__ float wfCellCost(const NavfnWfRule& rule, uint8_t cost) {
   if (!rule.global_planner) return cost < kCostObs ? (float)cost : -1.0f;
-  float c = cost;
-  if (c < rule.lethal_cost - 1 || (rule.allow_unknown && c == 255)) {
-    c = c * rule.cost_factor + rule.neutral_cost;
-    if (c >= rule.lethal_cost) c = rule.lethal_cost - 1;
-    return (float)(uint8_t)c;
-  }
-  return -1.0f;
+  float c;
+  return gpTraversableCost(cost, rule.lethal_cost, rule.neutral_cost, rule.cost_factor, rule.allow_unknown != 0, c) ? (float)(uint8_t)c : -1.0f;
 }
 
 // the arrays a search starts from: POT_HIGH everywhere but the seeds (navfn: the goal, 0 - setupNavFn + initCost :379-453;
@@ -454,27 +349,12 @@ __global__ __launch_bounds__(kWfThreads) void k_navfn_wf_round(NavfnDev nv, uint
           const int q = 2 * colour + k;
           const float hf = hf4[q];
           const float l = sP[row + 1][col], r = sP[row + 1][col + 2], u = sP[row][col + 1], d = sP[row + 2][col + 1];
-          float ta, tc;
-          if (l < r) tc = l; else tc = r;
-          if (u < d) ta = u; else ta = d;
-          if (tc == seen_h[q] && ta == seen_v[q]) continue;
+          const float tc = l < r ? l : r, ta = u < d ? u : d;
+          if (tc == seen_h[q] && ta == seen_v[q]) continue;  // (a cell whose two minima have not moved: the rules below give what they gave)
           seen_h[q] = tc;
           seen_v[q] = ta;
-          float dc = tc - ta;
-          if (dc < 0) {
-            dc = -dc;
-            ta = tc;
-          }
-          float pot;
-          if (!rule.quadratic)  // PotentialCalculator::calculatePotential (potential_calculator.h:50-59)
-            pot = fminf(fminf(l, r), fminf(u, d)) + hf;
-          else if (dc >= hf)
-            pot = ta + hf;
-          else {  // (hf > 0 here: 0 <= dc < hf)
-            const float dd = dc / hf;
-            const float v = (float)(-0.2301 * dd * dd + 0.5307 * dd + 0.7040);
-            pot = ta + hf * v;
-          }
+          // PotentialCalculator::calculatePotential (potential_calculator.h:50-59), or the interpolation; hf >= 0 is tested after
+          const float pot = !rule.quadratic ? fminf(fminf(l, r), fminf(u, d)) + hf : interpolatePotential(tc, ta, hf);
           if (hf >= 0.0f && pot < sP[row + 1][col + 1]) {
             sP[row + 1][col + 1] = pot;
             changed = 1;
@@ -559,7 +439,6 @@ __global__ __launch_bounds__(64) void k_navfn_wf_path(NavfnDev nv, uint32_t firs
   const float pot_nx1 = potarr[nx + 1];  // gradCell's `potarr[nx + 1]` (:1020, as written in the reference)
   int wx0 = 0, wy0 = 0;
   bool have_win = false;
-  const float pathStep = 0.5f;
   int stc = startCell, npath = 0, found = 0;
   float dx = 0, dy = 0;
   float px1 = 0, py1 = 0, px2 = 0, py2 = 0;  // the two points before the last one (oscillation test)
@@ -607,69 +486,21 @@ __global__ __launch_bounds__(64) void k_navfn_wf_path(NavfnDev nv, uint32_t firs
     const int l9 = lane < 9 ? lane : 0;
     const bool high9 = lane < 9 && P(l9 % 3 - 1, l9 / 3 - 1) >= kPotHigh;
     if (__ballot(high9) != 0ull || oscillation_detected) {
-      // potential-function boundary: follow the grid to the lowest of the eight neighbours (:893-925; minp is an int there)
-      int mox = 0, moy = 0;
-      int minp = truncX86(P(0, 0));
-      const int ox[8] = {-1, 0, 1, -1, 1, -1, 0, 1}, oy[8] = {-1, -1, -1, 0, 0, 1, 1, 1};
-      for (int q = 0; q < 8; ++q) {
-        const float v = P(ox[q], oy[q]);
-        if (v < (float)minp) {
-          minp = (int)v;
-          mox = ox[q];
-          moy = oy[q];
-        }
-      }
+      int mox, moy;
+      lowestOfEight(P, mox, moy);
       const float pm = P(mox, moy);
       stc += mox + moy * nx;
       dx = 0;
       dy = 0;
       if (pm >= kPotHigh) break;
     } else {
-      // gradCell (:1001-1056) of stc, stc + 1, stc + nx, stc + nx + 1 on lanes 0..3
+      // gradCell of stc, stc + 1, stc + nx, stc + nx + 1 on lanes 0..3 (no memo: it only saves recomputation)
       const int q = lane & 3, qx = q & 1, qy = q >> 1;
-      const int n = stc + qx + qy * nx;
-      float gx = 0.0f, gy = 0.0f;
-      if (!(n < nx || n > ns - nx)) {
-        const float cv = P(qx, qy);
-        float ddx = 0.0f, ddy = 0.0f;
-        if (cv >= kPotHigh) {
-          if (P(qx - 1, qy) < kPotHigh)
-            ddx = -kCostObs;
-          else if (P(qx + 1, qy) < kPotHigh)
-            ddx = kCostObs;
-          if (P(qx, qy - 1) < kPotHigh)
-            ddy = -kCostObs;
-          else if (pot_nx1 < kPotHigh)
-            ddy = kCostObs;
-        } else {
-          if (P(qx - 1, qy) < kPotHigh) ddx += P(qx - 1, qy) - cv;
-          if (P(qx + 1, qy) < kPotHigh) ddx += cv - P(qx + 1, qy);
-          if (P(qx, qy - 1) < kPotHigh) ddy += P(qx, qy - 1) - cv;
-          if (P(qx, qy + 1) < kPotHigh) ddy += cv - P(qx, qy + 1);
-        }
-        float norm = (float)hypot((double)ddx, (double)ddy);
-        if (norm > 0) {
-          norm = (float)(1.0 / norm);
-          gx = norm * ddx;
-          gy = norm * ddy;
-        }
-      }
-      const float gx0 = __shfl(gx, 0), gx1 = __shfl(gx, 1), gx2 = __shfl(gx, 2), gx3 = __shfl(gx, 3);
-      const float gy0 = __shfl(gy, 0), gy1 = __shfl(gy, 1), gy2 = __shfl(gy, 2), gy3 = __shfl(gy, 3);
-      const float x1 = (float)((1.0 - dx) * gx0 + dx * gx1);
-      const float x2 = (float)((1.0 - dx) * gx2 + dx * gx3);
-      const float x = (float)((1.0 - dy) * x1 + dy * x2);
-      const float y1 = (float)((1.0 - dx) * gy0 + dx * gy1);
-      const float y2 = (float)((1.0 - dx) * gy2 + dx * gy3);
-      const float y = (float)((1.0 - dy) * y1 + dy * y2);
-      if (x == 0.0 && y == 0.0) break;  // zero gradient
-      const float ss = (float)(pathStep / hypot((double)x, (double)y));
-      dx += x * ss;
-      dy += y * ss;
-      if (dx > 1.0) { stc++; dx = (float)(dx - 1.0); }
-      if (dx < -1.0) { stc--; dx = (float)(dx + 1.0); }
-      if (dy > 1.0) { stc += nx; dy = (float)(dy - 1.0); }
-      if (dy < -1.0) { stc -= nx; dy = (float)(dy + 1.0); }
+      float gx, gy;
+      cellGradient(P, qx, qy, stc + qx + qy * nx, nx, ns, pot_nx1, (float)kCostObs, gx, gy);
+      const float gxs[4] = {__shfl(gx, 0), __shfl(gx, 1), __shfl(gx, 2), __shfl(gx, 3)};
+      const float gys[4] = {__shfl(gy, 0), __shfl(gy, 1), __shfl(gy, 2), __shfl(gy, 3)};
+      if (!gradientStep(gxs, gys, nx, stc, dx, dy)) break;  // zero gradient
     }
   }
   if (lane == 0) {
@@ -697,387 +528,331 @@ struct GpHeapEntry {  // astar.h:47-55 Index
   int i;
   float cost;
 };
-// WAVEFRONT: the expansion has already run as a tiled wavefront (k_navfn_wf_round with the global_planner rule) and left its
-// potentials in `wf_potential`, its round count in `wf_rounds`; what remains is makePlan's tail - found_legal, clearEndpoint,
-// the traceback - on one lane, the same code as the reference-order kernel's.
-template <bool WAVEFRONT>
-__device__ __forceinline__ void gpPlanBody(const NavfnDev& nv, uint32_t first, const navgpu_global_planner_params& gp, const double* starts,
-                                           const double* goals, const int32_t* goal_cells, GpHeapEntry* heaps, float* wf_potential, int wf_rounds) {
-  const uint32_t plan = first + blockIdx.x;
-  const int nx = nv.nx, ny = nv.ny, ns = nv.ns;
-  uint8_t* costs = nv.costarr + (size_t)plan * nv.ns_padded;
-  uint8_t* pending = nv.pending + (size_t)plan * nv.ns_padded;
-  float* potential = WAVEFRONT ? wf_potential : nv.potarr + (size_t)plan * nv.ns_padded;
-  float* gradx = nv.gradx + (size_t)plan * nv.ns_padded;
-  float* grady = nv.grady + (size_t)plan * nv.ns_padded;
-  float* pathx = nv.path + (size_t)plan * 2 * nv.path_cap;
-  float* pathy = pathx + nv.path_cap;
-  const double start_x = starts[2 * blockIdx.x], start_y = starts[2 * blockIdx.x + 1];
-  const double goal_x = goals[2 * blockIdx.x], goal_y = goals[2 * blockIdx.x + 1];
-  const int lethal = gp.lethal_cost, neutral = gp.neutral_cost;
-  const float factor = gp.cost_factor;
-  const bool unknown = gp.allow_unknown != 0, quadratic = gp.use_quadratic != 0;
-  constexpr float kHigh = 1.0e10f;
-  // all lanes: the arrays every expansion starts from, and GlobalPlanner::outlineMap
-  if (!WAVEFRONT) {
-    for (int i = threadIdx.x; i < ns; i += blockDim.x) {
-      potential[i] = kHigh;
-      gradx[i] = 0.0f;
-      grady[i] = 0.0f;
-      pending[i] = 0;
-      const int y = i / nx, x = i - y * nx;
-      if (gp.outline_map && (y == 0 || y == ny - 1 || x == 0 || x == nx - 1)) costs[i] = 254;  // costmap_2d::LETHAL_OBSTACLE
-    }
-    __syncthreads();
-  }
-  (void)ny;
-  (void)pending;
-  if (threadIdx.x != 0) return;
 
-  // A border cell can enter the expansion when nothing outlines the map (gp.outline_map == 0) or when the outline's 254 is
-  // below lethal_cost (A* with lethal_cost 255).  The reference then reads potential[n - nx] / costs[n + nx] outside its
-  // arrays (harmless garbage on the CPU heap); here every neighbour access goes through potAt() / getCost(), which give
-  // an off-array cell the values of an unreached lethal one.  In-array reads are unchanged, bit for bit.
-  auto potAt = [&](int n) -> float { return (n >= 0 && n < ns) ? potential[n] : kHigh; };
-  auto calculatePotential = [&](uint8_t cost, int n, float prev_potential) -> float {
-    if (!quadratic) {
-      if (prev_potential < 0) {
-        const float min_h = fminf(potAt(n - 1), potAt(n + 1)), min_v = fminf(potAt(n - nx), potAt(n + nx));
-        prev_potential = fminf(min_h, min_v);
-      }
-      return prev_potential + cost;
-    }
+// One plan as the stages below see it: its arrays, its end points and the cost / potential rules its parameters select.
+// A border cell can enter the expansion when nothing outlines the map (outline_map == 0) or when the outline's 254 is
+// below lethal_cost (A* with lethal_cost 255).  The reference then reads potential[n - nx] / costs[n + nx] outside its
+// arrays (harmless garbage on the CPU heap); here every neighbour access goes through potAt() / getCost(), which give
+// an off-array cell the values of an unreached lethal one.  In-array reads are unchanged, bit for bit.
+struct GpPlan {
+  int nx, ny, ns;
+  uint8_t *costs, *pending;
+  float *potential, *gradx, *grady;
+  double start_x, start_y, goal_x, goal_y;
+  int lethal, neutral;
+  float factor;
+  bool unknown, quadratic;
+  __device__ __forceinline__ int startCell() const { return (int)start_x + nx * (int)start_y; }
+  __device__ __forceinline__ int endCell() const { return (int)goal_x + nx * (int)goal_y; }
+  __device__ __forceinline__ int maxCycles() const { return nx * ny * 2; }
+  __device__ __forceinline__ float potAt(int n) const { return (n >= 0 && n < ns) ? potential[n] : kPotHigh; }
+  __device__ __forceinline__ float getCost(int n) const {  // DijkstraExpansion::getCost: what is not traversable costs lethal_cost
+    float c;
+    return (n >= 0 && n < ns && gpTraversableCost(costs[n], lethal, neutral, factor, unknown, c)) ? c : (float)lethal;
+  }
+  // PotentialCalculator / QuadraticCalculator::calculatePotential (potential_calculator.h:50-59, quadratic_calculator.cpp:41-77)
+  __device__ __forceinline__ float calculatePotential(uint8_t cost, int n, float prev_potential) const {
+    if (!quadratic && !(prev_potential < 0)) return prev_potential + cost;
     const float l = potAt(n - 1), r = potAt(n + 1), u = potAt(n - nx), d = potAt(n + nx);
-    float ta, tc;
-    if (l < r) tc = l; else tc = r;
-    if (u < d) ta = u; else ta = d;
-    const float hf = cost;
-    float dc = tc - ta;
-    if (dc < 0) {
-      dc = -dc;
-      ta = tc;
-    }
-    if (dc >= hf) return ta + hf;
-    const float dd = dc / hf;
-    const float v = (float)(-0.2301 * dd * dd + 0.5307 * dd + 0.7040);
-    return ta + hf * v;
-  };
-  auto getCost = [&](int n) -> float {
-    if (n < 0 || n >= ns) return lethal;
-    float c = costs[n];
-    if (c < lethal - 1 || (unknown && c == 255)) {
-      c = c * factor + neutral;
-      if (c >= lethal) c = lethal - 1;
-      return c;
-    }
-    return lethal;
-  };
-  const int cycles = nx * ny * 2;
-  int cycle = 0;
-  bool found_legal = false;
-  const int endCell = (int)goal_x + nx * (int)goal_y;
-  if (WAVEFRONT) {
-    cycle = wf_rounds;
-    found_legal = potential[endCell] < kHigh;  // the reference leaves its loop through `break` exactly when the goal cell has a potential
-  } else if (gp.use_dijkstra) {
-    int* cur = nv.pb + (size_t)plan * 3 * kPriorityBufSize;
-    int* nxt = cur + kPriorityBufSize;
-    int* ovr = nxt + kPriorityBufSize;
-    int curE = 0, nxtE = 0, ovrE = 0;
-    float threshold = lethal;
-    const float priorityIncrement = 2 * neutral;
-    auto push = [&](int* buf, int& end, int n) {
-      if (n >= 0 && n < ns && !pending[n] && getCost(n) < lethal && end < kPriorityBufSize) {
-        buf[end++] = n;
-        pending[n] = 1;
-      }
-    };
-    const int k = (int)start_x + nx * (int)start_y;
-    if (!gp.old_navfn_behavior) {  // setPreciseStart(true) (planner_core.cpp:124-127)
-      double dx = start_x - (int)start_x, dy = start_y - (int)start_y;
-      dx = floorf((float)(dx * 100 + 0.5)) / 100;
-      dy = floorf((float)(dy * 100 + 0.5)) / 100;
-      potential[k] = (float)(neutral * 2 * dx * dy);
-      potential[k + 1] = (float)(neutral * 2 * (1 - dx) * dy);
-      potential[k + nx] = (float)(neutral * 2 * dx * (1 - dy));
-      potential[k + nx + 1] = (float)(neutral * 2 * (1 - dx) * (1 - dy));
-      push(cur, curE, k + 2);
-      push(cur, curE, k - 1);
-      push(cur, curE, k + nx - 1);
-      push(cur, curE, k + nx + 2);
-      push(cur, curE, k - nx);
-      push(cur, curE, k - nx + 1);
-      push(cur, curE, k + nx * 2);
-      push(cur, curE, k + nx * 2 + 1);
-    } else {
-      potential[k] = 0;
-      push(cur, curE, k + 1);
-      push(cur, curE, k - 1);
-      push(cur, curE, k - nx);
-      push(cur, curE, k + nx);
-    }
-    bool ran_dry = false;
-    for (; cycle < cycles; cycle++) {
-      if (curE == 0 && nxtE == 0) {
-        ran_dry = true;
-        break;
-      }
-      for (int i = 0; i < curE; i++) pending[cur[i]] = 0;
-      for (int i = 0; i < curE; i++) {  // updateCell
-        const int n = cur[i];
-        const float c = getCost(n);
-        if (c >= lethal) continue;
-        const float pot = calculatePotential((uint8_t)c, n, -1.0f);
-        if (pot < potential[n]) {
-          const float le = (float)(0.707106781 * (float)getCost(n - 1));
-          const float re = (float)(0.707106781 * (float)getCost(n + 1));
-          const float ue = (float)(0.707106781 * (float)getCost(n - nx));
-          const float de = (float)(0.707106781 * (float)getCost(n + nx));
-          potential[n] = pot;
-          if (pot < threshold) {
-            if (potAt(n - 1) > pot + le) push(nxt, nxtE, n - 1);
-            if (potAt(n + 1) > pot + re) push(nxt, nxtE, n + 1);
-            if (potAt(n - nx) > pot + ue) push(nxt, nxtE, n - nx);
-            if (potAt(n + nx) > pot + de) push(nxt, nxtE, n + nx);
-          } else {
-            if (potAt(n - 1) > pot + le) push(ovr, ovrE, n - 1);
-            if (potAt(n + 1) > pot + re) push(ovr, ovrE, n + 1);
-            if (potAt(n - nx) > pot + ue) push(ovr, ovrE, n - nx);
-            if (potAt(n + nx) > pot + de) push(ovr, ovrE, n + nx);
-          }
-        }
-      }
-      curE = nxtE;
-      nxtE = 0;
-      int* t = cur;
-      cur = nxt;
-      nxt = t;
-      if (curE == 0) {
-        threshold += priorityIncrement;
-        curE = ovrE;
-        ovrE = 0;
-        t = cur;
-        cur = ovr;
-        ovr = t;
-      }
-      if (potential[endCell] < kHigh) break;
-    }
-    found_legal = !ran_dry && cycle < cycles;
+    if (quadratic) return interpolatePotential(l < r ? l : r, u < d ? u : d, cost);
+    return fminf(fminf(l, r), fminf(u, d)) + cost;
+  }
+};
+__device__ __forceinline__ GpPlan gpPlanOf(const NavfnDev& nv, uint32_t plan, const navgpu_global_planner_params& gp, const double* starts,
+                                           const double* goals, float* potential) {
+  const size_t base = (size_t)plan * nv.ns_padded;
+  GpPlan p;
+  p.nx = nv.nx, p.ny = nv.ny, p.ns = nv.ns;
+  p.costs = nv.costarr + base, p.pending = nv.pending + base;
+  p.potential = potential, p.gradx = nv.gradx + base, p.grady = nv.grady + base;
+  p.start_x = starts[2 * blockIdx.x], p.start_y = starts[2 * blockIdx.x + 1];
+  p.goal_x = goals[2 * blockIdx.x], p.goal_y = goals[2 * blockIdx.x + 1];
+  p.lethal = gp.lethal_cost, p.neutral = gp.neutral_cost, p.factor = gp.cost_factor;
+  p.unknown = gp.allow_unknown != 0, p.quadratic = gp.use_quadratic != 0;
+  return p;
+}
+
+// all lanes: the arrays every expansion starts from, and GlobalPlanner::outlineMap (planner_core.cpp:62-76)
+__device__ __forceinline__ void gpSetup(const GpPlan& p, bool outline_map) {
+  for (int i = threadIdx.x; i < p.ns; i += blockDim.x) {
+    p.potential[i] = kPotHigh;
+    p.gradx[i] = 0.0f;
+    p.grady[i] = 0.0f;
+    p.pending[i] = 0;
+    const int y = i / p.nx, x = i - y * p.nx;
+    if (outline_map && (y == 0 || y == p.ny - 1 || x == 0 || x == p.nx - 1)) p.costs[i] = 254;  // costmap_2d::LETHAL_OBSTACLE
+  }
+  __syncthreads();
+}
+
+// DijkstraExpansion::calculatePotentials / updateCell (dijkstra.cpp:71-229), one lane: whether a legal potential was found
+__device__ bool gpDijkstra(const GpPlan& p, int* buffers, bool precise_start, int& cycle) {
+  const int nx = p.nx, lethal = p.lethal;
+  float* potential = p.potential;
+  PriorityBuffers pb(buffers, p.pending, p.ns);
+  float threshold = lethal;
+  const float priorityIncrement = 2 * p.neutral;
+  auto pushable = [&](int n) { return p.getCost(n) < lethal; };
+  const int k = p.startCell();
+  if (precise_start) {  // setPreciseStart(true) (planner_core.cpp:124-127)
+    int cells[4];
+    float vals[4];
+    preciseStartSeeds(p.start_x, p.start_y, nx, p.neutral, cells, vals);
+    const int around[8] = {k + 2, k - 1, k + nx - 1, k + nx + 2, k - nx, k - nx + 1, k + nx * 2, k + nx * 2 + 1};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) potential[cells[i]] = vals[i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pb.pushCur(around[i], pushable);
   } else {
-    GpHeapEntry* heap = heaps + (size_t)plan * nv.ns_padded;
-    long len = 0;
-    auto pushHeap = [&](long hole, const GpHeapEntry value) {  // std::__push_heap with greater1: parent.cost > value.cost moves down
-      long parent = (hole - 1) / 2;
-      while (hole > 0 && heap[parent].cost > value.cost) {
-        heap[hole] = heap[parent];
-        hole = parent;
-        parent = (hole - 1) / 2;
-      }
-      heap[hole] = value;
-    };
-    const int start_i = (int)start_x + nx * (int)start_y;
-    heap[len++] = GpHeapEntry{start_i, 0.0f};  // queue_.push_back(Index(start_i, 0)) - no push_heap on the first element
-    potential[start_i] = 0;
-    const int ex = (int)goal_x, ey = (int)goal_y;
-    auto add = [&](float prev_potential, int next_i) {
-      if (next_i < 0 || next_i >= ns) return;
-      if (potential[next_i] < kHigh) return;
-      if (costs[next_i] >= lethal && !(unknown && costs[next_i] == 255)) return;
-      potential[next_i] = calculatePotential((uint8_t)(costs[next_i] + neutral), next_i, prev_potential);
-      const int x = next_i % nx, y = next_i / nx;
-      const float distance = (float)(abs(ex - x) + abs(ey - y));
-      pushHeap(len, GpHeapEntry{next_i, potential[next_i] + distance * neutral});
-      ++len;
-    };
-    while (len > 0 && cycle < cycles) {
-      const GpHeapEntry top = heap[0];
-      if (len > 1) {  // std::pop_heap: __adjust_heap(first, 0, len - 1, value = last element)
-        const GpHeapEntry value = heap[len - 1];
-        const long l = len - 1;
-        long hole = 0, child = 0;
-        while (child < (l - 1) / 2) {
-          child = 2 * (child + 1);
-          if (heap[child].cost > heap[child - 1].cost) child--;
-          heap[hole] = heap[child];
-          hole = child;
-        }
-        if ((l & 1) == 0 && child == (l - 2) / 2) {
-          child = 2 * (child + 1);
-          heap[hole] = heap[child - 1];
-          hole = child - 1;
-        }
-        pushHeap(hole, value);
-      }
-      --len;
-      const int i = top.i;
-      if (i == endCell) {
-        found_legal = true;
-        break;
-      }
-      add(potential[i], i + 1);
-      add(potential[i], i - 1);
-      add(potential[i], i + nx);
-      add(potential[i], i - nx);
-      cycle++;
+    potential[k] = 0;
+    pb.pushCur(k + 1, pushable);
+    pb.pushCur(k - 1, pushable);
+    pb.pushCur(k - nx, pushable);
+    pb.pushCur(k + nx, pushable);
+  }
+  const int cycles = p.maxCycles(), endCell = p.endCell();
+  bool ran_dry = false;
+  for (; cycle < cycles; cycle++) {
+    if (pb.cur_end == 0 && pb.next_end == 0) {
+      ran_dry = true;
+      break;
     }
-  }
-  if (!gp.old_navfn_behavior) {  // Expander::clearEndpoint(costs, potential, goal_x_i, goal_y_i, 2) (expander.h:76-89)
-    const int startCell = goal_cells[2 * blockIdx.x] + nx * goal_cells[2 * blockIdx.x + 1];
-    for (int i = -2; i <= 2; i++)
-      for (int j = -2; j <= 2; j++) {
-        const int n = startCell + i + nx * j;
-        if (n < nx + 1 || n >= ns - nx - 1) continue;  // (the reference reads outside its arrays for a goal this close to the border)
-        if (potential[n] < kHigh) continue;
-        const float c = (float)(costs[n] + neutral);
-        potential[n] = calculatePotential((uint8_t)c, n, -1.0f);
+    pb.beginBlock();
+    for (int i = 0; i < pb.cur_end; i++) {  // updateCell
+      const int n = pb.cur[i];
+      const float c = p.getCost(n);
+      if (c >= lethal) continue;
+      const float pot = p.calculatePotential((uint8_t)c, n, -1.0f);
+      if (pot < potential[n]) {
+        const float le = (float)(0.707106781 * (float)p.getCost(n - 1));
+        const float re = (float)(0.707106781 * (float)p.getCost(n + 1));
+        const float ue = (float)(0.707106781 * (float)p.getCost(n - nx));
+        const float de = (float)(0.707106781 * (float)p.getCost(n + nx));
+        potential[n] = pot;
+        pb.pushNeighbours(pot < threshold, n, nx, pot, p.potAt(n - 1), p.potAt(n + 1), p.potAt(n - nx), p.potAt(n + nx), le, re, ue, de, pushable);
       }
+    }
+    pb.endBlock(threshold, priorityIncrement);
+    if (potential[endCell] < kPotHigh) break;  // (always, where NavFn stops only when asked to; a dry run is told apart above)
   }
-  // ---- traceback (only when a legal potential was found, planner_core.cpp:303-311)
-  int npath = 0, found = 0;
-  float last3x[3] = {0, 0, 0}, last3y[3] = {0, 0, 0};  // the path's last three points (all of it may not fit the buffer)
-  auto pushPoint = [&](float x, float y) {
-    if (npath < (int)nv.path_cap) {
-      pathx[npath] = x;
-      pathy[npath] = y;
+  return !ran_dry && cycle < cycles;
+}
+
+// AStarExpansion::calculatePotentials / add (astar.cpp:46-95: std::push_heap / pop_heap with greater1), one lane
+__device__ bool gpAstar(const GpPlan& p, GpHeapEntry* heap, int& cycle) {
+  const int nx = p.nx, ns = p.ns, lethal = p.lethal, neutral = p.neutral;
+  float* potential = p.potential;
+  const uint8_t* costs = p.costs;
+  long len = 0;
+  auto pushHeap = [&](long hole, const GpHeapEntry value) {  // std::__push_heap with greater1: parent.cost > value.cost moves down
+    long parent = (hole - 1) / 2;
+    while (hole > 0 && heap[parent].cost > value.cost) {
+      heap[hole] = heap[parent];
+      hole = parent;
+      parent = (hole - 1) / 2;
+    }
+    heap[hole] = value;
+  };
+  const int start_i = p.startCell(), endCell = p.endCell(), cycles = p.maxCycles();
+  heap[len++] = GpHeapEntry{start_i, 0.0f};  // queue_.push_back(Index(start_i, 0)) - no push_heap on the first element
+  potential[start_i] = 0;
+  const int ex = (int)p.goal_x, ey = (int)p.goal_y;
+  auto add = [&](float prev_potential, int next_i) {
+    if (next_i < 0 || next_i >= ns) return;
+    if (potential[next_i] < kPotHigh) return;
+    if (costs[next_i] >= lethal && !(p.unknown && costs[next_i] == 255)) return;
+    potential[next_i] = p.calculatePotential((uint8_t)(costs[next_i] + neutral), next_i, prev_potential);
+    const int x = next_i % nx, y = next_i / nx;
+    const float distance = (float)(abs(ex - x) + abs(ey - y));
+    pushHeap(len, GpHeapEntry{next_i, potential[next_i] + distance * neutral});
+    ++len;
+  };
+  while (len > 0 && cycle < cycles) {
+    const GpHeapEntry top = heap[0];
+    if (len > 1) {  // std::pop_heap: __adjust_heap(first, 0, len - 1, value = last element)
+      const GpHeapEntry value = heap[len - 1];
+      const long l = len - 1;
+      long hole = 0, child = 0;
+      while (child < (l - 1) / 2) {
+        child = 2 * (child + 1);
+        if (heap[child].cost > heap[child - 1].cost) child--;
+        heap[hole] = heap[child];
+        hole = child;
+      }
+      if ((l & 1) == 0 && child == (l - 2) / 2) {
+        child = 2 * (child + 1);
+        heap[hole] = heap[child - 1];
+        hole = child - 1;
+      }
+      pushHeap(hole, value);
+    }
+    --len;
+    const int i = top.i;
+    if (i == endCell) return true;
+    add(potential[i], i + 1);
+    add(potential[i], i - 1);
+    add(potential[i], i + nx);
+    add(potential[i], i - nx);
+    cycle++;
+  }
+  return false;
+}
+
+// Expander::clearEndpoint(costs, potential, goal_x_i, goal_y_i, 2) (expander.h:76-89)
+__device__ void gpClearEndpoint(const GpPlan& p, int goal_cell) {
+  for (int i = -2; i <= 2; i++)
+    for (int j = -2; j <= 2; j++) {
+      const int n = goal_cell + i + p.nx * j;
+      if (n < p.nx + 1 || n >= p.ns - p.nx - 1) continue;  // (the reference reads outside its arrays for a goal this close to the border)
+      if (p.potential[n] < kPotHigh) continue;
+      const float c = (float)(p.costs[n] + p.neutral);
+      p.potential[n] = p.calculatePotential((uint8_t)c, n, -1.0f);
+    }
+}
+
+// the traceback's points: every one counted, those that fit the buffer stored, the last three kept (all of it may not fit)
+struct GpPathOut {
+  float *x, *y;
+  int cap, n = 0;
+  float last3x[3] = {0, 0, 0}, last3y[3] = {0, 0, 0};
+  __device__ __forceinline__ void push(float px, float py) {
+    if (n < cap) {
+      x[n] = px;
+      y[n] = py;
     }
     last3x[0] = last3x[1];
     last3y[0] = last3y[1];
     last3x[1] = last3x[2];
     last3y[1] = last3y[2];
-    last3x[2] = x;
-    last3y[2] = y;
-    ++npath;
-  };
-  if (found_legal && !gp.use_grid_path) {  // GradientPath::getPath (gradient_path.cpp:68-248)
-    auto gradCell = [&](int n) {
-      if (n < nx || n > nx * ny - nx) return;  // (the reference tests this second: its gradx_[n] read may lie past the array)
-      if (gradx[n] + grady[n] > 0.0) return;
-      const float cv = potential[n];
-      float dx = 0.0f, dy = 0.0f;
-      if (cv >= kHigh) {
-        if (potential[n - 1] < kHigh)
-          dx = -lethal;
-        else if (potential[n + 1] < kHigh)
-          dx = lethal;
-        if (potential[n - nx] < kHigh)
-          dy = -lethal;
-        else if (potential[nx + 1] < kHigh)  // as written in the reference (:287)
-          dy = lethal;
-      } else {
-        if (potential[n - 1] < kHigh) dx += potential[n - 1] - cv;
-        if (potential[n + 1] < kHigh) dx += cv - potential[n + 1];
-        if (potential[n - nx] < kHigh) dy += potential[n - nx] - cv;
-        if (potAt(n + nx) < kHigh) dy += cv - potAt(n + nx);  // (n = ns - nx passes the test above)
-      }
-      float norm = (float)hypot((double)dx, (double)dy);
-      if (norm > 0) {
-        norm = (float)(1.0 / norm);
-        gradx[n] = norm * dx;
-        grady[n] = norm * dy;
-      }
-    };
-    int stc = (int)goal_x + nx * (int)goal_y;
-    float dx = (float)(goal_x - (int)goal_x), dy = (float)(goal_y - (int)goal_y);
-    const long lim = (long)ns * 4;
-    long c = 0;
-    while (c++ < lim) {
-      const double px = stc % nx + dx, py = stc / nx + dy;
-      if (fabs(px - start_x) < .5 && fabs(py - start_y) < .5) {
-        pushPoint((float)start_x, (float)start_y);
-        found = 1;
-        break;
-      }
-      if (stc < nx || stc > nx * ny - nx) break;
-      pushPoint((float)px, (float)py);
-      const bool oscillation_detected = npath > 2 && last3x[2] == last3x[0] && last3y[2] == last3y[0];
-      const int stcnx = stc + nx, stcpx = stc - nx;
-      if (potential[stc] >= kHigh || potAt(stc + 1) >= kHigh || potAt(stc - 1) >= kHigh || potAt(stcnx) >= kHigh ||
-          potAt(stcnx + 1) >= kHigh || potAt(stcnx - 1) >= kHigh || potAt(stcpx) >= kHigh || potAt(stcpx + 1) >= kHigh ||
-          potAt(stcpx - 1) >= kHigh || oscillation_detected) {
-        int minc = stc;
-        int minp = truncX86(potential[stc]);
-        const int nb[8] = {stcpx - 1, stcpx, stcpx + 1, stc - 1, stc + 1, stcnx - 1, stcnx, stcnx + 1};
-        for (int q = 0; q < 8; ++q)
-          if (potAt(nb[q]) < (float)minp) {
-            minp = (int)potAt(nb[q]);
-            minc = nb[q];
-          }
-        stc = minc;
-        dx = 0;
-        dy = 0;
-        if (potential[stc] >= kHigh) break;
-      } else {
-        gradCell(stc);
-        gradCell(stc + 1);
-        gradCell(stcnx);
-        gradCell(stcnx + 1);
-        auto gAt = [&](const float* g, int n) -> float { return n < ns ? g[n] : 0.0f; };  // (stc on the last row: the reference reads past its arrays)
-        const float x1 = (float)((1.0 - dx) * gradx[stc] + dx * gAt(gradx, stc + 1));
-        const float x2 = (float)((1.0 - dx) * gAt(gradx, stcnx) + dx * gAt(gradx, stcnx + 1));
-        const float x = (float)((1.0 - dy) * x1 + dy * x2);
-        const float y1 = (float)((1.0 - dx) * grady[stc] + dx * gAt(grady, stc + 1));
-        const float y2 = (float)((1.0 - dx) * gAt(grady, stcnx) + dx * gAt(grady, stcnx + 1));
-        const float y = (float)((1.0 - dy) * y1 + dy * y2);
-        if (x == 0.0 && y == 0.0) break;
-        const float ss = (float)(0.5f / hypot((double)x, (double)y));  // pathStep_ = 0.5 (:47)
-        dx += x * ss;
-        dy += y * ss;
-        if (dx > 1.0) { stc++; dx = (float)(dx - 1.0); }
-        if (dx < -1.0) { stc--; dx = (float)(dx + 1.0); }
-        if (dy > 1.0) { stc += nx; dy = (float)(dy - 1.0); }
-        if (dy < -1.0) { stc -= nx; dy = (float)(dy + 1.0); }
-      }
+    last3x[2] = px;
+    last3y[2] = py;
+    ++n;
+  }
+};
+
+// GradientPath::getPath / gradCell (gradient_path.cpp:68-313), one lane, from the goal down to the start: 1 = arrived
+__device__ int gpGradientPath(const GpPlan& p, GpPathOut& out) {
+  const int nx = p.nx, ns = p.ns;
+  const float *potential = p.potential;
+  float *gradx = p.gradx, *grady = p.grady;
+  const float pot_nx1 = potential[nx + 1];
+  int stc = p.endCell();
+  float dx = (float)(p.goal_x - (int)p.goal_x), dy = (float)(p.goal_y - (int)p.goal_y);
+  auto pot = [&](int ox, int oy) -> float { return p.potAt(stc + ox + oy * nx); };
+  auto gradCell = [&](int qx, int qy) {  // GradientPath tests the memo second (its gradx_[n] read may lie past the array; never here)
+    const int n = stc + qx + qy * nx;
+    if (n < nx || n > ns - nx) return;
+    if (gradx[n] + grady[n] > 0.0) return;
+    float gx, gy;
+    if (cellGradient(pot, qx, qy, n, nx, ns, pot_nx1, (float)p.lethal, gx, gy)) {
+      gradx[n] = gx;
+      grady[n] = gy;
     }
-  } else if (found_legal) {  // GridPath::getPath (grid_path.cpp:44-82)
-    float cx = (float)goal_x, cy = (float)goal_y;
-    const int start_index = (int)start_x + nx * (int)start_y;
-    pushPoint(cx, cy);
-    long c = 0;
-    found = 1;
-    while ((int)cx + nx * (int)cy != start_index) {
-      float min_val = 1e10f;
-      int min_x = 0, min_y = 0;
-      for (int xd = -1; xd <= 1; xd++)
-        for (int yd = -1; yd <= 1; yd++) {
-          if (xd == 0 && yd == 0) continue;
-          const int x = (int)(cx + xd), y = (int)(cy + yd);
-          const int index = x + nx * y;
-          if (index < 0 || index >= ns) continue;  // (the reference reads outside its array here)
-          if (potential[index] < min_val) {
-            min_val = potential[index];
-            min_x = x;
-            min_y = y;
-          }
-        }
-      if (min_x == 0 && min_y == 0) {
-        found = 0;
-        break;
-      }
-      cx = (float)min_x;
-      cy = (float)min_y;
-      pushPoint(cx, cy);
-      if (c++ > (long)ns * 4) {
-        found = 0;
-        break;
-      }
+  };
+  auto gAt = [&](const float* g, int n) -> float { return n < ns ? g[n] : 0.0f; };  // (stc on the last row: the reference reads past its arrays)
+  const long lim = (long)ns * 4;
+  long c = 0;
+  while (c++ < lim) {
+    const double px = stc % nx + dx, py = stc / nx + dy;
+    if (fabs(px - p.start_x) < .5 && fabs(py - p.start_y) < .5) {  // (in double, against the start itself, where NavFn looks at a potential)
+      out.push((float)p.start_x, (float)p.start_y);
+      return 1;
+    }
+    if (stc < nx || stc > ns - nx) break;
+    out.push((float)px, (float)py);
+    const bool oscillation_detected = out.n > 2 && out.last3x[2] == out.last3x[0] && out.last3y[2] == out.last3y[0];
+    if (highAmongNine(pot) || oscillation_detected) {
+      int mox, moy;
+      lowestOfEight(pot, mox, moy);
+      stc += mox + moy * nx;
+      dx = 0;
+      dy = 0;
+      if (potential[stc] >= kPotHigh) break;
+    } else {
+      gradCell(0, 0);
+      gradCell(1, 0);
+      gradCell(0, 1);
+      gradCell(1, 1);
+      const int stcnx = stc + nx;
+      const float gx[4] = {gradx[stc], gAt(gradx, stc + 1), gAt(gradx, stcnx), gAt(gradx, stcnx + 1)};
+      const float gy[4] = {grady[stc], gAt(grady, stc + 1), gAt(grady, stcnx), gAt(grady, stcnx + 1)};
+      if (!gradientStep(gx, gy, nx, stc, dx, dy)) break;
     }
   }
+  return 0;
+}
+
+// GridPath::getPath (grid_path.cpp:44-82), one lane: 1 = arrived
+__device__ int gpGridPath(const GpPlan& p, GpPathOut& out) {
+  const int nx = p.nx, ns = p.ns;
+  float cx = (float)p.goal_x, cy = (float)p.goal_y;
+  const int start_index = p.startCell();
+  out.push(cx, cy);
+  long c = 0;
+  while ((int)cx + nx * (int)cy != start_index) {
+    float min_val = 1e10f;
+    int min_x = 0, min_y = 0;
+    for (int xd = -1; xd <= 1; xd++)
+      for (int yd = -1; yd <= 1; yd++) {
+        if (xd == 0 && yd == 0) continue;
+        const int x = (int)(cx + xd), y = (int)(cy + yd);
+        const int index = x + nx * y;
+        if (index < 0 || index >= ns) continue;  // (the reference reads outside its array here)
+        if (p.potential[index] < min_val) {
+          min_val = p.potential[index];
+          min_x = x;
+          min_y = y;
+        }
+      }
+    if (min_x == 0 && min_y == 0) return 0;
+    cx = (float)min_x;
+    cy = (float)min_y;
+    out.push(cx, cy);
+    if (c++ > (long)ns * 4) return 0;
+  }
+  return 1;
+}
+
+// makePlan's tail (planner_core.cpp:299-311), one lane: clearEndpoint, the traceback - only when a legal potential was found -
+// and the result record
+__device__ void gpFinish(const NavfnDev& nv, uint32_t plan, const GpPlan& p, const navgpu_global_planner_params& gp, const int32_t* goal_cells,
+                         bool found_legal, int cycle) {
+  if (!gp.old_navfn_behavior) gpClearEndpoint(p, goal_cells[2 * blockIdx.x] + p.nx * goal_cells[2 * blockIdx.x + 1]);
+  GpPathOut out;
+  out.x = nv.path + (size_t)plan * 2 * nv.path_cap;
+  out.y = out.x + nv.path_cap;
+  out.cap = (int)nv.path_cap;
+  int found = 0;
+  if (found_legal) found = gp.use_grid_path ? gpGridPath(p, out) : gpGradientPath(p, out);
   navgpu_navfn_result r;
-  r.found = (found && npath <= (int)nv.path_cap) ? 1 : 0;
-  r.path_length = r.found ? npath : 0;
+  r.found = (found && out.n <= out.cap) ? 1 : 0;
+  r.path_length = r.found ? out.n : 0;
   r.cycles = cycle;
-  r.start_potential = potential[endCell];
+  r.start_potential = p.potential[p.endCell()];
   nv.results[plan] = r;
 }
+
 __global__ __launch_bounds__(256) void k_gp_plan(NavfnDev nv, uint32_t first, navgpu_global_planner_params gp, const double* starts, const double* goals,
                                                  const int32_t* goal_cells, GpHeapEntry* heaps) {
-  gpPlanBody<false>(nv, first, gp, starts, goals, goal_cells, heaps, nullptr, 0);
+  const uint32_t plan = first + blockIdx.x;
+  const GpPlan p = gpPlanOf(nv, plan, gp, starts, goals, nv.potarr + (size_t)plan * nv.ns_padded);
+  gpSetup(p, gp.outline_map != 0);
+  if (threadIdx.x != 0) return;
+  int cycle = 0;
+  const bool found_legal = gp.use_dijkstra ? gpDijkstra(p, nv.pb + (size_t)plan * 3 * kPriorityBufSize, !gp.old_navfn_behavior, cycle)
+                                           : gpAstar(p, heaps + (size_t)plan * nv.ns_padded, cycle);
+  gpFinish(nv, plan, p, gp, goal_cells, found_legal, cycle);
 }
+// The expansion has already run as a tiled wavefront (k_navfn_wf_round with the global_planner rule): what remains is makePlan's
+// tail on one lane, the stages the reference-order kernel ends with.  The reference leaves its loop through `break` exactly when
+// the goal cell has a potential.
 __global__ __launch_bounds__(64) void k_gp_wf_finish(NavfnDev nv, uint32_t first, navgpu_global_planner_params gp, const double* starts, const double* goals,
                                                      const int32_t* goal_cells) {
   const uint32_t plan = first + blockIdx.x;
+  if (threadIdx.x != 0) return;
   const NavfnWfStatus st = nv.wf_status[plan];
-  gpPlanBody<true>(nv, first, gp, starts, goals, goal_cells, nullptr, (st.final_array ? nv.potalt : nv.potarr) + (size_t)plan * nv.ns_padded, st.rounds);
+  const GpPlan p = gpPlanOf(nv, plan, gp, starts, goals, (st.final_array ? nv.potalt : nv.potarr) + (size_t)plan * nv.ns_padded);
+  gpFinish(nv, plan, p, gp, goal_cells, p.potential[p.endCell()] < kPotHigh, st.rounds);
 }
 
 void launch_navfn_costmap(const NavfnDev& nv, uint32_t first, uint32_t count, const uint8_t* cmap, size_t stride, int cost_mode, int allow_unknown,

@@ -1,4 +1,5 @@
 // navgpu_navfn_*: host side of the navfn::NavFn batch (see navfn_kernels.hip and include/navgpu.h).
+#include "navfn_rules.h"
 #include "navgpu_fleet.h"
 
 struct navgpu_navfn {
@@ -73,7 +74,7 @@ int navgpu_navfn_create(uint32_t nx, uint32_t ny, uint32_t n_plans, int32_t devi
   A(nv.potarr, (size_t)n_plans * nv.ns_padded);
   A(nv.gradx, (size_t)n_plans * nv.ns_padded);
   A(nv.grady, (size_t)n_plans * nv.ns_padded);
-  A(nv.pb, (size_t)n_plans * 3 * 10000);
+  A(nv.pb, (size_t)n_plans * 3 * kPriorityBufSize);
   A(nv.path, (size_t)n_plans * 2 * nv.path_cap);
   A(nv.results, n_plans);
   A(h->d_cmap, (size_t)n_plans * nv.ns_padded);
@@ -105,6 +106,31 @@ int navgpu_navfn_destroy(navgpu_navfn* h) {
 
 static bool navfnRange(const navgpu_navfn* h, uint32_t first, uint32_t count) { return count > 0 && first < h->n && count <= h->n - first; }
 
+// NavFn's goal and start cells of a call: checked (the reference indexes its arrays with these without a check: keep them inside the
+// border) and uploaded
+static int navfnEndpoints(navgpu_navfn* h, const char* call, uint32_t count, const int32_t* goals, const int32_t* starts) {
+  const NavfnDev& nv = h->nv;
+  for (uint32_t k = 0; k < count; ++k) {
+    const int32_t* g = goals + 2 * k;
+    const int32_t* s = starts + 2 * k;
+    if (g[0] < 1 || g[1] < 1 || g[0] > nv.nx - 2 || g[1] > nv.ny - 2 || s[0] < 0 || s[1] < 0 || s[0] >= nv.nx || s[1] >= nv.ny) {
+      g_last_error = std::string(call) + ": goal / start cell outside the map";
+      return NAVGPU_ERR_INVALID;
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(h->d_goal, goals, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_start, starts, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
+  return NAVGPU_OK;
+}
+
+// the end of every plan call: the result records back, to the caller too, and the launches' own errors
+static int finishPlans(navgpu_navfn* h, uint32_t first, uint32_t count, navgpu_navfn_result* results) {
+  HIP_TRY(hipMemcpyAsync(h->h_results + first, h->nv.results + first, sizeof(navgpu_navfn_result) * count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  if (results) memcpy(results, h->h_results + first, sizeof(navgpu_navfn_result) * count);
+  return checkLaunch();
+}
+
 int navgpu_navfn_set_costmap(navgpu_navfn* h, uint32_t first, uint32_t count, const uint8_t* cmap, int32_t shared, int32_t cost_mode,
                              int32_t allow_unknown) {
   if (!h || !cmap || !navfnRange(h, first, count) || cost_mode < 0 || cost_mode > 2) return NAVGPU_ERR_INVALID;
@@ -133,23 +159,11 @@ int navgpu_navfn_plan(navgpu_navfn* h, uint32_t first, uint32_t count, const int
                       navgpu_navfn_result* results) {
   if (!h || !goals || !starts || !navfnRange(h, first, count)) return NAVGPU_ERR_INVALID;
   NavfnGuard guard_(h);
-  const NavfnDev& nv = h->nv;
-  for (uint32_t k = 0; k < count; ++k) {  // the reference indexes its arrays with these without a check: keep them inside the border
-    const int32_t* g = goals + 2 * k;
-    const int32_t* s = starts + 2 * k;
-    if (g[0] < 1 || g[1] < 1 || g[0] > nv.nx - 2 || g[1] > nv.ny - 2 || s[0] < 0 || s[1] < 0 || s[0] >= nv.nx || s[1] >= nv.ny) {
-      g_last_error = "navgpu_navfn_plan: goal / start cell outside the map";
-      return NAVGPU_ERR_INVALID;
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_goal, goals, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_start, starts, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  launch_navfn_plan(nv, first, count, h->d_goal, h->d_start, astar ? 1 : 0, at_start ? 1 : 0, h->stream);
+  int rc = navfnEndpoints(h, "navgpu_navfn_plan", count, goals, starts);
+  if (rc) return rc;
+  launch_navfn_plan(h->nv, first, count, h->d_goal, h->d_start, astar ? 1 : 0, at_start ? 1 : 0, h->stream);
   std::fill(h->final_array.begin() + first, h->final_array.begin() + first + count, (uint8_t)0);
-  HIP_TRY(hipMemcpyAsync(h->h_results + first, nv.results + first, sizeof(navgpu_navfn_result) * count, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(waitStream(h->stream));
-  if (results) memcpy(results, h->h_results + first, sizeof(navgpu_navfn_result) * count);
-  return checkLaunch();
+  return finishPlans(h, first, count, results);
 }
 
 // The expansion as a tiled wavefront (navfn_kernels.hip: k_navfn_wf_*): rounds are queued a batch at a time, the per-plan
@@ -215,33 +229,25 @@ int navgpu_navfn_plan_wavefront(navgpu_navfn* h, uint32_t first, uint32_t count,
   if (!h || !goals || !starts || !navfnRange(h, first, count)) return NAVGPU_ERR_INVALID;
   NavfnGuard guard_(h);
   NavfnDev& nv = h->nv;
+  int rc = navfnEndpoints(h, "navgpu_navfn_plan_wavefront", count, goals, starts);
+  if (rc) return rc;
   std::vector<int32_t> seed_cells((size_t)count * 4, -1), stop(count);
   std::vector<float> seed_vals((size_t)count * 4, 0.0f);
   for (uint32_t k = 0; k < count; ++k) {
-    const int32_t* g = goals + 2 * k;
-    const int32_t* s = starts + 2 * k;
-    if (g[0] < 1 || g[1] < 1 || g[0] > nv.nx - 2 || g[1] > nv.ny - 2 || s[0] < 0 || s[1] < 0 || s[0] >= nv.nx || s[1] >= nv.ny) {
-      g_last_error = "navgpu_navfn_plan_wavefront: goal / start cell outside the map";
-      return NAVGPU_ERR_INVALID;
-    }
-    seed_cells[4 * k] = g[0] + g[1] * nv.nx;  // initCost(goal, 0)
-    stop[k] = s[0] + s[1] * nv.nx;
+    seed_cells[4 * k] = goals[2 * k] + goals[2 * k + 1] * nv.nx;  // initCost(goal, 0)
+    stop[k] = starts[2 * k] + starts[2 * k + 1] * nv.nx;
   }
   NavfnWfRule rule{};
   rule.quadratic = 1;
   rule.outline = 1;
-  HIP_TRY(hipMemcpyAsync(h->d_goal, goals, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_start, starts, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  int rc = runWavefront(h, first, count, rule, seed_cells.data(), seed_vals.data(), stop.data(), at_start);
+  rc = runWavefront(h, first, count, rule, seed_cells.data(), seed_vals.data(), stop.data(), at_start);
   if (rc) return rc;
   launch_navfn_wf_path(nv, first, count, h->d_goal, h->d_start, h->stream);
-  HIP_TRY(hipMemcpyAsync(h->h_results + first, nv.results + first, sizeof(navgpu_navfn_result) * count, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(waitStream(h->stream));
-  if (results) memcpy(results, h->h_results + first, sizeof(navgpu_navfn_result) * count);
-  return checkLaunch();
+  return finishPlans(h, first, count, results);
 }
 
-static int gpValidate(const navgpu_navfn* h, uint32_t count, const navgpu_global_planner_params* gp, const double* starts, const double* goals,
+// global_planner's end points of a call: checked, then uploaded (starts and goals into the two halves of d_xy, goal cells into d_goal)
+static int gpEndpoints(navgpu_navfn* h, uint32_t count, const navgpu_global_planner_params* gp, const double* starts, const double* goals,
                       const int32_t* goal_cells) {
   const NavfnDev& nv = h->nv;
   if (gp->lethal_cost < 2 || gp->lethal_cost > 255 || gp->neutral_cost < 0 || gp->neutral_cost > 255) return NAVGPU_ERR_INVALID;
@@ -254,6 +260,9 @@ static int gpValidate(const navgpu_navfn* h, uint32_t count, const navgpu_global
       return NAVGPU_ERR_INVALID;
     }
   }
+  HIP_TRY(hipMemcpyAsync(h->d_xy, starts, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_xy + (size_t)2 * h->n, goals, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_goal, goal_cells, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
   return NAVGPU_OK;
 }
 
@@ -267,27 +276,20 @@ int navgpu_global_planner_plan_wavefront(navgpu_navfn* h, uint32_t first, uint32
     g_last_error = "navgpu_global_planner_plan_wavefront: AStarExpansion has no fixed-point reading; use navgpu_global_planner_plan";
     return NAVGPU_ERR_INVALID;
   }
-  int rc = gpValidate(h, count, gp, starts, goals, goal_cells);
+  int rc = gpEndpoints(h, count, gp, starts, goals, goal_cells);
   if (rc) return rc;
   NavfnDev& nv = h->nv;
   std::vector<int32_t> seed_cells((size_t)count * 4, -1), stop(count);
   std::vector<float> seed_vals((size_t)count * 4, 0.0f);
   for (uint32_t q = 0; q < count; ++q) {
-    const double start_x = starts[2 * q], start_y = starts[2 * q + 1];
-    const int k = (int)start_x + nv.nx * (int)start_y;  // toIndex(double, double)
-    if (!gp->old_navfn_behavior) {                      // setPreciseStart(true) (planner_core.cpp:124-127, dijkstra.cpp:88-103)
-      double dx = start_x - (int)start_x, dy = start_y - (int)start_y;
-      dx = floorf((float)(dx * 100 + 0.5)) / 100;
-      dy = floorf((float)(dy * 100 + 0.5)) / 100;
-      const int cells[4] = {k, k + 1, k + nv.nx, k + nv.nx + 1};
-      const float vals[4] = {(float)(gp->neutral_cost * 2 * dx * dy), (float)(gp->neutral_cost * 2 * (1 - dx) * dy),
-                             (float)(gp->neutral_cost * 2 * dx * (1 - dy)), (float)(gp->neutral_cost * 2 * (1 - dx) * (1 - dy))};
-      for (int i = 0; i < 4; ++i) {
-        seed_cells[4 * q + i] = cells[i];
-        seed_vals[4 * q + i] = vals[i];
-      }
+    if (!gp->old_navfn_behavior) {  // setPreciseStart(true)
+      int cells[4];
+      float vals[4];
+      preciseStartSeeds(starts[2 * q], starts[2 * q + 1], nv.nx, gp->neutral_cost, cells, vals);
+      std::copy(cells, cells + 4, seed_cells.begin() + 4 * q);
+      std::copy(vals, vals + 4, seed_vals.begin() + 4 * q);
     } else {
-      seed_cells[4 * q] = k;
+      seed_cells[4 * q] = (int)starts[2 * q] + nv.nx * (int)starts[2 * q + 1];  // toIndex(double, double)
     }
     stop[q] = (int)goals[2 * q] + nv.nx * (int)goals[2 * q + 1];
   }
@@ -299,16 +301,10 @@ int navgpu_global_planner_plan_wavefront(navgpu_navfn* h, uint32_t first, uint32
   rule.lethal_cost = gp->lethal_cost;
   rule.neutral_cost = gp->neutral_cost;
   rule.cost_factor = gp->cost_factor;
-  HIP_TRY(hipMemcpyAsync(h->d_xy, starts, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_xy + (size_t)2 * h->n, goals, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_goal, goal_cells, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
   rc = runWavefront(h, first, count, rule, seed_cells.data(), seed_vals.data(), stop.data(), 1);
   if (rc) return rc;
   launch_gp_wf_finish(nv, first, count, *gp, h->d_xy, h->d_xy + (size_t)2 * h->n, h->d_goal, h->stream);
-  HIP_TRY(hipMemcpyAsync(h->h_results + first, nv.results + first, sizeof(navgpu_navfn_result) * count, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(waitStream(h->stream));
-  if (results) memcpy(results, h->h_results + first, sizeof(navgpu_navfn_result) * count);
-  return checkLaunch();
+  return finishPlans(h, first, count, results);
 }
 
 int navgpu_global_planner_plan(navgpu_navfn* h, uint32_t first, uint32_t count, const navgpu_global_planner_params* gp, const double* starts,
@@ -316,25 +312,17 @@ int navgpu_global_planner_plan(navgpu_navfn* h, uint32_t first, uint32_t count, 
   if (!h || !gp || !starts || !goals || !goal_cells || !navfnRange(h, first, count)) return NAVGPU_ERR_INVALID;
   NavfnGuard guard_(h);
   const NavfnDev& nv = h->nv;
-  {
-    int rc = gpValidate(h, count, gp, starts, goals, goal_cells);
-    if (rc) return rc;
-  }
+  int rc = gpEndpoints(h, count, gp, starts, goals, goal_cells);
+  if (rc) return rc;
   if (!gp->use_dijkstra && !h->d_heap) {
     uint64_t* q = nullptr;  // 8 bytes per entry (int index, float cost); a cell enters the queue at most once
-    int rc = h->alloc(&q, (size_t)h->n * nv.ns_padded);
+    rc = h->alloc(&q, (size_t)h->n * nv.ns_padded);
     if (rc) return rc;
     h->d_heap = q;
   }
-  HIP_TRY(hipMemcpyAsync(h->d_xy, starts, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_xy + (size_t)2 * h->n, goals, sizeof(double) * 2 * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_goal, goal_cells, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, h->stream));
   launch_gp_plan(nv, first, count, *gp, h->d_xy, h->d_xy + (size_t)2 * h->n, h->d_goal, h->d_heap, h->stream);
   std::fill(h->final_array.begin() + first, h->final_array.begin() + first + count, (uint8_t)0);
-  HIP_TRY(hipMemcpyAsync(h->h_results + first, nv.results + first, sizeof(navgpu_navfn_result) * count, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(waitStream(h->stream));
-  if (results) memcpy(results, h->h_results + first, sizeof(navgpu_navfn_result) * count);
-  return checkLaunch();
+  return finishPlans(h, first, count, results);
 }
 
 int navgpu_navfn_path(navgpu_navfn* h, uint32_t plan, float* xy, uint32_t cap) {

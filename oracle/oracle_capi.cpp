@@ -788,6 +788,22 @@ int orc_navfn_fixed_point(const uint8_t* cmap, int nx, int ny, int cost_mode, in
   }
   return len;
 }
+// NavFn::calcPath(nx * ny / 2) alone over a potential array handed in (zeroed gradient arrays): the checker of the HIP path's
+// wave-wide walk, which must give these points bit for bit on the array it walked.  Returns the path length (0 = none).
+int orc_navfn_calc_path(const float* potarr, int nx, int ny, const int* goal, const int* start, float* path_xy, int path_cap) {
+  NavFnOracle nav(nx, ny);
+  memcpy(nav.potarr.data(), potarr, sizeof(float) * (size_t)nx * ny);
+  nav.goal[0] = goal[0];
+  nav.goal[1] = goal[1];
+  nav.start[0] = start[0];
+  nav.start[1] = start[1];
+  const int len = nav.calcPath(nx * ny / 2);
+  for (int i = 0; i < len && i < path_cap && path_xy; ++i) {
+    path_xy[2 * i] = nav.pathx[i];
+    path_xy[2 * i + 1] = nav.pathy[i];
+  }
+  return len;
+}
 // ------------------------------------------------------------------ global_planner (second half)
 // params = {use_dijkstra, use_quadratic, use_grid_path, old_navfn_behavior, allow_unknown, lethal_cost, neutral_cost, outline_map,
 //           fixed_point (1: the Dijkstra rule's fixed point instead of the reference-order expansion - the wavefront mode's checker)}

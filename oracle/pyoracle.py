@@ -164,6 +164,7 @@ def lib():
     sig("orc_global_planner_plan", i, u8p, i, i, i32p, C.c_float, f64p, f64p, i32p, C.c_void_p, C.c_void_p, i, C.POINTER(i), C.POINTER(i))
     sig("orc_navfn_plan", i, u8p, i, i, i, i, i32p, i32p, i, i, C.c_void_p, C.c_void_p, i, C.POINTER(i))
     sig("orc_navfn_fixed_point", i, u8p, i, i, i, i, i32p, i32p, C.c_void_p, C.c_void_p, i)
+    sig("orc_navfn_calc_path", i, f32p, i, i, i32p, i32p, C.c_void_p, i)
     sig("orc_bench_dwa", d, u, u, d, u8p, u, C.POINTER(DwaConfig), f32p, f32p, f64p, u, f64p, f64p, u, u, u,
         C.POINTER(C.c_uint64))
     sig("orc_bench_inflate", d, u8p, u, u, u, d, d, d, d, u, u)
@@ -591,6 +592,17 @@ def navfn_fixed_point(cmap, goal, start, cost_mode=1, allow_unknown=True):
     n = lib().orc_navfn_fixed_point(g, nx, ny, cost_mode, int(allow_unknown), np.ascontiguousarray(goal, np.int32), np.ascontiguousarray(start, np.int32),
                                     pot.ctypes.data, path.ctypes.data, cap)
     return path[:n].copy(), pot
+
+
+def navfn_calc_path(potarr, goal, start):
+    """NavFn::calcPath(nx * ny / 2) over the given potential array (ny, nx) float32, gradients zeroed: path (n, 2) float32."""
+    pot = np.ascontiguousarray(potarr, np.float32)
+    ny, nx = pot.shape
+    cap = nx * ny // 2 + 4
+    path = np.zeros((cap, 2), np.float32)
+    n = lib().orc_navfn_calc_path(pot.reshape(-1), nx, ny, np.ascontiguousarray(goal, np.int32), np.ascontiguousarray(start, np.int32),
+                                  path.ctypes.data, cap)
+    return path[:n].copy()
 
 
 GP_DEFAULTS = dict(use_dijkstra=1, use_quadratic=1, use_grid_path=0, old_navfn_behavior=0, allow_unknown=1, lethal_cost=253, neutral_cost=50,

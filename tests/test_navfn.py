@@ -435,6 +435,58 @@ def test_navfn_wavefront_tile_edges_and_small_maps(orc):
         nf.close()
 
 
+def _wf_path_cases():
+    """(costmap, goal, start) of test_navfn_wavefront_path_is_calcpath_of_its_array."""
+    cases = []
+    cm = np.zeros((70, 70), np.uint8)        # a walk longer than the 64-cell LDS window: the window is reloaded
+    cases.append((cm, (60, 8), (5, 60)))
+    cm = np.zeros((70, 70), np.uint8)        # round a wall's end: grid steps next to its POT_HIGH cells
+    cm[35, 0:55] = 254
+    cases.append((cm, (5, 8), (5, 60)))
+    cm = np.zeros((9, 9), np.uint8)          # the window hangs off the map on every side
+    cases.append((cm, (2, 2), (6, 6)))
+    cm = np.zeros((33, 65), np.uint8)        # the map of the tile-edge test
+    cm[16, 5:60] = 254
+    cases.append((cm, (10, 5), (60, 28)))
+    return cases
+
+
+def _wf_path_conditions(paths):
+    """What keeps the pin from passing vacuously, over the ORACLE's paths of the cases above."""
+    assert all(len(p) > 0 for p in paths)                                   # every case finds a path
+    frac = [(p != np.floor(p)).any(axis=1) for p in paths]
+    assert any(f.any() for f in frac)                                       # a gradient step somewhere
+    assert any((~f[1:-1]).any() for f in frac)                              # a grid step somewhere: an integral interior point
+    assert paths[0][:, 0].max() - paths[0][:, 0].min() > 40                 # the first walk leaves its first window
+
+
+def test_oracle_wavefront_path_cases_meet_their_conditions(orc):
+    """The conditions of the pin below, on the fixed point's own paths: no GPU needed to see that the cases are not vacuous."""
+    _wf_path_conditions([orc.navfn_fixed_point(cm, goal, start, cost_mode=1)[0] for cm, goal, start in _wf_path_cases()])
+
+
+@pytest.mark.gpu
+def test_navfn_wavefront_path_is_calcpath_of_its_array(orc):
+    """k_navfn_wf_path (one wave, LDS window, ballot, four-lane gradCell) gives NavFn::calcPath's points bit for bit: the oracle's
+    calcPath over exactly the potential array the wavefront left."""
+    import navigation_amd as nav
+    expected = []
+    for cm, goal, start in _wf_path_cases():
+        ny, nx = cm.shape
+        nf = nav.NavFn(nx, ny, 1)
+        nf.set_costmap(cm, cost_mode=1)
+        res = nf.plan_wavefront([goal], [start])
+        want = orc.navfn_calc_path(nf.potential(0), goal, start)
+        got = nf.path(0)
+        nf.close()
+        expected.append(want)
+        assert bool(res[0].found) == (len(want) > 0) and res[0].path_length == len(want), (cm.shape, res[0].path_length, len(want))
+        assert got.shape == want.shape
+        diff = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=1))[0]
+        assert diff.size == 0, f"{cm.shape}: first differing point {diff[0]}: {got[diff[0]]} != {want[diff[0]]}"
+    _wf_path_conditions(expected)
+
+
 # ------------------------------------------------------------------------------------------------ global_planner, tiled wavefront
 GP_WF_VARIANTS = [dict(), dict(use_quadratic=0), dict(use_grid_path=1), dict(old_navfn_behavior=1), dict(allow_unknown=0, cost_factor=0.55, neutral_cost=66)]
 
