@@ -258,7 +258,9 @@ int navgpu_layer_reset_bounding_box(navgpu_fleet* fleet, uint32_t first, uint32_
 /* ------------------------------------------------------------------------------------------ */
 /* replaces: StaticLayer::incomingMap (plugins/static_layer.cpp:167-228): occupancy is the
  * nav_msgs/OccupancyGrid int8 data of one map, interpreted with interpretValue (:149-163) on the
- * device and broadcast to [first, first+count). */
+ * device and broadcast to [first, first+count).  The interpreted bytes are per instance; use_maximum is ONE setting of the
+ * fleet (unlike the reference, where every costmap owns its StaticLayer): the value of the latest call, here or in
+ * navgpu_static_set_rolling_map, holds for every robot from the next update on, whatever range that call named. */
 int navgpu_static_set_map(navgpu_fleet* fleet, uint32_t first, uint32_t count, const int8_t* occupancy,
                           int32_t track_unknown_space, int32_t use_maximum, int32_t trinary_costmap,
                           int32_t lethal_cost_threshold, int32_t unknown_cost_value);
@@ -741,6 +743,9 @@ int navgpu_navfn_plan_wavefront(navgpu_navfn* nav, uint32_t first, uint32_t coun
 int navgpu_navfn_path(navgpu_navfn* nav, uint32_t plan, float* xy, uint32_t capacity_points);
 /* NavFn::potarr of one plan (ny x nx floats, POT_HIGH = 1e10 where unassigned) */
 int navgpu_navfn_potential(navgpu_navfn* nav, uint32_t plan, float* potarr);
+/* NavFn::costarr of one plan (ny x nx bytes): what the last navgpu_navfn_set_costmap / _from_fleet wrote for it.  A plan call
+ * afterwards outlines the array's border with COST_OBS, as NavFn::setupNavFn does (navfn.cpp:412-425). */
+int navgpu_navfn_costarr(navgpu_navfn* nav, uint32_t plan, uint8_t* costarr);
 
 /* global_planner::GlobalPlanner's expansion and traceback on the same arrays (the other half of SURVEY 8 f-4).
  * Parameters as planner_core.cpp:105-152 reads them and GlobalPlanner.cfg sets them. */

@@ -369,6 +369,7 @@ SYMBOLS = [
     ("navgpu_global_planner_plan_wavefront", C.c_int, [vp, u32, u32, C.POINTER(GlobalPlannerParams), vp, vp, vp, vp]),
     ("navgpu_navfn_path", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_navfn_potential", C.c_int, [vp, u32, vp]),
+    ("navgpu_navfn_costarr", C.c_int, [vp, u32, vp]),
     ("navgpu_footprint_radii", C.c_int, [vp, u32, C.POINTER(dbl), C.POINTER(dbl)]),
     ("navgpu_footprint_pad", C.c_int, [vp, u32, dbl]),
     ("navgpu_footprint_from_radius", C.c_int, [dbl, vp]),

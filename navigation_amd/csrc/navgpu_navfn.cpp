@@ -352,4 +352,12 @@ int navgpu_navfn_potential(navgpu_navfn* h, uint32_t plan, float* potarr) {
   return NAVGPU_OK;
 }
 
+int navgpu_navfn_costarr(navgpu_navfn* h, uint32_t plan, uint8_t* costarr) {
+  if (!h || plan >= h->n || !costarr) return NAVGPU_ERR_INVALID;
+  NavfnGuard guard_(h);
+  HIP_TRY(hipMemcpyAsync(costarr, h->nv.costarr + (size_t)plan * h->nv.ns_padded, (size_t)h->nv.ns, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
 }  // extern "C"

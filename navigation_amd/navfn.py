@@ -4,6 +4,7 @@
   plan          NavFn::setGoal / setStart + calcNavFnDijkstra | calcNavFnAstar   (navfn.cpp:145-171, 293-345)
   path          NavFn::getPathX / getPathY / getPathLen
   potential     NavFn::potarr
+  costarr       NavFn::costarr
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -90,4 +91,10 @@ class NavFn:
     def potential(self, plan=0):
         out = np.zeros((self.ny, self.nx), np.float32)
         check(self.L.navgpu_navfn_potential(self.h, plan, out.ctypes.data_as(C.c_void_p)), "navfn_potential")
+        return out
+
+    def costarr(self, plan=0):
+        """NavFn::costarr as the last set_costmap / set_costmap_from_fleet left it, (ny, nx) uint8."""
+        out = np.zeros((self.ny, self.nx), np.uint8)
+        check(self.L.navgpu_navfn_costarr(self.h, plan, out.ctypes.data_as(C.c_void_p)), "navfn_costarr")
         return out

@@ -77,6 +77,15 @@ void orc_lc_get_origin(void* h, double* xy) {
 void orc_lc_resize(void* h, uint32_t sx, uint32_t sy, double res, double ox, double oy) {
   static_cast<LayeredCostmapOracle*>(h)->resizeMap(sx, sy, res, ox, oy);
 }
+// StaticLayer::onInitialize's interpretation parameters (static_layer.cpp:76-81) for the orc_lc_add_static that follows; a
+// costmap that never calls this keeps the reference's defaults (trinary, 100, -1).  A call of its own, so that
+// orc_lc_add_static keeps the argument list its callers were built against.
+void orc_lc_set_static_interpretation(void* h, int trinary, int lethal_threshold, int unknown_cost_value) {
+  auto* lc = static_cast<LayeredCostmapOracle*>(h);
+  lc->slayer.trinary_costmap = trinary != 0;
+  lc->slayer.lethal_threshold = (uint8_t)std::max(std::min(lethal_threshold, 100), 0);  // static_layer.cpp:80
+  lc->slayer.unknown_cost_value = (uint8_t)unknown_cost_value;                           // :81, int -> unsigned char
+}
 void orc_lc_add_static(void* h, const int8_t* occ, uint32_t sx, uint32_t sy, double res, double ox, double oy,
                        int track_unknown_space, int use_maximum) {
   auto* lc = static_cast<LayeredCostmapOracle*>(h);
@@ -764,6 +773,15 @@ int orc_navfn_plan(const uint8_t* cmap, int nx, int ny, int cost_mode, int allow
     path_xy[2 * i + 1] = nav.pathy[i];
   }
   return len;
+}
+// NavFn::costarr as setCostmap leaves it (before setupNavFn outlines the border): ns bytes.  cost_mode as orc_navfn_plan.
+void orc_navfn_costarr(const uint8_t* cmap, int nx, int ny, int cost_mode, int allow_unknown, uint8_t* costarr_out) {
+  NavFnOracle nav(nx, ny);
+  if (cost_mode == 0)
+    memcpy(nav.costarr.data(), cmap, (size_t)nx * ny);
+  else
+    nav.setCostmap(cmap, cost_mode == 1, allow_unknown != 0);
+  memcpy(costarr_out, nav.costarr.data(), (size_t)nx * ny);
 }
 // The fixed point of NavFn::updateCell's rule (NavFnOracle::propagateFixedPoint) + calcPath on it: the checker of the HIP
 // path's tiled wavefront mode.  Same arguments as orc_navfn_plan (Dijkstra only).

@@ -89,6 +89,7 @@ def lib():
     sig("orc_lc_get_origin", None, vp, f64p)
     sig("orc_lc_resize", None, vp, u, u, d, d, d)
     sig("orc_lc_add_static", None, vp, i8p, u, u, d, d, d, i, i)
+    sig("orc_lc_set_static_interpretation", None, vp, i, i, i)
     sig("orc_lc_add_static_rolling", None, vp, i8p, u, u, d, d, d, i, i, i, i, i)
     sig("orc_lc_set_static_transform", None, vp, f64p)
     sig("orc_lc_add_obstacle", None, vp, i, i, d)
@@ -163,6 +164,7 @@ def lib():
     sig("orc_gp_grid_path", i, f32p, i, i, C.c_double, C.c_double, C.c_double, C.c_double, f32p, i)
     sig("orc_global_planner_plan", i, u8p, i, i, i32p, C.c_float, f64p, f64p, i32p, C.c_void_p, C.c_void_p, i, C.POINTER(i), C.POINTER(i))
     sig("orc_navfn_plan", i, u8p, i, i, i, i, i32p, i32p, i, i, C.c_void_p, C.c_void_p, i, C.POINTER(i))
+    sig("orc_navfn_costarr", None, u8p, i, i, i, i, u8p)
     sig("orc_navfn_fixed_point", i, u8p, i, i, i, i, i32p, i32p, C.c_void_p, C.c_void_p, i)
     sig("orc_navfn_calc_path", i, f32p, i, i, i32p, i32p, C.c_void_p, i)
     sig("orc_bench_dwa", d, u, u, d, u8p, u, C.POINTER(DwaConfig), f32p, f32p, f64p, u, f64p, f64p, u, u, u,
@@ -244,9 +246,12 @@ class LayeredCostmap:
         self.L.orc_lc_get_origin(self.h, o)
         return o
 
-    def add_static(self, occ, res=1.0, ox=0.0, oy=0.0, track_unknown_space=True, use_maximum=False):
+    def add_static(self, occ, res=1.0, ox=0.0, oy=0.0, track_unknown_space=True, use_maximum=False, trinary=True, lethal_threshold=100,
+                   unknown_cost_value=-1):
+        """StaticLayer::onInitialize's parameters (static_layer.cpp:72-81) + incomingMap; the defaults are the reference's."""
         occ = np.ascontiguousarray(occ, dtype=np.int8)
         sy, sx = occ.shape
+        self.L.orc_lc_set_static_interpretation(self.h, int(trinary), int(lethal_threshold), int(unknown_cost_value) & 0xFF)
         self.L.orc_lc_add_static(self.h, occ, sx, sy, res, ox, oy, int(track_unknown_space), int(use_maximum))
 
     def add_static_rolling(self, occ, res, ox, oy, track_unknown_space=True, use_maximum=False, trinary=True, lethal_threshold=100,
@@ -579,6 +584,24 @@ def navfn_plan(cmap, goal, start, cost_mode=1, allow_unknown=True, astar=False, 
     n = lib().orc_navfn_plan(g, nx, ny, cost_mode, int(allow_unknown), np.ascontiguousarray(goal, np.int32), np.ascontiguousarray(start, np.int32),
                              int(astar), int(at_start), pot.ctypes.data if want_potential else None, path.ctypes.data, cap, C.byref(cyc))
     return path[:n].copy(), pot, cyc.value
+
+
+def merge(layer, master, mode, box=None):
+    """CostmapLayer::updateWithOverwrite (mode 0) | updateWithMax (1) | updateWithTrueOverwrite (2) (costmap_layer.cpp:62-124) of
+    `layer` into a copy of `master` over box = (min_i, min_j, max_i, max_j), default the whole grid."""
+    m = np.ascontiguousarray(master, np.uint8).copy()
+    sy, sx = m.shape
+    b = (0, 0, sx, sy) if box is None else box
+    lib().orc_merge(np.ascontiguousarray(layer, np.uint8), m, sx, sy, mode, b[0], b[1], b[2], b[3])
+    return m
+
+
+def navfn_costarr(cmap, cost_mode=1, allow_unknown=True):
+    """NavFn::costarr after setCostmap (navfn_oracle.hpp), (ny, nx) uint8; cost_mode as navfn_plan."""
+    g = np.ascontiguousarray(cmap, np.uint8)
+    out = np.zeros_like(g)
+    lib().orc_navfn_costarr(g, g.shape[1], g.shape[0], cost_mode, int(allow_unknown), out)
+    return out
 
 
 def navfn_fixed_point(cmap, goal, start, cost_mode=1, allow_unknown=True):
