@@ -33,64 +33,87 @@ __host__ __device__ inline size_t bfs_rows_lds_words(uint32_t nx, uint32_t ny) {
 // written over f once every neighbour in the group has been read.  The old last word goes to p before the skip, live or not:
 // it is the next group's left neighbour L, so the caller alternates two registers (a group that is not live holds no frontier
 // cell, and its last word is that).  R: the next group's first word, still old.
+#define NAVGPU_ROWS_DPP " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define NAVGPU_ROWS_GROUP_WORDS                                    \
+  "v_mov_b32 %[p], %[f3]\n\t"                                      \
+  "s_bitcmp1_b32 %[aw], %[g]\n\t"                                  \
+  "s_cbranch_scc0 1f\n\t"                                          \
+  "v_alignbit_b32 %[u0], %[f0], %[L], 31\n\t"                      \
+  "v_alignbit_b32 %[u1], %[f1], %[f0], 31\n\t"                     \
+  "v_alignbit_b32 %[u2], %[f2], %[f1], 31\n\t"                     \
+  "v_alignbit_b32 %[u3], %[f3], %[f2], 31\n\t"                     \
+  "v_alignbit_b32 %[t0], %[f1], %[f0], 1\n\t"                      \
+  "v_alignbit_b32 %[t1], %[f2], %[f1], 1\n\t"                      \
+  "v_alignbit_b32 %[t2], %[f3], %[f2], 1\n\t"                      \
+  "v_alignbit_b32 %[t3], %[R], %[f3], 1\n\t"                       \
+  "v_or_b32_dpp %[u0], %[f0], %[u0] wave_shr:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[u1], %[f1], %[u1] wave_shr:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[u2], %[f2], %[u2] wave_shr:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[u3], %[f3], %[u3] wave_shr:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[t0], %[f0], %[t0] wave_shl:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[t1], %[f1], %[t1] wave_shl:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[t2], %[f2], %[t2] wave_shl:1" NAVGPU_ROWS_DPP    \
+  "v_or_b32_dpp %[t3], %[f3], %[t3] wave_shl:1" NAVGPU_ROWS_DPP    \
+  "v_bitop3_b32 %[f0], %[u0], %[b0], %[t0] bitop3:0x32\n\t"        \
+  "v_bitop3_b32 %[f1], %[u1], %[b1], %[t1] bitop3:0x32\n\t"        \
+  "v_bitop3_b32 %[f2], %[u2], %[b2], %[t2] bitop3:0x32\n\t"        \
+  "v_bitop3_b32 %[f3], %[u3], %[b3], %[t3] bitop3:0x32\n\t"        \
+  "v_or3_b32 %[b0], %[b0], %[u0], %[t0]\n\t"                       \
+  "v_or3_b32 %[b1], %[b1], %[u1], %[t1]\n\t"                       \
+  "v_or3_b32 %[b2], %[b2], %[u2], %[t2]\n\t"                       \
+  "v_or3_b32 %[b3], %[b3], %[u3], %[t3]\n\t"
+#define NAVGPU_ROWS_GROUP_REGS                                                                                                              \
+  [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [b3] "+v"(b[3]), [f0] "+v"(f[0]), [f1] "+v"(f[1]), [f2] "+v"(f[2]), [f3] "+v"(f[3]), \
+      [p] "=&v"(p), [u0] "=&v"(u0), [u1] "=&v"(u1), [u2] "=&v"(u2), [u3] "=&v"(u3), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),       \
+      [t3] "=&v"(t3)
+// The group as the block-of-levels loop of bfsRowsGrid runs it: which groups are live is fixed for the block, so all that is
+// worked out besides the words is acc, the lanes that got a new cell in any group since the caller cleared it (the stop flag: an
+// SGPR pair, one compare and one scalar or per group).
+__device__ __forceinline__ void rowsGroup4(const int g, const uint32_t aw, uint64_t& acc, uint32_t* __restrict__ b, uint32_t* __restrict__ f,
+                                           const uint32_t L, const uint32_t R, uint32_t& p) {
+  uint32_t u0, u1, u2, u3, t0, t1, t2, t3;
+  uint64_t c0;
+  asm volatile(NAVGPU_ROWS_GROUP_WORDS
+               "v_or3_b32 %[u0], %[f0], %[f1], %[f2]\n\t"
+               "v_or_b32_e32 %[u0], %[u0], %[f3]\n\t"
+               "v_cmp_ne_u32_e64 %[c0], 0, %[u0]\n\t"
+               "s_or_b64 %[acc], %[acc], %[c0]\n\t"
+               "1:\n\t"
+               : NAVGPU_ROWS_GROUP_REGS, [acc] "+s"(acc), [c0] "=&s"(c0)
+               : [aw] "s"(aw), [g] "n"(g), [L] "v"(L), [R] "v"(R)
+               : "scc");
+}
+// The group as the level-by-level loop runs it (W = 20 only, see bfsRowsGrid): the live groups of the next level come from
 // nz: bit g set when any lane has new cells in the group; lo / hi: when its first / last word has (the neighbouring group
 // borders them next level).  The three tests are compares into SGPR pairs combined by scalar ops after the vector work: no
 // vcc -> branch round trip in the group's path.
-__device__ __forceinline__ void rowsGroup4(const int g, const uint32_t aw, uint32_t& nz, uint32_t& lo, uint32_t& hi, uint32_t* __restrict__ b,
-                                           uint32_t* __restrict__ f, const uint32_t L, const uint32_t R, uint32_t& p) {
+__device__ __forceinline__ void rowsGroup4PerLevel(const int g, const uint32_t aw, uint32_t& nz, uint32_t& lo, uint32_t& hi, uint32_t* __restrict__ b,
+                                                   uint32_t* __restrict__ f, const uint32_t L, const uint32_t R, uint32_t& p) {
   uint32_t u0, u1, u2, u3, t0, t1, t2, t3, st;
   uint64_t c0, c1, c2;
-#define NAVGPU_ROWS_DPP " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-  asm volatile(
-      "v_mov_b32 %[p], %[f3]\n\t"
-      "s_bitcmp1_b32 %[aw], %[g]\n\t"
-      "s_cbranch_scc0 1f\n\t"
-      "v_alignbit_b32 %[u0], %[f0], %[L], 31\n\t"
-      "v_alignbit_b32 %[u1], %[f1], %[f0], 31\n\t"
-      "v_alignbit_b32 %[u2], %[f2], %[f1], 31\n\t"
-      "v_alignbit_b32 %[u3], %[f3], %[f2], 31\n\t"
-      "v_alignbit_b32 %[t0], %[f1], %[f0], 1\n\t"
-      "v_alignbit_b32 %[t1], %[f2], %[f1], 1\n\t"
-      "v_alignbit_b32 %[t2], %[f3], %[f2], 1\n\t"
-      "v_alignbit_b32 %[t3], %[R], %[f3], 1\n\t"
-      "v_or_b32_dpp %[u0], %[f0], %[u0] wave_shr:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[u1], %[f1], %[u1] wave_shr:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[u2], %[f2], %[u2] wave_shr:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[u3], %[f3], %[u3] wave_shr:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[t0], %[f0], %[t0] wave_shl:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[t1], %[f1], %[t1] wave_shl:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[t2], %[f2], %[t2] wave_shl:1" NAVGPU_ROWS_DPP
-      "v_or_b32_dpp %[t3], %[f3], %[t3] wave_shl:1" NAVGPU_ROWS_DPP
-      "v_bitop3_b32 %[f0], %[u0], %[b0], %[t0] bitop3:0x32\n\t"
-      "v_bitop3_b32 %[f1], %[u1], %[b1], %[t1] bitop3:0x32\n\t"
-      "v_bitop3_b32 %[f2], %[u2], %[b2], %[t2] bitop3:0x32\n\t"
-      "v_bitop3_b32 %[f3], %[u3], %[b3], %[t3] bitop3:0x32\n\t"
-      "v_or3_b32 %[b0], %[b0], %[u0], %[t0]\n\t"
-      "v_or3_b32 %[b1], %[b1], %[u1], %[t1]\n\t"
-      "v_or3_b32 %[b2], %[b2], %[u2], %[t2]\n\t"
-      "v_or3_b32 %[b3], %[b3], %[u3], %[t3]\n\t"
-      "v_or3_b32 %[u0], %[f0], %[f1], %[f2]\n\t"
-      "v_cmp_ne_u32_e64 %[c1], 0, %[f0]\n\t"
-      "v_or_b32_e32 %[u0], %[u0], %[f3]\n\t"
-      "v_cmp_ne_u32_e64 %[c2], 0, %[f3]\n\t"
-      "v_cmp_ne_u32_e64 %[c0], 0, %[u0]\n\t"
-      "s_cmp_lg_u64 %[c1], 0\n\t"
-      "s_cselect_b32 %[st], %[bit], 0\n\t"
-      "s_or_b32 %[lo], %[lo], %[st]\n\t"
-      "s_cmp_lg_u64 %[c2], 0\n\t"
-      "s_cselect_b32 %[st], %[bit], 0\n\t"
-      "s_or_b32 %[hi], %[hi], %[st]\n\t"
-      "s_cmp_lg_u64 %[c0], 0\n\t"
-      "s_cselect_b32 %[st], %[bit], 0\n\t"
-      "s_or_b32 %[nz], %[nz], %[st]\n\t"
-      "1:\n\t"
-      : [b0] "+v"(b[0]), [b1] "+v"(b[1]), [b2] "+v"(b[2]), [b3] "+v"(b[3]), [f0] "+v"(f[0]), [f1] "+v"(f[1]), [f2] "+v"(f[2]), [f3] "+v"(f[3]),
-        [p] "=&v"(p), [u0] "=&v"(u0), [u1] "=&v"(u1), [u2] "=&v"(u2), [u3] "=&v"(u3), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
-        [t3] "=&v"(t3), [nz] "+s"(nz), [lo] "+s"(lo), [hi] "+s"(hi), [c0] "=&s"(c0), [c1] "=&s"(c1), [c2] "=&s"(c2), [st] "=&s"(st)
-      : [aw] "s"(aw), [g] "n"(g), [bit] "n"(1 << g), [L] "v"(L), [R] "v"(R)
-      : "scc");
-#undef NAVGPU_ROWS_DPP
+  asm volatile(NAVGPU_ROWS_GROUP_WORDS
+               "v_or3_b32 %[u0], %[f0], %[f1], %[f2]\n\t"
+               "v_cmp_ne_u32_e64 %[c1], 0, %[f0]\n\t"
+               "v_or_b32_e32 %[u0], %[u0], %[f3]\n\t"
+               "v_cmp_ne_u32_e64 %[c2], 0, %[f3]\n\t"
+               "v_cmp_ne_u32_e64 %[c0], 0, %[u0]\n\t"
+               "s_cmp_lg_u64 %[c1], 0\n\t"
+               "s_cselect_b32 %[st], %[bit], 0\n\t"
+               "s_or_b32 %[lo], %[lo], %[st]\n\t"
+               "s_cmp_lg_u64 %[c2], 0\n\t"
+               "s_cselect_b32 %[st], %[bit], 0\n\t"
+               "s_or_b32 %[hi], %[hi], %[st]\n\t"
+               "s_cmp_lg_u64 %[c0], 0\n\t"
+               "s_cselect_b32 %[st], %[bit], 0\n\t"
+               "s_or_b32 %[nz], %[nz], %[st]\n\t"
+               "1:\n\t"
+               : NAVGPU_ROWS_GROUP_REGS, [nz] "+s"(nz), [lo] "+s"(lo), [hi] "+s"(hi), [c0] "=&s"(c0), [c1] "=&s"(c1), [c2] "=&s"(c2), [st] "=&s"(st)
+               : [aw] "s"(aw), [g] "n"(g), [bit] "n"(1 << g), [L] "v"(L), [R] "v"(R)
+               : "scc");
 }
+#undef NAVGPU_ROWS_GROUP_REGS
+#undef NAVGPU_ROWS_GROUP_WORDS
+#undef NAVGPU_ROWS_DPP
 template <int W>
 __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t inst, const int which, const uint32_t item) {
   constexpr int NG = (W + 3) / 4;         // groups of four words
@@ -170,7 +193,14 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   const uint32_t halo_rd = ((halo_top ? (wave_id * 2 + 1) : ((wave_id + 2) * 2)) * D + (halo_top ? lane : lane - (64u - D))) * RS;
   constexpr uint32_t gmask = (1u << NG) - 1u;
 
-  // which groups hold or border a frontier cell of this wave's 64 rows
+  // The groups that are live for the next block of D levels: those that hold a frontier cell of this wave's 64 rows now, or
+  // can get one from a neighbouring group before the waves meet again.  A cell moves one column per level and nothing comes
+  // in from outside the 64 rows during a block, so only the D columns next to a group's edge can send one across it.
+  // W = 20 still works the live groups out level by level, from whole edge words: with the block loop its kernel spills one
+  // register more (7 for 6) than with this one, the other two sizes none with either.
+  constexpr bool kBlockLive = W != 20;
+  static_assert(D >= 1 && D < 32, "the edge masks take D bits of one word");
+  constexpr uint32_t edge_lo = kBlockLive ? (1u << D) - 1u : 0xFFFFFFFFu, edge_hi = kBlockLive ? ~(0xFFFFFFFFu >> D) : 0xFFFFFFFFu;
   auto activity = [&]() -> uint32_t {
     uint32_t nz = 0, lo = 0, hi = 0;
 #pragma unroll
@@ -178,8 +208,8 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
       const uint32_t t = fr[4 * q] | fr[4 * q + 1] | fr[4 * q + 2] | fr[4 * q + 3];
       if (__builtin_amdgcn_ballot_w64(t != 0) != 0) {
         nz |= 1u << q;
-        if (__builtin_amdgcn_ballot_w64(fr[4 * q] != 0) != 0) lo |= 1u << q;
-        if (__builtin_amdgcn_ballot_w64(fr[4 * q + 3] != 0) != 0) hi |= 1u << q;
+        if (__builtin_amdgcn_ballot_w64((fr[4 * q] & edge_lo) != 0) != 0) lo |= 1u << q;
+        if (__builtin_amdgcn_ballot_w64((fr[4 * q + 3] & edge_hi) != 0) != 0) hi |= 1u << q;
       }
     }
     return (nz | (lo >> 1) | (hi << 1)) & gmask;
@@ -190,57 +220,97 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
       if (j >= w0 && j <= w1 && row_in_box) storeCells(j, fr[j], 0u);  // the seeds: distance 0
   }
   uint32_t a_own = activity();
-  uint32_t level = 0, xch = 0, any_blk = 0;
+  uint32_t level = 0, xch = 0;
   bfsStamp(pl, tid, item, 2);
   bool done = false;
 #ifdef NAVGPU_BFS_STATS
   unsigned long long bst[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-  while (!done) {
-    // ---- D levels on the wave's own: registers and DPP only
-    for (int k = 0; k < D; ++k) {
-      BFS_STAMP(ts1);
-      BFS_ACC(5, 1);
-      const uint32_t aw = __builtin_amdgcn_readfirstlane(a_own);  // (provably uniform, but the "s" operands below need the compiler to know it)
-      BFS_ACC(7, aw != 0 ? 1 : 0);
-      BFS_ACC(8, __builtin_popcount(aw));
-      if (aw != 0) {
-        uint32_t nz = 0, lo = 0, hi = 0;
-        // One group = one asm statement that carries its own wave-uniform skip, so the compiler sees straight-line code
-        // with in-place (tied) updates of `blocked` and `fr`.  (Written as C++ branches the same loop made it rename both
-        // arrays per word: register copies in the path of every SKIPPED word and a dozen more at the loop's back edge.)
-        // p[q & 1] carries group q's old last word to group q + 1.
-        uint32_t p[2];
-        const uint32_t zero = 0;
+  // the new cells of the robot's region get their distance from the lane that owns the row.  groups (wave-uniform): the groups
+  // that may hold new cells (one that is not live holds none; a live one that got none fails every lane's test)
+  auto storeNew = [&](const uint32_t groups) {
+    if (wave_in_box && (groups & region_groups) != 0) {
 #pragma unroll
-        for (int q = 0; q < NG; ++q)
-          rowsGroup4(q, aw, nz, lo, hi, &blocked[4 * q], &fr[4 * q], q > 0 ? p[(q + 1) & 1] : zero, q + 1 < NG ? fr[q + 1 < NG ? 4 * q + 4 : 0] : zero,
-                     p[q & 1]);
-        BFS_STAMP(ts2);
-        BFS_ACC(1, ts2 - ts1);
-        // the new cells of the robot's region get their distance now, from the lane that owns the row
-        if (wave_in_box && (nz & region_groups) != 0) {
+      for (int q = 0; q < NG; ++q) {
+        if (((groups & region_groups) >> q) & 1u) {  // wave-uniform
 #pragma unroll
-          for (int q = 0; q < NG; ++q) {
-            if (((nz & region_groups) >> q) & 1u) {  // wave-uniform
-#pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                const int j = 4 * q + c;
-                if (j < W && j >= w0 && j <= w1) {
+          for (int c = 0; c < 4; ++c) {
+            const int j = 4 * q + c;
+            if (j < W && j >= w0 && j <= w1) {
 #ifndef NAVGPU_BFS_X_NOSTORE  // (timing experiment, results garbage: the levels without their distance stores - 126 M -> 102 M wave-instructions, 0.33 -> 0.27 ms)
-                  if (row_in_box && fr[j < W ? j : 0] != 0) storeCells(j, fr[j < W ? j : 0], level + 1);
+              if (row_in_box && fr[j < W ? j : 0] != 0) storeCells(j, fr[j < W ? j : 0], level + 1);
 #endif
-                }
-              }
             }
           }
         }
-        BFS_STAMP(ts3);
-        BFS_ACC(2, ts3 - ts2);
-        any_blk |= nz;
-        a_own = (nz | (lo >> 1) | (hi << 1)) & gmask;
       }
-      ++level;
+    }
+  };
+  // One group = one asm statement that carries its own wave-uniform skip, so the compiler sees straight-line code with
+  // in-place (tied) updates of `blocked` and `fr`.  (Written as C++ branches the same loop made it rename both arrays per
+  // word: register copies in the path of every SKIPPED word and a dozen more at the loop's back edge.)
+  // p[q & 1] carries group q's old last word to group q + 1.
+  while (!done) {
+    // ---- D levels on the wave's own: registers and DPP only
+    bool any_new;  // wave-uniform: some lane got a new cell in this block
+    if constexpr (kBlockLive) {  // the same live groups at every level of the block
+      const uint32_t aw = __builtin_amdgcn_readfirstlane(a_own);  // (provably uniform, but the "s" operands below need the compiler to know it)
+      uint64_t acc = 0;
+      if (aw == 0) {  // nothing can reach this wave before the next exchange
+        BFS_ACC(5, D);
+        level += D;
+      } else {
+        for (int k = 0; k < D; ++k) {
+          BFS_STAMP(ts1);
+          BFS_ACC(5, 1);
+          BFS_ACC(7, 1);
+          BFS_ACC(8, __builtin_popcount(aw));
+          // The level's copy of the mask is opaque: knowing that the same groups are skipped at every level of the block,
+          // the compiler hoists per-word work of the stores out of this loop and keeps it live across it (28 spilled
+          // registers at W = 13).
+          uint32_t awk = aw;
+          asm volatile("" : "+s"(awk));
+          uint32_t p[2];
+          const uint32_t zero = 0;
+#pragma unroll
+          for (int q = 0; q < NG; ++q)
+            rowsGroup4(q, awk, acc, &blocked[4 * q], &fr[4 * q], q > 0 ? p[(q + 1) & 1] : zero, q + 1 < NG ? fr[q + 1 < NG ? 4 * q + 4 : 0] : zero, p[q & 1]);
+          BFS_STAMP(ts2);
+          BFS_ACC(1, ts2 - ts1);
+          storeNew(awk);
+          BFS_STAMP(ts3);
+          BFS_ACC(2, ts3 - ts2);
+          ++level;
+        }
+      }
+      any_new = acc != 0;
+    } else {  // the live groups of a level from the one before
+      uint32_t any_blk = 0;
+      for (int k = 0; k < D; ++k) {
+        BFS_STAMP(ts1);
+        BFS_ACC(5, 1);
+        const uint32_t aw = __builtin_amdgcn_readfirstlane(a_own);
+        BFS_ACC(7, aw != 0 ? 1 : 0);
+        BFS_ACC(8, __builtin_popcount(aw));
+        if (aw != 0) {
+          uint32_t nz = 0, lo = 0, hi = 0;
+          uint32_t p[2];
+          const uint32_t zero = 0;
+#pragma unroll
+          for (int q = 0; q < NG; ++q)
+            rowsGroup4PerLevel(q, aw, nz, lo, hi, &blocked[4 * q], &fr[4 * q], q > 0 ? p[(q + 1) & 1] : zero, q + 1 < NG ? fr[q + 1 < NG ? 4 * q + 4 : 0] : zero,
+                               p[q & 1]);
+          BFS_STAMP(ts2);
+          BFS_ACC(1, ts2 - ts1);
+          storeNew(nz);
+          BFS_STAMP(ts3);
+          BFS_ACC(2, ts3 - ts2);
+          any_blk |= nz;
+          a_own = (nz | (lo >> 1) | (hi << 1)) & gmask;
+        }
+        ++level;
+      }
+      any_new = any_blk != 0;
     }
     // ---- exchange: the outer D own rows go to the neighbours, theirs come into the halo lanes; stop flags
     BFS_STAMP(ts4);
@@ -252,7 +322,7 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
         *reinterpret_cast<uint4*>(edge + pub_wr + WP + q) = make_uint4(blocked[q], blocked[q + 1], blocked[q + 2], blocked[q + 3]);
       }
     }
-    if (any_blk) s_flag[slot] = 1;
+    if (any_new) s_flag[slot] = 1;
     if (wave_in_box) {  // wave-uniform: is anything of the robot's box still open, or a frontier cell inside the region?
       uint32_t open_any = 0;
       const uint32_t rr = (uint32_t)(row_i - by0);
@@ -298,7 +368,6 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
       __syncthreads();  // the records are free for the next exchange
     }
     ++xch;
-    any_blk = 0;
     BFS_STAMP(ts6);
     BFS_ACC(4, ts6 - ts5);
   }
@@ -385,14 +454,14 @@ __host__ __device__ inline size_t bfs_rows2_lds_words(uint32_t ny) {
 //   row A: x = left | right | (row B of the lane above) | own row B;   row B: x = left | right | own row A | (row A of the lane below)
 //   new frontier = x & ~blocked;   blocked |= x
 // The words are updated where they stand, so the old last word of the group is kept in pA / pB for the next group's left
-// neighbour.  They are valid only if this group was live; a group that is not holds no frontier cell (it either never had one
-// or wrote its empty result back the level it went quiet), so its neighbour shifts in zeros instead (the G > 0 prologue).
-// rA / rB: the first word of the next group (still old).  nz / lo / hi as rowsGroup4.
+// neighbour.  They are valid only if this group was live; a group that is not holds no frontier cell (bfsRows2Grid's activity
+// mask), so its neighbour shifts in zeros instead (the G > 0 prologue).
+// rA / rB: the first word of the next group (still old).  acc as rowsGroup4.
 template <int G>
-__device__ __forceinline__ void rows2Group(const uint32_t aw, uint32_t& nz, uint32_t& lo, uint32_t& hi, uint32_t* __restrict__ bA, uint32_t* __restrict__ bB,
-                                           uint32_t* __restrict__ fA, uint32_t* __restrict__ fB, uint32_t& pA, uint32_t& pB, const uint32_t rA,
-                                           const uint32_t rB) {
-  uint32_t u0, u1, u2, u3, v0, v1, v2, v3, h0, h1, h2, h3, st;
+__device__ __forceinline__ void rows2Group(const uint32_t aw, uint64_t& acc, uint32_t* __restrict__ bA, uint32_t* __restrict__ bB, uint32_t* __restrict__ fA,
+                                           uint32_t* __restrict__ fB, uint32_t& pA, uint32_t& pB, const uint32_t rA, const uint32_t rB) {
+  uint32_t u0, u1, u2, u3, v0, v1, v2, v3, h0, h1, h2, h3;
+  uint64_t c0;
 #define NAVGPU_ROWS2_HEAD_FIRST                \
   "s_bitcmp1_b32 %[aw], %[g]\n\t"              \
   "s_cbranch_scc0 1f\n\t"                      \
@@ -461,29 +530,20 @@ __device__ __forceinline__ void rows2Group(const uint32_t aw, uint32_t& nz, uint
       "v_or_b32_e32 %[bB1], %[bB1], %[v1]\n\t"                                                         \
       "v_or_b32_e32 %[bB2], %[bB2], %[v2]\n\t"                                                         \
       "v_or_b32_e32 %[bB3], %[bB3], %[v3]\n\t"                                                         \
-      "v_or_b32_e32 %[h0], %[fA0], %[fB0]\n\t"                                                         \
-      "v_or_b32_e32 %[h3], %[fA3], %[fB3]\n\t"                                                         \
-      "v_or3_b32 %[h1], %[fA1], %[fA2], %[fB1]\n\t"                                                    \
-      "v_or3_b32 %[h2], %[h0], %[h3], %[fB2]\n\t"                                                      \
-      "v_or_b32_e32 %[h1], %[h1], %[h2]\n\t"                                                           \
-      "v_cmp_ne_u32_e32 vcc, 0, %[h1]\n\t"                                                             \
-      "s_cbranch_vccz 1f\n\t"                                                                          \
-      "s_bitset1_b32 %[nz], %[g]\n\t"                                                                  \
-      "v_cmp_ne_u32_e32 vcc, 0, %[h0]\n\t"                                                             \
-      "s_cbranch_vccz 3f\n\t"                                                                          \
-      "s_bitset1_b32 %[lo], %[g]\n\t"                                                                  \
-      "3:\n\t"                                                                                         \
-      "v_cmp_ne_u32_e32 vcc, 0, %[h3]\n\t"                                                             \
-      "s_cbranch_vccz 1f\n\t"                                                                          \
-      "s_bitset1_b32 %[hi], %[g]\n\t"                                                                  \
+      "v_or3_b32 %[h0], %[fA0], %[fB0], %[fA1]\n\t"                                                    \
+      "v_or3_b32 %[h1], %[fB1], %[fA2], %[fB2]\n\t"                                                    \
+      "v_or3_b32 %[h0], %[h0], %[fA3], %[fB3]\n\t"                                                     \
+      "v_or_b32_e32 %[h0], %[h0], %[h1]\n\t"                                                           \
+      "v_cmp_ne_u32_e64 %[c0], 0, %[h0]\n\t"                                                           \
+      "s_or_b64 %[acc], %[acc], %[c0]\n\t"                                                             \
       "1:\n\t"                                                                                         \
       : [bA0] "+v"(bA[0]), [bA1] "+v"(bA[1]), [bA2] "+v"(bA[2]), [bA3] "+v"(bA[3]), [bB0] "+v"(bB[0]), [bB1] "+v"(bB[1]), [bB2] "+v"(bB[2]),  \
         [bB3] "+v"(bB[3]), [fA0] "+v"(fA[0]), [fA1] "+v"(fA[1]), [fA2] "+v"(fA[2]), [fA3] "+v"(fA[3]), [fB0] "+v"(fB[0]), [fB1] "+v"(fB[1]),   \
-        [fB2] "+v"(fB[2]), [fB3] "+v"(fB[3]), [pA] "+v"(pA), [pB] "+v"(pB), [nz] "+s"(nz), [lo] "+s"(lo), [hi] "+s"(hi), [u0] "=&v"(u0),       \
+        [fB2] "+v"(fB[2]), [fB3] "+v"(fB[3]), [pA] "+v"(pA), [pB] "+v"(pB), [acc] "+s"(acc), [c0] "=&s"(c0), [u0] "=&v"(u0),                  \
         [u1] "=&v"(u1), [u2] "=&v"(u2), [u3] "=&v"(u3), [v0] "=&v"(v0), [v1] "=&v"(v1), [v2] "=&v"(v2), [v3] "=&v"(v3), [h0] "=&v"(h0),        \
-        [h1] "=&v"(h1), [h2] "=&v"(h2), [h3] "=&v"(h3), [st] "=&s"(st)                                                                         \
+        [h1] "=&v"(h1), [h2] "=&v"(h2), [h3] "=&v"(h3)                                                                                         \
       : [aw] "s"(aw), [g] "n"(G), [gp] "n"(G > 0 ? G - 1 : 0), [rA] "v"(rA), [rB] "v"(rB)                                                      \
-      : "vcc", "scc")
+      : "scc")
   if constexpr (G == 0) NAVGPU_ROWS2_BODY(NAVGPU_ROWS2_HEAD_FIRST);
   else NAVGPU_ROWS2_BODY(NAVGPU_ROWS2_HEAD_NEXT);
 #undef NAVGPU_ROWS2_BODY
@@ -492,13 +552,13 @@ __device__ __forceinline__ void rows2Group(const uint32_t aw, uint32_t& nz, uint
 }
 // the NG groups of a level, first to last (a compile-time recursion: the group number is an immediate of the asm block)
 template <int G>
-__device__ __forceinline__ void rows2Level(const uint32_t aw, uint32_t& nz, uint32_t& lo, uint32_t& hi, uint32_t* __restrict__ blA, uint32_t* __restrict__ blB,
-                                           uint32_t* __restrict__ frA, uint32_t* __restrict__ frB, uint32_t& pA, uint32_t& pB, const uint32_t zero) {
+__device__ __forceinline__ void rows2Level(const uint32_t aw, uint64_t& acc, uint32_t* __restrict__ blA, uint32_t* __restrict__ blB, uint32_t* __restrict__ frA,
+                                           uint32_t* __restrict__ frB, uint32_t& pA, uint32_t& pB, const uint32_t zero) {
   constexpr int NG = kRows2Words / 4;
   if constexpr (G < NG) {
-    rows2Group<G>(aw, nz, lo, hi, blA + 4 * G, blB + 4 * G, frA + 4 * G, frB + 4 * G, pA, pB, G + 1 < NG ? frA[G + 1 < NG ? 4 * G + 4 : 0] : zero,
+    rows2Group<G>(aw, acc, blA + 4 * G, blB + 4 * G, frA + 4 * G, frB + 4 * G, pA, pB, G + 1 < NG ? frA[G + 1 < NG ? 4 * G + 4 : 0] : zero,
                   G + 1 < NG ? frB[G + 1 < NG ? 4 * G + 4 : 0] : zero);
-    rows2Level<G + 1>(aw, nz, lo, hi, blA, blB, frA, frB, pA, pB, zero);
+    rows2Level<G + 1>(aw, acc, blA, blB, frA, frB, pA, pB, zero);
   }
 }
 __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_t inst, const int which, const uint32_t item, uint32_t* seedw) {
@@ -605,6 +665,9 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   const uint32_t halo_rd = ((halo_top ? (wave_id * 2 + 1) : ((wave_id + 2) * 2)) * HL + (halo_top ? lane : lane - (64u - HL))) * 4 * W;
   constexpr uint32_t gmask = (1u << NG) - 1u;
 
+  // the groups that are live for the next block of D levels (as in bfsRowsGrid: a cell moves one column per level)
+  static_assert(D >= 1 && D < 32, "the edge masks take D bits of one word");
+  constexpr uint32_t edge_lo = (1u << D) - 1u, edge_hi = ~(0xFFFFFFFFu >> D);
   auto activity = [&]() -> uint32_t {
     uint32_t nz = 0, lo = 0, hi = 0;
 #pragma unroll
@@ -612,8 +675,8 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
       const uint32_t t = frA[4 * q] | frA[4 * q + 1] | frA[4 * q + 2] | frA[4 * q + 3] | frB[4 * q] | frB[4 * q + 1] | frB[4 * q + 2] | frB[4 * q + 3];
       if (__builtin_amdgcn_ballot_w64(t != 0) != 0) {
         nz |= 1u << q;
-        if (__builtin_amdgcn_ballot_w64((frA[4 * q] | frB[4 * q]) != 0) != 0) lo |= 1u << q;
-        if (__builtin_amdgcn_ballot_w64((frA[4 * q + 3] | frB[4 * q + 3]) != 0) != 0) hi |= 1u << q;
+        if (__builtin_amdgcn_ballot_w64(((frA[4 * q] | frB[4 * q]) & edge_lo) != 0) != 0) lo |= 1u << q;
+        if (__builtin_amdgcn_ballot_w64(((frA[4 * q + 3] | frB[4 * q + 3]) & edge_hi) != 0) != 0) hi |= 1u << q;
       }
     }
     return (nz | (lo >> 1) | (hi << 1)) & gmask;
@@ -627,48 +690,52 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
       }
   }
   uint32_t a_own = activity();
-  uint32_t level = 0, xch = 0, any_blk = 0;
+  uint32_t level = 0, xch = 0;
   bfsStamp(pl, tid, item, 2);
   bool done = false;
 #ifdef NAVGPU_BFS_STATS
   unsigned long long bst[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
   while (!done) {
-    // ---- D levels on the wave's own: registers and DPP only
+    // ---- D levels on the wave's own: registers and DPP only, the same live groups at every one of them
+    const uint32_t aw = __builtin_amdgcn_readfirstlane(a_own);
+    uint64_t acc = 0;  // lanes that got a new cell in this block
     for (int k = 0; k < D; ++k) {
       BFS_STAMP(ts1);
       BFS_ACC(5, 1);
-      const uint32_t aw = __builtin_amdgcn_readfirstlane(a_own);
-      BFS_ACC(7, aw != 0 ? 1 : 0);
-      BFS_ACC(8, __builtin_popcount(aw));
-      if (aw != 0) {
-        uint32_t nz = 0, lo = 0, hi = 0;
-        uint32_t pA = 0, pB = 0;  // the old last words of the previous live group
-        const uint32_t zero = 0;
-        rows2Level<0>(aw, nz, lo, hi, blA, blB, frA, frB, pA, pB, zero);
-        BFS_STAMP(ts2);
-        BFS_ACC(1, ts2 - ts1);
-        // the new cells of the robot's region get their distance now, from the lane that owns the row
-        if (wave_in_box && (nz & region_groups) != 0) {
+      // The level's copy of the mask is opaque, as in bfsRowsGrid, and an idle wave finds that out level by level: with one
+      // test ahead of the loop this kernel spills one register more (135 for 134).
+      uint32_t awk = aw;
+      asm volatile("" : "+s"(awk));
+      BFS_ACC(7, awk != 0 ? 1 : 0);
+      BFS_ACC(8, __builtin_popcount(awk));
+      if (awk == 0) {
+        ++level;
+        continue;
+      }
+      uint32_t pA = 0, pB = 0;  // the old last words of the previous live group
+      const uint32_t zero = 0;
+      rows2Level<0>(awk, acc, blA, blB, frA, frB, pA, pB, zero);
+      BFS_STAMP(ts2);
+      BFS_ACC(1, ts2 - ts1);
+      // the new cells of the robot's region get their distance now, from the lane that owns the row
+      if (wave_in_box && (awk & region_groups) != 0) {
 #pragma unroll
-          for (int q = 0; q < NG; ++q) {
-            if (((nz & region_groups) >> q) & 1u) {  // wave-uniform
+        for (int q = 0; q < NG; ++q) {
+          if (((awk & region_groups) >> q) & 1u) {  // wave-uniform
 #pragma unroll
-              for (int c = 0; c < 4; ++c) {
-                const int j = 4 * q + c;
-                if (j >= w0 && j <= w1) {
-                  if (inA && frA[j] != 0) storeCells(rowA, j, frA[j], level + 1);
-                  if (inB && frB[j] != 0) storeCells(rowB, j, frB[j], level + 1);
-                }
+            for (int c = 0; c < 4; ++c) {
+              const int j = 4 * q + c;
+              if (j >= w0 && j <= w1) {
+                if (inA && frA[j] != 0) storeCells(rowA, j, frA[j], level + 1);
+                if (inB && frB[j] != 0) storeCells(rowB, j, frB[j], level + 1);
               }
             }
           }
         }
-        BFS_STAMP(ts3);
-        BFS_ACC(2, ts3 - ts2);
-        any_blk |= nz;
-        a_own = (nz | (lo >> 1) | (hi << 1)) & gmask;
       }
+      BFS_STAMP(ts3);
+      BFS_ACC(2, ts3 - ts2);
       ++level;
     }
     // ---- exchange: the outer D own rows go to the neighbours, theirs come into the halo lanes; stop flags
@@ -693,7 +760,7 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
         *reinterpret_cast<uint4*>(edge + pub_wr + 3 * W + q) = quad(blB + q);
       }
     }
-    if (any_blk) s_flag[slot] = 1;
+    if (acc != 0) s_flag[slot] = 1;
     if (wave_in_box) {  // wave-uniform: is anything of the robot's box still open, or a frontier cell inside the region?
       uint32_t open_any = 0;
       const uint32_t rrA = (uint32_t)(rowA_i - by0), rrB = (uint32_t)(rowB_i - by0);
@@ -740,7 +807,6 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
       __syncthreads();  // the records are free for the next exchange
     }
     ++xch;
-    any_blk = 0;
     BFS_STAMP(ts6);
     BFS_ACC(4, ts6 - ts5);
   }
