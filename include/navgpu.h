@@ -394,6 +394,47 @@ int navgpu_planner_check_trajectory(navgpu_fleet* fleet, uint32_t instance, cons
  * reference's order (cx outer, cy inner, cells for which getCellCosts returns false skipped).  Returns the
  * number of points of the full cloud. */
 int navgpu_planner_cost_cloud(navgpu_fleet* fleet, uint32_t instance, float* points, uint32_t capacity);
+/* replaces: the publish_traj_pc parameter (dwa_planner.cpp:160-163), per robot.  An enabled robot's navgpu_planner_cycle runs a
+ * terms pass behind its scoring launch and before the winner is selected (the reference builds the cloud before
+ * updateOscillationFlags, dwa_planner.cpp:321-357): every sample slot is scored again and the raw value of each critic, the
+ * first failing critic and the point count are kept.  Robots that are not enabled run the launches they ran before.  At most
+ * NAVGPU_TRAJ_CLOUD_MAX_ROBOTS robots of a fleet are enabled at once (NAVGPU_ERR_INVALID beyond that; the records live in
+ * memory that exists only for them); NAVGPU_ERR_STATE with two cycles in flight (navgpu_planner_set_cycles_in_flight, which in
+ * turn refuses 2 while a robot is enabled); NAVGPU_ERR_CAPACITY when max_sim_steps points do not fit a workgroup's LDS. */
+#define NAVGPU_TRAJ_CLOUD_MAX_ROBOTS 16
+int navgpu_planner_set_trajectory_cloud(navgpu_fleet* fleet, uint32_t first, uint32_t count, int32_t enable);
+/* replaces: the trajectory_cloud of DWAPlanner::findBestPath (dwa_planner.cpp:318-348): every point of every explored
+ * trajectory whose cost is >= 0, slot by slot and within a slot point by point.  points = up to `capacity` x
+ * {x, y, z, path_cost, goal_cost, occ_cost, total_cost} (MapGridCostPoint): x = (float)p_x, y = (float)p_y, z = 0,
+ * path_cost = (float)p_th, total_cost = (float)cost.  The reference assigns these five fields of an uninitialised local
+ * (dwa_planner.cpp:323, 339-343) and leaves goal_cost and occ_cost indeterminate; they are 0 here.
+ * reference_costs = 1: the cost is Trajectory::cost_ as SimpleScoredSamplingPlanner::scoreTrajectory left it
+ * (simple_scored_sampling_planner.cpp:50-79, 111-127): the in-order sum of the critic terms, cut at the first failing critic
+ * or behind the first term that takes it above the best cost of the slots before it - so most costs are partial sums, and a
+ * slot whose later critic would have failed can be a member.  reference_costs = 0: the cost is the full sum and the members
+ * are the slots whose full sum is >= 0 (independent of the order of the slots).
+ * Returns the number of points of the full cloud; points beyond `capacity` are not written and nothing is written behind the
+ * last point; points = NULL with capacity = 0 counts only.  The cloud is built at this call from the terms of the robot's last
+ * cycle.  NAVGPU_ERR_STATE: the robot is not enabled, no cycle has run since it was, or it was staged or reconfigured after
+ * that cycle; NAVGPU_ERR_INVALID: bad instance, or points == NULL with a capacity. */
+int navgpu_planner_trajectory_cloud(navgpu_fleet* fleet, uint32_t instance, int32_t reference_costs, float* points, uint32_t capacity);
+/* one sample slot of the last cycle of an enabled robot (no counterpart as a call: what scoreTrajectory,
+ * simple_scored_sampling_planner.cpp:50-79, works through for all_explored[i]) */
+typedef struct {
+  double critic[5];      /* raw (unscaled) value of obstacle, goal_front, alignment, path, goal (dwa_planner.cpp:167-173 after the
+                            oscillation critic); the failing critic holds its code; NaN where the reference never evaluated the
+                            critic: scale 0, or behind the first failing critic */
+  double cost_full;      /* every term summed; the failing critic's code; -1 for a slot the generator rejected */
+  double cost_ref;       /* Trajectory::cost_ in the reference's flow (early-out against the incumbent) */
+  int32_t first_fail;    /* 0 oscillation, 1 obstacle ... 5 goal, 6 none */
+  int32_t status;        /* NAVGPU_SAMPLE_* */
+  int32_t n_points;
+  int32_t member;        /* 1: the slot's points are in the cloud (reference_costs = 1) */
+  uint32_t point_offset; /* index of its first point in that cloud (the points of the members before it) */
+  uint32_t reserved;
+} navgpu_sample_terms;
+/* out = up to `capacity` slots in slot order; returns the number of slots.  Errors as for navgpu_planner_trajectory_cloud. */
+int navgpu_planner_sample_terms(navgpu_fleet* fleet, uint32_t instance, navgpu_sample_terms* out, uint32_t capacity);
 /* OscillationCostFunction state access (persists across cycles per instance) */
 int navgpu_planner_get_oscillation(navgpu_fleet* fleet, uint32_t first, uint32_t count, uint32_t* flags,
                                    float* prev_stationary_pos_xyz);

@@ -89,6 +89,16 @@ class PlanResult(C.Structure):
                 ("cost", C.c_double), ("drive", C.c_double * 3)]
 
 
+TRAJ_CLOUD_MAX_ROBOTS = 16
+
+
+class SampleTerms(C.Structure):
+    """navgpu_sample_terms: one sample slot of an enabled robot's last cycle (navgpu_planner_sample_terms)."""
+    _fields_ = [("critic", C.c_double * 5), ("cost_full", C.c_double), ("cost_ref", C.c_double), ("first_fail", C.c_int32),
+                ("status", C.c_int32), ("n_points", C.c_int32), ("member", C.c_int32), ("point_offset", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class LocalLimits(C.Structure):
     _fields_ = [("xy_goal_tolerance", C.c_double), ("yaw_goal_tolerance", C.c_double), ("rot_stopped_vel", C.c_double),
                 ("trans_stopped_vel", C.c_double), ("max_rot_vel", C.c_double), ("min_rot_vel", C.c_double),
@@ -336,6 +346,9 @@ SYMBOLS = [
     ("navgpu_planner_samples", C.c_int, [vp, u32, vp, vp, vp, u32]),
     ("navgpu_planner_check_trajectory", C.c_int, [vp, u32, vp, C.POINTER(i32)]),
     ("navgpu_planner_cost_cloud", C.c_int, [vp, u32, vp, u32]),
+    ("navgpu_planner_set_trajectory_cloud", C.c_int, [vp, u32, u32, i32]),
+    ("navgpu_planner_trajectory_cloud", C.c_int, [vp, u32, i32, vp, u32]),
+    ("navgpu_planner_sample_terms", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_planner_get_oscillation", C.c_int, [vp, u32, u32, vp, vp]),
     ("navgpu_planner_set_oscillation", C.c_int, [vp, u32, u32, vp, vp]),
     ("navgpu_local_plan_window", C.c_int, [vp, u32, vp, vp, dbl, i32, vp, u32, C.POINTER(u32), C.POINTER(u32)]),

@@ -173,6 +173,31 @@ struct PlannerDev {
   double* traj;               // [n][max_sim_steps][3]
 };
 
+// trajectory cloud (navgpu_planner_set_trajectory_cloud): what the terms pass keeps of one sample slot
+struct SampleTerms {
+  double v[5];         // raw (unscaled) values of the obstacle, goal_front, alignment, path and goal critics
+  int32_t first_fail;  // order of the first failing critic: 0 oscillation, 1..5 as above, 6 none
+  int32_t fail_code;   // its (negative) code
+  int32_t status;      // NAVGPU_SAMPLE_*
+  int32_t n_points;    // points of the trajectory (0: rejected by the generator)
+};
+static_assert(sizeof(SampleTerms) == 56, "terms record");
+// per-launch view of one enabled robot (traj_cloud_kernels.hip)
+struct TrajCloudDev {
+  const SampleTerms* terms;   // [max_samples]
+  navgpu_sample_terms* out;   // [max_samples] what k_traj_scan derives per slot
+  uint32_t* totals;           // [2] points of the cloud, sample slots
+  float* points;              // [capacity][7] or null
+  uint32_t capacity;          // points `points` holds
+  uint32_t slots_per_group;   // consecutive slots of a k_traj_emit workgroup
+  double scale[5];            // the critics' scales at the cycle (alignment: 0 when switched off)
+  int32_t reference_costs;
+};
+void launch_score_terms(const PlannerDev& pl, uint32_t inst, SampleTerms* terms, hipStream_t s);
+void launch_traj_scan(const PlannerDev& pl, const TrajCloudDev& t, uint32_t inst, hipStream_t s);
+void launch_traj_emit(const PlannerDev& pl, const TrajCloudDev& t, uint32_t inst, uint32_t n_slots, hipStream_t s);
+uint32_t traj_emit_slots_per_group(uint32_t max_sim_steps);  // 0: a trajectory of that many points does not fit a workgroup's LDS
+
 // legacy TrajectoryPlanner (tp_kernels.hip)
 struct TpOut {  // per generateTrajectory call
   double cost;

@@ -2,7 +2,7 @@
 // translation units share (navgpu_host.cpp: lifetime / costmap layers / DWA planner / measurement,
 // navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner,
 // navgpu_recovery.cpp: footprint-cost queries, RotateRecovery, CarrotPlanner, navgpu_voxel_export.cpp: voxel-layer debug
-// outputs).
+// outputs, navgpu_traj_cloud.cpp: DWAPlanner's trajectory cloud).
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -143,6 +143,26 @@ struct navgpu_fleet {
     void* d_xyz = nullptr;
     size_t xyz_bytes = 0;
   } vx;
+  // trajectory cloud (navgpu_traj_cloud.cpp): the robots navgpu_planner_set_trajectory_cloud enabled, each with the records
+  // its cycles' terms pass writes - memory that exists only for them - and what the read calls share
+  struct TrajCloud {
+    struct Robot {
+      uint32_t inst = 0;
+      SampleTerms* d_terms = nullptr;         // [cap_samples] written by the terms pass
+      navgpu_sample_terms* d_out = nullptr;   // [cap_samples] written by k_traj_scan at a read call
+      uint32_t cap_samples = 0;
+      bool have_cycle = false;                // a cycle has run since the robot was enabled
+      uint64_t gen = 0;                       // cycle_gen of that cycle
+      double scale[5] = {0, 0, 0, 0, 0};      // the critics' scales at that cycle
+    };
+    std::vector<Robot> robots;                // at most NAVGPU_TRAJ_CLOUD_MAX_ROBOTS
+    // the terms pass navgpu_planner_cycle runs while robots are enabled; set by the enabling call, so that the cycle's
+    // translation unit carries no reference to the feature's launchers (it also links without them: tests/tsan)
+    int (*terms_pass)(navgpu_fleet* f, uint32_t first, uint32_t count) = nullptr;
+    uint32_t* h_totals = nullptr;             // pinned [2]: points, slots (k_traj_scan)
+    float* d_points = nullptr;
+    size_t points_cap = 0;                    // points d_points holds
+  } tc;
   std::vector<uint8_t> obs_consumed;            // [n] an update has run on what navgpu_costmap_stage staged last
   navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers

@@ -1426,8 +1426,13 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
 #endif
   uint32_t n_blocks = 0;
   PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score(pl, first, count, nullptr, f->stream));
+  int rc_terms = NAVGPU_OK;
+  if (!f->tc.robots.empty()) {  // publish_traj_pc robots: their terms, under the oscillation flags the scorer saw (k_select updates them)
+    rc_terms = f->tc.terms_pass(f, first, count);
+  }
   PROFILED(f, NAVGPU_K_SELECT, launch_select(pl, first, count, n_blocks, f->stream));
   int rc = checkLaunch();
+  if (rc == NAVGPU_OK) rc = rc_terms;  // (the cycle itself is complete either way)
   if (f->cycles_in_flight > 1) {
     const int slot = prev_slot ^ 1;
     if (rc == NAVGPU_OK && hipEventRecord(f->ev_cycle[slot], f->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;
@@ -1445,6 +1450,7 @@ int navgpu_planner_set_cycles_in_flight(navgpu_fleet* f, int32_t cycles) {
   if (!f || cycles < 1 || cycles > 2) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   HIP_TRY(waitStream(f->stream));  // nothing in flight across the switch
+  if (cycles > 1 && !f->tc.robots.empty()) return NAVGPU_ERR_STATE;  // the trajectory cloud's records are one cycle's (navgpu_planner_set_trajectory_cloud)
   if (cycles > 1)
     for (hipEvent_t* e : {&f->ev_cycle[0], &f->ev_cycle[1], &f->ev_cm_h2d, &f->ev_pl_h2d})
       if (!*e) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));

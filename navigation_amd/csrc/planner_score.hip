@@ -386,9 +386,12 @@ __device__ __forceinline__ void loadImage(const PlannerDev& pl, const ScoreRobot
 
 // ---- stage: one lane per velocity sample - rollout, critics, the sample's outputs - and the workgroup's partial argmin
 // CHUNK: cells of a footprint edge fetched per LDS round trip (see planner_score.h); AGG: the general MapGrid step
-template <bool EXPLICIT, int CHUNK, bool AGG>
+// TERMS (k_score_terms*, the trajectory cloud's terms pass): the stage stores one SampleTerms record per slot to `terms` and
+// NOTHING else - no sample_cost / sample_status, no partial argmin, no counters (the cycle's own scoring launch has written those)
+template <bool EXPLICIT, int CHUNK, bool AGG, bool TERMS = false>
 __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRobot& r, const double* s_fp, const float (*s_axis)[kMaxAxis],
-                                             const uint8_t* s_dyn, double* s_rc, int* s_ri, int* s_cnt, const float* explicit_sample) {
+                                             const uint8_t* s_dyn, double* s_rc, int* s_ri, int* s_cnt, const float* explicit_sample,
+                                             SampleTerms* terms = nullptr) {
   const uint32_t tid = threadIdx.x;
   const navgpu_dwa_config& c = pl.cfg;
   const Geom& g = r.g;
@@ -422,6 +425,9 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
   const bool in_range = sidx < n_samples;
   double total = -1.0;
   int status = NAVGPU_SAMPLE_REJECTED;
+  struct NoTerms {};
+  [[maybe_unused]] std::conditional_t<TERMS, SampleTerms, NoTerms> rec{};  // (a slot the generator rejects keeps this one)
+  if constexpr (TERMS) rec = SampleTerms{{0, 0, 0, 0, 0}, 6, 0, NAVGPU_SAMPLE_REJECTED, 0};
 
   if (in_range) {
     float vs[3];
@@ -828,12 +834,18 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
           addCritic(total, en_goal, v_goal, sc_goal);
         }
       }
+      if constexpr (TERMS) {  // the raw critic values in critic order; the oscillation critic fails as order 0
+        rec = SampleTerms{{v_obs, v_gf, v_al, v_path, v_goal}, osc_fail ? 0 : first_fail, osc_fail ? -5 : (int32_t)fail_code, status, num_steps};
+      }
     }
-    if (!EXPLICIT && pl.sample_cost) {
+    if constexpr (TERMS) {
+      terms[sidx] = rec;
+    } else if (!EXPLICIT && pl.sample_cost) {
       pl.sample_cost[(size_t)inst * pl.max_samples + sidx] = total;
       pl.sample_status[(size_t)inst * pl.max_samples + sidx] = status;
     }
   }
+  if constexpr (TERMS) return;
 
   // ---- workgroup argmin (lowest index wins ties == first strict minimum of the sequential loop)
   const bool valid = in_range && status == NAVGPU_SAMPLE_SCORED && total >= 0.0;
@@ -915,8 +927,8 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_prep_gen(PlannerDev pl,
   storeImage(pl, r, s_dyn);
 }
 // k_score_gen<CHUNK> / k_score_gen_agg: the samples of a robot, from the image k_score_prep_gen stored
-template <int CHUNK, bool AGG>
-__device__ __forceinline__ void scoreGen(const PlannerDev& pl, uint32_t first) {
+template <int CHUNK, bool AGG, bool TERMS = false>
+__device__ __forceinline__ void scoreGen(const PlannerDev& pl, uint32_t first, SampleTerms* terms = nullptr) {
   extern __shared__ __align__(16) uint8_t s_dyn[];
   __shared__ double s_fp[2 * kMaxFootprint];
   __shared__ float s_axis[3][kMaxAxis];
@@ -937,7 +949,7 @@ __device__ __forceinline__ void scoreGen(const PlannerDev& pl, uint32_t first) {
   placeWindow(r);
   loadImage(pl, r, in, s_fp, s_axis, s_dyn);
   __builtin_amdgcn_s_setprio(0);
-  scoreSamples<false, CHUNK, AGG>(pl, r, s_fp, s_axis, s_dyn, s_rc, s_ri, s_cnt, nullptr);
+  scoreSamples<false, CHUNK, AGG, TERMS>(pl, r, s_fp, s_axis, s_dyn, s_rc, s_ri, s_cnt, nullptr, terms);
 }
 // k_score_explicit(_agg): checkTrajectory's one sample, on an image built in the workgroup itself
 template <bool AGG>
@@ -967,6 +979,16 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_explicit(PlannerDev pl,
 }
 __global__ __launch_bounds__(kScoreThreads) void k_score_explicit_agg(PlannerDev pl, uint32_t first, const float* explicit_sample) {
   scoreExplicit<true>(pl, first, explicit_sample);
+}
+
+// k_score_terms / k_score_terms_agg (the trajectory cloud's terms pass, navgpu_planner_set_trajectory_cloud): the general stage with
+// TERMS set, for ONE robot whose records go to `terms` [max_samples].  The footprint chunk only groups LDS reads (the
+// critic values do not depend on it), so one instantiation serves every footprint.
+__global__ __launch_bounds__(kScoreThreads) void k_score_terms(PlannerDev pl, uint32_t inst, SampleTerms* terms) {
+  scoreGen<16, false, true>(pl, inst, terms);
+}
+__global__ __launch_bounds__(kScoreThreads) void k_score_terms_agg(PlannerDev pl, uint32_t inst, SampleTerms* terms) {
+  scoreGen<16, true, true>(pl, inst, terms);
 }
 
 size_t score_window_bytes(uint32_t win) {  // costmap window + the four per-cell screens
@@ -1026,6 +1048,19 @@ uint32_t launch_score(const PlannerDev& pl_in, uint32_t first, uint32_t count, c
                                  : k_score_gen<16>;
   launchScore(gen, dim3(gen_blocks, count), kScoreThreads, win_bytes, s, pl, first, explicit_sample);
   return gen_blocks;
+}
+
+// The terms pass of one robot, behind the cycle's scoring launch: its image is rebuilt in its slot of pl.prep in the general
+// kernels' form (a table configuration's image has been consumed by k_score_sweep by now), then every slot is scored again
+// into `terms`.
+void launch_score_terms(const PlannerDev& pl_in, uint32_t inst, SampleTerms* terms, hipStream_t s) {
+  PlannerDev pl = pl_in;
+  const size_t win_bytes = score_window_bytes(pl.win);
+  pl.use_tables = 0;
+  pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
+  const uint32_t gen_blocks = (pl.max_samples + kScoreThreads - 1) / kScoreThreads;
+  launchScore(k_score_prep_gen, dim3(1, 1), kScoreThreads, win_bytes + score_scratch_bytes((int)pl.win), s, pl, inst);
+  launchScore(pl.mg_generic ? k_score_terms_agg : k_score_terms, dim3(gen_blocks, 1), kScoreThreads, win_bytes, s, pl, inst, terms);
 }
 
 #ifdef NAVGPU_PREP_TIMING

@@ -12,6 +12,7 @@ Method names follow the reference interfaces they front:
   carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
   voxel_points          costmap_2d_cloud / costmap_2d_markers voxelCallback (costmap_2d/src/costmap_2d_cloud.cpp:85-122)
   voxel_clearing_endpoints  VoxelLayer::raytraceFreespace's clearing_endpoints cloud (plugins/voxel_layer.cpp:286-381)
+  trajectory_cloud      DWAPlanner::findBestPath's trajectory_cloud (dwa_planner.cpp:318-348); sample_terms: the breakdown behind it
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -347,6 +348,34 @@ class Fleet:
         buf = np.zeros((cap, 7), np.float32)
         n = check(self.L.navgpu_planner_cost_cloud(self.h, instance, _ptr(buf), cap), "cost_cloud")
         return buf[:n].copy()
+
+    def set_trajectory_cloud(self, enable=True, first=0, count=None):
+        """publish_traj_pc per robot: an enabled robot's cycles keep the per-sample critic terms (at most 16 robots)."""
+        first, count = self._range(first, count)
+        check(self.L.navgpu_planner_set_trajectory_cloud(self.h, first, count, 1 if enable else 0), "set_trajectory_cloud")
+
+    def trajectory_cloud(self, instance, reference_costs=True):
+        """DWAPlanner's trajectory_cloud of one enabled robot's last cycle: (n, 7) float32 x, y, z, path_cost (= theta),
+        goal_cost, occ_cost, total_cost; every point of every explored trajectory with a cost >= 0, in slot order.
+        reference_costs: the reference's early-out costs, else every slot's full sum."""
+        ref = 1 if reference_costs else 0
+        n = check(self.L.navgpu_planner_trajectory_cloud(self.h, instance, ref, None, 0), "trajectory_cloud")
+        buf = np.zeros((n, 7), np.float32)
+        if n:
+            check(self.L.navgpu_planner_trajectory_cloud(self.h, instance, ref, _ptr(buf), n), "trajectory_cloud")
+        return buf
+
+    SAMPLE_TERMS_DTYPE = np.dtype([("critic", np.float64, 5), ("cost_full", np.float64), ("cost_ref", np.float64), ("first_fail", np.int32),
+                                   ("status", np.int32), ("n_points", np.int32), ("member", np.int32), ("point_offset", np.uint32),
+                                   ("reserved", np.uint32)])
+
+    def sample_terms(self, instance):
+        """Per-slot breakdown behind trajectory_cloud: a structured array (navgpu_sample_terms) in slot order."""
+        n = check(self.L.navgpu_planner_sample_terms(self.h, instance, None, 0), "sample_terms")
+        out = np.zeros(n, self.SAMPLE_TERMS_DTYPE)
+        if n:
+            check(self.L.navgpu_planner_sample_terms(self.h, instance, _ptr(out), n), "sample_terms")
+        return out
 
     def oscillation(self, first=0, count=None):
         first, count = self._range(first, count)

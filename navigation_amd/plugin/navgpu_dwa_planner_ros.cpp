@@ -10,7 +10,7 @@ PLUGINLIB_EXPORT_CLASS(navgpu::DWAPlannerROS, nav_core::BaseLocalPlanner)  // dw
 namespace navgpu {
 
 DWAPlannerROS::DWAPlannerROS() : tf_(NULL), costmap_ros_(NULL), odom_helper_("odom"), dsrv_(NULL), setup_(false),
-                                 initialized_(false), fleet_(NULL), sim_period_(0.05) {}
+                                 initialized_(false), publish_traj_pc_(false), fleet_(NULL), sim_period_(0.05) {}
 DWAPlannerROS::~DWAPlannerROS() {
   delete dsrv_;
   if (fleet_) navgpu_fleet_destroy(fleet_);
@@ -43,6 +43,12 @@ void DWAPlannerROS::initialize(std::string name, tf::TransformListener* tf, cost
   d.max_sim_steps = 256;
   if (navgpu_fleet_create(&d, &fleet_) != NAVGPU_OK)
     throw std::runtime_error(std::string("navgpu: ") + navgpu_last_error());  // init failures throw (obstacle_layer.cpp:113-114)
+
+  // publish_traj_pc (dwa_planner.cpp:163): the cycles keep the per-sample terms the trajectory cloud is built from.  Nothing is
+  // published here; trajectoryCloud() hands the points to whoever wants to.
+  private_nh.param("publish_traj_pc", publish_traj_pc_, false);
+  if (publish_traj_pc_ && navgpu_planner_set_trajectory_cloud(fleet_, 0, 1, 1) != NAVGPU_OK)
+    throw std::runtime_error(std::string("navgpu: ") + navgpu_last_error());
 
   if (private_nh.hasParam("odom_topic")) {
     std::string odom_topic;

@@ -32,6 +32,19 @@ class DWAPlannerROS : public nav_core::BaseLocalPlanner {
   bool computeVelocityCommands(geometry_msgs::Twist& cmd_vel);
   bool setPlan(const std::vector<geometry_msgs::PoseStamped>& orig_global_plan);
   bool isGoalReached();
+  // DWAPlanner's trajectory_cloud (dwa_planner.cpp:318-348) of the last computeVelocityCommands that ran findBestPath, as a flat
+  // vector of MapGridCostPoint records {x, y, z, path_cost, goal_cost, occ_cost, total_cost}; empty unless publish_traj_pc is set
+  // (or when the last cycle took the stop-and-rotate branch).  The adapter publishes nothing itself.
+  std::vector<float> trajectoryCloud() {
+    std::vector<float> points;
+    boost::unique_lock<boost::mutex> l(configuration_mutex_);
+    if (!publish_traj_pc_ || !fleet_) return points;
+    const int n = navgpu_planner_trajectory_cloud(fleet_, 0, 1, NULL, 0);
+    if (n <= 0) return points;
+    points.resize((size_t)n * 7);
+    if (navgpu_planner_trajectory_cloud(fleet_, 0, 1, points.data(), (uint32_t)n) != n) points.clear();
+    return points;
+  }
 
  private:
   void reconfigureCB(dwa_local_planner::DWAPlannerConfig& config, uint32_t level);
@@ -49,6 +62,7 @@ class DWAPlannerROS : public nav_core::BaseLocalPlanner {
   dynamic_reconfigure::Server<dwa_local_planner::DWAPlannerConfig>* dsrv_;
   dwa_local_planner::DWAPlannerConfig default_config_;
   bool setup_, initialized_;
+  bool publish_traj_pc_;
   // DWAPlanner::configuration_mutex_ (dwa_planner.h:163): reconfigure() takes it (dwa_planner.cpp:55) and so does
   // findBestPath (:301); here it also covers the staging and checkTrajectory, because cfg_ and the fleet's tables are
   // shared between the dynamic_reconfigure (spinner) thread and move_base's control thread.  libnavgpu serialises the
