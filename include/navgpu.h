@@ -823,6 +823,75 @@ int navgpu_global_planner_plan(navgpu_navfn* nav, uint32_t first, uint32_t count
 int navgpu_global_planner_plan_wavefront(navgpu_navfn* nav, uint32_t first, uint32_t count, const navgpu_global_planner_params* params,
                                          const double* starts_xy, const double* goals_xy, const int32_t* goal_cells_xy, navgpu_navfn_result* results);
 
+/* GlobalPlanner::makePlan end to end, world coordinates in and world poses out, for a batch of plans. */
+#define NAVGPU_ORIENT_NONE 0      /* GlobalPlanner.cfg orientation_mode, orientation_filter.h:43 */
+#define NAVGPU_ORIENT_FORWARD 1
+#define NAVGPU_ORIENT_INTERPOLATE 2
+#define NAVGPU_ORIENT_FORWARD_THEN_INTERPOLATE 3
+
+#define NAVGPU_MAKE_PLAN_OK 0
+#define NAVGPU_MAKE_PLAN_START_OFF_MAP 1  /* Costmap2D::worldToMap fails, planner_core.cpp:256-260 */
+#define NAVGPU_MAKE_PLAN_GOAL_OFF_MAP 2   /* :271-275 */
+#define NAVGPU_MAKE_PLAN_NO_PLAN 3        /* found_legal false, or "NO PATH!": the reference returns an empty plan */
+#define NAVGPU_MAKE_PLAN_BORDER 4         /* the library's own limit: start < 2 cells, goal < 1 cell from the border */
+
+typedef struct { double x, y, yaw; } navgpu_global_pose;
+typedef struct {
+  int32_t orientation_mode;  /* NAVGPU_ORIENT_*                                                                  */
+  int32_t wavefront;         /* 1: the expansion of navgpu_global_planner_plan_wavefront (use_dijkstra must be 1) */
+} navgpu_make_plan_options;
+typedef struct {
+  int32_t status;            /* NAVGPU_MAKE_PLAN_*                                                                */
+  int32_t n_poses;           /* path_length + 1 (+ 2 with old_navfn_behavior); 0 unless status is OK              */
+  int32_t found, cycles;     /* as navgpu_navfn_result; 0 for a plan that was not attempted                       */
+  int32_t start_cell[2], goal_cell[2]; /* Costmap2D::worldToMap's cells (what it succeeded for)                   */
+  float start_potential;
+  int32_t reserved;
+} navgpu_make_plan_result;
+/* replaces: GlobalPlanner::makePlan (planner_core.cpp:222-327) without its frame checks and publishers, for the plans
+ * [first, first+count): Costmap2D::worldToMap of start and goal (costmap_2d.cpp:208-220), GlobalPlanner::worldToMap (:201-215;
+ * its return value is ignored, as makePlan ignores it), clearRobotCell (:176-185, 283-286), the core of
+ * navgpu_global_planner_plan (or _plan_wavefront with options->wavefront), getPlanFromPotential (:351-395) with goal_copy
+ * (:306-312), and OrientationFilter::processPath (orientation_filter.cpp:53-111) on yaws.
+ * frames = count x {origin_x, origin_y, resolution} (the costmap of each plan); starts_xyyaw / goals_xyyaw = count x
+ * {x, y, yaw} in the world.  The cost bytes are those set with cost_mode 0.  clearRobotCell writes FREE_SPACE (0) to the start
+ * cell of the plan's own cost array on the device; it stays there until the next navgpu_navfn_set_costmap*, as the reference's
+ * write stays in its costmap.
+ * A plan whose status is not OK is not attempted (START_OFF_MAP, GOAL_OFF_MAP, BORDER) or came back empty (NO_PLAN); it does
+ * not disturb the others and is no error of the call.  tolerance, planner_window_x/y and default_tolerance have no effect in
+ * the reference and no counterpart here.
+ * The assembled plan: the traceback's points in reverse order, each origin + ((double)point + convert_offset) * resolution
+ * with yaw 0; the goal pose with old_navfn_behavior; the goal pose (goal_copy).  Then, with n = n_poses:
+ *   FORWARD      yaw[i] = atan2(y[i+1] - y[i], x[i+1] - x[i]) for i < n - 1
+ *   INTERPOLATE  yaw[0] = the start's yaw, then interpolate(0, n - 1)
+ *   FORWARD_THEN_INTERPOLATE  FORWARD; i = n - 3, last = yaw[i]; while i > 0 and |shortest_angular_distance(yaw[i-1], last)|
+ *                <= 0.35: --i (last is never updated, :72-81); yaw[0] = the start's yaw; interpolate(i, n - 1).  For n < 3 the
+ *                reference reads before its array; the library takes i = 0.
+ *   interpolate(a, b): increment = shortest_angular_distance(yaw[a], yaw[b]) / (b - a); yaw[i] = yaw[a] + increment * i for
+ *                a <= i <= b - the absolute i, as written (:107-110) - not normalised.
+ * shortest_angular_distance is navgpu_shortest_angular_distance (the fmod form).  The reference carries the yaws through
+ * quaternions (tf::createQuaternionMsgFromYaw / tf::getYaw, outside the reference tree); the library keeps yaws.
+ * Returns NAVGPU_ERR_INVALID for a bad range, a resolution that is not positive, an orientation_mode outside 0..3, the
+ * parameter limits of navgpu_global_planner_plan, or wavefront without use_dijkstra. */
+int navgpu_global_planner_make_plan(navgpu_navfn* nav, uint32_t first, uint32_t count, const navgpu_global_planner_params* params,
+                                    const navgpu_make_plan_options* options, const double* frames, const double* starts_xyyaw,
+                                    const double* goals_xyyaw, navgpu_make_plan_result* results);
+/* replaces: the plan vector GlobalPlanner::makePlan fills (planner_core.cpp:306-321), for the plans [first, first+count) as
+ * the last navgpu_global_planner_make_plan left them, concatenated in plan order: offsets[k] = first pose of plan first + k,
+ * offsets[count] = the total.  Offsets are always true; poses at or beyond capacity are not written; poses = NULL with
+ * capacity = 0 counts only (navgpu_voxel_points' conventions).  One device pass and one copy for the whole range; two calls
+ * give identical bytes.  NAVGPU_ERR_STATE if, for a plan of the range, make_plan is not the last call that set its costs or
+ * planned on it. */
+int navgpu_global_planner_plans(navgpu_navfn* nav, uint32_t first, uint32_t count, uint32_t capacity, navgpu_global_pose* poses,
+                                uint32_t* offsets);
+/* replaces: GlobalPlanner::publishPotential's data (planner_core.cpp:417-434) for the plans [first, first+count): grids = count
+ * x ny x nx bytes, maxima (may be NULL) = count floats.  max over the cells with potential < POT_HIGH; a cell is -1 where the
+ * potential is >= POT_HIGH, else (int8)(potential * publish_scale / max) in float arithmetic as written.  Where max == 0 the
+ * reference divides by zero; the library writes 0.  Reads the array that holds the plan's last result (as
+ * navgpu_navfn_potential).  The message's origin (:411-413) is the caller's. */
+int navgpu_global_planner_potential_grid(navgpu_navfn* nav, uint32_t first, uint32_t count, int32_t publish_scale, int8_t* grids,
+                                         float* maxima);
+
 /* ------------------------------------------------------------------------------------------ */
 /* amcl::AMCLLaser - the laser sensor update of a batch of particle filters (one per robot)   */
 /* ------------------------------------------------------------------------------------------ */

@@ -214,6 +214,26 @@ class GlobalPlannerParams(C.Structure):
             setattr(self, k, v)
 
 
+ORIENT_NONE, ORIENT_FORWARD, ORIENT_INTERPOLATE, ORIENT_FORWARD_THEN_INTERPOLATE = range(4)  # NAVGPU_ORIENT_*
+MAKE_PLAN_OK, MAKE_PLAN_START_OFF_MAP, MAKE_PLAN_GOAL_OFF_MAP, MAKE_PLAN_NO_PLAN, MAKE_PLAN_BORDER = range(5)  # NAVGPU_MAKE_PLAN_*
+
+
+class GlobalPose(C.Structure):
+    """Mirror of navgpu_global_pose (include/navgpu.h)."""
+    _fields_ = [("x", C.c_double), ("y", C.c_double), ("yaw", C.c_double)]
+
+
+class MakePlanOptions(C.Structure):
+    """Mirror of navgpu_make_plan_options (include/navgpu.h)."""
+    _fields_ = [("orientation_mode", C.c_int32), ("wavefront", C.c_int32)]
+
+
+class MakePlanResult(C.Structure):
+    """Mirror of navgpu_make_plan_result (include/navgpu.h)."""
+    _fields_ = [("status", C.c_int32), ("n_poses", C.c_int32), ("found", C.c_int32), ("cycles", C.c_int32), ("start_cell", C.c_int32 * 2),
+                ("goal_cell", C.c_int32 * 2), ("start_potential", C.c_float), ("reserved", C.c_int32)]
+
+
 AMCL_MODEL_BEAM, AMCL_MODEL_LIKELIHOOD_FIELD, AMCL_MODEL_LIKELIHOOD_FIELD_PROB, AMCL_MODEL_LIKELIHOOD_FIELD_GOMPERTZ = range(4)
 
 
@@ -380,6 +400,9 @@ SYMBOLS = [
     ("navgpu_navfn_plan_wavefront", C.c_int, [vp, u32, u32, vp, vp, i32, vp]),
     ("navgpu_global_planner_plan", C.c_int, [vp, u32, u32, C.POINTER(GlobalPlannerParams), vp, vp, vp, vp]),
     ("navgpu_global_planner_plan_wavefront", C.c_int, [vp, u32, u32, C.POINTER(GlobalPlannerParams), vp, vp, vp, vp]),
+    ("navgpu_global_planner_make_plan", C.c_int, [vp, u32, u32, C.POINTER(GlobalPlannerParams), C.POINTER(MakePlanOptions), vp, vp, vp, vp]),
+    ("navgpu_global_planner_plans", C.c_int, [vp, u32, u32, u32, vp, vp]),
+    ("navgpu_global_planner_potential_grid", C.c_int, [vp, u32, u32, i32, vp, vp]),
     ("navgpu_navfn_path", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_navfn_potential", C.c_int, [vp, u32, vp]),
     ("navgpu_navfn_costarr", C.c_int, [vp, u32, vp]),

@@ -1,45 +1,5 @@
 // navgpu_navfn_*: host side of the navfn::NavFn batch (see navfn_kernels.hip and include/navgpu.h).
-#include "navfn_rules.h"
-#include "navgpu_fleet.h"
-
-struct navgpu_navfn {
-  NavfnDev nv{};
-  uint32_t n = 0;
-  int device = 0;
-  std::recursive_mutex mu;  // calls on one handle are serialised inside the library (as on a fleet)
-  hipStream_t stream = nullptr;
-  std::vector<void*> allocs;
-  uint8_t* d_cmap = nullptr;   // staging for host cost maps: [n][ns_padded]
-  int32_t* d_goal = nullptr;   // [n][2]
-  int32_t* d_start = nullptr;  // [n][2]
-  navgpu_navfn_result* h_results = nullptr;  // pinned
-  double* d_xy = nullptr;      // [n][2][2] start / goal map coordinates (global_planner)
-  void* d_heap = nullptr;      // [n][ns_padded] AStarExpansion's queue_, allocated when A* is first asked for
-  NavfnWfStatus* h_wf_status = nullptr;  // pinned; the tiled wavefront's per-plan state as the host last read it
-  int32_t *d_seed_cells = nullptr, *d_stop = nullptr;  // [n][4] / [n] the tiled wavefront's seeds and stop cells
-  float* d_seed_vals = nullptr;                        // [n][4]
-  std::vector<uint8_t> final_array;      // [n] which potential array holds a plan's result (1: potalt, wavefront mode only)
-  template <class T>
-  int alloc(T** p, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    if (hipMalloc(&q, bytes) != hipSuccess) {
-      g_last_error = "hipMalloc failed (navfn)";
-      return NAVGPU_ERR_HIP;
-    }
-    hipMemsetAsync(q, 0, bytes, stream);
-    allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return NAVGPU_OK;
-  }
-};
-
-namespace {
-struct NavfnGuard {  // lock + make the handle's GPU current on the calling thread
-  std::lock_guard<std::recursive_mutex> lk;
-  explicit NavfnGuard(navgpu_navfn* h) : lk(h->mu) { (void)hipSetDevice(h->device); }
-};
-}  // namespace
+#include "navgpu_navfn.h"
 
 extern "C" {
 
@@ -104,8 +64,6 @@ int navgpu_navfn_destroy(navgpu_navfn* h) {
   return NAVGPU_OK;
 }
 
-static bool navfnRange(const navgpu_navfn* h, uint32_t first, uint32_t count) { return count > 0 && first < h->n && count <= h->n - first; }
-
 // NavFn's goal and start cells of a call: checked (the reference indexes its arrays with these without a check: keep them inside the
 // border) and uploaded
 static int navfnEndpoints(navgpu_navfn* h, const char* call, uint32_t count, const int32_t* goals, const int32_t* starts) {
@@ -125,6 +83,7 @@ static int navfnEndpoints(navgpu_navfn* h, const char* call, uint32_t count, con
 
 // the end of every plan call: the result records back, to the caller too, and the launches' own errors
 static int finishPlans(navgpu_navfn* h, uint32_t first, uint32_t count, navgpu_navfn_result* results) {
+  h->made.forget(first, count);  // nv.path and nv.results of these plans are no longer a make_plan call's
   HIP_TRY(hipMemcpyAsync(h->h_results + first, h->nv.results + first, sizeof(navgpu_navfn_result) * count, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(waitStream(h->stream));
   if (results) memcpy(results, h->h_results + first, sizeof(navgpu_navfn_result) * count);
@@ -140,6 +99,7 @@ int navgpu_navfn_set_costmap(navgpu_navfn* h, uint32_t first, uint32_t count, co
   for (uint32_t k = 0; k < maps; ++k)
     HIP_TRY(hipMemcpyAsync(h->d_cmap + (size_t)k * nv.ns_padded, cmap + (size_t)k * nv.ns, (size_t)nv.ns, hipMemcpyHostToDevice, h->stream));
   launch_navfn_costmap(nv, first, count, h->d_cmap, shared ? 0 : nv.ns_padded, cost_mode, allow_unknown, h->stream);
+  h->made.forget(first, count);
   HIP_TRY(waitStream(h->stream));  // the caller's buffer and the staging area are free again
   return checkLaunch();
 }
@@ -151,6 +111,7 @@ int navgpu_navfn_set_costmap_from_fleet(navgpu_navfn* h, uint32_t first, uint32_
   FleetGuard fleet_guard_(f);
   HIP_TRY(waitStream(f->stream));  // the fleet's last costmap update has landed
   launch_navfn_costmap(h->nv, first, count, f->cm.master + (size_t)fleet_first * f->cm.cells_padded, f->cm.cells_padded, 1, allow_unknown, h->stream);
+  h->made.forget(first, count);
   HIP_TRY(waitStream(h->stream));
   return checkLaunch();
 }
@@ -169,8 +130,8 @@ int navgpu_navfn_plan(navgpu_navfn* h, uint32_t first, uint32_t count, const int
 // The expansion as a tiled wavefront (navfn_kernels.hip: k_navfn_wf_*): rounds are queued a batch at a time, the per-plan
 // status (done / which array / rounds) is read between batches; a round launched after its plan has finished leaves at once.
 // seeds = count x 4 (cell, value) pairs (cell < 0: unused), stop_cells = count cells whose potential ends the search.
-static int runWavefront(navgpu_navfn* h, uint32_t first, uint32_t count, const NavfnWfRule& rule_in, const int32_t* seed_cells, const float* seed_vals,
-                        const int32_t* stop_cells, int at_start) {
+extern "C++" int runWavefront(navgpu_navfn* h, uint32_t first, uint32_t count, const NavfnWfRule& rule_in, const int32_t* seed_cells,
+                              const float* seed_vals, const int32_t* stop_cells, int at_start) {
   NavfnDev& nv = h->nv;
   constexpr int kTile = 32, kMaxRounds = 8192, kBatch = 16;
   NavfnWfRule rule = rule_in;
@@ -279,28 +240,10 @@ int navgpu_global_planner_plan_wavefront(navgpu_navfn* h, uint32_t first, uint32
   int rc = gpEndpoints(h, count, gp, starts, goals, goal_cells);
   if (rc) return rc;
   NavfnDev& nv = h->nv;
-  std::vector<int32_t> seed_cells((size_t)count * 4, -1), stop(count);
-  std::vector<float> seed_vals((size_t)count * 4, 0.0f);
-  for (uint32_t q = 0; q < count; ++q) {
-    if (!gp->old_navfn_behavior) {  // setPreciseStart(true)
-      int cells[4];
-      float vals[4];
-      preciseStartSeeds(starts[2 * q], starts[2 * q + 1], nv.nx, gp->neutral_cost, cells, vals);
-      std::copy(cells, cells + 4, seed_cells.begin() + 4 * q);
-      std::copy(vals, vals + 4, seed_vals.begin() + 4 * q);
-    } else {
-      seed_cells[4 * q] = (int)starts[2 * q] + nv.nx * (int)starts[2 * q + 1];  // toIndex(double, double)
-    }
-    stop[q] = (int)goals[2 * q] + nv.nx * (int)goals[2 * q + 1];
-  }
-  NavfnWfRule rule{};
-  rule.global_planner = 1;
-  rule.quadratic = gp->use_quadratic ? 1 : 0;
-  rule.outline = gp->outline_map ? 1 : 0;
-  rule.allow_unknown = gp->allow_unknown ? 1 : 0;
-  rule.lethal_cost = gp->lethal_cost;
-  rule.neutral_cost = gp->neutral_cost;
-  rule.cost_factor = gp->cost_factor;
+  std::vector<int32_t> seed_cells, stop;
+  std::vector<float> seed_vals;
+  gpWavefrontSeeds(nv.nx, *gp, count, starts, goals, seed_cells, seed_vals, stop);
+  const NavfnWfRule rule = gpWavefrontRule(*gp);
   rc = runWavefront(h, first, count, rule, seed_cells.data(), seed_vals.data(), stop.data(), 1);
   if (rc) return rc;
   launch_gp_wf_finish(nv, first, count, *gp, h->d_xy, h->d_xy + (size_t)2 * h->n, h->d_goal, h->stream);

@@ -5,13 +5,16 @@
   path          NavFn::getPathX / getPathY / getPathLen
   potential     NavFn::potarr
   costarr       NavFn::costarr
+  make_plan     GlobalPlanner::makePlan                  (global_planner/src/planner_core.cpp:222-327)
+  plans         the plans makePlan fills, concatenated   (planner_core.cpp:306-321, 351-395; orientation_filter.cpp:53-111)
+  potential_grid  GlobalPlanner::publishPotential's data (planner_core.cpp:417-434)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
 
 import numpy as np
 
-from ._lib import GlobalPlannerParams, NavfnResult, check, lib
+from ._lib import GlobalPlannerParams, GlobalPose, MakePlanOptions, MakePlanResult, NavfnResult, check, lib
 
 
 class NavFn:
@@ -80,6 +83,46 @@ class NavFn:
         check(fn(self.h, first, len(st), C.byref(gp), st.ctypes.data_as(C.c_void_p), gl.ctypes.data_as(C.c_void_p),
                  gc.ctypes.data_as(C.c_void_p), C.cast(res, C.c_void_p)), "global_planner_plan")
         return list(res)
+
+    def make_plan(self, frames, starts_xyyaw, goals_xyyaw, first=0, orientation_mode=0, wavefront=False, **params):
+        """navgpu_global_planner_make_plan: GlobalPlanner::makePlan from world poses (costs set with cost_mode=0).  frames:
+        (count, 3) {origin_x, origin_y, resolution}, or one triple for every plan.  Returns a list of MakePlanResult; a plan
+        whose status is not MAKE_PLAN_OK has no poses and does not fail the call."""
+        st = np.ascontiguousarray(starts_xyyaw, np.float64).reshape(-1, 3)
+        gl = np.ascontiguousarray(goals_xyyaw, np.float64).reshape(-1, 3)
+        assert len(st) == len(gl)
+        fr = np.ascontiguousarray(np.broadcast_to(np.asarray(frames, np.float64).reshape(-1, 3), (len(st), 3)))
+        gp = GlobalPlannerParams(**params)
+        opt = MakePlanOptions(int(orientation_mode), int(wavefront))
+        res = (MakePlanResult * len(st))()
+        check(self.L.navgpu_global_planner_make_plan(self.h, first, len(st), C.byref(gp), C.byref(opt), fr.ctypes.data_as(C.c_void_p),
+                                                     st.ctypes.data_as(C.c_void_p), gl.ctypes.data_as(C.c_void_p), C.cast(res, C.c_void_p)),
+              "global_planner_make_plan")
+        return list(res)
+
+    def plans(self, first=0, count=None, capacity=None):
+        """navgpu_global_planner_plans: (poses (total, 3) float64 {x, y, yaw}, offsets (count + 1,) uint32) of the last make_plan
+        over the range; plan first + k is poses[offsets[k]:offsets[k + 1]].  capacity: write at most that many poses (the
+        offsets stay true); 0 counts only."""
+        count = (self.n - first) if count is None else count
+        offsets = np.zeros(count + 1, np.uint32)
+        if capacity is None:
+            check(self.L.navgpu_global_planner_plans(self.h, first, count, 0, None, offsets.ctypes.data_as(C.c_void_p)), "global_planner_plans")
+            capacity = int(offsets[-1])
+        poses = np.zeros((capacity, C.sizeof(GlobalPose) // 8), np.float64)
+        if capacity:
+            check(self.L.navgpu_global_planner_plans(self.h, first, count, capacity, poses.ctypes.data_as(C.c_void_p),
+                                                     offsets.ctypes.data_as(C.c_void_p)), "global_planner_plans")
+        return poses, offsets
+
+    def potential_grid(self, first=0, count=None, publish_scale=100):
+        """navgpu_global_planner_potential_grid: (grids (count, ny, nx) int8, maxima (count,) float32)."""
+        count = (self.n - first) if count is None else count
+        grids = np.zeros((count, self.ny, self.nx), np.int8)
+        maxima = np.zeros(count, np.float32)
+        check(self.L.navgpu_global_planner_potential_grid(self.h, first, count, int(publish_scale), grids.ctypes.data_as(C.c_void_p),
+                                                          maxima.ctypes.data_as(C.c_void_p)), "global_planner_potential_grid")
+        return grids, maxima
 
     def path(self, plan=0):
         n = check(self.L.navgpu_navfn_path(self.h, plan, None, 0), "navfn_path")
