@@ -892,6 +892,101 @@ int navgpu_global_planner_plans(navgpu_navfn* nav, uint32_t first, uint32_t coun
 int navgpu_global_planner_potential_grid(navgpu_navfn* nav, uint32_t first, uint32_t count, int32_t publish_scale, int8_t* grids,
                                          float* maxima);
 
+/* navfn::NavfnROS (navfn/src/navfn_ros.cpp) round the same handle: makePlan end to end and the potential queries, for a batch of
+ * plans.  The cost bytes are those of navgpu_navfn_set_costmap with cost_mode 1 or of navgpu_navfn_set_costmap_from_fleet:
+ * makePlan hands getCharMap() to setCostmap(.., true, allow_unknown) (:263-264).  frames = count x {origin_x, origin_y,
+ * resolution}, as in navgpu_global_planner_make_plan; every call returns NAVGPU_ERR_INVALID for a bad range, a NULL argument
+ * or a resolution that is not positive.  The NAVGPU_MAKE_PLAN_* statuses are reused; BORDER does not occur. */
+#define NAVGPU_NAVFN_ROS_MAX_WINDOW 4096 /* candidates per axis of a tolerance window */
+typedef struct {
+  double tolerance_weight_dist_from_goal; /* the window's cost = dist * this + potential * the next (:316-317) */
+  double tolerance_weight_path_length;
+  int32_t wavefront;                      /* 1: the expansion of navgpu_navfn_plan_wavefront                   */
+  int32_t reserved;
+} navgpu_navfn_ros_params;
+typedef struct {
+  int32_t status;            /* NAVGPU_MAKE_PLAN_*                                                                       */
+  int32_t n_poses;           /* poses of the plan; 0 unless status is OK                                                 */
+  int32_t found, cycles;     /* calcNavFnDijkstra's return value (which makePlan ignores) and cycles; 0 if not attempted */
+  int32_t start_cell[2];     /* the robot's cell: NavFn's goal                                                           */
+  int32_t goal_cell[2];      /* the goal's (or the point's) cell; (0, 0) where worldToMap failed                         */
+  int32_t best_cell[2];      /* the cell of the window's best candidate, (-1, -1) without one                            */
+  int32_t candidates;        /* window candidates with potential < POT_HIGH                                              */
+  float start_potential;     /* potarr[NavFn's start] after the expansion                                                */
+  double best_x, best_y;     /* best_pose's position (:321)                                                              */
+  double best_cost;          /* its cost                                                                                 */
+} navgpu_navfn_ros_result;
+typedef struct { float x, y, z, pot_value; } navgpu_navfn_ros_cloud_point; /* PotarrPoint (navfn/potarr_point.h) */
+
+/* replaces: NavfnROS::makePlan(start, goal, tolerance, plan) (navfn_ros.cpp:218-374) without its frame checks and publishers,
+ * for the plans [first, first+count).  starts_xyyaw / goals_xyyaw = count x {x, y, yaw} in the world, tolerances = count doubles
+ * (the overload without a tolerance, :213-216, is the caller passing default_tolerance).  As written there:
+ *   worldToMap(start) fails -> START_OFF_MAP; worldToMap(goal) fails -> GOAL_OFF_MAP if tolerance <= 0, else the goal's cell is
+ *   (0, 0) (:282-289); NavFn's goal is the robot's cell and NavFn's start the goal's; calcNavFnDijkstra(true) through
+ *   navgpu_navfn_plan's bit-exact kernel (or navgpu_navfn_plan_wavefront's rounds with params->wavefront), its return value
+ *   ignored.  clearRobotCell is NOT called: this makePlan never calls it.
+ *   The tolerance window (:301-327): p.y = goal.y - tolerance, += resolution while <= goal.y + tolerance, inside it p.x
+ *   likewise - sequential fp64 sums, built on the host; for each candidate the potential of its cell (DBL_MAX off the map), a
+ *   candidate if < POT_HIGH, cost = sqrt(dx * dx + dy * dy) * tolerance_weight_dist_from_goal + potential *
+ *   tolerance_weight_path_length in fp64; the first candidate in scan order (y outer, x inner) of the lowest cost below DBL_MAX
+ *   is best_pose.  tolerance == 0 is one candidate; tolerance < 0 or NaN none (NO_PLAN).  One workgroup per plan, reduced
+ *   without atomics: a pure function of the inputs.
+ *   With a best_pose, getPlanFromPotential(best_pose) (:400-461): calcPath(4 nx) from its cell to the robot's over the same
+ *   potential; an empty path is NO_PLAN ("Failed to get a plan from potential when a legal potential was found").  The plan:
+ *   the path's points in reverse order, each origin + (double)point * resolution with yaw 0, then best_pose with the goal's
+ *   yaw (:333-335): n_poses = path length + 1.
+ * Limit: more than NAVGPU_NAVFN_ROS_MAX_WINDOW candidates on an axis of a window (tolerance > ~2048 resolution, or a sum that no
+ * longer moves) is NAVGPU_ERR_INVALID for the call; nothing has run then.  From the cells (0, 1) and (0, ny - 1) the
+ * reference's calcPath reads one element outside potarr; the library ends that walk as the reference does when those
+ * elements hold ordinary values (no path); a walk that only arrives on one of those two cells reads them, as in navgpu_navfn_plan.
+ * Departure: where calcPath fails after walking some points (out of steps, zero gradient, high potential) the reference's
+ * getPlanFromPotential reads getPathLen(), the points walked so far, and returns them as a plan; the library reports NO_PLAN and
+ * no poses, here and in navgpu_navfn_ros_plan_from_potential.
+ * Parity is bit for bit against the reference built with C's <math.h>, where NavFn's hypot on floats is hypot(double, double) (as
+ * navgpu_navfn_plan's walk has always restated it); with libstdc++'s math.h from GCC 6 on the same source calls hypotf and a
+ * few path points differ in the last bit.
+ * A plan whose status is not OK does not fail the call or disturb the others.  navgpu_navfn_potential then returns the
+ * potential, navgpu_navfn_path the second path (nothing for a plan whose status is not OK). */
+int navgpu_navfn_ros_make_plan(navgpu_navfn* nav, uint32_t first, uint32_t count, const navgpu_navfn_ros_params* params, const double* frames,
+                               const double* starts_xyyaw, const double* goals_xyyaw, const double* tolerances,
+                               navgpu_navfn_ros_result* results);
+/* replaces: the plan vector NavfnROS::makePlan / getPlanFromPotential fills (:331-336, 440-456), for the plans [first, first+count)
+ * as the last navgpu_navfn_ros_make_plan or navgpu_navfn_ros_plan_from_potential left them.  Conventions are
+ * navgpu_global_planner_plans': offsets always true, poses beyond capacity not written, NULL with capacity 0 counts only, one
+ * device pass and one copy.  NAVGPU_ERR_STATE if, for a plan of the range, neither of the two is the last call that set its
+ * costs or planned on it (navgpu_global_planner_make_plan included: the two families do not read each other's plans). */
+int navgpu_navfn_ros_plans(navgpu_navfn* nav, uint32_t first, uint32_t count, uint32_t capacity, navgpu_global_pose* poses, uint32_t* offsets);
+/* replaces: NavfnROS::getPlanFromPotential(goal, plan) (:400-461) on the potential each plan holds: worldToMap(goal) fails ->
+ * GOAL_OFF_MAP; setStart(goal's cell); calcPath(4 nx) to NavFn's goal, which is that of the last navgpu_navfn_ros_make_plan /
+ * _compute_potential on the plan ((0, 0) before any; results[k].start_cell reports it).  The plan is the reversed path, no goal
+ * appended: n_poses = path length, 0 -> NO_PLAN.  results[k].found = the walk's. */
+int navgpu_navfn_ros_plan_from_potential(navgpu_navfn* nav, uint32_t first, uint32_t count, const double* frames, const double* goals_xyyaw,
+                                         navgpu_navfn_ros_result* results);
+/* replaces: NavfnROS::computePotential(world_point) (:171-197): points_xy = count x {x, y}; worldToMap fails -> status
+ * GOAL_OFF_MAP (the reference returns false) and nothing runs for that plan; else NavFn's goal = the point's cell, start =
+ * (0, 0), calcNavFnDijkstra() without the early stop; results[k].found is its return value.  params: only wavefront is read. */
+int navgpu_navfn_ros_compute_potential(navgpu_navfn* nav, uint32_t first, uint32_t count, const navgpu_navfn_ros_params* params,
+                                       const double* frames, const double* points_xy, navgpu_navfn_ros_result* results);
+/* replaces: NavfnROS::getPointPotential (:157-169), batched: plan first + k has query_counts[k] points, packed in plan order in
+ * points_xy; potentials[q] = (double)potarr[cell], DBL_MAX where worldToMap fails.  One lane per query on the resident array. */
+int navgpu_navfn_ros_point_potential(navgpu_navfn* nav, uint32_t first, uint32_t count, const double* frames, const uint32_t* query_counts,
+                                     const double* points_xy, double* potentials);
+/* replaces: NavfnROS::validPointPotential(world_point, tolerance) (:130-155), batched as above with a tolerance per point:
+ * flags[q] = 1 if any candidate of the window (sequences as in make_plan) has potential < POT_HIGH.  The same limit of
+ * NAVGPU_NAVFN_ROS_MAX_WINDOW candidates per axis. */
+int navgpu_navfn_ros_valid_point_potential(navgpu_navfn* nav, uint32_t first, uint32_t count, const double* frames,
+                                           const uint32_t* query_counts, const double* points_xy, const double* tolerances, int32_t* flags);
+/* replaces: the `potential` topic's cloud (:342-368) for the plans [first, first+count): the cells with (double)potarr[i] < 10e7
+ * in row-major order, x = (float)(origin_x + (double)(i % nx) * resolution), y likewise, z = potarr[i] / potarr[start] * 20 in
+ * float arithmetic, pot_value = potarr[i].  start is NavFn's start cell as the last navgpu_navfn_ros_* call on the plan left it:
+ * the best cell after a make_plan that found one, the goal's cell (or (0, 0)) after one that did not, (0, 0) after
+ * compute_potential, the goal's cell after plan_from_potential; (0, 0) before any.  A zero or huge divisor gives what IEEE float
+ * division gives; nothing is patched.  Plans are concatenated: offsets[k] = first point of plan first + k, offsets[count] = the
+ * total, always true; points at or beyond capacity are not written; points = NULL with capacity 0 counts only.  The positions
+ * come from a prefix sum, not from atomics: two calls give identical bytes.  count <= 65535 and count * nx * ny < 2^32. */
+int navgpu_navfn_ros_potential_cloud(navgpu_navfn* nav, uint32_t first, uint32_t count, const double* frames, uint32_t capacity,
+                                     navgpu_navfn_ros_cloud_point* points, uint32_t* offsets);
+
 /* ------------------------------------------------------------------------------------------ */
 /* amcl::AMCLLaser - the laser sensor update of a batch of particle filters (one per robot)   */
 /* ------------------------------------------------------------------------------------------ */

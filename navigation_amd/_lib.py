@@ -234,6 +234,27 @@ class MakePlanResult(C.Structure):
                 ("goal_cell", C.c_int32 * 2), ("start_potential", C.c_float), ("reserved", C.c_int32)]
 
 
+class NavfnRosParams(C.Structure):
+    """Mirror of navgpu_navfn_ros_params (include/navgpu.h); defaults = NavfnROS.cfg's weights."""
+    _fields_ = [("tolerance_weight_dist_from_goal", C.c_double), ("tolerance_weight_path_length", C.c_double), ("wavefront", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class NavfnRosResult(C.Structure):
+    """Mirror of navgpu_navfn_ros_result (include/navgpu.h)."""
+    _fields_ = [("status", C.c_int32), ("n_poses", C.c_int32), ("found", C.c_int32), ("cycles", C.c_int32), ("start_cell", C.c_int32 * 2),
+                ("goal_cell", C.c_int32 * 2), ("best_cell", C.c_int32 * 2), ("candidates", C.c_int32), ("start_potential", C.c_float),
+                ("best_x", C.c_double), ("best_y", C.c_double), ("best_cost", C.c_double)]
+
+
+class NavfnRosCloudPoint(C.Structure):
+    """Mirror of navgpu_navfn_ros_cloud_point (include/navgpu.h)."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("pot_value", C.c_float)]
+
+
+NAVFN_ROS_MAX_WINDOW = 4096  # NAVGPU_NAVFN_ROS_MAX_WINDOW
+
+
 AMCL_MODEL_BEAM, AMCL_MODEL_LIKELIHOOD_FIELD, AMCL_MODEL_LIKELIHOOD_FIELD_PROB, AMCL_MODEL_LIKELIHOOD_FIELD_GOMPERTZ = range(4)
 
 
@@ -403,6 +424,13 @@ SYMBOLS = [
     ("navgpu_global_planner_make_plan", C.c_int, [vp, u32, u32, C.POINTER(GlobalPlannerParams), C.POINTER(MakePlanOptions), vp, vp, vp, vp]),
     ("navgpu_global_planner_plans", C.c_int, [vp, u32, u32, u32, vp, vp]),
     ("navgpu_global_planner_potential_grid", C.c_int, [vp, u32, u32, i32, vp, vp]),
+    ("navgpu_navfn_ros_make_plan", C.c_int, [vp, u32, u32, C.POINTER(NavfnRosParams), vp, vp, vp, vp, vp]),
+    ("navgpu_navfn_ros_plans", C.c_int, [vp, u32, u32, u32, vp, vp]),
+    ("navgpu_navfn_ros_plan_from_potential", C.c_int, [vp, u32, u32, vp, vp, vp]),
+    ("navgpu_navfn_ros_compute_potential", C.c_int, [vp, u32, u32, C.POINTER(NavfnRosParams), vp, vp, vp]),
+    ("navgpu_navfn_ros_point_potential", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+    ("navgpu_navfn_ros_valid_point_potential", C.c_int, [vp, u32, u32, vp, vp, vp, vp, vp]),
+    ("navgpu_navfn_ros_potential_cloud", C.c_int, [vp, u32, u32, vp, u32, vp, vp]),
     ("navgpu_navfn_path", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_navfn_potential", C.c_int, [vp, u32, vp]),
     ("navgpu_navfn_costarr", C.c_int, [vp, u32, vp]),

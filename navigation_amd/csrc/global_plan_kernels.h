@@ -13,6 +13,18 @@ struct GpPlanRec {
   int32_t n_path, n_poses, mode, pad;
 };
 
+// Costmap2D::worldToMap (costmap_2d.cpp:208-220) on a map of nx x ny cells.  (int) of a quotient outside int's range is 0x80000000
+// on the reference's amd64 builds, which as unsigned fails the size test: restated as "off the map" (a NaN takes the same way).
+__host__ __device__ inline bool costmapWorldToMap(double wx, double wy, double origin_x, double origin_y, double resolution, int nx, int ny,
+                                                  int32_t cell[2]) {
+  if (wx < origin_x || wy < origin_y) return false;
+  const double qx = (wx - origin_x) / resolution, qy = (wy - origin_y) / resolution;
+  if (!(qx < 2147483648.0) || !(qy < 2147483648.0)) return false;
+  cell[0] = (int)qx;
+  cell[1] = (int)qy;
+  return cell[0] < nx && cell[1] < ny;
+}
+
 // costarr[first + k][cells[k]] = FREE_SPACE for cells[k] >= 0
 void launch_gp_clear_cells(const NavfnDev& nv, uint32_t first, uint32_t count, const int32_t* cells, hipStream_t s);
 // offsets[0 .. count] = exclusive prefix sums of recs[k].n_poses

@@ -2,46 +2,42 @@
 // (global_plan_kernels.hip has the kernels, navgpu_navfn.cpp the handle and the expansion's entry points; include/navgpu.h the contract).
 #include "navgpu_navfn.h"
 
-namespace {
+using navgpu::costmapWorldToMap;
 
-// Costmap2D::worldToMap (costmap_2d.cpp:208-220) on a map of nx x ny cells.  (int) of a quotient outside int's range is 0x80000000
-// on the reference's amd64 builds, which as unsigned fails the size test: restated as "off the map" (a NaN takes the same way).
-bool costmapWorldToMap(double wx, double wy, double origin_x, double origin_y, double resolution, int nx, int ny, int32_t cell[2]) {
-  if (wx < origin_x || wy < origin_y) return false;
-  const double qx = (wx - origin_x) / resolution, qy = (wy - origin_y) / resolution;
-  if (!(qx < 2147483648.0) || !(qy < 2147483648.0)) return false;
-  cell[0] = (int)qx;
-  cell[1] = (int)qy;
-  return cell[0] < nx && cell[1] < ny;
-}
-
-// the buffers of the three calls, allocated when the first of them runs
-int reserveMadePlans(navgpu_navfn* h) {
+// navgpu_global_planner_plans and navgpu_navfn_ros_plans: the plans of the range as their maker's records describe them
+int assembleMadePlans(navgpu_navfn* h, uint32_t first, uint32_t count, uint8_t maker, uint32_t capacity, navgpu_global_pose* poses, uint32_t* offsets) {
+  if (!h || !offsets || (!poses && capacity) || !navfnRange(h, first, count)) return NAVGPU_ERR_INVALID;
+  NavfnGuard guard_(h);
   MadePlans& m = h->made;
-  if (m.d_maxima) return NAVGPU_OK;
-  m.valid.assign(h->n, 0);
-  m.rec.assign(h->n, navgpu::GpPlanRec{});
-  int rc = 0;
-  if (!rc && !m.d_rec) rc = h->alloc(&m.d_rec, h->n);
-  if (!rc && !m.d_clear) rc = h->alloc(&m.d_clear, h->n);
-  if (!rc && !m.d_alt) rc = h->alloc(&m.d_alt, h->n);
-  if (!rc) rc = h->alloc(&m.d_maxima, h->n);  // last: its presence says the others exist
-  return rc;
-}
-
-// a device buffer that only grows; what it replaces is freed with the handle
-template <class T>
-int growBuffer(navgpu_navfn* h, T** buf, size_t* have, size_t want) {
-  if (want <= *have) return NAVGPU_OK;
-  T* q = nullptr;
-  const int rc = h->alloc(&q, want);
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    if (m.valid.empty() || m.valid[first + k] != maker) {
+      g_last_error = maker == kMadeByGlobalPlanner
+                         ? "navgpu_global_planner_plans: no navgpu_global_planner_make_plan since the plan's costs were set or it was planned otherwise"
+                         : "navgpu_navfn_ros_plans: no navgpu_navfn_ros_make_plan / _plan_from_potential since the plan's costs were set or it was planned otherwise";
+      return NAVGPU_ERR_STATE;
+    }
+    total += (uint64_t)m.rec[first + k].n_poses;
+  }
+  // one buffer, one copy: the offsets (padded to the poses' alignment), then the poses that fit
+  const size_t n_write = (size_t)std::min<uint64_t>(total, capacity);
+  const size_t off_bytes = ((size_t)(count + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
+  const size_t bytes = off_bytes + n_write * sizeof(navgpu_global_pose);
+  int rc = growBuffer(h, &m.d_out, &m.out_bytes, bytes);
   if (rc) return rc;
-  *buf = q;
-  *have = want;
+  uint32_t* d_offsets = reinterpret_cast<uint32_t*>(m.d_out);
+  navgpu_global_pose* d_poses = reinterpret_cast<navgpu_global_pose*>(m.d_out + off_bytes);
+  launch_gp_plan_scan(m.d_rec + first, count, d_offsets, h->stream);
+  launch_gp_plan_emit(h->nv, first, count, m.d_rec + first, d_offsets, d_poses, (uint32_t)n_write, h->stream);
+  m.h_out.resize(bytes);
+  HIP_TRY(hipMemcpyAsync(m.h_out.data(), m.d_out, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  rc = checkLaunch();
+  if (rc) return rc;
+  memcpy(offsets, m.h_out.data(), sizeof(uint32_t) * (count + 1));
+  if (n_write) memcpy(poses, m.h_out.data() + off_bytes, n_write * sizeof(navgpu_global_pose));
   return NAVGPU_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -164,7 +160,7 @@ int navgpu_global_planner_make_plan(navgpu_navfn* h, uint32_t first, uint32_t co
       rec.n_poses = r.n_poses;
       rec.mode = opt->orientation_mode;
     }
-    m.valid[first + k] = 1;
+    m.valid[first + k] = kMadeByGlobalPlanner;
   }
   HIP_TRY(hipMemcpyAsync(m.d_rec + first, m.rec.data() + first, sizeof(navgpu::GpPlanRec) * count, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(waitStream(h->stream));
@@ -172,35 +168,7 @@ int navgpu_global_planner_make_plan(navgpu_navfn* h, uint32_t first, uint32_t co
 }
 
 int navgpu_global_planner_plans(navgpu_navfn* h, uint32_t first, uint32_t count, uint32_t capacity, navgpu_global_pose* poses, uint32_t* offsets) {
-  if (!h || !offsets || (!poses && capacity) || !navfnRange(h, first, count)) return NAVGPU_ERR_INVALID;
-  NavfnGuard guard_(h);
-  MadePlans& m = h->made;
-  uint64_t total = 0;
-  for (uint32_t k = 0; k < count; ++k) {
-    if (m.valid.empty() || !m.valid[first + k]) {
-      g_last_error = "navgpu_global_planner_plans: no navgpu_global_planner_make_plan since the plan's costs were set or it was planned otherwise";
-      return NAVGPU_ERR_STATE;
-    }
-    total += (uint64_t)m.rec[first + k].n_poses;
-  }
-  // one buffer, one copy: the offsets (padded to the poses' alignment), then the poses that fit
-  const size_t n_write = (size_t)std::min<uint64_t>(total, capacity);
-  const size_t off_bytes = ((size_t)(count + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
-  const size_t bytes = off_bytes + n_write * sizeof(navgpu_global_pose);
-  int rc = growBuffer(h, &m.d_out, &m.out_bytes, bytes);
-  if (rc) return rc;
-  uint32_t* d_offsets = reinterpret_cast<uint32_t*>(m.d_out);
-  navgpu_global_pose* d_poses = reinterpret_cast<navgpu_global_pose*>(m.d_out + off_bytes);
-  launch_gp_plan_scan(m.d_rec + first, count, d_offsets, h->stream);
-  launch_gp_plan_emit(h->nv, first, count, m.d_rec + first, d_offsets, d_poses, (uint32_t)n_write, h->stream);
-  m.h_out.resize(bytes);
-  HIP_TRY(hipMemcpyAsync(m.h_out.data(), m.d_out, bytes, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(waitStream(h->stream));
-  rc = checkLaunch();
-  if (rc) return rc;
-  memcpy(offsets, m.h_out.data(), sizeof(uint32_t) * (count + 1));
-  if (n_write) memcpy(poses, m.h_out.data() + off_bytes, n_write * sizeof(navgpu_global_pose));
-  return NAVGPU_OK;
+  return assembleMadePlans(h, first, count, kMadeByGlobalPlanner, capacity, poses, offsets);
 }
 
 int navgpu_global_planner_potential_grid(navgpu_navfn* h, uint32_t first, uint32_t count, int32_t publish_scale, int8_t* grids, float* maxima) {

@@ -8,13 +8,19 @@
   make_plan     GlobalPlanner::makePlan                  (global_planner/src/planner_core.cpp:222-327)
   plans         the plans makePlan fills, concatenated   (planner_core.cpp:306-321, 351-395; orientation_filter.cpp:53-111)
   potential_grid  GlobalPlanner::publishPotential's data (planner_core.cpp:417-434)
+  navfn_ros_make_plan / navfn_ros_plans   NavfnROS::makePlan                 (navfn/src/navfn_ros.cpp:218-374)
+  navfn_ros_plan_from_potential           NavfnROS::getPlanFromPotential     (:400-461)
+  navfn_ros_compute_potential             NavfnROS::computePotential         (:171-197)
+  navfn_ros_point_potential / navfn_ros_valid_point_potential   getPointPotential / validPointPotential (:130-169)
+  navfn_ros_potential_cloud               the `potential` topic's cloud      (:342-368)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
 
 import numpy as np
 
-from ._lib import GlobalPlannerParams, GlobalPose, MakePlanOptions, MakePlanResult, NavfnResult, check, lib
+from ._lib import (GlobalPlannerParams, GlobalPose, MakePlanOptions, MakePlanResult, NavfnResult, NavfnRosCloudPoint, NavfnRosParams,
+                   NavfnRosResult, check, lib)
 
 
 class NavFn:
@@ -123,6 +129,97 @@ class NavFn:
         check(self.L.navgpu_global_planner_potential_grid(self.h, first, count, int(publish_scale), grids.ctypes.data_as(C.c_void_p),
                                                           maxima.ctypes.data_as(C.c_void_p)), "global_planner_potential_grid")
         return grids, maxima
+
+    def _frames(self, frames, count):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(frames, np.float64).reshape(-1, 3), (count, 3)))
+
+    def navfn_ros_make_plan(self, frames, starts_xyyaw, goals_xyyaw, tolerances=0.0, first=0, w_dist=1.0, w_len=0.0, wavefront=False):
+        """navgpu_navfn_ros_make_plan: NavfnROS::makePlan from world poses (costs set with cost_mode=1 or from a fleet).
+        tolerances: one per plan, or one for all.  Returns a list of NavfnRosResult."""
+        st = np.ascontiguousarray(starts_xyyaw, np.float64).reshape(-1, 3)
+        gl = np.ascontiguousarray(goals_xyyaw, np.float64).reshape(-1, 3)
+        assert len(st) == len(gl)
+        fr = self._frames(frames, len(st))
+        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tolerances, np.float64).reshape(-1), (len(st),)))
+        pr = NavfnRosParams(float(w_dist), float(w_len), int(wavefront), 0)
+        res = (NavfnRosResult * len(st))()
+        check(self.L.navgpu_navfn_ros_make_plan(self.h, first, len(st), C.byref(pr), fr.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p),
+                                                gl.ctypes.data_as(C.c_void_p), tol.ctypes.data_as(C.c_void_p), C.cast(res, C.c_void_p)),
+              "navfn_ros_make_plan")
+        return list(res)
+
+    def navfn_ros_plans(self, first=0, count=None, capacity=None):
+        """navgpu_navfn_ros_plans: (poses (total, 3) float64 {x, y, yaw}, offsets (count + 1,) uint32), as plans()."""
+        count = (self.n - first) if count is None else count
+        offsets = np.zeros(count + 1, np.uint32)
+        if capacity is None:
+            check(self.L.navgpu_navfn_ros_plans(self.h, first, count, 0, None, offsets.ctypes.data_as(C.c_void_p)), "navfn_ros_plans")
+            capacity = int(offsets[-1])
+        poses = np.zeros((capacity, C.sizeof(GlobalPose) // 8), np.float64)
+        check(self.L.navgpu_navfn_ros_plans(self.h, first, count, capacity, poses.ctypes.data_as(C.c_void_p) if capacity else None,
+                                            offsets.ctypes.data_as(C.c_void_p)), "navfn_ros_plans")
+        return poses[:min(capacity, int(offsets[-1]))], offsets
+
+    def navfn_ros_plan_from_potential(self, frames, goals_xyyaw, first=0):
+        """navgpu_navfn_ros_plan_from_potential: getPlanFromPotential on the potential each plan holds; navfn_ros_plans reads the plans."""
+        gl = np.ascontiguousarray(goals_xyyaw, np.float64).reshape(-1, 3)
+        fr = self._frames(frames, len(gl))
+        res = (NavfnRosResult * len(gl))()
+        check(self.L.navgpu_navfn_ros_plan_from_potential(self.h, first, len(gl), fr.ctypes.data_as(C.c_void_p), gl.ctypes.data_as(C.c_void_p),
+                                                          C.cast(res, C.c_void_p)), "navfn_ros_plan_from_potential")
+        return list(res)
+
+    def navfn_ros_compute_potential(self, frames, points_xy, first=0, wavefront=False):
+        """navgpu_navfn_ros_compute_potential: computePotential of one world point per plan."""
+        pt = np.ascontiguousarray(points_xy, np.float64).reshape(-1, 2)
+        fr = self._frames(frames, len(pt))
+        pr = NavfnRosParams(1.0, 0.0, int(wavefront), 0)
+        res = (NavfnRosResult * len(pt))()
+        check(self.L.navgpu_navfn_ros_compute_potential(self.h, first, len(pt), C.byref(pr), fr.ctypes.data_as(C.c_void_p),
+                                                        pt.ctypes.data_as(C.c_void_p), C.cast(res, C.c_void_p)), "navfn_ros_compute_potential")
+        return list(res)
+
+    def _queries(self, frames, points_xy, first, count):
+        """points_xy: one (m_k, 2) array per plan -> (frames, counts, packed points)"""
+        count = (self.n - first) if count is None else count
+        per_plan = [np.asarray(p, np.float64).reshape(-1, 2) for p in points_xy]
+        assert len(per_plan) == count
+        counts = np.array([len(p) for p in per_plan], np.uint32)
+        packed = np.ascontiguousarray(np.concatenate(per_plan) if per_plan else np.zeros((0, 2)))
+        return count, self._frames(frames, count), counts, packed
+
+    def navfn_ros_point_potential(self, frames, points_xy, first=0, count=None):
+        """navgpu_navfn_ros_point_potential: points_xy is one (m_k, 2) array per plan; returns the packed float64 potentials."""
+        count, fr, counts, packed = self._queries(frames, points_xy, first, count)
+        out = np.zeros(len(packed), np.float64)
+        check(self.L.navgpu_navfn_ros_point_potential(self.h, first, count, fr.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                      packed.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)), "navfn_ros_point_potential")
+        return out
+
+    def navfn_ros_valid_point_potential(self, frames, points_xy, tolerances, first=0, count=None):
+        """navgpu_navfn_ros_valid_point_potential: tolerances packed like the points (or one for all); returns int32 flags."""
+        count, fr, counts, packed = self._queries(frames, points_xy, first, count)
+        tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tolerances, np.float64).reshape(-1), (len(packed),)))
+        out = np.zeros(len(packed), np.int32)
+        check(self.L.navgpu_navfn_ros_valid_point_potential(self.h, first, count, fr.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                                                            packed.ctypes.data_as(C.c_void_p), tol.ctypes.data_as(C.c_void_p),
+                                                            out.ctypes.data_as(C.c_void_p)), "navfn_ros_valid_point_potential")
+        return out
+
+    def navfn_ros_potential_cloud(self, frames, first=0, count=None, capacity=None):
+        """navgpu_navfn_ros_potential_cloud: (points (total, 4) float32 {x, y, z, pot_value}, offsets (count + 1,) uint32)."""
+        count = (self.n - first) if count is None else count
+        fr = self._frames(frames, count)
+        offsets = np.zeros(count + 1, np.uint32)
+        if capacity is None:
+            check(self.L.navgpu_navfn_ros_potential_cloud(self.h, first, count, fr.ctypes.data_as(C.c_void_p), 0, None,
+                                                          offsets.ctypes.data_as(C.c_void_p)), "navfn_ros_potential_cloud")
+            capacity = int(offsets[-1])
+        pts = np.zeros((capacity, C.sizeof(NavfnRosCloudPoint) // 4), np.float32)
+        check(self.L.navgpu_navfn_ros_potential_cloud(self.h, first, count, fr.ctypes.data_as(C.c_void_p), capacity,
+                                                      pts.ctypes.data_as(C.c_void_p) if capacity else None, offsets.ctypes.data_as(C.c_void_p)),
+              "navfn_ros_potential_cloud")
+        return pts[:min(capacity, int(offsets[-1]))], offsets
 
     def path(self, plan=0):
         n = check(self.L.navgpu_navfn_path(self.h, plan, None, 0), "navfn_path")
