@@ -90,7 +90,9 @@ typedef struct {
   uint32_t max_footprint;   /* capacity: footprint polygon vertices                                     */
   uint32_t max_sim_steps;   /* capacity: trajectory points (ceil(sim_time/sim_granularity) or the
                                per-sample bound when discretize_by_time = 0)                            */
-  int32_t keep_sample_costs;/* 1: keep every sample's total cost + status for navgpu_planner_samples    */
+  int32_t keep_sample_costs;/* 1: keep every sample's total cost + status for navgpu_planner_samples.  The failure code of an
+                               invalid sample (-2 .. -9) is computed only when it is kept: without this the product scoring launch
+                               decides validity alone (same navgpu_plan_result, bit for bit)                */
   int32_t rolling_window;   /* LayeredCostmap(rolling_window): every update re-centres the grids on the robot
                                (Costmap2D::updateOrigin, costmap_2d.cpp:264-313; not with NAVGPU_LAYER_STATIC,
                                whose rolling branch needs tf)                                            */

@@ -22,6 +22,24 @@
 // scoreTrajectory returns the code of the FIRST critic in the list that fails anywhere on the trajectory, the obstacle
 // critic is the first of those a walk can fail, and the other critics' failures are kept by order as before.
 // A full queue stalls the lanes that could not push: they take the same step again in the next block.
+//
+// Validity, not codes, unless the codes are kept (template parameter KEEP).  navgpu_plan_result holds the winner, n_scored (the
+// slots the generator accepted) and n_valid (the slots with a total >= 0); WHICH code an invalid sample got (-2 .. -9) reaches a
+// caller only through pl.sample_cost / pl.sample_status, which exist only with navgpu_fleet_desc::keep_sample_costs - as in the
+// reference, whose findBestTrajectory only tests `cost >= 0` (simple_scored_sampling_planner.cpp:111).
+//   KEEP = true   (pl.sample_cost != nullptr) everything above: a lane whose later critic has failed rolls on while an earlier one
+//                 in the list could still fail, the failing cell's grid value says -3 or -2, every slot's total and status are stored.
+//   KEEP = false  (the product form) the same partial results and the same two counters per robot, hence the same
+//                 navgpu_plan_result bit for bit, and nothing else:
+//                 - the robot-level exit: k_score_prep_tab's start_fail (aux[8]) says that the path or goal critic fails at the
+//                   robot's own cell - point 0 of every trajectory, and both critics stop at a failing point - so no accepted
+//                   sample can be valid.  The workgroup counts its accepted slots, reports "no valid sample" like an idle
+//                   workgroup and returns before the image copy: no rollout, no walk.  (Not with that critic's scale at 0:
+//                   its screen is clear then.  The robot's wavefronts still run: their grids are exposed on their own.)
+//                 - the lane-level stop: alive_m means "no critic has failed"; a lane that has failed anything pushes no further
+//                   walk, asks for no last-point cost and records no last cell.
+//                 - no codes: first_fail < 6 only says "failed"; fail_code, fail_cell, the failing cell's grid load and the
+//                   per-sample stores are not compiled in.  A failed lane's total is -1.
 #include "planner_score.h"
 
 namespace navgpu {
@@ -58,7 +76,9 @@ __device__ unsigned long long g_sweep_stats[16];
 
 // TRIGF: navgpu_dwa_config::rollout_trig = 1 - computeNewPositions' cos(pos[2]) / sin(pos[2]) name the float functions and
 // vel[0] * cos(pos[2]) is a float product (its value: the table's double, rounded to float)
-template <int CHUNK, bool TRIGF>
+// KEEP: the fleet keeps every sample's cost and status (navgpu_fleet_desc::keep_sample_costs, pl.sample_cost != nullptr).  Only then
+// does anybody read WHICH critic failed a sample; without it the kernel decides validity alone (the file's head, "Validity").
+template <int CHUNK, bool TRIGF, bool KEEP>
 __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(PlannerDev pl, uint32_t first) {
   constexpr int THREADS = kSweepThreads;
   extern __shared__ __align__(16) uint8_t s_dyn[];
@@ -145,6 +165,22 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   const uint32_t amax = pl.max_axis - 1u;
   const float vs0 = axis[min((uint32_t)s_ix, amax)], vs1 = axis[pl.max_axis + min((uint32_t)s_iy, amax)], vs2 = axis[2u * pl.max_axis + min((uint32_t)t_ith, amax)];
   const uint32_t rej_xy = rej_bytes[in_range ? t_r : 0];  // the (vx, vy) pair's half of the reject tests (k_score_prep_tab)
+  // generateTrajectory: reject tests (:193-200); the step count is the tables' (ceil(sim_time / sim_granularity), host)
+  auto rejected = [&]() { return !in_range || ((rej_xy & 1u) && (c.min_rot_vel >= 0 && fabs((double)vs2) + 1e-4 < c.min_rot_vel)) || (rej_xy & 2u) || K <= 0; };  // `return num_steps > 0` (:250)
+  if constexpr (!KEEP) {
+    // ---- the robot-level exit: the path / goal critic fails at the robot's own cell, which is point 0 of every trajectory, and both
+    // stop at a failing point wherever it lies (map_grid_cost_function.cpp:106-112) - every accepted sample's total is negative
+    // whatever the other critics say.  Count the accepted slots, report "no valid sample" like an idle workgroup; no image, no rollout.
+    if (start_fail != 0) {  // (uniform over the robot's workgroups)
+      const unsigned long long m_acc = __ballot(!rejected());
+      if ((tid & 63u) == 0 && m_acc != 0ull) atomicAdd(&pl.counters[2 * inst], __popcll(m_acc));
+      if (tid == 0) {
+        pl.part_cost[(size_t)inst * pl.score_blocks + part_slot] = 1.0e300;
+        pl.part_index[(size_t)inst * pl.score_blocks + part_slot] = 0x7FFFFFFF;
+      }
+      return;
+    }
+  }
   {  // window + screens, and of the tables only the v_theta rows this workgroup's samples use, at their usual place
     const uint4* img = reinterpret_cast<const uint4*>(pl.prep + (size_t)inst * pl.prep_stride);
     uint4* lds = reinterpret_cast<uint4*>(s_dyn);
@@ -306,8 +342,7 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   double total = -1.0;
   int status = NAVGPU_SAMPLE_REJECTED;
   const float vs[3] = {vs0, vs1, vs2};
-  // generateTrajectory: reject tests (:193-200); the step count is the tables' (ceil(sim_time / sim_granularity), host)
-  const bool reject = !in_range || ((rej_xy & 1u) && (c.min_rot_vel >= 0 && fabs((double)vs2) + 1e-4 < c.min_rot_vel)) || (rej_xy & 2u) || K <= 0;  // `return num_steps > 0` (:250)
+  const bool reject = rejected();
   if (in_range && !reject) status = NAVGPU_SAMPLE_SCORED;
   const double dt = pl.tab_dt;
   const double xv = vs[0], yv = vs[1], thv = vs[2];  // traj.xv_, yv_, thetav_
@@ -318,7 +353,8 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
                sc_goal = pl.scale_goal;
   const bool en_obs = sc_obs != 0, en_gf = sc_gf != 0, en_al = sc_al != 0, en_path = sc_path != 0, en_goal = sc_goal != 0;
   // first_fail: order index of the earliest critic in the list that has failed (1 obstacle .. 5 goal), 6 = none; fail_code its
-  // code - the only one scoreTrajectory's in-order sum can return (simple_scored_sampling_planner.cpp:59-66)
+  // code - the only one scoreTrajectory's in-order sum can return (simple_scored_sampling_planner.cpp:59-66).  Without KEEP
+  // first_fail < 6 only says "failed": fail_code and fail_cell are never read and the compiler drops what computes them.
   int first_fail = 6;
   int fail_code = 0;
   uint32_t d_gf = 0, d_al = 0, d_path = 0, d_goal = 0;  // the map-grid critics' values (aggregation Last: the final point's)
@@ -334,8 +370,10 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
     first_fail = 1;
   }
   // a critic is live while no critic before it in the order has failed; the lowest enabled order decides when nothing is
-  // left to evaluate
-  const int min_order = en_obs ? 1 : en_gf ? 2 : en_al ? 3 : en_path ? 4 : en_goal ? 5 : 6;
+  // left to evaluate.  Without KEEP the first failure of ANY critic settles the sample (invalid; which code, nobody asks):
+  // the rollout goes on while no critic has failed
+  const int min_order_keep = en_obs ? 1 : en_gf ? 2 : en_al ? 3 : en_path ? 4 : en_goal ? 5 : 6;
+  const int min_order = KEEP ? min_order_keep : (min_order_keep < 6 ? 5 : 6);
   uint32_t fb_off = (uint32_t)win_bytes;  // (in a vector register: as a scalar it is spilled and read back with v_readlane at every point)
   asm volatile("" : "+v"(fb_off));
   const uint4* s_fb4 = reinterpret_cast<const uint4*>(s_dyn + fb_off);
@@ -384,13 +422,15 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   if (alive_m != 0u) step = k_free;
   SW_COUNT(9, k_free);
   SW_COUNT(10, (unsigned)k_free * (unsigned)__popcll(__ballot(alive_m != 0u)));
-  if (k_free > 0 && start_fail != 0 && alive_m != 0u) {  // what looking closer at point 0 would have found (the free run skipped it)
-    first_fail = start_fail;
-    fail_code = 0;
-    fail_cell = (uint32_t)(wy0 + win / 2) * g.nx + (uint32_t)(wx0 + win / 2);
-    scr_z = first_fail > 4 ? 0xFFFFFFFFu : 0u;
-    scr_w = 0u;
-    alive_m = first_fail > min_order ? 0xFFFFFFFFu : 0u;
+  if constexpr (KEEP) {  // (without KEEP such a robot has left by the robot-level exit)
+    if (k_free > 0 && start_fail != 0 && alive_m != 0u) {  // what looking closer at point 0 would have found (the free run skipped it)
+      first_fail = start_fail;
+      fail_code = 0;
+      fail_cell = (uint32_t)(wy0 + win / 2) * g.nx + (uint32_t)(wx0 + win / 2);
+      scr_z = first_fail > 4 ? 0xFFFFFFFFu : 0u;
+      scr_w = 0u;
+      alive_m = first_fail > min_order ? 0xFFFFFFFFu : 0u;
+    }
   }
   for (uint32_t blk = 0;; ++blk) {
     SW_STAMP(sb0);
@@ -558,6 +598,10 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
             }
             last_f = sel(m_go & ~m_fwd & m_last, 0u, last_f);  // (reached; no forward critic to read for)
           }
+          // (Without KEEP a lane that has failed is not alive, so these two masks and the `< first_fail` tests above could be constants
+          // there.  Built so, the allocator kept them out of the vector registers and spilled scalars of the screened path instead:
+          // 4 - 5 v_readlane per point in that path against none, 48 / 114 lane moves in the loop (CHUNK 9 / 16) against 12 / 28; the
+          // step time was the same within the runs' spread.  They stay per lane in both forms.)
           scr_z = first_fail > 4 ? 0xFFFFFFFFu : 0u;  // (always the lane's first_fail put as masks: it only changes in here)
           scr_w = first_fail > 5 ? 0xFFFFFFFFu : 0u;
           // a stalled lane goes back to the point as it was: (float)x is the old px exactly
@@ -638,10 +682,12 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   {  // ---- the distance grids, once: every load in flight before the first is used (clamped addresses; unused ones are ignored)
     const bool reached = last_f != 0xFFFFFFFFu && first_fail > 1;  // the final point was scored (and no walk failed since)
     const uint32_t cmax = pl.cells - 1u;
-    const uint32_t v_fail = (first_fail == 4 ? dpath : dgoal)[min(fail_cell, cmax)];
+    uint32_t v_fail = 0;
+    if constexpr (KEEP) v_fail = (first_fail == 4 ? dpath : dgoal)[min(fail_cell, cmax)];
     const uint32_t v_gf = dfront[min(last_f, cmax)], v_al = dpath[min(last_f, cmax)];
     const uint32_t v_path = dpath[min(last_c, cmax)], v_goal = dgoal[min(last_c, cmax)];
-    if ((first_fail == 4 || first_fail == 5) && fail_code == 0) fail_code = v_fail == N_obst ? -3 : -2;
+    if constexpr (KEEP)
+      if ((first_fail == 4 || first_fail == 5) && fail_code == 0) fail_code = v_fail == N_obst ? -3 : -2;
     if (reached) {  // in the critics' order; a critic that failed earlier on the trajectory (or follows one that did) is not read
       if (en_gf && 2 < first_fail) d_gf = v_gf;
       if (en_al && 3 < first_fail) d_al = v_al;
@@ -665,7 +711,7 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
     if (osc_fail) {
       total = -5.0;
     } else if (first_fail < 6) {
-      total = (double)fail_code;
+      total = KEEP ? (double)fail_code : -1.0;  // (negative: all that findBestTrajectory tests, simple_scored_sampling_planner.cpp:111)
     } else {
       // scoreTrajectory's sum in critic order (a term that is 0 is not scaled: `if (cost != 0) cost *= scale`)
       total = 0.0;
@@ -676,9 +722,11 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
       addCritic(total, en_goal, (double)d_goal, sc_goal);
     }
   }
-  if (in_range && pl.sample_cost) {
-    pl.sample_cost[(size_t)inst * pl.max_samples + sidx] = total;
-    pl.sample_status[(size_t)inst * pl.max_samples + sidx] = status;
+  if constexpr (KEEP) {
+    if (in_range && pl.sample_cost) {
+      pl.sample_cost[(size_t)inst * pl.max_samples + sidx] = total;
+      pl.sample_status[(size_t)inst * pl.max_samples + sidx] = status;
+    }
   }
 
   // ---- workgroup argmin (lowest index wins ties == first strict minimum of the sequential loop)
@@ -738,19 +786,26 @@ bool score_sweep_applies(const PlannerDev& pl) {
   const dim3 grid = score_sweep_grid(pl, 1);
   return pl.use_tables && !pl.mg_generic && grid.x * grid.y <= pl.score_blocks;
 }
+// KEEP follows the fleet: the per-sample arrays exist only with navgpu_fleet_desc::keep_sample_costs (navgpu_configure_planner)
+template <int CHUNK>
+static void launchSweep(const PlannerDev& pl, dim3 grid, size_t lds, hipStream_t s, uint32_t first) {
+  const bool trigf = pl.cfg.rollout_trig != 0, keep = pl.sample_cost != nullptr;
+  // (allowed from 40 KB: beside the dynamic LDS the kernel holds 10 KB of static LDS, the walk queue)
+  launchScore<40 * 1024>(keep ? (trigf ? k_score_sweep<CHUNK, true, true> : k_score_sweep<CHUNK, false, true>)
+                              : (trigf ? k_score_sweep<CHUNK, true, false> : k_score_sweep<CHUNK, false, false>),
+                         grid, kSweepThreads, lds, s, pl, first);
+}
 uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) {
   const size_t lds = score_window_bytes(pl.win) + score_table_lds_bytes(pl);
   const dim3 grid = score_sweep_grid(pl, count);  // (grid.x * grid.y <= score_blocks: score_sweep_applies)
-  // (allowed from 40 KB: beside the dynamic LDS the kernel holds 10 KB of static LDS, the walk queue)
-  const bool trigf = pl.cfg.rollout_trig != 0;
   if (pl.fp_chunk <= 6)
-    launchScore<40 * 1024>(trigf ? k_score_sweep<6, true> : k_score_sweep<6, false>, grid, kSweepThreads, lds, s, pl, first);
+    launchSweep<6>(pl, grid, lds, s, first);
   else if (pl.fp_chunk <= 9)
-    launchScore<40 * 1024>(trigf ? k_score_sweep<9, true> : k_score_sweep<9, false>, grid, kSweepThreads, lds, s, pl, first);
+    launchSweep<9>(pl, grid, lds, s, first);
   else if (pl.fp_chunk <= 12)
-    launchScore<40 * 1024>(trigf ? k_score_sweep<12, true> : k_score_sweep<12, false>, grid, kSweepThreads, lds, s, pl, first);
+    launchSweep<12>(pl, grid, lds, s, first);
   else
-    launchScore<40 * 1024>(trigf ? k_score_sweep<16, true> : k_score_sweep<16, false>, grid, kSweepThreads, lds, s, pl, first);
+    launchSweep<16>(pl, grid, lds, s, first);
   return grid.x * grid.y;
 }
 
