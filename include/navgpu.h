@@ -711,6 +711,104 @@ int navgpu_voxel_clearing_endpoints(navgpu_fleet* fleet, uint32_t first, uint32_
                                     uint32_t* obs_counts, uint32_t* counts);
 
 /* ------------------------------------------------------------------------------------------ */
+/* costmap_2d::ObservationBuffer on the device: clouds and laser scans, resident until purged   */
+/* ------------------------------------------------------------------------------------------ */
+/* What costmap_2d::ObservationBuffer (costmap_2d/src/observation_buffer.cpp:66-256) and the sensor callbacks of ObstacleLayer
+ * (plugins/obstacle_layer.cpp:252-338, 466-496) do, with the tf LOOK-UP left to the caller as navgpu_static_set_transform leaves
+ * it: sensor data goes up once, in the sensor's own frame, and stays on the device until the reference would purge it.  Per
+ * (robot, source) the time-ordered list is host metadata, the points live in a ring of `slots` slots on the device.  Times are
+ * int64 nanoseconds (ros::Time / ros::Duration are integers; the purge test is an exact comparison).
+ *
+ * Arithmetic (the library is built with -ffp-contract=off; nothing below is fused):
+ *   cloud transform  pcl_ros::transformAsMatrix + pcl::transformPointCloud are not in the reference tree; RESTATED here, parity
+ *                    unpinned (as for tf): the 12 doubles of `transform` are narrowed to float, then in fp32, left to right,
+ *                      x' = ((m00*x + m01*y) + m02*z) + m03      y' = ((m10*x + m11*y) + m12*z) + m13      z' likewise
+ *                    with m03, m13, m23 the origin (transform[9..11]).
+ *   height filter    keep iff (double)z' <= max_obstacle_height && (double)z' >= min_obstacle_height (:169-170); NaN drops.
+ *   scan             laser_geometry is not in the tree either: projectLaser RESTATED, parity unpinned
+ *                    (transformLaserScanToPointCloud into the scan's own frame reduces to it, both look-ups being the identity).
+ *                    With inf_is_valid a range that is not finite and > 0 first becomes range_max - 0.0001f in float
+ *                    (obstacle_layer.cpp:281-289).  Beam i is kept iff r >= range_min && r < range_max (NaN, -inf, and +inf
+ *                    without the flag drop out); its point is x = (float)((double)r * cos(a)), y = (float)((double)r * sin(a)),
+ *                    z = 0 with a = (double)angle_min + (double)i * (double)angle_increment and the device's double sincos
+ *                    (navgpu_device_sincos returns the same values); the cloud transform follows.  The per-beam time
+ *                    interpolation of a scan taken while the sensor moves is not done.
+ * Two stated departures from the reference: a list is bounded by `slots` (the reference's is unbounded) - an entry pushed out
+ * is counted as `evicted`; and the capacity check of navgpu_obsbuf_stage uses the UNFILTERED sizes of the kept clouds, the
+ * host never learning a filtered count on that path. */
+typedef struct {                     /* one entry of observation_sources (obstacle_layer.cpp:96-140) */
+  int64_t observation_keep_time_ns;  /* 0: keep only the newest (observation_buffer.cpp:217-221) */
+  int64_t expected_update_rate_ns;   /* 0: always current (:240-241) */
+  double min_obstacle_height, max_obstacle_height; /* the BUFFER's filter, :169-170 */
+  double obstacle_range, raytrace_range;           /* copied into every observation, :151-152 */
+  uint32_t flags;                    /* NAVGPU_OBS_MARKING | NAVGPU_OBS_CLEARING */
+  int32_t inf_is_valid;              /* scans: laserScanValidInfCallback instead of laserScanCallback */
+} navgpu_obs_source_params;
+
+#define NAVGPU_OBSBUF_MAX_SOURCES 8
+#define NAVGPU_OBSBUF_MAX_CLOUD_POINTS 65536
+#define NAVGPU_CLOUD_XYZ 0           /* float xyz in the cloud's frame (pointCloud2Callback) */
+#define NAVGPU_CLOUD_SCAN 1          /* float ranges (laserScanCallback / laserScanValidInfCallback) */
+typedef struct {
+  uint32_t instance, source, kind;
+  uint32_t first, n;                 /* into points_xyz (points) or ranges (beams) of the call */
+  uint32_t reserved;
+  int64_t stamp_ns;                  /* cloud.header.stamp */
+  double origin[3];                  /* tf_.transformPoint(global, (0,0,0) of sensor_frame / cloud frame), :142-148 */
+  double transform[12];              /* global <- cloud frame: basis row-major, then origin (tf::Transform) */
+  float angle_min, angle_increment, range_min, range_max; /* SCAN only */
+} navgpu_cloud;
+
+typedef struct {
+  uint32_t kept;                     /* observations in the robot's lists */
+  uint32_t points;                   /* their points after the height filter (read back from the device) */
+  uint64_t evicted;                  /* entries pushed out of a full ring since configure */
+  int32_t current;                   /* isCurrent of every source at the `now_ns` the last buffer / stage / reset call gave */
+  int32_t reserved;
+} navgpu_obsbuf_robot_status;
+
+/* Any navgpu_obsbuf_* call but this one returns NAVGPU_ERR_STATE before a successful configure.
+ * Allocates, per (robot, source), a ring of slots x max_cloud_points x 3 floats and slots counts; empties every list, zeroes
+ * `evicted` and sets every last_updated to 0 (call navgpu_obsbuf_reset_last_updated as ObstacleLayer::activate does).
+ * NAVGPU_ERR_INVALID unless 1 <= n_sources <= 8, 1 <= slots, 1 <= max_cloud_points <= 65536 and slots * n_sources <=
+ * max_observations of the fleet.  All-or-nothing: a failed call leaves the previous configuration, and its lists, in force. */
+int navgpu_obsbuf_configure(navgpu_fleet* fleet, const navgpu_obs_source_params* sources, uint32_t n_sources, uint32_t slots,
+                            uint32_t max_cloud_points);
+/* replaces: ObservationBuffer::bufferCloud (:129-195) behind pointCloud2Callback / laserScanCallback / laserScanValidInfCallback
+ * (obstacle_layer.cpp:252-338) for each cloud of the call, in call order: push_front, origin and ranges, transform, height
+ * filter in cloud order into a slot, last_updated = now_ns, purgeStaleObservations (:211-236: the newest only with a keep time
+ * of 0, else everything from the first entry with last_updated - stamp > keep_time on).  A list longer than `slots` then loses
+ * its oldest entry (counted as evicted).  NAVGPU_ERR_CAPACITY for a cloud with n > max_cloud_points; NAVGPU_ERR_INVALID for a
+ * bad instance / source / kind, a range outside points_xyz / ranges, a non-finite transform or origin; a failing call buffers
+ * nothing.  Asynchronous on the fleet's stream: one host-to-device copy of the call's points and ranges out of a pinned mirror
+ * and one launch (k_obs_ingest); the host does not learn a filtered count here. */
+int navgpu_obsbuf_buffer(navgpu_fleet* fleet, const navgpu_cloud* clouds, uint32_t n_clouds, const float* points_xyz, uint32_t n_points,
+                         const float* ranges, uint32_t n_ranges, int64_t now_ns);
+/* replaces: ObstacleLayer::getMarkingObservations + getClearingObservations (:466-496) + navgpu_costmap_stage for the range.
+ * Per robot and source the list is purged as getObservations does (:198-209); one observation per kept entry is staged, sources
+ * in configuration order, each newest first, with the source's flags (k_obstacle clears with every clearing observation before
+ * it marks with any: one descriptor with both bits equals the reference's two passes).  current_out[r] (or NULL) = AND over
+ * the sources of expected_update_rate == 0 || now_ns - last_updated <= expected_update_rate (:238-251).  Pose, transformed
+ * footprint and rolling-window origin are staged exactly as navgpu_costmap_stage stages them, and everything around the call
+ * (NAVGPU_ERR_STATE for a staged rolling-window shift not yet consumed, two cycles in flight, navgpu_voxel_clearing_endpoints
+ * after the update) behaves as after it.  NAVGPU_ERR_CAPACITY, nothing staged, when the UNFILTERED sizes of a robot's kept
+ * clouds sum to more than max_points. */
+int navgpu_obsbuf_stage(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* robot_poses, int64_t now_ns, int32_t* current_out);
+/* Synchronous read-back, for tests and debugging, of exactly what navgpu_obsbuf_stage would hand over for one robot: the
+ * descriptors with the filtered n_points (first_point into points_xyz) and the global-frame points.  Changes no state (now_ns
+ * is accepted for symmetry: the purge compares with last_updated).  Returns the number of observations, n_points_out the
+ * points; NAVGPU_ERR_CAPACITY when either buffer is too small. */
+int navgpu_obsbuf_observations(navgpu_fleet* fleet, uint32_t instance, int64_t now_ns, navgpu_observation* obs, uint32_t obs_capacity,
+                               float* points_xyz, uint32_t point_capacity, uint32_t* n_points_out);
+/* replaces: ObservationBuffer::setGlobalFrame (:66-109) with the looked-up transform M = new_global <- global, 12 doubles per
+ * robot as above: every kept origin becomes M * origin in fp64 (tf::Transform::operator*: row . v + origin), every kept point
+ * M * p by the cloud transform above, in place; nothing is filtered again (the reference does not). */
+int navgpu_obsbuf_set_global_frame(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* transforms12);
+/* replaces: ObservationBuffer::resetLastUpdated (:253-256) of every source, as ObstacleLayer::activate does */
+int navgpu_obsbuf_reset_last_updated(navgpu_fleet* fleet, uint32_t first, uint32_t count, int64_t now_ns);
+int navgpu_obsbuf_status(navgpu_fleet* fleet, uint32_t first, uint32_t count, navgpu_obsbuf_robot_status* out);
+
+/* ------------------------------------------------------------------------------------------ */
 /* measurement                                                                                */
 /* ------------------------------------------------------------------------------------------ */
 typedef enum {
@@ -722,7 +820,8 @@ typedef enum {
   NAVGPU_K_SELECT = 5,   /* argmin + result + oscillation update          */
   NAVGPU_K_FOOTPRINT = 6,/* batched footprint-cost queries                */
   NAVGPU_K_VOXEL_EXPORT = 7, /* voxel points / clearing endpoints: count, scan and emit launches */
-  NAVGPU_K_COUNT = 8
+  NAVGPU_K_OBS_INGEST = 8,   /* observation buffer: transform + filter + compaction of the clouds of a call */
+  NAVGPU_K_COUNT = 9
 } navgpu_kernel_id;
 /* HIP-event timing of the kernels on the fleet's stream.  While enabled every launch of the
  * listed kernels is bracketed by two hipEventRecord calls; read() synchronises and returns the

@@ -12,8 +12,10 @@ LAYER_STATIC, LAYER_OBSTACLE, LAYER_VOXEL, LAYER_INFLATION = 1, 2, 4, 8
 GRID_MASTER, GRID_STATIC, GRID_OBSTACLE, GRID_VOXEL, GRID_PATH, GRID_GOAL, GRID_GOAL_FRONT = range(7)
 OBS_MARKING, OBS_CLEARING = 1, 2
 VOXEL_UNKNOWN, VOXEL_MARKED = 1, 2  # voxel_grid::VoxelStatus
-K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT, K_VOXEL_EXPORT = range(8)
-KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export")
+K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT, K_VOXEL_EXPORT, K_OBS_INGEST = range(9)
+KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export", "k_obs_ingest")
+CLOUD_XYZ, CLOUD_SCAN = 0, 1  # NAVGPU_CLOUD_*
+OBSBUF_MAX_SOURCES, OBSBUF_MAX_CLOUD_POINTS = 8, 65536
 
 
 class NavgpuError(RuntimeError):
@@ -32,6 +34,34 @@ class Observation(C.Structure):
     _fields_ = [("instance", C.c_uint32), ("first_point", C.c_uint32), ("n_points", C.c_uint32),
                 ("flags", C.c_uint32), ("origin_x", C.c_double), ("origin_y", C.c_double),
                 ("origin_z", C.c_double), ("obstacle_range", C.c_double), ("raytrace_range", C.c_double)]
+
+
+class ObsSourceParams(C.Structure):
+    """Mirror of navgpu_obs_source_params (include/navgpu.h): one entry of observation_sources.  Defaults: obstacle_layer.cpp:96-140."""
+    _fields_ = [("observation_keep_time_ns", C.c_int64), ("expected_update_rate_ns", C.c_int64), ("min_obstacle_height", C.c_double),
+                ("max_obstacle_height", C.c_double), ("obstacle_range", C.c_double), ("raytrace_range", C.c_double), ("flags", C.c_uint32),
+                ("inf_is_valid", C.c_int32)]
+    DEFAULTS = dict(observation_keep_time_ns=0, expected_update_rate_ns=0, min_obstacle_height=0.0, max_obstacle_height=2.0,
+                    obstacle_range=2.5, raytrace_range=3.0, flags=OBS_MARKING | OBS_CLEARING, inf_is_valid=0)
+
+    def __init__(self, **kw):
+        super().__init__()
+        d = dict(self.DEFAULTS)
+        d.update(kw)
+        for k, v in d.items():
+            setattr(self, k, v)
+
+
+class Cloud(C.Structure):
+    """Mirror of navgpu_cloud (include/navgpu.h): one cloud or scan of a navgpu_obsbuf_buffer call."""
+    _fields_ = [("instance", C.c_uint32), ("source", C.c_uint32), ("kind", C.c_uint32), ("first", C.c_uint32), ("n", C.c_uint32),
+                ("reserved", C.c_uint32), ("stamp_ns", C.c_int64), ("origin", C.c_double * 3), ("transform", C.c_double * 12),
+                ("angle_min", C.c_float), ("angle_increment", C.c_float), ("range_min", C.c_float), ("range_max", C.c_float)]
+
+
+class ObsBufRobotStatus(C.Structure):
+    """Mirror of navgpu_obsbuf_robot_status (include/navgpu.h)."""
+    _fields_ = [("kept", C.c_uint32), ("points", C.c_uint32), ("evicted", C.c_uint64), ("current", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ObstacleParams(C.Structure):
@@ -413,6 +443,13 @@ SYMBOLS = [
     ("navgpu_carrot_plan", C.c_int, [vp, u32, u32, vp, vp, i32, vp, vp]),
     ("navgpu_voxel_points", C.c_int, [vp, u32, u32, C.c_int, C.c_int, u32, vp, vp]),
     ("navgpu_voxel_clearing_endpoints", C.c_int, [vp, u32, u32, u32, vp, vp, vp]),
+    ("navgpu_obsbuf_configure", C.c_int, [vp, vp, u32, u32, u32]),
+    ("navgpu_obsbuf_buffer", C.c_int, [vp, vp, u32, vp, u32, vp, u32, C.c_int64]),
+    ("navgpu_obsbuf_stage", C.c_int, [vp, u32, u32, vp, C.c_int64, vp]),
+    ("navgpu_obsbuf_observations", C.c_int, [vp, u32, C.c_int64, vp, u32, vp, u32, C.POINTER(u32)]),
+    ("navgpu_obsbuf_set_global_frame", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_obsbuf_reset_last_updated", C.c_int, [vp, u32, u32, C.c_int64]),
+    ("navgpu_obsbuf_status", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_navfn_create", C.c_int, [u32, u32, u32, i32, C.POINTER(vp)]),
     ("navgpu_navfn_destroy", C.c_int, [vp]),
     ("navgpu_navfn_set_costmap", C.c_int, [vp, u32, u32, vp, i32, i32, i32]),

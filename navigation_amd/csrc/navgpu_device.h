@@ -260,6 +260,28 @@ void launch_voxel_points_emit(const CostmapDev& cm, const VoxelExportDev& v, uin
 void launch_clear_endpoints_count(const CostmapDev& cm, const VoxelExportDev& v, uint32_t first, uint32_t count, hipStream_t s);
 void launch_clear_endpoints_emit(const CostmapDev& cm, const VoxelExportDev& v, uint32_t first, uint32_t count, hipStream_t s);
 
+// observation buffer (obs_buffer_kernels.hip): the device-resident rings behind navgpu_obsbuf_*
+struct ObsIngestCloud {  // one cloud of a navgpu_obsbuf_buffer call that is still in its list when the call returns
+  uint32_t kind, first, n, slot;  // NAVGPU_CLOUD_*; into the call's points / ranges; ring slot ((robot * sources + source) * slots + s)
+  float m[12];                    // global <- cloud frame, narrowed: basis row-major, origin
+  double min_h, max_h;            // the source's height filter
+  float angle_min, angle_increment, range_min, range_max;
+  int32_t inf_is_valid, pad;
+};
+static_assert(sizeof(ObsIngestCloud) == 104, "ingest descriptor");
+struct ObsRetransform {  // one kept slot of navgpu_obsbuf_set_global_frame
+  uint32_t slot, pad;
+  float m[12];
+};
+struct ObsBufDev {
+  float* ring;            // [n][sources][slots][max_cloud_points][3] global-frame points that passed the height filter, cloud order
+  uint32_t* counts;       // [n][sources][slots] points of a slot
+  uint32_t max_cloud_points, slots_per_robot;  // slots_per_robot = sources * slots
+};
+void launch_obs_ingest(const ObsBufDev& ob, const ObsIngestCloud* clouds, uint32_t n_clouds, const float* points, const float* ranges, hipStream_t s);
+void launch_obs_gather(const ObsBufDev& ob, const CostmapDev& cm, uint32_t first, uint32_t count, hipStream_t s);
+void launch_obs_retransform(const ObsBufDev& ob, const ObsRetransform* items, uint32_t n_items, hipStream_t s);
+
 // ---- launchers (defined in the .hip files) ---------------------------------------------------
 void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const double* bounds_in, int only_bounds,
                      hipStream_t s);

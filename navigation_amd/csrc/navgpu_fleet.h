@@ -2,7 +2,7 @@
 // translation units share (navgpu_host.cpp: lifetime / costmap layers / DWA planner / measurement,
 // navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner,
 // navgpu_recovery.cpp: footprint-cost queries, RotateRecovery, CarrotPlanner, navgpu_voxel_export.cpp: voxel-layer debug
-// outputs, navgpu_traj_cloud.cpp: DWAPlanner's trajectory cloud).
+// outputs, navgpu_traj_cloud.cpp: DWAPlanner's trajectory cloud, navgpu_obs_buffer.cpp: ObservationBuffer on the device).
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <deque>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -40,6 +41,10 @@ struct EventPair {
   hipEvent_t a, b;
 };
 int ensureCompleteGrids(navgpu_fleet* f, uint32_t first, uint32_t count);
+// What a costmap cycle stages besides its observations, for [first, first + count): pose, transformed footprint and vertex
+// count into the pinned mirrors, and for a rolling window the new origins and pending shift (host and device).  Shared by
+// navgpu_costmap_stage and navgpu_obsbuf_stage; the caller has waited for the mirrors and copies them afterwards.
+int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses);
 }  // namespace navgpu
 
 struct navgpu_fleet {
@@ -163,6 +168,31 @@ struct navgpu_fleet {
     float* d_points = nullptr;
     size_t points_cap = 0;                    // points d_points holds
   } tc;
+  // ObservationBuffer on the device (navgpu_obs_buffer.cpp): per (robot, source) a time-ordered list on the host, newest
+  // first, whose entries name ring slots on the device
+  struct ObsBuf {
+    struct Entry {
+      int64_t stamp;
+      double origin[3];
+      uint32_t slot, n;  // ring slot of the (robot, source); UNFILTERED points (the host never learns the filtered count)
+    };
+    struct List {
+      std::deque<Entry> entries;  // observation_list_
+      int64_t last_updated = 0;   // last_updated_
+    };
+    bool configured = false;
+    uint32_t n_sources = 0, slots = 0;
+    navgpu_obs_source_params src[NAVGPU_OBSBUF_MAX_SOURCES] = {};
+    ObsBufDev dev{};
+    std::vector<List> lists;        // [n][n_sources]
+    std::vector<uint64_t> evicted;  // [n]
+    int64_t last_now = 0;           // `now_ns` of the last call that took one (navgpu_obsbuf_status' `current`)
+    // what a call hands over - descriptors, then points, then ranges - as one pinned block and its device twin, grown on demand
+    uint8_t *h_in = nullptr, *d_in = nullptr;
+    size_t in_bytes = 0;
+    hipEvent_t ev_h2d = nullptr;    // behind the copy out of h_in
+    bool ev_set = false;
+  } ob;
   std::vector<uint8_t> obs_consumed;            // [n] an update has run on what navgpu_costmap_stage staged last
   navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers

@@ -30,7 +30,7 @@ int navgpu_device_count(void) {
   return n;
 }
 const char* navgpu_kernel_name(int32_t k) {
-  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export"};
+  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export", "k_obs_ingest"};
   return (k >= 0 && k < NAVGPU_K_COUNT) ? names[k] : "?";
 }
 
@@ -278,7 +278,7 @@ int navgpu_fleet_destroy(navgpu_fleet* f) {
     hipEventDestroy(e.a);
     hipEventDestroy(e.b);
   }
-  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d})
+  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d})
     if (e) hipEventDestroy(e);
   for (void* p : f->allocs) hipFree(p);
   for (void* p : f->pinned) hipHostFree(p);
@@ -852,36 +852,11 @@ int navgpu_set_footprint(navgpu_fleet* f, uint32_t first, uint32_t count, const 
   return NAVGPU_OK;
 }
 
-int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses, const navgpu_observation* obs,
-                         uint32_t n_obs, const float* points, uint32_t n_points_total) {
-  if (!f || !poses || !f->rangeOk(first, count) || (n_obs && (!obs || (!points && n_points_total)))) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
+}  // extern "C"
+
+namespace navgpu {
+int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses) {
   CostmapDev& cm = f->cm;
-  if (f->desc.rolling_window && f->shift_pending) return NAVGPU_ERR_STATE;  // previous stage not consumed by an update yet
-  if (f->desc.rolling_window) f->touchInputs(first, count);  // the origins move now
-  HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
-  for (uint32_t li = 0; li < count; ++li) f->hp_cnt[first + li] = f->hp_used[first + li] = 0;
-  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 0);
-  for (uint32_t k = 0; k < n_obs; ++k) {
-    const navgpu_observation& o = obs[k];
-    if (o.instance < first || o.instance >= first + count) return NAVGPU_ERR_INVALID;
-    const uint32_t i = o.instance;
-    if (f->hp_cnt[i] >= cm.max_obs || f->hp_used[i] + o.n_points > cm.max_points) return NAVGPU_ERR_CAPACITY;
-    if ((uint64_t)o.first_point + o.n_points > n_points_total) return NAVGPU_ERR_INVALID;
-    ObsCsr& d = f->hp_obs[(size_t)i * cm.max_obs + f->hp_cnt[i]++];
-    d.first_point = f->hp_used[i];
-    d.n_points = o.n_points;
-    d.flags = o.flags;
-    d.pad = 0;
-    d.ox = o.origin_x;
-    d.oy = o.origin_y;
-    d.oz = o.origin_z;
-    d.obstacle_range = o.obstacle_range;
-    d.raytrace_range = o.raytrace_range;
-    if (o.n_points)
-      memcpy(&f->hp_pts[((size_t)i * cm.max_points + f->hp_used[i]) * 3], points + (size_t)o.first_point * 3, sizeof(float) * 3 * o.n_points);
-    f->hp_used[i] += o.n_points;
-  }
   // rolling window: LayeredCostmap::updateMap :86-91 + Costmap2D::updateOrigin :264-276, evaluated here
   // in fp64 exactly as the reference does; the grids are shifted on the device by navgpu_costmap_update
   if (f->desc.rolling_window) {
@@ -917,6 +892,46 @@ int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
     }
   }
   memcpy(f->hp_fpn + first, &f->h_fp_n[first], sizeof(uint32_t) * count);
+  return NAVGPU_OK;
+}
+}  // namespace navgpu
+
+extern "C" {
+
+int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses, const navgpu_observation* obs,
+                         uint32_t n_obs, const float* points, uint32_t n_points_total) {
+  if (!f || !poses || !f->rangeOk(first, count) || (n_obs && (!obs || (!points && n_points_total)))) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  CostmapDev& cm = f->cm;
+  if (f->desc.rolling_window && f->shift_pending) return NAVGPU_ERR_STATE;  // previous stage not consumed by an update yet
+  if (f->desc.rolling_window) f->touchInputs(first, count);  // the origins move now
+  HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
+  for (uint32_t li = 0; li < count; ++li) f->hp_cnt[first + li] = f->hp_used[first + li] = 0;
+  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 0);
+  for (uint32_t k = 0; k < n_obs; ++k) {
+    const navgpu_observation& o = obs[k];
+    if (o.instance < first || o.instance >= first + count) return NAVGPU_ERR_INVALID;
+    const uint32_t i = o.instance;
+    if (f->hp_cnt[i] >= cm.max_obs || f->hp_used[i] + o.n_points > cm.max_points) return NAVGPU_ERR_CAPACITY;
+    if ((uint64_t)o.first_point + o.n_points > n_points_total) return NAVGPU_ERR_INVALID;
+    ObsCsr& d = f->hp_obs[(size_t)i * cm.max_obs + f->hp_cnt[i]++];
+    d.first_point = f->hp_used[i];
+    d.n_points = o.n_points;
+    d.flags = o.flags;
+    d.pad = 0;
+    d.ox = o.origin_x;
+    d.oy = o.origin_y;
+    d.oz = o.origin_z;
+    d.obstacle_range = o.obstacle_range;
+    d.raytrace_range = o.raytrace_range;
+    if (o.n_points)
+      memcpy(&f->hp_pts[((size_t)i * cm.max_points + f->hp_used[i]) * 3], points + (size_t)o.first_point * 3, sizeof(float) * 3 * o.n_points);
+    f->hp_used[i] += o.n_points;
+  }
+  {
+    int rc = stageRobotPoses(f, first, count, poses);
+    if (rc) return rc;
+  }
   if (first == 0 && count == f->desc.n_instances) {  // the whole fleet: one copy of the block
     HIP_TRY(hipMemcpyAsync(f->cm_stage_dev, f->cm_stage_host, f->cm_stage_bytes, hipMemcpyHostToDevice, f->stream));
   } else {

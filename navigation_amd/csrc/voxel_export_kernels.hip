@@ -14,33 +14,12 @@
 //   (c) emit  : as (a), each lane recomputes its offset inside the chunk - shuffles inside the wave, the waves' totals through
 //               LDS - and writes at base + offset while that is below the capacity
 // No atomic decides a position: the output is the same bytes from run to run.  Compiled with -ffp-contract=off.
+#include "block_scan.h"
 #include "navgpu_device.h"
 
 namespace navgpu {
 
-// Exclusive prefix of v over the workgroup's lanes in lane order, and the workgroup's total.  Inside a wave a Hillis-Steele
-// scan on __shfl_up (6 steps for 64 lanes), across the 4 waves their totals through LDS.
-__device__ __forceinline__ uint32_t blockExclusive(uint32_t v, uint32_t* s_wave, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0;
-  total = 0;
-#pragma unroll
-  for (uint32_t w = 0; w < kVxThreads / 64; ++w) {
-    const uint32_t t = s_wave[w];
-    before += w < wave ? t : 0u;
-    total += t;
-  }
-  __syncthreads();  // s_wave may be written again
-  return before + inc - v;
-}
+static_assert(kVxThreads == kScanThreads, "blockExclusive (block_scan.h) scans a workgroup of kScanThreads lanes");
 
 // ------------------------------------------------------------------------------------------------ voxel points
 // the z bits of a column whose VoxelGrid::getVoxel (voxel_grid.h:183-206) equals the status asked for

@@ -12,6 +12,8 @@ Method names follow the reference interfaces they front:
   carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
   voxel_points          costmap_2d_cloud / costmap_2d_markers voxelCallback (costmap_2d/src/costmap_2d_cloud.cpp:85-122)
   voxel_clearing_endpoints  VoxelLayer::raytraceFreespace's clearing_endpoints cloud (plugins/voxel_layer.cpp:286-381)
+  obs_buffer / obs_stage  ObservationBuffer::bufferCloud / getObservations behind ObstacleLayer's sensor callbacks
+                        (costmap_2d/src/observation_buffer.cpp:111-251, plugins/obstacle_layer.cpp:252-338, 466-496)
   trajectory_cloud      DWAPlanner::findBestPath's trajectory_cloud (dwa_planner.cpp:318-348); sample_terms: the breakdown behind it
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
@@ -220,6 +222,84 @@ class Fleet:
     def obstacle_update_costs(self, boxes, first=0):
         b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
         check(self.L.navgpu_obstacle_update_costs(self.h, first, len(b), _ptr(b)), "obstacle_update_costs")
+
+    # ---------------------------------------------------------------- ObservationBuffer on the device
+    def obs_configure(self, sources, slots, max_cloud_points):
+        """sources: ObsSourceParams, or dicts of its fields, one per entry of observation_sources."""
+        arr = (N.ObsSourceParams * len(sources))(*[s if isinstance(s, N.ObsSourceParams) else N.ObsSourceParams(**s) for s in sources])
+        check(self.L.navgpu_obsbuf_configure(self.h, C.cast(arr, C.c_void_p), len(sources), int(slots), int(max_cloud_points)), "obsbuf_configure")
+
+    @staticmethod
+    def pack_clouds(clouds):
+        """The arguments of navgpu_obsbuf_buffer from a list of dicts {instance, source, stamp_ns, origin(3), transform(12):
+        basis row-major then origin} with either points (k, 3) float32, or ranges (k,) float32 and angle_min, angle_increment,
+        range_min, range_max: (Cloud array, packed points, packed ranges)."""
+        arr = (N.Cloud * max(1, len(clouds)))()
+        pts, rng = [], []
+        n_pts = n_rng = 0
+        for k, c in enumerate(clouds):
+            a = arr[k]
+            a.instance, a.source, a.stamp_ns = c["instance"], c.get("source", 0), int(c["stamp_ns"])
+            a.origin[:] = [float(v) for v in c.get("origin", (0.0, 0.0, 0.0))]
+            a.transform[:] = [float(v) for v in np.asarray(c.get("transform", (1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0)), np.float64).ravel()]
+            if "ranges" in c:
+                r = np.ascontiguousarray(c["ranges"], np.float32).ravel()
+                a.kind, a.first, a.n = N.CLOUD_SCAN, n_rng, len(r)
+                a.angle_min, a.angle_increment, a.range_min, a.range_max = (float(c[k]) for k in ("angle_min", "angle_increment", "range_min", "range_max"))
+                rng.append(r)
+                n_rng += len(r)
+            else:
+                p = np.ascontiguousarray(c["points"], np.float32).reshape(-1, 3)
+                a.kind, a.first, a.n = N.CLOUD_XYZ, n_pts, len(p)
+                pts.append(p)
+                n_pts += len(p)
+        points = np.ascontiguousarray(np.concatenate(pts) if pts else np.zeros((0, 3), np.float32), np.float32)
+        ranges = np.ascontiguousarray(np.concatenate(rng) if rng else np.zeros(0, np.float32), np.float32)
+        return arr, points, ranges
+
+    def obs_buffer(self, clouds, now_ns):
+        """ObservationBuffer::bufferCloud for every cloud / scan of `clouds` (see pack_clouds), in order."""
+        arr, points, ranges = self.pack_clouds(clouds)
+        self.obs_buffer_raw(arr, len(clouds), points, ranges, now_ns)
+
+    def obs_buffer_raw(self, cloud_array, n_clouds, points, ranges, now_ns):
+        """Pre-built ctypes Cloud array + packed float32 points / ranges (no Python loops on the per-cycle path)."""
+        check(self.L.navgpu_obsbuf_buffer(self.h, C.cast(cloud_array, C.c_void_p), n_clouds, _ptr(points) if len(points) else None, len(points),
+                                          _ptr(ranges) if len(ranges) else None, len(ranges), int(now_ns)), "obsbuf_buffer")
+
+    def obs_stage(self, poses, now_ns, first=0, want_current=True):
+        """getMarkingObservations + getClearingObservations + the staging of the cycle.  Returns isCurrent per robot (bool array)."""
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        cur = np.zeros(len(poses), np.int32)
+        check(self.L.navgpu_obsbuf_stage(self.h, first, len(poses), _ptr(poses), int(now_ns), _ptr(cur) if want_current else None), "obsbuf_stage")
+        return cur.astype(bool)
+
+    def obs_observations(self, instance, now_ns=0):
+        """What obs_stage would hand over for one robot: a list of dicts {flags, origin, obstacle_range, raytrace_range, points (k, 3)}."""
+        max_obs = max(1, self.desc.max_observations)
+        obs = (Observation * max_obs)()
+        pts = np.zeros((max(1, self.obs_status(instance, 1)[0].points), 3), np.float32)
+        n_pts = C.c_uint32()
+        n = check(self.L.navgpu_obsbuf_observations(self.h, instance, int(now_ns), C.cast(obs, C.c_void_p), max_obs, _ptr(pts), len(pts), C.byref(n_pts)),
+                  "obsbuf_observations")
+        return [dict(flags=o.flags, origin=(o.origin_x, o.origin_y, o.origin_z), obstacle_range=o.obstacle_range, raytrace_range=o.raytrace_range,
+                     points=pts[o.first_point:o.first_point + o.n_points].copy()) for o in obs[:n]]
+
+    def obs_status(self, first=0, count=None):
+        first, count = self._range(first, count)
+        out = (N.ObsBufRobotStatus * count)()
+        check(self.L.navgpu_obsbuf_status(self.h, first, count, C.cast(out, C.c_void_p)), "obsbuf_status")
+        return list(out)
+
+    def obs_set_global_frame(self, transforms12, first=0, count=None):
+        """ObservationBuffer::setGlobalFrame with the looked-up new_global <- global transform, one per robot or one for all."""
+        first, count = self._range(first, count)
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(transforms12, np.float64).reshape(-1, 12), (count, 12)))
+        check(self.L.navgpu_obsbuf_set_global_frame(self.h, first, count, _ptr(m)), "obsbuf_set_global_frame")
+
+    def obs_reset_last_updated(self, now_ns, first=0, count=None):
+        first, count = self._range(first, count)
+        check(self.L.navgpu_obsbuf_reset_last_updated(self.h, first, count, int(now_ns)), "obsbuf_reset_last_updated")
 
     # ---------------------------------------------------------------- planner
     def configure_planner(self, cfg):
