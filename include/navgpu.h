@@ -76,6 +76,7 @@ typedef enum {
 } navgpu_grid_id;
 
 typedef struct navgpu_fleet navgpu_fleet;
+typedef struct navgpu_navfn navgpu_navfn;  /* a batch of global plans (NavFn section below) */
 
 typedef struct {
   uint32_t n_instances;
@@ -517,6 +518,67 @@ int navgpu_local_planner_is_goal_reached(navgpu_fleet* fleet, uint32_t first, ui
                                          const navgpu_robot_input* in, int32_t* reached);
 /* the stored global plan of one instance after pruning; returns its length (poses) or < 0 */
 int navgpu_local_planner_get_plan(navgpu_fleet* fleet, uint32_t instance, double* xyyaw, uint32_t capacity);
+
+/* ---- Device-resident global plans: LocalPlannerUtil::getLocalPlan as a kernel (k_plan_window) ----
+ * A robot's global plan may live on the device instead of in the host vector navgpu_local_planner_set_plan keeps.  The store
+ * holds n_instances x max_global_plan (x, y, yaw) records; per robot the host keeps where the live part of its slot starts and
+ * how long it is (prunePlan's erase from the front moves the start, no pose is moved), the planar plan -> global transform and
+ * whether the robot's plan is resident at all.  navgpu_local_planner_compute_velocity_commands then runs getLocalPlan for the
+ * resident robots of its range as one kernel launch and reads one navgpu_local_window (plus the window's last point and the
+ * goal pose) per robot back; no plan pose crosses the bus in either direction.  Robots whose plan came through
+ * navgpu_local_planner_set_plan keep the host path; one range may hold both kinds.
+ * navgpu_planner_stage on a resident robot replaces the window of that one cycle as it does for any robot (the caller hands
+ * it a local plan); the next navgpu_local_planner_compute_velocity_commands derives the window from the store again.
+ * navgpu_planner_stage_poses after a resident cycle behaves as after a host-path cycle: a cycle whose local plan comes out empty
+ * (nothing within reach, or everything pruned) stages nothing, and the robot's window of the cycle before stays on the device.
+ * One difference: when the call returns NAVGPU_ERR_CAPACITY because a resident robot's window does not fit, the resident robots
+ * of the range whose windows did fit already hold this cycle's window on the device (the host path stages none then); the
+ * library's record of every such window's length and last point follows, so a later navgpu_planner_stage_poses is consistent
+ * with it.  Stored plans are pruned only for the robots before the failing one, as on the host path. */
+typedef enum {
+  NAVGPU_LOCAL_WINDOW_OK = 0,
+  NAVGPU_LOCAL_WINDOW_NONE = 1,      /* no window was taken: no pose, no plan, or "Received plan with zero length"        */
+  NAVGPU_LOCAL_WINDOW_CAPACITY = 2   /* the window has more than max_plan poses; the stored plan was left as it was        */
+} navgpu_local_window_status;
+typedef struct {
+  int32_t first_index;  /* index in the stored plan (before the erase) of the first pose within reach, -1: none (also: host path) */
+  int32_t n_window;     /* poses transformGlobalPlan took, the one that leaves the reach included                            */
+  int32_t n_erased;     /* poses prunePlan erased from the front of both plans                                               */
+  int32_t n_local;      /* n_window - n_erased: the local plan's length                                                      */
+  int32_t remaining;    /* length of the stored plan after the erase                                                         */
+  int32_t status;       /* navgpu_local_window_status                                                                        */
+} navgpu_local_window;
+typedef enum { NAVGPU_PLAN_FAMILY_GLOBAL_PLANNER = 0, NAVGPU_PLAN_FAMILY_NAVFN_ROS = 1 } navgpu_plan_family;
+
+/* replaces: the storage behind LocalPlannerUtil::setPlan's global_plan_ (base_local_planner/src/local_planner_util.cpp:87-103)
+ * for a fleet.  Allocates the store, or resizes it (resident plans are carried over; one that is longer than the new size:
+ * NAVGPU_ERR_CAPACITY).  A call that fails leaves the previous store, its plans included, in force.  A fleet that never calls
+ * this allocates nothing for it. */
+int navgpu_local_planner_reserve_plans(navgpu_fleet* fleet, uint32_t max_global_plan);
+/* replaces: DWAPlannerROS::setPlan (dwa_local_planner/src/dwa_planner_ros.cpp:130-140) -> LocalPlannerUtil::setPlan
+ * (local_planner_util.cpp:87-103) for robots [first, first+count) at once: plan k is poses_xyyaw[offsets[k] .. offsets[k+1])
+ * as (x, y, yaw) triples in its own frame, plan_to_global = count x (x, y, yaw) transforms or NULL (plans already in the global
+ * frame).  One upload; goal-tolerance latches cleared, oscillation flags reset.  A plan of zero poses is stored as such (the
+ * cycle then reports "Received plan with zero length": ok 0, NAVGPU_BRANCH_NONE).  A plan longer than max_global_plan:
+ * NAVGPU_ERR_CAPACITY, nothing stored for any robot.  NAVGPU_ERR_STATE without a store or a configured local planner. */
+int navgpu_local_planner_set_plans(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* poses_xyyaw,
+                                   const uint32_t* offsets, const double* plan_to_global);
+/* replaces: move_base handing planner_->makePlan's result to tc_->setPlan (move_base/src/move_base.cpp:576-600, 888) for plans
+ * [nav_first, nav_first+count) of a NavFn handle and robots [fleet_first, fleet_first+count), without the plans leaving the
+ * device: the emit kernel of navgpu_global_planner_plans / navgpu_navfn_ros_plans (family: navgpu_plan_family) writes plan
+ * nav_first + k into the slot of robot fleet_first + k.  State checks as in those calls (NAVGPU_ERR_STATE when a plan's last
+ * maker was not of that family).  A plan that was not made (n_poses 0) is not adopted: the robot keeps its previous plan and
+ * adopted_out[k] = 0, as move_base keeps the controller's plan when makePlan fails.  A plan longer than max_global_plan is not
+ * adopted either, and the call returns NAVGPU_ERR_CAPACITY AFTER adopting the others (adopted_out says which).  Both handles
+ * must live on the same device (NAVGPU_ERR_INVALID).  The two streams are ordered with events.  adopted_out may be NULL. */
+int navgpu_local_planner_adopt_plans(navgpu_fleet* fleet, uint32_t fleet_first, navgpu_navfn* nav, uint32_t nav_first,
+                                     uint32_t count, int32_t family, const double* plan_to_global, int32_t* adopted_out);
+/* replaces: publishGlobalPlan(transformed_plan) (dwa_local_planner/src/dwa_planner_ros.cpp:166-168, 278, 292): the transformed, pruned plan of the instance's last cycle as (x, y, yaw) triples; returns its length or < 0.
+ * Works for host-path and resident robots (for the latter the poses are read from the store and transformed on the host). */
+int navgpu_local_planner_local_plan(navgpu_fleet* fleet, uint32_t instance, double* xyyaw, uint32_t capacity);
+/* replaces: what LocalPlannerUtil::getLocalPlan (local_planner_util.cpp:105-123) did in the last cycle, per robot:
+ * transformGlobalPlan's window and prunePlan's erase (goal_functions.cpp:69-174) as counts. */
+int navgpu_local_planner_windows(navgpu_fleet* fleet, uint32_t first, uint32_t count, navgpu_local_window* out);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Legacy base_local_planner::TrajectoryPlanner ("Trajectory Rollout")              */

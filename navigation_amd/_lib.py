@@ -148,6 +148,16 @@ class CmdResult(C.Structure):
 BRANCH_NONE, BRANCH_DWA, BRANCH_STOP, BRANCH_ROTATE, BRANCH_AT_GOAL = range(5)
 
 
+class LocalWindow(C.Structure):
+    """Mirror of navgpu_local_window (include/navgpu.h): what getLocalPlan did for one robot in the last cycle."""
+    _fields_ = [("first_index", C.c_int32), ("n_window", C.c_int32), ("n_erased", C.c_int32), ("n_local", C.c_int32),
+                ("remaining", C.c_int32), ("status", C.c_int32)]
+
+
+LOCAL_WINDOW_OK, LOCAL_WINDOW_NONE, LOCAL_WINDOW_CAPACITY = range(3)  # navgpu_local_window_status
+PLAN_FAMILY_GLOBAL_PLANNER, PLAN_FAMILY_NAVFN_ROS = range(2)  # navgpu_plan_family
+
+
 class TpConfig(C.Structure):
     """navgpu_tp_config; defaults are BaseLocalPlanner.cfg's (base_local_planner/cfg/BaseLocalPlanner.cfg)."""
     _fields_ = [(n, C.c_double) for n in (
@@ -429,6 +439,11 @@ SYMBOLS = [
     ("navgpu_local_planner_compute_velocity_commands", C.c_int, [vp, u32, u32, vp, vp]),
     ("navgpu_local_planner_is_goal_reached", C.c_int, [vp, u32, u32, vp, vp]),
     ("navgpu_local_planner_get_plan", C.c_int, [vp, u32, vp, u32]),
+    ("navgpu_local_planner_reserve_plans", C.c_int, [vp, u32]),
+    ("navgpu_local_planner_set_plans", C.c_int, [vp, u32, u32, vp, vp, vp]),
+    ("navgpu_local_planner_adopt_plans", C.c_int, [vp, u32, vp, u32, u32, i32, vp, vp]),
+    ("navgpu_local_planner_local_plan", C.c_int, [vp, u32, vp, u32]),
+    ("navgpu_local_planner_windows", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_tp_configure", C.c_int, [vp, C.POINTER(TpConfig)]),
     ("navgpu_tp_update_plan", C.c_int, [vp, u32, vp, u32, i32]),
     ("navgpu_tp_find_best_path", C.c_int, [vp, u32, u32, vp, vp]),

@@ -318,6 +318,29 @@ struct PoseChunk {
 static_assert(sizeof(PoseChunk) <= 4096, "kernel arguments are limited to 4 KB");
 void launch_stage_poses(const PoseChunk& c, hipStream_t s);
 void launch_sincos(const double* th, uint32_t n, double* sn, double* cs, hipStream_t s);
+// ---- device-resident global plans (local_plan_kernels.hip): LocalPlannerUtil::getLocalPlan per robot and cycle
+constexpr uint32_t kPlanWindowThreads = 256;
+constexpr uint32_t kPwActive = 1u, kPwTransform = 2u, kPwPrune = 4u;
+struct PlanWindowIn {   // what a cycle hands k_plan_window for one robot; every transcendental was taken on the host (libm)
+  double pose[2];       // the robot in the global frame
+  double robot[2];      // the robot in the plan's frame (tf.transformPose, goal_functions.cpp:113-114)
+  double c, sn, tx, ty, tyaw;  // plan -> global: cos / sin of its yaw, translation, yaw
+  uint32_t start, len;  // the live part of the robot's slot
+  uint32_t flags;       // kPw*
+  uint32_t pad;
+};
+struct PlanWindowRec {  // what it leaves: the public record, the local plan's last point, getGoalPose
+  navgpu_local_window w;
+  double last[2];
+  double goal[3];
+};
+static_assert(sizeof(PlanWindowIn) == 88 && sizeof(PlanWindowRec) == 64, "staged as arrays of these");
+// robots [first, first+count): in / rec are indexed by absolute instance, store is [n][max_global_plan]
+void launch_plan_window(const PlannerDev& pl, const navgpu_global_pose* store, uint32_t max_global_plan, uint32_t first, uint32_t count,
+                        const PlanWindowIn* in, PlanWindowRec* rec, double sq_dist_threshold, hipStream_t s);
+// slot k of the store takes poses[offsets[k] .. offsets[k + 1]) (navgpu_local_planner_set_plans' one upload, scattered)
+void launch_plan_scatter(const navgpu_global_pose* poses, const uint32_t* offsets, uint32_t count, navgpu_global_pose* slots,
+                         uint32_t max_global_plan, hipStream_t s);
 size_t score_table_bytes(const PlannerDev& pl);
 size_t score_window_bytes(uint32_t win);
 size_t score_prep_bytes(const PlannerDev& pl);

@@ -45,6 +45,9 @@ int ensureCompleteGrids(navgpu_fleet* f, uint32_t first, uint32_t count);
 // count into the pinned mirrors, and for a rolling window the new origins and pending shift (host and device).  Shared by
 // navgpu_costmap_stage and navgpu_obsbuf_stage; the caller has waited for the mirrors and copies them afterwards.
 int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses);
+// navgpu_planner_stage_poses without its "a plan was staged" check: for robots whose plan is on the device and whose length and last
+// point the pinned mirrors hold (navgpu_host.cpp)
+int stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth);
 }  // namespace navgpu
 
 struct navgpu_fleet {
@@ -113,8 +116,39 @@ struct navgpu_fleet {
     double T[3] = {0, 0, 0};       // planar plan -> global transform
     bool has_T = false, have_plan = false;
     bool xy_tolerance_latch = false, rotating_to_goal = false;  // LatchedStopRotateController members
+    std::vector<double> local;     // host path: the transformed, pruned plan of the last cycle (navgpu_local_planner_local_plan)
+    navgpu_local_window window{-1, 0, 0, 0, 0, NAVGPU_LOCAL_WINDOW_NONE};  // what getLocalPlan did in the last cycle
   };
   std::vector<LocalPlannerState> lp;
+  // device-resident global plans (navgpu_local_planner_reserve_plans ...): absent (cap 0) unless asked for
+  struct ResidentPlans {
+    uint32_t cap = 0;                         // max_global_plan
+    navgpu_global_pose* d_poses = nullptr;    // [n][cap]
+    PlanWindowIn *d_in = nullptr, *h_in = nullptr;     // [n] a cycle's inputs; h_: pinned
+    PlanWindowRec *d_rec = nullptr, *h_rec = nullptr;  // [n] and what k_plan_window left
+    uint32_t *d_off = nullptr, *h_off = nullptr;       // [n + 1] an adoption's slot offsets / an upload's plan offsets
+    uint8_t* d_up = nullptr;                  // navgpu_local_planner_set_plans' concatenated poses, grown on demand
+    size_t up_bytes = 0;
+    hipEvent_t ev_fleet = nullptr, ev_nav = nullptr;   // adoption: the store is free / the plans are in place
+    bool ev_nav_set = false;
+    struct Robot {
+      bool resident = false;       // the robot's plan is the one in its slot (not LocalPlannerState::plan)
+      uint32_t start = 0, len = 0; // live part of the slot: prunePlan's erase is start += n, len -= n
+      bool has_T = false;
+      double T[3] = {0, 0, 0};     // planar plan -> global transform
+      bool goal_known = false;
+      double goal[3] = {0, 0, 0};  // getGoalPose of the stored plan (cached: the last pose stays until the plan is replaced)
+      uint32_t loc_first = 0, loc_n = 0;  // slot positions of the last cycle's local plan
+    };
+    std::vector<Robot> robots;     // [n]
+    bool residentAt(uint32_t i) const { return cap && robots[i].resident; }
+    // What the control cycle's translation unit needs of the store, set by navgpu_local_planner_reserve_plans, so that it carries
+    // no reference to the feature's launchers (as TrajCloud::terms_pass: it also links without them, tests/tsan).
+    // window_pass: k_plan_window for the resident robots of the range with a pose and a plan, their records read into h_rec.
+    int (*window_pass)(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_input* in, double dist_threshold, int32_t prune) = nullptr;
+    bool (*goal_pose)(navgpu_fleet* f, uint32_t i, double goal[3]) = nullptr;                    // getGoalPose of a resident robot
+    int (*stored_plan)(navgpu_fleet* f, uint32_t i, double* xyyaw, uint32_t capacity) = nullptr;  // navgpu_local_planner_get_plan
+  } rp;
   navgpu_local_limits lp_limits{};
   bool lp_configured = false;
   // legacy TrajectoryPlanner (navgpu_tp_*)

@@ -278,7 +278,7 @@ int navgpu_fleet_destroy(navgpu_fleet* f) {
     hipEventDestroy(e.a);
     hipEventDestroy(e.b);
   }
-  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d})
+  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav})
     if (e) hipEventDestroy(e);
   for (void* p : f->allocs) hipFree(p);
   for (void* p : f->pinned) hipHostFree(p);
@@ -1332,6 +1332,13 @@ int navgpu_planner_stage_poses(navgpu_fleet* f, uint32_t first, uint32_t count, 
   if (!f || !pos_xyth || !vel_xyth || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   if (!f->planner_configured || !f->planner_staged) return NAVGPU_ERR_STATE;
+  return stagePosesFromMirrors(f, first, count, pos_xyth, vel_xyth);
+}
+// The body of navgpu_planner_stage_poses, also what the control cycle runs for robots whose window k_plan_window has just left on the
+// device.  Precondition, checked here: every robot of the range has a plan on the device whose length and last point the pinned
+// mirrors (hp_plan_cnt, hp_plan) hold - after navgpu_planner_stage, or written from k_plan_window's records.
+extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth) {
+  if (!f->planner_configured) return NAVGPU_ERR_STATE;
   PlannerDev& pl = f->pl;
   const navgpu_dwa_config& c = pl.cfg;
   for (uint32_t i = first; i < first + count; ++i)
@@ -1375,6 +1382,7 @@ int navgpu_planner_stage_poses(navgpu_fleet* f, uint32_t first, uint32_t count, 
     memcpy(ch.reach, f->hp_reach + ch.first, sizeof(uint32_t) * ch.count);
     launch_stage_poses(ch, f->stream);
   }
+  f->planner_staged = true;  // (the device holds a staged state for these robots, however their windows got there)
   return checkLaunch();
 }
 

@@ -88,6 +88,9 @@ int navgpu_local_planner_set_plan(navgpu_fleet* f, uint32_t instance, const doub
   if (!f->lp_configured || !f->planner_configured) return NAVGPU_ERR_STATE;
   navgpu_fleet::LocalPlannerState& st = f->lp[instance];
   st.xy_tolerance_latch = false;  // latchedStopRotateController_.resetLatching() (dwa_planner_ros.cpp:136)
+  if (f->rp.cap) f->rp.robots[instance].resident = false;  // a resident robot is back on the host path
+  st.local.clear();
+  st.window = navgpu_local_window{-1, 0, 0, 0, (int32_t)n, NAVGPU_LOCAL_WINDOW_NONE};
   st.plan.assign(plan, plan + 3 * (size_t)n);
   st.have_plan = true;
   st.has_T = T != nullptr;
@@ -98,6 +101,7 @@ int navgpu_local_planner_set_plan(navgpu_fleet* f, uint32_t instance, const doub
 int navgpu_local_planner_get_plan(navgpu_fleet* f, uint32_t instance, double* xyyaw, uint32_t capacity) {
   if (!f || instance >= f->desc.n_instances || !f->lp_configured) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
+  if (f->rp.residentAt(instance)) return f->rp.stored_plan(f, instance, xyyaw, capacity);  // read from the robot's slot
   const std::vector<double>& pl = f->lp[instance].plan;
   const uint32_t n = (uint32_t)(pl.size() / 3);
   if (xyyaw) {
@@ -108,7 +112,9 @@ int navgpu_local_planner_get_plan(navgpu_fleet* f, uint32_t instance, double* xy
 }
 
 // getGoalPose (goal_functions.cpp:175-214): the last pose of the stored plan in the global frame
-static bool goalPose(const navgpu_fleet::LocalPlannerState& st, double goal[3]) {
+static bool goalPose(navgpu_fleet* f, uint32_t instance, double goal[3]) {
+  if (f->rp.residentAt(instance)) return f->rp.goal_pose(f, instance, goal);  // from the last cycle's record, or the store
+  const navgpu_fleet::LocalPlannerState& st = f->lp[instance];
   if (st.plan.empty()) return false;
   const double* g = &st.plan[st.plan.size() - 3];
   if (st.has_T) {
@@ -136,7 +142,7 @@ int navgpu_local_planner_is_goal_reached(navgpu_fleet* f, uint32_t first, uint32
     navgpu_fleet::LocalPlannerState& st = f->lp[first + k];
     reached[k] = 0;
     double goal[3];
-    if (!in[k].have_pose || !goalPose(st, goal)) continue;
+    if (!in[k].have_pose || !goalPose(f, first + k, goal)) continue;
     // LatchedStopRotateController::isGoalReached (:66-109)
     const double dist = hypot(goal[0] - in[k].pose[0], goal[1] - in[k].pose[1]);
     if ((lim.latch_xy_goal_tolerance && st.xy_tolerance_latch) || dist <= lim.xy_goal_tolerance) {
@@ -160,19 +166,74 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
   std::vector<navgpu_robot_state> states(count);
   std::vector<uint8_t> valid(count, 0), dwa(count, 0);
   packed.reserve((size_t)count * max_plan * 2);
+  // --- getLocalPlan of the robots whose plan is resident: one k_plan_window launch, their records read back in one copy
+  bool any_resident = false;
+  for (uint32_t k = 0; k < count; ++k) any_resident = any_resident || f->rp.residentAt(first + k);
+  if (any_resident) {
+    int rc = f->rp.window_pass(f, first, count, in, dist_threshold, lim.prune_plan);
+    if (rc != NAVGPU_OK) return rc;
+    // The mirrors follow the device at once, for EVERY robot whose window the kernel emitted - also those behind a robot whose window
+    // does not fit (the call then returns before it looks at them): they say what navgpu_planner_stage_poses and restageReach read
+    // of a plan, its length and last point.  A robot whose local plan came out empty keeps window and mirrors of the cycle before,
+    // as on the host path, where nothing is staged then.  (The window pass has waited for the stream: no copy out of the mirrors
+    // is pending.)
+    for (uint32_t k = 0; k < count; ++k) {
+      const uint32_t i = first + k;
+      if (!f->rp.residentAt(i) || !in[k].have_pose || f->rp.robots[i].len == 0) continue;
+      const PlanWindowRec& rec = f->rp.h_rec[i];
+      if (rec.w.status != NAVGPU_LOCAL_WINDOW_OK || rec.w.n_local <= 0) continue;
+      const uint32_t n_loc = (uint32_t)rec.w.n_local;
+      f->hp_plan_cnt[i] = n_loc;
+      f->hp_plan[((size_t)i * max_plan + n_loc - 1) * 2] = rec.last[0];
+      f->hp_plan[((size_t)i * max_plan + n_loc - 1) * 2 + 1] = rec.last[1];
+    }
+  }
+  std::vector<float> res_pos((size_t)count * 3), res_vel((size_t)count * 3);
   // --- getLocalPlan per robot (computeVelocityCommands :254-271)
   for (uint32_t k = 0; k < count; ++k) {
     navgpu_fleet::LocalPlannerState& st = f->lp[first + k];
     navgpu_cmd_result& o = out[k];
     o = navgpu_cmd_result();
+    st.local.clear();
+    st.window = navgpu_local_window{-1, 0, 0, 0, 0, NAVGPU_LOCAL_WINDOW_NONE};
+    if (f->rp.residentAt(first + k)) {
+      navgpu_fleet::ResidentPlans::Robot& R = f->rp.robots[first + k];
+      R.loc_n = 0;
+      st.window.remaining = (int32_t)R.len;
+      if (!in[k].have_pose || R.len == 0) continue;    // as below
+      const PlanWindowRec& rec = f->rp.h_rec[first + k];
+      st.window = rec.w;
+      if (rec.w.status == NAVGPU_LOCAL_WINDOW_CAPACITY) return NAVGPU_ERR_CAPACITY;  // (before pruning, as the host path)
+      const uint32_t n_loc = (uint32_t)rec.w.n_local;
+      R.loc_first = R.start + (uint32_t)(rec.w.first_index < 0 ? 0 : rec.w.first_index) + (uint32_t)rec.w.n_erased;
+      R.loc_n = n_loc;
+      R.start += (uint32_t)rec.w.n_erased;             // prunePlan's erase from the front of the stored plan
+      R.len -= (uint32_t)rec.w.n_erased;
+      memcpy(R.goal, rec.goal, sizeof(R.goal));
+      R.goal_known = true;
+      o.local_plan_points = (int32_t)n_loc;
+      if (n_loc == 0) continue;
+      valid[k] = 2;
+      for (int a = 0; a < 3; ++a) {
+        res_pos[3 * (size_t)k + a] = (float)in[k].pose[a];
+        res_vel[3 * (size_t)k + a] = (float)in[k].odom_vel[a];
+      }
+      continue;
+    }
     if (!in[k].have_pose) continue;                    // "Could not get robot pose"
+    st.window.remaining = (int32_t)(st.plan.size() / 3);
     if (!st.have_plan || st.plan.empty()) continue;    // transformGlobalPlan: "Received plan with zero length"
     uint32_t n_loc = 0, n_er = 0;
     int rc = navgpu_local_plan_window(st.plan.data(), (uint32_t)(st.plan.size() / 3), in[k].pose, st.has_T ? st.T : nullptr,
                                       dist_threshold, lim.prune_plan, &local[(size_t)k * max_plan * 3], max_plan, &n_loc, &n_er);
-    if (rc == NAVGPU_ERR_CAPACITY) return rc;
+    if (rc == NAVGPU_ERR_CAPACITY) {
+      st.window.status = NAVGPU_LOCAL_WINDOW_CAPACITY;
+      return rc;
+    }
     if (rc != NAVGPU_OK) continue;
     if (n_er) st.plan.erase(st.plan.begin(), st.plan.begin() + 3 * (size_t)std::min<size_t>(n_er, st.plan.size() / 3));
+    st.local.assign(&local[(size_t)k * max_plan * 3], &local[(size_t)k * max_plan * 3] + 3 * (size_t)n_loc);
+    st.window = navgpu_local_window{-1, (int32_t)(n_loc + n_er), (int32_t)n_er, (int32_t)n_loc, (int32_t)(st.plan.size() / 3), NAVGPU_LOCAL_WINDOW_OK};
     o.local_plan_points = (int32_t)n_loc;
     if (n_loc == 0) continue;                          // "Received an empty transformed plan."
     valid[k] = 1;
@@ -195,8 +256,13 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
       continue;
     }
     uint32_t e = k;
-    while (e < count && valid[e]) ++e;
-    int rc = navgpu_planner_stage(f, first + k, e - k, &states[k], packed.data(), (uint32_t)(packed.size() / 2));
+    while (e < count && valid[e] == valid[k]) ++e;
+    int rc;
+    if (valid[k] == 1) {
+      rc = navgpu_planner_stage(f, first + k, e - k, &states[k], packed.data(), (uint32_t)(packed.size() / 2));
+    } else {  // resident: the window is on the device already; pose, nose goal, alignment switch and reach through k_stage_poses
+      rc = stagePosesFromMirrors(f, first + k, e - k, &res_pos[3 * (size_t)k], &res_vel[3 * (size_t)k]);
+    }
     if (rc != NAVGPU_OK) return rc;
     k = e;
   }
@@ -206,7 +272,7 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
     navgpu_fleet::LocalPlannerState& st = f->lp[first + k];
     double goal[3];
     bool reached = false;
-    if (goalPose(st, goal)) {
+    if (goalPose(f, first + k, goal)) {
       const double dist = hypot(goal[0] - in[k].pose[0], goal[1] - in[k].pose[1]);
       if ((lim.latch_xy_goal_tolerance && st.xy_tolerance_latch) || dist <= lim.xy_goal_tolerance) {
         st.xy_tolerance_latch = true;
@@ -220,7 +286,7 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
     }
     // computeVelocityCommandsStopRotate (:211-273)
     navgpu_cmd_result& o = out[k];
-    if (!goalPose(st, goal)) continue;  // "Could not get goal pose"
+    if (!goalPose(f, first + k, goal)) continue;  // "Could not get goal pose"
     if (lim.latch_xy_goal_tolerance && !st.xy_tolerance_latch) st.xy_tolerance_latch = true;
     const double yaw = in[k].pose[2], vel_yaw = in[k].odom_vel[2];
     const double angle = navgpu_shortest_angular_distance(yaw, goal[2]);

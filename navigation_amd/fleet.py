@@ -488,6 +488,53 @@ class Fleet:
             check(self.L.navgpu_local_planner_get_plan(self.h, instance, _ptr(out), n), "local_planner_get_plan")
         return out
 
+    def reserve_global_plans(self, max_global_plan):
+        """Allocates (or resizes) the device store of global plans: n_instances x max_global_plan poses."""
+        check(self.L.navgpu_local_planner_reserve_plans(self.h, int(max_global_plan)), "local_planner_reserve_plans")
+
+    def set_global_plans(self, plans_xyyaw, plans_to_global=None, first=0):
+        """DWAPlannerROS::setPlan for robots first .. first + len(plans) - 1 in one upload; the plans stay on the device.
+        plans_to_global: None, or one (x, y, yaw) per plan (all plans then carry a transform)."""
+        plans = [np.ascontiguousarray(p, np.float64).reshape(-1, 3) for p in plans_xyyaw]
+        offsets = np.zeros(len(plans) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(p) for p in plans])
+        poses = np.ascontiguousarray(np.concatenate(plans) if plans else np.zeros((0, 3)))
+        T = None if plans_to_global is None else np.ascontiguousarray(plans_to_global, np.float64).reshape(len(plans), 3)
+        check(self.L.navgpu_local_planner_set_plans(self.h, first, len(plans), _ptr(poses) if len(poses) else None, _ptr(offsets),
+                                                    None if T is None else _ptr(T)), "local_planner_set_plans")
+
+    def adopt_global_plans(self, navfn, family, count=None, first=0, nav_first=0, plans_to_global=None):
+        """The plans nav_first .. of a NavFn batch's last make_plan (family: PLAN_FAMILY_GLOBAL_PLANNER / _NAVFN_ROS) become the
+        plans of robots first ..; nothing leaves the device.  Returns a bool per robot: adopted (False: the plan was not made or is
+        too long; the robot keeps its previous plan).  On NAVGPU_ERR_CAPACITY the others were adopted first: the NavgpuError raised
+        carries that list as `.adopted`."""
+        count = navfn.n - nav_first if count is None else count
+        T = None if plans_to_global is None else np.ascontiguousarray(plans_to_global, np.float64).reshape(count, 3)
+        adopted = np.zeros(count, np.int32)
+        rc = self.L.navgpu_local_planner_adopt_plans(self.h, first, navfn.h, nav_first, count, int(family), None if T is None else _ptr(T),
+                                                     _ptr(adopted))
+        try:
+            check(rc, "local_planner_adopt_plans")
+        except NavgpuError as e:
+            e.adopted = [bool(v) for v in adopted] if rc == -4 else None  # NAVGPU_ERR_CAPACITY: who was adopted before the error
+            raise
+        return [bool(v) for v in adopted]
+
+    def local_plan(self, instance):
+        """The transformed, pruned plan of the robot's last cycle, (m, 3)."""
+        n = check(self.L.navgpu_local_planner_local_plan(self.h, instance, None, 0), "local_planner_local_plan")
+        out = np.zeros((n, 3))
+        if n:
+            check(self.L.navgpu_local_planner_local_plan(self.h, instance, _ptr(out), n), "local_planner_local_plan")
+        return out
+
+    def local_windows(self, first=0, count=None):
+        """navgpu_local_window of the last cycle per robot -> list of LocalWindow."""
+        count = self.n - first if count is None else count
+        out = (N.LocalWindow * count)()
+        check(self.L.navgpu_local_planner_windows(self.h, first, count, out), "local_planner_windows")
+        return list(out)
+
     def _robot_inputs(self, poses, odom_vels, have_pose):
         poses = np.asarray(poses, np.float64).reshape(-1, 3)
         vels = np.asarray(odom_vels, np.float64).reshape(-1, 3)
