@@ -927,6 +927,11 @@ int navgpu_navfn_set_costmap(navgpu_navfn* nav, uint32_t first, uint32_t count, 
  * plan first + k takes the master grid of fleet instance fleet_first + k; nothing crosses PCIe */
 int navgpu_navfn_set_costmap_from_fleet(navgpu_navfn* nav, uint32_t first, uint32_t count, navgpu_fleet* fleet, uint32_t fleet_first,
                                         int32_t allow_unknown);
+/* replaces: the same hand-over (navfn_ros.cpp:265-268; planner_core.cpp:290 for cost_mode 0) where a run of plans works on ONE
+ * robot's costmap - the candidate goals of navgpu_move_base_plan_service: every plan of [first, first+count) takes the master grid
+ * of fleet instance `instance`, through cost_mode as in navgpu_navfn_set_costmap */
+int navgpu_navfn_set_costmap_from_fleet_instance(navgpu_navfn* nav, uint32_t first, uint32_t count, navgpu_fleet* fleet, uint32_t instance,
+                                                 int32_t cost_mode, int32_t allow_unknown);
 /* replaces: NavFn::setGoal / setStart + calcNavFnDijkstra(at_start) | calcNavFnAstar() (navfn.cpp:145-171, 293-345).
  * goals_xy, starts_xy = count x {x, y} cells.  (NavfnROS passes the robot as "goal" and the goal as "start",
  * navfn_ros.cpp:270-281: the potential is grown from the robot.) */
@@ -1149,6 +1154,135 @@ int navgpu_navfn_ros_valid_point_potential(navgpu_navfn* nav, uint32_t first, ui
  * come from a prefix sum, not from atomics: two calls give identical bytes.  count <= 65535 and count * nx * ny < 2^32. */
 int navgpu_navfn_ros_potential_cloud(navgpu_navfn* nav, uint32_t first, uint32_t count, const double* frames, uint32_t capacity,
                                      navgpu_navfn_ros_cloud_point* points, uint32_t* offsets);
+
+/* ------------------------------------------------------------------------------------------ */
+/* move_base's planner-side executive for a fleet: polygon writes, clearing windows, the plan   */
+/* handover with its persistence policy (move_base/src/move_base.cpp)                           */
+/* ------------------------------------------------------------------------------------------ */
+#define NAVGPU_MAX_POLYGON 256 /* vertices of one polygon of navgpu_costmap_set_polygon_cost */
+/* replaces: Costmap2D::setConvexPolygonCost(polygon, cost_value) (costmap_2d.cpp:315-428: worldToMap of every vertex,
+ * polygonOutlineCells' raytraceLine walk, convexFillCells' column fill) as a public operation, for robots [first, first+count) at
+ * once: polygon k is polys_xy[offsets[k] .. offsets[k+1]) as world {x, y} pairs, written with `value` (any byte) into `grid` of
+ * robot first + k.  grid is NAVGPU_GRID_MASTER (what MoveBase::clearCostmapWindows writes, move_base.cpp:304, 329) or
+ * NAVGPU_GRID_OBSTACLE (what MoveSlowAndClear writes into its "obstacles" layers, move_slow_and_clear.cpp:109-127); anything else
+ * is NAVGPU_ERR_INVALID, an obstacle grid the fleet does not have NAVGPU_ERR_STATE.
+ * As in the reference: a vertex whose worldToMap fails gives ok_out[k] = 0 and nothing is written for that robot (the other
+ * robots are unaffected; no error of the call); fewer than 3 vertices give ok_out[k] = 1 and nothing written; else per column
+ * every cell from the lowest to the highest outline cell is written - which is what the bubble sort and pairwise walk of
+ * convexFillCells amount to, for polygons that are not convex too (tests/test_gpu_polygon_cost.py holds it to the compiled
+ * rule).  A polygon may have up to NAVGPU_MAX_POLYGON vertices (NAVGPU_ERR_CAPACITY above) and span any number of columns.
+ * offsets must not decrease (NAVGPU_ERR_INVALID); ok_out may be NULL.  NAVGPU_ERR_STATE while a staged rolling-window origin has
+ * not been applied by an update yet (the polygons are in world coordinates).  A call that fails changes nothing.  The layer's
+ * bounds are not touched: the reference's callers do not touch them either (MoveSlowAndClear's write reaches the master grid
+ * with the next update whose bounds cover it). */
+int navgpu_costmap_set_polygon_cost(navgpu_fleet* fleet, int grid, uint32_t first, uint32_t count, const double* polys_xy,
+                                    const uint32_t* offsets, uint8_t value, int32_t* ok_out);
+/* replaces: one half of MoveBase::clearCostmapWindows(size_x, size_y) (move_base.cpp:277-330) - the reference clears the planner's
+ * and the controller's costmap; here the caller names the fleet that holds each - for robots [first, first+count): poses_xy =
+ * count x {x, y} (getRobotPose's origin), the polygon (x - size_x / 2, y - size_y / 2), (x + size_x / 2, y - size_y / 2),
+ * (x + size_x / 2, y + size_y / 2), (x - size_x / 2, y + size_y / 2) in that order and those expressions, FREE_SPACE on the master
+ * grid through navgpu_costmap_set_polygon_cost.  A window with a corner off the map clears nothing, as in the reference (which
+ * ignores setConvexPolygonCost's return value); ok_out (may be NULL) reports it. */
+int navgpu_move_base_clear_costmap_windows(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* poses_xy, double size_x,
+                                           double size_y, int32_t* ok_out);
+
+/* MoveBase::persistence_end_ per robot, held as the reference holds it: a time in ns whose two special values are times too */
+#define NAVGPU_PERSISTENCE_INITIAL 0LL           /* PERSISTENCE_INITIAL = ros::Time(0, 0) (move_base.cpp:58)  */
+#define NAVGPU_PERSISTENCE_NEWPLAN 1000000000LL  /* PERSISTENCE_NEWPLAN = ros::Time(1, 0) (:59)               */
+typedef enum {
+  NAVGPU_HANDOVER_NONE = 0,     /* the plan was not made (n_poses 0): new_global_plan_ is false, the robot and its state untouched */
+  NAVGPU_HANDOVER_ADOPT = 1,    /* preferPrevPlan returned false: the new plan is the controller's plan                           */
+  NAVGPU_HANDOVER_KEEP = 2,     /* it returned true: the controller keeps its plan, the caller replans (state_ = PLANNING)         */
+  NAVGPU_HANDOVER_TOO_LONG = 3  /* the plan is longer than max_global_plan: the robot and its state untouched                      */
+} navgpu_handover_decision;
+typedef struct {
+  int32_t decision;            /* navgpu_handover_decision                                                           */
+  int32_t closest_index;       /* findClosestPlanIndex: an index of the controller plan as it was handed over        */
+  int32_t prev_len;            /* prev_plan_len = controller_plan_->size() - closest_i                               */
+  int32_t new_len;             /* latest_plan_->size()                                                               */
+  int32_t dropped;             /* leading poses of the controller plan that are no longer stored (a store resize)    */
+  int32_t reserved;
+  int64_t persistence_end_ns;  /* the robot's state after the call                                                   */
+} navgpu_handover_record;
+/* replaces: executeCycle's `if(new_global_plan_ && !preferPrevPlan(current_position))` handing controller_plan_ to tc_->setPlan
+ * (move_base.cpp:873-888) with MoveBase::preferPrevPlan and findClosestPlanIndex (:784-836), for robots [fleet_first,
+ * fleet_first+count) and plans [nav_first, nav_first+count) of a NavFn handle.  The arguments of navgpu_local_planner_adopt_plans,
+ * and: positions_xy = count x {x, y}, the robots' positions in their plans' frame; now_ns (ros::Time::now()); persistence_timeout_ns
+ * (plan_persistence_timeout_, 10 s by default, :57); out = one record per robot (may be NULL).
+ * Per robot whose plan was made and fits the store, on the device (k_plan_prefer, a workgroup per robot):
+ *   closest_i  the first index with the strictly smallest hypot(pos.x - p.x, pos.y - p.y) below 1e9 over indices 0, 4, 8, ... of
+ *              the controller plan AS IT WAS HANDED OVER - move_base's controller_plan_ is never pruned, and the store keeps the
+ *              poses prunePlan erased in place; 0 when none is below 1e9 (NaN included), for an empty plan and for a robot without
+ *              a resident plan (whose controller plan counts as empty).  hypot is restated (within 1 ulp of libm's): the index is
+ *              libm's unless two sampled distances are closer than that.
+ *   prev_len = original length - closest_i; prefer_prev = prev_len + 320 < new_len.
+ *   If prefer_prev and the state is not INITIAL: a state of NEWPLAN becomes now + timeout; then now < state is KEEP.
+ *   In every other case the state becomes NEWPLAN and the decision is ADOPT.
+ * ADOPT is navgpu_local_planner_adopt_plans for that robot (slot written by the emit kernel, latch cleared, oscillation flags
+ * reset); the emit kernel is predicated per robot on the decision, which has not left the device by then.  KEEP changes nothing
+ * of the robot but its persistence state.  One record per robot is read back afterwards; no plan pose crosses the bus.
+ * Departure: navgpu_local_planner_reserve_plans' resize carries only the live part of a plan over.  `dropped` counts the leading
+ * poses lost that way; the search then visits the original indices >= dropped that are multiples of 4 (prev_len still counts
+ * from the original length).
+ * Returns as navgpu_local_planner_adopt_plans: NAVGPU_ERR_CAPACITY after handling the others when a plan is too long (its
+ * record says TOO_LONG); NAVGPU_ERR_INVALID also for a NULL positions_xy or a negative timeout.  A call that fails with
+ * NAVGPU_ERR_INVALID or NAVGPU_ERR_STATE has changed nothing.  NAVGPU_ERR_HIP (a launch or copy failed) may come after the device
+ * has updated persistence states and written slots whose host bookkeeping was not done: hand those robots their plans again
+ * (navgpu_local_planner_set_plans) and set their states before going on, as after any failed device call. */
+int navgpu_move_base_handover_plans(navgpu_fleet* fleet, uint32_t fleet_first, navgpu_navfn* nav, uint32_t nav_first, uint32_t count,
+                                    int32_t family, const double* plan_to_global, const double* positions_xy, int64_t now_ns,
+                                    int64_t persistence_timeout_ns, navgpu_handover_record* out);
+/* replaces: `persistence_end_ = PERSISTENCE_INITIAL` on a new goal (move_base.cpp:664, 707) for robots [first, first+count) */
+int navgpu_move_base_reset_persistence(navgpu_fleet* fleet, uint32_t first, uint32_t count);
+/* replaces: nothing in the reference, which keeps persistence_end_ private: the robots' states for tests and checkpoints,
+ * count x int64 ns.  NAVGPU_ERR_STATE (all three calls) without a store (navgpu_local_planner_reserve_plans). */
+int navgpu_move_base_get_persistence(navgpu_fleet* fleet, uint32_t first, uint32_t count, int64_t* persistence_end_ns);
+int navgpu_move_base_set_persistence(navgpu_fleet* fleet, uint32_t first, uint32_t count, const int64_t* persistence_end_ns);
+
+/* MoveBase::planService's search for a feasible goal (move_base.cpp:340-426) on a NavFn handle: every candidate goal of a request
+ * is a plan of one batch. */
+#define NAVGPU_PLAN_SERVICE_MAX_CANDIDATES 1024 /* candidates of one request, the exact goal included */
+typedef struct {
+  double start[3];           /* the start pose {x, y, yaw}: req.start, or the robot's pose (:355-360)                        */
+  double goal[3];            /* req.goal                                                                                      */
+  double frame[3];           /* {origin_x, origin_y, resolution} of the planner's costmap                                     */
+  double tolerance;          /* req.tolerance                                                                                 */
+  double default_tolerance;  /* navfn_ros family: what makePlan(start, goal, plan) hands on (navfn_ros.cpp:213-216); else unread */
+} navgpu_plan_service_request;
+typedef struct {
+  int32_t winner;        /* index of the first candidate, in the reference's order, whose plan was made; -1: none             */
+  int32_t slot;          /* the plan slot that holds its plan (navgpu_*_plans, navgpu_move_base_handover_plans); -1: none     */
+  int32_t tried;         /* makePlan calls the reference would have made: winner + 1, or every candidate                      */
+  int32_t n_candidates;  /* candidates of the request, the exact goal included                                                */
+  int32_t n_poses;       /* poses of the winner's plan, the appended req.goal included; 0: none                               */
+  int32_t rounds;        /* batches this request took part in                                                                 */
+} navgpu_plan_service_result;
+/* replaces: the candidate goals of planService (move_base.cpp:372-396) for one request, on the host: candidate 0 is the exact
+ * goal; then, in float arithmetic as written (float resolution, search_increment = (float)(resolution * 3.0), replaced by
+ * (float)tolerance when 0 < tolerance < search_increment; float loop variables compared with doubles; the max_offset - 1e-9 and
+ * -1 * 0 skips), goal + (double)(offset * mult) for every ring.  out_xy = up to capacity x {x, y}; returns the number of
+ * candidates (all of them, whatever the capacity), or NAVGPU_ERR_INVALID for NULL arguments or a resolution that is not positive
+ * and finite.  The count stops at NAVGPU_PLAN_SERVICE_MAX_CANDIDATES + 1. */
+int navgpu_move_base_plan_service_candidates(const double* goal_xy, double resolution, double tolerance, uint32_t capacity, double* out_xy);
+/* replaces: planService's makePlan loop (move_base.cpp:365-417) for n_requests requests at once.  Request q owns the plan slots
+ * [first_slot + q * slots_per_request, + slots_per_request) of the handle; their cost arrays must hold the request's costmap
+ * (navgpu_navfn_set_costmap with shared = 1, or navgpu_navfn_set_costmap_from_fleet_instance, for the cost mode the family takes;
+ * clearCostmapWindows (:363) is the caller's step before that, navgpu_move_base_clear_costmap_windows).  The candidates of each
+ * request run through the family's make_plan (navgpu_global_planner_make_plan with params / options, or navgpu_navfn_ros_make_plan
+ * with ros_params and the request's default_tolerance) slots_per_request at a time, every request of a round in one batch; a
+ * request stops after the first round that holds a success, so with slots_per_request >= its candidates it is one batch.
+ * The winner is the first candidate in the reference's order with status OK and n_poses > 0; when it is not candidate 0, req.goal
+ * is appended to its plan (:402) by the emit pass: navgpu_*_plans and navgpu_move_base_handover_plans see the pose without a
+ * host round trip.  winner_results (may be NULL) = n_requests x the family's make_plan result struct, the winner's (zeroed
+ * without one; n_poses there does not count the appended pose).
+ * Departure: the reference stops at the first success; here the candidates behind it in its round were planned too
+ * (speculatively - their results are discarded, `tried` counts as the reference would).
+ * NAVGPU_ERR_INVALID for NULL arguments, a bad range or family, what the family's make_plan refuses, or a request with more than
+ * NAVGPU_PLAN_SERVICE_MAX_CANDIDATES candidates; nothing has run then. */
+int navgpu_move_base_plan_service(navgpu_navfn* nav, uint32_t first_slot, uint32_t slots_per_request, uint32_t n_requests, int32_t family,
+                                  const navgpu_global_planner_params* params, const navgpu_make_plan_options* options,
+                                  const navgpu_navfn_ros_params* ros_params, const navgpu_plan_service_request* requests,
+                                  navgpu_plan_service_result* results, void* winner_results);
 
 /* ------------------------------------------------------------------------------------------ */
 /* amcl::AMCLLaser - the laser sensor update of a batch of particle filters (one per robot)   */

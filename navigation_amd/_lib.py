@@ -158,6 +158,30 @@ LOCAL_WINDOW_OK, LOCAL_WINDOW_NONE, LOCAL_WINDOW_CAPACITY = range(3)  # navgpu_l
 PLAN_FAMILY_GLOBAL_PLANNER, PLAN_FAMILY_NAVFN_ROS = range(2)  # navgpu_plan_family
 
 
+class HandoverRecord(C.Structure):
+    """Mirror of navgpu_handover_record (include/navgpu.h): what MoveBase::preferPrevPlan decided for one robot."""
+    _fields_ = [("decision", C.c_int32), ("closest_index", C.c_int32), ("prev_len", C.c_int32), ("new_len", C.c_int32),
+                ("dropped", C.c_int32), ("reserved", C.c_int32), ("persistence_end_ns", C.c_int64)]
+
+
+class PlanServiceRequest(C.Structure):
+    """Mirror of navgpu_plan_service_request (include/navgpu.h): one nav_msgs::GetPlan request of MoveBase::planService."""
+    _fields_ = [("start", C.c_double * 3), ("goal", C.c_double * 3), ("frame", C.c_double * 3), ("tolerance", C.c_double),
+                ("default_tolerance", C.c_double)]
+
+
+class PlanServiceResult(C.Structure):
+    """Mirror of navgpu_plan_service_result (include/navgpu.h)."""
+    _fields_ = [("winner", C.c_int32), ("slot", C.c_int32), ("tried", C.c_int32), ("n_candidates", C.c_int32), ("n_poses", C.c_int32),
+                ("rounds", C.c_int32)]
+
+
+PLAN_SERVICE_MAX_CANDIDATES = 1024  # NAVGPU_PLAN_SERVICE_MAX_CANDIDATES
+HANDOVER_NONE, HANDOVER_ADOPT, HANDOVER_KEEP, HANDOVER_TOO_LONG = range(4)  # navgpu_handover_decision
+PERSISTENCE_INITIAL, PERSISTENCE_NEWPLAN = 0, 1000000000  # MoveBase::persistence_end_'s special values, ns
+MAX_POLYGON = 256  # NAVGPU_MAX_POLYGON
+
+
 class TpConfig(C.Structure):
     """navgpu_tp_config; defaults are BaseLocalPlanner.cfg's (base_local_planner/cfg/BaseLocalPlanner.cfg)."""
     _fields_ = [(n, C.c_double) for n in (
@@ -444,6 +468,15 @@ SYMBOLS = [
     ("navgpu_local_planner_adopt_plans", C.c_int, [vp, u32, vp, u32, u32, i32, vp, vp]),
     ("navgpu_local_planner_local_plan", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_local_planner_windows", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_costmap_set_polygon_cost", C.c_int, [vp, C.c_int, u32, u32, vp, vp, C.c_uint8, vp]),
+    ("navgpu_move_base_clear_costmap_windows", C.c_int, [vp, u32, u32, vp, C.c_double, C.c_double, vp]),
+    ("navgpu_move_base_handover_plans", C.c_int, [vp, u32, vp, u32, u32, i32, vp, vp, C.c_int64, C.c_int64, vp]),
+    ("navgpu_move_base_reset_persistence", C.c_int, [vp, u32, u32]),
+    ("navgpu_move_base_get_persistence", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_move_base_set_persistence", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_move_base_plan_service_candidates", C.c_int, [vp, C.c_double, C.c_double, u32, vp]),
+    ("navgpu_move_base_plan_service", C.c_int, [vp, u32, u32, u32, i32, vp, vp, vp, vp, vp, vp]),
+    ("navgpu_navfn_set_costmap_from_fleet_instance", C.c_int, [vp, u32, u32, vp, u32, i32, i32]),
     ("navgpu_tp_configure", C.c_int, [vp, C.POINTER(TpConfig)]),
     ("navgpu_tp_update_plan", C.c_int, [vp, u32, vp, u32, i32]),
     ("navgpu_tp_find_best_path", C.c_int, [vp, u32, u32, vp, vp]),

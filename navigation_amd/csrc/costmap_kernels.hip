@@ -122,45 +122,7 @@ void launch_shift_u32(const uint32_t* src, uint32_t* dst, const CostmapDev& cm, 
 // ------------------------------------------------------------------------------------------------
 // Bresenham walkers
 // ------------------------------------------------------------------------------------------------
-// Costmap2D::raytraceLine + bresenham2D (costmap_2d.h:359-417): `at(offset)` on every visited cell
-template <class F>
-__device__ __forceinline__ void raytrace2d(uint32_t nx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t max_length,
-                                           F&& at) {
-  int dx = (int)x1 - (int)x0, dy = (int)y1 - (int)y0;
-  uint32_t abs_dx = dx < 0 ? -dx : dx, abs_dy = dy < 0 ? -dy : dy;
-  int offset_dx = dx > 0 ? 1 : -1;  // sign(0) == -1 (costmap_2d.h:414-417)
-  int offset_dy = (dy > 0 ? 1 : -1) * (int)nx;
-  uint32_t offset = y0 * nx + x0;
-  double dist = sqrt((double)dx * (double)dx + (double)dy * (double)dy);  // exact integers: == hypot(dx, dy)
-  double scale = (dist == 0.0) ? 1.0 : fmin(1.0, (double)max_length / dist);
-  uint32_t abs_da, abs_db, lim;
-  int offset_a, offset_b;
-  if (abs_dx >= abs_dy) {
-    abs_da = abs_dx;
-    abs_db = abs_dy;
-    offset_a = offset_dx;
-    offset_b = offset_dy;
-  } else {
-    abs_da = abs_dy;
-    abs_db = abs_dx;
-    offset_a = offset_dy;
-    offset_b = offset_dx;
-  }
-  lim = (uint32_t)(scale * abs_da);
-  int error_b = abs_da / 2;
-  uint32_t end = lim < abs_da ? lim : abs_da;
-  for (uint32_t i = 0; i < end; ++i) {
-    at(offset);
-    offset += offset_a;
-    error_b += abs_db;
-    if ((uint32_t)error_b >= abs_da) {
-      offset += offset_b;
-      error_b -= abs_da;
-    }
-  }
-  at(offset);
-}
-
+// (raytrace2d - Costmap2D::raytraceLine + bresenham2D - is in navgpu_device.h: k_set_polygon_cost walks outlines with it too)
 // VoxelGrid::raytraceLine + bresenham3D (voxel_grid.h:226-308): `at(offset, z_mask)`
 template <class F>
 __device__ __forceinline__ void raytrace3d(uint32_t nx, double x0, double y0, double z0, double x1, double y1, double z1,

@@ -80,11 +80,15 @@ __global__ __launch_bounds__(kGpThreads) void k_gp_plan_emit(NavfnDev nv, uint32
   __shared__ int wave_best[kGpWaves];
   GpPlanView p;
   p.r = recs[blockIdx.x];
-  const int n = p.r.n_poses, mode = p.r.mode;
+  const int n = p.r.n_poses - (p.r.has_tail ? 1 : 0), mode = p.r.mode;  // the planner's own plan; a tail pose goes behind it untouched
   if (n <= 0) return;  // (the whole workgroup)
   p.px = nv.path + (size_t)(first + blockIdx.x) * 2 * nv.path_cap;
   p.py = p.px + nv.path_cap;
   const uint32_t base = offsets[blockIdx.x];
+  // (the whole workgroup) nothing of this plan fits.  In 64 bits, as below: kPpNoWrite, the offset of a plan that a handover keeps out
+  // of its robot's slot (navgpu_device.h), is 0xFFFFFFFF and capacity at most that.
+  if ((uint64_t)base >= capacity) return;
+  if (p.r.has_tail && threadIdx.x == 0 && (uint64_t)base + n < capacity) poses[base + n] = navgpu_global_pose{p.r.tail_x, p.r.tail_y, p.r.tail_yaw};
   const bool forward = mode == NAVGPU_ORIENT_FORWARD || mode == NAVGPU_ORIENT_FORWARD_THEN_INTERPOLATE;
   const bool search = mode == NAVGPU_ORIENT_FORWARD_THEN_INTERPOLATE && n >= 3;
   const double last = search ? p.forward(n - 3) : 0.0;

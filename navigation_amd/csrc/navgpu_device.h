@@ -341,6 +341,25 @@ void launch_plan_window(const PlannerDev& pl, const navgpu_global_pose* store, u
 // slot k of the store takes poses[offsets[k] .. offsets[k + 1]) (navgpu_local_planner_set_plans' one upload, scattered)
 void launch_plan_scatter(const navgpu_global_pose* poses, const uint32_t* offsets, uint32_t count, navgpu_global_pose* slots,
                          uint32_t max_global_plan, hipStream_t s);
+// ---- move_base's plan handover and polygon writes (move_base_kernels.hip)
+constexpr uint32_t kPlanPreferThreads = 256;  // sampled poses (every fourth of the plan) a workgroup looks at per chunk
+constexpr uint32_t kPpActive = 1u;
+constexpr uint32_t kPpNoWrite = 0xFFFFFFFFu;  // an emit offset at or beyond any capacity (a uint32_t): k_gp_plan_emit leaves at once for that plan
+struct PlanPreferIn {    // what a handover hands k_plan_prefer for one robot
+  double x, y;           // the robot in the plan's frame
+  uint32_t stored;       // poses in the robot's slot from its beginning (erased prefix + live part); 0: no resident plan
+  uint32_t dropped;      // leading poses of the plan as handed over that a store resize lost
+  uint32_t new_len;      // latest_plan_->size()
+  uint32_t flags;        // kPpActive: the new plan was made and fits the store
+};
+static_assert(sizeof(PlanPreferIn) == 32 && sizeof(navgpu_handover_record) == 32, "staged as arrays of these");
+// robots [first, first+count): in / rec / emit_off are indexed from 0, persistence by absolute instance, store is [n][max_global_plan].
+// emit_off[k] = the robot's slot offset where the decision is ADOPT, kPpNoWrite otherwise.
+void launch_plan_prefer(const navgpu_global_pose* store, uint32_t max_global_plan, uint32_t first, uint32_t count, const PlanPreferIn* in,
+                        int64_t* persistence, int64_t now_ns, int64_t timeout_ns, navgpu_handover_record* rec, uint32_t* emit_off, hipStream_t s);
+// polygon k = xy[off[k] .. off[k + 1]) into grid[(first + k) * stride ...]; ok[k] as Costmap2D::setConvexPolygonCost returns
+void launch_set_polygon_cost(const CostmapDev& cm, uint8_t* grid, uint32_t first, uint32_t count, const double* xy, const uint32_t* off,
+                             uint8_t value, int32_t* ok, hipStream_t s);
 size_t score_table_bytes(const PlannerDev& pl);
 size_t score_window_bytes(uint32_t win);
 size_t score_prep_bytes(const PlannerDev& pl);
@@ -364,6 +383,45 @@ __device__ __forceinline__ bool worldToMap(const Geom& g, double wx, double wy, 
   mx = (uint32_t)(int)fx;
   my = (uint32_t)(int)fy;
   return mx < g.nx && my < g.ny;
+}
+
+// Costmap2D::raytraceLine + bresenham2D (costmap_2d.h:359-417): `at(offset)` on every visited cell
+template <class F>
+__device__ __forceinline__ void raytrace2d(uint32_t nx, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t max_length,
+                                           F&& at) {
+  int dx = (int)x1 - (int)x0, dy = (int)y1 - (int)y0;
+  uint32_t abs_dx = dx < 0 ? -dx : dx, abs_dy = dy < 0 ? -dy : dy;
+  int offset_dx = dx > 0 ? 1 : -1;  // sign(0) == -1 (costmap_2d.h:414-417)
+  int offset_dy = (dy > 0 ? 1 : -1) * (int)nx;
+  uint32_t offset = y0 * nx + x0;
+  double dist = sqrt((double)dx * (double)dx + (double)dy * (double)dy);  // exact integers: == hypot(dx, dy)
+  double scale = (dist == 0.0) ? 1.0 : fmin(1.0, (double)max_length / dist);
+  uint32_t abs_da, abs_db, lim;
+  int offset_a, offset_b;
+  if (abs_dx >= abs_dy) {
+    abs_da = abs_dx;
+    abs_db = abs_dy;
+    offset_a = offset_dx;
+    offset_b = offset_dy;
+  } else {
+    abs_da = abs_dy;
+    abs_db = abs_dx;
+    offset_a = offset_dy;
+    offset_b = offset_dx;
+  }
+  lim = (uint32_t)(scale * abs_da);
+  int error_b = abs_da / 2;
+  uint32_t end = lim < abs_da ? lim : abs_da;
+  for (uint32_t i = 0; i < end; ++i) {
+    at(offset);
+    offset += offset_a;
+    error_b += abs_db;
+    if ((uint32_t)error_b >= abs_da) {
+      offset += offset_b;
+      error_b -= abs_da;
+    }
+  }
+  at(offset);
 }
 
 // |(x, y)| for generic doubles: sqrt of the correctly summed squares (within 1 ulp of libm hypot)

@@ -48,6 +48,10 @@ int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const doubl
 // navgpu_planner_stage_poses without its "a plan was staged" check: for robots whose plan is on the device and whose length and last
 // point the pinned mirrors hold (navgpu_host.cpp)
 int stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth);
+// device-resident global plans (navgpu_resident_plan.cpp), for the handover of navgpu_move_base.cpp: wait until the last adoption's
+// copies out of ResidentPlans::h_off have run; a robot's slot has just taken a new plan of len poses (DWAPlannerROS::setPlan's host side)
+int waitAdoption(navgpu_fleet* f);
+void becomeResident(navgpu_fleet* f, uint32_t i, uint32_t len, const double* T);
 }  // namespace navgpu
 
 struct navgpu_fleet {
@@ -134,6 +138,7 @@ struct navgpu_fleet {
     struct Robot {
       bool resident = false;       // the robot's plan is the one in its slot (not LocalPlannerState::plan)
       uint32_t start = 0, len = 0; // live part of the slot: prunePlan's erase is start += n, len -= n
+      uint32_t dropped = 0;        // poses erased before a store resize: no longer in the slot (the resize moves the live part to its front)
       bool has_T = false;
       double T[3] = {0, 0, 0};     // planar plan -> global transform
       bool goal_known = false;
@@ -149,6 +154,17 @@ struct navgpu_fleet {
     bool (*goal_pose)(navgpu_fleet* f, uint32_t i, double goal[3]) = nullptr;                    // getGoalPose of a resident robot
     int (*stored_plan)(navgpu_fleet* f, uint32_t i, double* xyyaw, uint32_t capacity) = nullptr;  // navgpu_local_planner_get_plan
   } rp;
+  // move_base's executive (navgpu_move_base.cpp): per-robot persistence_end_ and the handover's and the polygon writes' staging,
+  // allocated when the first of those calls runs
+  struct MoveBaseState {
+    int64_t* d_persist = nullptr;                           // [n] MoveBase::persistence_end_ in ns
+    PlanPreferIn *d_in = nullptr, *h_in = nullptr;          // [n] a handover's inputs; h_: pinned
+    navgpu_handover_record *d_rec = nullptr, *h_rec = nullptr;  // [n] and its records
+    uint32_t *d_poly_off = nullptr, *h_poly_off = nullptr;  // [n + 1] a polygon write's vertex offsets
+    int32_t *d_poly_ok = nullptr, *h_poly_ok = nullptr;     // [n] and what setConvexPolygonCost returned
+    double* d_poly_xy = nullptr;                            // its vertices, grown on demand
+    size_t poly_cap = 0;                                    // vertices d_poly_xy holds
+  } mb;
   navgpu_local_limits lp_limits{};
   bool lp_configured = false;
   // legacy TrajectoryPlanner (navgpu_tp_*)

@@ -116,6 +116,19 @@ int navgpu_navfn_set_costmap_from_fleet(navgpu_navfn* h, uint32_t first, uint32_
   return checkLaunch();
 }
 
+int navgpu_navfn_set_costmap_from_fleet_instance(navgpu_navfn* h, uint32_t first, uint32_t count, navgpu_fleet* f, uint32_t instance,
+                                                 int32_t cost_mode, int32_t allow_unknown) {
+  if (!h || !f || !navfnRange(h, first, count) || instance >= f->desc.n_instances || cost_mode < 0 || cost_mode > 2) return NAVGPU_ERR_INVALID;
+  if ((int)f->cm.nx != h->nv.nx || (int)f->cm.ny != h->nv.ny || f->desc.device != h->device) return NAVGPU_ERR_INVALID;
+  NavfnGuard guard_(h);
+  FleetGuard fleet_guard_(f);
+  HIP_TRY(waitStream(f->stream));  // the fleet's last costmap update has landed
+  launch_navfn_costmap(h->nv, first, count, f->cm.master + (size_t)instance * f->cm.cells_padded, 0, cost_mode, allow_unknown, h->stream);  // stride 0: one map for all
+  h->made.forget(first, count);
+  HIP_TRY(waitStream(h->stream));
+  return checkLaunch();
+}
+
 int navgpu_navfn_plan(navgpu_navfn* h, uint32_t first, uint32_t count, const int32_t* goals, const int32_t* starts, int32_t astar, int32_t at_start,
                       navgpu_navfn_result* results) {
   if (!h || !goals || !starts || !navfnRange(h, first, count)) return NAVGPU_ERR_INVALID;

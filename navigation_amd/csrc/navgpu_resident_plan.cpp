@@ -4,9 +4,9 @@
 // local_plan_kernels.hip has the kernels.
 #include "navgpu_navfn.h"
 
-namespace {
-
 using Robot = navgpu_fleet::ResidentPlans::Robot;
+
+namespace navgpu {
 
 // the slot offsets / plan offsets in h_off may still feed an adoption's copy on the NavFn handle's stream
 int waitAdoption(navgpu_fleet* f) {
@@ -14,6 +14,29 @@ int waitAdoption(navgpu_fleet* f) {
   f->rp.ev_nav_set = false;
   return NAVGPU_OK;
 }
+
+// a robot's plan has been replaced: DWAPlannerROS::setPlan's host side (latch cleared), the host copy dropped
+void becomeResident(navgpu_fleet* f, uint32_t i, uint32_t len, const double* T) {
+  Robot& R = f->rp.robots[i];
+  R.resident = true;
+  R.start = 0;
+  R.dropped = 0;
+  R.len = len;
+  R.has_T = T != nullptr;
+  if (T) memcpy(R.T, T, sizeof(R.T));
+  R.goal_known = false;
+  R.loc_first = R.loc_n = 0;
+  navgpu_fleet::LocalPlannerState& st = f->lp[i];
+  st.xy_tolerance_latch = false;  // latchedStopRotateController_.resetLatching() (dwa_planner_ros.cpp:136)
+  st.plan.clear();
+  st.have_plan = false;
+  st.local.clear();
+  st.window = navgpu_local_window{-1, 0, 0, 0, (int32_t)len, NAVGPU_LOCAL_WINDOW_NONE};
+}
+
+}  // namespace navgpu
+
+namespace {
 
 void toGlobal(const Robot& R, const navgpu_global_pose& p, double out[3]) {  // goal_functions.cpp:148-150, planar
   if (R.has_T) {
@@ -26,24 +49,6 @@ void toGlobal(const Robot& R, const navgpu_global_pose& p, double out[3]) {  // 
     out[1] = p.y;
     out[2] = p.yaw;
   }
-}
-
-// a robot's plan has been replaced: DWAPlannerROS::setPlan's host side (latch cleared), the host copy dropped
-void becomeResident(navgpu_fleet* f, uint32_t i, uint32_t len, const double* T) {
-  Robot& R = f->rp.robots[i];
-  R.resident = true;
-  R.start = 0;
-  R.len = len;
-  R.has_T = T != nullptr;
-  if (T) memcpy(R.T, T, sizeof(R.T));
-  R.goal_known = false;
-  R.loc_first = R.loc_n = 0;
-  navgpu_fleet::LocalPlannerState& st = f->lp[i];
-  st.xy_tolerance_latch = false;  // latchedStopRotateController_.resetLatching() (dwa_planner_ros.cpp:136)
-  st.plan.clear();
-  st.have_plan = false;
-  st.local.clear();
-  st.window = navgpu_local_window{-1, 0, 0, 0, (int32_t)len, NAVGPU_LOCAL_WINDOW_NONE};
 }
 
 int windowPass(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_input* in, double dist_threshold, int32_t prune) {
@@ -167,6 +172,7 @@ int navgpu_local_planner_reserve_plans(navgpu_fleet* f, uint32_t max_global_plan
   for (uint32_t i = 0; i < n; ++i) {
     Robot& R = rp.robots[i];
     if (R.loc_n) R.loc_first -= R.start;
+    R.dropped += R.start;  // the erased prefix is not carried over (navgpu_move_base_handover_plans reports it)
     R.start = 0;
   }
   f->release(rp.d_poses);

@@ -123,6 +123,27 @@ class Fleet:
         b = np.ascontiguousarray(np.broadcast_to(np.asarray(boxes, np.float64).reshape(-1, 4), (count, 4)))
         check(self.L.navgpu_layer_reset_bounding_box(self.h, first, count, _ptr(b)), "layer_reset_bounding_box")
 
+    def set_polygon_cost(self, grid, polygons, value, first=0):
+        """Costmap2D::setConvexPolygonCost on GRID_MASTER or GRID_OBSTACLE of robots first ..: one polygon (k, 2) of world points per
+        robot (an empty one writes nothing).  Returns a bool per robot: False where a vertex is off the map (nothing written)."""
+        polys = [np.ascontiguousarray(p, np.float64).reshape(-1, 2) for p in polygons]
+        offsets = np.zeros(len(polys) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(p) for p in polys])
+        xy = np.ascontiguousarray(np.concatenate(polys) if polys else np.zeros((0, 2)))
+        ok = np.zeros(len(polys), np.int32)
+        check(self.L.navgpu_costmap_set_polygon_cost(self.h, grid, first, len(polys), _ptr(xy) if len(xy) else None, _ptr(offsets),
+                                                     int(value), _ptr(ok)), "costmap_set_polygon_cost")
+        return [bool(v) for v in ok]
+
+    def clear_costmap_windows(self, poses_xy, size_x, size_y, first=0):
+        """MoveBase::clearCostmapWindows on this fleet's master grids: a size_x x size_y window round each robot becomes FREE_SPACE.
+        Returns a bool per robot: False where a corner is off the map (nothing cleared, as in the reference)."""
+        p = np.ascontiguousarray(np.asarray(poses_xy, np.float64).reshape(-1, 2))
+        ok = np.zeros(len(p), np.int32)
+        check(self.L.navgpu_move_base_clear_costmap_windows(self.h, first, len(p), _ptr(p), float(size_x), float(size_y), _ptr(ok)),
+              "move_base_clear_costmap_windows")
+        return [bool(v) for v in ok]
+
     # ---------------------------------------------------------------- layers
     def add_static_map(self, occupancy, first=0, count=None, track_unknown_space=True, use_maximum=False,
                        trinary_costmap=True, lethal_cost_threshold=100, unknown_cost_value=-1):
@@ -519,6 +540,39 @@ class Fleet:
             e.adopted = [bool(v) for v in adopted] if rc == -4 else None  # NAVGPU_ERR_CAPACITY: who was adopted before the error
             raise
         return [bool(v) for v in adopted]
+
+    def handover_global_plans(self, navfn, family, positions_xy, now_ns, persistence_timeout_ns=10_000_000_000, count=None, first=0,
+                              nav_first=0, plans_to_global=None):
+        """move_base's handover of a NavFn batch's plans with MoveBase::preferPrevPlan's persistence policy, decided on the device:
+        adopt_global_plans' arguments, the robots' positions in their plans' frame (count, 2) and the time.  Returns a list of
+        HandoverRecord.  On NAVGPU_ERR_CAPACITY the others were handled first: the NavgpuError raised carries the list as `.records`."""
+        count = navfn.n - nav_first if count is None else count
+        T = None if plans_to_global is None else np.ascontiguousarray(plans_to_global, np.float64).reshape(count, 3)
+        pos = np.ascontiguousarray(np.asarray(positions_xy, np.float64).reshape(count, 2))
+        out = (N.HandoverRecord * count)()
+        rc = self.L.navgpu_move_base_handover_plans(self.h, first, navfn.h, nav_first, count, int(family), None if T is None else _ptr(T),
+                                                    _ptr(pos), int(now_ns), int(persistence_timeout_ns), out)
+        try:
+            check(rc, "move_base_handover_plans")
+        except NavgpuError as e:
+            e.records = list(out) if rc == -4 else None
+            raise
+        return list(out)
+
+    def reset_plan_persistence(self, first=0, count=None):
+        """persistence_end_ = PERSISTENCE_INITIAL (a new goal)."""
+        first, count = self._range(first, count)
+        check(self.L.navgpu_move_base_reset_persistence(self.h, first, count), "move_base_reset_persistence")
+
+    def plan_persistence(self, first=0, count=None):
+        first, count = self._range(first, count)
+        out = np.zeros(count, np.int64)
+        check(self.L.navgpu_move_base_get_persistence(self.h, first, count, _ptr(out)), "move_base_get_persistence")
+        return out
+
+    def set_plan_persistence(self, persistence_end_ns, first=0):
+        a = np.ascontiguousarray(persistence_end_ns, np.int64).reshape(-1)
+        check(self.L.navgpu_move_base_set_persistence(self.h, first, len(a), _ptr(a)), "move_base_set_persistence")
 
     def local_plan(self, instance):
         """The transformed, pruned plan of the robot's last cycle, (m, 3)."""

@@ -13,14 +13,15 @@
   navfn_ros_compute_potential             NavfnROS::computePotential         (:171-197)
   navfn_ros_point_potential / navfn_ros_valid_point_potential   getPointPotential / validPointPotential (:130-169)
   navfn_ros_potential_cloud               the `potential` topic's cloud      (:342-368)
+  plan_service / plan_service_candidates  MoveBase::planService's goal search (move_base/src/move_base.cpp:365-417)
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
 
 import numpy as np
 
-from ._lib import (GlobalPlannerParams, GlobalPose, MakePlanOptions, MakePlanResult, NavfnResult, NavfnRosCloudPoint, NavfnRosParams,
-                   NavfnRosResult, check, lib)
+from ._lib import (PLAN_FAMILY_GLOBAL_PLANNER, GlobalPlannerParams, GlobalPose, MakePlanOptions, MakePlanResult, NavfnResult,
+                   NavfnRosCloudPoint, NavfnRosParams, NavfnRosResult, PlanServiceRequest, PlanServiceResult, check, lib)
 
 
 class NavFn:
@@ -57,6 +58,12 @@ class NavFn:
     def set_costmap_from_fleet(self, fleet, first=0, count=None, fleet_first=0, allow_unknown=True):
         count = (self.n - first) if count is None else count
         check(self.L.navgpu_navfn_set_costmap_from_fleet(self.h, first, count, fleet.h, fleet_first, int(allow_unknown)), "navfn_set_costmap_from_fleet")
+
+    def set_costmap_from_fleet_instance(self, fleet, instance, first=0, count=None, cost_mode=1, allow_unknown=True):
+        """every plan of the range takes the master grid of ONE fleet instance (the slots of a plan_service request)"""
+        count = (self.n - first) if count is None else count
+        check(self.L.navgpu_navfn_set_costmap_from_fleet_instance(self.h, first, count, fleet.h, instance, cost_mode, int(allow_unknown)),
+              "navfn_set_costmap_from_fleet_instance")
 
     def plan(self, goals, starts, first=0, astar=False, at_start=True):
         g = np.ascontiguousarray(goals, np.int32).reshape(-1, 2)
@@ -220,6 +227,40 @@ class NavFn:
                                                       pts.ctypes.data_as(C.c_void_p) if capacity else None, offsets.ctypes.data_as(C.c_void_p)),
               "navfn_ros_potential_cloud")
         return pts[:min(capacity, int(offsets[-1]))], offsets
+
+    def plan_service_candidates(self, goal_xy, resolution, tolerance):
+        """planService's candidate goals, the exact goal first: (n, 2) float64"""
+        g = np.ascontiguousarray(goal_xy, np.float64).reshape(2)
+        n = check(self.L.navgpu_move_base_plan_service_candidates(g.ctypes.data_as(C.c_void_p), float(resolution), float(tolerance), 0, None),
+                  "move_base_plan_service_candidates")
+        out = np.zeros((n, 2))
+        check(self.L.navgpu_move_base_plan_service_candidates(g.ctypes.data_as(C.c_void_p), float(resolution), float(tolerance), n,
+                                                              out.ctypes.data_as(C.c_void_p)), "move_base_plan_service_candidates")
+        return out
+
+    def plan_service(self, family, requests, slots_per_request, first_slot=0, orientation_mode=0, wavefront=False, w_dist=1.0, w_len=0.0,
+                     **params):
+        """navgpu_move_base_plan_service: MoveBase::planService's goal search for a list of requests - dicts with start, goal
+        (x, y, yaw), frame (origin_x, origin_y, resolution), tolerance and, for the navfn_ros family, default_tolerance.  Request q
+        owns the slots first_slot + q * slots_per_request ...; their costs must be set.  Returns (list of PlanServiceResult, list of
+        the winners' make_plan results); the winner's plan is read with plans() / navfn_ros_plans(first=result.slot, count=1)."""
+        arr = (PlanServiceRequest * len(requests))()
+        for a, r in zip(arr, requests):
+            a.start[:] = [float(v) for v in r["start"]]
+            a.goal[:] = [float(v) for v in r["goal"]]
+            a.frame[:] = [float(v) for v in r["frame"]]
+            a.tolerance = float(r["tolerance"])
+            a.default_tolerance = float(r.get("default_tolerance", 0.0))
+        res = (PlanServiceResult * len(requests))()
+        is_gp = int(family) == PLAN_FAMILY_GLOBAL_PLANNER
+        won = ((MakePlanResult if is_gp else NavfnRosResult) * len(requests))()
+        gp, opt = GlobalPlannerParams(**params), MakePlanOptions(int(orientation_mode), int(wavefront))
+        nr = NavfnRosParams(float(w_dist), float(w_len), int(wavefront), 0)
+        check(self.L.navgpu_move_base_plan_service(self.h, first_slot, int(slots_per_request), len(requests), int(family),
+                                                   C.byref(gp) if is_gp else None, C.byref(opt) if is_gp else None, None if is_gp else C.byref(nr),
+                                                   C.cast(arr, C.c_void_p), C.cast(res, C.c_void_p), C.cast(won, C.c_void_p)),
+              "move_base_plan_service")
+        return list(res), list(won)
 
     def path(self, plan=0):
         n = check(self.L.navgpu_navfn_path(self.h, plan, None, 0), "navfn_path")

@@ -236,6 +236,21 @@ void ObstacleLayer::resetMap(unsigned int x0, unsigned int y0, unsigned int xn, 
   if (gpu_.fleet() && navgpu_grid_reset_window(gpu_.fleet(), NAVGPU_GRID_OBSTACLE, 0, 1, x0, y0, xn, yn) != NAVGPU_OK)
     ROS_ERROR("navgpu_grid_reset_window: %s", navgpu_last_error());
 }
+bool ObstacleLayer::setConvexPolygonCostOnDevice(const std::vector<geometry_msgs::Point>& polygon, unsigned char cost_value) {
+  boost::unique_lock<boost::recursive_mutex> lock(gpu_access_);
+  const bool ok = costmap_2d::ObstacleLayer::setConvexPolygonCost(polygon, cost_value);
+  if (!gpu_.fleet()) return ok;
+  std::vector<double> xy;
+  for (size_t i = 0; i < polygon.size(); ++i) {
+    xy.push_back(polygon[i].x);
+    xy.push_back(polygon[i].y);
+  }
+  const uint32_t offsets[2] = {0, (uint32_t)polygon.size()};
+  int32_t device_ok = 0;
+  if (navgpu_costmap_set_polygon_cost(gpu_.fleet(), NAVGPU_GRID_OBSTACLE, 0, 1, xy.empty() ? NULL : &xy[0], offsets, cost_value, &device_ok) != NAVGPU_OK)
+    return false;
+  return ok && device_ok != 0;
+}
 bool ObstacleLayer::gpuUpdateBounds(double rx, double ry, double ryaw, double* min_x, double* min_y, double* max_x, double* max_y) {
   boost::unique_lock<boost::recursive_mutex> lock(gpu_access_);
   // obstacle_layer.cpp:340-413.  The reconfigurable parameters are re-pushed every cycle (ObstaclePluginConfig's

@@ -110,6 +110,10 @@ class ObstacleLayer : public costmap_2d::ObstacleLayer {
   virtual void matchSize();
   virtual void reset();
   virtual void resetMap(unsigned int x0, unsigned int y0, unsigned int xn, unsigned int yn);  // CostmapLayer::resetBoundingBox's clear
+  // Costmap2D::setConvexPolygonCost (not virtual in the reference) on the host copy and on the device-resident layer grid: what a
+  // caller that clears this layer from outside uses (navgpu::MoveSlowAndClear).  The host copy's return value; false also when the
+  // device refuses (navgpu_last_error says why).
+  bool setConvexPolygonCostOnDevice(const std::vector<geometry_msgs::Point>& polygon, unsigned char cost_value);
   virtual void updateBounds(double robot_x, double robot_y, double robot_yaw, double* min_x, double* min_y, double* max_x,
                             double* max_y);
   virtual void updateCosts(costmap_2d::Costmap2D& master_grid, int min_i, int min_j, int max_i, int max_j);
