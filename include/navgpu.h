@@ -391,6 +391,23 @@ int navgpu_planner_samples(navgpu_fleet* fleet, uint32_t instance, double* costs
 /* replaces: DWAPlanner::checkTrajectory (dwa_planner.cpp:213-237) for one instance; uses the
  * staged state of that instance.  *ok = 1 when the single sample scores >= 0. */
 int navgpu_planner_check_trajectory(navgpu_fleet* fleet, uint32_t instance, const float vel_samples[3], int32_t* ok);
+/* replaces: a loop of DWAPlanner::checkTrajectory(pos, vel, vel_samples) calls (dwa_planner.cpp:213-237) over robots and samples.
+ * instances: n_robots strictly increasing absolute robot indices (any subset of the fleet).  Robot k of the list owns the probes
+ * probe_offsets[k] .. probe_offsets[k + 1] (probe_offsets[0] = 0, never decreasing); a robot without probes is left entirely alone,
+ * its oscillation flags included.  Per (robot, probe) the contract is the single call's: the pose and velocity of the robot's last
+ * navgpu_planner_stage / _stage_poses, the configuration, footprint, MapGrid options and rollout_trig in force; ordered on the
+ * fleet's stream behind whatever is queued; returns when the answers are in the caller's arrays.  costs[p] is what
+ * scoreTrajectory(traj, -1) returns - the full weighted sum, or the code of the first failing critic in the list - and
+ * ok[p] = costs[p] >= 0 (costs may be NULL).  A probe the generator rejects is an empty trajectory: cost 0, ok 1 (the reference ignores
+ * generateTrajectory's return value).  The oscillation critic sees cleared flags, and the flags of every robot with at least one
+ * probe are zero afterwards (checkTrajectory resets them, :217).  One upload, one launch (k_check_traj) and one read-back for the
+ * whole list; the answers go through a buffer of their own, so navgpu_planner_results / _samples / _trajectory still describe the
+ * last cycle.  NAVGPU_ERR_INVALID: a null or malformed list (not increasing, out of range, decreasing offsets);
+ * NAVGPU_ERR_STATE: before configure / stage.  The probe buffers grow on demand and are kept; when they cannot be allocated the
+ * call fails with nothing launched and no flag reset. */
+int navgpu_planner_check_trajectories(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances,
+                                      const uint32_t* probe_offsets /* n_robots + 1 */, const float* vel_samples /* 3 per probe */,
+                                      int32_t* ok /* per probe */, double* costs /* per probe, may be NULL */);
 /* replaces: DWAPlanner::getCellCosts (dwa_planner.cpp:185-202) over the whole map + MapGridVisualizer::publishCostCloud
  * (base_local_planner/src/map_grid_visualizer.cpp:55-83): the cost cloud of one instance from the grids of its last
  * cycle.  points = up to `capacity` x {x, y, z, path_cost, goal_cost, occ_cost, total_cost} (MapGridCostPoint), in the
@@ -883,7 +900,8 @@ typedef enum {
   NAVGPU_K_FOOTPRINT = 6,/* batched footprint-cost queries                */
   NAVGPU_K_VOXEL_EXPORT = 7, /* voxel points / clearing endpoints: count, scan and emit launches */
   NAVGPU_K_OBS_INGEST = 8,   /* observation buffer: transform + filter + compaction of the clouds of a call */
-  NAVGPU_K_COUNT = 9
+  NAVGPU_K_CHECK_TRAJ = 9,  /* batched checkTrajectory: the probes of a robot list (navgpu_planner_check_trajectories) */
+  NAVGPU_K_COUNT = 10
 } navgpu_kernel_id;
 /* HIP-event timing of the kernels on the fleet's stream.  While enabled every launch of the
  * listed kernels is bracketed by two hipEventRecord calls; read() synchronises and returns the

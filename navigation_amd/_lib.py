@@ -12,8 +12,8 @@ LAYER_STATIC, LAYER_OBSTACLE, LAYER_VOXEL, LAYER_INFLATION = 1, 2, 4, 8
 GRID_MASTER, GRID_STATIC, GRID_OBSTACLE, GRID_VOXEL, GRID_PATH, GRID_GOAL, GRID_GOAL_FRONT = range(7)
 OBS_MARKING, OBS_CLEARING = 1, 2
 VOXEL_UNKNOWN, VOXEL_MARKED = 1, 2  # voxel_grid::VoxelStatus
-K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT, K_VOXEL_EXPORT, K_OBS_INGEST = range(9)
-KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export", "k_obs_ingest")
+K_OBSTACLE, K_MERGE, K_INFLATE, K_BFS, K_SCORE, K_SELECT, K_FOOTPRINT, K_VOXEL_EXPORT, K_OBS_INGEST, K_CHECK_TRAJ = range(10)
+KERNELS = ("k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export", "k_obs_ingest", "k_check_traj")
 CLOUD_XYZ, CLOUD_SCAN = 0, 1  # NAVGPU_CLOUD_*
 OBSBUF_MAX_SOURCES, OBSBUF_MAX_CLOUD_POINTS = 8, 65536
 
@@ -450,6 +450,7 @@ SYMBOLS = [
     ("navgpu_planner_trajectory", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_planner_samples", C.c_int, [vp, u32, vp, vp, vp, u32]),
     ("navgpu_planner_check_trajectory", C.c_int, [vp, u32, vp, C.POINTER(i32)]),
+    ("navgpu_planner_check_trajectories", C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
     ("navgpu_planner_cost_cloud", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_planner_set_trajectory_cloud", C.c_int, [vp, u32, u32, i32]),
     ("navgpu_planner_trajectory_cloud", C.c_int, [vp, u32, i32, vp, u32]),

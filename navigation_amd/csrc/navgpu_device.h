@@ -194,6 +194,17 @@ struct TrajCloudDev {
   int32_t reference_costs;
 };
 void launch_score_terms(const PlannerDev& pl, uint32_t inst, SampleTerms* terms, hipStream_t s);
+// batched checkTrajectory (navgpu_planner_check_trajectories): per-launch view of the fleet's probe buffers
+struct ProbeBatch {
+  const uint32_t* instances;  // [n_robots] absolute robot indices, strictly increasing
+  const uint32_t* offsets;    // [n_robots + 1] robot k owns probes offsets[k] .. offsets[k + 1]
+  const float* vel;           // [probes][3] velocity samples
+  double* cost;               // [probes] scoreTrajectory's value: the weighted sum, or the first failing critic's code
+};
+// Weak: navgpu_planner_check_trajectories sits beside the single call in navgpu_host.cpp, and that translation unit is also linked
+// against a stand-in for the kernels that knows the launchers of its day (tests/tsan); there the call answers NAVGPU_ERR_STATE.
+// libnavgpu.so always carries the launcher (planner_score.hip).
+__attribute__((weak)) void launch_check_traj(const PlannerDev& pl, const ProbeBatch& pb, uint32_t n_robots, uint32_t max_probes, hipStream_t s);
 void launch_traj_scan(const PlannerDev& pl, const TrajCloudDev& t, uint32_t inst, hipStream_t s);
 void launch_traj_emit(const PlannerDev& pl, const TrajCloudDev& t, uint32_t inst, uint32_t n_slots, hipStream_t s);
 uint32_t traj_emit_slots_per_group(uint32_t max_sim_steps);  // 0: a trajectory of that many points does not fit a workgroup's LDS

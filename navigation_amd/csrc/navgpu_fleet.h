@@ -243,6 +243,13 @@ struct navgpu_fleet {
     hipEvent_t ev_h2d = nullptr;    // behind the copy out of h_in
     bool ev_set = false;
   } ob;
+  // batched checkTrajectory (navgpu_planner_check_trajectories): what a call hands over - robot list, offsets, samples - as one
+  // pinned block and its device twin, and the costs coming back; grown on demand (all four or none) and kept
+  struct Probes {
+    uint32_t cap = 0;             // probes the buffers hold
+    uint32_t *d_in = nullptr, *h_in = nullptr;    // [n] instances, [n + 1] offsets, [cap][3] samples (floats)
+    double *d_cost = nullptr, *h_cost = nullptr;  // [cap]
+  } pb;
   std::vector<uint8_t> obs_consumed;            // [n] an update has run on what navgpu_costmap_stage staged last
   navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers

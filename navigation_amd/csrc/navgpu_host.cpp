@@ -30,7 +30,7 @@ int navgpu_device_count(void) {
   return n;
 }
 const char* navgpu_kernel_name(int32_t k) {
-  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export", "k_obs_ingest"};
+  static const char* names[NAVGPU_K_COUNT] = {"k_obstacle", "k_merge", "k_inflate", "k_bfs", "k_score", "k_select", "k_footprint_cost", "k_voxel_export", "k_obs_ingest", "k_check_traj"};
   return (k >= 0 && k < NAVGPU_K_COUNT) ? names[k] : "?";
 }
 
@@ -1573,6 +1573,86 @@ int navgpu_planner_check_trajectory(navgpu_fleet* f, uint32_t instance, const fl
   HIP_TRY(waitStream(f->stream));
   *ok = (idx != 0x7FFFFFFF) ? 1 : 0;
   return checkLaunch();
+}
+
+// The batched form: one upload, one k_check_traj launch, one read-back for the probes of all listed robots.  The answers go through
+// buffers of their own (navgpu_fleet::Probes): the cycle's partial argmin, per-sample costs and counters are not touched.
+int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const uint32_t* probe_offsets,
+                                      const float* vel_samples, int32_t* ok, double* costs) {
+  if (!f || !n_robots || !instances || !probe_offsets || n_robots > f->desc.n_instances || probe_offsets[0] != 0) return NAVGPU_ERR_INVALID;
+  uint32_t max_probes = 0;
+  for (uint32_t k = 0; k < n_robots; ++k) {
+    if (instances[k] >= f->desc.n_instances || (k && instances[k] <= instances[k - 1]) || probe_offsets[k + 1] < probe_offsets[k]) return NAVGPU_ERR_INVALID;
+    max_probes = std::max(max_probes, probe_offsets[k + 1] - probe_offsets[k]);
+  }
+  const uint32_t total = probe_offsets[n_robots];
+  if (total && (!vel_samples || !ok)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->planner_configured || !f->planner_staged || !launch_check_traj) return NAVGPU_ERR_STATE;
+  if (!total) return NAVGPU_OK;  // no robot has a probe: nobody's flags are reset
+  PlannerDev& pl = f->pl;
+  navgpu_fleet::Probes& pb = f->pb;
+  const size_t head = 2 * (size_t)n_robots + 1;  // words in front of the samples
+  if (total > pb.cap) {  // all four buffers or none; the ones they replace are idle (every call drains the stream)
+    navgpu_fleet::Probes nb;
+    nb.cap = (total + 255u) & ~255u;
+    const size_t words = 2 * (size_t)f->desc.n_instances + 1 + 3 * (size_t)nb.cap;
+    int rc = f->alloc(&nb.d_in, words);
+    if (!rc) rc = f->alloc(&nb.d_cost, nb.cap);
+    if (!rc) rc = f->allocPinned(&nb.h_in, words);
+    if (!rc) rc = f->allocPinned(&nb.h_cost, nb.cap);
+    if (rc) {
+      f->release(nb.d_in);
+      f->release(nb.d_cost);
+      f->releasePinned(nb.h_in);
+      f->releasePinned(nb.h_cost);
+      return rc;
+    }
+    f->release(pb.d_in);
+    f->release(pb.d_cost);
+    f->releasePinned(pb.h_in);
+    f->releasePinned(pb.h_cost);
+    pb = nb;
+  }
+  // Bounded MapGrids: the single call's test per listed robot, with the largest reach over its probes; the robots that fail it get
+  // complete grids, in contiguous runs
+  for (uint32_t k = 0; k < n_robots;) {
+    auto leavesBox = [&](uint32_t q) {
+      const uint32_t i = instances[q];
+      if (!f->grid_partial[i] || probe_offsets[q + 1] == probe_offsets[q]) return false;
+      const navgpu_robot_state& st = f->hp_state[i];
+      double reach = 0.0;
+      for (uint32_t p = probe_offsets[q]; p < probe_offsets[q + 1]; ++p) reach = std::max(reach, reachMetres(pl.cfg, st.vel, vel_samples + 3 * (size_t)p));
+      const uint32_t need = (uint32_t)std::min(ceil(reach / pl.res) + 3.0, 32768.0);
+      int32_t nb[4];
+      const int32_t* hb = &f->h_box[(size_t)4 * i];
+      return !(!pl.mg_generic && robotBox(f, i, st.pos, need, nb) && nb[0] >= hb[0] && nb[1] <= hb[1] && nb[2] >= hb[2] && nb[3] <= hb[3]);
+    };
+    if (!leavesBox(k)) {
+      ++k;
+      continue;
+    }
+    uint32_t e = k + 1;
+    while (e < n_robots && instances[e] == instances[e - 1] + 1 && leavesBox(e)) ++e;
+    int rc = ensureCompleteGrids(f, instances[k], e - k);
+    if (rc) return rc;
+    k = e;
+  }
+  memcpy(pb.h_in, instances, sizeof(uint32_t) * n_robots);
+  memcpy(pb.h_in + n_robots, probe_offsets, sizeof(uint32_t) * (n_robots + 1));
+  memcpy(pb.h_in + head, vel_samples, sizeof(float) * 3 * total);
+  HIP_TRY(hipMemcpyAsync(pb.d_in, pb.h_in, sizeof(uint32_t) * (head + 3 * (size_t)total), hipMemcpyHostToDevice, f->stream));
+  const ProbeBatch batch{pb.d_in, pb.d_in + n_robots, reinterpret_cast<const float*>(pb.d_in + head), pb.d_cost};
+  PROFILED(f, NAVGPU_K_CHECK_TRAJ, launch_check_traj(pl, batch, n_robots, max_probes, f->stream));
+  HIP_TRY(hipMemcpyAsync(pb.h_cost, pb.d_cost, sizeof(double) * total, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(waitStream(f->stream));
+  int rc = checkLaunch();
+  if (rc) return rc;
+  for (uint32_t p = 0; p < total; ++p) {
+    ok[p] = pb.h_cost[p] >= 0 ? 1 : 0;
+    if (costs) costs[p] = pb.h_cost[p];
+  }
+  return NAVGPU_OK;
 }
 
 int navgpu_planner_cost_cloud(navgpu_fleet* f, uint32_t instance, float* points, uint32_t capacity) {

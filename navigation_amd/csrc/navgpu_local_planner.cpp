@@ -266,7 +266,18 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
     if (rc != NAVGPU_OK) return rc;
     k = e;
   }
-  // --- dispatch: isPositionReached (latched_stop_rotate_controller.cpp:37-58)
+  // --- dispatch: isPositionReached (latched_stop_rotate_controller.cpp:37-58).  The stop / rotate candidates are collected here -
+  // robot indices rise with k - and checked in ONE navgpu_planner_check_trajectories call behind the loop
+  std::vector<uint32_t> chk_inst, chk_k, chk_off(1, 0u);
+  std::vector<float> chk_vs;
+  std::vector<double> chk_cmd;  // the candidate in fp64, as cmd_vel takes it
+  auto candidate = [&](uint32_t k, const float vs[3], double vx, double vy, double vth) {
+    chk_inst.push_back(first + k);
+    chk_k.push_back(k);
+    chk_off.push_back((uint32_t)chk_inst.size());
+    chk_vs.insert(chk_vs.end(), vs, vs + 3);
+    chk_cmd.insert(chk_cmd.end(), {vx, vy, vth});
+  };
   for (uint32_t k = 0; k < count; ++k) {
     if (!valid[k]) continue;
     navgpu_fleet::LocalPlannerState& st = f->lp[first + k];
@@ -299,7 +310,6 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
     }
     const double acc[3] = {lim.acc_lim_x, lim.acc_lim_y, lim.acc_lim_theta};
     float vs[3];
-    int32_t okc = 0;
     if (!st.rotating_to_goal && !stoppedOdom(in[k].odom_vel, lim.rot_stopped_vel, lim.trans_stopped_vel)) {
       // stopWithAccLimits (:111-146); Eigen::Vector3f narrows the samples to float
       const double vx = signOf(in[k].odom_vel[0]) * std::max(0.0, fabs(in[k].odom_vel[0]) - acc[0] * lim.sim_period);
@@ -308,15 +318,8 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
       vs[0] = (float)vx;
       vs[1] = (float)vy;
       vs[2] = (float)vth;
-      int rc = navgpu_planner_check_trajectory(f, first + k, vs, &okc);
-      if (rc != NAVGPU_OK) return rc;
       o.branch = NAVGPU_BRANCH_STOP;
-      if (okc) {
-        o.cmd_vel[0] = vx;
-        o.cmd_vel[1] = vy;
-        o.cmd_vel[2] = vth;
-        o.ok = 1;
-      }  // else: zeros, "Error when stopping." -> false
+      candidate(k, vs, vx, vy, vth);
     } else {
       // rotateToGoal (:148-209)
       st.rotating_to_goal = true;
@@ -332,13 +335,21 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
       vs[0] = 0.f;
       vs[1] = 0.f;
       vs[2] = (float)v;
-      int rc = navgpu_planner_check_trajectory(f, first + k, vs, &okc);
-      if (rc != NAVGPU_OK) return rc;
       o.branch = NAVGPU_BRANCH_ROTATE;
-      if (okc) {
-        o.cmd_vel[2] = v;
-        o.ok = 1;
-      }  // else: "Rotation cmd in collision" -> zeros, false
+      candidate(k, vs, 0.0, 0.0, v);
+    }
+  }
+  if (!chk_inst.empty()) {
+    std::vector<int32_t> okc(chk_inst.size(), 0);
+    int rc = navgpu_planner_check_trajectories(f, (uint32_t)chk_inst.size(), chk_inst.data(), chk_off.data(), chk_vs.data(), okc.data(), nullptr);
+    if (rc != NAVGPU_OK) return rc;
+    for (size_t q = 0; q < chk_inst.size(); ++q) {
+      if (!okc[q]) continue;  // zeros, false: "Error when stopping." / "Rotation cmd in collision"
+      navgpu_cmd_result& o = out[chk_k[q]];
+      o.cmd_vel[0] = chk_cmd[3 * q];
+      o.cmd_vel[1] = chk_cmd[3 * q + 1];
+      o.cmd_vel[2] = chk_cmd[3 * q + 2];
+      o.ok = 1;
     }
   }
   // --- dwaComputeVelocityCommands (:176-247) for the others, in contiguous runs

@@ -388,10 +388,14 @@ __device__ __forceinline__ void loadImage(const PlannerDev& pl, const ScoreRobot
 // CHUNK: cells of a footprint edge fetched per LDS round trip (see planner_score.h); AGG: the general MapGrid step
 // TERMS (k_score_terms*, the trajectory cloud's terms pass): the stage stores one SampleTerms record per slot to `terms` and
 // NOTHING else - no sample_cost / sample_status, no partial argmin, no counters (the cycle's own scoring launch has written those)
-template <bool EXPLICIT, int CHUNK, bool AGG, bool TERMS = false>
+// PROBES (k_check_traj*, with EXPLICIT: every probe is scored as checkTrajectory scores its sample): the robot has n_probes samples at
+// `explicit_sample`, three floats each; the lane of slot s reads probe s and stores scoreTrajectory's value to probe_cost[s] and NOTHING
+// else, as above - the cycle's result buffers stay the last cycle's
+template <bool EXPLICIT, int CHUNK, bool AGG, bool TERMS = false, bool PROBES = false>
 __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRobot& r, const double* s_fp, const float (*s_axis)[kMaxAxis],
                                              const uint8_t* s_dyn, double* s_rc, int* s_ri, int* s_cnt, const float* explicit_sample,
-                                             SampleTerms* terms = nullptr) {
+                                             SampleTerms* terms = nullptr, uint32_t n_probes = 0, double* probe_cost = nullptr) {
+  static_assert(!PROBES || (EXPLICIT && !TERMS), "probes are explicit samples");
   const uint32_t tid = threadIdx.x;
   const navgpu_dwa_config& c = pl.cfg;
   const Geom& g = r.g;
@@ -400,7 +404,7 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
   const uint32_t *dpath = r.dpath, *dgoal = r.dgoal, *dfront = r.dfront;
   const int32_t* cnt = r.cnt;
   const uint32_t inst = r.inst, nfp = r.nfp;
-  const int n_samples = EXPLICIT ? 1 : cnt[3];
+  const int n_samples = PROBES ? (int)n_probes : EXPLICIT ? 1 : cnt[3];
   const int win = r.win, wx0 = r.wx0, wy0 = r.wy0, win_bytes = r.win_bytes, nw = r.nw;
   const uint8_t* s_win = s_dyn;
   const bool walk_swap = pl.cfg.allow_unknown != 0;  // the window bytes are in walk order (buildScreens)
@@ -432,9 +436,10 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
   if (in_range) {
     float vs[3];
     if (EXPLICIT) {
-      vs[0] = explicit_sample[0];
-      vs[1] = explicit_sample[1];
-      vs[2] = explicit_sample[2];
+      const float* es = PROBES ? explicit_sample + 3 * (size_t)sidx : explicit_sample;
+      vs[0] = es[0];
+      vs[1] = es[1];
+      vs[2] = es[2];
     } else {
       const int nth = cnt[2], nyv = cnt[1];
       const int ix = sidx / (nyv * nth);
@@ -840,12 +845,14 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
     }
     if constexpr (TERMS) {
       terms[sidx] = rec;
+    } else if constexpr (PROBES) {
+      probe_cost[sidx] = total;
     } else if (!EXPLICIT && pl.sample_cost) {
       pl.sample_cost[(size_t)inst * pl.max_samples + sidx] = total;
       pl.sample_status[(size_t)inst * pl.max_samples + sidx] = status;
     }
   }
-  if constexpr (TERMS) return;
+  if constexpr (TERMS || PROBES) return;
 
   // ---- workgroup argmin (lowest index wins ties == first strict minimum of the sequential loop)
   const bool valid = in_range && status == NAVGPU_SAMPLE_SCORED && total >= 0.0;
@@ -980,6 +987,29 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_explicit(PlannerDev pl,
 __global__ __launch_bounds__(kScoreThreads) void k_score_explicit_agg(PlannerDev pl, uint32_t first, const float* explicit_sample) {
   scoreExplicit<true>(pl, first, explicit_sample);
 }
+// k_check_traj(_agg): checkTrajectory for the robots of a list, each with a run of probes (navgpu_planner_check_trajectories).
+// blockIdx.y = position in the list, blockIdx.x = block of kScoreThreads probes of that robot: the workgroup builds the robot's image as
+// scoreExplicit does, then scores one probe per lane.  A robot with fewer probes than the launch's widest has workgroups with
+// nothing to do: they leave before the first barrier.  The oscillation flags of a robot with probes are cleared here
+// (dwa_planner.cpp:217; no probe reads them: an explicit sample is scored against cleared flags).
+template <bool AGG>
+__device__ __forceinline__ void checkTraj(const PlannerDev& pl, const ProbeBatch& pb) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ int s_cnt[2];
+  const uint32_t p0 = pb.offsets[blockIdx.y], n = pb.offsets[blockIdx.y + 1] - p0;
+  if (blockIdx.x * kScoreThreads >= n) return;  // (the same for every lane of the workgroup)
+  ScoreRobot r = scoreRobot(pl, pb.instances[blockIdx.y]);
+  if (blockIdx.x == 0 && threadIdx.x == 0) pl.osc_flags[r.inst] = 0;
+  stageInputs<true>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
+  __syncthreads();
+  buildScreens(pl, r, s_dyn, reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes + score_bits_bytes(r.win)));
+  __syncthreads();
+  scoreSamples<true, 12, AGG, false, true>(pl, r, s_fp, s_axis, s_dyn, nullptr, nullptr, s_cnt, pb.vel + 3 * (size_t)p0, nullptr, n, pb.cost + p0);
+}
+__global__ __launch_bounds__(kScoreThreads) void k_check_traj(PlannerDev pl, ProbeBatch pb) { checkTraj<false>(pl, pb); }
+__global__ __launch_bounds__(kScoreThreads) void k_check_traj_agg(PlannerDev pl, ProbeBatch pb) { checkTraj<true>(pl, pb); }
 
 // k_score_terms / k_score_terms_agg (the trajectory cloud's terms pass, navgpu_planner_set_trajectory_cloud): the general stage with
 // TERMS set, for ONE robot whose records go to `terms` [max_samples].  The footprint chunk only groups LDS reads (the
@@ -1048,6 +1078,13 @@ uint32_t launch_score(const PlannerDev& pl_in, uint32_t first, uint32_t count, c
                                  : k_score_gen<16>;
   launchScore(gen, dim3(gen_blocks, count), kScoreThreads, win_bytes, s, pl, first, explicit_sample);
   return gen_blocks;
+}
+
+// The probes of n_robots listed robots in one launch; max_probes: the longest run of the list (> 0).  The image is built in the
+// workgroup, so the dynamic LDS is k_score_explicit's.
+void launch_check_traj(const PlannerDev& pl, const ProbeBatch& pb, uint32_t n_robots, uint32_t max_probes, hipStream_t s) {
+  const size_t lds = score_window_bytes(pl.win) + score_scratch_bytes((int)pl.win);
+  launchScore(pl.mg_generic ? k_check_traj_agg : k_check_traj, dim3((max_probes + kScoreThreads - 1) / kScoreThreads, n_robots), kScoreThreads, lds, s, pl, pb);
 }
 
 // The terms pass of one robot, behind the cycle's scoring launch: its image is rebuilt in its slot of pl.prep in the general

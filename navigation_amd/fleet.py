@@ -7,6 +7,7 @@ Method names follow the reference interfaces they front:
   set_plan              DWAPlanner::setPlan                  (dwa_local_planner/src/dwa_planner.cpp:204-207)
   find_best_path        DWAPlanner::updatePlanAndLocalCosts + findBestPath (dwa_planner.cpp:240-371)
   check_trajectory      DWAPlanner::checkTrajectory          (dwa_planner.cpp:213-237)
+  check_trajectories    a loop of checkTrajectory calls over robots and velocity probes, one launch
   footprint_cost        CostmapModel::footprintCost          (base_local_planner/src/costmap_model.cpp:50-142)
   rotate_recovery_step  RotateRecovery::runBehavior, one pass (rotate_recovery/src/rotate_recovery.cpp:105-153)
   carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
@@ -442,6 +443,29 @@ class Fleet:
         ok = C.c_int32()
         check(self.L.navgpu_planner_check_trajectory(self.h, instance, _ptr(v), C.byref(ok)), "check_trajectory")
         return bool(ok.value)
+
+    def check_trajectories(self, instances, probes, offsets=None):
+        """DWAPlanner::checkTrajectory for a list of robots (strictly increasing indices), each with a run of velocity probes,
+        in one launch.  probes: a list of (n_k, 3) arrays, one per robot, or - with offsets (len(instances) + 1, from 0) - one
+        flat (total, 3) array.  Returns (ok, costs): bool and float64 per probe, in probe order; costs as scoreTrajectory
+        returns them (the weighted sum, or the first failing critic's code)."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        if offsets is None:
+            runs = [np.asarray(p, np.float32).reshape(-1, 3) for p in probes]
+            off = np.zeros(len(runs) + 1, np.uint32)
+            off[1:] = np.cumsum([len(r) for r in runs])
+            vel = np.concatenate(runs) if runs else np.zeros((0, 3), np.float32)
+        else:
+            off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+            vel = np.asarray(probes, np.float32).reshape(-1, 3)
+        if len(off) != len(inst) + 1 or (len(off) and int(off[-1]) != len(vel)):
+            raise ValueError("check_trajectories: one run of probes per robot (offsets: len(instances) + 1 entries ending at the probe count)")
+        vel = np.ascontiguousarray(vel, np.float32)
+        ok = np.zeros(max(len(vel), 1), np.int32)
+        costs = np.zeros(max(len(vel), 1), np.float64)
+        check(self.L.navgpu_planner_check_trajectories(self.h, len(inst), _ptr(inst), _ptr(off), _ptr(vel), _ptr(ok), _ptr(costs)),
+              "check_trajectories")
+        return ok[:len(vel)].astype(bool), costs[:len(vel)].copy()
 
     def cost_cloud(self, instance):
         """MapGridVisualizer's cost cloud of one robot: (n, 7) float32 x, y, z, path, goal, occ, total."""
