@@ -672,7 +672,7 @@ int orc_tp_find_best_path(void* h, const float* pos, const float* vel, navgpu_tp
     for (int i = 0; i < 3; ++i) out->drive[i] = drive[i];
     out->n_points = (int)best.x.size();
     out->n_samples = (int)rec.size();
-    out->best_sample = -1;
+    out->best_sample = p->tp.best_call;
   }
   for (size_t i = 0; i < best.x.size() && (int)i < traj_cap; ++i) {
     traj_xyth[3 * i] = best.x[i];
@@ -682,6 +682,18 @@ int orc_tp_find_best_path(void* h, const float* pos, const float* vel, navgpu_tp
   for (size_t i = 0; i < rec.size() && (int)i < sample_cap; ++i)
     samples[i] = navgpu_tp_sample{rec[i].vx, rec[i].vy, rec[i].vth, rec[i].cost, rec[i].n_points, 0};
   return (int)rec.size();
+}
+// the last point of every generateTrajectory call of the last cycle (NaN without points); returns the number of calls
+int orc_tp_call_ends(void* h, double* xyth, int cap) {
+  const auto& rec = static_cast<TpHandle*>(h)->tp.records;
+  for (size_t i = 0; i < rec.size() && (int)i < cap; ++i)
+    for (int j = 0; j < 3; ++j) xyth[3 * i + j] = rec[i].end[j];
+  return (int)rec.size();
+}
+// path_map_'s within_robot marks as the last findBestPath left them, one byte per cell
+void orc_tp_get_within(void* h, uint8_t* out) {
+  const MapGridOracle& g = static_cast<TpHandle*>(h)->tp.path_map;
+  for (size_t i = 0; i < g.within_robot.size(); ++i) out[i] = g.within_robot[i] ? 1 : 0;
 }
 double orc_tp_score_trajectory(void* h, const double* pose, const double* vel, const double* vs) {
   return static_cast<TpHandle*>(h)->tp.scoreTrajectory(pose[0], pose[1], pose[2], vel[0], vel[1], vel[2], vs[0], vs[1], vs[2]);

@@ -155,6 +155,8 @@ def lib():
     sig("orc_tp_update_plan", None, vp, C.c_void_p, u, i)
     sig("orc_tp_find_best_path", i, vp, f32p, f32p, C.c_void_p, C.c_void_p, i, C.c_void_p, i)
     sig("orc_tp_score_trajectory", d, vp, f64p, f64p, f64p)
+    sig("orc_tp_call_ends", i, vp, f64p, i)
+    sig("orc_tp_get_within", None, vp, u8p)
     sig("orc_tp_generate", d, vp, f64p, f64p, f64p, f64p, d)
     sig("orc_tp_get_grid", None, vp, i, f64p)
     sig("orc_tp_get_state", None, vp, C.c_void_p)
@@ -533,6 +535,17 @@ class TrajectoryPlanner:
         n = self.L.orc_tp_find_best_path(self.h, _f32(pos), _f32(vel), C.addressof(res), traj.ctypes.data, traj_cap,
                                          C.addressof(samples), sample_cap)
         return res, traj[:res.n_points].copy(), [(s.vx, s.vy, s.vtheta, s.cost, s.n_points) for s in samples[:n]]
+
+    def call_ends(self, cap=4096):
+        """The last point of every generateTrajectory call of the last cycle, (n, 3); NaN rows for calls without points."""
+        out = np.zeros((cap, 3), np.float64)
+        return out[:self.L.orc_tp_call_ends(self.h, out, cap)].copy()
+
+    def within_robot(self):
+        """Indices (y * size_x + x) of the cells the last find_best_path marked within_robot."""
+        out = np.zeros(self.shape, np.uint8)
+        self.L.orc_tp_get_within(self.h, out)
+        return np.flatnonzero(out).astype(np.int32)
 
     def score_trajectory(self, pose, vel, vel_samples):
         return self.L.orc_tp_score_trajectory(self.h, _f64(pose), _f64(vel), _f64(vel_samples))

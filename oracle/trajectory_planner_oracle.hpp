@@ -5,9 +5,12 @@
 // updatePlan :474-500, checkTrajectory/scoreTrajectory :502-531, createTrajectories :537-906,
 // findBestPath :908-984), include/base_local_planner/trajectory_planner.h:332-374 (computeNew*),
 // src/footprint_helper.cpp:51-258 (getLineCells, getFillCells, getFootprintCells).
-// Pinned by base_local_planner/test/utest.cpp:75-102 (footprintObstacles: two generateTrajectory
-// known answers), test/footprint_helper_test.cpp (outline / fill cells) and the MapGrid fixtures; the
-// sequential selection logic of createTrajectories has no reference test — restated line by line.
+// Pinned by tests/golden/g16_tp_reference.npz: the reference's own TrajectoryPlanner, compiled in place by
+// tools/make_tp_goldens.py, run over the five sampling stages, both flag-update blocks, escape mode, heading scoring and the
+// degenerate sample counts; tests/test_tp_reference.py holds this oracle to it bit for bit (grids, within_robot cells, every
+// generateTrajectory call, winner and its call index, points, flags, state, scoreTrajectory / checkTrajectory).  Also by
+// base_local_planner/test/utest.cpp:75-102 (footprintObstacles), test/footprint_helper_test.cpp and the MapGrid fixtures.
+// On reading only: NO_INFORMATION cells (the reference reads allow_unknown from an uninitialised copy) and tpNormalizeAngle.
 // heading_scoring_ / simple_attractor_ (both default false) included: headingDiff :372-386 with the planner's own
 // lineCost / pointCost (:388-472; pointCost also fails on INSCRIBED cells, unlike CostmapModel's).
 #pragma once
@@ -120,6 +123,7 @@ inline double tpNormalizeAngle(double a) {  // angles::normalize_angle (fmod for
 struct TpSampleRecord {  // every generateTrajectory call of one createTrajectories, in call order
   double vx, vy, vth, cost;
   int n_points;
+  double end[3];  // the last point (NaN without points)
 };
 
 struct TrajectoryPlannerOracle {
@@ -137,6 +141,7 @@ struct TrajectoryPlannerOracle {
   double prev_x = 0, prev_y = 0, escape_x = 0, escape_y = 0, escape_theta = 0;
   Trajectory traj_one, traj_two;
   std::vector<TpSampleRecord> records;
+  int best_call = -1;  // index into records of the call that produced the returned trajectory
 
   void bind(const Grid2D* costmap, const TpConfig& cfg, const std::vector<Pt2>& fp) {
     cm = costmap;
@@ -309,6 +314,7 @@ struct TrajectoryPlannerOracle {
   Trajectory createTrajectories(double x, double y, double theta, double vx, double vy, double vtheta, double acc_x, double acc_y,
                                 double acc_theta) {  // :537-906
     records.clear();
+    best_call = -1;
     double max_vel_x = c.max_vel_x, max_vel_theta, min_vel_x, min_vel_theta;
     if (final_goal_position_valid) {
       double final_goal_dist = hypot(final_goal_x - x, final_goal_y - y);
@@ -335,10 +341,16 @@ struct TrajectoryPlannerOracle {
     double impossible_cost = path_map.obstacleCosts();
     auto gen = [&](double a, double b, double w) {
       generateTrajectory(x, y, theta, vx, vy, vtheta, a, b, w, acc_x, acc_y, acc_theta, impossible_cost, *comp_traj);
-      records.push_back(TpSampleRecord{a, b, w, comp_traj->cost, (int)comp_traj->x.size()});
+      TpSampleRecord r = {a, b, w, comp_traj->cost, (int)comp_traj->x.size(), {NAN, NAN, NAN}};
+      if (r.n_points) r.end[0] = comp_traj->x.back(), r.end[1] = comp_traj->y.back(), r.end[2] = comp_traj->th.back();
+      records.push_back(r);
+    };
+    auto take = [&]() {  // the reference's three-line swap; the call just made becomes the best
+      std::swap(best_traj, comp_traj);
+      best_call = (int)records.size() - 1;
     };
     auto takeIfBetter = [&]() {
-      if (comp_traj->cost >= 0 && (comp_traj->cost < best_traj->cost || best_traj->cost < 0)) std::swap(best_traj, comp_traj);
+      if (comp_traj->cost >= 0 && (comp_traj->cost < best_traj->cost || best_traj->cost < 0)) take();
     };
     if (!escaping) {
       for (int i = 0; i < c.vx_samples; ++i) {
@@ -388,10 +400,10 @@ struct TrajectoryPlannerOracle {
         if (aheadDist(ahead_gdist)) {
           if (ahead_gdist < heading_dist) {
             if (vtheta_samp < 0 && !stuck_left) {
-              std::swap(best_traj, comp_traj);
+              take();
               heading_dist = ahead_gdist;
             } else if (vtheta_samp > 0 && !stuck_right) {
-              std::swap(best_traj, comp_traj);
+              take();
               heading_dist = ahead_gdist;
             }
           }
@@ -433,10 +445,10 @@ struct TrajectoryPlannerOracle {
           if (aheadDist(ahead_gdist)) {
             if (ahead_gdist < heading_dist) {
               if (vy_samp > 0 && !stuck_left_strafe) {
-                std::swap(best_traj, comp_traj);
+                take();
                 heading_dist = ahead_gdist;
               } else if (vy_samp < 0 && !stuck_right_strafe) {
-                std::swap(best_traj, comp_traj);
+                take();
                 heading_dist = ahead_gdist;
               }
             }
@@ -471,7 +483,7 @@ struct TrajectoryPlannerOracle {
     vx_samp = c.backup_vel;
     vy_samp = 0.0;
     gen(vx_samp, vy_samp, vtheta_samp);
-    std::swap(best_traj, comp_traj);
+    take();
     resetOscillationIfMoved(x, y);
     if (!escaping && best_traj->cost > -2.0) {
       escape_x = x;
