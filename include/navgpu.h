@@ -494,7 +494,8 @@ typedef enum {
   NAVGPU_BRANCH_DWA = 1,      /* dwaComputeVelocityCommands                                                 */
   NAVGPU_BRANCH_STOP = 2,     /* stop-rotate: stopWithAccLimits                                             */
   NAVGPU_BRANCH_ROTATE = 3,   /* stop-rotate: rotateToGoal                                                  */
-  NAVGPU_BRANCH_AT_GOAL = 4   /* stop-rotate: goal orientation reached, zero command                        */
+  NAVGPU_BRANCH_AT_GOAL = 4,  /* stop-rotate: goal orientation reached, zero command                        */
+  NAVGPU_BRANCH_ROLLOUT = 5   /* TrajectoryPlannerROS: tc_->findBestPath's drive velocities (navgpu_tp_ros_*) */
 } navgpu_branch;
 
 typedef struct {
@@ -676,6 +677,87 @@ int navgpu_tp_score_trajectory(navgpu_fleet* fleet, uint32_t instance, const dou
                                const double vel_samples[3], double* cost);
 int navgpu_tp_get_state(navgpu_fleet* fleet, uint32_t first, uint32_t count, navgpu_tp_state* states);
 int navgpu_tp_set_state(navgpu_fleet* fleet, uint32_t first, uint32_t count, const navgpu_tp_state* states);
+/* replaces: TrajectoryPlanner::updatePlan(new_plan, compute_dists) (trajectory_planner.cpp:474-500) for robots [first, first+count):
+ * plan k = plans_xy[offsets[k] .. offsets[k+1]) as {x, y} pairs in the costmap's global frame (offsets never decrease).  Per robot the
+ * effects of navgpu_tp_update_plan; with compute_dists the plans of the range go up together, ONE wavefront launch covers the range and
+ * the call waits once.  A plan longer than max_plan: NAVGPU_ERR_CAPACITY, nothing changed for any robot. */
+int navgpu_tp_update_plans(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* plans_xy,
+                           const uint32_t* offsets /* count + 1 */, int32_t compute_dists);
+/* replaces: a loop of TrajectoryPlanner::scoreTrajectory / checkTrajectory calls (trajectory_planner.cpp:502-531) over robots and
+ * probes, against the robots' current grids.  The conventions of navgpu_planner_check_trajectories: instances = n_robots strictly
+ * increasing robot indices, robot k owns the probes probe_offsets[k] .. probe_offsets[k + 1] (probe_offsets[0] = 0, never decreasing), a
+ * robot without probes is left alone; an empty list (n_robots = 0) is no work and no error.  A probe is 9 doubles: pose x, y, theta,
+ * velocity x, y, theta, sample x, y, theta.  costs[p] is scoreTrajectory's value (>= 0, -1 off the map or in collision, -2 no path to
+ * the goal), ok[p] = costs[p] >= 0 is checkTrajectory's (ok may be NULL).  One upload, one launch (k_tp_probe: a wave per probe, a lane
+ * per step; bit-equal to the single call) and one read-back for the whole list, ordered on the fleet's stream.  The probes go through
+ * buffers of their own, grown on demand and kept: navgpu_tp_samples / _trajectory and the results of the last navgpu_tp_find_best_path
+ * still describe that cycle (the single call, navgpu_tp_score_trajectory, borrows the robot's sample slot 0 and start state).
+ * NAVGPU_ERR_INVALID: a null or malformed list (not increasing, out of range, decreasing offsets) or a probe value that is not finite;
+ * NAVGPU_ERR_STATE, nothing launched: before navgpu_tp_configure, or simple_attractor with an empty plan on a listed robot that has
+ * probes. */
+int navgpu_tp_score_trajectories(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances,
+                                 const uint32_t* probe_offsets /* n_robots + 1 */, const double* probes /* 9 per probe */,
+                                 double* costs /* per probe */, int32_t* ok /* per probe, may be NULL */);
+
+/* ---- TrajectoryPlannerROS control cycle for a fleet (base_local_planner/src/trajectory_planner_ros.cpp:283-597) ----
+ * Host-side mirror, free of ROS types, of TrajectoryPlannerROS::setPlan / computeVelocityCommands / stopWithAccLimits / rotateToGoal /
+ * checkTrajectory / scoreTrajectory / isGoalReached round the navgpu_tp_* core, as navgpu_local_planner_* mirrors DWAPlannerROS: poses are
+ * (x, y, yaw) triples, the tf lookup is an optional planar plan -> global transform, transformGlobalPlan + prunePlan are
+ * navgpu_local_plan_window (the goal_functions.cpp code TrajectoryPlannerROS calls at :386-393).  The class needs tf and ROS and cannot be
+ * compiled against the reference tree here: parity of these entry points is unpinned in the sense of the DWAPlannerROS mirror above.
+ * Acceleration limits, max_vel_th, min_vel_th, min_in_place_vel_th and sim_period are those of navgpu_tp_config. */
+typedef struct {
+  double xy_goal_tolerance, yaw_goal_tolerance;         /* 0.10, 0.05 (trajectory_planner_ros.cpp:118-119)   */
+  double rot_stopped_velocity, trans_stopped_velocity;  /* 1e-2, 1e-2 (:97-98)                               */
+  int32_t latch_xy_goal_tolerance;                      /* 0 (:126)                                          */
+  int32_t prune_plan;                                   /* 1 (:116)                                          */
+} navgpu_tp_ros_params;
+/* replaces: the parameter reads of TrajectoryPlannerROS::initialize / reconfigureCB that belong to the ROS class itself.
+ * NAVGPU_ERR_STATE before navgpu_tp_configure. */
+int navgpu_tp_ros_configure(navgpu_fleet* fleet, const navgpu_tp_ros_params* params);
+/* replaces: TrajectoryPlannerROS::setPlan (:355-370) for robots [first, first+count): plan k is poses_xyyaw[offsets[k] .. offsets[k+1])
+ * as (x, y, yaw) triples in its own frame, plan_to_global = count x (x, y, yaw) or NULL.  Clears xy_tolerance_latch_ and reached_goal_;
+ * rotating_to_goal_ stays as it is (the reference does not reset it there). */
+int navgpu_tp_ros_set_plans(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* poses_xyyaw, const uint32_t* offsets,
+                            const double* plan_to_global);
+/* replaces: TrajectoryPlannerROS::computeVelocityCommands (:372-526) for robots [first, first+count), line by line:
+ * 1. the window per robot (navgpu_local_plan_window, dist_threshold = max(size_x, size_y) * resolution / 2; the stored plan is erased in
+ *    lockstep when prune_plan is set).  No pose, a zero-length plan or an empty window: ok 0, NAVGPU_BRANCH_NONE.  A window longer than
+ *    max_plan: NAVGPU_ERR_CAPACITY for the call, as in navgpu_local_planner_compute_velocity_commands.
+ * 2. the goal is the LAST POSE OF THE TRANSFORMED WINDOW (:411-419), not the end of the global plan.  Position reached:
+ *    xy_tolerance_latch_ || distance <= xy_goal_tolerance; the latch is set only with latch_xy_goal_tolerance.
+ * 3. reached and |shortest_angular_distance(yaw, goal_th)| <= yaw_goal_tolerance: zero command, rotating_to_goal_ and the latch cleared,
+ *    reached_goal_ set, ok 1, NAVGPU_BRANCH_AT_GOAL; no updatePlan / findBestPath for this robot.
+ * 4. every other robot with a window: updatePlan(transformed_plan) + findBestPath - also the robots whose position is reached (:443-444:
+ *    the reference refreshes the grids and advances the planner's oscillation / escape state there and discards the result).  One
+ *    navgpu_tp_update_plans + navgpu_tp_find_best_path per CONTIGUOUS RUN of such robots: robots of step 3 split the runs (the limitation
+ *    the DWA cycle has for robots without a local plan).
+ * 5. position reached: stopWithAccLimits' candidate while !rotating_to_goal_ && !stopped(odom) (NAVGPU_BRANCH_STOP), else
+ *    rotating_to_goal_ = true and rotateToGoal's (NAVGPU_BRANCH_ROTATE).  All candidates are checked in ONE navgpu_tp_score_trajectories
+ *    call behind step 4, so they see this cycle's grids, within_robot included.  Invalid: zero command, ok 0.
+ * 6. the others: NAVGPU_BRANCH_ROLLOUT, cmd_vel = drive velocities, ok = cost >= 0, trajectory_points = the winner's length (0 when
+ *    the cost is negative); the points stay readable through navgpu_tp_trajectory.
+ * local_plan_points = the window's length. */
+int navgpu_tp_ros_compute_velocity_commands(navgpu_fleet* fleet, uint32_t first, uint32_t count, const navgpu_robot_input* in,
+                                            navgpu_cmd_result* out);
+/* replaces: TrajectoryPlannerROS::isGoalReached (:590-597): reached_goal_, the flag the last cycle set */
+int navgpu_tp_ros_is_goal_reached(navgpu_fleet* fleet, uint32_t first, uint32_t count, int32_t* reached);
+/* replaces: a loop of TrajectoryPlannerROS::checkTrajectory / scoreTrajectory(vx, vy, vtheta, update_map) calls (:528-588) over robots
+ * (instances strictly increasing, in[k] the input of robot instances[k]) and velocity samples (3 doubles per probe, probe_offsets as in
+ * navgpu_tp_score_trajectories).  With update_map the listed robots first get updatePlan({pose}, true) - the planner's plan and final
+ * goal become the robot's pose, as in the reference - in runs of navgpu_tp_update_plans; then one navgpu_tp_score_trajectories call with
+ * pose and vel = odom_vel.  A robot without a pose: cost -1.0, ok 0, neither updated nor probed.  ok may be NULL. */
+int navgpu_tp_ros_check_trajectories(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_input* in,
+                                     const uint32_t* probe_offsets, const double* vel_samples, int32_t update_map, double* costs,
+                                     int32_t* ok);
+/* global_plan_ of one instance after pruning; returns its length (poses) or < 0 */
+int navgpu_tp_ros_get_plan(navgpu_fleet* fleet, uint32_t instance, double* xyyaw, uint32_t capacity);
+/* replaces: publishPlan(transformed_plan, g_plan_pub_) (:468, :499, :523): the window of the instance's last cycle; its length or < 0 */
+int navgpu_tp_ros_transformed_plan(navgpu_fleet* fleet, uint32_t instance, double* xyyaw, uint32_t capacity);
+/* Pure host function, needs no fleet: the velocity candidate of stopWithAccLimits (:283-290, rotate = 0; pose and goal_th unused) or of
+ * rotateToGoal (:312-337, rotate = 1) as vel_samples_out = {vx, vy, vth}.  NAVGPU_ERR_INVALID for a NULL argument. */
+int navgpu_tp_ros_candidate(const navgpu_tp_config* config, int32_t rotate, const double pose[3], const double odom_vel[3],
+                            double goal_th, double vel_samples_out[3]);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Footprint-cost queries, rotate_recovery::RotateRecovery, carrot_planner::CarrotPlanner       */

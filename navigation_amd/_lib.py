@@ -145,7 +145,7 @@ class CmdResult(C.Structure):
                 ("trajectory_points", C.c_int32)]
 
 
-BRANCH_NONE, BRANCH_DWA, BRANCH_STOP, BRANCH_ROTATE, BRANCH_AT_GOAL = range(5)
+BRANCH_NONE, BRANCH_DWA, BRANCH_STOP, BRANCH_ROTATE, BRANCH_AT_GOAL, BRANCH_ROLLOUT = range(6)
 
 
 class LocalWindow(C.Structure):
@@ -217,6 +217,17 @@ class TpConfig(C.Structure):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("y_vels", "n_y_vels")}
         d["y_vels"] = tuple(self.y_vels[i] for i in range(self.n_y_vels))
         return d
+
+
+class TpRosParams(C.Structure):
+    """navgpu_tp_ros_params; defaults are TrajectoryPlannerROS's own (trajectory_planner_ros.cpp:97-98, 116-126)."""
+    _fields_ = [("xy_goal_tolerance", C.c_double), ("yaw_goal_tolerance", C.c_double), ("rot_stopped_velocity", C.c_double),
+                ("trans_stopped_velocity", C.c_double), ("latch_xy_goal_tolerance", C.c_int32), ("prune_plan", C.c_int32)]
+
+    def __init__(self, xy_goal_tolerance=0.10, yaw_goal_tolerance=0.05, rot_stopped_velocity=1e-2, trans_stopped_velocity=1e-2,
+                 latch_xy_goal_tolerance=0, prune_plan=1):
+        super().__init__(xy_goal_tolerance, yaw_goal_tolerance, rot_stopped_velocity, trans_stopped_velocity, int(latch_xy_goal_tolerance),
+                         int(prune_plan))
 
 
 class TpState(C.Structure):
@@ -486,6 +497,16 @@ SYMBOLS = [
     ("navgpu_tp_score_trajectory", C.c_int, [vp, u32, vp, vp, vp, C.POINTER(dbl)]),
     ("navgpu_tp_get_state", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_tp_set_state", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_tp_update_plans", C.c_int, [vp, u32, u32, vp, vp, i32]),
+    ("navgpu_tp_score_trajectories", C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
+    ("navgpu_tp_ros_configure", C.c_int, [vp, C.POINTER(TpRosParams)]),
+    ("navgpu_tp_ros_set_plans", C.c_int, [vp, u32, u32, vp, vp, vp]),
+    ("navgpu_tp_ros_compute_velocity_commands", C.c_int, [vp, u32, u32, vp, vp]),
+    ("navgpu_tp_ros_is_goal_reached", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_tp_ros_check_trajectories", C.c_int, [vp, u32, vp, vp, vp, vp, i32, vp, vp]),
+    ("navgpu_tp_ros_get_plan", C.c_int, [vp, u32, vp, u32]),
+    ("navgpu_tp_ros_transformed_plan", C.c_int, [vp, u32, vp, u32]),
+    ("navgpu_tp_ros_candidate", C.c_int, [C.POINTER(TpConfig), i32, vp, vp, dbl, vp]),
     ("navgpu_footprint_cost", C.c_int, [vp, u32, u32, vp, vp, i32, vp, vp]),
     ("navgpu_rotate_recovery_configure", C.c_int, [vp, C.POINTER(RotateRecoveryParams)]),
     ("navgpu_rotate_recovery_step", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),

@@ -233,6 +233,16 @@ struct TpDev {
 };
 void launch_tp_within(const PlannerDev& pl, const TpDev& tp, uint32_t first, uint32_t count, hipStream_t s);
 void launch_tp_rollout(const PlannerDev& pl, const TpDev& tp, uint32_t first, uint32_t count, int store_points, hipStream_t s);
+// batched scoreTrajectory (navgpu_tp_score_trajectories, tp_probe_kernels.hip): per-launch view of the fleet's probe buffers
+struct TpProbeBatch {
+  const double* probes;      // [n_probes][9] pose x y theta, velocity x y theta, sample x y theta
+  const uint32_t* instance;  // [n_probes] the robot a probe belongs to
+  double* cost;              // [n_probes] what scoreTrajectory returns
+  uint32_t n_probes;
+};
+// Weak for the reason launch_check_traj is: navgpu_tp.cpp is also linked against a stand-in for the kernels that knows the launchers
+// of its day (tests/tsan); there navgpu_tp_score_trajectories answers NAVGPU_ERR_STATE.  libnavgpu.so always carries the launcher.
+__attribute__((weak)) void launch_tp_probe(const PlannerDev& pl, const TpDev& tp, const TpProbeBatch& pb, hipStream_t s);
 
 // batched CostmapModel::footprintCost queries (footprint_kernels.hip): runs of poses per robot of a launch, packed
 struct FootprintDev {

@@ -1,6 +1,6 @@
 // Internal to libnavgpu.so: the fleet object behind the opaque navgpu_fleet handle and the helpers the host
 // translation units share (navgpu_host.cpp: lifetime / costmap layers / DWA planner / measurement,
-// navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner,
+// navgpu_local_planner.cpp: DWAPlannerROS control cycle, navgpu_tp.cpp: legacy TrajectoryPlanner, navgpu_tp_ros.cpp: its ROS class,
 // navgpu_recovery.cpp: footprint-cost queries, RotateRecovery, CarrotPlanner, navgpu_voxel_export.cpp: voxel-layer debug
 // outputs, navgpu_traj_cloud.cpp: DWAPlanner's trajectory cloud, navgpu_obs_buffer.cpp: ObservationBuffer on the device).
 #pragma once
@@ -183,6 +183,26 @@ struct navgpu_fleet {
   std::vector<TpOut> tp_h_out;
   std::vector<uint32_t> tp_h_nsamples, tp_h_within, tp_h_within_count;
   std::vector<int32_t> tp_h_winner;
+  // batched scoreTrajectory (navgpu_tp_score_trajectories): what a call hands over - the probes, then the robot of each - as one pinned
+  // block and its device twin, and the costs coming back; grown on demand (all four or none) and kept.  Its own buffers: the sample
+  // slots, start states and results of the last navgpu_tp_find_best_path stay as that cycle left them.
+  struct TpProbes {
+    static constexpr size_t kBytesPerProbe = 9 * sizeof(double) + sizeof(uint32_t);
+    uint32_t cap = 0;             // probes the buffers hold
+    uint8_t *d_in = nullptr, *h_in = nullptr;     // [cap][9] doubles, [cap] robot indices
+    double *d_cost = nullptr, *h_cost = nullptr;  // [cap]
+  } tpb;
+  // TrajectoryPlannerROS mirror (navgpu_tp_ros.cpp): per-instance controller state, host only
+  struct TpRosState {
+    std::vector<double> plan;      // global_plan_: (x, y, yaw) triples in the plan's frame (prunePlan shrinks it)
+    double T[3] = {0, 0, 0};       // planar plan -> global transform
+    bool has_T = false, have_plan = false;
+    bool xy_tolerance_latch = false, rotating_to_goal = false, reached_goal = false;  // TrajectoryPlannerROS members
+    std::vector<double> transformed;  // transformed_plan of the last cycle (what g_plan_pub_ publishes)
+  };
+  std::vector<TpRosState> tpr;
+  navgpu_tp_ros_params tpr_params{};
+  bool tpr_configured = false;
   // footprint-cost queries, rotate recovery, carrot planner (navgpu_recovery.cpp): query staging, grown on demand
   struct FootprintQueries {
     uint32_t cap = 0;             // queries the buffers hold

@@ -570,6 +570,101 @@ int navgpu_tp_score_trajectory(navgpu_fleet* f, uint32_t instance, const double 
   return checkLaunch();
 }
 
+int navgpu_tp_update_plans(navgpu_fleet* f, uint32_t first, uint32_t count, const double* plans_xy, const uint32_t* offsets, int32_t compute_dists) {
+  if (!f || !offsets || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  for (uint32_t k = 0; k < count; ++k)
+    if (offsets[k + 1] < offsets[k]) return NAVGPU_ERR_INVALID;
+  if (offsets[count] > offsets[0] && !plans_xy) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->tp_configured) return NAVGPU_ERR_STATE;
+  for (uint32_t k = 0; k < count; ++k)  // before anything changes for any robot
+    if (offsets[k + 1] - offsets[k] > f->pl.max_plan) return NAVGPU_ERR_CAPACITY;
+  for (uint32_t k = 0; k < count; ++k) {
+    navgpu_fleet::TpHost& h = f->tph[first + k];
+    const uint32_t n = offsets[k + 1] - offsets[k];
+    const double* p = n ? plans_xy + 2 * (size_t)offsets[k] : nullptr;
+    h.plan.assign(p, p + 2 * (size_t)n);
+    if (n) {  // :480-487
+      h.final_goal_x = p[2 * (size_t)(n - 1)];
+      h.final_goal_y = p[2 * (size_t)(n - 1) + 1];
+      h.final_goal_position_valid = true;
+    } else {
+      h.final_goal_position_valid = false;
+    }
+  }
+  if (!compute_dists) return NAVGPU_OK;
+  // :489-499 for the whole range: the plans and their lengths go up together, one wavefront launch covers the range, one wait
+  int rc = tpUploadPlans(f, first, count);
+  if (rc) return rc;
+  rc = tpLaunchGrids(f, first, count, false);
+  if (rc) return rc;
+  HIP_TRY(waitStream(f->stream));
+  return checkLaunch();
+}
+
+int navgpu_tp_score_trajectories(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const uint32_t* probe_offsets,
+                                 const double* probes, double* costs, int32_t* ok) {
+  if (!f || !probe_offsets || (n_robots && !instances) || n_robots > f->desc.n_instances || probe_offsets[0] != 0) return NAVGPU_ERR_INVALID;
+  for (uint32_t k = 0; k < n_robots; ++k)
+    if (instances[k] >= f->desc.n_instances || (k && instances[k] <= instances[k - 1]) || probe_offsets[k + 1] < probe_offsets[k])
+      return NAVGPU_ERR_INVALID;
+  const uint32_t total = probe_offsets[n_robots];
+  if (total && (!probes || !costs)) return NAVGPU_ERR_INVALID;
+  for (size_t v = 0; v < 9 * (size_t)total; ++v)
+    if (!std::isfinite(probes[v])) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->tp_configured || !launch_tp_probe) return NAVGPU_ERR_STATE;
+  TpDev& tp = f->tp;
+  if (tp.cfg.simple_attractor)  // the reference indexes global_plan_[size() - 1] (:311-314)
+    for (uint32_t k = 0; k < n_robots; ++k)
+      if (probe_offsets[k + 1] > probe_offsets[k] && f->tph[instances[k]].plan.empty()) {
+        g_last_error = "navgpu_tp_score_trajectories: simple_attractor needs a plan";
+        return NAVGPU_ERR_STATE;
+      }
+  if (!total) return NAVGPU_OK;  // nobody has a probe: nothing is launched
+  navgpu_fleet::TpProbes& pb = f->tpb;
+  if (total > pb.cap) {  // all four buffers or none; the ones they replace are idle (every call drains the stream)
+    navgpu_fleet::TpProbes nb;
+    nb.cap = (total + 255u) & ~255u;
+    const size_t bytes = (size_t)nb.cap * navgpu_fleet::TpProbes::kBytesPerProbe;
+    int rc = f->alloc(&nb.d_in, bytes);
+    if (!rc) rc = f->alloc(&nb.d_cost, nb.cap);
+    if (!rc) rc = f->allocPinned(&nb.h_in, bytes);
+    if (!rc) rc = f->allocPinned(&nb.h_cost, nb.cap);
+    if (rc) {
+      f->release(nb.d_in);
+      f->release(nb.d_cost);
+      f->releasePinned(nb.h_in);
+      f->releasePinned(nb.h_cost);
+      return rc;
+    }
+    f->release(pb.d_in);
+    f->release(pb.d_cost);
+    f->releasePinned(pb.h_in);
+    f->releasePinned(pb.h_cost);
+    pb = nb;
+  }
+  // one block: the probes, then the robot of each (the kernel gives a probe a workgroup of its own and needs no search for its robot)
+  memcpy(pb.h_in, probes, sizeof(double) * 9 * (size_t)total);
+  uint32_t* h_inst = reinterpret_cast<uint32_t*>(pb.h_in + sizeof(double) * 9 * (size_t)total);
+  for (uint32_t k = 0; k < n_robots; ++k)
+    for (uint32_t p = probe_offsets[k]; p < probe_offsets[k + 1]; ++p) h_inst[p] = instances[k];
+  const size_t used = (size_t)total * navgpu_fleet::TpProbes::kBytesPerProbe;
+  HIP_TRY(hipMemcpyAsync(pb.d_in, pb.h_in, used, hipMemcpyHostToDevice, f->stream));
+  const TpProbeBatch batch{reinterpret_cast<const double*>(pb.d_in), reinterpret_cast<const uint32_t*>(pb.d_in + sizeof(double) * 9 * (size_t)total),
+                           pb.d_cost, total};
+  PROFILED(f, NAVGPU_K_SCORE, launch_tp_probe(f->pl, tp, batch, f->stream));
+  HIP_TRY(hipMemcpyAsync(pb.h_cost, pb.d_cost, sizeof(double) * total, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(waitStream(f->stream));
+  int rc = checkLaunch();
+  if (rc) return rc;
+  for (uint32_t p = 0; p < total; ++p) {
+    costs[p] = pb.h_cost[p];
+    if (ok) ok[p] = pb.h_cost[p] >= 0 ? 1 : 0;  // checkTrajectory (:502-516): cost >= 0
+  }
+  return NAVGPU_OK;
+}
+
 int navgpu_tp_get_state(navgpu_fleet* f, uint32_t first, uint32_t count, navgpu_tp_state* states) {
   if (!f || !states || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);

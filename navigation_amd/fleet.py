@@ -15,6 +15,10 @@ Method names follow the reference interfaces they front:
   voxel_clearing_endpoints  VoxelLayer::raytraceFreespace's clearing_endpoints cloud (plugins/voxel_layer.cpp:286-381)
   obs_buffer / obs_stage  ObservationBuffer::bufferCloud / getObservations behind ObstacleLayer's sensor callbacks
                         (costmap_2d/src/observation_buffer.cpp:111-251, plugins/obstacle_layer.cpp:252-338, 466-496)
+  tp_update_plans / tp_score_trajectories  TrajectoryPlanner::updatePlan / scoreTrajectory for a range / a list of robots
+                        (base_local_planner/src/trajectory_planner.cpp:474-531)
+  tp_ros_*              TrajectoryPlannerROS::setPlan / computeVelocityCommands / checkTrajectory / isGoalReached for a fleet
+                        (base_local_planner/src/trajectory_planner_ros.cpp:283-597)
   trajectory_cloud      DWAPlanner::findBestPath's trajectory_cloud (dwa_planner.cpp:318-348); sample_terms: the breakdown behind it
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
@@ -683,6 +687,98 @@ class Fleet:
     def tp_set_state(self, states, first=0):
         arr = (N.TpState * len(states))(*states)
         check(self.L.navgpu_tp_set_state(self.h, first, len(states), arr), "tp_set_state")
+
+    def tp_update_plans(self, plans_xy, compute_dists=False, first=0):
+        """TrajectoryPlanner::updatePlan for robots first .. first + len(plans_xy) - 1: one upload, one wavefront launch, one wait."""
+        plans = [np.ascontiguousarray(p, np.float64).reshape(-1, 2) for p in plans_xy]
+        offsets = np.zeros(len(plans) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(p) for p in plans])
+        xy = np.ascontiguousarray(np.concatenate(plans) if plans else np.zeros((0, 2)))
+        check(self.L.navgpu_tp_update_plans(self.h, first, len(plans), _ptr(xy) if len(xy) else None, _ptr(offsets), int(compute_dists)),
+              "tp_update_plans")
+
+    @staticmethod
+    def _probe_runs(instances, probes, offsets, width):
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        if offsets is None:
+            runs = [np.asarray(p, np.float64).reshape(-1, width) for p in probes]
+            off = np.zeros(len(runs) + 1, np.uint32)
+            off[1:] = np.cumsum([len(r) for r in runs])
+            flat = np.concatenate(runs) if runs else np.zeros((0, width))
+        else:
+            off = np.ascontiguousarray(offsets, np.uint32).reshape(-1)
+            flat = np.asarray(probes, np.float64).reshape(-1, width)
+        if len(off) != len(inst) + 1 or int(off[-1]) != len(flat):
+            raise ValueError("one run of probes per robot (offsets: len(instances) + 1 entries ending at the probe count)")
+        return inst, off, np.ascontiguousarray(flat, np.float64)
+
+    def tp_score_trajectories(self, instances, probes, offsets=None):
+        """TrajectoryPlanner::scoreTrajectory / checkTrajectory for a list of robots (strictly increasing indices), each with a run of
+        probes of 9 doubles (pose x y theta, velocity x y theta, sample x y theta), in one launch.  probes: a list of (n_k, 9) arrays,
+        one per robot, or - with offsets - one flat (total, 9) array.  Returns (costs, ok) per probe, in probe order."""
+        inst, off, flat = self._probe_runs(instances, probes, offsets, 9)
+        costs = np.zeros(max(len(flat), 1), np.float64)
+        ok = np.zeros(max(len(flat), 1), np.int32)
+        check(self.L.navgpu_tp_score_trajectories(self.h, len(inst), _ptr(inst), _ptr(off), _ptr(flat), _ptr(costs), _ptr(ok)),
+              "tp_score_trajectories")
+        return costs[:len(flat)].copy(), ok[:len(flat)].astype(bool)
+
+    # ---------------------------------------------------------------- TrajectoryPlannerROS control cycle
+    def configure_tp_ros(self, params=None, **kw):
+        """TrajectoryPlannerROS's own parameters (navgpu_tp_ros_params); the planner's come from configure_trajectory_planner."""
+        p = params if params is not None else N.TpRosParams(**kw)
+        check(self.L.navgpu_tp_ros_configure(self.h, C.byref(p)), "tp_ros_configure")
+
+    def tp_ros_set_plans(self, plans_xyyaw, plans_to_global=None, first=0):
+        """TrajectoryPlannerROS::setPlan for robots first .. first + len(plans) - 1."""
+        plans = [np.ascontiguousarray(p, np.float64).reshape(-1, 3) for p in plans_xyyaw]
+        offsets = np.zeros(len(plans) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(p) for p in plans])
+        poses = np.ascontiguousarray(np.concatenate(plans) if plans else np.zeros((0, 3)))
+        T = None if plans_to_global is None else np.ascontiguousarray(plans_to_global, np.float64).reshape(len(plans), 3)
+        check(self.L.navgpu_tp_ros_set_plans(self.h, first, len(plans), _ptr(poses) if len(poses) else None, _ptr(offsets),
+                                             None if T is None else _ptr(T)), "tp_ros_set_plans")
+
+    def tp_ros_compute_velocity_commands(self, poses, odom_vels, first=0, have_pose=None):
+        """TrajectoryPlannerROS::computeVelocityCommands for len(poses) robots -> list of CmdResult."""
+        arr = self._robot_inputs(poses, odom_vels, have_pose)
+        out = (N.CmdResult * len(arr))()
+        check(self.L.navgpu_tp_ros_compute_velocity_commands(self.h, first, len(arr), arr, out), "tp_ros_compute_velocity_commands")
+        return list(out)
+
+    def tp_ros_is_goal_reached(self, first=0, count=None):
+        first, count = self._range(first, count)
+        out = (C.c_int32 * count)()
+        check(self.L.navgpu_tp_ros_is_goal_reached(self.h, first, count, out), "tp_ros_is_goal_reached")
+        return [bool(v) for v in out]
+
+    def tp_ros_check_trajectories(self, instances, poses, odom_vels, vel_samples, update_map=False, have_pose=None, offsets=None):
+        """TrajectoryPlannerROS::scoreTrajectory / checkTrajectory(vx, vy, vtheta, update_map) for a list of robots: poses / odom_vels /
+        have_pose per listed robot, vel_samples a list of (n_k, 3) arrays (or flat with offsets).  Returns (costs, ok) per probe."""
+        inst, off, flat = self._probe_runs(instances, vel_samples, offsets, 3)
+        arr = self._robot_inputs(poses, odom_vels, have_pose)
+        if len(arr) != len(inst):
+            raise ValueError("tp_ros_check_trajectories: one pose per listed robot")
+        costs = np.zeros(max(len(flat), 1), np.float64)
+        ok = np.zeros(max(len(flat), 1), np.int32)
+        check(self.L.navgpu_tp_ros_check_trajectories(self.h, len(inst), _ptr(inst), arr, _ptr(off), _ptr(flat), int(bool(update_map)),
+                                                      _ptr(costs), _ptr(ok)), "tp_ros_check_trajectories")
+        return costs[:len(flat)].copy(), ok[:len(flat)].astype(bool)
+
+    def _tp_ros_plan(self, fn, what, instance):
+        n = check(fn(self.h, instance, None, 0), what)
+        out = np.zeros((n, 3))
+        if n:
+            check(fn(self.h, instance, _ptr(out), n), what)
+        return out
+
+    def tp_ros_global_plan(self, instance):
+        """global_plan_ of the robot after pruning, (n, 3)."""
+        return self._tp_ros_plan(self.L.navgpu_tp_ros_get_plan, "tp_ros_get_plan", instance)
+
+    def tp_ros_transformed_plan(self, instance):
+        """The transformed (and pruned) window of the robot's last cycle, (m, 3): what g_plan_pub_ publishes."""
+        return self._tp_ros_plan(self.L.navgpu_tp_ros_transformed_plan, "tp_ros_transformed_plan", instance)
 
     # ---------------------------------------------------------------- footprint queries, rotate recovery, carrot planner
     def footprint_cost(self, poses, first=0, allow_unknown=True, want_first_illegal=True):
