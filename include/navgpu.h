@@ -1649,6 +1649,123 @@ int navgpu_amcl_init_uniform(navgpu_amcl* amcl, uint32_t first, uint32_t count, 
                              const double* ranges_xy, const uint32_t* range_counts, const double* range_max, int32_t draw_source,
                              uint64_t* drand48_state, uint64_t seed, uint64_t* candidates_used, int32_t* status);
 
+/* ---- amcl node: AmclNode::laserReceived for every filter of a slice, one call per scan ---- */
+/* A ROS-free mirror of what AmclNode keeps and decides between scans (amcl/src/amcl_node.cpp:1316-1756), one laser per filter
+ * (lasers_update_ is one flag).  The pf steps are the calls above, with device draws; here they are chained for the whole slice
+ * with each filter predicated by what the node decides for it, and the call waits for the device once.  The tf look-ups stay
+ * with the caller (getOdomPose's result and the two tf::getYaw results of the scan's first two rays are inputs), as does every
+ * message.  tf's 3-D arithmetic is restated in its planar form, not pinned. */
+typedef struct {
+  double d_thresh, a_thresh;      /* update_min_d / update_min_a (amcl_node.cpp:1403-1412)                                 */
+  double laser_min_range;         /* <= 0: unset, the message's range_min holds (amcl_node.cpp:1518-1522)                  */
+  double laser_max_range;         /* <= 0: unset (amcl_node.cpp:1514-1517)                                                 */
+  int32_t resample_interval;      /* >= 1 (amcl_node.cpp:1546)                                                             */
+  int32_t use_odom_integrator;    /* odom_integrator_topic_.size() != 0 (amcl_node.cpp:1403, 1454)                         */
+} navgpu_amcl_node_params;
+/* replaces: the node's parameters read at amcl_node.cpp:1403-1412, 1514-1522, 1546.  All or nothing: NAVGPU_ERR_INVALID for a
+ * NaN, resample_interval < 1 (the reference would compute % 0) or use_odom_integrator outside {0, 1}; the configuration in
+ * force stays then. */
+int navgpu_amcl_node_configure(navgpu_amcl* amcl, const navgpu_amcl_node_params* params);
+#define NAVGPU_AMCL_SCAN_PRESENT 1u /* navgpu_amcl_scan::flags bit 0: a LaserScan arrived for this filter in this call */
+typedef struct {
+  uint32_t flags;                 /* NAVGPU_AMCL_SCAN_PRESENT; a filter without it is untouched, its node state included   */
+  uint32_t range_count;           /* laser_scan->ranges.size()                                                             */
+  uint32_t range_offset;          /* first range of this filter in the call's `ranges` array                               */
+  float range_min, range_max;     /* the message's floats                                                                  */
+  uint32_t reserved;
+  double yaw_min, yaw_inc;        /* tf::getYaw(min_q), tf::getYaw(inc_q) after transformQuaternion (amcl_node.cpp:1505-1506) */
+  double odom_pose[3];            /* getOdomPose's x, y, yaw at the scan's stamp (amcl_node.cpp:1383)                      */
+} navgpu_amcl_scan;
+typedef struct {
+  int32_t status;                 /* NAVGPU_OK; NAVGPU_ERR_INVALID: the filter was refused and is untouched (see below)    */
+  int32_t moved;                  /* AMCLOdom::UpdateAction ran (amcl_node.cpp:1442-1470)                                  */
+  int32_t updated;                /* the sensor step ran: the `if (lasers_update_[laser_index])` block (:1474-1582)        */
+  int32_t resampled;              /* pf_update_resample ran (:1546-1549)                                                   */
+  int32_t cloud_due;              /* the particle cloud would be published: `if (!m_force_update)` (:1562) inside that block */
+  int32_t published;              /* max_weight > 0.0 (:1614): pose, covariance and map_to_odom below are this scan's      */
+  int32_t republish;              /* the `else if (latest_tf_valid_)` branch (:1726): latest_tf_ is sent again              */
+  int32_t global_localization_converged; /* global_localization_active_ was cleared by this call (:1550-1554)              */
+  int32_t sample_count, converged;/* the current set after the call                                                        */
+  int32_t cluster_count;          /* hypotheses read (0 unless resampled or force_publication)                             */
+  int32_t max_weight_hyp;         /* -1 when none has weight > 0                                                           */
+  double max_weight;
+  double pose[3];                 /* hyps[max_weight_hyp].pf_pose_mean                                                     */
+  double cov_xx, cov_xy, cov_yx, cov_yy, cov_aa; /* set->cov.m[0][0], [0][1], [1][0], [1][1], [2][2] (:1637-1651)         */
+  double map_to_odom[3];          /* x, y, theta of latest_tf_.inverse() (:1708): what is broadcast global -> odom          */
+} navgpu_amcl_node_result;
+/* replaces: AmclNode::laserReceived from getOdomPose's result on (amcl_node.cpp:1381-1756) for filters first .. first + count - 1.
+ * scans = count records; ranges = every flagged filter's raw LaserScan::ranges as floats (a filter reads range_count of them at
+ * range_offset; the call uploads max(range_offset + range_count) floats); results = count records, zeroed for a filter
+ * without NAVGPU_AMCL_SCAN_PRESENT.  Per flagged filter, in the reference's order:
+ * - delta = pose - pf_odom_pose_ with angle_diff on the yaw (:1397-1399, the host's libm); update = |delta x|, |delta y| > d_thresh
+ *   or |delta yaw| > a_thresh, or with use_odom_integrator sqrt(abs x^2 + abs y^2) >= d_thresh or abs yaw >= a_thresh over the
+ *   integrator's absolute motion (:1403-1412); update |= m_force_update and m_force_update is cleared, only inside if (pf_init_);
+ * - a filter with pf_init_ false takes the first-scan branch (:1423-1440): pf_odom_pose_ = pose, lasers_update_, resample_count_ = 0,
+ *   the integrator not ready, force_publication; a pending nomotion request survives it and forces the next scan's update;
+ * - otherwise, with lasers_update_, UpdateAction with odata.pose / delta / absolute_motion (:1447-1464: navgpu_amcl_update_action's
+ *   9 doubles) and the integrator's absolute motion is zeroed (:1469);
+ * - with lasers_update_: the scan is converted (:1505-1537): angle_increment = fmod(yaw_inc - yaw_min + 5 pi, 2 pi) - pi on the
+ *   host; range_max = min(msg range_max, (float)laser_max_range) and range_min = max(msg range_min, (float)laser_min_range) as
+ *   floats when set, then widened; on the device (k_amcl_scan), only for the rays the model's subsampling step reads:
+ *   range = (double)ranges[i] <= range_min ? range_max : ranges[i] (a NaN passes through), bearing = angle_min + (i * angle_increment)
+ *   with the product rounded before the sum: the bytes of a host-built AMCLLaserData.  Then UpdateSensor, lasers_update_ = false,
+ *   pf_odom_pose_ = pose; when !(++resample_count_ % resample_interval) the resample, and global_localization_active_ is
+ *   cleared when the resampled filter is converged (:1546-1555);
+ * - when resampled or force_publication the hypotheses are read (:1584-1651, navgpu_amcl_hypotheses below) and, with
+ *   max_weight > 0, latest_tf_ is set; else with latest_tf_valid_ the result says republish.
+ * map_to_odom: for the hypothesis h and the scan's odometry pose o, theta = h.theta - o.theta, (x, y) = h.xy - R(theta) o.xy, the
+ *   planar form of :1678-1700 computed on the host; latest_tf_ (navgpu_amcl_node_get_state) is its inverse, {-R(-theta) xy, -theta}.
+ *   This restates tf's 3-D quaternion arithmetic and is not pinned to it: expect its rounding to differ in the last bits.
+ * Draws are the device generator's (NAVGPU_AMCL_DRAW_DEVICE) keyed by `seed`; a filter's call counter goes up by one for each
+ * of UpdateAction and the resample that ran for it, and by none otherwise: the bytes are those of navgpu_amcl_update_action,
+ * navgpu_amcl_update_sensor and navgpu_amcl_update_resample called for that filter alone, in this order, with the same seed.
+ * With laser max_beams < 2 UpdateSensor returns false in the reference (amcl_laser.cpp:163-164) and nothing of the sensor step
+ * runs on the device; the node's bookkeeping (updated, resample_count_) goes on as in the reference.
+ * One call enqueues the motion model, the conversion, the sensor model, the resample and the read-out for the slice back to
+ * back and waits once; nothing of a step's result is read by the host in between.
+ * NAVGPU_ERR_STATE before navgpu_amcl_node_configure, navgpu_amcl_laser_configure, navgpu_amcl_odom_configure or
+ * navgpu_amcl_resample_configure, or for a flagged filter without a map: nothing runs and no state changes.  A flagged filter
+ * whose beam model would loop forever (1 <= range_count < max_beams, amcl_laser.cpp:265), whether or not its update is due, gets
+ * status = NAVGPU_ERR_INVALID and is untouched, node state included; the others run and the call returns NAVGPU_ERR_INVALID,
+ * as it does when a resample fails a filter (status = that code; navgpu_amcl_update_resample). */
+int navgpu_amcl_node_laser_received(navgpu_amcl* amcl, uint32_t first, uint32_t count, const navgpu_amcl_scan* scans,
+                                    const float* ranges, uint64_t seed, navgpu_amcl_node_result* results);
+/* replaces: the hypothesis read-out of amcl_node.cpp:1584-1651 alone, for every filter of the slice, from whatever clusters the
+ * last resample or init left (k_amcl_hypothesis, one read-back for the slice).  This is what force_publication reads right
+ * after an init.  Fills cluster_count, max_weight_hyp, max_weight, published, pose, the covariance entries, sample_count and
+ * converged; the other fields are 0 (map_to_odom needs a scan's odometry pose).  The hypothesis is the first cluster with the
+ * strictly largest weight in the device's cluster order (clusters are numbered by their lowest sample index, get_clusters):
+ * with exactly equal weights the reference's kd-tree order may pick another cluster.  A filter that was never resampled or
+ * initialised reports published = 0, cluster_count = 0. */
+int navgpu_amcl_hypotheses(navgpu_amcl* amcl, uint32_t first, uint32_t count, navgpu_amcl_node_result* results);
+typedef struct {
+  int32_t pf_init;                       /* pf_init_                                                                      */
+  int32_t lasers_update;                 /* lasers_update_[0] (true when the laser is first seen, amcl_node.cpp:1344)     */
+  int32_t force_update;                  /* m_force_update                                                                */
+  int32_t resample_count;                /* resample_count_                                                               */
+  int32_t odom_integrator_ready;         /* odom_integrator_ready_                                                        */
+  int32_t global_localization_active;    /* global_localization_active_                                                   */
+  int32_t latest_tf_valid;               /* latest_tf_valid_                                                              */
+  int32_t reserved;
+  double pf_odom_pose[3];                /* pf_odom_pose_                                                                 */
+  double odom_integrator_absolute_motion[3]; /* odom_integrator_absolute_motion_                                          */
+  double odom_integrator_last_pose[3];   /* odom_integrator_last_pose_                                                    */
+  double latest_tf[3];                   /* latest_tf_ as planar x, y, theta (odom -> global)                             */
+} navgpu_amcl_node_state;
+/* Host-only, no device work.  replaces: what applyInitialPose (amcl_node.cpp:1862-1876) and globalLocalizationCallback
+ * (:1265-1293) do to the node after the init call the caller makes itself: pf_init_ = false, and
+ * global_localization_active_ = global_localization != 0. */
+int navgpu_amcl_node_reset(navgpu_amcl* amcl, uint32_t first, uint32_t count, int32_t global_localization);
+/* replaces: AmclNode::nomotionUpdateCallback (amcl_node.cpp:1296-1303): m_force_update = true */
+int navgpu_amcl_node_request_nomotion_update(navgpu_amcl* amcl, uint32_t first, uint32_t count);
+/* replaces: AmclNode::integrateOdom (amcl_node.cpp:1120-1172) for one odometry message per filter of the slice, in the
+ * reference's own expressions with the host's libm.  poses = count x {x, y, yaw} of the message (getEulerYPR's yaw is the
+ * caller's).  NAVGPU_ERR_INVALID for a NULL argument. */
+int navgpu_amcl_node_integrate_odom(navgpu_amcl* amcl, uint32_t first, uint32_t count, const double* poses);
+/* Every member the mirror keeps, per filter of the slice (checkpointing, tests) */
+int navgpu_amcl_node_get_state(navgpu_amcl* amcl, uint32_t first, uint32_t count, navgpu_amcl_node_state* states);
+int navgpu_amcl_node_set_state(navgpu_amcl* amcl, uint32_t first, uint32_t count, const navgpu_amcl_node_state* states);
+
 #ifdef __cplusplus
 }
 #endif

@@ -405,6 +405,49 @@ class AmclOdomParams(C.Structure):
             setattr(self, k, v)
 
 
+class AmclNodeParams(C.Structure):
+    """Mirror of navgpu_amcl_node_params (include/navgpu.h).  Defaults: amcl_node's update_min_d 0.2, update_min_a pi / 6,
+    resample_interval 2, laser_min_range / laser_max_range -1 (unset) and no odom integrator topic."""
+    _fields_ = [("d_thresh", C.c_double), ("a_thresh", C.c_double), ("laser_min_range", C.c_double), ("laser_max_range", C.c_double),
+                ("resample_interval", C.c_int32), ("use_odom_integrator", C.c_int32)]
+    DEFAULTS = dict(d_thresh=0.2, a_thresh=0.5235987755982988, laser_min_range=-1.0, laser_max_range=-1.0, resample_interval=2,
+                    use_odom_integrator=0)
+
+    def __init__(self, **kw):
+        super().__init__()
+        d = dict(self.DEFAULTS)
+        d.update(kw)
+        for k, v in d.items():
+            setattr(self, k, v)
+
+
+AMCL_SCAN_PRESENT = 1  # NAVGPU_AMCL_SCAN_PRESENT
+
+
+class AmclScan(C.Structure):
+    """Mirror of navgpu_amcl_scan (include/navgpu.h)."""
+    _fields_ = [("flags", C.c_uint32), ("range_count", C.c_uint32), ("range_offset", C.c_uint32), ("range_min", C.c_float),
+                ("range_max", C.c_float), ("reserved", C.c_uint32), ("yaw_min", C.c_double), ("yaw_inc", C.c_double),
+                ("odom_pose", C.c_double * 3)]
+
+
+class AmclNodeResult(C.Structure):
+    """Mirror of navgpu_amcl_node_result (include/navgpu.h)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "status", "moved", "updated", "resampled", "cloud_due", "published", "republish", "global_localization_converged",
+        "sample_count", "converged", "cluster_count", "max_weight_hyp")] + [
+        ("max_weight", C.c_double), ("pose", C.c_double * 3)] + [(n, C.c_double) for n in (
+            "cov_xx", "cov_xy", "cov_yx", "cov_yy", "cov_aa")] + [("map_to_odom", C.c_double * 3)]
+
+
+class AmclNodeState(C.Structure):
+    """Mirror of navgpu_amcl_node_state (include/navgpu.h)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "pf_init", "lasers_update", "force_update", "resample_count", "odom_integrator_ready", "global_localization_active",
+        "latest_tf_valid", "reserved")] + [(n, C.c_double * 3) for n in (
+            "pf_odom_pose", "odom_integrator_absolute_motion", "odom_integrator_last_pose", "latest_tf")]
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -576,6 +619,14 @@ SYMBOLS = [
     ("navgpu_amcl_update_action", C.c_int, [vp, u32, u32, vp, i32, vp, C.c_uint64, vp]),
     ("navgpu_amcl_init_gaussian", C.c_int, [vp, u32, u32, vp, vp, i32, vp, C.c_uint64, vp]),
     ("navgpu_amcl_init_uniform", C.c_int, [vp, u32, u32, C.POINTER(AmclUniformParams), vp, vp, vp, i32, vp, C.c_uint64, vp, vp]),
+    ("navgpu_amcl_node_configure", C.c_int, [vp, C.POINTER(AmclNodeParams)]),
+    ("navgpu_amcl_node_laser_received", C.c_int, [vp, u32, u32, vp, vp, C.c_uint64, vp]),
+    ("navgpu_amcl_hypotheses", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_node_reset", C.c_int, [vp, u32, u32, i32]),
+    ("navgpu_amcl_node_request_nomotion_update", C.c_int, [vp, u32, u32]),
+    ("navgpu_amcl_node_integrate_odom", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_node_get_state", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_amcl_node_set_state", C.c_int, [vp, u32, u32, vp]),
 ]
 
 

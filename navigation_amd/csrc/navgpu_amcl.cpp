@@ -1,124 +1,9 @@
 // navgpu_amcl_*: host side of the amcl laser update for a batch of particle filters (see amcl_kernels.hip and include/navgpu.h).
-#include <algorithm>
-#include <cmath>
-#include <memory>
-
-#include "navgpu_amcl.h"
-#include "navgpu_fleet.h"
+#include "navgpu_amcl_host.h"
 
 #include <array>
 
 namespace {
-// One map_t on the device; several filters may hold the same one (set_map with shared != 0)
-struct AmclMap {
-  int8_t* occ = nullptr;
-  float* dist = nullptr;
-  int32_t* free_cells = nullptr;  // occ_state == -1, x-major (AmclNode::free_space_indices, amcl_node.cpp:1028-1033)
-  int n_free = 0;
-  // the same restricted to map_occ_dist > radius, as the node builds it (init_uniform); rebuilt when the radius or distances change
-  int32_t* free_r = nullptr;
-  int n_free_r = 0;
-  double free_r_radius = 0;
-  bool free_r_valid = false;
-  int sx = 0, sy = 0;
-  double scale = 0, ox = 0, oy = 0, max_occ_dist = 0;
-  ~AmclMap() {
-    if (occ) hipFree(occ);
-    if (dist) hipFree(dist);
-    if (free_cells) hipFree(free_cells);
-    if (free_r) hipFree(free_r);
-  }
-};
-}  // namespace
-
-struct navgpu_amcl {
-  AmclDev d{};
-  uint32_t n = 0;
-  int device = 0;
-  std::recursive_mutex mu;
-  hipStream_t stream = nullptr;
-  std::vector<void*> allocs;
-  std::vector<std::shared_ptr<AmclMap>> maps;  // [n]
-  std::vector<AmclMapDev> map_desc;            // [n] mirror of d.maps
-  std::vector<int32_t> sample_count, converged;
-  std::vector<double> laser;                   // [n][3]
-  navgpu_amcl_laser_params params{};
-  bool configured = false;
-  AmclFilterDev* d_filters = nullptr;          // [n]
-  double* d_beams = nullptr;                   // [n][2 * max_beams][2] subsampled {range, bearing}
-  // resampling (navgpu_amcl_update_resample); the workspace is allocated by the first call
-  navgpu_amcl_resample_params rparams{};
-  bool rconfigured = false;
-  AmclResampleDev rs{};
-  bool rs_ready = false;
-  AmclResampleFilterDev* d_rfilters = nullptr;  // [n]
-  std::vector<int32_t> leaf, cluster_count;     // kd-tree leaf count of the current set at its creation; its cluster count
-  std::vector<uint64_t> rng_ctr;                // device draws: calls made per filter
-  void* d_upload = nullptr;                     // supplied draws of the last call
-  size_t upload_bytes = 0;
-  // motion model (navgpu_amcl_update_action); the record workspace is allocated by the first configure
-  navgpu_amcl_odom_params oparams{};
-  bool oconfigured = false;
-  double2* d_records = nullptr;                 // [n][3 max_samples] drand48 Gaussian records {x2, s}
-  AmclOdomFilterDev* d_ofilters = nullptr;      // [n]
-  AmclInitFilterDev* d_ifilters = nullptr;      // [n] init calls (navgpu_amcl_init_*)
-  template <class T>
-  int alloc(T** p, size_t count) {
-    void* q = nullptr;
-    const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    if (hipMalloc(&q, bytes) != hipSuccess) {
-      g_last_error = "hipMalloc failed (amcl)";
-      return NAVGPU_ERR_HIP;
-    }
-    hipMemsetAsync(q, 0, bytes, stream);
-    allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return NAVGPU_OK;
-  }
-  bool rangeOk(uint32_t first, uint32_t count) const { return count > 0 && first < n && count <= n - first; }
-  // the resampling workspace (also the init's), allocated by the first call that needs it
-  int resampleWorkspace() {
-    if (rs_ready) return NAVGPU_OK;
-    const size_t ms = d.max_samples, n = this->n;
-    AmclResampleDev& r = rs;
-    uint32_t P = 1;
-    while (P < ms) P <<= 1;
-    r.P = P;
-    int rc = 0;
-#define A(ptr, cnt) \
-  if (!rc) rc = alloc(&(ptr), (size_t)(cnt));
-    A(r.c, n * (ms + 1));
-    A(r.cand, n * ms * 3);
-    A(r.cs, n * ms * 2);
-    A(r.skey, n * P);
-    A(r.sidx, n * P);
-    A(r.a, n * P);
-    A(r.b, n * P);
-    A(r.label, n * ms);
-    A(r.ukey, n * ms);
-    A(r.cstart, n * ms);
-    A(r.cl_count, n * ms);
-    A(r.cl_stats, n * ms * 13);
-    A(r.set_stats, n * 12);
-#undef A
-    if (rc) return rc;
-    HIP_TRY(waitStream(stream));
-    rs_ready = true;
-    return NAVGPU_OK;
-  }
-  int uploadMaps() {
-    HIP_TRY(hipMemcpyAsync(d.maps, map_desc.data(), sizeof(AmclMapDev) * n, hipMemcpyHostToDevice, stream));
-    HIP_TRY(waitStream(stream));
-    return NAVGPU_OK;
-  }
-};
-
-namespace {
-struct AmclGuard {
-  std::lock_guard<std::recursive_mutex> lk;
-  explicit AmclGuard(navgpu_amcl* h) : lk(h->mu) { (void)hipSetDevice(h->device); }
-};
-
 bool isFinite(double v) { return std::isfinite(v); }
 
 bool paramsValid(const navgpu_amcl_laser_params& p) {
@@ -164,6 +49,7 @@ int navgpu_amcl_create(uint32_t n_filters, uint32_t max_samples, uint32_t max_be
   h->leaf.assign(n_filters, 0);
   h->cluster_count.assign(n_filters, 0);
   h->rng_ctr.assign(n_filters, 0);
+  h->node.assign(n_filters, AmclNodeFilter{});
   AmclDev& d = h->d;
   d.max_samples = max_samples;
   d.max_beams = max_beams;
@@ -197,6 +83,8 @@ int navgpu_amcl_destroy(navgpu_amcl* h) {
   h->maps.clear();
   for (void* p : h->allocs) hipFree(p);
   if (h->d_upload) hipFree(h->d_upload);
+  if (h->d_raw) hipFree(h->d_raw);
+  if (h->node_readback) hipHostFree(h->node_readback);
   if (h->stream) hipStreamDestroy(h->stream);
   delete h;
   return NAVGPU_OK;
@@ -237,19 +125,7 @@ int32_t leafCount(const double* poses, int n) {
   return (int32_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
 }
 
-// The models' subsampling step of a scan (amcl_laser.cpp:265, 334-338, 417-421, 637-641); < 1 where the beam model's loop would
-// never end.  max_beams >= 2.
-int beamStep(const navgpu_amcl_laser_params& P, int rcount) {
-  int step;
-  if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB) {
-    step = (int)ceil(rcount / static_cast<double>(P.max_beams));
-    if (step < 1) step = 1;
-  } else {
-    step = (rcount - 1) / (P.max_beams - 1);
-    if (step < 1 && P.model_type != NAVGPU_AMCL_MODEL_BEAM) step = 1;
-  }
-  return step;
-}
+int beamStep(const navgpu_amcl_laser_params& P, int rcount) { return navgpu::amclBeamStep(P, rcount); }
 
 // Maps of a slice: `src` is OccupancyGrid data (height x width, scaled up by `factor` on the device) or, with `cells`, map_t
 // occ_state values copied as they are (factor 1); scale and the centre origin (ox, oy) are map_t's own.
@@ -306,7 +182,226 @@ int setMaps(navgpu_amcl* h, uint32_t first, uint32_t count, const int8_t* src, u
   }
   return h->uploadMaps();
 }
+
+void odomConstants(const navgpu_amcl_odom_params& P, const double* o, double* k);
 }  // namespace
+
+// The steps' bodies (navgpu_amcl_host.h): what the public calls below run, and what navgpu_amcl_node_laser_received chains
+namespace navgpu {
+
+int amclBeamStep(const navgpu_amcl_laser_params& P, int rcount) {
+  int step;
+  if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB) {
+    step = (int)ceil(rcount / static_cast<double>(P.max_beams));
+    if (step < 1) step = 1;
+  } else {
+    step = (rcount - 1) / (P.max_beams - 1);
+    if (step < 1 && P.model_type != NAVGPU_AMCL_MODEL_BEAM) step = 1;
+  }
+  return step;
+}
+
+int amclSensorEnqueue(navgpu_amcl* h, uint32_t first, uint32_t count, const double* ranges_xy, const uint32_t* range_counts,
+                      const double* range_max, int32_t* updated, const uint8_t* mask, AmclSensorCall& c) {
+  const navgpu_amcl_laser_params& P = h->params;
+  // Subsample every filter's scan with the model's step (amcl_laser.cpp:265, 334-338, 417-421, 637-641)
+  std::vector<AmclFilterDev>& fd = c.fd;
+  std::vector<double>& beams = c.beams;
+  std::vector<AmclScanDev>* const scans = c.scans;
+  fd.assign(count, AmclFilterDev{});
+  beams.clear();
+  if (!scans) beams.reserve((size_t)count * 4 * P.max_beams);
+  int rc = NAVGPU_OK, max_samples = 0, max_nb = 0;
+  const double* src = ranges_xy;
+  size_t n_pairs = 0;
+  bool any = false;
+  for (uint32_t k = 0; k < count; ++k) {
+    const int rcount = (int)range_counts[k];
+    const uint32_t f = first + k;
+    AmclFilterDev& e = fd[k];
+    e = AmclFilterDev{};
+    if (mask && !mask[k]) {  // e.active == 0
+      updated[k] = 0;
+      if (scans) (*scans)[k].active = 0;
+      if (!scans) src += 2 * (size_t)rcount;
+      continue;
+    }
+    const int step = amclBeamStep(P, rcount);
+    e.sample_count = h->sample_count[f];
+    e.converged = h->converged[f];
+    e.range_max = range_max[k];
+    std::copy(&h->laser[3 * (size_t)f], &h->laser[3 * (size_t)f] + 3, e.laser);
+    e.beam_off = (uint32_t)n_pairs;
+    e.active = 1;
+    if (step < 1 && rcount > 0) {  // the beam model's loop would never end
+      e.active = 0;
+      updated[k] = NAVGPU_ERR_INVALID;
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_update_sensor: beam model with 1 <= range_count < max_beams (the reference loops forever)";
+      if (scans) (*scans)[k].active = 0;
+    } else {
+      updated[k] = 1;
+      any = true;
+      if (scans) {
+        (*scans)[k].active = 1;
+        (*scans)[k].step = step;
+        if (rcount > 0) n_pairs += ((size_t)rcount + step - 1) / step;
+      } else {
+        for (int i = 0; i < rcount; i += step) {
+          beams.push_back(src[2 * (size_t)i]);
+          beams.push_back(src[2 * (size_t)i + 1]);
+        }
+        n_pairs = beams.size() / 2;
+      }
+      e.n_beams = (int)(n_pairs - e.beam_off);
+      max_samples = std::max(max_samples, e.sample_count);
+      max_nb = std::max(max_nb, e.n_beams);
+    }
+    if (!scans) src += 2 * (size_t)rcount;
+  }
+  c.soft = rc;
+  if (2 * n_pairs > (size_t)h->n * 2 * h->d.max_beams * 2) return NAVGPU_ERR_CAPACITY;  // cannot happen: < 2 max_beams per filter
+  if (mask && !any) return NAVGPU_OK;
+  if (!beams.empty())
+    HIP_TRY(hipMemcpyAsync(h->d_beams, beams.data(), sizeof(double) * beams.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_filters, amclStaged(c.stage, fd.data(), sizeof(AmclFilterDev) * count), sizeof(AmclFilterDev) * count,
+                         hipMemcpyHostToDevice, h->stream));
+  if (scans) {
+    HIP_TRY(hipMemcpyAsync(h->d_scans, amclStaged(c.scan_stage, scans->data(), sizeof(AmclScanDev) * count), sizeof(AmclScanDev) * count,
+                           hipMemcpyHostToDevice, h->stream));
+    launch_amcl_scan(h->d, first, count, h->d_filters, h->d_scans, h->d_raw, h->d_beams, h->stream);
+  } else {
+    HIP_TRY(hipMemsetAsync(h->d.obs_count + (size_t)first * h->d.max_beams, 0, sizeof(int32_t) * count * h->d.max_beams, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d.obs_mask + (size_t)first * h->d.max_beams, 0, (size_t)count * h->d.max_beams, h->stream));
+    HIP_TRY(hipMemsetAsync(h->d.skip_info + 2 * (size_t)first, 0, sizeof(int32_t) * 2 * count, h->stream));
+  }
+  if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB && P.do_beamskip)
+    launch_amcl_laser(h->d, P, first, count, h->d_filters, h->d_beams, max_samples, max_nb, 1, h->stream);
+  launch_amcl_laser(h->d, P, first, count, h->d_filters, h->d_beams, max_samples, max_nb, 0, h->stream);
+  launch_amcl_normalize(h->d, P, first, count, h->d_filters, h->stream);
+  return checkLaunch();
+}
+
+int amclResampleEnqueue(navgpu_amcl* h, uint32_t first, uint32_t count, bool dev, const double* u, const double* systematic_start,
+                        const double* random_poses, const uint32_t* random_pose_counts, uint64_t pool_total, uint64_t seed,
+                        const uint8_t* mask, AmclResampleCall& c) {
+  const navgpu_amcl_resample_params& R = h->rparams;
+  const bool sys = R.resample_model == NAVGPU_AMCL_RESAMPLE_SYSTEMATIC;
+  const size_t ms = h->d.max_samples;
+  AmclResampleDev& r = h->rs;
+  if (int rc = h->resampleWorkspace()) return rc;
+  // supplied draws: {u_flag, u_pick} pairs (multinomial) then the random-pose pool, in one upload
+  const size_t u_doubles = (!dev && !sys) ? (size_t)count * ms * 2 : 0, bytes = sizeof(double) * (u_doubles + 3 * pool_total);
+  r.u = nullptr;
+  r.pool = nullptr;
+  if (bytes) {
+    if (bytes > h->upload_bytes) {
+      if (h->d_upload) hipFree(h->d_upload);
+      h->d_upload = nullptr;
+      h->upload_bytes = 0;
+      HIP_TRY(hipMalloc(&h->d_upload, bytes));
+      h->upload_bytes = bytes;
+    }
+    double* up = static_cast<double*>(h->d_upload);
+    if (u_doubles) HIP_TRY(hipMemcpyAsync(up, u, sizeof(double) * u_doubles, hipMemcpyHostToDevice, h->stream));
+    if (pool_total)
+      HIP_TRY(hipMemcpyAsync(up + u_doubles, random_poses, sizeof(double) * 3 * pool_total, hipMemcpyHostToDevice, h->stream));
+    r.u = up;
+    r.pool = up + u_doubles;
+  }
+  c.dev = dev;
+  std::vector<AmclResampleFilterDev>& fd = c.fd;
+  fd.assign(count, AmclResampleFilterDev{});
+  uint64_t pool_off = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    AmclResampleFilterDev& e = fd[k];
+    const uint32_t f = first + k;
+    e.sample_count = h->sample_count[f];
+    e.leaf_in = h->leaf[f];
+    e.pool_count = dev ? 0 : (int32_t)random_pose_counts[k];
+    e.pool_off = pool_off;
+    pool_off += dev ? 0 : random_pose_counts[k];
+    e.rng_ctr = h->rng_ctr[f];
+    e.sys_start = (!dev && sys) ? systematic_start[k] : 0.0;
+    e.active = (mask && !mask[k]) ? 0 : 1;
+    e.status = NAVGPU_ERR_INVALID;
+  }
+  HIP_TRY(hipMemcpyAsync(h->d_rfilters, amclStaged(c.stage, fd.data(), sizeof(AmclResampleFilterDev) * count),
+                         sizeof(AmclResampleFilterDev) * count, hipMemcpyHostToDevice, h->stream));
+  const AmclResampleParamsDev P{R.resample_model, R.min_samples, (int32_t)ms, dev ? 1 : 0, R.pop_err, R.pop_z, R.dist_threshold, seed};
+  launch_amcl_resample(h->d, r, P, first, count, h->d_rfilters, h->stream);
+  return checkLaunch();
+}
+
+int amclResampleCommit(navgpu_amcl* h, uint32_t first, uint32_t count, int32_t* status, const AmclResampleCall& c) {
+  int rc = NAVGPU_OK;
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t f = first + k;
+    const AmclResampleFilterDev& e = c.fd[k];
+    if (!e.active) {
+      status[k] = 0;
+      continue;
+    }
+    status[k] = e.status;
+    if (c.dev) ++h->rng_ctr[f];
+    if (e.status != NAVGPU_OK) {
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_update_resample: a filter has no samples, too few supplied random poses, no free cell or a pose "
+                     "outside the histogram's range";
+      continue;
+    }
+    h->sample_count[f] = e.count;
+    h->leaf[f] = e.leaf_out;
+    h->converged[f] = e.converged;
+    h->cluster_count[f] = e.cluster_count;
+  }
+  return rc;
+}
+
+int amclActionEnqueue(navgpu_amcl* h, uint32_t first, uint32_t count, const double* odom, bool dev, const uint64_t* drand48_state,
+                      uint64_t seed, int32_t* status, const uint8_t* mask, AmclActionCall& c) {
+  std::vector<AmclOdomFilterDev>& fd = c.fd;
+  fd.assign(count, AmclOdomFilterDev{});
+  c.dev = dev;
+  int rc = NAVGPU_OK, max_count = 0;
+  for (uint32_t k = 0; k < count; ++k) {
+    AmclOdomFilterDev& e = fd[k];
+    const uint32_t f = first + k;
+    status[k] = NAVGPU_OK;
+    if (mask && !mask[k]) continue;  // e.active == 0
+    e.sample_count = h->sample_count[f];
+    e.active = 1;
+    e.state = dev ? 0 : drand48_state[k];
+    e.rng_ctr = h->rng_ctr[f];
+    odomConstants(h->oparams, odom + 9 * (size_t)k, e.k);
+    if (!dev && drand48_state[k] > kAmclDrand48Mask) {
+      e.active = 0;
+      status[k] = NAVGPU_ERR_INVALID;
+      rc = NAVGPU_ERR_INVALID;
+      g_last_error = "navgpu_amcl_update_action: a drand48 state >= 2^48";
+      continue;
+    }
+    max_count = std::max(max_count, e.sample_count);
+  }
+  c.soft = rc;
+  HIP_TRY(hipMemcpyAsync(h->d_ofilters, amclStaged(c.stage, fd.data(), sizeof(AmclOdomFilterDev) * count),
+                         sizeof(AmclOdomFilterDev) * count, hipMemcpyHostToDevice, h->stream));
+  if (!dev) launch_amcl_drand48_gauss(h->d_records, h->d.max_samples, count, h->d_ofilters, h->stream);
+  launch_amcl_odom(h->d, h->oparams.model_type, dev ? 1 : 0, seed, h->d_records, first, count, max_count, h->d_ofilters, h->stream);
+  return checkLaunch();
+}
+
+void amclActionCommit(navgpu_amcl* h, uint32_t first, uint32_t count, uint64_t* drand48_state, const AmclActionCall& c) {
+  for (uint32_t k = 0; k < count; ++k) {
+    if (!c.fd[k].active) continue;
+    if (c.dev)
+      ++h->rng_ctr[first + k];
+    else
+      drand48_state[k] = c.fd[k].state;
+  }
+}
+
+}  // namespace navgpu
 
 extern "C" {
 
@@ -461,54 +556,11 @@ int navgpu_amcl_update_sensor(navgpu_amcl* h, uint32_t first, uint32_t count, co
       return NAVGPU_ERR_STATE;
     }
   }
-  // Subsample every filter's scan with the model's step (amcl_laser.cpp:265, 334-338, 417-421, 637-641)
-  std::vector<AmclFilterDev> fd(count);
-  std::vector<double> beams;
-  beams.reserve((size_t)count * 4 * P.max_beams);
-  int rc = NAVGPU_OK, max_samples = 0, max_nb = 0;
-  const double* src = ranges_xy;
-  for (uint32_t k = 0; k < count; ++k) {
-    const int rcount = (int)range_counts[k];
-    const uint32_t f = first + k;
-    const int step = beamStep(P, rcount);
-    AmclFilterDev& e = fd[k];
-    e.sample_count = h->sample_count[f];
-    e.converged = h->converged[f];
-    e.range_max = range_max[k];
-    std::copy(&h->laser[3 * (size_t)f], &h->laser[3 * (size_t)f] + 3, e.laser);
-    e.beam_off = (uint32_t)(beams.size() / 2);
-    e.active = 1;
-    if (step < 1 && rcount > 0) {  // the beam model's loop would never end
-      e.active = 0;
-      updated[k] = NAVGPU_ERR_INVALID;
-      rc = NAVGPU_ERR_INVALID;
-      g_last_error = "navgpu_amcl_update_sensor: beam model with 1 <= range_count < max_beams (the reference loops forever)";
-    } else {
-      updated[k] = 1;
-      for (int i = 0; i < rcount; i += step) {
-        beams.push_back(src[2 * (size_t)i]);
-        beams.push_back(src[2 * (size_t)i + 1]);
-      }
-      e.n_beams = (int)(beams.size() / 2 - e.beam_off);
-      max_samples = std::max(max_samples, e.sample_count);
-      max_nb = std::max(max_nb, e.n_beams);
-    }
-    src += 2 * (size_t)rcount;
-  }
-  if (beams.size() > (size_t)h->n * 2 * h->d.max_beams * 2) return NAVGPU_ERR_CAPACITY;  // cannot happen: < 2 max_beams per filter
-  if (!beams.empty())
-    HIP_TRY(hipMemcpyAsync(h->d_beams, beams.data(), sizeof(double) * beams.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_filters, fd.data(), sizeof(AmclFilterDev) * count, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemsetAsync(h->d.obs_count + (size_t)first * h->d.max_beams, 0, sizeof(int32_t) * count * h->d.max_beams, h->stream));
-  HIP_TRY(hipMemsetAsync(h->d.obs_mask + (size_t)first * h->d.max_beams, 0, (size_t)count * h->d.max_beams, h->stream));
-  HIP_TRY(hipMemsetAsync(h->d.skip_info + 2 * (size_t)first, 0, sizeof(int32_t) * 2 * count, h->stream));
-  if (P.model_type == NAVGPU_AMCL_MODEL_LIKELIHOOD_FIELD_PROB && P.do_beamskip)
-    launch_amcl_laser(h->d, P, first, count, h->d_filters, h->d_beams, max_samples, max_nb, 1, h->stream);
-  launch_amcl_laser(h->d, P, first, count, h->d_filters, h->d_beams, max_samples, max_nb, 0, h->stream);
-  launch_amcl_normalize(h->d, P, first, count, h->d_filters, h->stream);
-  const int lrc = checkLaunch();
+  AmclSensorCall c;
+  const int lrc = amclSensorEnqueue(h, first, count, ranges_xy, range_counts, range_max, updated, nullptr, c);
+  if (lrc == NAVGPU_ERR_CAPACITY) return lrc;
   HIP_TRY(waitStream(h->stream));
-  return lrc ? lrc : rc;
+  return lrc ? lrc : c.soft;
 }
 
 int navgpu_amcl_beam_skip_state(navgpu_amcl* h, uint32_t filter, int32_t* obs_count, uint8_t* obs_mask, int32_t* error, int32_t* active) {
@@ -577,9 +629,7 @@ int navgpu_amcl_update_resample(navgpu_amcl* h, uint32_t first, uint32_t count, 
     g_last_error = "navgpu_amcl_update_resample before navgpu_amcl_resample_configure";
     return NAVGPU_ERR_STATE;
   }
-  const navgpu_amcl_resample_params& R = h->rparams;
-  const bool sys = R.resample_model == NAVGPU_AMCL_RESAMPLE_SYSTEMATIC, dev = draw_source == NAVGPU_AMCL_DRAW_DEVICE;
-  const size_t ms = h->d.max_samples;
+  const bool sys = h->rparams.resample_model == NAVGPU_AMCL_RESAMPLE_SYSTEMATIC, dev = draw_source == NAVGPU_AMCL_DRAW_DEVICE;
   uint64_t pool_total = 0;
   if (!dev) {
     if (!random_pose_counts || (!sys && !u) || (sys && !systematic_start)) return NAVGPU_ERR_INVALID;
@@ -593,67 +643,12 @@ int navgpu_amcl_update_resample(navgpu_amcl* h, uint32_t first, uint32_t count, 
         return NAVGPU_ERR_STATE;
       }
   }
-  AmclResampleDev& r = h->rs;
-  if (int rc = h->resampleWorkspace()) return rc;
-  // supplied draws: {u_flag, u_pick} pairs (multinomial) then the random-pose pool, in one upload
-  const size_t u_doubles = (!dev && !sys) ? (size_t)count * ms * 2 : 0, bytes = sizeof(double) * (u_doubles + 3 * pool_total);
-  r.u = nullptr;
-  r.pool = nullptr;
-  if (bytes) {
-    if (bytes > h->upload_bytes) {
-      if (h->d_upload) hipFree(h->d_upload);
-      h->d_upload = nullptr;
-      h->upload_bytes = 0;
-      HIP_TRY(hipMalloc(&h->d_upload, bytes));
-      h->upload_bytes = bytes;
-    }
-    double* up = static_cast<double*>(h->d_upload);
-    if (u_doubles) HIP_TRY(hipMemcpyAsync(up, u, sizeof(double) * u_doubles, hipMemcpyHostToDevice, h->stream));
-    if (pool_total)
-      HIP_TRY(hipMemcpyAsync(up + u_doubles, random_poses, sizeof(double) * 3 * pool_total, hipMemcpyHostToDevice, h->stream));
-    r.u = up;
-    r.pool = up + u_doubles;
-  }
-  std::vector<AmclResampleFilterDev> fd(count);
-  uint64_t pool_off = 0;
-  for (uint32_t k = 0; k < count; ++k) {
-    AmclResampleFilterDev& e = fd[k];
-    const uint32_t f = first + k;
-    e.sample_count = h->sample_count[f];
-    e.leaf_in = h->leaf[f];
-    e.pool_count = dev ? 0 : (int32_t)random_pose_counts[k];
-    e.pool_off = pool_off;
-    pool_off += dev ? 0 : random_pose_counts[k];
-    e.rng_ctr = h->rng_ctr[f];
-    e.sys_start = (!dev && sys) ? systematic_start[k] : 0.0;
-    e.active = 1;
-    e.status = NAVGPU_ERR_INVALID;
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_rfilters, fd.data(), sizeof(AmclResampleFilterDev) * count, hipMemcpyHostToDevice, h->stream));
-  const AmclResampleParamsDev P{R.resample_model, R.min_samples, (int32_t)ms, dev ? 1 : 0, R.pop_err, R.pop_z, R.dist_threshold, seed};
-  launch_amcl_resample(h->d, r, P, first, count, h->d_rfilters, h->stream);
-  const int lrc = checkLaunch();
-  if (lrc) return lrc;
-  HIP_TRY(hipMemcpyAsync(fd.data(), h->d_rfilters, sizeof(AmclResampleFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
+  AmclResampleCall c;
+  if (int lrc = amclResampleEnqueue(h, first, count, dev, u, systematic_start, random_poses, random_pose_counts, pool_total, seed, nullptr, c))
+    return lrc;
+  HIP_TRY(hipMemcpyAsync(c.fd.data(), h->d_rfilters, sizeof(AmclResampleFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(waitStream(h->stream));
-  int rc = NAVGPU_OK;
-  for (uint32_t k = 0; k < count; ++k) {
-    const uint32_t f = first + k;
-    const AmclResampleFilterDev& e = fd[k];
-    status[k] = e.status;
-    if (dev) ++h->rng_ctr[f];
-    if (e.status != NAVGPU_OK) {
-      rc = NAVGPU_ERR_INVALID;
-      g_last_error = "navgpu_amcl_update_resample: a filter has no samples, too few supplied random poses, no free cell or a pose "
-                     "outside the histogram's range";
-      continue;
-    }
-    h->sample_count[f] = e.count;
-    h->leaf[f] = e.leaf_out;
-    h->converged[f] = e.converged;
-    h->cluster_count[f] = e.cluster_count;
-  }
-  return rc;
+  return amclResampleCommit(h, first, count, status, c);
 }
 
 int navgpu_amcl_get_clusters(navgpu_amcl* h, uint32_t filter, int32_t* cluster_count, uint32_t capacity, int32_t* counts, double* weights,
@@ -689,17 +684,9 @@ int navgpu_amcl_get_clusters(navgpu_amcl* h, uint32_t filter, int32_t* cluster_c
 }  // extern "C"
 
 namespace {
-// amcl_odom.cpp's normalize / angle_diff (:35-56), evaluated with the host's libm as the reference evaluates them
-double normalizeAngle(double z) { return atan2(sin(z), cos(z)); }
-double angleDiff(double a, double b) {
-  a = normalizeAngle(a);
-  b = normalizeAngle(b);
-  const double d1 = a - b;
-  double d2 = 2 * M_PI - fabs(d1);
-  if (d1 > 0) d2 *= -1.0;
-  if (fabs(d1) < fabs(d2)) return d1;
-  return d2;
-}
+// amcl_odom.cpp's normalize / angle_diff (:35-56): navgpu_amcl_host.h
+double normalizeAngle(double z) { return amclNormalizeAngle(z); }
+double angleDiff(double a, double b) { return amclAngleDiff(a, b); }
 
 // What AMCLOdom::UpdateAction computes from the odometry alone (amcl_odom.cpp:128-379), in its own expressions; the per-particle
 // part is k_amcl_odom.  The diff models evaluate their stddevs inside the sample loop: the same value for every sample.
@@ -807,40 +794,12 @@ int navgpu_amcl_update_action(navgpu_amcl* h, uint32_t first, uint32_t count, co
     g_last_error = "navgpu_amcl_update_action before navgpu_amcl_odom_configure";
     return NAVGPU_ERR_STATE;
   }
-  std::vector<AmclOdomFilterDev> fd(count);
-  int rc = NAVGPU_OK, max_count = 0;
-  for (uint32_t k = 0; k < count; ++k) {
-    AmclOdomFilterDev& e = fd[k];
-    const uint32_t f = first + k;
-    e.sample_count = h->sample_count[f];
-    e.active = 1;
-    e.state = dev ? 0 : drand48_state[k];
-    e.rng_ctr = h->rng_ctr[f];
-    odomConstants(h->oparams, odom + 9 * (size_t)k, e.k);
-    status[k] = NAVGPU_OK;
-    if (!dev && drand48_state[k] > kAmclDrand48Mask) {
-      e.active = 0;
-      status[k] = NAVGPU_ERR_INVALID;
-      rc = NAVGPU_ERR_INVALID;
-      g_last_error = "navgpu_amcl_update_action: a drand48 state >= 2^48";
-      continue;
-    }
-    max_count = std::max(max_count, e.sample_count);
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_ofilters, fd.data(), sizeof(AmclOdomFilterDev) * count, hipMemcpyHostToDevice, h->stream));
-  if (!dev) launch_amcl_drand48_gauss(h->d_records, h->d.max_samples, count, h->d_ofilters, h->stream);
-  launch_amcl_odom(h->d, h->oparams.model_type, dev ? 1 : 0, seed, h->d_records, first, count, max_count, h->d_ofilters, h->stream);
-  const int lrc = checkLaunch();
-  if (lrc) return lrc;
-  if (!dev) HIP_TRY(hipMemcpyAsync(fd.data(), h->d_ofilters, sizeof(AmclOdomFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
+  AmclActionCall c;
+  if (int lrc = amclActionEnqueue(h, first, count, odom, dev, drand48_state, seed, status, nullptr, c)) return lrc;
+  if (!dev) HIP_TRY(hipMemcpyAsync(c.fd.data(), h->d_ofilters, sizeof(AmclOdomFilterDev) * count, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(waitStream(h->stream));
-  for (uint32_t k = 0; k < count; ++k) {
-    if (dev)
-      ++h->rng_ctr[first + k];
-    else if (fd[k].active)
-      drand48_state[k] = fd[k].state;
-  }
-  return rc;
+  amclActionCommit(h, first, count, drand48_state, c);
+  return c.soft;
 }
 
 }  // extern "C"

@@ -10,6 +10,8 @@
 // set_stats double [n][12] {mean[3], cov[9]}.
 // The motion model (amcl_motion_kernels.hip) adds, in drand48 mode, a record workspace: double2 [n][3 max_samples] {x2, s}.
 // The init (amcl_init_kernels.hip) uses the resampling workspace and, for the Gaussian in drand48 mode, the record workspace.
+// The node cycle (amcl_node_kernels.hip) adds per-filter scan and hypothesis records (AmclScanDev, AmclHypDev [n]) and the raw
+// float ranges of the last call; its beams go into the sensor update's beam buffer.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -175,6 +177,35 @@ struct AmclInitParamsDev {
 void launch_amcl_init(const AmclDev& d, const AmclResampleDev& r, const AmclInitParamsDev& p, const navgpu_amcl_laser_params& P,
                       const double* beams, int max_n_beams, double2* records, uint32_t first, uint32_t count, AmclInitFilterDev* filters,
                       hipStream_t s);
+
+// AmclNode's laser cycle (amcl_node_kernels.hip).  One filter's LaserScan as amcl_node.cpp:1505-1537 reads it; filter k of the
+// slice writes its subsampled beams where its AmclFilterDev says (beam_off, n_beams)
+struct AmclScanDev {
+  int32_t active;        // 0: the filter is skipped
+  int32_t step;          // the model's subsampling step (>= 1 for an active filter)
+  uint32_t range_off;    // first raw range of this filter
+  int32_t range_count;
+  double range_min, range_max;  // the float thresholds of :1514-1522, widened
+  double angle_min, angle_inc;  // :1505-1509
+};
+// One filter's hypothesis read-out (amcl_node.cpp:1584-1651)
+struct AmclHypDev {
+  // in
+  int32_t active;
+  int32_t cluster_count;   // the set's cluster count as the host knows it
+  int32_t from_resample;   // 1: this call's resample record of the filter holds the count when its status is NAVGPU_OK
+  // out
+  int32_t clusters;        // the count that was read
+  int32_t max_weight_hyp;  // -1: no cluster with weight > 0
+  int32_t pad;
+  double max_weight;
+  double pose[3];          // hyps[max_weight_hyp].pf_pose_mean
+  double cov[5];           // set->cov.m[0][0], [0][1], [1][0], [1][1], [2][2]
+};
+void launch_amcl_scan(const AmclDev& d, uint32_t first, uint32_t count, const AmclFilterDev* filters, const AmclScanDev* scans,
+                      const float* raw, double* beams, hipStream_t s);
+void launch_amcl_hypothesis(const AmclResampleDev& r, uint32_t max_samples, uint32_t first, uint32_t count,
+                            const AmclResampleFilterDev* rfilters, AmclHypDev* hyps, hipStream_t s);
 
 void launch_amcl_convert(const int8_t* msg, uint32_t width, uint32_t height, int factor, int8_t* occ, int sx, int sy, hipStream_t s);
 void launch_amcl_cspace(const int8_t* occ, int sx, int sy, int radius, double scale, double max_occ_dist, int32_t* g, float* dist,

@@ -12,6 +12,10 @@
   update_action      AMCLOdom::UpdateAction -> pf_update_action: the odometry motion model (amcl_odom.cpp:128-379)
   init_gaussian      pf_init: a Gaussian set                             (pf.c:138-176)
   init_uniform       pf_init_model with AmclNode::uniformPoseGenerator (global localisation, amcl_node.cpp:1200-1263)
+  configure_node     AmclNode's update_min_d / update_min_a / resample_interval / laser range overrides / odom integrator
+  laser_received     AmclNode::laserReceived for the fleet, one call per scan                (amcl_node.cpp:1381-1756)
+  hypotheses         the hypothesis read-out alone                                           (amcl_node.cpp:1584-1651)
+  node_reset, request_nomotion_update, integrate_odom, node_state, set_node_state: the node's state between scans
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers.
 """
 import ctypes as C
@@ -19,11 +23,15 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import (AMCL_DRAW_DEVICE, AMCL_DRAW_DRAND48, AMCL_DRAW_SUPPLIED, AMCL_RESAMPLE_SYSTEMATIC, AmclLaserParams, AmclOdomParams,
-                   AmclResampleParams, AmclUniformParams, check, lib)
+from ._lib import (AMCL_DRAW_DEVICE, AMCL_DRAW_DRAND48, AMCL_DRAW_SUPPLIED, AMCL_RESAMPLE_SYSTEMATIC, AMCL_SCAN_PRESENT, AmclLaserParams,
+                   AmclNodeParams, AmclNodeResult, AmclNodeState, AmclOdomParams, AmclResampleParams, AmclScan, AmclUniformParams, check,
+                   lib)
 
 # pf_sample_set_t's clusters and overall statistics: count (C,), weight (C,), mean (C, 3), cov (C, 3, 3), set_mean (3,), set_cov (3, 3)
 AmclClusters = namedtuple("AmclClusters", "count weight mean cov set_mean set_cov")
+# numpy layouts of navgpu_amcl_node_result / navgpu_amcl_node_state, taken from their ctypes mirrors
+NODE_RESULT_DTYPE = np.dtype(AmclNodeResult)
+NODE_STATE_DTYPE = np.dtype(AmclNodeState)
 
 
 def _p(a):
@@ -293,6 +301,77 @@ class AmclLaser:
         if raise_on_error:
             check(rc, "amcl_init_uniform")
         return rc, st, x, used
+
+    # ---- AmclNode::laserReceived for the fleet (navgpu_amcl_node_*) ----
+    def configure_node(self, params=None, **kw):
+        """navgpu_amcl_node_params fields: d_thresh, a_thresh, laser_min_range, laser_max_range, resample_interval,
+        use_odom_integrator."""
+        p = params if params is not None else AmclNodeParams(**kw)
+        check(self.L.navgpu_amcl_node_configure(self.h, C.byref(p)), "amcl_node_configure")
+        self.node_params = p
+        return p
+
+    def laser_received(self, scans, seed=0, first=0, raise_on_error=True):
+        """AmclNode::laserReceived for the filters first .. first + len(scans) - 1.  scans: one entry per filter, None (no scan for
+        this filter in this call) or a dict with ranges (the raw LaserScan::ranges), range_min, range_max, yaw_min, yaw_inc (the two
+        tf::getYaw results of amcl_node.cpp:1505-1506) and odom_pose (x, y, yaw).
+        -> (status, a numpy record array with navgpu_amcl_node_result's fields, one record per filter)"""
+        count = len(scans)
+        recs = (AmclScan * count)()
+        parts, off = [], 0
+        for k, s in enumerate(scans):
+            if s is None:
+                continue
+            r = np.ascontiguousarray(s["ranges"], np.float32).ravel()
+            recs[k].flags = AMCL_SCAN_PRESENT
+            recs[k].range_count = len(r)
+            recs[k].range_offset = off
+            recs[k].range_min = s["range_min"]
+            recs[k].range_max = s["range_max"]
+            recs[k].yaw_min = s["yaw_min"]
+            recs[k].yaw_inc = s["yaw_inc"]
+            recs[k].odom_pose = tuple(float(v) for v in s["odom_pose"])
+            parts.append(r)
+            off += len(r)
+        raw = np.ascontiguousarray(np.concatenate(parts) if off else np.zeros(1), np.float32)
+        out = np.zeros(count, NODE_RESULT_DTYPE)
+        rc = self.L.navgpu_amcl_node_laser_received(self.h, first, count, C.byref(recs), _p(raw), int(seed) & (2 ** 64 - 1), _p(out))
+        if raise_on_error:
+            check(rc, "amcl_node_laser_received")
+        return rc, out.view(np.recarray)
+
+    def hypotheses(self, first=0, count=None):
+        """The hypothesis read-out (amcl_node.cpp:1584-1651) of every filter of the slice, from the clusters the last resample or
+        init left -> a numpy record array (cluster_count, max_weight_hyp, max_weight, published, pose, cov_*, sample_count,
+        converged; the other fields 0)."""
+        count = self._count(first, count)
+        out = np.zeros(count, NODE_RESULT_DTYPE)
+        check(self.L.navgpu_amcl_hypotheses(self.h, first, count, _p(out)), "amcl_hypotheses")
+        return out.view(np.recarray)
+
+    def node_reset(self, global_localization=False, first=0, count=None):
+        """After an init the caller made itself: pf_init_ = false, global_localization_active_ = global_localization."""
+        check(self.L.navgpu_amcl_node_reset(self.h, first, self._count(first, count), int(bool(global_localization))), "amcl_node_reset")
+
+    def request_nomotion_update(self, first=0, count=None):
+        check(self.L.navgpu_amcl_node_request_nomotion_update(self.h, first, self._count(first, count)),
+              "amcl_node_request_nomotion_update")
+
+    def integrate_odom(self, poses, first=0):
+        """AmclNode::integrateOdom for one odometry message per filter of the slice; poses: (count, 3) {x, y, yaw}."""
+        a = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        check(self.L.navgpu_amcl_node_integrate_odom(self.h, first, len(a), _p(a)), "amcl_node_integrate_odom")
+
+    def node_state(self, first=0, count=None):
+        """-> a numpy record array with navgpu_amcl_node_state's fields, one record per filter (a copy)"""
+        count = self._count(first, count)
+        out = np.zeros(count, NODE_STATE_DTYPE)
+        check(self.L.navgpu_amcl_node_get_state(self.h, first, count, _p(out)), "amcl_node_get_state")
+        return out.view(np.recarray)
+
+    def set_node_state(self, states, first=0):
+        a = np.ascontiguousarray(states, NODE_STATE_DTYPE).ravel()
+        check(self.L.navgpu_amcl_node_set_state(self.h, first, len(a), _p(a)), "amcl_node_set_state")
 
     @staticmethod
     def _draws(drand48_state, seed, count):
