@@ -408,6 +408,32 @@ int navgpu_planner_check_trajectory(navgpu_fleet* fleet, uint32_t instance, cons
 int navgpu_planner_check_trajectories(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances,
                                       const uint32_t* probe_offsets /* n_robots + 1 */, const float* vel_samples /* 3 per probe */,
                                       int32_t* ok /* per probe */, double* costs /* per probe, may be NULL */);
+/* The planner cycle for a robot LIST: navgpu_planner_stage / _stage_poses / _cycle / _results for the robots instances[0 .. n_robots),
+ * strictly increasing absolute robot indices, each < n_instances, 1 <= n_robots <= n_instances (the conventions of
+ * navgpu_planner_check_trajectories); anything else is NAVGPU_ERR_INVALID with nothing changed.  Per-robot arrays are indexed by
+ * list position k.  In a fleet the robots inside their goal tolerance are scattered among the driving ones; a list costs one
+ * launch of each kernel of the cycle whatever it looks like, where contiguous ranges cost a stage, a cycle and a wait per run.
+ * Contract: the listed robots end up as if every contiguous run of the list had been handed to the range calls in turn - nothing
+ * in the cycle reduces across robots, so that is bit equality - and every robot outside the list keeps result, trajectory,
+ * sample costs, oscillation flags, MapGrids, wavefront levels and boxes and trajectory-cloud records as they were.
+ * replaces (per listed robot), as the range forms do:
+ *   _stage_list        DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:240-286); states[k].plan_first / plan_count index
+ *                      plan_xy as in navgpu_planner_stage.  Same validation, all or nothing (plan_count 0: NAVGPU_ERR_INVALID, above
+ *                      max_plan: NAVGPU_ERR_CAPACITY).  One packed upload - the records and only the poses in use - and one scatter
+ *                      kernel (k_stage_scatter).
+ *   _stage_poses_list  the pose-only stage of a cycle whose plans have not changed (pos_xyth, vel_xyth = n_robots x 3 floats);
+ *                      NAVGPU_ERR_STATE naming the robot when a listed robot has no staged plan.
+ *   _cycle_list        dwaComputeVelocityCommands' planner call (dwa_planner_ros.cpp:176-247) = DWAPlanner::findBestPath
+ *                      (dwa_planner.cpp:292-371) per listed robot.  NAVGPU_ERR_STATE before configure / stage, and with two cycles
+ *                      in flight (navgpu_planner_set_cycles_in_flight(f, 2) takes whole-fleet range cycles only).  An enabled
+ *                      trajectory-cloud robot gets its terms pass when it is in the list, and only then.
+ *   _results_list      one wait; results[k] is the result of instances[k]. */
+int navgpu_planner_stage_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_state* states,
+                              const double* plan_xy, uint32_t n_plan_total);
+int navgpu_planner_stage_poses_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth,
+                                    const float* vel_xyth);
+int navgpu_planner_cycle_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances);
+int navgpu_planner_results_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, navgpu_plan_result* results);
 /* replaces: DWAPlanner::getCellCosts (dwa_planner.cpp:185-202) over the whole map + MapGridVisualizer::publishCostCloud
  * (base_local_planner/src/map_grid_visualizer.cpp:55-83): the cost cloud of one instance from the grids of its last
  * cycle.  points = up to `capacity` x {x, y, z, path_cost, goal_cost, occ_cost, total_cost} (MapGridCostPoint), in the

@@ -505,6 +505,10 @@ SYMBOLS = [
     ("navgpu_planner_samples", C.c_int, [vp, u32, vp, vp, vp, u32]),
     ("navgpu_planner_check_trajectory", C.c_int, [vp, u32, vp, C.POINTER(i32)]),
     ("navgpu_planner_check_trajectories", C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
+    ("navgpu_planner_stage_list", C.c_int, [vp, u32, vp, vp, vp, u32]),
+    ("navgpu_planner_stage_poses_list", C.c_int, [vp, u32, vp, vp, vp]),
+    ("navgpu_planner_cycle_list", C.c_int, [vp, u32, vp]),
+    ("navgpu_planner_results_list", C.c_int, [vp, u32, vp, vp]),
     ("navgpu_planner_cost_cloud", C.c_int, [vp, u32, vp, u32]),
     ("navgpu_planner_set_trajectory_cloud", C.c_int, [vp, u32, u32, i32]),
     ("navgpu_planner_trajectory_cloud", C.c_int, [vp, u32, i32, vp, u32]),

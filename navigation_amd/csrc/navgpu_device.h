@@ -338,6 +338,28 @@ struct PoseChunk {
 };
 static_assert(sizeof(PoseChunk) <= 4096, "kernel arguments are limited to 4 KB");
 void launch_stage_poses(const PoseChunk& c, hipStream_t s);
+// ---- the cycle for a robot list (navgpu_planner_*_list): robot k of a launch is list[k], a device array, strictly increasing.
+// Weak for the reason launch_check_traj is: navgpu_host.cpp is also linked against a stand-in for the kernels that knows the
+// launchers of its day (tests/tsan); there the listed calls answer NAVGPU_ERR_STATE.  libnavgpu.so always carries the launchers.
+struct PoseChunkList : PoseChunk {  // `first` unused: entry li belongs to robot inst[li]
+  uint32_t inst[kPoseChunk];
+};
+static_assert(sizeof(PoseChunkList) <= 4096, "kernel arguments are limited to 4 KB");
+struct StageRec {  // navgpu_planner_stage_list's record of one robot, as uploaded
+  navgpu_robot_state st;
+  double front[2];    // nose goal
+  int32_t align;      // alignment switch
+  uint32_t reach;     // wavefront box half edge
+  uint32_t inst;      // the robot
+  uint32_t plan_off;  // its first pose among the upload's packed poses
+};
+static_assert(sizeof(StageRec) == 64, "staged as an array of these in front of the poses");
+__attribute__((weak)) void launch_stage_poses_list(const PoseChunkList& c, hipStream_t s);
+__attribute__((weak)) void launch_stage_scatter(const PlannerDev& pl, const StageRec* rec, const double* poses, uint32_t n_robots, hipStream_t s);
+__attribute__((weak)) void launch_samples_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);
+__attribute__((weak)) void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order);
+__attribute__((weak)) uint32_t launch_score_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);  // returns blocks per instance
+__attribute__((weak)) void launch_select_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, uint32_t n_blocks, hipStream_t s);
 void launch_sincos(const double* th, uint32_t n, double* sn, double* cs, hipStream_t s);
 // ---- device-resident global plans (local_plan_kernels.hip): LocalPlannerUtil::getLocalPlan per robot and cycle
 constexpr uint32_t kPlanWindowThreads = 256;

@@ -48,6 +48,8 @@ int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const doubl
 // navgpu_planner_stage_poses without its "a plan was staged" check: for robots whose plan is on the device and whose length and last
 // point the pinned mirrors hold (navgpu_host.cpp)
 int stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth);
+// the same for the robots instances[0 .. n_robots) of a valid list (navgpu_planner_stage_poses_list without its check)
+int stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth, const float* vel_xyth);
 // device-resident global plans (navgpu_resident_plan.cpp), for the handover of navgpu_move_base.cpp: wait until the last adoption's
 // copies out of ResidentPlans::h_off have run; a robot's slot has just taken a new plan of len poses (DWAPlannerROS::setPlan's host side)
 int waitAdoption(navgpu_fleet* f);
@@ -270,6 +272,14 @@ struct navgpu_fleet {
     uint32_t *d_in = nullptr, *h_in = nullptr;    // [n] instances, [n + 1] offsets, [cap][3] samples (floats)
     double *d_cost = nullptr, *h_cost = nullptr;  // [cap]
   } pb;
+  // the planner cycle for a robot list (navgpu_planner_*_list), allocated by the first listed call, sized for the whole fleet:
+  // the list the cycle's kernels read, and navgpu_planner_stage_list's packed upload - a pinned block and its device twin
+  struct CycleList {
+    uint32_t *d_list = nullptr, *h_list = nullptr;  // [n]
+    hipEvent_t ev_list = nullptr;                   // behind the copy out of h_list
+    bool ev_set = false;
+    uint8_t *d_stage = nullptr, *h_stage = nullptr; // [n] StageRec, then [n][max_plan][2] doubles (only the poses in use travel)
+  } cl;
   std::vector<uint8_t> obs_consumed;            // [n] an update has run on what navgpu_costmap_stage staged last
   navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers

@@ -278,7 +278,7 @@ int navgpu_fleet_destroy(navgpu_fleet* f) {
     hipEventDestroy(e.a);
     hipEventDestroy(e.b);
   }
-  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav})
+  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.ev_list})
     if (e) hipEventDestroy(e);
   for (void* p : f->allocs) hipFree(p);
   for (void* p : f->pinned) hipHostFree(p);
@@ -1275,35 +1275,43 @@ int navgpu_planner_set_plan(navgpu_fleet* f, uint32_t first, uint32_t count) {
   return NAVGPU_OK;
 }
 
-int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, const double* plan_xy,
-                         uint32_t n_plan_total) {
-  if (!f || !states || !plan_xy || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
-  if (!f->planner_configured) return NAVGPU_ERR_STATE;
-  PlannerDev& pl = f->pl;
-  const navgpu_dwa_config& c = pl.cfg;
+// what a stage call checks of the states before it changes anything (navgpu_planner_stage, navgpu_planner_stage_list)
+static int checkStageStates(const PlannerDev& pl, uint32_t count, const navgpu_robot_state* states, uint32_t n_plan_total) {
   for (uint32_t li = 0; li < count; ++li) {
     const navgpu_robot_state& s = states[li];
     if (s.plan_count == 0) return NAVGPU_ERR_INVALID;  // the ROS wrapper rejects empty plans before this point
     if (s.plan_count > pl.max_plan) return NAVGPU_ERR_CAPACITY;
     if ((uint64_t)s.plan_first + s.plan_count > n_plan_total) return NAVGPU_ERR_INVALID;
   }
+  return NAVGPU_OK;
+}
+// robot i's pinned mirrors from its staged state and plan
+static void stageMirrors(navgpu_fleet* f, uint32_t i, const navgpu_robot_state& s, const double* plan_xy) {
+  const PlannerDev& pl = f->pl;
+  const navgpu_dwa_config& c = pl.cfg;
+  f->hp_state[i] = s;
+  memcpy(&f->hp_plan[(size_t)i * pl.max_plan * 2], plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
+  f->hp_plan_cnt[i] = s.plan_count;
+  // DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285); pos is the float-narrowed pose
+  const double gx = plan_xy[((size_t)s.plan_first + s.plan_count - 1) * 2], gy = plan_xy[((size_t)s.plan_first + s.plan_count - 1) * 2 + 1];
+  const double sq_dist = (s.pos[0] - gx) * (s.pos[0] - gx) + (s.pos[1] - gy) * (s.pos[1] - gy);
+  const double angle_to_goal = atan2(gy - s.pos[1], gx - s.pos[0]);
+  f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
+  f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
+  f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
+  f->hp_reach[i] = bfsReachCells(f, s, gx, gy);
+}
+
+int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, const double* plan_xy,
+                         uint32_t n_plan_total) {
+  if (!f || !states || !plan_xy || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->planner_configured) return NAVGPU_ERR_STATE;
+  PlannerDev& pl = f->pl;
+  int rc = checkStageStates(pl, count, states, n_plan_total);
+  if (rc != NAVGPU_OK) return rc;
   HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));  // the pinned mirrors may still feed an earlier copy
-  for (uint32_t li = 0; li < count; ++li) {
-    const uint32_t i = first + li;
-    const navgpu_robot_state& s = states[li];
-    f->hp_state[i] = s;
-    memcpy(&f->hp_plan[(size_t)i * pl.max_plan * 2], plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
-    f->hp_plan_cnt[i] = s.plan_count;
-    // DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285); pos is the float-narrowed pose
-    const double gx = plan_xy[((size_t)s.plan_first + s.plan_count - 1) * 2], gy = plan_xy[((size_t)s.plan_first + s.plan_count - 1) * 2 + 1];
-    const double sq_dist = (s.pos[0] - gx) * (s.pos[0] - gx) + (s.pos[1] - gy) * (s.pos[1] - gy);
-    const double angle_to_goal = atan2(gy - s.pos[1], gx - s.pos[0]);
-    f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
-    f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
-    f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
-    f->hp_reach[i] = bfsReachCells(f, s, gx, gy);
-  }
+  for (uint32_t li = 0; li < count; ++li) stageMirrors(f, first + li, states[li], plan_xy);
   f->touchInputs(first, count);
   if (first == 0 && count == f->desc.n_instances) {  // the whole fleet: one copy of the block
     HIP_TRY(hipMemcpyAsync(f->pl_stage_dev, f->pl_stage_host, f->pl_stage_bytes, hipMemcpyHostToDevice, f->stream));
@@ -1324,6 +1332,73 @@ int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
   return NAVGPU_OK;
 }
 
+// ---- the cycle for a robot list: instances[0 .. n_robots) strictly increasing, each < n_instances (navgpu_planner_check_trajectories'
+// conventions)
+static bool listOk(const navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances) {
+  if (!n_robots || !instances || n_robots > f->desc.n_instances) return false;
+  for (uint32_t k = 0; k < n_robots; ++k)
+    if (instances[k] >= f->desc.n_instances || (k && instances[k] <= instances[k - 1])) return false;
+  return true;
+}
+// the buffers of the listed calls, all or none
+static int reserveCycleList(navgpu_fleet* f) {
+  navgpu_fleet::CycleList& cl = f->cl;
+  if (cl.d_list) return NAVGPU_OK;
+  const uint32_t n = f->desc.n_instances;
+  const size_t stage_bytes = (size_t)n * (sizeof(StageRec) + sizeof(double) * 2 * f->pl.max_plan);
+  navgpu_fleet::CycleList nl;
+  int rc = f->alloc(&nl.d_list, n);
+  if (!rc) rc = f->alloc(&nl.d_stage, stage_bytes);
+  if (!rc) rc = f->allocPinned(&nl.h_list, n);
+  if (!rc) rc = f->allocPinned(&nl.h_stage, stage_bytes);
+  if (!rc && hipEventCreateWithFlags(&nl.ev_list, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
+  if (rc) {
+    f->release(nl.d_list);
+    f->release(nl.d_stage);
+    f->releasePinned(nl.h_list);
+    f->releasePinned(nl.h_stage);
+    return rc;
+  }
+  cl = nl;
+  return NAVGPU_OK;
+}
+
+int navgpu_planner_stage_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_state* states,
+                              const double* plan_xy, uint32_t n_plan_total) {
+  if (!f || !states || !plan_xy || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->planner_configured || !launch_stage_scatter) return NAVGPU_ERR_STATE;
+  PlannerDev& pl = f->pl;
+  int rc = checkStageStates(pl, n_robots, states, n_plan_total);
+  if (rc == NAVGPU_OK) rc = reserveCycleList(f);
+  if (rc != NAVGPU_OK) return rc;
+  // the pinned mirrors may still feed an earlier copy, and so may the packed block (the marker of two cycles in flight is recorded
+  // behind its copy as well)
+  HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
+  StageRec* rec = reinterpret_cast<StageRec*>(f->cl.h_stage);
+  double* poses = reinterpret_cast<double*>(f->cl.h_stage + sizeof(StageRec) * n_robots);
+  uint32_t n_poses = 0;
+  for (uint32_t k = 0; k < n_robots; ++k) {
+    const uint32_t i = instances[k];
+    const navgpu_robot_state& s = states[k];
+    stageMirrors(f, i, s, plan_xy);
+    f->touchInputs(i, 1);
+    rec[k] = StageRec{s, {f->hp_front[2 * i], f->hp_front[2 * i + 1]}, f->hp_align[i], f->hp_reach[i], i, n_poses};
+    memcpy(poses + 2 * (size_t)n_poses, plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
+    n_poses += s.plan_count;  // (<= n_instances * max_plan: the block holds them)
+  }
+  const size_t bytes = sizeof(StageRec) * n_robots + sizeof(double) * 2 * (size_t)n_poses;
+  HIP_TRY(hipMemcpyAsync(f->cl.d_stage, f->cl.h_stage, bytes, hipMemcpyHostToDevice, f->stream));
+  launch_stage_scatter(pl, reinterpret_cast<const StageRec*>(f->cl.d_stage), reinterpret_cast<const double*>(f->cl.d_stage + sizeof(StageRec) * n_robots),
+                       n_robots, f->stream);
+  if (f->cycles_in_flight > 1) {
+    HIP_TRY(hipEventRecord(f->ev_pl_h2d, f->stream));
+    f->ev_pl_set = true;
+  }
+  f->planner_staged = true;
+  return checkLaunch();
+}
+
 // A control cycle whose plan has not changed (the plan arrives at ~1 Hz, the pose at controller_frequency): only pose and
 // velocity are staged, 24 B per robot; the nose goal, the alignment switch and the wavefront box are re-derived from the
 // resident plan exactly as navgpu_planner_stage derives them.  The values travel as kernel arguments (k_stage_poses): the call
@@ -1337,10 +1412,28 @@ int navgpu_planner_stage_poses(navgpu_fleet* f, uint32_t first, uint32_t count, 
 // The body of navgpu_planner_stage_poses, also what the control cycle runs for robots whose window k_plan_window has just left on the
 // device.  Precondition, checked here: every robot of the range has a plan on the device whose length and last point the pinned
 // mirrors (hp_plan_cnt, hp_plan) hold - after navgpu_planner_stage, or written from k_plan_window's records.
+// robot i's pinned mirrors from a new pose and velocity and the last point of its resident plan
+static void poseMirrors(navgpu_fleet* f, uint32_t i, const float pos[3], const float vel[3]) {
+  const PlannerDev& pl = f->pl;
+  const navgpu_dwa_config& c = pl.cfg;
+  navgpu_robot_state& s = f->hp_state[i];
+  for (int k = 0; k < 3; ++k) {
+    s.pos[k] = pos[k];
+    s.vel[k] = vel[k];
+  }
+  const double* last = &f->hp_plan[((size_t)i * pl.max_plan + f->hp_plan_cnt[i] - 1) * 2];
+  const double gx = last[0], gy = last[1];
+  // DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285), as in navgpu_planner_stage
+  const double sq_dist = (s.pos[0] - gx) * (s.pos[0] - gx) + (s.pos[1] - gy) * (s.pos[1] - gy);
+  const double angle_to_goal = atan2(gy - s.pos[1], gx - s.pos[0]);
+  f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
+  f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
+  f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
+  f->hp_reach[i] = bfsReachCells(f, s, gx, gy);
+}
 extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth) {
   if (!f->planner_configured) return NAVGPU_ERR_STATE;
   PlannerDev& pl = f->pl;
-  const navgpu_dwa_config& c = pl.cfg;
   for (uint32_t i = first; i < first + count; ++i)
     if (!f->hp_plan_cnt[i]) {
       g_last_error = "navgpu_planner_stage_poses: instance " + std::to_string(i) + " has no staged plan";
@@ -1350,23 +1443,7 @@ extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, 
     HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
     f->hp_dma_pending = false;
   }
-  for (uint32_t li = 0; li < count; ++li) {
-    const uint32_t i = first + li;
-    navgpu_robot_state& s = f->hp_state[i];
-    for (int k = 0; k < 3; ++k) {
-      s.pos[k] = pos_xyth[3 * li + k];
-      s.vel[k] = vel_xyth[3 * li + k];
-    }
-    const double* last = &f->hp_plan[((size_t)i * pl.max_plan + f->hp_plan_cnt[i] - 1) * 2];
-    const double gx = last[0], gy = last[1];
-    // DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285), as in navgpu_planner_stage
-    const double sq_dist = (s.pos[0] - gx) * (s.pos[0] - gx) + (s.pos[1] - gy) * (s.pos[1] - gy);
-    const double angle_to_goal = atan2(gy - s.pos[1], gx - s.pos[0]);
-    f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
-    f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
-    f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
-    f->hp_reach[i] = bfsReachCells(f, s, gx, gy);
-  }
+  for (uint32_t li = 0; li < count; ++li) poseMirrors(f, first + li, pos_xyth + 3 * (size_t)li, vel_xyth + 3 * (size_t)li);
   f->touchInputs(first, count);
   PoseChunk ch;
   ch.state = pl.state;
@@ -1383,6 +1460,50 @@ extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, 
     launch_stage_poses(ch, f->stream);
   }
   f->planner_staged = true;  // (the device holds a staged state for these robots, however their windows got there)
+  return checkLaunch();
+}
+int navgpu_planner_stage_poses_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth, const float* vel_xyth) {
+  if (!f || !pos_xyth || !vel_xyth || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->planner_configured || !f->planner_staged) return NAVGPU_ERR_STATE;
+  return stagePosesListFromMirrors(f, n_robots, instances, pos_xyth, vel_xyth);
+}
+// stagePosesFromMirrors for a list: the same precondition per listed robot, a chunk entry names its robot
+extern "C++" int navgpu::stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth,
+                                                   const float* vel_xyth) {
+  if (!f->planner_configured || !launch_stage_poses_list) return NAVGPU_ERR_STATE;
+  PlannerDev& pl = f->pl;
+  for (uint32_t k = 0; k < n_robots; ++k)
+    if (!f->hp_plan_cnt[instances[k]]) {
+      g_last_error = "navgpu_planner_stage_poses_list: instance " + std::to_string(instances[k]) + " has no staged plan";
+      return NAVGPU_ERR_STATE;
+    }
+  if (f->hp_dma_pending) {  // the host mirrors written below may still feed a full stage's copies
+    HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
+    f->hp_dma_pending = false;
+  }
+  PoseChunkList ch;
+  ch.state = pl.state;
+  ch.front_last = pl.front_last;
+  ch.align_on = pl.align_on;
+  ch.bfs_reach = pl.bfs_reach;
+  ch.first = 0;
+  for (uint32_t at = 0; at < n_robots; at += kPoseChunk) {
+    ch.count = std::min(kPoseChunk, n_robots - at);
+    for (uint32_t q = 0; q < ch.count; ++q) {
+      const uint32_t i = instances[at + q];
+      poseMirrors(f, i, pos_xyth + 3 * (size_t)(at + q), vel_xyth + 3 * (size_t)(at + q));
+      f->touchInputs(i, 1);
+      ch.inst[q] = i;
+      ch.st[q] = f->hp_state[i];
+      ch.front[2 * q] = f->hp_front[2 * i];
+      ch.front[2 * q + 1] = f->hp_front[2 * i + 1];
+      ch.align[q] = f->hp_align[i];
+      ch.reach[q] = f->hp_reach[i];
+    }
+    launch_stage_poses_list(ch, f->stream);
+  }
+  f->planner_staged = true;
   return checkLaunch();
 }
 
@@ -1467,6 +1588,56 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
     }
   }
   return rc;
+}
+
+// navgpu_planner_cycle for a robot list: the same launches, each once, with the list in device memory where the range form
+// passes `first`.  One cycle in flight only (a listed cycle writes into the result slot the range cycles of that mode use).
+int navgpu_planner_cycle_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances) {
+  if (!f || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->planner_configured || !f->planner_staged || f->cycles_in_flight > 1) return NAVGPU_ERR_STATE;
+  if (!launch_samples_list || !launch_bfs_list || !launch_score_list || !launch_select_list) return NAVGPU_ERR_STATE;
+  int rc = reserveCycleList(f);
+  if (rc != NAVGPU_OK) return rc;
+  PlannerDev& pl = f->pl;
+  navgpu_fleet::CycleList& cl = f->cl;
+  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));  // the pinned list may still feed the copy of the listed cycle before
+  memcpy(cl.h_list, instances, sizeof(uint32_t) * n_robots);
+  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n_robots, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
+  cl.ev_set = true;
+  pl.bfs_bounded = 1;  // per robot: bfs_reach (0 = whole grid)
+  for (uint32_t k = 0; k < n_robots; ++k) {
+    const uint32_t i = instances[k];
+    f->grid_partial[i] = robotBox(f, i, f->hp_state[i].pos, f->hp_reach[i], &f->h_box[(size_t)4 * i]) ? 1 : 0;
+    f->cycle_gen[i] = f->inputs_gen[i];
+  }
+  launch_samples_list(pl, cl.d_list, n_robots, f->stream);
+  // (the launch's dispatch order sits where the range cycle of instances[0] .. would put it: n_robots <= n_instances - instances[0])
+  PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
+  uint32_t n_blocks = 0;
+  PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_list(pl, cl.d_list, n_robots, f->stream));
+  int rc_terms = NAVGPU_OK;
+  if (!f->tc.robots.empty()) {  // publish_traj_pc robots that are in the list: run by run, the pass takes a range
+    for (uint32_t k = 0; k < n_robots && rc_terms == NAVGPU_OK;) {
+      uint32_t e = k + 1;
+      while (e < n_robots && instances[e] == instances[e - 1] + 1) ++e;
+      rc_terms = f->tc.terms_pass(f, instances[k], e - k);
+      k = e;
+    }
+  }
+  PROFILED(f, NAVGPU_K_SELECT, launch_select_list(pl, cl.d_list, n_robots, n_blocks, f->stream));
+  rc = checkLaunch();
+  return rc == NAVGPU_OK ? rc_terms : rc;  // (the cycle itself is complete either way)
+}
+
+int navgpu_planner_results_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, navgpu_plan_result* results) {
+  if (!f || !results || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  HIP_TRY(waitStream(f->stream));  // zero-copy, as navgpu_planner_results
+  const navgpu_plan_result* slot = f->hp_result + (size_t)f->res_slot * f->desc.n_instances;
+  for (uint32_t k = 0; k < n_robots; ++k) results[k] = slot[instances[k]];
+  return NAVGPU_OK;
 }
 
 int navgpu_planner_set_cycles_in_flight(navgpu_fleet* f, int32_t cycles) {

@@ -249,22 +249,46 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
       packed.push_back(local[((size_t)k * max_plan + q) * 3 + 1]);
     }
   }
-  // --- updatePlanAndLocalCosts for every robot that has a local plan (:274), in contiguous runs
-  for (uint32_t k = 0; k < count;) {
-    if (!valid[k]) {
-      ++k;
-      continue;
-    }
-    uint32_t e = k;
-    while (e < count && valid[e] == valid[k]) ++e;
+  // --- updatePlanAndLocalCosts for every robot that has a local plan (:274): the host-path robots in one stage call, the resident
+  // ones in another.  A set that is one contiguous run takes the range call, any other the listed one.
+  std::vector<uint32_t> ks;  // positions k of the set at hand, rising
+  auto collect = [&](const std::vector<uint8_t>& flag, uint8_t want) {
+    ks.clear();
+    for (uint32_t k = 0; k < count; ++k)
+      if (flag[k] == want) ks.push_back(k);
+    return !ks.empty();
+  };
+  auto oneRun = [&] { return ks.back() - ks.front() + 1 == ks.size(); };
+  auto robotsOf = [&] {
+    std::vector<uint32_t> inst(ks.size());
+    for (size_t q = 0; q < ks.size(); ++q) inst[q] = first + ks[q];
+    return inst;
+  };
+  if (collect(valid, 1)) {
     int rc;
-    if (valid[k] == 1) {
-      rc = navgpu_planner_stage(f, first + k, e - k, &states[k], packed.data(), (uint32_t)(packed.size() / 2));
-    } else {  // resident: the window is on the device already; pose, nose goal, alignment switch and reach through k_stage_poses
-      rc = stagePosesFromMirrors(f, first + k, e - k, &res_pos[3 * (size_t)k], &res_vel[3 * (size_t)k]);
+    if (oneRun()) {
+      rc = navgpu_planner_stage(f, first + ks.front(), (uint32_t)ks.size(), &states[ks.front()], packed.data(), (uint32_t)(packed.size() / 2));
+    } else {
+      std::vector<navgpu_robot_state> lst(ks.size());
+      for (size_t q = 0; q < ks.size(); ++q) lst[q] = states[ks[q]];
+      rc = navgpu_planner_stage_list(f, (uint32_t)ks.size(), robotsOf().data(), lst.data(), packed.data(), (uint32_t)(packed.size() / 2));
     }
     if (rc != NAVGPU_OK) return rc;
-    k = e;
+  }
+  if (collect(valid, 2)) {  // resident: the window is on the device already; pose, nose goal, alignment switch and reach through k_stage_poses
+    int rc;
+    if (oneRun()) {
+      rc = stagePosesFromMirrors(f, first + ks.front(), (uint32_t)ks.size(), &res_pos[3 * (size_t)ks.front()], &res_vel[3 * (size_t)ks.front()]);
+    } else {
+      std::vector<float> lp(3 * ks.size()), lv(3 * ks.size());
+      for (size_t q = 0; q < ks.size(); ++q)
+        for (int a = 0; a < 3; ++a) {
+          lp[3 * q + a] = res_pos[3 * (size_t)ks[q] + a];
+          lv[3 * q + a] = res_vel[3 * (size_t)ks[q] + a];
+        }
+      rc = stagePosesListFromMirrors(f, (uint32_t)ks.size(), robotsOf().data(), lp.data(), lv.data());
+    }
+    if (rc != NAVGPU_OK) return rc;
   }
   // --- dispatch: isPositionReached (latched_stop_rotate_controller.cpp:37-58).  The stop / rotate candidates are collected here -
   // robot indices rise with k - and checked in ONE navgpu_planner_check_trajectories call behind the loop
@@ -352,28 +376,27 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
       o.ok = 1;
     }
   }
-  // --- dwaComputeVelocityCommands (:176-247) for the others, in contiguous runs
-  std::vector<navgpu_plan_result> res(count);
-  for (uint32_t k = 0; k < count;) {
-    if (!dwa[k]) {
-      ++k;
-      continue;
+  // --- dwaComputeVelocityCommands (:176-247) for the others: one cycle and one wait, by range when they are one contiguous run
+  if (collect(dwa, 1)) {
+    std::vector<navgpu_plan_result> res(ks.size());
+    int rc;
+    if (oneRun()) {
+      rc = navgpu_planner_cycle(f, first + ks.front(), (uint32_t)ks.size());
+      if (rc == NAVGPU_OK) rc = navgpu_planner_results(f, first + ks.front(), (uint32_t)ks.size(), res.data());
+    } else {
+      const std::vector<uint32_t> inst = robotsOf();
+      rc = navgpu_planner_cycle_list(f, (uint32_t)inst.size(), inst.data());
+      if (rc == NAVGPU_OK) rc = navgpu_planner_results_list(f, (uint32_t)inst.size(), inst.data(), res.data());
     }
-    uint32_t e = k;
-    while (e < count && dwa[e]) ++e;
-    int rc = navgpu_planner_cycle(f, first + k, e - k);
     if (rc != NAVGPU_OK) return rc;
-    rc = navgpu_planner_results(f, first + k, e - k, &res[k]);
-    if (rc != NAVGPU_OK) return rc;
-    for (uint32_t q = k; q < e; ++q) {
-      navgpu_cmd_result& o = out[q];
+    for (size_t q = 0; q < ks.size(); ++q) {
+      navgpu_cmd_result& o = out[ks[q]];
       o.cmd_vel[0] = res[q].drive[0];
       o.cmd_vel[1] = res[q].drive[1];
       o.cmd_vel[2] = res[q].drive[2];
       o.ok = res[q].cost >= 0 ? 1 : 0;  // path.cost_ < 0: "failed to find a valid plan"
       o.trajectory_points = o.ok ? res[q].n_points : 0;
     }
-    k = e;
   }
   return NAVGPU_OK;
 }

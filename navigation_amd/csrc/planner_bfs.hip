@@ -27,11 +27,12 @@ __global__ __launch_bounds__(256) void k_free_bits(PlannerDev pl, uint32_t first
 // (35 ms for the dense sweep it replaces).
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kMaxTiles = 8192;  // 128 x 16-cell tiles of the largest map k_bfs_global accepts (32 KB of flags)
-__global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, uint32_t first, uint32_t* scratch) {
+template <class Robots>
+__global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, Robots robots, uint32_t* scratch) {
   __shared__ uint32_t s_wave[16];
   __shared__ uint8_t s_act[4 * kMaxTiles];
   const int which = (int)pl.bfs_grids - 1 - (int)blockIdx.y;  // longest searches (goal grids) are dispatched first
-  const uint32_t inst = first + blockIdx.x;
+  const uint32_t inst = robots(blockIdx.x);
   const uint32_t tid = threadIdx.x;
   const Geom g = geomOf(pl, inst);
   const uint32_t nx = pl.nx, ny = pl.ny, W = (nx + 31) >> 5, words = ny * W;
@@ -210,7 +211,14 @@ void launch_bfs(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_
   }
   if (launch_bfs_rows(pl, first, count, s, order)) return;
   if (launch_bfs_rows2(pl, first, count, s, order)) return;
-  hipLaunchKernelGGL(k_bfs_global, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, first, pl.bfs_scratch);
+  hipLaunchKernelGGL(k_bfs_global<RobotRange>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, RobotRange{first}, pl.bfs_scratch);
+}
+// The wavefronts of a cycle for the robots list[0 .. count): the bitmaps and the zeroed work counters are k_samples' (the
+// free_ready form above), the scratch slots go by position in the launch as they do there.
+void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order) {
+  if (launch_bfs_rows_list(pl, list, count, s, order)) return;
+  if (launch_bfs_rows2_list(pl, list, count, s, order)) return;
+  hipLaunchKernelGGL(k_bfs_global<RobotList>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, RobotList{list}, pl.bfs_scratch);
 }
 
 }  // namespace navgpu

@@ -417,8 +417,8 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   }
   bfsFinish(pl, tid, inst, which, item, level);
 }
-template <int W>
-__global__ __launch_bounds__(1024, 6) void k_bfs_rows(PlannerDev pl, uint32_t first, uint32_t count, uint32_t* next_item, const uint32_t* order) {
+template <int W, class Robots>
+__global__ __launch_bounds__(1024, 6) void k_bfs_rows(PlannerDev pl, Robots robots, uint32_t count, uint32_t* next_item, const uint32_t* order) {
   __shared__ uint32_t s_item;
   const uint32_t total = count * pl.bfs_grids;  // 3 (DWA: path, goal, goal_front) or 2 (legacy TrajectoryPlanner)
   for (;;) {
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(1024, 6) void k_bfs_rows(PlannerDev pl, uint32_t fi
     if (slot >= total) break;  // (every workgroup gets here: the counter only grows)
     const uint32_t item = order ? order[slot] : slot;  // longest searches first
     const uint32_t g = item / count;
-    bfsRowsGrid<W>(pl, first + (item - g * count), (int)pl.bfs_grids - 1 - (int)g, item);
+    bfsRowsGrid<W>(pl, robots(item - g * count), (int)pl.bfs_grids - 1 - (int)g, item);
     __syncthreads();
   }
 }
@@ -882,7 +882,8 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   }
   bfsFinish(pl, tid, inst, which, item, level);
 }
-__global__ __launch_bounds__(768, 3) void k_bfs_rows2(PlannerDev pl, uint32_t first, uint32_t count, uint32_t* next_item, const uint32_t* order, uint32_t* scratch) {
+template <class Robots>
+__global__ __launch_bounds__(768, 3) void k_bfs_rows2(PlannerDev pl, Robots robots, uint32_t count, uint32_t* next_item, const uint32_t* order, uint32_t* scratch) {
   __shared__ uint32_t s_item;
   const uint32_t total = count * pl.bfs_grids;  // 3 (DWA: path, goal, goal_front) or 2 (legacy TrajectoryPlanner)
   uint32_t* seedw = scratch + (size_t)blockIdx.x * pl.ny * ((pl.nx + 31) >> 5);  // this workgroup's seed bitmap
@@ -893,7 +894,7 @@ __global__ __launch_bounds__(768, 3) void k_bfs_rows2(PlannerDev pl, uint32_t fi
     if (slot >= total) break;  // (every workgroup gets here: the counter only grows)
     const uint32_t item = order ? order[slot] : slot;  // longest searches first
     const uint32_t g = item / count;
-    bfsRows2Grid(pl, first + (item - g * count), (int)pl.bfs_grids - 1 - (int)g, item, seedw);
+    bfsRows2Grid(pl, robots(item - g * count), (int)pl.bfs_grids - 1 - (int)g, item, seedw);
     __syncthreads();
   }
 }
@@ -906,30 +907,44 @@ static int bfs_rows_words(uint32_t nx, uint32_t ny) {
 }
 bool bfs_rows_fits(uint32_t nx, uint32_t ny) { return bfs_rows_words(nx, ny) != 0; }
 // searches resident per CU: as many as the wave slots and LDS hold, at most four
-template <int W>
-static void launch_bfs_rows_w(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order) {
+template <int W, class Robots>
+static void launch_bfs_rows_w(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order) {
   const uint32_t nw = bfs_rows_waves(pl.ny);
   const size_t lds = bfs_rows_lds_words<W>(pl.nx, pl.ny) * 4;
-  if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k_bfs_rows<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k_bfs_rows<W, Robots>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const uint32_t per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(24u / nw, (uint32_t)((156u * 1024u) / (lds + 1024))), 4u));
-  hipLaunchKernelGGL(k_bfs_rows<W>, dim3(std::min(count * pl.bfs_grids, per_cu * bfs_cu_count())), dim3(nw * 64), lds, s, pl, first, count, pl.bfs_next_item + 1, order);
+  hipLaunchKernelGGL((k_bfs_rows<W, Robots>), dim3(std::min(count * pl.bfs_grids, per_cu * bfs_cu_count())), dim3(nw * 64), lds, s, pl, robots, count, pl.bfs_next_item + 1, order);
 }
-bool launch_bfs_rows(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order) {
+template <class Robots>
+static bool launchBfsRows(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order) {
   switch (bfs_rows_words(pl.nx, pl.ny)) {
-    case 7: launch_bfs_rows_w<7>(pl, first, count, s, order); return true;
-    case 13: launch_bfs_rows_w<13>(pl, first, count, s, order); return true;
-    case 20: launch_bfs_rows_w<20>(pl, first, count, s, order); return true;
+    case 7: launch_bfs_rows_w<7>(pl, robots, count, s, order); return true;
+    case 13: launch_bfs_rows_w<13>(pl, robots, count, s, order); return true;
+    case 20: launch_bfs_rows_w<20>(pl, robots, count, s, order); return true;
     default: return false;
   }
 }
-bool launch_bfs_rows2(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order) {
+bool launch_bfs_rows(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order) {
+  return launchBfsRows(pl, RobotRange{first}, count, s, order);
+}
+bool launch_bfs_rows_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order) {
+  return launchBfsRows(pl, RobotList{list}, count, s, order);
+}
+template <class Robots>
+static bool launchBfsRows2(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order) {
   if (NAVGPU_DEBUG_ENV("NAVGPU_DEBUG_BFS_NO_ROWS")) return false;  // A/B timing (tool builds only): k_bfs_global
   if ((pl.nx + 31) / 32 > (uint32_t)kRows2Words || bfs_rows2_waves(pl.ny) > 12) return false;  // 12 waves of 168 registers
   // (the scratch holds 12 bitmaps per robot of the fleet; a workgroup uses one)
   const size_t lds2 = bfs_rows2_lds_words(pl.ny) * 4;
-  if (lds2 > 48 * 1024) hipFuncSetAttribute((const void*)k_bfs_rows2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-  hipLaunchKernelGGL(k_bfs_rows2, dim3(std::min(count * pl.bfs_grids, bfs_cu_count())), dim3(bfs_rows2_waves(pl.ny) * 64), lds2, s, pl, first, count, pl.bfs_next_item, order, pl.bfs_scratch);
+  if (lds2 > 48 * 1024) hipFuncSetAttribute((const void*)k_bfs_rows2<Robots>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+  hipLaunchKernelGGL(k_bfs_rows2<Robots>, dim3(std::min(count * pl.bfs_grids, bfs_cu_count())), dim3(bfs_rows2_waves(pl.ny) * 64), lds2, s, pl, robots, count, pl.bfs_next_item, order, pl.bfs_scratch);
   return true;
+}
+bool launch_bfs_rows2(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order) {
+  return launchBfsRows2(pl, RobotRange{first}, count, s, order);
+}
+bool launch_bfs_rows2_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order) {
+  return launchBfsRows2(pl, RobotList{list}, count, s, order);
 }
 
 #ifdef NAVGPU_BFS_STATS

@@ -13,6 +13,22 @@ __device__ __forceinline__ Geom geomOf(const PlannerDev& pl, uint32_t inst) {
   return Geom{pl.origin[2 * inst], pl.origin[2 * inst + 1], pl.res, pl.nx, pl.ny};
 }
 
+// Which robot block or work item k of a cycle launch belongs to: the k-th of a contiguous range (navgpu_planner_cycle) or
+// of a strictly increasing list in device memory (navgpu_planner_cycle_list).  Every kernel of the cycle is a template over one
+// of the two, one copy of its body.  RobotRange has the size and alignment of the `uint32_t first` it stands for: the range
+// instantiations take the argument block, and compile to the code, they had as plain kernels.
+struct RobotRange {
+  uint32_t first;
+  __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return first + k; }
+  __device__ __forceinline__ uint32_t front() const { return first; }
+};
+struct RobotList {
+  const uint32_t* list;
+  __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return list[k]; }
+  __device__ __forceinline__ uint32_t front() const { return list[0]; }
+};
+static_assert(sizeof(RobotRange) == sizeof(uint32_t) && alignof(RobotRange) == alignof(uint32_t), "the range kernels' argument block");
+
 // free-cell bitmap word of one map row (bit b = cell wi*32+b is traversable)
 // four cost bytes -> four "obstacle" bits (LETHAL, INSCRIBED, and NO_INFORMATION unless unknown cells are allowed), SWAR
 __device__ __forceinline__ uint32_t bfsObstacleNibble(uint32_t v, uint32_t unknown_is_obstacle) {
@@ -130,6 +146,8 @@ constexpr int kRowsPerWave = 64 - 2 * kRowsHalo;   // rows a wave owns
 __host__ __device__ inline uint32_t bfs_rows_waves(uint32_t ny) { return (ny + kRowsPerWave - 1) / kRowsPerWave; }
 bool launch_bfs_rows(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order);   // false: not this map's kernel
 bool launch_bfs_rows2(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order);  // false: not this map's kernel
+bool launch_bfs_rows_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order);   // the same for a robot list
+bool launch_bfs_rows2_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order);
 uint32_t bfs_cu_count();
 bool bfs_rows_fits(uint32_t nx, uint32_t ny);  // the map is k_bfs_rows' (no scratch)
 

@@ -15,7 +15,8 @@ namespace navgpu {
 //   [count, 2 count)    wave 0: the robot's three items ranked for the longest-first dispatch; wave 1: its velocity samples,
 //   behind them         the traversable-cell bitmaps of the launch, 128 words per block.
 constexpr int kSamplesThreads = 128;
-__global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint32_t first, uint32_t count) {
+template <class Robots>
+__global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, Robots robots, uint32_t count) {
   const uint32_t tid = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   if (blockIdx.x >= 2 * count) {
     // the traversable-cell bitmaps of the launch (what k_free_bits does on its own for the other callers of launch_bfs):
@@ -24,13 +25,14 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint
     const uint32_t b = blockIdx.x - 2 * count, r = b / per, i = (b - r * per) * kSamplesThreads + threadIdx.x;
     if (i < words) {
       const uint32_t row = i / W, wi = i - row * W;
-      pl.bfs_free[(size_t)(first + r) * words + i] = bfsFreeWord(pl.master + (size_t)(first + r) * pl.cells_padded, row, pl.nx, wi, pl.cfg.allow_unknown != 0 ? 0u : 1u);
+      const uint32_t inst = robots(r);
+      pl.bfs_free[(size_t)inst * words + i] = bfsFreeWord(pl.master + (size_t)inst * pl.cells_padded, row, pl.nx, wi, pl.cfg.allow_unknown != 0 ? 0u : 1u);
     }
     return;
   }
   const navgpu_dwa_config& c = pl.cfg;
   if (blockIdx.x >= count) {
-    const uint32_t robot = blockIdx.x - count, inst = first + robot;
+    const uint32_t robot = blockIdx.x - count, inst = robots(robot);
     if (wv == 0) {
       // dispatch order of this launch's wavefronts (the row sweeps take items off a counter): longest first, predicted by
       // the level count of the robot's previous cycle.  item = g * count + robot, g = 0 goal_front, 1 goal, 2 path;
@@ -42,14 +44,14 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint
 #pragma unroll 4
       for (uint32_t j = tid; j < total; j += 64) {
         const uint32_t gj = j / count, rj = j - gj * count;
-        const uint32_t kj = pl.bfs_levels[(size_t)(first + rj) * 3 + (2 - gj)];
+        const uint32_t kj = pl.bfs_levels[(size_t)robots(rj) * 3 + (2 - gj)];
 #pragma unroll
         for (uint32_t g = 0; g < 3; ++g) before[g] += (kj > key[g] || (kj == key[g] && j < g * count + robot)) ? 1u : 0u;
       }
 #pragma unroll
       for (uint32_t g = 0; g < 3; ++g)
         for (int o = 32; o > 0; o >>= 1) before[g] += __shfl_xor(before[g], o);
-      if (tid < 3) pl.bfs_order[(size_t)first * 3 + (tid == 0 ? before[0] : (tid == 1 ? before[1] : before[2]))] = tid * count + robot;
+      if (tid < 3) pl.bfs_order[(size_t)robots.front() * 3 + (tid == 0 ? before[0] : (tid == 1 ? before[1] : before[2]))] = tid * count + robot;
       if (robot == 0 && tid < 2) pl.bfs_next_item[tid] = 0;  // the work counters of the launch_bfs that follows
       return;
     }
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint
     }
     return;
   }
-  const uint32_t inst = first + blockIdx.x;
+  const uint32_t inst = robots(blockIdx.x);
   const navgpu_robot_state st = pl.state[inst];
   // Bounded wavefronts (bfsRegion, planner_bfs_common.h).  The box = every cell a MapGrid look-up of this robot's samples can fall in: the
   // staged reach around the robot's cell.  The region = the box grown by two cells, clipped to the map.  A search may
@@ -285,10 +287,14 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, uint
     }
   }
 }
-void launch_samples(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) {
+template <class Robots>
+static void launchSamples(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s) {
   const uint32_t words = pl.ny * ((pl.nx + 31) / 32);
   // (+ the bitmaps and the zeroed work counters of launch_bfs(..., free_ready))
-  hipLaunchKernelGGL(k_samples, dim3(2 * count + count * ((words + kSamplesThreads - 1) / kSamplesThreads)), dim3(kSamplesThreads), 0, s, pl, first, count);
+  hipLaunchKernelGGL(k_samples<Robots>, dim3(2 * count + count * ((words + kSamplesThreads - 1) / kSamplesThreads)), dim3(kSamplesThreads), 0, s, pl, robots, count);
 }
+void launch_samples(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) { launchSamples(pl, RobotRange{first}, count, s); }
+// the robots list[0 .. count) (device memory); the dispatch order goes where the range form of list[0] puts it
+void launch_samples_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s) { launchSamples(pl, RobotList{list}, count, s); }
 
 }  // namespace navgpu

@@ -85,5 +85,6 @@ size_t score_table_lds_bytes(const PlannerDev& pl);
 // k_score_sweep (planner_score_sweep.hip): the launch for use_tables with DWAPlanner's own MapGrid options
 bool score_sweep_applies(const PlannerDev& pl);
 uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s);  // returns blocks per instance
+uint32_t launch_score_sweep_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);  // the same for a robot list
 
 }  // namespace navgpu

@@ -891,7 +891,8 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
 constexpr int kScorePrepThreads = NAVGPU_SCORE_PREP_THREADS;  // the workgroup that builds a robot's image
 
 // k_score_prep_tab: a robot's image with the heading tables, and what k_score_sweep reads behind it
-__global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev pl, uint32_t first) {
+template <class Robots>
+__global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev pl, Robots robots) {
   extern __shared__ __align__(16) uint8_t s_dyn[];
   __shared__ double s_fp[2 * kMaxFootprint];
   __shared__ float s_axis[3][kMaxAxis];
@@ -900,7 +901,7 @@ __global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev
   unsigned long long prep_t[6];
 #endif
   PREP_STAMP(0);
-  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  ScoreRobot r = scoreRobot(pl, robots(blockIdx.y));
   stageInputs<false>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
   __syncthreads();
   PREP_STAMP(1);
@@ -921,21 +922,35 @@ __global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev
 #endif
 }
 // k_score_prep_gen: a robot's image (window and screens) for the k_score_gen* workgroups
-__global__ __launch_bounds__(kScoreThreads) void k_score_prep_gen(PlannerDev pl, uint32_t first) {
+// (Plain kernels around one body, not a template like the others: the statics of a kernel template have vague linkage, and the
+// compiler then keeps the 2 KB of s_fp / s_axis that this kernel stages and never reads - as a plain kernel it drops them.)
+template <class Robots>
+__device__ __forceinline__ void scorePrepGen(const PlannerDev& pl, Robots robots, double* s_fp, float (*s_axis)[kMaxAxis], int* s_cnt) {
   extern __shared__ __align__(16) uint8_t s_dyn[];
-  __shared__ double s_fp[2 * kMaxFootprint];
-  __shared__ float s_axis[3][kMaxAxis];
-  __shared__ int s_cnt[2];
-  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  ScoreRobot r = scoreRobot(pl, robots(blockIdx.y));
   stageInputs<false>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
   __syncthreads();
   buildScreens(pl, r, s_dyn, reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes + score_bits_bytes(r.win)));
   __syncthreads();
   storeImage(pl, r, s_dyn);
 }
+__global__ __launch_bounds__(kScoreThreads) void k_score_prep_gen(PlannerDev pl, RobotRange robots) {
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ int s_cnt[2];
+  scorePrepGen(pl, robots, s_fp, s_axis, s_cnt);
+}
+__global__ __launch_bounds__(kScoreThreads) void k_score_prep_gen_list(PlannerDev pl, RobotList robots) {
+  __shared__ double s_fp[2 * kMaxFootprint];
+  __shared__ float s_axis[3][kMaxAxis];
+  __shared__ int s_cnt[2];
+  scorePrepGen(pl, robots, s_fp, s_axis, s_cnt);
+}
+static auto prepGenKernel(RobotRange) { return k_score_prep_gen; }
+static auto prepGenKernel(RobotList) { return k_score_prep_gen_list; }
 // k_score_gen<CHUNK> / k_score_gen_agg: the samples of a robot, from the image k_score_prep_gen stored
-template <int CHUNK, bool AGG, bool TERMS = false>
-__device__ __forceinline__ void scoreGen(const PlannerDev& pl, uint32_t first, SampleTerms* terms = nullptr) {
+template <int CHUNK, bool AGG, bool TERMS = false, class Robots>
+__device__ __forceinline__ void scoreGen(const PlannerDev& pl, Robots robots, SampleTerms* terms = nullptr) {
   extern __shared__ __align__(16) uint8_t s_dyn[];
   __shared__ double s_fp[2 * kMaxFootprint];
   __shared__ float s_axis[3][kMaxAxis];
@@ -947,7 +962,7 @@ __device__ __forceinline__ void scoreGen(const PlannerDev& pl, uint32_t first, S
   // rollout loops: measured 40 % of a workgroup's residence before its first trajectory point.  Raised priority until the
   // image is in place gets it out of the way.
   __builtin_amdgcn_s_setprio(3);
-  ScoreRobot r = scoreRobot(pl, first + blockIdx.y);
+  ScoreRobot r = scoreRobot(pl, robots(blockIdx.y));
   // The footprint and axis samples stay in registers until the image is copied, and go to LDS with it: ONE batch of
   // loads in flight and one barrier instead of five dependent round trips and three barriers (a load takes several
   // microseconds while 24 waves per CU gather from the distance grids).
@@ -974,12 +989,13 @@ __device__ __forceinline__ void scoreExplicit(const PlannerDev& pl, uint32_t fir
   __syncthreads();
   scoreSamples<true, 12, AGG>(pl, r, s_fp, s_axis, s_dyn, s_rc, s_ri, s_cnt, explicit_sample);
 }
-template <int CHUNK>
-__global__ __launch_bounds__(kScoreThreads) void k_score_gen(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  scoreGen<CHUNK, false>(pl, first);
+template <int CHUNK, class Robots>
+__global__ __launch_bounds__(kScoreThreads) void k_score_gen(PlannerDev pl, Robots robots, const float* explicit_sample) {
+  scoreGen<CHUNK, false>(pl, robots);
 }
-__global__ __launch_bounds__(kScoreThreads) void k_score_gen_agg(PlannerDev pl, uint32_t first, const float* explicit_sample) {
-  scoreGen<16, true>(pl, first);
+template <class Robots>
+__global__ __launch_bounds__(kScoreThreads) void k_score_gen_agg(PlannerDev pl, Robots robots, const float* explicit_sample) {
+  scoreGen<16, true>(pl, robots);
 }
 __global__ __launch_bounds__(kScoreThreads) void k_score_explicit(PlannerDev pl, uint32_t first, const float* explicit_sample) {
   scoreExplicit<false>(pl, first, explicit_sample);
@@ -1015,10 +1031,10 @@ __global__ __launch_bounds__(kScoreThreads) void k_check_traj_agg(PlannerDev pl,
 // TERMS set, for ONE robot whose records go to `terms` [max_samples].  The footprint chunk only groups LDS reads (the
 // critic values do not depend on it), so one instantiation serves every footprint.
 __global__ __launch_bounds__(kScoreThreads) void k_score_terms(PlannerDev pl, uint32_t inst, SampleTerms* terms) {
-  scoreGen<16, false, true>(pl, inst, terms);
+  scoreGen<16, false, true>(pl, RobotRange{inst}, terms);
 }
 __global__ __launch_bounds__(kScoreThreads) void k_score_terms_agg(PlannerDev pl, uint32_t inst, SampleTerms* terms) {
-  scoreGen<16, true, true>(pl, inst, terms);
+  scoreGen<16, true, true>(pl, RobotRange{inst}, terms);
 }
 
 size_t score_window_bytes(uint32_t win) {  // costmap window + the four per-cell screens
@@ -1050,35 +1066,43 @@ size_t score_prep_bytes(const PlannerDev& pl) {  // the LDS image k_score_prep* 
 size_t score_prep_slot_bytes(const PlannerDev& pl) {  // a robot's slot of pl.prep: the image, the sweep launch's scalars, the pairs' reject bytes
   return ((score_prep_bytes(pl) + 255) & ~(size_t)255) + kScoreAuxBytes + score_prep_reject_bytes(pl);
 }
-uint32_t launch_score(const PlannerDev& pl_in, uint32_t first, uint32_t count, const float* explicit_sample, hipStream_t s) {
+static uint32_t sweepLaunch(const PlannerDev& pl, RobotRange r, uint32_t count, hipStream_t s) { return launch_score_sweep(pl, r.first, count, s); }
+static uint32_t sweepLaunch(const PlannerDev& pl, RobotList r, uint32_t count, hipStream_t s) { return launch_score_sweep_list(pl, r.list, count, s); }
+// a cycle's scoring launches for the robots of a range or a list
+template <class Robots>
+static uint32_t launchScoreCycle(const PlannerDev& pl_in, Robots robots, uint32_t count, hipStream_t s) {
   PlannerDev pl = pl_in;
   const size_t win_bytes = score_window_bytes(pl.win);
   const size_t scratch = score_scratch_bytes((int)pl.win);  // only where the image is built
-  if (explicit_sample) {
-    launchScore(pl.mg_generic ? k_score_explicit_agg : k_score_explicit, dim3(1, count), kScoreThreads, win_bytes + scratch, s, pl, first,
-                explicit_sample);
-    return 1;
-  }
   if (score_sweep_applies(pl)) {
     // the prep launch builds all table rows (its LDS holds the whole image); a sweep workgroup loads one row group
     pl.tab_bytes = (uint32_t)score_table_bytes(pl);
     pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
-    launchScore(k_score_prep_tab, dim3(1, count), kScorePrepThreads, win_bytes + score_table_bytes(pl) + scratch, s, pl, first);
-    return launch_score_sweep(pl, first, count, s);
+    launchScore(k_score_prep_tab<Robots>, dim3(1, count), kScorePrepThreads, win_bytes + score_table_bytes(pl) + scratch, s, pl, robots);
+    return sweepLaunch(pl, robots, count, s);
   }
   // the general path (no tables, or mg_generic: the general step has no table variant)
   pl.use_tables = 0;
   pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
   const uint32_t gen_blocks = (pl.max_samples + kScoreThreads - 1) / kScoreThreads;  // (score_blocks is the capacity of the partial results)
-  launchScore(k_score_prep_gen, dim3(1, count), kScoreThreads, win_bytes + scratch, s, pl, first);
-  auto gen = pl.mg_generic        ? k_score_gen_agg
-             : pl.fp_chunk <= 6  ? k_score_gen<6>
-             : pl.fp_chunk <= 9  ? k_score_gen<9>
-             : pl.fp_chunk <= 12 ? k_score_gen<12>
-                                 : k_score_gen<16>;
-  launchScore(gen, dim3(gen_blocks, count), kScoreThreads, win_bytes, s, pl, first, explicit_sample);
+  launchScore(prepGenKernel(robots), dim3(1, count), kScoreThreads, win_bytes + scratch, s, pl, robots);
+  auto gen = pl.mg_generic        ? k_score_gen_agg<Robots>
+             : pl.fp_chunk <= 6  ? k_score_gen<6, Robots>
+             : pl.fp_chunk <= 9  ? k_score_gen<9, Robots>
+             : pl.fp_chunk <= 12 ? k_score_gen<12, Robots>
+                                 : k_score_gen<16, Robots>;
+  launchScore(gen, dim3(gen_blocks, count), kScoreThreads, win_bytes, s, pl, robots, (const float*)nullptr);
   return gen_blocks;
 }
+uint32_t launch_score(const PlannerDev& pl, uint32_t first, uint32_t count, const float* explicit_sample, hipStream_t s) {
+  if (explicit_sample) {
+    const size_t lds = score_window_bytes(pl.win) + score_scratch_bytes((int)pl.win);
+    launchScore(pl.mg_generic ? k_score_explicit_agg : k_score_explicit, dim3(1, count), kScoreThreads, lds, s, pl, first, explicit_sample);
+    return 1;
+  }
+  return launchScoreCycle(pl, RobotRange{first}, count, s);
+}
+uint32_t launch_score_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s) { return launchScoreCycle(pl, RobotList{list}, count, s); }
 
 // The probes of n_robots listed robots in one launch; max_probes: the longest run of the list (> 0).  The image is built in the
 // workgroup, so the dynamic LDS is k_score_explicit's.
@@ -1096,7 +1120,7 @@ void launch_score_terms(const PlannerDev& pl_in, uint32_t inst, SampleTerms* ter
   pl.use_tables = 0;
   pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
   const uint32_t gen_blocks = (pl.max_samples + kScoreThreads - 1) / kScoreThreads;
-  launchScore(k_score_prep_gen, dim3(1, 1), kScoreThreads, win_bytes + score_scratch_bytes((int)pl.win), s, pl, inst);
+  launchScore(k_score_prep_gen, dim3(1, 1), kScoreThreads, win_bytes + score_scratch_bytes((int)pl.win), s, pl, RobotRange{inst});
   launchScore(pl.mg_generic ? k_score_terms_agg : k_score_terms, dim3(gen_blocks, 1), kScoreThreads, win_bytes, s, pl, inst, terms);
 }
 

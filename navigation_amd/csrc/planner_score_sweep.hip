@@ -78,8 +78,8 @@ __device__ unsigned long long g_sweep_stats[16];
 // vel[0] * cos(pos[2]) is a float product (its value: the table's double, rounded to float)
 // KEEP: the fleet keeps every sample's cost and status (navgpu_fleet_desc::keep_sample_costs, pl.sample_cost != nullptr).  Only then
 // does anybody read WHICH critic failed a sample; without it the kernel decides validity alone (the file's head, "Validity").
-template <int CHUNK, bool TRIGF, bool KEEP>
-__global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(PlannerDev pl, uint32_t first) {
+template <int CHUNK, bool TRIGF, bool KEEP, class Robots>
+__global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(PlannerDev pl, Robots robots) {
   constexpr int THREADS = kSweepThreads;
   extern __shared__ __align__(16) uint8_t s_dyn[];
   uint8_t* s_win = s_dyn;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   __shared__ uint32_t s_qn[2];
   __shared__ uint32_t s_more[3];  // rotating by block: any lane of the workgroup still rolling out?
 
-  const uint32_t inst = first + blockIdx.z;  // grid: x = workgroup within its row group, y = row group, z = robot (a robot's workgroups are dispatched together)
+  const uint32_t inst = robots(blockIdx.z);  // grid: x = workgroup within its row group, y = row group, z = robot (a robot's workgroups are dispatched together)
   const uint32_t tid = threadIdx.x;
 #ifdef NAVGPU_SWEEP_TIMING
   unsigned long long sw_t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -787,27 +787,30 @@ bool score_sweep_applies(const PlannerDev& pl) {
   return pl.use_tables && !pl.mg_generic && grid.x * grid.y <= pl.score_blocks;
 }
 // KEEP follows the fleet: the per-sample arrays exist only with navgpu_fleet_desc::keep_sample_costs (navgpu_configure_planner)
-template <int CHUNK>
-static void launchSweep(const PlannerDev& pl, dim3 grid, size_t lds, hipStream_t s, uint32_t first) {
+template <int CHUNK, class Robots>
+static void launchSweep(const PlannerDev& pl, dim3 grid, size_t lds, hipStream_t s, Robots robots) {
   const bool trigf = pl.cfg.rollout_trig != 0, keep = pl.sample_cost != nullptr;
   // (allowed from 40 KB: beside the dynamic LDS the kernel holds 10 KB of static LDS, the walk queue)
-  launchScore<40 * 1024>(keep ? (trigf ? k_score_sweep<CHUNK, true, true> : k_score_sweep<CHUNK, false, true>)
-                              : (trigf ? k_score_sweep<CHUNK, true, false> : k_score_sweep<CHUNK, false, false>),
-                         grid, kSweepThreads, lds, s, pl, first);
+  launchScore<40 * 1024>(keep ? (trigf ? k_score_sweep<CHUNK, true, true, Robots> : k_score_sweep<CHUNK, false, true, Robots>)
+                              : (trigf ? k_score_sweep<CHUNK, true, false, Robots> : k_score_sweep<CHUNK, false, false, Robots>),
+                         grid, kSweepThreads, lds, s, pl, robots);
 }
-uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) {
+template <class Robots>
+static uint32_t launchScoreSweep(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s) {
   const size_t lds = score_window_bytes(pl.win) + score_table_lds_bytes(pl);
   const dim3 grid = score_sweep_grid(pl, count);  // (grid.x * grid.y <= score_blocks: score_sweep_applies)
   if (pl.fp_chunk <= 6)
-    launchSweep<6>(pl, grid, lds, s, first);
+    launchSweep<6>(pl, grid, lds, s, robots);
   else if (pl.fp_chunk <= 9)
-    launchSweep<9>(pl, grid, lds, s, first);
+    launchSweep<9>(pl, grid, lds, s, robots);
   else if (pl.fp_chunk <= 12)
-    launchSweep<12>(pl, grid, lds, s, first);
+    launchSweep<12>(pl, grid, lds, s, robots);
   else
-    launchSweep<16>(pl, grid, lds, s, first);
+    launchSweep<16>(pl, grid, lds, s, robots);
   return grid.x * grid.y;
 }
+uint32_t launch_score_sweep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) { return launchScoreSweep(pl, RobotRange{first}, count, s); }
+uint32_t launch_score_sweep_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s) { return launchScoreSweep(pl, RobotList{list}, count, s); }
 
 #ifdef NAVGPU_SWEEP_COUNTS
 extern "C" int navgpu_debug_sweep_counts(unsigned long long* out16, int reset) {

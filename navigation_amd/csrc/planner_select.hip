@@ -1,5 +1,5 @@
 // k_select (first-strict-minimum selection, winner trajectory, oscillation flag update), k_cell_costs, k_stage_poses,
-// k_sincos (gfx950).
+// k_stage_scatter, k_sincos (gfx950).
 #include "planner_common.h"
 
 namespace navgpu {
@@ -34,8 +34,9 @@ void launch_cell_costs(const PlannerDev& pl, uint32_t inst, float4* out, hipStre
 // (oscillation_cost_function.cpp:56-164), fill drive velocities.
 // ------------------------------------------------------------------------------------------------
 constexpr int kSelectSteps = 128;  // steps whose trigonometry k_select computes side by side (longer trajectories: one lane)
-__global__ __launch_bounds__(64) void k_select(PlannerDev pl, uint32_t first, uint32_t n_blocks) {
-  const uint32_t inst = first + blockIdx.x;
+template <class Robots>
+__global__ __launch_bounds__(64) void k_select(PlannerDev pl, Robots robots, uint32_t n_blocks) {
+  const uint32_t inst = robots(blockIdx.x);
   const uint32_t tid = threadIdx.x;
   const navgpu_dwa_config& c = pl.cfg;
   double bc = 1.0e300;
@@ -290,7 +291,10 @@ __global__ __launch_bounds__(64) void k_select(PlannerDev pl, uint32_t first, ui
   pl.result[inst] = r;
 }
 void launch_select(const PlannerDev& pl, uint32_t first, uint32_t count, uint32_t n_blocks, hipStream_t s) {
-  hipLaunchKernelGGL(k_select, dim3(count), dim3(64), 0, s, pl, first, n_blocks);
+  hipLaunchKernelGGL(k_select<RobotRange>, dim3(count), dim3(64), 0, s, pl, RobotRange{first}, n_blocks);
+}
+void launch_select_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, uint32_t n_blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_select<RobotList>, dim3(count), dim3(64), 0, s, pl, RobotList{list}, n_blocks);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -300,17 +304,46 @@ void launch_select(const PlannerDev& pl, uint32_t first, uint32_t count, uint32_
 // drained, an event wait to cost 2 ms while timing events are recorded in the same process, and a host spin on a
 // device-written flag to starve the queue.)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_stage_poses(PoseChunk c) {
+__device__ __forceinline__ uint32_t poseRobot(const PoseChunk& c, uint32_t li) { return c.first + li; }
+__device__ __forceinline__ uint32_t poseRobot(const PoseChunkList& c, uint32_t li) { return c.inst[li]; }  // (navgpu_planner_stage_poses_list)
+template <class Chunk>
+__global__ __launch_bounds__(64) void k_stage_poses(Chunk c) {
   const uint32_t li = threadIdx.x;
   if (li >= c.count) return;
-  const uint32_t i = c.first + li;
+  const uint32_t i = poseRobot(c, li);
   c.state[i] = c.st[li];
   c.front_last[2 * i] = c.front[2 * li];
   c.front_last[2 * i + 1] = c.front[2 * li + 1];
   c.align_on[i] = c.align[li];
   c.bfs_reach[i] = c.reach[li];
 }
-void launch_stage_poses(const PoseChunk& c, hipStream_t s) { hipLaunchKernelGGL(k_stage_poses, dim3(1), dim3(64), 0, s, c); }
+void launch_stage_poses(const PoseChunk& c, hipStream_t s) { hipLaunchKernelGGL(k_stage_poses<PoseChunk>, dim3(1), dim3(64), 0, s, c); }
+void launch_stage_poses_list(const PoseChunkList& c, hipStream_t s) { hipLaunchKernelGGL(k_stage_poses<PoseChunkList>, dim3(1), dim3(64), 0, s, c); }
+
+// ------------------------------------------------------------------------------------------------
+// k_stage_scatter (navgpu_planner_stage_list): what navgpu_planner_stage copies into the slots of a contiguous range, for
+// the robots of a list - one workgroup per record.  The records and the poses in use arrive packed in one upload; a robot's
+// record names its slot and where its poses begin.  (rec[k].st.plan_count <= max_plan: checked by the host.)
+// ------------------------------------------------------------------------------------------------
+constexpr int kStageScatterThreads = 128;
+__global__ __launch_bounds__(kStageScatterThreads) void k_stage_scatter(PlannerDev pl, const StageRec* rec, const double* poses) {
+  const StageRec r = rec[blockIdx.x];
+  const uint32_t i = r.inst;
+  if (threadIdx.x == 0) {
+    pl.state[i] = r.st;
+    pl.plan_count[i] = r.st.plan_count;
+    pl.front_last[2 * i] = r.front[0];
+    pl.front_last[2 * i + 1] = r.front[1];
+    pl.align_on[i] = r.align;
+    pl.bfs_reach[i] = r.reach;
+  }
+  const double* src = poses + (size_t)r.plan_off * 2;
+  double* dst = pl.plan + (size_t)i * pl.max_plan * 2;
+  for (uint32_t j = threadIdx.x; j < 2 * r.st.plan_count; j += kStageScatterThreads) dst[j] = src[j];
+}
+void launch_stage_scatter(const PlannerDev& pl, const StageRec* rec, const double* poses, uint32_t n_robots, hipStream_t s) {
+  hipLaunchKernelGGL(k_stage_scatter, dim3(n_robots), dim3(kStageScatterThreads), 0, s, pl, rec, poses);
+}
 
 // sin / cos of the headings as scoreSamples evaluates them (navgpu_device_sincos: the floating-point contract, checkable)
 __global__ void k_sincos(const double* th, uint32_t n, double* sn, double* cs) {

@@ -8,6 +8,8 @@ Method names follow the reference interfaces they front:
   find_best_path        DWAPlanner::updatePlanAndLocalCosts + findBestPath (dwa_planner.cpp:240-371)
   check_trajectory      DWAPlanner::checkTrajectory          (dwa_planner.cpp:213-237)
   check_trajectories    a loop of checkTrajectory calls over robots and velocity probes, one launch
+  stage_planner_list / stage_poses_list / planner_cycle_list / results_list  the planner cycle (dwa_planner_ros.cpp:176-247 per robot)
+                        for a robot list instead of a contiguous range, one launch of each kernel
   footprint_cost        CostmapModel::footprintCost          (base_local_planner/src/costmap_model.cpp:50-142)
   rotate_recovery_step  RotateRecovery::runBehavior, one pass (rotate_recovery/src/rotate_recovery.cpp:105-153)
   carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
@@ -470,6 +472,47 @@ class Fleet:
         check(self.L.navgpu_planner_check_trajectories(self.h, len(inst), _ptr(inst), _ptr(off), _ptr(vel), _ptr(ok), _ptr(costs)),
               "check_trajectories")
         return ok[:len(vel)].astype(bool), costs[:len(vel)].copy()
+
+    # ---- the planner cycle for a robot list (strictly increasing indices): one launch of each kernel whatever the list looks like
+    def stage_planner_list(self, instances, pos, vel, plans):
+        """stage_planner for the listed robots; pos, vel, plans are indexed by list position."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        vel = np.ascontiguousarray(vel, np.float32).reshape(-1, 3)
+        if len(pos) != len(inst) or len(vel) != len(inst) or len(plans) != len(inst):
+            raise ValueError("stage_planner_list: one pose, velocity and plan per listed robot")
+        counts = [len(p) for p in plans]
+        packed = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float64).reshape(-1, 2) for p in plans])) if counts else np.zeros((0, 2))
+        states = (RobotState * max(len(inst), 1))()
+        off = 0
+        for k in range(len(inst)):
+            states[k].pos[:] = pos[k].tolist()
+            states[k].vel[:] = vel[k].tolist()
+            states[k].plan_first = off
+            states[k].plan_count = counts[k]
+            off += counts[k]
+        check(self.L.navgpu_planner_stage_list(self.h, len(inst), _ptr(inst), C.cast(states, C.c_void_p), _ptr(packed), len(packed)),
+              "planner_stage_list")
+
+    def stage_poses_list(self, instances, pos, vel):
+        """stage_poses for the listed robots (plans unchanged); pos, vel: one row per listed robot."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        vel = np.ascontiguousarray(vel, np.float32).reshape(-1, 3)
+        if len(pos) != len(inst) or len(vel) != len(inst):
+            raise ValueError("stage_poses_list: one pose and velocity per listed robot")
+        check(self.L.navgpu_planner_stage_poses_list(self.h, len(inst), _ptr(inst), _ptr(pos), _ptr(vel)), "planner_stage_poses_list")
+
+    def planner_cycle_list(self, instances):
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        check(self.L.navgpu_planner_cycle_list(self.h, len(inst), _ptr(inst)), "planner_cycle_list")
+
+    def results_list(self, instances):
+        """The results of the listed robots, in list order."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        r = (PlanResult * max(len(inst), 1))()
+        check(self.L.navgpu_planner_results_list(self.h, len(inst), _ptr(inst), C.cast(r, C.c_void_p)), "planner_results_list")
+        return list(r)[:len(inst)]
 
     def cost_cloud(self, instance):
         """MapGridVisualizer's cost cloud of one robot: (n, 7) float32 x, y, z, path, goal, occ, total."""
