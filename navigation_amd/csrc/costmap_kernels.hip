@@ -6,6 +6,7 @@
 // Reference citations are on each kernel.  Compiled with -ffp-contract=off: every fp64 expression
 // must round exactly like the reference's x86-64 build.
 #include "navgpu_device.h"
+#include "costmap_word_rules.h"
 
 namespace navgpu {
 
@@ -677,17 +678,15 @@ struct UpdateBox {
 // them), else the one finishBounds left in the robot's state - InstCostmapState::box, ordered x0, xn, y0, yn as updateMap declares
 // them.  false: that box is empty (layered_costmap.cpp:128-135), nothing to update.
 __device__ __forceinline__ bool updateBox(const CostmapDev& cm, const int32_t* boxes, uint32_t k, uint32_t inst, UpdateBox& box) {
-  if (boxes) {
-    box = UpdateBox{boxes[4 * k + 0], boxes[4 * k + 1], boxes[4 * k + 2], boxes[4 * k + 3]};
-    return true;
-  }
+  // (one address and one four-word load for either source - both wave-uniform - and the order sorted out on the values)
   const InstCostmapState* st = cm.state + inst;
-  if (!st->box_valid) return false;
-  box.x0 = st->box[0];
-  box.xn = st->box[1];
-  box.y0 = st->box[2];
-  box.yn = st->box[3];
-  return true;
+  const int32_t* p = boxes ? boxes + 4 * (size_t)k : st->box;
+  const int b0 = p[0], b1 = p[1], b2 = p[2], b3 = p[3];
+  box.x0 = b0;
+  box.y0 = boxes ? b1 : b2;
+  box.xn = boxes ? b2 : b1;
+  box.yn = b3;
+  return boxes ? true : st->box_valid != 0;
 }
 // InflationLayer::updateCosts' seed box (inflation_layer.cpp:200-211): grown by the inflation radius R, clamped to the nx x ny grid
 __device__ __forceinline__ UpdateBox inflateBox(const UpdateBox& box, int R, uint32_t nx, uint32_t ny) {
@@ -707,11 +706,65 @@ void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const
 // k_merge: Costmap2D::resetMap (costmap_2d.cpp:93-99) over the box, then StaticLayer::updateCosts
 // (static_layer.cpp:285-299: updateWithTrueOverwrite | updateWithMax) and ObstacleLayer::updateCosts
 // (obstacle_layer.cpp:437-447: updateWithOverwrite | updateWithMax, costmap_layer.cpp:62-124),
-// fused per byte.  16 cells per thread: three 16-byte reads and one 16-byte write, fully coalesced.
+// fused.  16 cells per thread: three 16-byte reads and one 16-byte write, fully coalesced.
 // layer_only: ObstacleLayer::updateCosts alone, as a costmap_2d::Layer plugin runs it - the master
 // grid it is handed already holds what the layers before it wrote (no reset, no static merge).
+//   k_merge        the rules on the group's four words (costmap_word_rules.h) under a byte mask of the box; what is the same for the
+//                  whole launch - which rules, and whether a group can straddle rows - is a template parameter (launch_merge)
+//   k_merge_bytes  byte by byte: the rolling static layer (static_layer.cpp:318-330, fp64 transforms per cell)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_merge(CostmapDev cm, uint32_t first, const int32_t* boxes, int static_received, int layer_only) {
+// ALIGNED: nx is a multiple of 16, so a group lies in one row and its box bitmap follows from its row and first column; else the
+// bitmap is built cell by cell (a group may cross any number of rows when nx < 16)
+template <bool ALIGNED, int STATIC, int OBST, bool LAYER_ONLY>
+__global__ __launch_bounds__(256) void k_merge(CostmapDev cm, uint32_t first, const int32_t* boxes, word_rules::FastDiv div_nx,
+                                                     word_rules::FastDiv div_gpr) {
+  using namespace word_rules;
+  const uint32_t inst = first + blockIdx.y;
+  UpdateBox box;
+  if (!updateBox(cm, boxes, blockIdx.y, inst, box)) return;
+  const int x0 = box.x0, y0 = box.y0, xn = box.xn, yn = box.yn;
+  // the wave's 64 groups (wave-uniform, scalar): none of their rows in the box's -> out
+  const uint32_t wq = blockIdx.x * 256u + (__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63u);
+  if (wq * 16u >= cm.cells) return;
+  const int wrow_first = (int)fastDiv(wq * 16u, div_nx), wrow_last = (int)fastDiv(min(wq * 16u + 1023u, cm.cells - 1u), div_nx);
+  if (wrow_last < y0 || wrow_first >= yn) return;
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;  // 16-cell group
+  const uint32_t base = q * 16u;
+  if (base >= cm.cells) return;
+  uint32_t bits;  // bit k: cell base + k lies in the box
+  if (ALIGNED) {
+    const uint32_t gpr = cm.nx >> 4, row = fastDiv(q, div_gpr);
+    bits = ((int)row >= y0 && (int)row < yn) ? boxBits((int)((q - row * gpr) << 4), x0, xn) : 0u;
+  } else {
+    int y = (int)fastDiv(base, div_nx);
+    int x = (int)(base - (uint32_t)y * cm.nx);
+    bits = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      if (base + k < cm.cells && x >= x0 && x < xn && y >= y0 && y < yn) bits |= 1u << k;
+      if (++x == (int)cm.nx) {
+        x = 0;
+        ++y;
+      }
+    }
+  }
+  if (bits == 0u) return;  // no cell in the box: nothing read, nothing written
+  const size_t off = (size_t)inst * cm.cells_padded + base;
+  const uint4 sv = STATIC ? *reinterpret_cast<const uint4*>(cm.stat + off) : make_uint4(0, 0, 0, 0);
+  const uint4 lv = OBST ? *reinterpret_cast<const uint4*>(cm.obst + off) : make_uint4(0, 0, 0, 0);
+  uint4 mv = make_uint4(0, 0, 0, 0);
+  // all 16 cells in the box: resetMap overwrites every byte, the master's old ones need not be read
+  // (the conditional load last: it is waited for inside its branch, with the other two already under way)
+  if (LAYER_ONLY || bits != 0xFFFFu) mv = *reinterpret_cast<const uint4*>(cm.master + off);
+  uint4 out;
+  out.x = mergeWord<STATIC, OBST, LAYER_ONLY>(mv.x, sv.x, lv.x, boxBytes(bits, 0), cm.master_default);
+  out.y = mergeWord<STATIC, OBST, LAYER_ONLY>(mv.y, sv.y, lv.y, boxBytes(bits, 1), cm.master_default);
+  out.z = mergeWord<STATIC, OBST, LAYER_ONLY>(mv.z, sv.z, lv.z, boxBytes(bits, 2), cm.master_default);
+  out.w = mergeWord<STATIC, OBST, LAYER_ONLY>(mv.w, sv.w, lv.w, boxBytes(bits, 3), cm.master_default);
+  *reinterpret_cast<uint4*>(cm.master + off) = out;
+}
+
+__global__ __launch_bounds__(256) void k_merge_bytes(CostmapDev cm, uint32_t first, const int32_t* boxes, int static_received, int layer_only) {
   const uint32_t inst = first + blockIdx.y;
   UpdateBox box;
   if (!updateBox(cm, boxes, blockIdx.y, inst, box)) return;
@@ -795,10 +848,52 @@ __global__ __launch_bounds__(256) void k_merge(CostmapDev cm, uint32_t first, co
   if (changed) *reinterpret_cast<uint4*>(cm.master + off) = make_uint4(mw[0], mw[1], mw[2], mw[3]);
 }
 
+template <bool ALIGNED, int STATIC, int OBST, bool LAYER_ONLY>
+static void launchMergeWords(const CostmapDev& cm, uint32_t first, const int32_t* boxes, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_merge<ALIGNED, STATIC, OBST, LAYER_ONLY>), grid, dim3(256), 0, s, cm, first, boxes, word_rules::fastDivOf(cm.nx),
+                     word_rules::fastDivOf(cm.nx >= 16 ? cm.nx >> 4 : 1));
+}
+template <bool ALIGNED, int STATIC>
+static void launchMergeObst(const CostmapDev& cm, uint32_t first, const int32_t* boxes, dim3 grid, hipStream_t s, int obst, bool layer_only) {
+  if (layer_only) {
+    if (STATIC != 0) return;  // (never asked for: launch_merge passes 0)
+    switch (obst) {
+      case 0: return launchMergeWords<ALIGNED, 0, 0, true>(cm, first, boxes, grid, s);
+      case 1: return launchMergeWords<ALIGNED, 0, 1, true>(cm, first, boxes, grid, s);
+      default: return launchMergeWords<ALIGNED, 0, 2, true>(cm, first, boxes, grid, s);
+    }
+  }
+  switch (obst) {
+    case 0: return launchMergeWords<ALIGNED, STATIC, 0, false>(cm, first, boxes, grid, s);
+    case 1: return launchMergeWords<ALIGNED, STATIC, 1, false>(cm, first, boxes, grid, s);
+    default: return launchMergeWords<ALIGNED, STATIC, 2, false>(cm, first, boxes, grid, s);
+  }
+}
+template <bool ALIGNED>
+static void launchMergeStatic(const CostmapDev& cm, uint32_t first, const int32_t* boxes, dim3 grid, hipStream_t s, int stat, int obst, bool layer_only) {
+  switch (stat) {
+    case 0: return launchMergeObst<ALIGNED, 0>(cm, first, boxes, grid, s, obst, layer_only);
+    case 1: return launchMergeObst<ALIGNED, 1>(cm, first, boxes, grid, s, obst, layer_only);
+    default: return launchMergeObst<ALIGNED, 2>(cm, first, boxes, grid, s, obst, layer_only);
+  }
+}
+
 void launch_merge(const CostmapDev& cm, uint32_t first, uint32_t count, const int32_t* boxes, hipStream_t s, bool layer_only) {
   uint32_t groups = (cm.cells + 15) / 16;
   dim3 grid((groups + 255) / 256, count);
-  hipLaunchKernelGGL(k_merge, grid, dim3(256), 0, s, cm, first, boxes, cm.static_received, layer_only ? 1 : 0);
+  // the rolling static layer goes byte by byte (and so would a map of 2^31 cells or more: the word kernel divides by multiplication)
+  if ((cm.stat_roll != nullptr && !layer_only) || cm.cells >= 0x80000000u) {
+    hipLaunchKernelGGL(k_merge_bytes, grid, dim3(256), 0, s, cm, first, boxes, cm.static_received, layer_only ? 1 : 0);
+    return;
+  }
+  const bool has_static = (cm.layers & NAVGPU_LAYER_STATIC) && cm.static_received && !layer_only && cm.stat;
+  const bool has_obst = (cm.layers & (NAVGPU_LAYER_OBSTACLE | NAVGPU_LAYER_VOXEL)) && cm.obs_enabled;
+  const int stat = !has_static ? 0 : (cm.static_use_maximum ? 2 : 1);
+  const int obst = !has_obst ? 0 : (cm.combination_method == 0 ? 1 : (cm.combination_method == 1 ? 2 : 0));
+  if (cm.nx % 16 == 0)
+    launchMergeStatic<true>(cm, first, boxes, grid, s, stat, obst, layer_only);
+  else
+    launchMergeStatic<false>(cm, first, boxes, grid, s, stat, obst, layer_only);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -897,7 +992,9 @@ __global__ __launch_bounds__(256) void k_inflate(CostmapDev cm, uint32_t first, 
 // Tile = 64 columns (one per lane) x 32 rows per 256-thread workgroup.
 // ------------------------------------------------------------------------------------------------
 constexpr int kBX = 64, kBY = 32;
-template <int RT>
+// BOXES: the caller passes the boxes (Fleet.inflate(boxes)); else they are the ones finishBounds left in the robots' states.  Known at
+// the launch, so that the three of four workgroups that only find out that their tile is out of reach do not sort that out first.
+template <int RT, bool BOXES>
 __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t first, uint32_t count, const int32_t* boxes) {
   // XCD-aware tile order: workgroups b and b + 8 of a launch (linear id, x fastest) share an XCD and its L2.  The grid is
   // (8 * tiles_x, tiles_y, robots / 8) and the robot 8 * z + x % 8, so a robot's tiles follow one another on ONE XCD: the 2R
@@ -908,32 +1005,34 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
   const uint32_t inst = first + rz;
   const int R = RT > 0 ? RT : (int)cm.R;
   UpdateBox box;
-  if (!updateBox(cm, boxes, rz, inst, box)) return;
+  if (BOXES) {
+    box = UpdateBox{boxes[4 * rz + 0], boxes[4 * rz + 1], boxes[4 * rz + 2], boxes[4 * rz + 3]};
+  } else {  // (InstCostmapState::box is ordered x0, xn, y0, yn: updateBox)
+    const InstCostmapState* st = cm.state + inst;
+    box = UpdateBox{st->box[0], st->box[2], st->box[1], st->box[3]};
+    if (!st->box_valid) return;
+  }
+  const int tx0 = (int)tbx * kBX, ty0 = (int)tby * kBY;
+  // A tile no seed of the grown box can reach leaves here: most of a launch's workgroups.  The test is on the box as loaded - the clamps
+  // of inflateBox change nothing for a tile that starts on the map (tx0 - R < nx <= the unclamped edge, tx0 + kBX + R > 0).
+  if (tx0 - 2 * R >= box.xn || tx0 + kBX + 2 * R <= box.x0 || ty0 - 2 * R >= box.yn || ty0 + kBY + 2 * R <= box.y0) return;
   box = inflateBox(box, R, cm.nx, cm.ny);
   const int min_i = box.x0, min_j = box.y0, max_i = box.xn, max_j = box.yn;
-  const int tx0 = (int)tbx * kBX, ty0 = (int)tby * kBY;
-  if (tx0 - R >= max_i || tx0 + kBX + R <= min_i || ty0 - R >= max_j || ty0 + kBY + R <= min_j) return;
 
   constexpr int kMaxHR = kBY + 2 * 14;      // halo'd rows
   constexpr int kOct = (kMaxHR + 7) / 8;    // row octets
-  __shared__ uint32_t s_rows[kMaxHR][4];    // seed bits of columns [tx0-32, tx0+96)
+  __shared__ __align__(16) uint32_t s_rows[kMaxHR][4];  // seed bits of columns [tx0-32, tx0+96)
   __shared__ uint32_t s_hd[kOct + 1][kBX];  // nibble-packed nearest-seed |dx| per (row octet, column)
   __shared__ uint8_t s_lut2[256];           // cost by squared distance
-  __shared__ int s_any;
-  __shared__ uint32_t s_rowany[2];                // bit r: halo row r of the tile holds a seed (pass B skips the others)
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (the wave's number as a scalar: the row numbers, loop bounds and LDS rows that follow from it are wave-uniform and stay out of the lanes)
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = (__builtin_amdgcn_readfirstlane(tid) >> 6) & 3u;
   const int HR = kBY + 2 * R;
   uint8_t* master = cm.master + (size_t)inst * cm.cells_padded;
-  if (tid == 0) s_any = 0;
-  if (tid < 2) s_rowany[tid] = 0;
-  s_lut2[tid] = cm.lut2[tid];
-  __syncthreads();
+  s_lut2[tid] = cm.lut2[tid];  // (read in pass B, two barriers on)
   // ---- seed bitmaps by ballot: wave w takes halo rows w, w+4, ...
   // (all of a wave's loads are issued before the first ballot needs one: in a rolled loop every load is waited for on
   // its own, 28 latencies in a row - that was most of this kernel's 57 us)
-  int any = 0;
-  uint32_t rows_lo = 0, rows_hi = 0;  // (wave-uniform) this wave's halo rows that hold a seed
-  constexpr int kSeedIt = (kMaxHR + 3) / 4;
+  constexpr int kSeedIt = ((RT > 0 ? kBY + 2 * RT : kMaxHR) + 3) / 4;
   // The loads are unconditional (clamped coordinates; a conditional load is waited for inside its branch) and the
   // conditions are applied to what they return.
   uint8_t cell[kSeedIt][2];
@@ -943,8 +1042,9 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
   const int lo_x = max(min_i, tx0 - R), lo_y = max(min_j, ty0 - R);  // (min_* >= 0; an inverted box leaves hi < lo: still on the map)
   const int hi_x = max(lo_x, min(max_i, tx0 + kBX + R) - 1), hi_y = max(lo_y, min(max_j, ty0 + kBY + R) - 1);
   const int cxa = min(min(max(gxa, lo_x), hi_x), (int)cm.nx - 1), cxb = min(min(max(gxb, lo_x), hi_x), (int)cm.nx - 1);
-  const bool xa_ok = gxa >= min_i && gxa < max_i && gxa >= tx0 - R && gxa < tx0 + kBX + R;
-  const bool xb_ok = gxb >= min_i && gxb < max_i && gxb >= tx0 - R && gxb < tx0 + kBX + R;
+  // the columns that may seed, as lane masks (the same for every row)
+  const unsigned long long xa_ok = __builtin_amdgcn_ballot_w64(gxa >= min_i && gxa < max_i && gxa >= tx0 - R && gxa < tx0 + kBX + R);
+  const unsigned long long xb_ok = __builtin_amdgcn_ballot_w64(gxb >= min_i && gxb < max_i && gxb >= tx0 - R && gxb < tx0 + kBX + R);
 #pragma unroll
   for (int it = 0; it < kSeedIt; ++it) {
     const int gy = ty0 - R + (int)wave + 4 * it;
@@ -952,60 +1052,55 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
     cell[it][0] = master[cy * cm.nx + cxa];
     cell[it][1] = master[cy * cm.nx + cxb];
   }
+  // A row's four ballot words are stored by every lane alike (the same 16 bytes to the same address: one store, no exec change)
 #pragma unroll
   for (int it = 0; it < kSeedIt; ++it) {
-    const int r = (int)wave + 4 * it, gy = ty0 - R + r;
+    const int r = (int)wave + 4 * it;
     if (r < HR) {  // (wave-uniform)
-      const bool row_ok = gy >= min_j && gy < max_j;
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const unsigned long long m = __ballot(row_ok && (half ? xb_ok : xa_ok) && cell[it][half] == kLethal);
-        if (lane == 0) {
-          s_rows[r][2 * half] = (uint32_t)m;
-          s_rows[r][2 * half + 1] = (uint32_t)(m >> 32);
-        }
-        any |= m != 0ull;
-        if (m != 0ull) {
-          if (r < 32)
-            rows_lo |= 1u << r;
-          else
-            rows_hi |= 1u << (r - 32);
-        }
-      }
+      // (a row outside the box's rows holds the bits of the row its load was clamped to: nobody reads them, see rowany_tile)
+      const unsigned long long ma = __builtin_amdgcn_ballot_w64(cell[it][0] == kLethal) & xa_ok;
+      const unsigned long long mb = __builtin_amdgcn_ballot_w64(cell[it][1] == kLethal) & xb_ok;
+      *reinterpret_cast<uint4*>(s_rows[r]) = make_uint4((uint32_t)ma, (uint32_t)(ma >> 32), (uint32_t)mb, (uint32_t)(mb >> 32));
     }
-  }
-  if (any && lane == 0) {
-    s_any = 1;
-    if (rows_lo) atomicOr(&s_rowany[0], rows_lo);
-    if (rows_hi) atomicOr(&s_rowany[1], rows_hi);
   }
   __syncthreads();
-  if (!s_any) return;
-  // ---- pass A: nearest seed |dx| (nibble, 15 = none within R) for every (halo row, column)
+  // Which halo rows of the tile hold a seed (bit r: row r), in every wave alike: lane r reads row r's words and knows whether row r is
+  // one of the box's.  Pass A and pass B skip the rows whose bit is not set, wave-uniformly - those outside the box among them, whose
+  // words are never read again; a tile without any leaves here.
+  unsigned long long rowany_tile;
+  {
+    const uint4 w = *reinterpret_cast<const uint4*>(s_rows[lane < (uint32_t)HR ? lane : 0u]);
+    const int gyl = ty0 - R + (int)lane;
+    rowany_tile = __builtin_amdgcn_ballot_w64(lane < (uint32_t)HR && gyl >= min_j && gyl < max_j && (w.x | w.y | w.z | w.w) != 0u);
+  }
+  if (rowany_tile == 0ull) return;
+  // ---- pass A: nearest seed |dx| (nibble, 15 = none within R) for every (halo row, column); a row without a seed is skipped before
+  // its words are read and keeps nibble 15; rows from HR on never have their bit set.
   const uint32_t lowmask = (1u << R) - 1u;
+  // cell column c = lane sits at bit 32 + c of the 128-bit row; window = bits [32+c-R, 32+c+R]: words wi and wi + 1 <= 3 (R <= 14 < 32)
+  const uint32_t sft = 32u + lane - (uint32_t)R;
+  const uint32_t wi = sft >> 5, bs = sft & 31u;
   for (int o = wave; o * 8 < HR; o += 4) {
-    uint32_t packed = 0;
+    const uint32_t oct = (uint32_t)(rowany_tile >> (8 * o)) & 0xFFu;
+    uint32_t near = 0;  // nibble k: 15 - h of row 8 o + k
+    if (oct != 0u) {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int r = o * 8 + k;
-      uint32_t h = 15;
-      // (a row without seeds needs no bit scans: wave-uniform, the row words are the same for every lane)
-      if (r < HR && (s_rows[r][0] | s_rows[r][1] | s_rows[r][2] | s_rows[r][3]) != 0u) {
-        // cell column c = lane sits at bit 32 + c of the 128-bit row; window = bits [32+c-R, 32+c+R]
-        const uint32_t sft = 32u + lane - (uint32_t)R;
-        const uint32_t wi = sft >> 5, bs = sft & 31u;
-        const unsigned long long two = ((unsigned long long)s_rows[r][wi + 1 < 4 ? wi + 1 : 3] << 32) | s_rows[r][wi];
-        const uint32_t q = (uint32_t)(two >> bs);
-        const uint32_t qr = q >> R;        // bit k: seed at dx = +k (k = 0..R after masking below)
-        const uint32_t ql = q & lowmask;   // bit j: seed at dx = j - R
-        uint32_t dr = 15, dl = 15;
-        if (qr & ((2u << R) - 1u)) dr = (uint32_t)__builtin_ctz(qr & ((2u << R) - 1u));
-        if (ql) dl = (uint32_t)R - (31u - (uint32_t)__builtin_clz(ql));
-        h = dr < dl ? dr : dl;
+      for (int k = 0; k < 8; ++k) {
+        if ((oct >> k) & 1u) {  // (wave-uniform)
+          const int r = o * 8 + k;
+          const unsigned long long two = ((unsigned long long)s_rows[r][wi + 1] << 32) | s_rows[r][wi];
+          const uint32_t q = (uint32_t)(two >> bs);
+          const uint32_t qr = q >> R;        // bit k: seed at dx = +k (k = 0..R after masking below)
+          const uint32_t ql = q & lowmask;   // bit j: seed at dx = j - R
+          uint32_t dr = 15, dl = 15;
+          if (qr & ((2u << R) - 1u)) dr = (uint32_t)__builtin_ctz(qr & ((2u << R) - 1u));
+          if (ql) dl = (uint32_t)R - (31u - (uint32_t)__builtin_clz(ql));
+          const uint32_t h = dr < dl ? dr : dl;
+          near |= (15u - h) << (4 * k);
+        }
       }
-      packed |= h << (4 * k);
     }
-    s_hd[o][lane] = packed;
+    s_hd[o][lane] = ~near;
   }
   __syncthreads();
   // ---- pass B: wave w owns output rows [8w, 8w+8) of the tile; halo rows [8w, 8w+8+2R) = 5 words
@@ -1016,29 +1111,46 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
   if (__ballot((hw[0] & hw[1] & hw[2] & hw[3] & hw[4]) != 0xFFFFFFFFu) == 0ull) return;
   const int gx = tx0 + (int)lane;
   const int R2 = R * R;
-  // R known at compile time: the halo rows outermost, and only those that hold a seed (wave-uniform: s_rowany) - a row's h^2 is worked
+  // The old bytes of the wave's eight output rows: unconditional loads at clamped cells (the tile's own, which no other workgroup
+  // writes), all under way while the distances are worked out, instead of one load per row waited for inside its branch.
+  uint8_t oldb[8];
+  {
+    const int cgx = min(gx, (int)cm.nx - 1);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) oldb[j] = master[min(ty0 + (int)wave * 8 + j, (int)cm.ny - 1) * cm.nx + cgx];
+  }
+  // R known at compile time: the halo rows outermost, and only those that hold a seed (wave-uniform: rowany_tile) - a row's h^2 is worked
   // out once and goes into the (up to 8) output rows it is within R of: 2 instructions per (row, output row) pair instead of 3 per
   // pair of ALL 8 + 2R rows
-  uint32_t bestr[8] = {0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu, 0xFFFFu};
+  // Two output rows per instruction: rows 2i and 2i + 1 are the 16-bit halves of bestp[i] (d^2 <= 15^2 + 14^2), an add and a packed
+  // 16-bit min per (row, pair).  A half whose row is further than R from the halo row gets kFar added instead of dy^2 and never wins.
+  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+  constexpr unsigned short kFar = 0x7000;
+  u16x2 bestp[4] = {{0xFFFFu, 0xFFFFu}, {0xFFFFu, 0xFFFFu}, {0xFFFFu, 0xFFFFu}, {0xFFFFu, 0xFFFFu}};
   if (RT > 0) {
-    const unsigned long long rowany = (((unsigned long long)s_rowany[1] << 32) | s_rowany[0]) >> (8u * wave);  // bit p: this wave's halo row p
-    const uint32_t ra_lo = __builtin_amdgcn_readfirstlane((uint32_t)rowany), ra_hi = __builtin_amdgcn_readfirstlane((uint32_t)(rowany >> 32));
+    const unsigned long long rowany = rowany_tile >> (8u * wave);  // bit p: this wave's halo row p
+    const uint32_t ra_lo = (uint32_t)rowany, ra_hi = (uint32_t)(rowany >> 32);
 #pragma unroll
     for (int p = 0; p < 8 + 2 * RT; ++p) {
       if (((p < 32 ? ra_lo >> (p & 31) : ra_hi >> (p & 31)) & 1u) != 0u) {  // (wave-uniform)
         const uint32_t h = (hw[p >> 3] >> (4 * (p & 7))) & 15u;
-        const uint32_t hh = h * h;
+        const uint32_t hh2 = (h * 0x10001u) * h;  // h^2 in both halves
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int dy = p - RT - j;
-          if (dy >= -RT && dy <= RT) {
-            const uint32_t d2 = hh + (uint32_t)(dy * dy);
-            bestr[j] = d2 < bestr[j] ? d2 : bestr[j];
+        for (int i = 0; i < 4; ++i) {
+          const int dy0 = p - RT - 2 * i, dy1 = dy0 - 1;
+          const bool in0 = dy0 >= -RT && dy0 <= RT, in1 = dy1 >= -RT && dy1 <= RT;
+          if (in0 || in1) {
+            // (a 32-bit add of a literal: nothing carries between the halves, h^2 + kFar < 2^16; a packed add takes its constant from a register)
+            const uint32_t dd = (in0 ? (uint32_t)(dy0 * dy0) : kFar) | ((in1 ? (uint32_t)(dy1 * dy1) : kFar) << 16);
+            bestp[i] = __builtin_elementwise_min(bestp[i], __builtin_bit_cast(u16x2, hh2 + dd));
           }
         }
       }
     }
   }
+  uint32_t bestr[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bestr[j] = (j & 1) ? bestp[j >> 1].y : bestp[j >> 1].x;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int gy = ty0 + (int)wave * 8 + j;
@@ -1053,12 +1165,12 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
         best = d2 < best ? d2 : best;
       }
     }
-    if (best > (uint32_t)R2 || gx >= (int)cm.nx || gy >= (int)cm.ny) continue;
-    const uint8_t cost = s_lut2[best];
-    if (cost == 0) continue;
-    const uint8_t old = master[gy * cm.nx + gx];
+    // one predicate and one store under it (cost 0: max(old, 0) == old and the 255-rule needs cost >= 253; lut2 holds 0 beyond the radius)
+    const uint8_t cost = s_lut2[best < 255u ? best : 255u];
+    const uint8_t old = oldb[j];
     const uint8_t nv = (old == kNoInfo && cost >= kInscribed) ? cost : (old > cost ? old : cost);
-    if (nv != old) master[gy * cm.nx + gx] = nv;
+    const uint32_t write = (uint32_t)(best <= (uint32_t)R2) & (uint32_t)(gx < (int)cm.nx) & (uint32_t)(gy < (int)cm.ny) & (uint32_t)(nv != old);
+    if (write) master[gy * cm.nx + gx] = nv;
   }
 }
 
@@ -1257,9 +1369,9 @@ void launch_inflate(const CostmapDev& cm, uint32_t first, uint32_t count, const 
   if (cm.lut2_ok && R >= 1 && R <= 14) {
     dim3 grid(8u * ((cm.nx + kBX - 1) / kBX), (cm.ny + kBY - 1) / kBY, (count + 7u) / 8u);  // (robot = 8 z + x % 8: see the kernel)
     if (R == 11)
-      hipLaunchKernelGGL(k_inflate_bits<11>, grid, dim3(256), 0, s, cm, first, count, boxes);
+      hipLaunchKernelGGL((boxes ? k_inflate_bits<11, true> : k_inflate_bits<11, false>), grid, dim3(256), 0, s, cm, first, count, boxes);
     else
-      hipLaunchKernelGGL(k_inflate_bits<0>, grid, dim3(256), 0, s, cm, first, count, boxes);
+      hipLaunchKernelGGL((boxes ? k_inflate_bits<0, true> : k_inflate_bits<0, false>), grid, dim3(256), 0, s, cm, first, count, boxes);
     return;
   }
   const int W = kTile + 2 * R, WS = (W + 3) & ~3;
