@@ -358,6 +358,18 @@ int navgpu_planner_cycle(navgpu_fleet* fleet, uint32_t first, uint32_t count);
  * stop-and-rotate controller keeps using them across cycles).  enable = 0: every cycle searches the whole grid, as
  * the reference does.  Planner results are identical either way. */
 int navgpu_planner_set_bounded_map_grids(navgpu_fleet* fleet, int32_t enable);
+/* Wavefront seed lists (no counterpart in the reference; results are identical either way).  enable = 1 (the default): a
+ * cycle turns each robot's plan into the seed cells of its three MapGrids once (adjustPlanResolution + setTargetCells |
+ * setLocalGoal, map_grid.cpp:135-258), ahead of the wavefronts, which then only scatter the cells.  enable = 0: every
+ * wavefront walks the plan itself, as the launches outside a cycle always do.  Takes effect at the next cycle. */
+int navgpu_planner_set_seed_lists(navgpu_fleet* fleet, int32_t enable);
+/* Test hook: the seed cells a list holds, 1 .. 1024 (the default).  A (robot, grid) with more seed cells than that has no
+ * list that cycle and its wavefront walks the plan.  NAVGPU_ERR_INVALID outside the range. */
+int navgpu_planner_set_seed_list_capacity(navgpu_fleet* fleet, uint32_t cells);
+/* introspection: the seed cells k_samples listed for the path / goal / goal_front wavefront of each instance the last time a
+ * cycle with seed lists ran for it (counts = count x 3; duplicates count), 0xFFFFFFFF where the cells did not fit or no such
+ * cycle has run. */
+int navgpu_planner_seed_list_counts(navgpu_fleet* fleet, uint32_t first, uint32_t count, uint32_t* counts);
 /* replaces: the MapGridCostFunction constructor arguments DWAPlanner never passes (map_grid_cost_function.h:64-69,
  * map_grid_cost_function.cpp:42-53, 75-129): aggregationType (0 Last - what DWAPlanner's four critics use -, 1 Sum,
  * 2 Product) and yshift (metres, sideways) of one critic: 0 path_costs_, 1 goal_costs_, 2 goal_front_costs_,

@@ -17,6 +17,8 @@ namespace navgpu {
 constexpr uint8_t kNoInfo = 255, kLethal = 254, kInscribed = 253, kFree = 0;
 constexpr int kMaxFootprint = 32;
 constexpr int kCareRows = 128, kCareWords = 4;  // bounded wavefronts: extent of the per-robot pocket mask (k_samples)
+constexpr uint32_t kSeedListMax = 1024;         // wavefront seed lists: entries allocated per (robot, grid) (k_samples)
+constexpr uint32_t kNoSeedList = 0xFFFFFFFFu;   // ... a list's count when its cells did not fit: that wavefront seeds from the plan
 #ifndef NAVGPU_SCORE_TAB_THREADS
 #define NAVGPU_SCORE_TAB_THREADS 256  // samples per k_score_sweep workgroup (as for round 2's table kernel - 512 with a 52 KB image: 0.523 ms; 256 with 26 KB: 0.516 ms, configs[4] 2.17 -> 1.82 ms)
 #endif
@@ -145,6 +147,9 @@ struct PlannerDev {
   uint32_t* bfs_free;         // [n][ny][W] traversable-cell bitmap of the costmaps (k_free_bits, per launch_bfs)
   uint32_t* bfs_levels;       // [n][3] levels the last wavefront of (robot, grid) ran: predicts the next one's length
   uint32_t* bfs_order;        // [n * 3] items of a launch sorted longest first, stored at first * 3 (k_samples)
+  uint32_t* bfs_seed_cells;   // [n][3][kSeedListMax] seed cells of (robot, grid) as row * 32 * (words per bitmap row) + column: bitmap word << 5 | bit (k_samples)
+  uint32_t* bfs_seed_count;   // [n][3] entries of each list, or kNoSeedList
+  uint32_t bfs_seed_cap;      // launch switch: 0 = every wavefront seeds from the plan itself, else k_samples fills the lists with up to that many cells
   uint32_t bfs_grids;         // wavefronts per robot: 3 (DWA: path, goal, goal_front) or 2 (legacy TrajectoryPlanner)
   uint32_t* within;           // legacy planner: [n][ny][W] MapCell::within_robot bits of path_map_ on entry to launch_bfs, whose k_free_bits ORs the costmap's free bits in (= path_map_'s traversable-cell bitmap); else null
   uint32_t win;               // edge (cells) of the costmap window staged in LDS by k_score

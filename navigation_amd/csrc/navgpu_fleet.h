@@ -93,6 +93,10 @@ struct navgpu_fleet {
   // bounded MapGrid wavefronts (navgpu_planner_set_bounded_map_grids): which robots hold grids that are exact inside
   // their box only, that box, and whether the inputs of the cycle that made them are still the staged ones
   bool bounded_grids = true;
+  // wavefront seed lists (navgpu_planner_set_seed_lists, navgpu_planner_set_seed_list_capacity): a cycle's k_samples turns every
+  // robot's plan into the seed cells of its three grids, once, and the wavefronts behind it scatter them
+  bool seed_lists = true;
+  uint32_t seed_list_cap = kSeedListMax;
   std::vector<uint8_t> grid_partial;            // [n]
   std::vector<int32_t> h_box;                   // [n][4] x0, x1, y0, y1 of the last bounded cycle
   std::vector<uint64_t> inputs_gen, cycle_gen;  // [n] bumped by whatever a wavefront reads / value at the last cycle

@@ -226,6 +226,9 @@ int navgpu_fleet_create(const navgpu_fleet_desc* d, navgpu_fleet** out) {
   A(pl.bfs_free, (size_t)n * cm.ny * ((cm.nx + 31) / 32));
   A(pl.bfs_levels, (size_t)n * 3);
   A(pl.bfs_order, (size_t)n * 3);
+  A(pl.bfs_seed_cells, (size_t)n * 3 * kSeedListMax);
+  A(pl.bfs_seed_count, (size_t)n * 3);
+  pl.bfs_seed_cap = 0;
   pl.bfs_bounded = 0;
   A(pl.counters, (size_t)n * 2);
   A(pl.osc_flags, n);
@@ -257,6 +260,7 @@ int navgpu_fleet_create(const navgpu_fleet_desc* d, navgpu_fleet** out) {
   hipError_t e = hipMemcpyAsync(cm.state, st.data(), sizeof(InstCostmapState) * n, hipMemcpyHostToDevice, f->stream);
   if (e == hipSuccess) e = hipMemsetAsync(pl.bfs_reach, 0, sizeof(uint32_t) * n, f->stream);
   if (e == hipSuccess) e = hipMemsetAsync(pl.bfs_levels, 0, sizeof(uint32_t) * 3 * n, f->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(pl.bfs_seed_count, 0xFF, sizeof(uint32_t) * 3 * n, f->stream);  // kNoSeedList
   if (e == hipSuccess) e = waitStream(f->stream);
   if (e != hipSuccess || checkLaunch() != NAVGPU_OK) {
     if (e != hipSuccess) g_last_error = std::string("fleet init: ") + hipGetErrorString(e);
@@ -1101,6 +1105,7 @@ extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, uint32_t first, ui
     }
   PlannerDev pl = f->pl;
   pl.bfs_bounded = 0;
+  pl.bfs_seed_cap = 0;  // (no k_samples in front of these launches: the lists are some earlier cycle's)
   for (uint32_t i = first; i < first + count;) {
     if (!f->grid_partial[i]) {
       ++i;
@@ -1143,6 +1148,32 @@ int navgpu_planner_set_bounded_map_grids(navgpu_fleet* f, int32_t enable) {
   FleetGuard guard_(f);
   f->bounded_grids = enable != 0;
   return restageReach(f);
+}
+// Wavefront seed lists.  The switch and the capacity take effect at the next cycle: a cycle passes them to its own k_samples
+// and wavefront launches, and no list outlives the cycle that wrote it.
+int navgpu_planner_set_seed_lists(navgpu_fleet* f, int32_t enable) {
+  if (!f) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  f->seed_lists = enable != 0;
+  return NAVGPU_OK;
+}
+int navgpu_planner_set_seed_list_capacity(navgpu_fleet* f, uint32_t cells) {
+  if (!f || cells == 0 || cells > kSeedListMax) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  f->seed_list_cap = cells;
+  return NAVGPU_OK;
+}
+int navgpu_planner_seed_list_counts(navgpu_fleet* f, uint32_t first, uint32_t count, uint32_t* counts) {
+  if (!f || !counts || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  HIP_TRY(hipMemcpyAsync(counts, f->pl.bfs_seed_count + (size_t)first * 3, sizeof(uint32_t) * 3 * count, hipMemcpyDeviceToHost, f->stream));
+  HIP_TRY(waitStream(f->stream));
+  return NAVGPU_OK;
+}
+// what a cycle's launches get for pl.bfs_seed_cap (a list entry is a bitmap bit index: it has to fit 32 bits)
+static uint32_t seedListCap(const navgpu_fleet* f) {
+  const uint64_t bits = 32ull * ((f->pl.nx + 31) / 32) * f->pl.ny;
+  return (f->seed_lists && bits <= 0xFFFFFFFFull) ? f->seed_list_cap : 0u;
 }
 int navgpu_planner_set_map_grid_options(navgpu_fleet* f, int32_t critic, int32_t aggregation, double yshift) {
   if (!f || critic < 0 || critic > 3 || aggregation < 0 || aggregation > 2 || !std::isfinite(yshift)) return NAVGPU_ERR_INVALID;
@@ -1547,6 +1578,7 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
     pl.result = f->hp_result + (size_t)(prev_slot ^ 1) * f->desc.n_instances;  // (the slot flips once the launches are out)
   }
   pl.bfs_bounded = 1;  // per robot: bfs_reach (0 = whole grid)
+  pl.bfs_seed_cap = seedListCap(f);
   for (uint32_t i = first; i < first + count; ++i) {
     f->grid_partial[i] = robotBox(f, i, f->hp_state[i].pos, f->hp_reach[i], &f->h_box[(size_t)4 * i]) ? 1 : 0;
     f->cycle_gen[i] = f->inputs_gen[i];
@@ -1607,6 +1639,7 @@ int navgpu_planner_cycle_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t
   HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
   cl.ev_set = true;
   pl.bfs_bounded = 1;  // per robot: bfs_reach (0 = whole grid)
+  pl.bfs_seed_cap = seedListCap(f);
   for (uint32_t k = 0; k < n_robots; ++k) {
     const uint32_t i = instances[k];
     f->grid_partial[i] = robotBox(f, i, f->hp_state[i].pos, f->hp_reach[i], &f->h_box[(size_t)4 * i]) ? 1 : 0;

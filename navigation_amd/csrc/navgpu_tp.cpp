@@ -192,6 +192,7 @@ static int tpLaunchGrids(navgpu_fleet* f, uint32_t first, uint32_t count, bool w
   pl.within = with_within ? f->tp.within_bits : nullptr;
   pl.cfg.allow_unknown = f->tp.cfg.allow_unknown;
   pl.bfs_bounded = 0;  // the legacy planner's look-ups are not confined to a box around the robot
+  pl.bfs_seed_cap = 0;  // no k_samples in front of this launch: the wavefronts seed from the plan
   for (uint32_t i = first; i < first + count; ++i) f->grid_partial[i] = 0;
   PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, first, count, f->stream));
   return NAVGPU_OK;

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, Robots robot
   const uint32_t N_obst = pl.cells, N_unreach = pl.cells + 1;
   const uint32_t last_mask = (nx & 31) ? ((1u << (nx & 31)) - 1u) : 0xFFFFFFFFu;
   const uint32_t* freew = bfsFreeBitmap(pl, which, inst, words);  // k_free_bits (or the extra blocks of k_samples)
+  const BfsSeedList seeds = bfsSeedList(pl, inst, which, tid);
   for (uint32_t w = tid; w < words; w += blockDim.x) {
     const uint32_t row = w / W, wi = w - row * W;
     fre[w] = freew[w] & ((wi + 1 == W) ? last_mask : 0xFFFFFFFFu);
@@ -54,10 +55,18 @@ __global__ __launch_bounds__(1024) void k_bfs_global(PlannerDev pl, Robots robot
     nxt[w] = 0;
   }
   __syncthreads();
-  bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
-    atomicOr(&cur[my * W + (mx >> 5)], 1u << (mx & 31));
-    dist[my * nx + mx] = 0;
-  });
+  if (seeds.listed) {
+    bfsListSeeds(seeds, tid, [&](uint32_t e) {
+      const uint32_t w = e >> 5, my = w / W;
+      atomicOr(&cur[w], 1u << (e & 31));
+      dist[my * nx + (w - my * W) * 32 + (e & 31)] = 0;
+    });
+  } else {
+    bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
+      atomicOr(&cur[my * W + (mx >> 5)], 1u << (mx & 31));
+      dist[my * nx + mx] = 0;
+    });
+  }
   __syncthreads();
   for (uint32_t w = tid; w < words; w += blockDim.x) vis[w] |= cur[w];
   // Activity-driven levels: the map is cut into tiles of 4 words x 16 rows (128 x 16 cells, one wave each; tile
@@ -204,10 +213,12 @@ uint32_t bfs_cu_count() {
 // Every wavefront kernel stops a bounded search at its robot's region (pl.bfs_bounded) and runs the legacy
 // planner's two-grid launches (pl.bfs_grids == 2, pl.within) as well: k_bfs_rows for maps up to 640 x 800, k_bfs_rows2 up to
 // 1024 x 1344, k_bfs_global beyond.  order: the launch's items longest first (k_samples), or null.
-void launch_bfs(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
-  if (!free_ready) {  // (a planner cycle has both done by its k_samples launch)
+void launch_bfs(const PlannerDev& pl_, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
+  PlannerDev pl = pl_;
+  if (!free_ready) {  // (a planner cycle has all three done by its k_samples launch)
     hipLaunchKernelGGL(k_free_bits, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, first);
     hipMemsetAsync(pl.bfs_next_item, 0, 2 * sizeof(uint32_t), s);
+    pl.bfs_seed_cap = 0;  // no seed lists either: the wavefronts walk the plans
   }
   if (launch_bfs_rows(pl, first, count, s, order)) return;
   if (launch_bfs_rows2(pl, first, count, s, order)) return;

@@ -56,6 +56,30 @@ __device__ __forceinline__ void bfsPlanSeeds(const PlannerDev& pl, const uint32_
     });
 }
 
+// The same cells as a list: in a cycle the k_samples launch in front of the wavefronts runs bfsPlanSeeds once per (robot,
+// grid) and leaves the cells in pl.bfs_seed_cells (pl.bfs_seed_cap != 0 for both launches), so an item only scatters them.
+// An entry is the cell's bit index in a [ny][Wr] bitmap, word << 5 | bit.  A list is not there when the launch has no
+// k_samples in front of it (cap 0) or the cells did not fit (count kNoSeedList): then the item walks the plan itself.
+struct BfsSeedList {
+  const uint32_t* cells;
+  uint32_t n;      // (uniform over the workgroup)
+  uint32_t first;  // this lane's first entry, loaded ahead of the item's zeroing pass
+  bool listed;
+};
+__device__ __forceinline__ BfsSeedList bfsSeedList(const PlannerDev& pl, const uint32_t inst, const int which, const uint32_t tid) {
+  BfsSeedList l{pl.bfs_seed_cells + ((size_t)inst * 3 + which) * kSeedListMax, 0, 0, false};
+  if (pl.bfs_seed_cap) l.n = __builtin_amdgcn_readfirstlane(pl.bfs_seed_count[(size_t)inst * 3 + which]);
+  l.listed = pl.bfs_seed_cap != 0 && l.n <= kSeedListMax;
+  if (l.listed && tid < l.n) l.first = l.cells[tid];
+  return l;
+}
+// set(entry) once per cell of the list, every lane of the workgroup taking a slice
+template <typename Set>
+__device__ __forceinline__ void bfsListSeeds(const BfsSeedList& l, const uint32_t tid, Set&& set) {
+  if (tid < l.n) set(l.first);
+  for (uint32_t i = tid + blockDim.x; i < l.n; i += blockDim.x) set(l.cells[i]);
+}
+
 // The robot's region: its box grown by two cells (k_samples), in cells x0 .. x1, y0 .. y1 and bitmap words w0 .. w1, and
 // whether its pockets are known (care_ok: pl.bfs_care holds the mask).  A search that is not bounded - the launch is not,
 // or the robot has no box this cycle - has the whole map for a region and no pocket mask: nothing is ever "settled".

@@ -144,7 +144,6 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   uint32_t* care_l = sm + seed_words;                     // [kCareRows][kCareWords]
   uint32_t* edge = care_l + kCareRows * kCareWords;       // [nw + 2][top | bottom][D rows][frontier WP | blocked WP]; slot = wave + 1
   constexpr uint32_t RS = 2 * WP + kRowsRecordPad;  // record stride (words)
-  const uint32_t edge_words = (nw + 2) * 2 * D * RS;
   const uint8_t* master = pl.master + (size_t)inst * pl.cells_padded;
   const uint32_t* freew = bfsFreeBitmap(pl, which, inst, ny * Wr);
   uint32_t* dist = (which == 0 ? pl.path : (which == 1 ? pl.goal : pl.goal_front)) + (size_t)inst * pl.cells;
@@ -152,7 +151,15 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   const uint32_t last_mask = (nx & 31) ? ((1u << (nx & 31)) - 1u) : 0xFFFFFFFFu;
   const bool aligned4 = (nx & 3) == 0;
 
-  for (uint32_t i = tid; i < seed_words + kCareRows * kCareWords + edge_words; i += blockDim.x) sm[i] = 0;
+  const BfsSeedList seeds = bfsSeedList(pl, inst, which, tid);
+  {
+    // What an item has to find zeroed: the seed bitmap, the care words and, of the exchange records, the two border slots
+    // (the rows above the map's first and below its last: no wave publishes into them).  The first of those follows the care
+    // words, the other is the last thing in the buffer; every part is whole 16-byte units.
+    uint4* sm4 = reinterpret_cast<uint4*>(sm);
+    const uint32_t slot4 = 2 * D * RS / 4, head4 = (seed_words + kCareRows * kCareWords) / 4 + slot4, tail4 = head4 + nw * slot4;
+    for (uint32_t i = tid; i < head4 + slot4; i += blockDim.x) sm4[i < head4 ? i : tail4 + (i - head4)] = make_uint4(0, 0, 0, 0);
+  }
   if (tid < 3) s_flag[tid] = s_open[tid] = 0;
   __syncthreads();
   bfsStamp(pl, tid, item, 4);
@@ -160,10 +167,14 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
     const uint32_t* care = pl.bfs_care + (size_t)inst * kCareRows * kCareWords;
     for (uint32_t i = tid; i < (uint32_t)(kCareRows * kCareWords); i += blockDim.x) care_l[i] = care[i];
   }
-  // --- seeds from the plan
-  bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
-    atomicOr(&seedm[my * Wr + (mx >> 5)], 1u << (mx & 31));  // a few hundred seeds, once
-  });
+  // --- seeds: the cycle's list, or from the plan
+  if (seeds.listed) {
+    bfsListSeeds(seeds, tid, [&](uint32_t e) { atomicOr(&seedm[e >> 5], 1u << (e & 31)); });
+  } else {
+    bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
+      atomicOr(&seedm[my * Wr + (mx >> 5)], 1u << (mx & 31));  // a few hundred seeds, once
+    });
+  }
   __syncthreads();
   bfsStamp(pl, tid, item, 5);
 
@@ -585,7 +596,6 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   const uint32_t rowA = realA ? (uint32_t)rowA_i : 0u, rowB = realB ? (uint32_t)rowB_i : 0u;
   uint32_t* care_l = sm;                             // [kCareRows][kCareWords]
   uint32_t* edge = care_l + kCareRows * kCareWords;  // [nw + 2][top | bottom][HL lanes][A frontier | A blocked | B frontier | B blocked][W]; slot = wave + 1
-  const uint32_t edge_words = (nw + 2) * 2 * HL * 4 * W;
   const uint8_t* master = pl.master + (size_t)inst * pl.cells_padded;
   const uint32_t* freew = bfsFreeBitmap(pl, which, inst, ny * Wr);
   uint32_t* dist = (which == 0 ? pl.path : (which == 1 ? pl.goal : pl.goal_front)) + (size_t)inst * pl.cells;
@@ -593,8 +603,20 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
   const uint32_t last_mask = (nx & 31) ? ((1u << (nx & 31)) - 1u) : 0xFFFFFFFFu;
   const bool aligned4 = (nx & 3) == 0;
 
-  for (uint32_t i = tid; i < kCareRows * kCareWords + edge_words; i += blockDim.x) sm[i] = 0;
-  for (uint32_t i = tid; i < ny * Wr; i += blockDim.x) seedw[i] = 0;
+  const BfsSeedList seeds = bfsSeedList(pl, inst, which, tid);
+  {
+    // zeroed per item, as in bfsRowsGrid: the care words and the exchange's two border slots (the first follows the care words,
+    // the other is the last thing in the buffer), in 16-byte units; and the seed bitmap, in 16-byte units where it is made of them
+    uint4* sm4 = reinterpret_cast<uint4*>(sm);
+    const uint32_t slot4 = 2 * HL * 4 * W / 4, head4 = kCareRows * kCareWords / 4 + slot4, tail4 = head4 + nw * slot4;
+    for (uint32_t i = tid; i < head4 + slot4; i += blockDim.x) sm4[i < head4 ? i : tail4 + (i - head4)] = make_uint4(0, 0, 0, 0);
+    const uint32_t words = ny * Wr;
+    if ((words & 3u) == 0) {  // (a workgroup's bitmap starts a multiple of `words` into the scratch)
+      for (uint32_t i = tid; i < words / 4; i += blockDim.x) reinterpret_cast<uint4*>(seedw)[i] = make_uint4(0, 0, 0, 0);
+    } else {
+      for (uint32_t i = tid; i < words; i += blockDim.x) seedw[i] = 0;
+    }
+  }
   if (tid < 3) s_flag[tid] = s_open[tid] = 0;
   __syncthreads();
   bfsStamp(pl, tid, item, 4);
@@ -602,9 +624,13 @@ __device__ __forceinline__ void bfsRows2Grid(const PlannerDev& pl, const uint32_
     const uint32_t* care = pl.bfs_care + (size_t)inst * kCareRows * kCareWords;
     for (uint32_t i = tid; i < (uint32_t)(kCareRows * kCareWords); i += blockDim.x) care_l[i] = care[i];
   }
-  bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
-    atomicOr(&seedw[my * Wr + (mx >> 5)], 1u << (mx & 31));
-  });
+  if (seeds.listed) {
+    bfsListSeeds(seeds, tid, [&](uint32_t e) { atomicOr(&seedw[e >> 5], 1u << (e & 31)); });
+  } else {
+    bfsPlanSeeds(pl, inst, which, g, master, nx, tid, s_wave, [&](uint32_t mx, uint32_t my) {
+      atomicOr(&seedw[my * Wr + (mx >> 5)], 1u << (mx & 31));
+    });
+  }
   __syncthreads();
   bfsStamp(pl, tid, item, 5);
   // The seed words were zeroed and set by other lanes of this workgroup and read by an earlier item: drop this CU's stale L1

@@ -1,6 +1,6 @@
 // k_samples (gfx950): VelocityIterator + SimpleTrajectoryGenerator::initialise, and the per-robot preparation of the
 // MapGrid wavefronts (region, pockets, dispatch ranks, traversable-cell bitmaps) that shares its launch.
-#include "planner_common.h"
+#include "planner_bfs_common.h"
 
 namespace navgpu {
 
@@ -9,20 +9,42 @@ namespace navgpu {
 // SimpleTrajectoryGenerator::initialise (src/simple_trajectory_generator.cpp:60-135).
 // One lane per axis: `next += step_size` is a sequential fp64 accumulation and must stay one.
 // ------------------------------------------------------------------------------------------------
-// Three kinds of 128-thread blocks, all latency-bound and independent of each other, side by side:
+// Four kinds of 128-thread blocks, the first three latency-bound and independent of each other, side by side:
 //   [0, count)          one robot's wavefront region, pocket floods and care words (wave 0: the region's flood, wave 1: the
 //                       large area's), 
 //   [count, 2 count)    wave 0: the robot's three items ranked for the longest-first dispatch; wave 1: its velocity samples,
+//   [2 count, 5 count)  with pl.bfs_seed_cap only: the seed cells of one wavefront (grid by grid: path, goal, goal_front),
 //   behind them         the traversable-cell bitmaps of the launch, 128 words per block.
 constexpr int kSamplesThreads = 128;
+// (seven waves per SIMD is what the kernel's registers allowed before it had the seed blocks; their fp64 took it to 73, one
+// register past that, and to a scratch reservation.  With the bound: 71, none.)
 template <class Robots>
-__global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, Robots robots, uint32_t count) {
+__global__ __launch_bounds__(kSamplesThreads, 7) void k_samples(PlannerDev pl, Robots robots, uint32_t count) {
   const uint32_t tid = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+  const uint32_t seed_blocks = pl.bfs_seed_cap ? 3 * count : 0;
+  if (blockIdx.x >= 2 * count && blockIdx.x < 2 * count + seed_blocks) {
+    // The seed list of one (robot, grid): bfsPlanSeeds as a wavefront would run it, its cells appended in any order
+    // (duplicates and all: the wavefront ORs them into a bitmap).  More cells than the capacity: no list.
+    __shared__ uint32_t s_wave[16];
+    __shared__ uint32_t s_n;
+    const uint32_t b = blockIdx.x - 2 * count, which = b / count, inst = robots(b - which * count);
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    uint32_t* cells = pl.bfs_seed_cells + ((size_t)inst * 3 + which) * kSeedListMax;
+    const uint32_t cap = min(pl.bfs_seed_cap, kSeedListMax), pitch = ((pl.nx + 31) >> 5) * 32;
+    bfsPlanSeeds(pl, inst, (int)which, geomOf(pl, inst), pl.master + (size_t)inst * pl.cells_padded, pl.nx, threadIdx.x, s_wave, [&](uint32_t mx, uint32_t my) {
+      const uint32_t k = atomicAdd(&s_n, 1u);
+      if (k < cap) cells[k] = my * pitch + mx;
+    });
+    __syncthreads();
+    if (threadIdx.x == 0) pl.bfs_seed_count[(size_t)inst * 3 + which] = s_n <= cap ? s_n : kNoSeedList;
+    return;
+  }
   if (blockIdx.x >= 2 * count) {
     // the traversable-cell bitmaps of the launch (what k_free_bits does on its own for the other callers of launch_bfs):
     // throughput work that fills the CUs while the per-robot waves wait on memory
     const uint32_t W = (pl.nx + 31) >> 5, words = pl.ny * W, per = (words + kSamplesThreads - 1) / kSamplesThreads;
-    const uint32_t b = blockIdx.x - 2 * count, r = b / per, i = (b - r * per) * kSamplesThreads + threadIdx.x;
+    const uint32_t b = blockIdx.x - 2 * count - seed_blocks, r = b / per, i = (b - r * per) * kSamplesThreads + threadIdx.x;
     if (i < words) {
       const uint32_t row = i / W, wi = i - row * W;
       const uint32_t inst = robots(r);
@@ -290,8 +312,9 @@ __global__ __launch_bounds__(kSamplesThreads) void k_samples(PlannerDev pl, Robo
 template <class Robots>
 static void launchSamples(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s) {
   const uint32_t words = pl.ny * ((pl.nx + 31) / 32);
-  // (+ the bitmaps and the zeroed work counters of launch_bfs(..., free_ready))
-  hipLaunchKernelGGL(k_samples<Robots>, dim3(2 * count + count * ((words + kSamplesThreads - 1) / kSamplesThreads)), dim3(kSamplesThreads), 0, s, pl, robots, count);
+  // (+ the seed lists, the bitmaps and the zeroed work counters of launch_bfs(..., free_ready))
+  hipLaunchKernelGGL(k_samples<Robots>, dim3((pl.bfs_seed_cap ? 5 : 2) * count + count * ((words + kSamplesThreads - 1) / kSamplesThreads)), dim3(kSamplesThreads), 0, s, pl,
+                     robots, count);
 }
 void launch_samples(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) { launchSamples(pl, RobotRange{first}, count, s); }
 // the robots list[0 .. count) (device memory); the dispatch order goes where the range form of list[0] puts it

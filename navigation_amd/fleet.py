@@ -389,6 +389,21 @@ class Fleet:
         """navgpu_planner_set_bounded_map_grids: wavefronts stop once the robot's box is settled (default on)."""
         check(self.L.navgpu_planner_set_bounded_map_grids(self.h, 1 if enable else 0), "set_bounded_map_grids")
 
+    def set_seed_lists(self, enable):
+        """navgpu_planner_set_seed_lists: a cycle's k_samples turns the plans into the wavefronts' seed cells (default on)."""
+        check(self.L.navgpu_planner_set_seed_lists(self.h, 1 if enable else 0), "set_seed_lists")
+
+    def set_seed_list_capacity(self, cells):
+        """navgpu_planner_set_seed_list_capacity (test hook): a (robot, grid) with more seed cells walks the plan itself."""
+        check(self.L.navgpu_planner_set_seed_list_capacity(self.h, int(cells)), "set_seed_list_capacity")
+
+    def seed_list_counts(self, first=0, count=None):
+        """Seed cells listed for the path / goal / goal_front wavefronts, [count, 3]; 0xFFFFFFFF = no list."""
+        first, count = self._range(first, count)
+        out = np.zeros((count, 3), np.uint32)
+        check(self.L.navgpu_planner_seed_list_counts(self.h, first, count, _ptr(out)), "seed_list_counts")
+        return out
+
     def wavefront_levels(self, first=0, count=None):
         """Levels the last cycle's path / goal / goal_front wavefronts ran, [count, 3]."""
         first, count = self._range(first, count)
