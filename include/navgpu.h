@@ -309,6 +309,29 @@ int navgpu_costmap_update(navgpu_fleet* fleet, uint32_t first, uint32_t count);
 /* boxes = count x {x0, xn, y0, yn}: LayeredCostmap::getBounds (layered_costmap.h:131-137) */
 int navgpu_costmap_bounds(navgpu_fleet* fleet, uint32_t first, uint32_t count, int32_t* boxes);
 
+/* ---- the costmap update for a robot list.  The three calls above take [first, first + count); these take instances[0 .. n_robots),
+ * strictly increasing, each < n_instances (NAVGPU_ERR_INVALID otherwise), as navgpu_planner_*_list do: the robots of a fleet whose
+ * scan has just arrived, whichever they are, in one launch of each kernel; every robot outside the list stays byte for byte as it
+ * was.  Per-robot arrays (robot_poses, boxes) are indexed by list position; navgpu_observation::instance stays a fleet index and
+ * must be in the list (NAVGPU_ERR_INVALID).  Capacity checks are the range form's (NAVGPU_ERR_CAPACITY); a failed stage leaves
+ * nothing staged.  Without a rolling window the calls leave what the range calls leave when they run contiguous run by
+ * contiguous run over the same robots, bit for bit.
+ * A rolling_window fleet takes these calls for ANY list (the range calls take it as a whole only): the origins and shifts of the
+ * listed robots alone move, and the update shifts their grids alone, leaving the fleet's buffers where they are.  The pending
+ * shift stays one per fleet: NAVGPU_ERR_STATE for a second stage before the update, for an update of another list than the one
+ * staged, and for a range update behind a listed stage or the reverse. */
+/* replaces: ObstacleLayer::getMarkingObservations / getClearingObservations (:466-496); rolling window: LayeredCostmap::updateMap
+ * (layered_costmap.cpp:86-91) + Costmap2D::updateOrigin (costmap_2d.cpp:264-276) of the listed robots.  One packed upload of what
+ * is in use and one scatter launch (k_cm_stage_scatter). */
+int navgpu_costmap_stage_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const double* robot_poses,
+                              const navgpu_observation* observations, uint32_t n_observations, const float* points_xyz,
+                              uint32_t n_points_total);
+/* replaces: LayeredCostmap::updateMap(robot_x, robot_y, robot_yaw) (layered_costmap.cpp:79-150) of the listed robots; rolling
+ * window: Costmap2D::updateOrigin (costmap_2d.cpp:264-313) / VoxelLayer::updateOrigin (voxel_layer.cpp:385-440) of their grids first. */
+int navgpu_costmap_update_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances);
+/* boxes = n_robots x {x0, xn, y0, yn}: LayeredCostmap::getBounds (layered_costmap.h:131-137) */
+int navgpu_costmap_bounds_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, int32_t* boxes);
+
 /* layer-granular calls for the costmap_2d::Layer adapters (layer.h:50-130).  boxes = count x
  * {min_i, min_j, max_i, max_j} as handed to Layer::updateCosts, or NULL to use the boxes the
  * last navgpu_costmap_update computed on the device.
@@ -993,6 +1016,12 @@ int navgpu_obsbuf_buffer(navgpu_fleet* fleet, const navgpu_cloud* clouds, uint32
  * after the update) behaves as after it.  NAVGPU_ERR_CAPACITY, nothing staged, when the UNFILTERED sizes of a robot's kept
  * clouds sum to more than max_points. */
 int navgpu_obsbuf_stage(navgpu_fleet* fleet, uint32_t first, uint32_t count, const double* robot_poses, int64_t now_ns, int32_t* current_out);
+/* navgpu_obsbuf_stage for a robot list (the conventions of navgpu_costmap_stage_list; current_out is indexed by list position).
+ * replaces: ObstacleLayer::getMarkingObservations + getClearingObservations (:466-496) over ObservationBuffer::getObservations
+ * (observation_buffer.cpp:198-209) and isCurrent (:238-251), for the listed robots: the purge, last_updated and isCurrent rules are
+ * the range form's; the descriptors travel in the packed upload and k_obs_gather runs once, on the list. */
+int navgpu_obsbuf_stage_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const double* robot_poses, int64_t now_ns,
+                             int32_t* current_out);
 /* Synchronous read-back, for tests and debugging, of exactly what navgpu_obsbuf_stage would hand over for one robot: the
  * descriptors with the filtered n_points (first_point into points_xyz) and the global-frame points.  Changes no state (now_ns
  * is accepted for symmetry: the purge compares with last_updated).  Returns the number of observations, n_points_out the

@@ -486,6 +486,9 @@ SYMBOLS = [
     ("navgpu_costmap_stage", C.c_int, [vp, u32, u32, vp, vp, u32, vp, u32]),
     ("navgpu_costmap_update", C.c_int, [vp, u32, u32]),
     ("navgpu_costmap_bounds", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_costmap_stage_list", C.c_int, [vp, u32, vp, vp, vp, u32, vp, u32]),
+    ("navgpu_costmap_update_list", C.c_int, [vp, u32, vp]),
+    ("navgpu_costmap_bounds_list", C.c_int, [vp, u32, vp, vp]),
     ("navgpu_inflate", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_obstacle_update_bounds", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_obstacle_update_costs", C.c_int, [vp, u32, u32, vp]),
@@ -566,6 +569,7 @@ SYMBOLS = [
     ("navgpu_obsbuf_configure", C.c_int, [vp, vp, u32, u32, u32]),
     ("navgpu_obsbuf_buffer", C.c_int, [vp, vp, u32, vp, u32, vp, u32, C.c_int64]),
     ("navgpu_obsbuf_stage", C.c_int, [vp, u32, u32, vp, C.c_int64, vp]),
+    ("navgpu_obsbuf_stage_list", C.c_int, [vp, u32, vp, vp, C.c_int64, vp]),
     ("navgpu_obsbuf_observations", C.c_int, [vp, u32, C.c_int64, vp, u32, vp, u32, C.POINTER(u32)]),
     ("navgpu_obsbuf_set_global_frame", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_obsbuf_reset_last_updated", C.c_int, [vp, u32, u32, C.c_int64]),

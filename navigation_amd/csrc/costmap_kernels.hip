@@ -99,9 +99,9 @@ void launch_export_window(const uint8_t* master, uint32_t nx, uint32_t x0, uint3
 // value.  dst(x, y) = src(x + cell_ox, y + cell_oy) when that lies in the grid.  Ping-pong buffers,
 // the host swaps the pointers afterwards.
 // ------------------------------------------------------------------------------------------------
-template <class T>
-__global__ __launch_bounds__(256) void k_shift(const T* src, T* dst, CostmapDev cm, uint32_t first, T fill) {
-  const uint32_t inst = first + blockIdx.y;
+template <class T, class Robots>
+__global__ __launch_bounds__(256) void k_shift(const T* src, T* dst, CostmapDev cm, Robots robots, T fill) {
+  const uint32_t inst = robots(blockIdx.y);
   const int ox = cm.shift[2 * inst], oy = cm.shift[2 * inst + 1];
   const T* s = src + (size_t)inst * cm.cells_padded;
   T* d = dst + (size_t)inst * cm.cells_padded;
@@ -111,13 +111,42 @@ __global__ __launch_bounds__(256) void k_shift(const T* src, T* dst, CostmapDev 
     d[i] = (sx >= 0 && sy >= 0 && sx < (int)cm.nx && sy < (int)cm.ny) ? s[sy * cm.nx + sx] : fill;
   }
 }
-void launch_shift_u8(const uint8_t* src, uint8_t* dst, const CostmapDev& cm, uint32_t first, uint32_t count, uint8_t fill, hipStream_t s) {
+// The listed update of a rolling fleet (navgpu_costmap_update_list) shifts its robots into the ping-pong target as above and then
+// brings them back: the fleet-wide pointers stay where they are, and so does every byte of the robots outside the list.
+template <class T>
+__global__ __launch_bounds__(256) void k_shift_back(const T* alt, T* grid, CostmapDev cm, RobotList robots) {
+  const uint32_t inst = robots(blockIdx.y);
+  const T* s = alt + (size_t)inst * cm.cells_padded;
+  T* d = grid + (size_t)inst * cm.cells_padded;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < cm.cells; i += gridDim.x * blockDim.x) d[i] = s[i];
+}
+template <class T, class Robots>
+static void launchShift(const T* src, T* dst, const CostmapDev& cm, Robots robots, uint32_t count, T fill, hipStream_t s) {
   dim3 grid(min((cm.cells + 255) / 256, 64u), count);
-  hipLaunchKernelGGL(k_shift<uint8_t>, grid, dim3(256), 0, s, src, dst, cm, first, fill);
+  hipLaunchKernelGGL((k_shift<T, Robots>), grid, dim3(256), 0, s, src, dst, cm, robots, fill);
+}
+template <class T>
+static void launchShiftBack(const T* alt, T* grid_p, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s) {
+  dim3 grid(min((cm.cells + 255) / 256, 64u), count);
+  hipLaunchKernelGGL(k_shift_back<T>, grid, dim3(256), 0, s, alt, grid_p, cm, robots);
+}
+void launch_shift_u8(const uint8_t* src, uint8_t* dst, const CostmapDev& cm, uint32_t first, uint32_t count, uint8_t fill, hipStream_t s) {
+  launchShift(src, dst, cm, RobotRange{first}, count, fill, s);
 }
 void launch_shift_u32(const uint32_t* src, uint32_t* dst, const CostmapDev& cm, uint32_t first, uint32_t count, uint32_t fill, hipStream_t s) {
-  dim3 grid(min((cm.cells + 255) / 256, 64u), count);
-  hipLaunchKernelGGL(k_shift<uint32_t>, grid, dim3(256), 0, s, src, dst, cm, first, fill);
+  launchShift(src, dst, cm, RobotRange{first}, count, fill, s);
+}
+void launch_shift_u8(const uint8_t* src, uint8_t* dst, const CostmapDev& cm, RobotList robots, uint32_t count, uint8_t fill, hipStream_t s) {
+  launchShift(src, dst, cm, robots, count, fill, s);
+}
+void launch_shift_u32(const uint32_t* src, uint32_t* dst, const CostmapDev& cm, RobotList robots, uint32_t count, uint32_t fill, hipStream_t s) {
+  launchShift(src, dst, cm, robots, count, fill, s);
+}
+void launch_shift_back_u8(const uint8_t* alt, uint8_t* grid, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s) {
+  launchShiftBack(alt, grid, cm, robots, count, s);
+}
+void launch_shift_back_u32(const uint32_t* alt, uint32_t* grid, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s) {
+  launchShiftBack(alt, grid, cm, robots, count, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -571,10 +600,10 @@ __device__ __forceinline__ void clearFootprintPolygon(const CostmapDev& cm, cons
 // All rays write FREE_SPACE, so write-write races between them are benign.  The voxel clear phase in two passes equals the
 // reference's ray-by-ray order because bits only ever get cleared during the phase.
 // ------------------------------------------------------------------------------------------------
-template <bool VOXEL>
-__global__ __launch_bounds__(256) void k_obstacle(CostmapDev cm, uint32_t first, const double* bounds_io_in, double* bounds_io_out,
+template <bool VOXEL, class Robots>
+__global__ __launch_bounds__(256) void k_obstacle(CostmapDev cm, Robots robots, const double* bounds_io_in, double* bounds_io_out,
                                                   int only_bounds) {
-  const uint32_t inst = first + blockIdx.x, tid = threadIdx.x;
+  const uint32_t inst = robots(blockIdx.x), tid = threadIdx.x;
   ObstacleGrids L;
   L.g = Geom{cm.origin[2 * inst], cm.origin[2 * inst + 1], cm.res, cm.nx, cm.ny};
   L.layer = cm.obst + (size_t)inst * cm.cells_padded;
@@ -693,13 +722,20 @@ __device__ __forceinline__ UpdateBox inflateBox(const UpdateBox& box, int R, uin
   return UpdateBox{max(0, box.x0 - R), max(0, box.y0 - R), min((int)nx, box.xn + R), min((int)ny, box.yn + R)};
 }
 
-void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const double* bounds_in, int only_bounds, hipStream_t s) {
+template <class Robots>
+static void launchObstacle(const CostmapDev& cm, Robots robots, uint32_t count, const double* bounds_in, int only_bounds, hipStream_t s) {
   // bounds_in doubles as the in/out buffer in only_bounds mode
   double* bounds_out = const_cast<double*>(bounds_in);
   if (cm.layers & NAVGPU_LAYER_VOXEL)
-    hipLaunchKernelGGL(k_obstacle<true>, dim3(count), dim3(256), 0, s, cm, first, bounds_in, bounds_out, only_bounds);
+    hipLaunchKernelGGL((k_obstacle<true, Robots>), dim3(count), dim3(256), 0, s, cm, robots, bounds_in, bounds_out, only_bounds);
   else
-    hipLaunchKernelGGL(k_obstacle<false>, dim3(count), dim3(256), 0, s, cm, first, bounds_in, bounds_out, only_bounds);
+    hipLaunchKernelGGL((k_obstacle<false, Robots>), dim3(count), dim3(256), 0, s, cm, robots, bounds_in, bounds_out, only_bounds);
+}
+void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const double* bounds_in, int only_bounds, hipStream_t s) {
+  launchObstacle(cm, RobotRange{first}, count, bounds_in, only_bounds, s);
+}
+void launch_obstacle(const CostmapDev& cm, RobotList robots, uint32_t count, const double* bounds_in, int only_bounds, hipStream_t s) {
+  launchObstacle(cm, robots, count, bounds_in, only_bounds, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -715,11 +751,11 @@ void launch_obstacle(const CostmapDev& cm, uint32_t first, uint32_t count, const
 // ------------------------------------------------------------------------------------------------
 // ALIGNED: nx is a multiple of 16, so a group lies in one row and its box bitmap follows from its row and first column; else the
 // bitmap is built cell by cell (a group may cross any number of rows when nx < 16)
-template <bool ALIGNED, int STATIC, int OBST, bool LAYER_ONLY>
-__global__ __launch_bounds__(256) void k_merge(CostmapDev cm, uint32_t first, const int32_t* boxes, word_rules::FastDiv div_nx,
+template <bool ALIGNED, int STATIC, int OBST, bool LAYER_ONLY, class Robots>
+__global__ __launch_bounds__(256) void k_merge(CostmapDev cm, Robots robots, const int32_t* boxes, word_rules::FastDiv div_nx,
                                                      word_rules::FastDiv div_gpr) {
   using namespace word_rules;
-  const uint32_t inst = first + blockIdx.y;
+  const uint32_t inst = robots(blockIdx.y);
   UpdateBox box;
   if (!updateBox(cm, boxes, blockIdx.y, inst, box)) return;
   const int x0 = box.x0, y0 = box.y0, xn = box.xn, yn = box.yn;
@@ -764,8 +800,9 @@ __global__ __launch_bounds__(256) void k_merge(CostmapDev cm, uint32_t first, co
   *reinterpret_cast<uint4*>(cm.master + off) = out;
 }
 
-__global__ __launch_bounds__(256) void k_merge_bytes(CostmapDev cm, uint32_t first, const int32_t* boxes, int static_received, int layer_only) {
-  const uint32_t inst = first + blockIdx.y;
+template <class Robots>
+__global__ __launch_bounds__(256) void k_merge_bytes(CostmapDev cm, Robots robots, const int32_t* boxes, int static_received, int layer_only) {
+  const uint32_t inst = robots(blockIdx.y);
   UpdateBox box;
   if (!updateBox(cm, boxes, blockIdx.y, inst, box)) return;
   const int x0 = box.x0, y0 = box.y0, xn = box.xn, yn = box.yn;
@@ -848,42 +885,43 @@ __global__ __launch_bounds__(256) void k_merge_bytes(CostmapDev cm, uint32_t fir
   if (changed) *reinterpret_cast<uint4*>(cm.master + off) = make_uint4(mw[0], mw[1], mw[2], mw[3]);
 }
 
-template <bool ALIGNED, int STATIC, int OBST, bool LAYER_ONLY>
-static void launchMergeWords(const CostmapDev& cm, uint32_t first, const int32_t* boxes, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_merge<ALIGNED, STATIC, OBST, LAYER_ONLY>), grid, dim3(256), 0, s, cm, first, boxes, word_rules::fastDivOf(cm.nx),
+template <bool ALIGNED, int STATIC, int OBST, bool LAYER_ONLY, class Robots>
+static void launchMergeWords(const CostmapDev& cm, Robots robots, const int32_t* boxes, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_merge<ALIGNED, STATIC, OBST, LAYER_ONLY, Robots>), grid, dim3(256), 0, s, cm, robots, boxes, word_rules::fastDivOf(cm.nx),
                      word_rules::fastDivOf(cm.nx >= 16 ? cm.nx >> 4 : 1));
 }
-template <bool ALIGNED, int STATIC>
-static void launchMergeObst(const CostmapDev& cm, uint32_t first, const int32_t* boxes, dim3 grid, hipStream_t s, int obst, bool layer_only) {
+template <bool ALIGNED, int STATIC, class Robots>
+static void launchMergeObst(const CostmapDev& cm, Robots robots, const int32_t* boxes, dim3 grid, hipStream_t s, int obst, bool layer_only) {
   if (layer_only) {
     if (STATIC != 0) return;  // (never asked for: launch_merge passes 0)
     switch (obst) {
-      case 0: return launchMergeWords<ALIGNED, 0, 0, true>(cm, first, boxes, grid, s);
-      case 1: return launchMergeWords<ALIGNED, 0, 1, true>(cm, first, boxes, grid, s);
-      default: return launchMergeWords<ALIGNED, 0, 2, true>(cm, first, boxes, grid, s);
+      case 0: return launchMergeWords<ALIGNED, 0, 0, true>(cm, robots, boxes, grid, s);
+      case 1: return launchMergeWords<ALIGNED, 0, 1, true>(cm, robots, boxes, grid, s);
+      default: return launchMergeWords<ALIGNED, 0, 2, true>(cm, robots, boxes, grid, s);
     }
   }
   switch (obst) {
-    case 0: return launchMergeWords<ALIGNED, STATIC, 0, false>(cm, first, boxes, grid, s);
-    case 1: return launchMergeWords<ALIGNED, STATIC, 1, false>(cm, first, boxes, grid, s);
-    default: return launchMergeWords<ALIGNED, STATIC, 2, false>(cm, first, boxes, grid, s);
+    case 0: return launchMergeWords<ALIGNED, STATIC, 0, false>(cm, robots, boxes, grid, s);
+    case 1: return launchMergeWords<ALIGNED, STATIC, 1, false>(cm, robots, boxes, grid, s);
+    default: return launchMergeWords<ALIGNED, STATIC, 2, false>(cm, robots, boxes, grid, s);
   }
 }
-template <bool ALIGNED>
-static void launchMergeStatic(const CostmapDev& cm, uint32_t first, const int32_t* boxes, dim3 grid, hipStream_t s, int stat, int obst, bool layer_only) {
+template <bool ALIGNED, class Robots>
+static void launchMergeStatic(const CostmapDev& cm, Robots robots, const int32_t* boxes, dim3 grid, hipStream_t s, int stat, int obst, bool layer_only) {
   switch (stat) {
-    case 0: return launchMergeObst<ALIGNED, 0>(cm, first, boxes, grid, s, obst, layer_only);
-    case 1: return launchMergeObst<ALIGNED, 1>(cm, first, boxes, grid, s, obst, layer_only);
-    default: return launchMergeObst<ALIGNED, 2>(cm, first, boxes, grid, s, obst, layer_only);
+    case 0: return launchMergeObst<ALIGNED, 0>(cm, robots, boxes, grid, s, obst, layer_only);
+    case 1: return launchMergeObst<ALIGNED, 1>(cm, robots, boxes, grid, s, obst, layer_only);
+    default: return launchMergeObst<ALIGNED, 2>(cm, robots, boxes, grid, s, obst, layer_only);
   }
 }
 
-void launch_merge(const CostmapDev& cm, uint32_t first, uint32_t count, const int32_t* boxes, hipStream_t s, bool layer_only) {
+template <class Robots>
+static void launchMerge(const CostmapDev& cm, Robots robots, uint32_t count, const int32_t* boxes, hipStream_t s, bool layer_only) {
   uint32_t groups = (cm.cells + 15) / 16;
   dim3 grid((groups + 255) / 256, count);
   // the rolling static layer goes byte by byte (and so would a map of 2^31 cells or more: the word kernel divides by multiplication)
   if ((cm.stat_roll != nullptr && !layer_only) || cm.cells >= 0x80000000u) {
-    hipLaunchKernelGGL(k_merge_bytes, grid, dim3(256), 0, s, cm, first, boxes, cm.static_received, layer_only ? 1 : 0);
+    hipLaunchKernelGGL(k_merge_bytes<Robots>, grid, dim3(256), 0, s, cm, robots, boxes, cm.static_received, layer_only ? 1 : 0);
     return;
   }
   const bool has_static = (cm.layers & NAVGPU_LAYER_STATIC) && cm.static_received && !layer_only && cm.stat;
@@ -891,9 +929,15 @@ void launch_merge(const CostmapDev& cm, uint32_t first, uint32_t count, const in
   const int stat = !has_static ? 0 : (cm.static_use_maximum ? 2 : 1);
   const int obst = !has_obst ? 0 : (cm.combination_method == 0 ? 1 : (cm.combination_method == 1 ? 2 : 0));
   if (cm.nx % 16 == 0)
-    launchMergeStatic<true>(cm, first, boxes, grid, s, stat, obst, layer_only);
+    launchMergeStatic<true>(cm, robots, boxes, grid, s, stat, obst, layer_only);
   else
-    launchMergeStatic<false>(cm, first, boxes, grid, s, stat, obst, layer_only);
+    launchMergeStatic<false>(cm, robots, boxes, grid, s, stat, obst, layer_only);
+}
+void launch_merge(const CostmapDev& cm, uint32_t first, uint32_t count, const int32_t* boxes, hipStream_t s, bool layer_only) {
+  launchMerge(cm, RobotRange{first}, count, boxes, s, layer_only);
+}
+void launch_merge(const CostmapDev& cm, RobotList robots, uint32_t count, const int32_t* boxes, hipStream_t s, bool layer_only) {
+  launchMerge(cm, robots, count, boxes, s, layer_only);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -908,9 +952,10 @@ void launch_merge(const CostmapDev& cm, uint32_t first, uint32_t count, const in
 // itself depends on std::priority_queue tie order (SURVEY §7 hard part 1).
 // ------------------------------------------------------------------------------------------------
 constexpr int kTile = 64;
-__global__ __launch_bounds__(256) void k_inflate(CostmapDev cm, uint32_t first, const int32_t* boxes) {
+template <class Robots>
+__global__ __launch_bounds__(256) void k_inflate(CostmapDev cm, Robots robots, const int32_t* boxes) {
   extern __shared__ __align__(16) uint8_t lds[];
-  const uint32_t inst = first + blockIdx.z;
+  const uint32_t inst = robots(blockIdx.z);
   const int R = (int)cm.R;
   UpdateBox box;
   if (!updateBox(cm, boxes, blockIdx.z, inst, box)) return;
@@ -994,15 +1039,15 @@ __global__ __launch_bounds__(256) void k_inflate(CostmapDev cm, uint32_t first, 
 constexpr int kBX = 64, kBY = 32;
 // BOXES: the caller passes the boxes (Fleet.inflate(boxes)); else they are the ones finishBounds left in the robots' states.  Known at
 // the launch, so that the three of four workgroups that only find out that their tile is out of reach do not sort that out first.
-template <int RT, bool BOXES>
-__global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t first, uint32_t count, const int32_t* boxes) {
+template <int RT, bool BOXES, class Robots>
+__global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, Robots robots, uint32_t count, const int32_t* boxes) {
   // XCD-aware tile order: workgroups b and b + 8 of a launch (linear id, x fastest) share an XCD and its L2.  The grid is
-  // (8 * tiles_x, tiles_y, robots / 8) and the robot 8 * z + x % 8, so a robot's tiles follow one another on ONE XCD: the 2R
+  // (8 * tiles_x, tiles_y, robots / 8) and the robot the (8 * z + x % 8)-th of the launch's range or list, so a robot's tiles follow one another on ONE XCD: the 2R
   // halo a tile reads around its 64 x 32 cells is its neighbours' interior and comes from that L2 instead of from the fabric
   // once per XCD (FETCH_SIZE x 2 + WRITE_SIZE per launch: 84.8 -> 19.4 MB for the benchmark's 256 windows)
   const uint32_t tbx = blockIdx.x >> 3, tby = blockIdx.y, rz = blockIdx.z * 8u + (blockIdx.x & 7u);
   if (rz >= count) return;
-  const uint32_t inst = first + rz;
+  const uint32_t inst = robots(rz);
   const int R = RT > 0 ? RT : (int)cm.R;
   UpdateBox box;
   if (BOXES) {
@@ -1195,9 +1240,10 @@ __global__ __launch_bounds__(256) void k_inflate_bits(CostmapDev cm, uint32_t fi
 constexpr uint32_t kPqSeenWords = 5120, kPqWinBytes = 65536;  // largest window whose seen_ bitmap / cost bytes live in LDS
 constexpr size_t kPqLdsBytes = 150 * 1024;                    // one workgroup per CU: the rest of it is the heap's top
 constexpr uint32_t kPqTabEntries = 66 * 66;
-__global__ __launch_bounds__(64) void k_inflate_pq(CostmapDev cm, uint32_t first, const int32_t* boxes) {
+template <class Robots>
+__global__ __launch_bounds__(64) void k_inflate_pq(CostmapDev cm, Robots robots, const int32_t* boxes) {
   extern __shared__ __align__(16) uint8_t pq_sm[];
-  const uint32_t inst = first + blockIdx.x;
+  const uint32_t inst = robots(blockIdx.x);
   const uint32_t tid = threadIdx.x;
   UpdateBox box;
   if (!updateBox(cm, boxes, blockIdx.x, inst, box)) return;
@@ -1357,27 +1403,76 @@ __global__ __launch_bounds__(64) void k_inflate_pq(CostmapDev cm, uint32_t first
     }
 }
 
-void launch_inflate(const CostmapDev& cm, uint32_t first, uint32_t count, const int32_t* boxes, hipStream_t s) {
+template <class Robots>
+static void launchInflate(const CostmapDev& cm, Robots robots, uint32_t count, const int32_t* boxes, hipStream_t s) {
   if (!cm.infl_enabled) return;
   const int R = (int)cm.R;
   if (cm.infl_pq) {
     if (!cm.pq_heap || !cm.pq_seen || !cm.dist_lut) return;  // (a reconfigure that could not allocate them keeps the previous mode: navgpu_inflation_configure)
-    hipFuncSetAttribute((const void*)k_inflate_pq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPqLdsBytes);
-    hipLaunchKernelGGL(k_inflate_pq, dim3(count), dim3(64), kPqLdsBytes, s, cm, first, boxes);
+    hipFuncSetAttribute((const void*)k_inflate_pq<Robots>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPqLdsBytes);
+    hipLaunchKernelGGL(k_inflate_pq<Robots>, dim3(count), dim3(64), kPqLdsBytes, s, cm, robots, boxes);
     return;
   }
   if (cm.lut2_ok && R >= 1 && R <= 14) {
-    dim3 grid(8u * ((cm.nx + kBX - 1) / kBX), (cm.ny + kBY - 1) / kBY, (count + 7u) / 8u);  // (robot = 8 z + x % 8: see the kernel)
+    dim3 grid(8u * ((cm.nx + kBX - 1) / kBX), (cm.ny + kBY - 1) / kBY, (count + 7u) / 8u);  // (robot = the (8 z + x % 8)-th: see the kernel)
     if (R == 11)
-      hipLaunchKernelGGL((boxes ? k_inflate_bits<11, true> : k_inflate_bits<11, false>), grid, dim3(256), 0, s, cm, first, count, boxes);
+      hipLaunchKernelGGL((boxes ? k_inflate_bits<11, true, Robots> : k_inflate_bits<11, false, Robots>), grid, dim3(256), 0, s, cm, robots, count, boxes);
     else
-      hipLaunchKernelGGL((boxes ? k_inflate_bits<0, true> : k_inflate_bits<0, false>), grid, dim3(256), 0, s, cm, first, count, boxes);
+      hipLaunchKernelGGL((boxes ? k_inflate_bits<0, true, Robots> : k_inflate_bits<0, false, Robots>), grid, dim3(256), 0, s, cm, robots, count, boxes);
     return;
   }
   const int W = kTile + 2 * R, WS = (W + 3) & ~3;
   size_t lds = (size_t)W * WS + (size_t)W * kTile + (size_t)(R + 2) * (R + 2);
   dim3 grid((cm.nx + kTile - 1) / kTile, (cm.ny + kTile - 1) / kTile, count);
-  hipLaunchKernelGGL(k_inflate, grid, dim3(256), lds, s, cm, first, boxes);
+  hipLaunchKernelGGL(k_inflate<Robots>, grid, dim3(256), lds, s, cm, robots, boxes);
+}
+void launch_inflate(const CostmapDev& cm, uint32_t first, uint32_t count, const int32_t* boxes, hipStream_t s) {
+  launchInflate(cm, RobotRange{first}, count, boxes, s);
+}
+void launch_inflate(const CostmapDev& cm, RobotList robots, uint32_t count, const int32_t* boxes, hipStream_t s) {
+  launchInflate(cm, robots, count, boxes, s);
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_cm_stage_scatter (navgpu_costmap_stage_list, navgpu_obsbuf_stage_list): what navgpu_costmap_stage copies into the slots of a
+// contiguous range, for the robots of a list - one workgroup per record.  Records, footprint vertices, observation descriptors and
+// (navgpu_costmap_stage_list) points arrive packed in one upload, only what is in use; a robot's record names its slot and where
+// its share of each begins.  (fp_n <= kMaxFootprint, obs_count <= max_obs, n_points <= max_points: checked by the host.)
+// ------------------------------------------------------------------------------------------------
+constexpr int kCmScatterThreads = 256;
+__global__ __launch_bounds__(kCmScatterThreads) void k_cm_stage_scatter(CostmapDev cm, const CmStageRec* rec, const double* fp, const ObsCsr* obs,
+                                                                        const float* points, int rolling) {
+  const CmStageRec r = rec[blockIdx.x];
+  const uint32_t i = r.inst, tid = threadIdx.x;
+  if (tid == 0) {
+    cm.pose[3 * i] = r.pose[0];
+    cm.pose[3 * i + 1] = r.pose[1];
+    cm.pose[3 * i + 2] = r.pose[2];
+    cm.fp_n[i] = r.fp_n;
+    cm.obs_count[i] = r.obs_count;
+    if (rolling) {
+      cm.origin[2 * i] = r.origin[0];
+      cm.origin[2 * i + 1] = r.origin[1];
+      cm.shift[2 * i] = r.shift[0];
+      cm.shift[2 * i + 1] = r.shift[1];
+    }
+  }
+  if (tid < 2 * r.fp_n) cm.fp_world[(size_t)i * kMaxFootprint * 2 + tid] = fp[(size_t)r.fp_off * 2 + tid];
+  {
+    constexpr uint32_t kWords = sizeof(ObsCsr) / sizeof(uint32_t);
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(obs + r.obs_off);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(cm.obs + (size_t)i * cm.max_obs);
+    for (uint32_t j = tid; j < r.obs_count * kWords; j += kCmScatterThreads) dst[j] = src[j];
+  }
+  if (r.n_points) {
+    const float* src = points + (size_t)r.pts_off * 3;
+    float* dst = cm.points + (size_t)i * cm.max_points * 3;
+    for (uint32_t j = tid; j < r.n_points * 3; j += kCmScatterThreads) dst[j] = src[j];
+  }
+}
+void launch_cm_stage_scatter(const CostmapDev& cm, const CmStageRec* rec, const double* fp, const ObsCsr* obs, const float* points, int rolling,
+                             uint32_t n_robots, hipStream_t s) {
+  hipLaunchKernelGGL(k_cm_stage_scatter, dim3(n_robots), dim3(kCmScatterThreads), 0, s, cm, rec, fp, obs, points, rolling);
 }
 
 }  // namespace navgpu

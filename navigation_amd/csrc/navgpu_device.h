@@ -40,6 +40,23 @@ constexpr uint32_t kNoSeedList = 0xFFFFFFFFu;   // ... a list's count when its c
 #endif
 constexpr int kScoreThreads = NAVGPU_SCORE_THREADS;  // samples per k_score workgroup  // vertices kept in registers/LDS by the kernels
 
+// Which robot block or work item k of a launch belongs to: the k-th of a contiguous range (navgpu_planner_cycle, navgpu_costmap_update)
+// or of a strictly increasing list in device memory (navgpu_planner_cycle_list, navgpu_costmap_update_list).  Every kernel of the
+// planner cycle and of the costmap update is a template over one of the two, one copy of its body.  RobotRange has the size and
+// alignment of the `uint32_t first` it stands for: the range instantiations take the argument block, and compile to the code, they
+// had as plain kernels.
+struct RobotRange {
+  uint32_t first;
+  __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return first + k; }
+  __device__ __forceinline__ uint32_t front() const { return first; }
+};
+struct RobotList {
+  const uint32_t* list;
+  __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return list[k]; }
+  __device__ __forceinline__ uint32_t front() const { return list[0]; }
+};
+static_assert(sizeof(RobotRange) == sizeof(uint32_t) && alignof(RobotRange) == alignof(uint32_t), "the range kernels' argument block");
+
 struct InstCostmapState {  // per-instance state that persists across update cycles (device resident)
   double last_min_x, last_min_y, last_max_x, last_max_y;  // InflationLayer::last_* (inflation_layer.cpp:63-66)
   int32_t need_reinflation;                               // InflationLayer::need_reinflation_
@@ -322,6 +339,33 @@ void launch_fill_u8(uint8_t* dst, uint8_t v, size_t n, hipStream_t s);
 void launch_fill_u32(uint32_t* dst, uint32_t v, size_t n, hipStream_t s);
 void launch_shift_u8(const uint8_t* src, uint8_t* dst, const CostmapDev& cm, uint32_t first, uint32_t count, uint8_t fill, hipStream_t s);
 void launch_shift_u32(const uint32_t* src, uint32_t* dst, const CostmapDev& cm, uint32_t first, uint32_t count, uint32_t fill, hipStream_t s);
+// ---- the costmap update for a robot list (navgpu_costmap_*_list): robot k of a launch is robots.list[k], a device array, strictly
+// increasing; arrays indexed by block (bounds_in, boxes) stay indexed by list position
+void launch_obstacle(const CostmapDev& cm, RobotList robots, uint32_t count, const double* bounds_in, int only_bounds, hipStream_t s);
+void launch_merge(const CostmapDev& cm, RobotList robots, uint32_t count, const int32_t* boxes, hipStream_t s, bool layer_only = false);
+void launch_inflate(const CostmapDev& cm, RobotList robots, uint32_t count, const int32_t* boxes, hipStream_t s);
+void launch_shift_u8(const uint8_t* src, uint8_t* dst, const CostmapDev& cm, RobotList robots, uint32_t count, uint8_t fill, hipStream_t s);
+void launch_shift_u32(const uint32_t* src, uint32_t* dst, const CostmapDev& cm, RobotList robots, uint32_t count, uint32_t fill, hipStream_t s);
+// a rolling fleet's listed update: the listed robots' shifted grids from the ping-pong target back into place (the fleet-wide
+// pointers stay where they are, the unlisted robots' grids untouched)
+void launch_shift_back_u8(const uint8_t* alt, uint8_t* grid, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s);
+void launch_shift_back_u32(const uint32_t* alt, uint32_t* grid, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s);
+void launch_obs_gather(const ObsBufDev& ob, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s);
+// navgpu_costmap_stage_list / navgpu_obsbuf_stage_list: one robot's record of the packed upload.  The block holds the records, then the
+// world footprints' vertices in use, then the observation descriptors in use, then (navgpu_costmap_stage_list) the points in use.
+struct CmStageRec {
+  double pose[3];
+  double origin[2];   // rolling window: the robot's new origin
+  int32_t shift[2];   // ... and its pending shift in cells
+  uint32_t inst;      // the robot
+  uint32_t fp_n, fp_off;        // footprint vertices and the first of them among the packed vertices
+  uint32_t obs_count, obs_off;  // observations and the first of them among the packed descriptors
+  uint32_t n_points, pts_off;   // points in use and the first of them among the packed points (0, 0: they stay on the device)
+  uint32_t pad;
+};
+static_assert(sizeof(CmStageRec) == 80, "staged as an array of these in front of the vertices");
+void launch_cm_stage_scatter(const CostmapDev& cm, const CmStageRec* rec, const double* fp, const ObsCsr* obs, const float* points, int rolling,
+                             uint32_t n_robots, hipStream_t s);
 
 void launch_cell_costs(const PlannerDev& pl, uint32_t inst, float4* out, hipStream_t s);
 void launch_samples(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s);

@@ -45,6 +45,29 @@ int ensureCompleteGrids(navgpu_fleet* f, uint32_t first, uint32_t count);
 // count into the pinned mirrors, and for a rolling window the new origins and pending shift (host and device).  Shared by
 // navgpu_costmap_stage and navgpu_obsbuf_stage; the caller has waited for the mirrors and copies them afterwards.
 int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses);
+// The robots of a costmap stage call: the contiguous range of navgpu_costmap_stage / navgpu_obsbuf_stage, or the strictly increasing
+// list of their listed forms.  What the two forms share - the checks of the observations, the pinned mirrors' arithmetic - takes one.
+struct RobotSet {
+  uint32_t first, count;
+  const uint32_t* list;  // null: the range [first, first + count)
+  uint32_t operator[](uint32_t k) const { return list ? list[k] : first + k; }
+  bool has(uint32_t i) const { return list ? std::binary_search(list, list + count, i) : (i >= first && i - first < count); }
+};
+// instances[0 .. n_robots) strictly increasing, each < n_instances (navgpu_planner_check_trajectories' conventions)
+bool listOk(const navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances);
+// what a costmap stage call checks of its observations before it changes anything: every one for a robot of the set, within the
+// fleet's capacities and the caller's points
+int checkStageObservations(navgpu_fleet* f, const RobotSet& r, const navgpu_observation* obs, uint32_t n_obs, uint32_t n_points_total);
+// the set's pinned mirrors of descriptors and points from checked observations; its obs_consumed flags fall
+void stageObservationMirrors(navgpu_fleet* f, const RobotSet& r, const navgpu_observation* obs, uint32_t n_obs, const float* points);
+// the set's pinned mirrors of pose, transformed footprint and vertex count, and for a rolling window its host origins and shift
+// mirrors (stageRobotPoses' arithmetic: poses[k] belongs to robot r[k])
+void stagePoseMirrors(navgpu_fleet* f, const RobotSet& r, const double* poses);
+// The listed costmap stage (navgpu_costmap_stage_list, navgpu_obsbuf_stage_list), behind the mirrors: the packed block of the listed
+// robots - records, footprint vertices, descriptors in use and, with_points, the points in use - in one upload, k_cm_stage_scatter
+// behind it, the marker of two cycles in flight, and for a rolling window the pending shift of this list (navgpu_costmap_list.cpp)
+int reserveCostmapList(navgpu_fleet* f);
+int sendCostmapStageList(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, bool with_points);
 // navgpu_planner_stage_poses without its "a plan was staged" check: for robots whose plan is on the device and whose length and last
 // point the pinned mirrors hold (navgpu_host.cpp)
 int stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth);
@@ -70,6 +93,8 @@ struct navgpu_fleet {
   bool planner_configured = false, inflation_configured = false, planner_staged = false;
   bool shift_pending = false;                   // rolling window: staged origins not yet applied to the grids
   uint32_t shift_first = 0, shift_count = 0;
+  bool shift_listed = false;                    // ... staged by a listed call, for the robots of shift_list: the update that names them applies it
+  std::vector<uint32_t> shift_list;
   std::vector<void*> allocs;
   // host mirrors
   std::vector<double> h_origin;                 // [n][2]
@@ -284,6 +309,17 @@ struct navgpu_fleet {
     bool ev_set = false;
     uint8_t *d_stage = nullptr, *h_stage = nullptr; // [n] StageRec, then [n][max_plan][2] doubles (only the poses in use travel)
   } cl;
+  // the costmap update for a robot list (navgpu_costmap_*_list), allocated by the first listed call, sized for the whole fleet: the
+  // list the update's kernels read, and the listed stages' packed upload - a pinned block and its device twin
+  struct CostmapList {
+    uint32_t *d_list = nullptr, *h_list = nullptr;  // [n]
+    hipEvent_t ev_list = nullptr;                   // behind the copy out of h_list
+    bool ev_set = false;
+    uint8_t *d_stage = nullptr, *h_stage = nullptr; // [n] CmStageRec, [n][kMaxFootprint][2] doubles, [n][max_obs] ObsCsr, [n][max_points][3] floats (only what is in use travels)
+    hipEvent_t ev_stage = nullptr;                  // behind the copy out of h_stage
+    bool ev_stage_set = false;
+  } cml;
+  std::vector<uint32_t> chk_cnt, chk_used;      // [n] checkStageObservations' running counts
   std::vector<uint8_t> obs_consumed;            // [n] an update has run on what navgpu_costmap_stage staged last
   navgpu_rotate_recovery_params rot{0.017, 3.2, 1.0, 0.4, 0.10, 0, 0};  // rotate_recovery.cpp:60-66
   // scratch device buffers

@@ -282,7 +282,7 @@ int navgpu_fleet_destroy(navgpu_fleet* f) {
     hipEventDestroy(e.a);
     hipEventDestroy(e.b);
   }
-  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.ev_list})
+  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.ev_list, f->cml.ev_list, f->cml.ev_stage})
     if (e) hipEventDestroy(e);
   for (void* p : f->allocs) hipFree(p);
   for (void* p : f->pinned) hipHostFree(p);
@@ -859,31 +859,27 @@ int navgpu_set_footprint(navgpu_fleet* f, uint32_t first, uint32_t count, const 
 }  // extern "C"
 
 namespace navgpu {
-int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses) {
+void stagePoseMirrors(navgpu_fleet* f, const RobotSet& r, const double* poses) {
   CostmapDev& cm = f->cm;
   // rolling window: LayeredCostmap::updateMap :86-91 + Costmap2D::updateOrigin :264-276, evaluated here
-  // in fp64 exactly as the reference does; the grids are shifted on the device by navgpu_costmap_update
+  // in fp64 exactly as the reference does; the grids are shifted on the device by the update
   if (f->desc.rolling_window) {
     const double size_m_x = (cm.nx - 1 + 0.5) * cm.res, size_m_y = (cm.ny - 1 + 0.5) * cm.res;  // getSizeInMetersX/Y
-    for (uint32_t li = 0; li < count; ++li) {
-      double& ox = f->h_origin[(size_t)(first + li) * 2];
-      double& oy = f->h_origin[(size_t)(first + li) * 2 + 1];
+    for (uint32_t li = 0; li < r.count; ++li) {
+      const uint32_t i = r[li];
+      double& ox = f->h_origin[(size_t)i * 2];
+      double& oy = f->h_origin[(size_t)i * 2 + 1];
       const double new_origin_x = poses[3 * li] - size_m_x / 2, new_origin_y = poses[3 * li + 1] - size_m_y / 2;
       const int cell_ox = int((new_origin_x - ox) / cm.res), cell_oy = int((new_origin_y - oy) / cm.res);
       ox = ox + cell_ox * cm.res;
       oy = oy + cell_oy * cm.res;
-      f->hp_shift[2 * (first + li)] = cell_ox;
-      f->hp_shift[2 * (first + li) + 1] = cell_oy;
+      f->hp_shift[2 * i] = cell_ox;
+      f->hp_shift[2 * i + 1] = cell_oy;
     }
-    HIP_TRY(hipMemcpyAsync(cm.shift + (size_t)first * 2, f->hp_shift + (size_t)first * 2, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(hipMemcpyAsync(cm.origin + (size_t)first * 2, &f->h_origin[(size_t)first * 2], sizeof(double) * 2 * count, hipMemcpyHostToDevice, f->stream));
-    f->shift_pending = true;
-    f->shift_first = first;
-    f->shift_count = count;
   }
   // transformFootprint (footprint.cpp:103-118) per instance, fp64 libm
-  for (uint32_t li = 0; li < count; ++li) {
-    const uint32_t i = first + li;
+  for (uint32_t li = 0; li < r.count; ++li) {
+    const uint32_t i = r[li];
     const double x = poses[3 * li], y = poses[3 * li + 1], th = poses[3 * li + 2];
     f->hp_pose[3 * i] = x;
     f->hp_pose[3 * i + 1] = y;
@@ -894,30 +890,55 @@ int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const doubl
       f->hp_fpw[((size_t)i * kMaxFootprint + v) * 2] = x + (sx * cos_th - sy * sin_th);
       f->hp_fpw[((size_t)i * kMaxFootprint + v) * 2 + 1] = y + (sx * sin_th + sy * cos_th);
     }
+    f->hp_fpn[i] = f->h_fp_n[i];
   }
-  memcpy(f->hp_fpn + first, &f->h_fp_n[first], sizeof(uint32_t) * count);
+}
+int stageRobotPoses(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses) {
+  CostmapDev& cm = f->cm;
+  stagePoseMirrors(f, RobotSet{first, count, nullptr}, poses);
+  if (f->desc.rolling_window) {
+    HIP_TRY(hipMemcpyAsync(cm.shift + (size_t)first * 2, f->hp_shift + (size_t)first * 2, sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(cm.origin + (size_t)first * 2, &f->h_origin[(size_t)first * 2], sizeof(double) * 2 * count, hipMemcpyHostToDevice, f->stream));
+    f->shift_pending = true;
+    f->shift_listed = false;
+    f->shift_first = first;
+    f->shift_count = count;
+  }
   return NAVGPU_OK;
 }
-}  // namespace navgpu
-
-extern "C" {
-
-int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses, const navgpu_observation* obs,
-                         uint32_t n_obs, const float* points, uint32_t n_points_total) {
-  if (!f || !poses || !f->rangeOk(first, count) || (n_obs && (!obs || (!points && n_points_total)))) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
-  CostmapDev& cm = f->cm;
-  if (f->desc.rolling_window && f->shift_pending) return NAVGPU_ERR_STATE;  // previous stage not consumed by an update yet
-  if (f->desc.rolling_window) f->touchInputs(first, count);  // the origins move now
-  HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
-  for (uint32_t li = 0; li < count; ++li) f->hp_cnt[first + li] = f->hp_used[first + li] = 0;
-  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 0);
+bool listOk(const navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances) {
+  if (!n_robots || !instances || n_robots > f->desc.n_instances) return false;
+  for (uint32_t k = 0; k < n_robots; ++k)
+    if (instances[k] >= f->desc.n_instances || (k && instances[k] <= instances[k - 1])) return false;
+  return true;
+}
+int checkStageObservations(navgpu_fleet* f, const RobotSet& r, const navgpu_observation* obs, uint32_t n_obs, uint32_t n_points_total) {
+  const CostmapDev& cm = f->cm;
+  f->chk_cnt.resize(f->desc.n_instances);
+  f->chk_used.resize(f->desc.n_instances);
+  for (uint32_t k = 0; k < n_obs; ++k)
+    if (obs[k].instance < f->desc.n_instances) f->chk_cnt[obs[k].instance] = f->chk_used[obs[k].instance] = 0;
   for (uint32_t k = 0; k < n_obs; ++k) {
     const navgpu_observation& o = obs[k];
-    if (o.instance < first || o.instance >= first + count) return NAVGPU_ERR_INVALID;
+    if (!r.has(o.instance)) return NAVGPU_ERR_INVALID;
     const uint32_t i = o.instance;
-    if (f->hp_cnt[i] >= cm.max_obs || f->hp_used[i] + o.n_points > cm.max_points) return NAVGPU_ERR_CAPACITY;
+    if (f->chk_cnt[i] >= cm.max_obs || f->chk_used[i] + o.n_points > cm.max_points) return NAVGPU_ERR_CAPACITY;
     if ((uint64_t)o.first_point + o.n_points > n_points_total) return NAVGPU_ERR_INVALID;
+    ++f->chk_cnt[i];
+    f->chk_used[i] += o.n_points;
+  }
+  return NAVGPU_OK;
+}
+void stageObservationMirrors(navgpu_fleet* f, const RobotSet& r, const navgpu_observation* obs, uint32_t n_obs, const float* points) {
+  const CostmapDev& cm = f->cm;
+  for (uint32_t li = 0; li < r.count; ++li) {
+    const uint32_t i = r[li];
+    f->hp_cnt[i] = f->hp_used[i] = 0;
+    f->obs_consumed[i] = 0;
+  }
+  for (uint32_t k = 0; k < n_obs; ++k) {
+    const navgpu_observation& o = obs[k];
+    const uint32_t i = o.instance;
     ObsCsr& d = f->hp_obs[(size_t)i * cm.max_obs + f->hp_cnt[i]++];
     d.first_point = f->hp_used[i];
     d.n_points = o.n_points;
@@ -932,6 +953,25 @@ int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
       memcpy(&f->hp_pts[((size_t)i * cm.max_points + f->hp_used[i]) * 3], points + (size_t)o.first_point * 3, sizeof(float) * 3 * o.n_points);
     f->hp_used[i] += o.n_points;
   }
+}
+}  // namespace navgpu
+
+extern "C" {
+
+int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const double* poses, const navgpu_observation* obs,
+                         uint32_t n_obs, const float* points, uint32_t n_points_total) {
+  if (!f || !poses || !f->rangeOk(first, count) || (n_obs && (!obs || (!points && n_points_total)))) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  CostmapDev& cm = f->cm;
+  if (f->desc.rolling_window && f->shift_pending) return NAVGPU_ERR_STATE;  // previous stage not consumed by an update yet
+  const RobotSet set{first, count, nullptr};
+  {
+    int rc = checkStageObservations(f, set, obs, n_obs, n_points_total);
+    if (rc) return rc;
+  }
+  if (f->desc.rolling_window) f->touchInputs(first, count);  // the origins move now
+  HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
+  stageObservationMirrors(f, set, obs, n_obs, points);
   {
     int rc = stageRobotPoses(f, first, count, poses);
     if (rc) return rc;
@@ -958,6 +998,7 @@ int navgpu_costmap_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
 static int applyPendingShift(navgpu_fleet* f, uint32_t first, uint32_t count) {
   CostmapDev& cm = f->cm;
   if (!(f->desc.rolling_window && f->shift_pending)) return NAVGPU_OK;
+  if (f->shift_listed) return NAVGPU_ERR_STATE;  // staged by a listed call: navgpu_costmap_update_list of that list applies it
   if (first != f->shift_first || count != f->shift_count) return NAVGPU_ERR_STATE;
   // the ping-pong swap is fleet-wide, so a rolling fleet is staged and updated as a whole
   if (first != 0 || count != f->desc.n_instances) return NAVGPU_ERR_INVALID;
@@ -1363,14 +1404,7 @@ int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
   return NAVGPU_OK;
 }
 
-// ---- the cycle for a robot list: instances[0 .. n_robots) strictly increasing, each < n_instances (navgpu_planner_check_trajectories'
-// conventions)
-static bool listOk(const navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances) {
-  if (!n_robots || !instances || n_robots > f->desc.n_instances) return false;
-  for (uint32_t k = 0; k < n_robots; ++k)
-    if (instances[k] >= f->desc.n_instances || (k && instances[k] <= instances[k - 1])) return false;
-  return true;
-}
+// ---- the cycle for a robot list: instances[0 .. n_robots) strictly increasing, each < n_instances (listOk)
 // the buffers of the listed calls, all or none
 static int reserveCycleList(navgpu_fleet* f) {
   navgpu_fleet::CycleList& cl = f->cl;

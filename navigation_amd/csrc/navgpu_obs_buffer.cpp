@@ -90,6 +90,60 @@ void keptOf(const ObsBuf& ob, uint32_t inst, std::vector<Kept>& out, std::vector
   }
 }
 
+
+// The kept entries of a set's robots, on copies, and what their lists look like after the purge; the host knows the clouds' unfiltered
+// sizes only, so those bound the capacity.  Changes nothing.
+struct KeptSet {
+  std::vector<std::vector<Kept>> kept;             // [robot of the set]
+  std::vector<std::deque<ObsBuf::Entry>> purged;   // [robot of the set][source]
+};
+int keptOfSet(const navgpu_fleet* f, const RobotSet& set, KeptSet& ks) {
+  const ObsBuf& ob = f->ob;
+  ks.kept.assign(set.count, {});
+  ks.purged.clear();
+  ks.purged.reserve((size_t)set.count * ob.n_sources);
+  for (uint32_t li = 0; li < set.count; ++li) {
+    keptOf(ob, set[li], ks.kept[li], &ks.purged);
+    uint64_t upper = 0;
+    for (const Kept& k : ks.kept[li]) upper += k.e.n;
+    if (ks.kept[li].size() > f->cm.max_obs || upper > f->cm.max_points) return NAVGPU_ERR_CAPACITY;
+  }
+  return NAVGPU_OK;
+}
+// The commit of a stage call: the purged lists, last_now, isCurrent per robot of the set, and - once the pinned mirrors are free - the
+// set's descriptors with the ring slot of each in `pad`; its obs_consumed flags fall.
+int stageKept(navgpu_fleet* f, const RobotSet& set, KeptSet& ks, int64_t now, int32_t* current_out) {
+  ObsBuf& ob = f->ob;
+  const CostmapDev& cm = f->cm;
+  ob.last_now = now;
+  for (uint32_t li = 0; li < set.count; ++li)
+    for (uint32_t s = 0; s < ob.n_sources; ++s) ob.lists[(size_t)set[li] * ob.n_sources + s].entries.swap(ks.purged[(size_t)li * ob.n_sources + s]);
+  if (current_out)
+    for (uint32_t li = 0; li < set.count; ++li) current_out[li] = robotCurrent(ob, set[li], now);
+  HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
+  for (uint32_t li = 0; li < set.count; ++li) {
+    const uint32_t i = set[li];
+    f->obs_consumed[i] = 0;
+    f->hp_cnt[i] = (uint32_t)ks.kept[li].size();
+    f->hp_used[i] = 0;
+    for (size_t k = 0; k < ks.kept[li].size(); ++k) {
+      const Kept& kp = ks.kept[li][k];
+      const navgpu_obs_source_params& sp = ob.src[kp.source];
+      ObsCsr& d = f->hp_obs[(size_t)i * cm.max_obs + k];
+      d.first_point = 0;  // k_obs_gather fills these two from the slots' counts
+      d.n_points = 0;
+      d.flags = sp.flags;
+      d.pad = kp.source * ob.slots + kp.e.slot;  // the robot's ring slot, for k_obs_gather (which zeroes it)
+      d.ox = kp.e.origin[0];
+      d.oy = kp.e.origin[1];
+      d.oz = kp.e.origin[2];
+      d.obstacle_range = sp.obstacle_range;
+      d.raytrace_range = sp.raytrace_range;
+    }
+  }
+  return NAVGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -238,48 +292,13 @@ int navgpu_obsbuf_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const d
   if (!poses || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
   CostmapDev& cm = f->cm;
   if (f->desc.rolling_window && f->shift_pending) return NAVGPU_ERR_STATE;  // previous stage not consumed by an update yet
-  // the robots' kept entries, on copies; the host knows the clouds' unfiltered sizes only, so those bound the capacity
-  std::vector<std::vector<Kept>> kept(count);
-  std::vector<std::deque<ObsBuf::Entry>> purged;
-  purged.reserve((size_t)count * ob.n_sources);
-  for (uint32_t li = 0; li < count; ++li) {
-    keptOf(ob, first + li, kept[li], &purged);
-    uint64_t upper = 0;
-    for (const Kept& k : kept[li]) upper += k.e.n;
-    if (kept[li].size() > cm.max_obs || upper > cm.max_points) return NAVGPU_ERR_CAPACITY;
-  }
-  // ---- commit
-  ob.last_now = now;
-  for (uint32_t li = 0; li < count; ++li)
-    for (uint32_t s = 0; s < ob.n_sources; ++s) ob.lists[(size_t)(first + li) * ob.n_sources + s].entries.swap(purged[(size_t)li * ob.n_sources + s]);
-  if (current_out)
-    for (uint32_t li = 0; li < count; ++li) current_out[li] = robotCurrent(ob, first + li, now);
+  const RobotSet set{first, count, nullptr};
+  KeptSet ks;
+  int rc = keptOfSet(f, set, ks);
+  if (rc) return rc;
   if (f->desc.rolling_window) f->touchInputs(first, count);  // the origins move now
-  HIP_TRY(f->waitMirrors(f->ev_cm_h2d, f->ev_cm_set));  // the pinned mirrors may still feed an earlier copy
-  std::fill(f->obs_consumed.begin() + first, f->obs_consumed.begin() + first + count, 0);
-  for (uint32_t li = 0; li < count; ++li) {
-    const uint32_t i = first + li;
-    f->hp_cnt[i] = (uint32_t)kept[li].size();
-    f->hp_used[i] = 0;
-    for (size_t k = 0; k < kept[li].size(); ++k) {
-      const Kept& kp = kept[li][k];
-      const navgpu_obs_source_params& sp = ob.src[kp.source];
-      ObsCsr& d = f->hp_obs[(size_t)i * cm.max_obs + k];
-      d.first_point = 0;  // k_obs_gather fills these two from the slots' counts
-      d.n_points = 0;
-      d.flags = sp.flags;
-      d.pad = kp.source * ob.slots + kp.e.slot;  // the robot's ring slot, for k_obs_gather (which zeroes it)
-      d.ox = kp.e.origin[0];
-      d.oy = kp.e.origin[1];
-      d.oz = kp.e.origin[2];
-      d.obstacle_range = sp.obstacle_range;
-      d.raytrace_range = sp.raytrace_range;
-    }
-  }
-  {
-    int rc = stageRobotPoses(f, first, count, poses);
-    if (rc) return rc;
-  }
+  if ((rc = stageKept(f, set, ks, now, current_out))) return rc;
+  if ((rc = stageRobotPoses(f, first, count, poses))) return rc;
   // array by array also for the whole fleet: the block copy of navgpu_costmap_stage would carry the mirror of cm.points
   HIP_TRY(hipMemcpyAsync(cm.pose + (size_t)first * 3, f->hp_pose + (size_t)first * 3, sizeof(double) * 3 * count, hipMemcpyHostToDevice, f->stream));
   HIP_TRY(hipMemcpyAsync(cm.fp_world + (size_t)first * kMaxFootprint * 2, f->hp_fpw + (size_t)first * kMaxFootprint * 2, sizeof(double) * 2 * kMaxFootprint * (size_t)count, hipMemcpyHostToDevice, f->stream));
@@ -291,6 +310,37 @@ int navgpu_obsbuf_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const d
     f->ev_cm_set = true;
   }
   launch_obs_gather(ob.dev, cm, first, count, f->stream);
+  return checkLaunch();
+}
+
+// navgpu_obsbuf_stage for a robot list: getMarkingObservations + getClearingObservations (obstacle_layer.cpp:449-478 over
+// observation_buffer.cpp:199-236, :238-251) of the listed robots; the hand-over is the packed block of navgpu_costmap_stage_list
+// without points, and k_obs_gather runs once, on the list
+int navgpu_obsbuf_stage_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const double* poses, int64_t now, int32_t* current_out) {
+  if (!f) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  ObsBuf& ob = f->ob;
+  if (!instances) return NAVGPU_ERR_INVALID;
+  if (!ob.configured) return NAVGPU_ERR_STATE;
+  if (!poses || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  CostmapDev& cm = f->cm;
+  if (f->desc.rolling_window && f->shift_pending) return NAVGPU_ERR_STATE;  // previous stage not consumed by an update yet
+  const RobotSet set{0, n_robots, instances};
+  KeptSet ks;
+  int rc = keptOfSet(f, set, ks);
+  if (rc == NAVGPU_OK) rc = reserveCostmapList(f);
+  if (rc) return rc;
+  if ((rc = stageKept(f, set, ks, now, current_out))) return rc;
+  stagePoseMirrors(f, set, poses);
+  if ((rc = sendCostmapStageList(f, n_robots, instances, false))) return rc;
+  // the list the gather reads: the block's records name the robots, the kernel wants them as a plain array
+  navgpu_fleet::CostmapList& cl = f->cml;
+  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));
+  memcpy(cl.h_list, instances, sizeof(uint32_t) * n_robots);
+  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n_robots, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
+  cl.ev_set = true;
+  launch_obs_gather(ob.dev, cm, RobotList{cl.d_list}, n_robots, f->stream);
   return checkLaunch();
 }
 

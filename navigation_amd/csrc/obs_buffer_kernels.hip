@@ -69,8 +69,9 @@ __global__ __launch_bounds__(kScanThreads) void k_obs_ingest(ObsBufDev ob, const
 }
 
 // The host staged the robot's descriptors (cm.obs, cm.obs_count) with the ring slot of each in `pad`.
-__global__ __launch_bounds__(kScanThreads) void k_obs_gather(ObsBufDev ob, CostmapDev cm, uint32_t first) {
-  const uint32_t inst = first + blockIdx.x;
+template <class Robots>
+__global__ __launch_bounds__(kScanThreads) void k_obs_gather(ObsBufDev ob, CostmapDev cm, Robots robots) {
+  const uint32_t inst = robots(blockIdx.x);
   ObsCsr* obs = cm.obs + (size_t)inst * cm.max_obs;
   const uint32_t n_obs = min(cm.obs_count[inst], cm.max_obs);
   const size_t slot0 = (size_t)inst * ob.slots_per_robot;
@@ -111,7 +112,10 @@ void launch_obs_ingest(const ObsBufDev& ob, const ObsIngestCloud* clouds, uint32
   hipLaunchKernelGGL(k_obs_ingest, dim3(n_clouds), dim3(kScanThreads), 0, s, ob, clouds, points, ranges);
 }
 void launch_obs_gather(const ObsBufDev& ob, const CostmapDev& cm, uint32_t first, uint32_t count, hipStream_t s) {
-  hipLaunchKernelGGL(k_obs_gather, dim3(count), dim3(kScanThreads), 0, s, ob, cm, first);
+  hipLaunchKernelGGL(k_obs_gather<RobotRange>, dim3(count), dim3(kScanThreads), 0, s, ob, cm, RobotRange{first});
+}
+void launch_obs_gather(const ObsBufDev& ob, const CostmapDev& cm, RobotList robots, uint32_t count, hipStream_t s) {
+  hipLaunchKernelGGL(k_obs_gather<RobotList>, dim3(count), dim3(kScanThreads), 0, s, ob, cm, robots);
 }
 void launch_obs_retransform(const ObsBufDev& ob, const ObsRetransform* items, uint32_t n_items, hipStream_t s) {
   hipLaunchKernelGGL(k_obs_retransform, dim3((ob.max_cloud_points + kScanThreads - 1) / kScanThreads, n_items), dim3(kScanThreads), 0, s, ob, items);

@@ -13,21 +13,7 @@ __device__ __forceinline__ Geom geomOf(const PlannerDev& pl, uint32_t inst) {
   return Geom{pl.origin[2 * inst], pl.origin[2 * inst + 1], pl.res, pl.nx, pl.ny};
 }
 
-// Which robot block or work item k of a cycle launch belongs to: the k-th of a contiguous range (navgpu_planner_cycle) or
-// of a strictly increasing list in device memory (navgpu_planner_cycle_list).  Every kernel of the cycle is a template over one
-// of the two, one copy of its body.  RobotRange has the size and alignment of the `uint32_t first` it stands for: the range
-// instantiations take the argument block, and compile to the code, they had as plain kernels.
-struct RobotRange {
-  uint32_t first;
-  __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return first + k; }
-  __device__ __forceinline__ uint32_t front() const { return first; }
-};
-struct RobotList {
-  const uint32_t* list;
-  __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return list[k]; }
-  __device__ __forceinline__ uint32_t front() const { return list[0]; }
-};
-static_assert(sizeof(RobotRange) == sizeof(uint32_t) && alignof(RobotRange) == alignof(uint32_t), "the range kernels' argument block");
+// (RobotRange / RobotList - which robot block or work item k of a launch belongs to - are in navgpu_device.h: the costmap kernels take them too)
 
 // free-cell bitmap word of one map row (bit b = cell wi*32+b is traversable)
 // four cost bytes -> four "obstacle" bits (LETHAL, INSCRIBED, and NO_INFORMATION unless unknown cells are allowed), SWAR

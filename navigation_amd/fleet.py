@@ -10,6 +10,8 @@ Method names follow the reference interfaces they front:
   check_trajectories    a loop of checkTrajectory calls over robots and velocity probes, one launch
   stage_planner_list / stage_poses_list / planner_cycle_list / results_list  the planner cycle (dwa_planner_ros.cpp:176-247 per robot)
                         for a robot list instead of a contiguous range, one launch of each kernel
+  stage_observations_list / obs_stage_list / update_map_list / bounds_list  the costmap update (layered_costmap.cpp:79-150 per robot)
+                        for a robot list; a rolling-window fleet takes any list
   footprint_cost        CostmapModel::footprintCost          (base_local_planner/src/costmap_model.cpp:50-142)
   rotate_recovery_step  RotateRecovery::runBehavior, one pass (rotate_recovery/src/rotate_recovery.cpp:105-153)
   carrot_plan           CarrotPlanner::makePlan              (carrot_planner/src/carrot_planner.cpp:116-169)
@@ -201,19 +203,7 @@ class Fleet:
         obstacle_range, raytrace_range, marking, clearing}."""
         poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
         count = len(poses)
-        obs_arr = (Observation * max(1, len(observations)))()
-        pts = []
-        off = 0
-        for k, o in enumerate(observations):
-            p = np.ascontiguousarray(o["points"], np.float32).reshape(-1, 3)
-            flags = (N.OBS_MARKING if o.get("marking", True) else 0) | (N.OBS_CLEARING if o.get("clearing", True) else 0)
-            org = o.get("origin", (0.0, 0.0, 1.0))
-            obs_arr[k] = Observation(o["instance"], off, len(p), flags, org[0], org[1], org[2],
-                                     o.get("obstacle_range", 2.5), o.get("raytrace_range", 3.0))
-            pts.append(p)
-            off += len(p)
-        allp = np.concatenate(pts) if pts else np.zeros((0, 3), np.float32)
-        allp = np.ascontiguousarray(allp, np.float32)
+        obs_arr, allp = self._pack_observations(observations)
         check(self.L.navgpu_costmap_stage(self.h, first, count, _ptr(poses), C.cast(obs_arr, C.c_void_p),
                                           len(observations), _ptr(allp) if len(allp) else None, len(allp)),
               "costmap_stage")
@@ -232,6 +222,61 @@ class Fleet:
         first, count = self._range(first, count)
         b = np.zeros((count, 4), np.int32)
         check(self.L.navgpu_costmap_bounds(self.h, first, count, _ptr(b)), "costmap_bounds")
+        return b
+
+    def _pack_observations(self, observations):
+        obs_arr = (Observation * max(1, len(observations)))()
+        pts = []
+        off = 0
+        for k, o in enumerate(observations):
+            p = np.ascontiguousarray(o["points"], np.float32).reshape(-1, 3)
+            flags = (N.OBS_MARKING if o.get("marking", True) else 0) | (N.OBS_CLEARING if o.get("clearing", True) else 0)
+            org = o.get("origin", (0.0, 0.0, 1.0))
+            obs_arr[k] = Observation(o["instance"], off, len(p), flags, org[0], org[1], org[2],
+                                     o.get("obstacle_range", 2.5), o.get("raytrace_range", 3.0))
+            pts.append(p)
+            off += len(p)
+        allp = np.concatenate(pts) if pts else np.zeros((0, 3), np.float32)
+        return obs_arr, np.ascontiguousarray(allp, np.float32)
+
+    def stage_observations_list(self, instances, poses, observations):
+        """stage_observations for the robots `instances` (strictly increasing): poses[k] belongs to instances[k]; an observation's
+        `instance` stays a fleet index and must be in the list.  One packed upload, one scatter launch."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        if len(poses) != len(inst):
+            raise ValueError("stage_observations_list: one pose per listed robot")
+        obs_arr, allp = self._pack_observations(observations)
+        check(self.L.navgpu_costmap_stage_list(self.h, len(inst), _ptr(inst), _ptr(poses), C.cast(obs_arr, C.c_void_p), len(observations),
+                                               _ptr(allp) if len(allp) else None, len(allp)), "costmap_stage_list")
+
+    def stage_observations_list_raw(self, instances, poses, obs_array, n_obs, points):
+        """Pre-built ctypes Observation array + packed float32 points (no Python loops on the per-cycle path)."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        check(self.L.navgpu_costmap_stage_list(self.h, len(inst), _ptr(inst), _ptr(poses), C.cast(obs_array, C.c_void_p), n_obs,
+                                               _ptr(points), len(points)), "costmap_stage_list")
+
+    def obs_stage_list(self, instances, poses, now_ns, want_current=True):
+        """obs_stage for the robots `instances`.  Returns isCurrent per listed robot (bool array)."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 3)
+        if len(poses) != len(inst):
+            raise ValueError("obs_stage_list: one pose per listed robot")
+        cur = np.zeros(len(inst), np.int32)
+        check(self.L.navgpu_obsbuf_stage_list(self.h, len(inst), _ptr(inst), _ptr(poses), int(now_ns), _ptr(cur) if want_current else None),
+              "obsbuf_stage_list")
+        return cur.astype(bool)
+
+    def update_map_list(self, instances):
+        """update_map for the robots `instances`: one launch of each kernel, the robots outside the list untouched."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        check(self.L.navgpu_costmap_update_list(self.h, len(inst), _ptr(inst)), "costmap_update_list")
+
+    def bounds_list(self, instances):
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        b = np.zeros((len(inst), 4), np.int32)
+        check(self.L.navgpu_costmap_bounds_list(self.h, len(inst), _ptr(inst), _ptr(b)), "costmap_bounds_list")
         return b
 
     def inflate(self, boxes=None, first=0, count=None):
