@@ -5,12 +5,11 @@
 // cpu_baseline leg may use anything in oracle/.  Every function cites the reference
 // file:line it restates (paths relative to /root/reference).
 //
-// Parity pinning: the reference needs ROS/boost/Eigen/pcl headers that this image
-// lacks, so it is NOT compiled here (no stand-in headers are written).  The
-// restatement is pinned by the reference's own test expectations
-// (tests/test_oracle_reference_fixtures.py) and, for the two header-only pieces
-// that compile from their own files (LineIterator, VelocityIterator), by
-// oracle/_ref built from the reference sources in place.
+// Parity pinning: tests/golden/g17_costmap_reference.npz holds what the reference's own LayeredCostmap, StaticLayer, ObstacleLayer,
+// VoxelLayer / VoxelGrid and InflationLayer compute, compiled in place by tools/make_costmap_goldens.py, and
+// tests/test_costmap_reference.py holds this restatement to it bit for bit (origins, boxes, layer grids, voxel words, the master
+// grid behind every layer, the cost table).  The reference's own test expectations (tests/test_oracle_reference_fixtures.py) and
+// oracle/_ref (LineIterator, VelocityIterator built from the reference sources in place) stay beside it.
 #pragma once
 #include <algorithm>
 #include <cfloat>
@@ -945,6 +944,8 @@ struct LayeredCostmapOracle {
   double inscribed_radius = 0, circumscribed_radius = 0;
   std::vector<Observation> marking, clearing;  // static observations (test hook), persist across cycles
   int bx0 = 0, bxn = 0, by0 = 0, byn = 0;
+  bool keep_layer_masters = false;                    // test hook: keep the master grid behind the static / obstacle layer's updateCosts
+  std::vector<uint8_t> after_static, after_obstacle;  // of the last cycle
 
   void init(bool track_unknown_) {
     track_unknown = track_unknown_;
@@ -1004,10 +1005,15 @@ struct LayeredCostmapOracle {
     bxn = xn;
     by0 = y0;
     byn = yn;
-    if (xn < x0 || yn < y0) return;
+    if (xn < x0 || yn < y0) {
+      if (keep_layer_masters) after_static = after_obstacle = master.cells;
+      return;
+    }
     master.resetMap(x0, y0, xn, yn);
     if (has_static) slayer.updateCosts(master, x0, y0, xn, yn);
+    if (keep_layer_masters) after_static = master.cells;
     if (has_obstacle) olayer.updateCosts(master, x0, y0, xn, yn);
+    if (keep_layer_masters) after_obstacle = master.cells;
     if (has_inflation) {
       if (inflation_exact)
         ilayer.updateCostsExact(master, x0, y0, xn, yn);

@@ -177,6 +177,12 @@ void orc_lc_get_master(void* h, uint8_t* out) {
   auto* lc = static_cast<LayeredCostmapOracle*>(h);
   memcpy(out, lc->master.cells.data(), lc->master.cells.size());
 }
+void orc_lc_keep_layer_masters(void* h, int keep) { static_cast<LayeredCostmapOracle*>(h)->keep_layer_masters = keep != 0; }
+void orc_lc_get_master_after(void* h, int which, uint8_t* out) {  // 1 behind the static layer, 2 behind the obstacle / voxel layer
+  auto* lc = static_cast<LayeredCostmapOracle*>(h);
+  const std::vector<uint8_t>& g = which == 1 ? lc->after_static : lc->after_obstacle;
+  if (!g.empty()) memcpy(out, g.data(), g.size());
+}
 void orc_lc_set_master(void* h, const uint8_t* in) {
   auto* lc = static_cast<LayeredCostmapOracle*>(h);
   memcpy(lc->master.cells.data(), in, lc->master.cells.size());

@@ -104,6 +104,8 @@ def lib():
     sig("orc_lc_update_map", None, vp, d, d, d)
     sig("orc_lc_reset_bounding_box", None, vp, d, d, d, d)
     sig("orc_lc_get_master", None, vp, u8p)
+    sig("orc_lc_keep_layer_masters", None, vp, i)
+    sig("orc_lc_get_master_after", None, vp, i, u8p)
     sig("orc_lc_set_master", None, vp, u8p)
     sig("orc_lc_get_layer", None, vp, i, u8p)
     sig("orc_lc_set_layer", None, vp, i, u8p)
@@ -313,6 +315,17 @@ class LayeredCostmap:
         sx, sy = self.size()
         out = np.empty((sy, sx), np.uint8)
         self.L.orc_lc_get_master(self.h, out)
+        return out
+
+    def keep_layer_masters(self, keep=True):
+        """from the next update_map on, keep the master grid behind each layer's updateCosts for master_after()"""
+        self.L.orc_lc_keep_layer_masters(self.h, int(keep))
+
+    def master_after(self, which):
+        """the master grid behind the static (1) or the obstacle / voxel (2) layer's updateCosts of the last update_map"""
+        sx, sy = self.size()
+        out = np.empty((sy, sx), np.uint8)
+        self.L.orc_lc_get_master_after(self.h, which, out)
         return out
 
     def layer(self, which=2):

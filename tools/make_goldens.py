@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Generate the golden vectors of SURVEY 8(c) (G1-G6; G7 navfn and G8 global_planner for row f-4) under tests/golden/ from the CPU oracle.
 
-The reference itself cannot be built in this image (its hot-path sources need ROS, Boost, Eigen and PCL headers), so these
-vectors come from oracle/ - the restatement that IS pinned by every fixture the reference's own tests hold
-(tests/test_oracle_reference_fixtures.py, tests/test_navfn.py).  They freeze its outputs on seeded inputs: a later edit
-of the oracle that changes any byte fails tests/test_goldens.py on the CPU, and the HIP path is checked against the
-same files on the GPU without the oracle in the loop.  Every file stores the seed and parameters it was made with.
+These vectors come from oracle/, not from the reference: they freeze the oracle's outputs on seeded inputs, so a later edit of the
+oracle that changes any byte fails tests/test_goldens.py on the CPU, and the HIP path is checked against the same files on the GPU
+without the oracle in the loop.  Every file stores the seed and parameters it was made with.  g1 (inflation) and g6 (voxel layer) remain
+such oracle-frozen vectors; what ties the costmap oracle and kernels to the reference itself is g17_costmap_reference.npz, written by
+tools/make_costmap_goldens.py from costmap_2d's and voxel_grid's own classes compiled in place (as g9-g16 are for amcl, global_planner,
+navfn, DWA and the legacy TrajectoryPlanner), with the known-answer scenarios of tests/test_oracle_reference_fixtures.py beside it.
     python tools/make_goldens.py        (rewrites tests/golden/g*.npz)"""
 import os
 import sys
