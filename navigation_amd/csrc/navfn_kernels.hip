@@ -529,7 +529,10 @@ __device__ bool gpDijkstra(const GpPlan& p, int* buffers, bool precise_start, in
   float* potential = p.potential;
   PriorityBuffers pb(buffers, p.pending, p.ns);
   float threshold = lethal;
-  const float priorityIncrement = 2 * p.neutral;
+  // The constructor's 2 * 50 (dijkstra.cpp:49), whatever neutral_cost is configured: GlobalPlanner sets the cost through its
+  // Expander* member (planner_core.cpp:170), Expander::setNeutralCost is not virtual (expander.h:67), and so
+  // DijkstraExpansion::setNeutralCost, which would recompute the increment, is never the one called.
+  const float priorityIncrement = 2 * 50;
   auto pushable = [&](int n) { return p.getCost(n) < lethal; };
   const int k = p.startCell();
   if (precise_start) {  // setPreciseStart(true) (planner_core.cpp:124-127)
@@ -643,8 +646,10 @@ __device__ void gpClearEndpoint(const GpPlan& p, int goal_cell) {
       const int n = goal_cell + i + p.nx * j;
       if (n < p.nx + 1 || n >= p.ns - p.nx - 1) continue;  // (the reference reads outside its arrays for a goal this close to the border)
       if (p.potential[n] < kPotHigh) continue;
-      const float c = (float)(p.costs[n] + p.neutral);
-      p.potential[n] = p.calculatePotential((uint8_t)c, n, -1.0f);
+      // `float c = costs[n] + neutral_cost_` handed to an unsigned char parameter (expander.h:84-85) is out of range from 256 on;
+      // amd64 converts through a 32-bit integer and keeps the low byte - the sum (0 ... 510, exact in a float) modulo 256.
+      // Stated in integers: what a float-to-byte conversion of such a value gives is not defined on this target either.
+      p.potential[n] = p.calculatePotential((uint8_t)((p.costs[n] + p.neutral) & 0xff), n, -1.0f);
     }
 }
 

@@ -2,10 +2,10 @@
 // (second half): Expander / DijkstraExpansion / AStarExpansion, PotentialCalculator /
 // QuadraticCalculator, GradientPath / GridPath, and the steps of GlobalPlanner::makePlan between worldToMap and
 // getPlanFromPotential (outlineMap, calculatePotentials with nx * ny * 2 cycles, clearEndpoint).  Every function cites the
-// reference lines it follows (global_planner/src, global_planner/include/global_planner).  The reference sources need
-// ROS headers (planner_core.h pulls in costmap_2d_ros, nav_core, dynamic_reconfigure) and are not compiled here; the
-// reference holds no test for this package, so this restatement is pinned by reading only ("parity unpinned" for the
-// global_planner half of f-4; the navfn half is pinned by navfn/test/path_calc_test.cpp, see navfn_oracle.hpp).
+// reference lines it follows (global_planner/src, global_planner/include/global_planner).  The reference holds no test for this
+// package; what pins this restatement is tests/golden/g18_global_planner_reference.npz, written by the reference's own classes
+// compiled in place and driven as planner_core.cpp drives them (tools/make_global_planner_goldens.py): tests/
+// test_global_planner_reference.py holds found_legal, both potential arrays and every path point of every case to it, bit for bit.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -38,6 +38,7 @@ struct GlobalPlannerOracle {
   GlobalPlannerParams p;
   std::vector<uint8_t> costs;
   std::vector<float> potential, gradx, grady;
+  std::vector<float> potential_before;  // plan(): the array as the expansion left it, before clearEndpoint
   std::vector<uint8_t> pending;
   std::vector<std::pair<float, float>> path;
   int cycles_used = 0;
@@ -97,7 +98,10 @@ struct GlobalPlannerOracle {
     int *cur = b1.data(), *nxt = b2.data(), *ovr = b3.data();
     int curE = 0, nxtE = 0, ovrE = 0;
     float threshold = p.lethal_cost;
-    const float priorityIncrement = 2 * p.neutral_cost;
+    // The constructor's 2 * 50 (dijkstra.cpp:49), whatever neutral_cost is configured: GlobalPlanner sets the cost through its
+    // Expander* member (planner_core.cpp:170) and Expander::setNeutralCost is not virtual (expander.h:67), so
+    // DijkstraExpansion::setNeutralCost (dijkstra.h:70-73), which would recompute the increment, is never the one called.
+    const float priorityIncrement = 2 * 50;
     std::fill(pending.begin(), pending.end(), 0);
     std::fill(potential.begin(), potential.end(), kPotHigh);
     auto push = [&](int* buf, int& end, int n) {
@@ -314,8 +318,10 @@ struct GlobalPlannerOracle {
       for (int j = -s; j <= s; j++) {
         const int n = startCell + i + nx * j;
         if (potential[n] < kPotHigh) continue;
-        const float c = costs[n] + p.neutral_cost;
-        potential[n] = calculatePotential((uint8_t)c, n);
+        // `float c = costs[n] + neutral_cost_` handed to an unsigned char parameter (expander.h:84-85): out of range from 256 on,
+        // undefined in C++; amd64 converts through a 32-bit integer and keeps its low byte, which for these sums (0 ... 510, exact
+        // in a float) is the sum modulo 256.  Stated in integers so that no compiler's float-to-byte cast decides it.
+        potential[n] = calculatePotential((uint8_t)((costs[n] + p.neutral_cost) & 0xff), n);
       }
   }
   // GradientPath::gradCell (gradient_path.cpp:268-313)
@@ -451,12 +457,11 @@ struct GlobalPlannerOracle {
       legal = dijkstra(start_x, start_y, goal_x, goal_y, nx * ny * 2, !p.old_navfn_behavior);  // setPreciseStart(true) unless old behaviour (planner_core.cpp:124-127)
     else
       legal = astar(start_x, start_y, goal_x, goal_y, nx * ny * 2);
+    potential_before = potential;
     if (!p.old_navfn_behavior) clearEndpoint(goal_x_i, goal_y_i, 2);
     if (found_legal) *found_legal = legal;
-    if (!legal) {
-      path.clear();
-      return false;
-    }
+    path.clear();
+    if (!legal) return false;
     return p.use_grid_path ? gridPath(start_x, start_y, goal_x, goal_y) : gradientPath(start_x, start_y, goal_x, goal_y);
   }
 };

@@ -868,6 +868,35 @@ int orc_global_planner_plan(const uint8_t* cmap, int nx, int ny, const int* para
   }
   return len;
 }
+// The same plan with everything the reference-written fixture records: the potential before clearEndpoint as well, the traceback's
+// return value (-1: not called) and the points it left whether it arrived or not.  Returns the number of points.
+int orc_global_planner_plan_trace(const uint8_t* cmap, int nx, int ny, const int* params, float cost_factor, const double* start_xy,
+                                  const double* goal_xy, const int* goal_cell, float* potential_before, float* potential_out, float* path_xy,
+                                  int path_cap, int* found_legal, int* path_ret) {
+  GlobalPlannerParams p;
+  p.use_dijkstra = params[0];
+  p.use_quadratic = params[1];
+  p.use_grid_path = params[2];
+  p.old_navfn_behavior = params[3];
+  p.allow_unknown = params[4];
+  p.lethal_cost = params[5];
+  p.neutral_cost = params[6];
+  p.outline_map = params[7];
+  p.cost_factor = cost_factor;
+  GlobalPlannerOracle gp(nx, ny, p);
+  bool legal = false;
+  const bool ok = gp.plan(cmap, start_xy[0], start_xy[1], goal_xy[0], goal_xy[1], goal_cell[0], goal_cell[1], &legal);
+  *found_legal = legal;
+  *path_ret = legal ? (ok ? 1 : 0) : -1;
+  memcpy(potential_before, gp.potential_before.data(), sizeof(float) * (size_t)nx * ny);
+  memcpy(potential_out, gp.potential.data(), sizeof(float) * (size_t)nx * ny);
+  const int len = (int)gp.path.size();
+  for (int i = 0; i < len && i < path_cap; ++i) {
+    path_xy[2 * i] = gp.path[i].first;
+    path_xy[2 * i + 1] = gp.path[i].second;
+  }
+  return len;
+}
 // the two pieces of the global_planner oracle that oracle/_ref/libref_gp.so can check directly
 void orc_gp_calculate_potential(int quadratic, const float* potential, int nx, int ny, const uint8_t* cost, const int* cells, const float* prev,
                                 int count, float* out) {

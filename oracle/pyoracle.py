@@ -167,6 +167,8 @@ def lib():
     sig("orc_gp_calculate_potential", None, i, f32p, i, i, u8p, i32p, f32p, i, f32p)
     sig("orc_gp_grid_path", i, f32p, i, i, C.c_double, C.c_double, C.c_double, C.c_double, f32p, i)
     sig("orc_global_planner_plan", i, u8p, i, i, i32p, C.c_float, f64p, f64p, i32p, C.c_void_p, C.c_void_p, i, C.POINTER(i), C.POINTER(i))
+    sig("orc_global_planner_plan_trace", i, u8p, i, i, i32p, C.c_float, f64p, f64p, i32p, C.c_void_p, C.c_void_p, C.c_void_p, i, C.POINTER(i),
+        C.POINTER(i))
     sig("orc_navfn_plan", i, u8p, i, i, i, i, i32p, i32p, i, i, C.c_void_p, C.c_void_p, i, C.POINTER(i))
     sig("orc_navfn_costarr", None, u8p, i, i, i, i, u8p)
     sig("orc_navfn_fixed_point", i, u8p, i, i, i, i, i32p, i32p, C.c_void_p, C.c_void_p, i)
@@ -675,3 +677,21 @@ def global_planner_plan(cmap, start_xy, goal_xy, goal_cell, fixed_point=False, *
                                       np.ascontiguousarray(goal_xy, np.float64), np.ascontiguousarray(goal_cell, np.int32), pot.ctypes.data,
                                       path.ctypes.data, len(path), C.byref(legal), C.byref(cyc))
     return path[:n].copy(), pot, bool(legal.value), cyc.value
+
+
+def global_planner_plan_trace(cmap, start_xy, goal_xy, goal_cell, **params):
+    """The same plan with what tests/golden/g18_global_planner_reference.npz records: dict(found_legal, potential_before, potential,
+    path_ret (-1: the traceback was not called), path - the points the traceback left, also where it did not arrive)."""
+    pr = dict(GP_DEFAULTS)
+    pr.update(params)
+    g = np.ascontiguousarray(cmap, np.uint8)
+    ny, nx = g.shape
+    before, pot = np.zeros((ny, nx), np.float32), np.zeros((ny, nx), np.float32)
+    path = np.zeros((4 * nx * ny + 4, 2), np.float32)
+    legal, ret = C.c_int(), C.c_int()
+    ints = np.array([pr[k] for k in ("use_dijkstra", "use_quadratic", "use_grid_path", "old_navfn_behavior", "allow_unknown", "lethal_cost",
+                                     "neutral_cost", "outline_map")], np.int32)
+    n = lib().orc_global_planner_plan_trace(g, nx, ny, ints, float(pr["cost_factor"]), np.ascontiguousarray(start_xy, np.float64),
+                                            np.ascontiguousarray(goal_xy, np.float64), np.ascontiguousarray(goal_cell, np.int32),
+                                            before.ctypes.data, pot.ctypes.data, path.ctypes.data, len(path), C.byref(legal), C.byref(ret))
+    return dict(found_legal=legal.value, potential_before=before, potential=pot, path_ret=ret.value, path=path[:n].copy())

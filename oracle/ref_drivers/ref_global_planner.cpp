@@ -2,7 +2,9 @@
 // QuadraticCalculator (src/quadratic_calculator.cpp) with its PotentialCalculator base, and GridPath (src/grid_path.cpp) --
 // compiled in place from /root/reference (nothing copied) behind a C ABI, so tests can pin the matching pieces of
 // oracle/global_planner_oracle.hpp against the reference itself.  dijkstra.cpp, astar.cpp and gradient_path.cpp include
-// planner_core.h (ros/ros.h, nav_core, dynamic_reconfigure): unbuildable here, no stand-in headers are written.
+// planner_core.h (ros/ros.h, nav_core, dynamic_reconfigure) and are not part of this library: they are compiled against the
+// stand-in header of tools/global_planner_ref_stubs/ by tools/make_global_planner_goldens.py, whose fixture
+// (tests/golden/g18_global_planner_reference.npz) pins the expanders, clearEndpoint and GradientPath.
 #include <algorithm>  // potential_calculator.h uses std::min without including <algorithm>
 #include <utility>
 #include <vector>

@@ -343,8 +343,9 @@ def test_oracle_global_planner_basic_properties(orc):
         path, pot, legal, cyc = orc.global_planner_plan(cm, start, goal, (int(goal[0]), int(goal[1])), **kw)
         assert legal, kw
         if not kw.get("use_dijkstra", 1) and not kw.get("use_grid_path"):
-            # A*'s narrow corridor + the interpolated gradient descent: the descent steps onto a cell A* never reached and
-            # `int minp = potential[stc]` (gradient_path.cpp:119) ends the trace -- the reference's known A*/gradient failure
+            # A*'s narrow corridor + the interpolated gradient descent: the walk takes grid steps beside the cells A* never reached
+            # and circles among them until its 4 * ns limit -- the reference's known A*/gradient failure (g18 records both this
+            # and the zero-gradient stop beside the start cell, from the reference's own classes)
             assert len(path) == 0
             continue
         assert len(path) > 1, kw

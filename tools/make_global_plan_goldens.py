@@ -7,7 +7,8 @@ tools/global_plan_harness.cpp) leaves as orientations in its four modes.
 Per case set S (batch, serpentine, short) and parameter variant V:
   S_frames, S_starts, S_goals, S_maps (+ S_map_index)     the inputs
   S_V_status, S_V_counts                                  status and n_poses per plan
-  S_V_path                                                the oracle's traceback points (float32, goal first), concatenated
+  S_V_path                                                the oracle's traceback points (float32, goal first), concatenated; for `batch`
+                                                          tests/test_global_planner_reference.py gets the same bits from the reference's classes
   S_V_plan                                                the assembled world plan before the filter: {x, y, yaw}, concatenated
   S_V_quat                                                4 x total x {z, w}: the reference's quaternions per orientation mode
   S_V_grid, S_V_max                                       publishPotential's bytes and maximum (scale 100) of the plans attempted

@@ -5,8 +5,10 @@ These vectors come from oracle/, not from the reference: they freeze the oracle'
 oracle that changes any byte fails tests/test_goldens.py on the CPU, and the HIP path is checked against the same files on the GPU
 without the oracle in the loop.  Every file stores the seed and parameters it was made with.  g1 (inflation) and g6 (voxel layer) remain
 such oracle-frozen vectors; what ties the costmap oracle and kernels to the reference itself is g17_costmap_reference.npz, written by
-tools/make_costmap_goldens.py from costmap_2d's and voxel_grid's own classes compiled in place (as g9-g16 are for amcl, global_planner,
-navfn, DWA and the legacy TrajectoryPlanner), with the known-answer scenarios of tests/test_oracle_reference_fixtures.py beside it.
+tools/make_costmap_goldens.py from costmap_2d's and voxel_grid's own classes compiled in place (as g9-g16 are for amcl, global_planner's orientation
+filter, navfn, DWA and the legacy TrajectoryPlanner), with the known-answer scenarios of tests/test_oracle_reference_fixtures.py beside it.
+g8 likewise freezes the oracle's global_planner core; what ties that core to the reference's own expanders and tracebacks is
+g18_global_planner_reference.npz (tools/make_global_planner_goldens.py).
     python tools/make_goldens.py        (rewrites tests/golden/g*.npz)"""
 import os
 import sys
