@@ -386,6 +386,11 @@ int navgpu_planner_set_bounded_map_grids(navgpu_fleet* fleet, int32_t enable);
  * setLocalGoal, map_grid.cpp:135-258), ahead of the wavefronts, which then only scatter the cells.  enable = 0: every
  * wavefront walks the plan itself, as the launches outside a cycle always do.  Takes effect at the next cycle. */
 int navgpu_planner_set_seed_lists(navgpu_fleet* fleet, int32_t enable);
+/* Split image build (default: on).  Where a cycle scores with k_score_sweep and its wavefronts run in k_bfs_rows, the part of a
+ * robot's scoring image that reads no distance grid (window, footprint screens, heading tables) is built by extra workgroups of
+ * the wavefront launch itself, and k_score_prep_grids adds the path / goal screens behind it.  enable = 0: k_score_prep_tab
+ * builds the whole image behind the wavefronts.  The results are the same bit for bit.  Takes effect at the next cycle. */
+int navgpu_planner_set_split_prep(navgpu_fleet* fleet, int32_t enable);
 /* Test hook: the seed cells a list holds, 1 .. 1024 (the default).  A (robot, grid) with more seed cells than that has no
  * list that cycle and its wavefront walks the plan.  NAVGPU_ERR_INVALID outside the range. */
 int navgpu_planner_set_seed_list_capacity(navgpu_fleet* fleet, uint32_t cells);

@@ -499,6 +499,7 @@ SYMBOLS = [
     ("navgpu_planner_cycle", C.c_int, [vp, u32, u32]),
     ("navgpu_planner_set_bounded_map_grids", C.c_int, [vp, C.c_int32]),
     ("navgpu_planner_set_seed_lists", C.c_int, [vp, C.c_int32]),
+    ("navgpu_planner_set_split_prep", C.c_int, [vp, C.c_int32]),
     ("navgpu_planner_set_seed_list_capacity", C.c_int, [vp, u32]),
     ("navgpu_planner_seed_list_counts", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_planner_set_map_grid_options", C.c_int, [vp, C.c_int32, C.c_int32, C.c_double]),

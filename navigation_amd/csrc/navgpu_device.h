@@ -409,6 +409,13 @@ __attribute__((weak)) void launch_samples_list(const PlannerDev& pl, const uint3
 __attribute__((weak)) void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order);
 __attribute__((weak)) uint32_t launch_score_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);  // returns blocks per instance
 __attribute__((weak)) void launch_select_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, uint32_t n_blocks, hipStream_t s);
+// ---- the split image build (navgpu_planner_set_split_prep): the wavefront launch with scorePrepFree workgroups, and the scoring
+// launches that complete the image (k_score_prep_grids) where launch_score builds it whole.  Weak as the list launchers are.
+__attribute__((weak)) bool split_prep_applies(const PlannerDev& pl);  // the sweep scores and the wavefronts are k_bfs_rows'
+__attribute__((weak)) void launch_bfs_prep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order);
+__attribute__((weak)) void launch_bfs_prep_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order);
+__attribute__((weak)) uint32_t launch_score_grids(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s);
+__attribute__((weak)) uint32_t launch_score_grids_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);
 void launch_sincos(const double* th, uint32_t n, double* sn, double* cs, hipStream_t s);
 // ---- device-resident global plans (local_plan_kernels.hip): LocalPlannerUtil::getLocalPlan per robot and cycle
 constexpr uint32_t kPlanWindowThreads = 256;

@@ -121,6 +121,8 @@ struct navgpu_fleet {
   // wavefront seed lists (navgpu_planner_set_seed_lists, navgpu_planner_set_seed_list_capacity): a cycle's k_samples turns every
   // robot's plan into the seed cells of its three grids, once, and the wavefronts behind it scatter them
   bool seed_lists = true;
+  // split image build (navgpu_planner_set_split_prep): a cycle's wavefront launch carries the grid-free part of the scoring image
+  bool split_prep = true;
   uint32_t seed_list_cap = kSeedListMax;
   std::vector<uint8_t> grid_partial;            // [n]
   std::vector<int32_t> h_box;                   // [n][4] x0, x1, y0, y1 of the last bounded cycle

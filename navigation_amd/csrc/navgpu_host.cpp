@@ -1198,6 +1198,19 @@ int navgpu_planner_set_seed_lists(navgpu_fleet* f, int32_t enable) {
   f->seed_lists = enable != 0;
   return NAVGPU_OK;
 }
+// The split image build.  The switch takes effect at the next cycle: a cycle decides for its own two launches, and the image is
+// rebuilt whole every cycle either way.
+int navgpu_planner_set_split_prep(navgpu_fleet* f, int32_t enable) {
+  if (!f) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  f->split_prep = enable != 0;
+  return NAVGPU_OK;
+}
+// does this cycle build the grid-free part of the scoring image inside its wavefront launch?
+static bool splitPrep(const navgpu_fleet* f) {
+  return f->split_prep && split_prep_applies && launch_bfs_prep && launch_bfs_prep_list && launch_score_grids && launch_score_grids_list &&
+         split_prep_applies(f->pl);
+}
 int navgpu_planner_set_seed_list_capacity(navgpu_fleet* f, uint32_t cells) {
   if (!f || cells == 0 || cells > kSeedListMax) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
@@ -1621,7 +1634,14 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
 #ifdef NAVGPU_DEBUG_SWITCHES  // tool builds only (tools/trace_bfs.py): per-item phase stamps of the wavefront launch, written to the named file
   if (getenv("NAVGPU_DEBUG_BFS_TRACE") && !pl.bfs_trace) f->alloc(&pl.bfs_trace, (size_t)f->desc.n_instances * 3 * 8);
 #endif
-  PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, first, count, f->stream, pl.bfs_order + (size_t)first * 3, true));
+  // split: the wavefront launch carries the workgroups that build the grid-free part of the robots' scoring images, and the scoring
+  // launches complete them.  One image buffer serves two cycles in flight: this launch is behind the k_select of the cycle before on
+  // the fleet's stream, and that cycle's k_score_sweep and terms pass, the only readers of its images, come before its k_select.
+  const bool split = splitPrep(f);
+  if (split)
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs_prep(pl, first, count, f->stream, pl.bfs_order + (size_t)first * 3));
+  else
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, first, count, f->stream, pl.bfs_order + (size_t)first * 3, true));
 #ifdef NAVGPU_DEBUG_SWITCHES
   if (pl.bfs_trace) {
     std::vector<unsigned long long> h((size_t)count * 24);
@@ -1635,7 +1655,10 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
   }
 #endif
   uint32_t n_blocks = 0;
-  PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score(pl, first, count, nullptr, f->stream));
+  if (split)
+    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_grids(pl, first, count, f->stream));
+  else
+    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score(pl, first, count, nullptr, f->stream));
   int rc_terms = NAVGPU_OK;
   if (!f->tc.robots.empty()) {  // publish_traj_pc robots: their terms, under the oscillation flags the scorer saw (k_select updates them)
     rc_terms = f->tc.terms_pass(f, first, count);
@@ -1681,9 +1704,16 @@ int navgpu_planner_cycle_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t
   }
   launch_samples_list(pl, cl.d_list, n_robots, f->stream);
   // (the launch's dispatch order sits where the range cycle of instances[0] .. would put it: n_robots <= n_instances - instances[0])
-  PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
+  const bool split = splitPrep(f);  // (as in navgpu_planner_cycle)
+  if (split)
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs_prep_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
+  else
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
   uint32_t n_blocks = 0;
-  PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_list(pl, cl.d_list, n_robots, f->stream));
+  if (split)
+    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_grids_list(pl, cl.d_list, n_robots, f->stream));
+  else
+    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_list(pl, cl.d_list, n_robots, f->stream));
   int rc_terms = NAVGPU_OK;
   if (!f->tc.robots.empty()) {  // publish_traj_pc robots that are in the list: run by run, the pass takes a range
     for (uint32_t k = 0; k < n_robots && rc_terms == NAVGPU_OK;) {

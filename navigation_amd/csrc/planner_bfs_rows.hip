@@ -3,6 +3,7 @@
 //   MapGrid::resetPathDist + adjustPlanResolution (map_grid.cpp:135-171) + setTargetCells (:174-213) | setLocalGoal
 //   (:216-258) + computeTargetDistance (:262-310) with updatePathCell (:103-122).
 #include "planner_bfs_common.h"
+#include "planner_score.h"
 
 namespace navgpu {
 
@@ -428,9 +429,21 @@ __device__ __forceinline__ void bfsRowsGrid(const PlannerDev& pl, const uint32_t
   }
   bfsFinish(pl, tid, inst, which, item, level);
 }
+// prep_count (the cycle's launch when the sweep scores, else 0): the last prep_count workgroups of the grid are no searches - workgroup
+// k of them builds the part of robot k's scoring image that reads no distance grid (scorePrepFree) and leaves.  They depend on
+// nothing the searches write, and they take the high block indices: the searches, the launch's critical path, are dispatched first.
 template <int W, class Robots>
-__global__ __launch_bounds__(1024, 6) void k_bfs_rows(PlannerDev pl, Robots robots, uint32_t count, uint32_t* next_item, const uint32_t* order) {
+__global__ __launch_bounds__(1024, 6) void k_bfs_rows(PlannerDev pl, Robots robots, uint32_t count, uint32_t* next_item, const uint32_t* order,
+                                                      uint32_t prep_count) {
   __shared__ uint32_t s_item;
+  const uint32_t search_blocks = gridDim.x - prep_count;
+  // (the same for every lane of the workgroup.  Marked unlikely: register allocation then weighs the search as it did without this
+  // branch - every instantiation keeps its VGPRs, spills and scratch; unmarked, <7> reserved 36 bytes of scratch)
+  if (__builtin_expect(blockIdx.x >= search_blocks, 0)) {
+    extern __shared__ __align__(16) uint32_t sm[];
+    scorePrepFree(pl, robots(blockIdx.x - search_blocks), reinterpret_cast<uint8_t*>(sm));
+    return;
+  }
   const uint32_t total = count * pl.bfs_grids;  // 3 (DWA: path, goal, goal_front) or 2 (legacy TrajectoryPlanner)
   for (;;) {
     if (threadIdx.x == 0) s_item = atomicAdd(next_item, 1u);
@@ -933,20 +946,26 @@ static int bfs_rows_words(uint32_t nx, uint32_t ny) {
 }
 bool bfs_rows_fits(uint32_t nx, uint32_t ny) { return bfs_rows_words(nx, ny) != 0; }
 // searches resident per CU: as many as the wave slots and LDS hold, at most four
+// prep_count: 0, or `count` workgroups more that run scorePrepFree for the launch's robots; the dynamic LDS is the larger of the two needs
 template <int W, class Robots>
-static void launch_bfs_rows_w(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order) {
+static void launch_bfs_rows_w(const PlannerDev& pl_in, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order, uint32_t prep_count) {
+  PlannerDev pl = pl_in;
   const uint32_t nw = bfs_rows_waves(pl.ny);
-  const size_t lds = bfs_rows_lds_words<W>(pl.nx, pl.ny) * 4;
+  size_t lds = bfs_rows_lds_words<W>(pl.nx, pl.ny) * 4;
+  if (prep_count) {
+    score_prep_tab_sizes(pl);
+    lds = std::max(lds, score_prep_free_lds_bytes(pl));
+  }
   if (lds > 48 * 1024) hipFuncSetAttribute((const void*)k_bfs_rows<W, Robots>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const uint32_t per_cu = std::max<uint32_t>(1u, std::min<uint32_t>(std::min<uint32_t>(24u / nw, (uint32_t)((156u * 1024u) / (lds + 1024))), 4u));
-  hipLaunchKernelGGL((k_bfs_rows<W, Robots>), dim3(std::min(count * pl.bfs_grids, per_cu * bfs_cu_count())), dim3(nw * 64), lds, s, pl, robots, count, pl.bfs_next_item + 1, order);
+  hipLaunchKernelGGL((k_bfs_rows<W, Robots>), dim3(std::min(count * pl.bfs_grids, per_cu * bfs_cu_count()) + prep_count), dim3(nw * 64), lds, s, pl, robots, count, pl.bfs_next_item + 1, order, prep_count);
 }
 template <class Robots>
-static bool launchBfsRows(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order) {
+static bool launchBfsRows(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order, uint32_t prep_count = 0) {
   switch (bfs_rows_words(pl.nx, pl.ny)) {
-    case 7: launch_bfs_rows_w<7>(pl, robots, count, s, order); return true;
-    case 13: launch_bfs_rows_w<13>(pl, robots, count, s, order); return true;
-    case 20: launch_bfs_rows_w<20>(pl, robots, count, s, order); return true;
+    case 7: launch_bfs_rows_w<7>(pl, robots, count, s, order, prep_count); return true;
+    case 13: launch_bfs_rows_w<13>(pl, robots, count, s, order, prep_count); return true;
+    case 20: launch_bfs_rows_w<20>(pl, robots, count, s, order, prep_count); return true;
     default: return false;
   }
 }
@@ -955,6 +974,17 @@ bool launch_bfs_rows(const PlannerDev& pl, uint32_t first, uint32_t count, hipSt
 }
 bool launch_bfs_rows_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order) {
   return launchBfsRows(pl, RobotList{list}, count, s, order);
+}
+// A cycle's wavefront launch with the grid-free part of the scoring image in it (navgpu_planner_set_split_prep): where the sweep
+// scores and the map is k_bfs_rows'.  The launch behind it is launch_score_grids(_list).
+// The image buffer stays single with two cycles in flight: this launch of cycle k + 1 is behind k_select of cycle k on the fleet's
+// one stream, and k_score_sweep and the terms pass of cycle k, the image's only readers, come before that k_select.
+bool split_prep_applies(const PlannerDev& pl) { return score_sweep_applies(pl) && bfs_rows_fits(pl.nx, pl.ny); }
+void launch_bfs_prep(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order) {
+  launchBfsRows(pl, RobotRange{first}, count, s, order, count);
+}
+void launch_bfs_prep_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order) {
+  launchBfsRows(pl, RobotList{list}, count, s, order, count);
 }
 template <class Robots>
 static bool launchBfsRows2(const PlannerDev& pl, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order) {

@@ -28,327 +28,6 @@ __device__ unsigned long long g_prep_stats[16];
 #define PREP_STAMP(i)
 #endif
 
-// The robot a workgroup works on (blockIdx.y) and its costmap window in LDS: win x win cells from map cell (wx0, wy0)
-struct ScoreRobot {
-  uint32_t inst;
-  Geom g;
-  navgpu_robot_state st;
-  const uint8_t* master;
-  const uint32_t *dpath, *dgoal, *dfront;
-  const int32_t* cnt;
-  uint32_t nfp;
-  int win, wx0, wy0;
-  int win_bytes, nw;  // the window's bytes rounded up to 16, 32-cell words per window row
-};
-__device__ __forceinline__ ScoreRobot scoreRobot(const PlannerDev& pl, uint32_t inst) {
-  ScoreRobot r;
-  r.inst = inst;
-  r.g = geomOf(pl, inst);
-  r.st = pl.state[inst];
-  r.master = pl.master + (size_t)inst * pl.cells_padded;
-  r.dpath = pl.path + (size_t)inst * pl.cells;
-  r.dgoal = pl.goal + (size_t)inst * pl.cells;
-  r.dfront = pl.goal_front + (size_t)inst * pl.cells;
-  r.cnt = pl.axis_count + 4 * inst;
-  r.nfp = pl.fp_n[inst];
-  r.win = (int)pl.win;
-  r.win_bytes = (r.win * r.win + 15) & ~15;
-  r.nw = (r.win + 31) >> 5;
-  return r;
-}
-// the window's origin: robot cell (floor of the map coordinate, also valid when the robot is off the map) - win / 2
-__device__ __forceinline__ void placeWindow(ScoreRobot& r) {
-  double fx = floor(((double)r.st.pos[0] - r.g.ox) / r.g.res), fy = floor(((double)r.st.pos[1] - r.g.oy) / r.g.res);
-  fx = fmin(fmax(fx, -1.0e6), 1.0e6);
-  fy = fmin(fmax(fy, -1.0e6), 1.0e6);
-  r.wx0 = (int)fx - r.win / 2;
-  r.wy0 = (int)fy - r.win / 2;
-}
-
-// ---- stage: footprint and per-axis samples (not for an explicit sample) to LDS, the workgroup's counters cleared, the
-// window placed and its bytes staged
-template <bool EXPLICIT>
-__device__ __forceinline__ void stageInputs(const PlannerDev& pl, ScoreRobot& r, double* s_fp, float (*s_axis)[kMaxAxis], int* s_cnt, uint8_t* s_win) {
-  const uint32_t tid = threadIdx.x;
-  const Geom& g = r.g;
-  if (tid < 2 * r.nfp) s_fp[tid] = pl.fp_spec[(size_t)r.inst * kMaxFootprint * 2 + tid];
-  if (!EXPLICIT) {
-    for (uint32_t i = tid; i < 3 * kMaxAxis; i += blockDim.x) {
-      uint32_t a = i / kMaxAxis, k = i - a * kMaxAxis;
-      s_axis[a][k] = k < pl.max_axis ? pl.axis_samples[((size_t)r.inst * 3 + a) * pl.max_axis + k] : 0.f;
-    }
-  }
-  if (tid == 0) s_cnt[0] = s_cnt[1] = 0;
-  placeWindow(r);
-  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0;
-  // (eight loads of a lane in flight at a time - unconditional, clamped: a conditional load in a rolled loop is waited
-  // for on its own, nine latencies in a row for a 65 x 65 window)
-  for (int i0 = tid; i0 < win * win; i0 += 8 * (int)blockDim.x) {
-    uint8_t v[8];
-    bool in_map[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int ic = min(i0 + u * (int)blockDim.x, win * win - 1);
-      const int ly = ic / win, lx = ic - ly * win;
-      const int gx = wx0 + lx, gy = wy0 + ly;
-      in_map[u] = gx >= 0 && gy >= 0 && gx < (int)g.nx && gy < (int)g.ny;
-      v[u] = r.master[min(max(gy, 0), (int)g.ny - 1) * g.nx + min(max(gx, 0), (int)g.nx - 1)];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + u * (int)blockDim.x;
-      if (i < win * win) s_win[i] = in_map[u] ? v[u] : (uint8_t)0;
-    }
-  }
-}
-
-// ---- stage: per-cell screens of the window, four bitmaps interleaved per 32-cell word: s_fb[(y * nw + j) * 4 + k]
-// Footprint shortcuts: the cells a footprint with centre cell c can touch lie within the Chebyshev radius
-// fp_rcells of c (>= circumscribed radius in cells + 1).  Two bitmaps of the window, dilated by that radius, are
-// built once per robot (bit-parallel: rows of 32-cell words, shifts for the horizontal pass, word ORs for the
-// vertical one; everything outside the window or off the map counts as set):
-//   k = 0: some cell in reach is not FREE_SPACE  -> clear = the point's footprint cost is exactly 0
-//   k = 1: some cell in reach fails pointCost    -> clear = the point is legal (cost not needed)
-// MapGrid screens (not dilated): a trajectory point only has to NOT be an obstacle / unreachable cell of the path and
-// goal grids unless it is the last one (aggregation Last, map_grid_cost_function.cpp:92-127):
-//   k = 2: path grid holds obstacleCosts() or unreachableCellCosts() here    k = 3: the goal grid does
-// s_ba: build scratch behind the image (window + bitmaps + tables): [win][nw][2] raw, [win][nw][2] after the horizontal pass.
-// The LDS window is kept in "walk order": with allow_unknown the bytes 254 (LETHAL) and 255 (NO_INFORMATION)
-// are swapped, so that in both modes a footprint cell fails pointCost iff its stored byte >= walk_fail and the
-// polygon walk needs nothing but a running maximum per cell (cellCost() undoes the swap).
-__device__ __forceinline__ void buildScreens(const PlannerDev& pl, const ScoreRobot& r, uint8_t* s_dyn, uint32_t* s_ba) {
-  const uint32_t tid = threadIdx.x;
-  const Geom& g = r.g;
-  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0, nw = r.nw;
-  const uint32_t *dpath = r.dpath, *dgoal = r.dgoal;
-  uint8_t* s_win = s_dyn;
-  uint32_t* s_fb = reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes);  // [win][nw][4]
-  const int rc = (int)pl.fp_rcells;
-  const uint8_t fail_span_w = (pl.cfg.allow_unknown != 0) ? 0 : 1;
-  {  // the raw bits: 64 consecutive cells of a (padded) window row per wave step, packed by ballot
-    const int row_cells = nw * 32;
-    const bool obst_off = pl.scale_obstacle == 0;  // obstacle critic off (scale 0: skipped, simple_scored_sampling_planner.cpp:55-57): nothing to screen
-    for (int base = (int)(tid & ~63u); base < win * row_cells; base += (int)blockDim.x) {
-      const int idx = base + (int)(tid & 63u);
-      const int y = idx / row_cells, lx = idx - y * row_cells;
-      // cells off the MAP count as set like cells outside the window: a footprint vertex there fails
-      // worldToMap, i.e. footprintCost = -1 (costmap_model.cpp:77-99), which only the polygon walk reports
-      const int gx = wx0 + lx, gy = wy0 + y;
-      const bool in = lx < win && y < win && gx >= 0 && gy >= 0 && gx < (int)g.nx && gy < (int)g.ny;
-      const uint8_t cc = s_win[in ? y * win + lx : 0];
-      const bool o = !obst_off && (!in || cc != 0), f = !obst_off && (!in || (uint8_t)(cc - kLethal) <= fail_span_w);
-      const unsigned long long mo = __ballot(o), mf = __ballot(f);
-      if ((tid & 63u) == 0) {
-        const int w = idx >> 5;  // linear word index y * nw + j; a wave covers two words (possibly of two rows)
-        s_ba[2 * w] = (uint32_t)mo;
-        s_ba[2 * w + 1] = (uint32_t)mf;
-        if (w + 1 < win * nw) {
-          s_ba[2 * (w + 1)] = (uint32_t)(mo >> 32);
-          s_ba[2 * (w + 1) + 1] = (uint32_t)(mf >> 32);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // The dilation: a DISC (PlannerDev::fp_halfw: per row offset dy the largest |dx| an outline cell can have), not the Chebyshev
-  // square around it - a fifth to a quarter fewer cells, and every cell less is trajectory points that need not be looked at.
-  // Grouped by dx: the rows that contribute at |dx| = d are |dy| <= Y(d) (the half widths fall with |dy|), so the rows are OR-ed
-  // in from the centre outwards (the word and its two neighbours) and row offset Y shifts the running OR by the d's it is the
-  // last row for: halfw[Y + 1] < d <= halfw[Y].  One shift pair per d instead of one per cell of the disc.
-  for (int it = tid; it < 2 * win * nw; it += blockDim.x) {
-    const int cell = it >> 1;
-    const int y = cell / nw, j = cell - y * nw;
-    uint32_t m = (y - rc < 0 || y + rc >= win || rc > 31) ? 0xFFFFFFFFu : 0u;  // (reach beyond the neighbouring words: no shortcut)
-    if (!m) {
-      uint32_t vc = 0, vl = j > 0 ? 0u : 0xFFFFFFFFu, vr = j + 1 < nw ? 0u : 0xFFFFFFFFu;
-      for (int Y = 0; Y <= rc; ++Y) {
-        const int w = (int)pl.fp_halfw[Y];
-        if (w == 0xFF) break;
-        const int up = it + 2 * Y * nw, dn = it - 2 * Y * nw;
-        vc |= s_ba[up] | s_ba[dn];
-        if (j > 0) vl |= s_ba[up - 2] | s_ba[dn - 2];
-        if (j + 1 < nw) vr |= s_ba[up + 2] | s_ba[dn + 2];
-        const int wn = (Y + 1 <= rc && pl.fp_halfw[Y + 1] != 0xFF) ? (int)pl.fp_halfw[Y + 1] : -1;  // (the outermost row: every d down to 0)
-        for (int d = wn + 1; d <= w; ++d) m |= d == 0 ? vc : (__builtin_amdgcn_alignbit(vc, vl, 32 - d) | __builtin_amdgcn_alignbit(vr, vc, d));
-      }
-    }
-    s_fb[4 * cell + (it & 1)] = m;
-  }
-  {  // MapGrid screens: 64 consecutive cells of a (padded) window row per wave step, packed by ballot
-    const uint32_t n_obst = pl.cells, n_unreach = pl.cells + 1;
-    const int row_cells = nw * 32;
-    // (four steps of a wave = eight distance loads per lane in flight, unconditional and clamped, as for the window above)
-    for (int base0 = (int)(tid & ~63u); base0 < win * row_cells; base0 += 4 * (int)blockDim.x) {
-      uint32_t dp[4], dg[4];
-      bool in_map[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int idx = min(base0 + u * (int)blockDim.x + (int)(tid & 63u), win * row_cells - 1);
-        const int y = idx / row_cells, lx = idx - y * row_cells;
-        const int gx = wx0 + lx, gy = wy0 + y;
-        in_map[u] = lx < win && gx >= 0 && gy >= 0 && gx < (int)g.nx && gy < (int)g.ny;
-        const uint32_t cell = (uint32_t)(min(max(gy, 0), (int)g.ny - 1)) * g.nx + (uint32_t)min(max(gx, 0), (int)g.nx - 1);
-        dp[u] = dpath[cell];
-        dg[u] = dgoal[cell];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int base = base0 + u * (int)blockDim.x;
-        if (base < win * row_cells) {  // (wave-uniform)
-          const int idx = base + (int)(tid & 63u);
-          bool pf = true, gf = true;
-          if (in_map[u] && idx < win * row_cells) {
-            pf = dp[u] == n_obst || dp[u] == n_unreach;
-            gf = dg[u] == n_obst || dg[u] == n_unreach;
-          }
-          pf = pf && pl.scale_path != 0;  // a critic with scale 0 is never evaluated: its screen stays clear
-          gf = gf && pl.scale_goal != 0;
-          const unsigned long long mp = __ballot(pf), mg = __ballot(gf);
-          if ((tid & 63u) == 0) {
-            const int w = idx >> 5;  // linear word index y * nw + j; a wave covers two words (possibly of two rows)
-            s_fb[4 * w + 2] = (uint32_t)mp;
-            s_fb[4 * w + 3] = (uint32_t)mg;
-            if (w + 1 < win * nw) {
-              s_fb[4 * (w + 1) + 2] = (uint32_t)(mp >> 32);
-              s_fb[4 * (w + 1) + 3] = (uint32_t)(mg >> 32);
-            }
-          }
-        }
-      }
-    }
-  }
-  if (pl.cfg.allow_unknown != 0) {  // walk order
-    __syncthreads();
-    for (int i = tid; i < win * win; i += blockDim.x) {
-      const uint8_t cc = s_win[i];
-      if (cc >= 254) s_win[i] = cc ^ 1u;
-    }
-  }
-}
-
-// ---- stage (the tables, use_tables: use_dwa && discretize_by_time, k_score_prep_tab only): per-(v_theta sample, step) heading, trig and
-// rotated footprint, all tab_nth v_theta rows, behind the screens
-__device__ __forceinline__ void buildTables(const PlannerDev& pl, const ScoreRobot& r, const double* s_fp, const float (*s_axis)[kMaxAxis], uint8_t* s_dyn) {
-  const uint32_t tid = threadIdx.x;
-  const navgpu_dwa_config& c = pl.cfg;
-  const navgpu_robot_state& st = r.st;
-  const uint32_t nfp = r.nfp;
-  const int K = (int)pl.tab_steps;
-  const int tnfp = (int)pl.tab_nfp;
-  const int nth_s = r.cnt[2];
-  const int lrows = (int)pl.tab_nth;
-  double* s_trig = reinterpret_cast<double*>(s_dyn + r.win_bytes + score_bits_bytes(r.win));  // [rows][K][4] cs, sn, cs2, sn2
-  double* s_rot = s_trig + (size_t)lrows * K * 4;                                              // [rows][K][tnfp][2]
-  float* s_th = reinterpret_cast<float*>(s_rot + (size_t)lrows * K * tnfp * 2);                // [rows][K]
-  __syncthreads();  // s_axis, s_fp staged
-  const double dt_t = c.sim_time / K;
-  if ((int)tid < nth_s) {
-    float pth = st.pos[2];
-    const float vth = s_axis[2][tid];
-    for (int k = 0; k < K; ++k) {
-      s_th[tid * K + k] = pth;
-      pth = (float)(pth + vth * dt_t);  // computeNewPositions :258
-    }
-  }
-  __syncthreads();
-  for (int e = tid; e < nth_s * K; e += blockDim.x) {
-    const double th = s_th[e];
-    double sn, cs, sn2, cs2;
-    sincos(th, &sn, &cs);
-    sincos(M_PI_2 + th, &sn2, &cs2);
-    s_trig[4 * e] = cs;
-    s_trig[4 * e + 1] = sn;
-    s_trig[4 * e + 2] = cs2;
-    s_trig[4 * e + 3] = sn2;
-    for (int v = 0; v < (int)nfp && v < tnfp; ++v) {
-      const double sx = s_fp[2 * v], sy = s_fp[2 * v + 1];
-      s_rot[(e * tnfp + v) * 2] = sx * cs - sy * sn;      // world_model.h:72-73
-      s_rot[(e * tnfp + v) * 2 + 1] = sx * sn + sy * cs;
-    }
-  }
-}
-
-// ---- stage: the LDS image as 16-byte words, [0, prep_bytes), to the robot's slot of pl.prep
-__device__ __forceinline__ void storeImage(const PlannerDev& pl, const ScoreRobot& r, const uint8_t* s_dyn) {
-  uint4* img = reinterpret_cast<uint4*>(pl.prep + (size_t)r.inst * pl.prep_stride);
-  const uint4* lds = reinterpret_cast<const uint4*>(s_dyn);
-  const uint32_t n16 = pl.prep_bytes >> 4;
-  for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) img[i] = lds[i];
-}
-
-// ---- stage (k_score_prep_tab only): the sweep's per-robot scalars and the reject bytes of the (vx, vy) pairs, behind the image
-__device__ __forceinline__ void storeSweepScalars(const PlannerDev& pl, const ScoreRobot& r, const float (*s_axis)[kMaxAxis], int* s_cnt,
-                                                  const uint8_t* s_dyn) {
-  const uint32_t tid = threadIdx.x;
-  const navgpu_dwa_config& c = pl.cfg;
-  const Geom& g = r.g;
-  const int32_t* cnt = r.cnt;
-  const uint32_t inst = r.inst;
-  const int win = r.win, wx0 = r.wx0, wy0 = r.wy0, nw = r.nw;
-  const uint32_t* s_fb = reinterpret_cast<const uint32_t*>(s_dyn + r.win_bytes);
-  // What every lane of the sweep launch would otherwise work out again: the robot's scalars (two fp64 divisions, a ceil)
-  // and the generator's reject tests of the (vx, vy) pairs (a compensated fp64 square root each) - behind the image.
-  uint8_t* rej = pl.prep + (size_t)inst * pl.prep_stride + score_prep_reject_offset(pl);
-  int32_t* aux = reinterpret_cast<int32_t*>(rej - kScoreAuxBytes);
-  // d0: how far (Euclidean, cells, rounded down) from the robot's own cell - the window's centre - the nearest cell lies at which ANY screen is
-  // set (or the window ends).  A trajectory point fewer cells away than that passes every screen whatever else: the sweep skips
-  // its worldToMap and look-up for as many steps as the sample's speed cannot cover d0 cells in (k_score_sweep).
-  // The path / goal screen at the robot's own cell decides those critics for EVERY sample at step 0 (all rollouts start there):
-  // start_fail = 4 (the path critic fails there; the goal critic, later in the list, no longer counts either) or 5 (the goal
-  // critic does - e.g. a goal inside an inflated wall, 17 % of the benchmark's robots) or 0.  The distance is taken over the
-  // screens that still count after that.
-  const int c0 = win / 2;
-  const uint32_t w_c0 = (uint32_t)(c0 * nw + (c0 >> 5));
-  const int start_fail = ((s_fb[4 * w_c0 + 2] >> (c0 & 31)) & 1u) ? 4 : (((s_fb[4 * w_c0 + 3] >> (c0 & 31)) & 1u) ? 5 : 0);
-  if (tid == 0) s_cnt[0] = (win / 2) * (win / 2);  // (squared: the distance is Euclidean - a pose moves |v| dt whatever its bearing)
-  __syncthreads();
-  {
-    int dmin = win * win;
-    for (int it = tid; it < win * nw; it += blockDim.x) {
-      const int y = it / nw, j = it - y * nw;
-      uint32_t m = (c.sum_scores ? s_fb[4 * it] : s_fb[4 * it + 1]) | (start_fail == 4 ? 0u : s_fb[4 * it + 2]) | (start_fail != 0 ? 0u : s_fb[4 * it + 3]);
-      const int dy = y > c0 ? y - c0 : c0 - y;
-      // the set cell nearest to column c0: the lowest set bit at or right of it, the highest left of it (no loop over the bits)
-      const int p = c0 - 32 * j;  // c0's bit position in this word (may lie outside it)
-      const uint32_t right = p <= 0 ? m : (p >= 32 ? 0u : m & (0xFFFFFFFFu << p)), left = m & ~right;
-      if (right) dmin = min(dmin, (32 * j + __ffs(right) - 1 - c0) * (32 * j + __ffs(right) - 1 - c0) + dy * dy);
-      if (left) dmin = min(dmin, (c0 - (32 * j + 31 - __clz(left))) * (c0 - (32 * j + 31 - __clz(left))) + dy * dy);
-    }
-    atomicMin(&s_cnt[0], dmin);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const double inv_res = pl.inv_res, fpd = c.forward_point_distance;
-    const bool en_fwd = pl.scale_goal != 0 || (pl.align_on[inst] && pl.scale_path != 0);  // goal_front or alignment critic on
-    // the forward point (x + fpd cos, y + fpd sin) stays on the map whenever the centre cell is this many cells away from
-    // every border; only then may a step skip its worldToMap
-    const uint32_t fwd_margin = (uint32_t)fmin(ceil(fabs(fpd) * inv_res) + 1.0, 1.0e6);
-    const bool fwd_screen = !en_fwd || (2u * fwd_margin < g.nx && 2u * fwd_margin < g.ny);
-    const uint32_t fwd_lo = en_fwd ? fwd_margin : 0u, fwd_nx = g.nx - 2u * fwd_lo, fwd_ny = g.ny - 2u * fwd_lo;
-    // the forward-margin test is only needed when the LDS window reaches into the margin band of the map
-    const bool need_margin = !((uint32_t)wx0 - fwd_lo < fwd_nx && (uint32_t)(wx0 + win - 1) - fwd_lo < fwd_nx && (uint32_t)wy0 - fwd_lo < fwd_ny &&
-                               (uint32_t)(wy0 + win - 1) - fwd_lo < fwd_ny);
-    aux[0] = wx0;
-    aux[1] = wy0;
-    aux[2] = (int32_t)fwd_lo;
-    aux[3] = (int32_t)fwd_nx;
-    aux[4] = (int32_t)fwd_ny;
-    aux[5] = need_margin ? 1 : 0;
-    aux[6] = fwd_screen ? 1 : 0;
-    aux[7] = (int)floor(sqrt((double)s_cnt[0]));
-    aux[8] = start_fail;
-  }
-  // generateTrajectory's reject tests (simple_trajectory_generator.cpp:193-200), the part that depends on (vx, vy) only:
-  // bit 0: vmag + eps < min_trans_vel (rejects together with the v_theta half), bit 1: vmag - eps > max_trans_vel
-  const int nyv = max(cnt[1], 1), nxyv = cnt[0] * cnt[1];
-  for (int i = tid; i < nxyv; i += blockDim.x) {
-    const int ix = i / nyv, iy = i - ix * nyv;
-    const double vmag = hyp2((double)s_axis[0][ix], (double)s_axis[1][iy]);
-    const double eps = 1e-4;
-    rej[i] = (uint8_t)(((c.min_trans_vel >= 0 && vmag + eps < c.min_trans_vel) ? 1 : 0) | ((c.max_trans_vel >= 0 && vmag - eps > c.max_trans_vel) ? 2 : 0));
-  }
-}
-
 // ---- stage (k_score_gen*): the footprint and the axis samples, loaded into registers before the image copy
 struct ScoreInputs {
   static constexpr int kAxisChunks = (3 * kMaxAxis + kScoreThreads - 1) / kScoreThreads;
@@ -921,6 +600,34 @@ __global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev
   }
 #endif
 }
+// k_score_prep_grids: completes the image scorePrepFree stored (the prep workgroups of the wavefront launch) once the path and goal
+// grids stand: words 2 and 3 of every screen cell, the free distance and start_fail (aux[7], aux[8]).  No other byte of the image
+// changes.  Latency bound, so every load it needs is issued before the first is waited for: STEPS covers the padded window.
+template <int STEPS, class Robots>
+__global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_grids(PlannerDev pl, Robots robots) {
+  extern __shared__ __align__(16) uint8_t s_dyn[];
+  __shared__ int s_min;
+  ScoreRobot r = scoreRobot(pl, robots(blockIdx.y));
+  placeWindow(r);
+  uint32_t* s_fb = reinterpret_cast<uint32_t*>(s_dyn);  // [win][nw][4]
+  uint4* img = reinterpret_cast<uint4*>(pl.prep + (size_t)r.inst * pl.prep_stride + r.win_bytes);
+  const int n = r.win * r.nw;
+  // words 0 and 1 come back from the stored image: the first of a lane is in flight with the grid loads
+  const uint4 v0 = img[min((int)threadIdx.x, n - 1)];
+  buildGridScreens<STEPS>(pl, r, s_fb);
+  if ((int)threadIdx.x < n) {
+    s_fb[4 * threadIdx.x] = v0.x;
+    s_fb[4 * threadIdx.x + 1] = v0.y;
+  }
+  for (int it = threadIdx.x + blockDim.x; it < n; it += blockDim.x) {
+    const uint4 v = img[it];
+    s_fb[4 * it] = v.x;
+    s_fb[4 * it + 1] = v.y;
+  }
+  __syncthreads();
+  for (int it = threadIdx.x; it < n; it += blockDim.x) *reinterpret_cast<uint2*>(&img[it].z) = make_uint2(s_fb[4 * it + 2], s_fb[4 * it + 3]);
+  storeFreeDistance(pl, r, s_fb, &s_min);
+}
 // k_score_prep_gen: a robot's image (window and screens) for the k_score_gen* workgroups
 // (Plain kernels around one body, not a template like the others: the statics of a kernel template have vague linkage, and the
 // compiler then keeps the 2 KB of s_fp / s_axis that this kernel stages and never reads - as a plain kernel it drops them.)
@@ -1066,19 +773,31 @@ size_t score_prep_bytes(const PlannerDev& pl) {  // the LDS image k_score_prep* 
 size_t score_prep_slot_bytes(const PlannerDev& pl) {  // a robot's slot of pl.prep: the image, the sweep launch's scalars, the pairs' reject bytes
   return ((score_prep_bytes(pl) + 255) & ~(size_t)255) + kScoreAuxBytes + score_prep_reject_bytes(pl);
 }
+size_t score_prep_free_lds_bytes(const PlannerDev& pl) {
+  return score_window_bytes(pl.win) + pl.tab_bytes + score_scratch_bytes((int)pl.win) + score_prep_free_tail_bytes();
+}
+void score_prep_tab_sizes(PlannerDev& pl) {
+  // the prep workgroup builds all table rows (its LDS holds the whole image); a sweep workgroup loads one row group
+  pl.tab_bytes = (uint32_t)score_table_bytes(pl);
+  pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
+}
 static uint32_t sweepLaunch(const PlannerDev& pl, RobotRange r, uint32_t count, hipStream_t s) { return launch_score_sweep(pl, r.first, count, s); }
 static uint32_t sweepLaunch(const PlannerDev& pl, RobotList r, uint32_t count, hipStream_t s) { return launch_score_sweep_list(pl, r.list, count, s); }
 // a cycle's scoring launches for the robots of a range or a list
 template <class Robots>
-static uint32_t launchScoreCycle(const PlannerDev& pl_in, Robots robots, uint32_t count, hipStream_t s) {
+static uint32_t launchScoreCycle(const PlannerDev& pl_in, Robots robots, uint32_t count, hipStream_t s, bool grids_only = false) {
   PlannerDev pl = pl_in;
   const size_t win_bytes = score_window_bytes(pl.win);
   const size_t scratch = score_scratch_bytes((int)pl.win);  // only where the image is built
   if (score_sweep_applies(pl)) {
-    // the prep launch builds all table rows (its LDS holds the whole image); a sweep workgroup loads one row group
-    pl.tab_bytes = (uint32_t)score_table_bytes(pl);
-    pl.prep_bytes = (uint32_t)score_prep_bytes(pl);
-    launchScore(k_score_prep_tab<Robots>, dim3(1, count), kScorePrepThreads, win_bytes + score_table_bytes(pl) + scratch, s, pl, robots);
+    score_prep_tab_sizes(pl);
+    if (grids_only) {  // the wavefront launch's prep workgroups have stored the rest of the image (launch_bfs_prep)
+      const uint32_t steps = ((uint32_t)pl.win * ((pl.win + 31) & ~31u) + kScorePrepThreads - 1) / kScorePrepThreads;
+      auto grids = steps <= 8 ? k_score_prep_grids<8, Robots> : (steps <= 16 ? k_score_prep_grids<16, Robots> : k_score_prep_grids<32, Robots>);
+      launchScore(grids, dim3(1, count), kScorePrepThreads, score_bits_bytes((int)pl.win), s, pl, robots);
+    } else {
+      launchScore(k_score_prep_tab<Robots>, dim3(1, count), kScorePrepThreads, win_bytes + score_table_bytes(pl) + scratch, s, pl, robots);
+    }
     return sweepLaunch(pl, robots, count, s);
   }
   // the general path (no tables, or mg_generic: the general step has no table variant)
@@ -1103,6 +822,11 @@ uint32_t launch_score(const PlannerDev& pl, uint32_t first, uint32_t count, cons
   return launchScoreCycle(pl, RobotRange{first}, count, s);
 }
 uint32_t launch_score_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s) { return launchScoreCycle(pl, RobotList{list}, count, s); }
+// the scoring launches behind a wavefront launch with prep workgroups (split_prep_applies): k_score_prep_grids in k_score_prep_tab's place
+uint32_t launch_score_grids(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s) { return launchScoreCycle(pl, RobotRange{first}, count, s, true); }
+uint32_t launch_score_grids_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s) {
+  return launchScoreCycle(pl, RobotList{list}, count, s, true);
+}
 
 // The probes of n_robots listed robots in one launch; max_probes: the longest run of the list (> 0).  The image is built in the
 // workgroup, so the dynamic LDS is k_score_explicit's.

@@ -438,6 +438,10 @@ class Fleet:
         """navgpu_planner_set_seed_lists: a cycle's k_samples turns the plans into the wavefronts' seed cells (default on)."""
         check(self.L.navgpu_planner_set_seed_lists(self.h, 1 if enable else 0), "set_seed_lists")
 
+    def set_split_prep(self, enable):
+        """navgpu_planner_set_split_prep: the grid-free part of the scoring image is built inside the wavefront launch (default on)."""
+        check(self.L.navgpu_planner_set_split_prep(self.h, 1 if enable else 0), "set_split_prep")
+
     def set_seed_list_capacity(self, cells):
         """navgpu_planner_set_seed_list_capacity (test hook): a (robot, grid) with more seed cells walks the plan itself."""
         check(self.L.navgpu_planner_set_seed_list_capacity(self.h, int(cells)), "set_seed_list_capacity")
