@@ -349,8 +349,43 @@ int navgpu_obstacle_update_costs(navgpu_fleet* fleet, uint32_t first, uint32_t c
 /* ------------------------------------------------------------------------------------------ */
 /* DWA local planner                                                                          */
 /* ------------------------------------------------------------------------------------------ */
-/* replaces: DWAPlanner::reconfigure (dwa_planner.cpp:52-116) */
+/* replaces: DWAPlanner::reconfigure (dwa_planner.cpp:52-116).  The eleven velocity / acceleration fields go into EVERY robot's limits
+ * record (navgpu_planner_set_limits below): a caller who slowed one robot sets that robot's limits again after this call. */
 int navgpu_planner_configure(navgpu_fleet* fleet, const navgpu_dwa_config* config);
+
+/* base_local_planner::LocalPlannerLimits of ONE robot (local_planner_limits.h:47-65); field order is ABI */
+typedef struct {
+  double max_trans_vel, min_trans_vel;
+  double max_vel_x, min_vel_x, max_vel_y, min_vel_y;
+  double max_rot_vel, min_rot_vel;
+  double acc_lim_x, acc_lim_y, acc_lim_theta;
+  double xy_goal_tolerance, yaw_goal_tolerance;
+  double trans_stopped_vel, rot_stopped_vel;
+  int32_t prune_plan, reserved;
+} navgpu_robot_limits;
+/* replaces: LocalPlannerUtil::reconfigureCB (local_planner_util.cpp:59-71) of the robots [first, first+count), each of which owns
+ * its LocalPlannerLimits in the reference (dwa_planner_ros.cpp:65-83), and MoveSlowAndClear::setRobotSpeed
+ * (move_slow_and_clear.cpp:135-150,188-214) for the one robot that is recovering.  limits = count records.
+ * One record feeds both halves, as the reference's one LocalPlannerLimits feeds DWAPlanner and LatchedStopRotateController: the
+ * planner's (the eleven velocity / acceleration limits: sample windows, reject tests, continued acceleration,
+ * updateOscillationFlags, the wavefront box) and the control cycle's (tolerances, stopped velocities, rot / acc limits, prune_plan).
+ * Robots outside the range stay byte for byte as they were; sim_period, latch_xy_goal_tolerance and every other field of
+ * navgpu_dwa_config stay the fleet's.  The fleet-wide calls keep their meaning: navgpu_planner_configure writes its eleven fields
+ * into every robot's record, navgpu_local_planner_configure its fields into every robot's control half - set one robot's limits
+ * again after either.  A fleet that never calls this behaves as if the call did not exist.
+ * Takes effect with the robot's next staged cycle or probe (navgpu_planner_stage*, navgpu_planner_check_trajector*, the control
+ * cycle), whose upload carries the record up: with two cycles in flight the queued cycle runs on the old limits, the next on the
+ * new.  Inside what the fleet's scoring window and step capacity were planned for - the largest limits since the last
+ * navgpu_planner_configure - the call allocates nothing and does not wait for the stream; beyond it, it re-plans the window and
+ * image as navgpu_planner_configure does, all-or-nothing (NAVGPU_ERR_HIP, NAVGPU_ERR_CAPACITY when discretize_by_time = 0 needs
+ * more than max_sim_steps: the previous limits stay in force).  NAVGPU_ERR_INVALID for a bad range, NULL or a non-finite field,
+ * nothing changed; NAVGPU_ERR_STATE before the first navgpu_planner_configure.  Negative max_trans_vel / min_trans_vel /
+ * min_rot_vel switch their test off, as in navgpu_dwa_config (the kernels' `>= 0` guards).
+ * The legacy TrajectoryPlanner (navgpu_tp_config) has its own configuration and kernels and does not read these records. */
+int navgpu_planner_set_limits(navgpu_fleet* fleet, uint32_t first, uint32_t count, const navgpu_robot_limits* limits);
+/* replaces: LocalPlannerUtil::getCurrentLimits (local_planner_util.cpp:77-80) of the robots [first, first+count): what the calls
+ * above left, the eleven velocity / acceleration fields from the planner's half */
+int navgpu_planner_get_limits(navgpu_fleet* fleet, uint32_t first, uint32_t count, navgpu_robot_limits* limits);
 /* replaces: DWAPlanner::setPlan (dwa_planner.cpp:204-207): resets the oscillation flags */
 int navgpu_planner_set_plan(navgpu_fleet* fleet, uint32_t first, uint32_t count);
 /* H2D staging of one control cycle (host -> HBM): robot states and the packed local plans
@@ -584,7 +619,8 @@ int navgpu_local_plan_window(const double* plan_xyyaw, uint32_t n, const double 
 /* angles::shortest_angular_distance(from, to) as restated here (exposed for the parity tests) */
 double navgpu_shortest_angular_distance(double from, double to);
 
-/* LocalPlannerUtil::reconfigureCB limits + LatchedStopRotateController parameters, for the whole fleet */
+/* LocalPlannerUtil::reconfigureCB limits + LatchedStopRotateController parameters, for the whole fleet: the control cycle's half
+ * of every robot's limits record (navgpu_planner_set_limits changes one robot's) */
 int navgpu_local_planner_configure(navgpu_fleet* fleet, const navgpu_local_limits* limits);
 /* DWAPlannerROS::setPlan: stores the global plan of one instance (n (x, y, yaw) triples in the plan's own
  * frame), clears the goal-tolerance latch and resets the oscillation flags.  plan_to_global = NULL: the

@@ -136,6 +136,19 @@ class LocalLimits(C.Structure):
                 ("sim_period", C.c_double), ("prune_plan", C.c_int32), ("latch_xy_goal_tolerance", C.c_int32)]
 
 
+class RobotLimits(C.Structure):
+    """navgpu_robot_limits: base_local_planner::LocalPlannerLimits of one robot (navgpu_planner_set_limits)."""
+    _fields_ = [(n, C.c_double) for n in (
+        "max_trans_vel", "min_trans_vel", "max_vel_x", "min_vel_x", "max_vel_y", "min_vel_y",
+        "max_rot_vel", "min_rot_vel", "acc_lim_x", "acc_lim_y", "acc_lim_theta",
+        "xy_goal_tolerance", "yaw_goal_tolerance", "trans_stopped_vel", "rot_stopped_vel")] + [
+        ("prune_plan", C.c_int32), ("reserved", C.c_int32)]
+    FIELDS = tuple(n for n, _ in _fields_[:-1])  # what a caller's record names; `reserved` is the library's
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n in self.FIELDS}
+
+
 class RobotInput(C.Structure):
     _fields_ = [("pose", C.c_double * 3), ("odom_vel", C.c_double * 3), ("have_pose", C.c_int32), ("reserved", C.c_int32)]
 
@@ -493,6 +506,8 @@ SYMBOLS = [
     ("navgpu_obstacle_update_bounds", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_obstacle_update_costs", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_planner_configure", C.c_int, [vp, C.POINTER(DwaConfig)]),
+    ("navgpu_planner_set_limits", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+    ("navgpu_planner_get_limits", C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
     ("navgpu_planner_set_plan", C.c_int, [vp, u32, u32]),
     ("navgpu_planner_stage", C.c_int, [vp, u32, u32, vp, vp, u32]),
     ("navgpu_planner_stage_poses", C.c_int, [vp, u32, u32, vp, vp]),

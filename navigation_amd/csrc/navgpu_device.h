@@ -131,6 +131,18 @@ struct CostmapDev {
   uint2* mark_seq;     // [n][max_points] voxel marking with mark_threshold > 0: (cell, valid | column bits before marking | z) in point order
 };
 
+// One robot's planner half of base_local_planner::LocalPlannerLimits (local_planner_limits.h:47-57): the eleven velocity and
+// acceleration limits, the leading fields of navgpu_dwa_config and of navgpu_robot_limits in their order.  PlannerDev::limits holds
+// one per instance; every kernel reads its robot's record where it used to read these fields of pl.cfg (whose copies are what
+// navgpu_planner_configure wrote last, for the legacy planner and the tools).
+struct RobotLimits {
+  double max_trans_vel, min_trans_vel;
+  double max_vel_x, min_vel_x, max_vel_y, min_vel_y;
+  double max_rot_vel, min_rot_vel;
+  double acc_lim_x, acc_lim_y, acc_lim_theta;
+};
+static_assert(sizeof(RobotLimits) == 88, "eleven doubles, as they lead navgpu_dwa_config and navgpu_robot_limits");
+
 struct PlannerDev {
   uint32_t nx, ny, cells;
   double res, inv_res;
@@ -138,6 +150,7 @@ struct PlannerDev {
   const uint8_t* master;
   uint32_t cells_padded;
   navgpu_dwa_config cfg;
+  RobotLimits* limits;        // [n] per-robot limits (navgpu_planner_set_limits; navgpu_planner_configure writes cfg's into every record)
   // derived once per configure (dwa_planner.cpp:64-75)
   double scale_path, scale_goal, scale_obstacle;
   uint32_t max_plan, max_sim_steps, max_axis;  // max_axis = per-axis sample capacity
@@ -387,6 +400,17 @@ struct PoseChunk {
 };
 static_assert(sizeof(PoseChunk) <= 4096, "kernel arguments are limited to 4 KB");
 void launch_stage_poses(const PoseChunk& c, hipStream_t s);
+// the limits records of up to 40 robots as one kernel-argument block, for the reason the poses travel that way (k_set_limits).
+// Weak as the list launchers below are; without it navgpu_planner_set_limits answers NAVGPU_ERR_STATE.
+constexpr uint32_t kLimitsChunk = 40;
+struct LimitsChunk {
+  RobotLimits* limits;  // the device table, indexed by absolute instance
+  uint32_t count, pad;
+  uint32_t inst[kLimitsChunk];
+  RobotLimits rec[kLimitsChunk];
+};
+static_assert(sizeof(LimitsChunk) <= 4096, "kernel arguments are limited to 4 KB");
+__attribute__((weak)) void launch_set_limits(const LimitsChunk& c, hipStream_t s);
 // ---- the cycle for a robot list (navgpu_planner_*_list): robot k of a launch is list[k], a device array, strictly increasing.
 // Weak for the reason launch_check_traj is: navgpu_host.cpp is also linked against a stand-in for the kernels that knows the
 // launchers of its day (tests/tsan); there the listed calls answer NAVGPU_ERR_STATE.  libnavgpu.so always carries the launchers.

@@ -183,7 +183,8 @@ struct navgpu_fleet {
     // What the control cycle's translation unit needs of the store, set by navgpu_local_planner_reserve_plans, so that it carries
     // no reference to the feature's launchers (as TrajCloud::terms_pass: it also links without them, tests/tsan).
     // window_pass: k_plan_window for the resident robots of the range with a pose and a plan, their records read into h_rec.
-    int (*window_pass)(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_input* in, double dist_threshold, int32_t prune) = nullptr;
+    // (prunePlan per robot: navgpu_fleet::lp_lim[i].prune_plan)
+    int (*window_pass)(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_input* in, double dist_threshold) = nullptr;
     bool (*goal_pose)(navgpu_fleet* f, uint32_t i, double goal[3]) = nullptr;                    // getGoalPose of a resident robot
     int (*stored_plan)(navgpu_fleet* f, uint32_t i, double* xyyaw, uint32_t capacity) = nullptr;  // navgpu_local_planner_get_plan
   } rp;
@@ -198,8 +199,17 @@ struct navgpu_fleet {
     double* d_poly_xy = nullptr;                            // its vertices, grown on demand
     size_t poly_cap = 0;                                    // vertices d_poly_xy holds
   } mb;
-  navgpu_local_limits lp_limits{};
+  navgpu_local_limits lp_limits{};               // what navgpu_local_planner_configure handed over: sim_period and the latch switch stay fleet-wide
+  std::vector<navgpu_local_limits> lp_lim;       // [n] the control cycle's half of every robot's limits (navgpu_planner_set_limits)
   bool lp_configured = false;
+  // Per-robot limits (navgpu_planner_set_limits): the planner's half of every robot's record as the host knows it.  A robot whose
+  // record has changed is dirty until the next call that stages it or probes it carries the record up to pl.limits (flushLimits):
+  // the reach that call works out on the host and the k_samples behind it then see the same limits, in stream order behind
+  // whatever cycle is still queued.
+  std::vector<RobotLimits> h_limits;             // [n]
+  std::vector<uint8_t> limits_dirty;             // [n]
+  uint32_t n_limits_dirty = 0;
+  double env_vmax = 0.0;                         // the speed the scoring window was planned for: the largest over the records since the last navgpu_planner_configure
   // legacy TrajectoryPlanner (navgpu_tp_*)
   struct TpHost {
     std::vector<double> plan;  // global_plan_ as x, y pairs

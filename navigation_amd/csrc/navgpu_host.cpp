@@ -233,11 +233,15 @@ int navgpu_fleet_create(const navgpu_fleet_desc* d, navgpu_fleet** out) {
   A(pl.counters, (size_t)n * 2);
   A(pl.osc_flags, n);
   A(pl.osc_prev, (size_t)n * 3);
+  A(pl.limits, n);
   A(pl.traj, (size_t)n * pl.max_sim_steps * 3);
 #undef A
   f->h_origin.assign((size_t)n * 2, 0.0);
   f->h_fp_spec.assign((size_t)n * kMaxFootprint * 2, 0.0);
   f->h_fp_n.assign(n, 0);
+  f->h_limits.assign(n, RobotLimits{});
+  f->limits_dirty.assign(n, 0);
+  f->lp_lim.assign(n, navgpu_local_limits{});
   f->grid_partial.assign(n, 0);
   f->obs_consumed.assign(n, 0);
   f->bounded_grids = true;  // navgpu_planner_set_bounded_map_grids
@@ -738,17 +742,26 @@ int navgpu_inflation_configure(navgpu_fleet* f, const navgpu_inflation_params* p
   return NAVGPU_OK;
 }
 
+// The largest speed a sample of a robot with these limits can have (generateTrajectory rejects what is faster than max_trans_vel)
+static double limitsVmax(const RobotLimits& c) {
+  if (c.max_trans_vel >= 0) return c.max_trans_vel + 1e-4;
+  return hypot(std::max(fabs(c.min_vel_x), fabs(c.max_vel_x)), std::max(fabs(c.min_vel_y), fabs(c.max_vel_y)));
+}
+// the planner's half of a robot's limits as a configuration carries it: its eleven leading fields
+static RobotLimits limitsOf(const navgpu_dwa_config& c) {
+  static_assert(offsetof(navgpu_dwa_config, acc_lim_theta) == offsetof(RobotLimits, acc_lim_theta) && offsetof(navgpu_dwa_config, sim_time) == sizeof(RobotLimits),
+                "the limits lead navgpu_dwa_config");
+  RobotLimits l;
+  memcpy(&l, &c, sizeof(l));
+  return l;
+}
 // The k_score image geometry (window, footprint chunk, heading tables) of a planner configuration `pl` with the given footprints,
 // worked out IN `pl` - a copy the caller commits only once everything the new configuration needs has been allocated.
-static void planWindow(const navgpu_fleet* f, PlannerDev& pl, const std::vector<uint32_t>& fp_n, const std::vector<double>& fp_spec, double fp_radius) {
+// vmax: limitsVmax over the robots' records - the fleet shares one window, planned for its fastest robot
+static void planWindow(const navgpu_fleet* f, PlannerDev& pl, const std::vector<uint32_t>& fp_n, const std::vector<double>& fp_spec, double fp_radius, double vmax) {
   // costmap window staged in LDS by k_score: everything a trajectory's footprint or shifted
   // point can touch.  Results never depend on it (cells outside fall back to global loads).
   const navgpu_dwa_config& c = pl.cfg;
-  double vmax;
-  if (c.max_trans_vel >= 0)
-    vmax = c.max_trans_vel + 1e-4;
-  else
-    vmax = hypot(std::max(fabs(c.min_vel_x), fabs(c.max_vel_x)), std::max(fabs(c.min_vel_y), fabs(c.max_vel_y)));
   double reach = vmax * c.sim_time + std::max(fp_radius, fabs(c.forward_point_distance));
   double cells = ceil(reach / pl.res) + 2;
   uint32_t win = (uint32_t)std::min(cells * 2 + 1, 240.0);
@@ -827,7 +840,7 @@ int navgpu_set_footprint(navgpu_fleet* f, uint32_t first, uint32_t count, const 
   uint8_t* fresh_prep = nullptr;
   uint32_t stride = f->pl.prep_stride;
   if (f->planner_configured) {
-    planWindow(f, np, fp_n, fp_spec, fp_radius);
+    planWindow(f, np, fp_n, fp_spec, fp_radius, f->env_vmax);
     int rc = allocPrep(f, np, &fresh_prep, &stride);
     if (rc != NAVGPU_OK) return rc;
   }
@@ -1100,19 +1113,19 @@ int navgpu_obstacle_update_costs(navgpu_fleet* f, uint32_t first, uint32_t count
 // the reach into the robot's box and a wavefront stops once that box is settled (k_bfs_rows, k_bfs_rows2, k_bfs_global); what it leaves open is
 // completed by ensureCompleteGrids before anybody else reads the grid.
 static const int kBoxMarginCells = 4;  // cell rounding of pose and points, the touched-obstacle ring, slack
-static double reachMetres(const navgpu_dwa_config& c, const float vel[3], const float* sample) {
+static double reachMetres(const navgpu_dwa_config& c, const RobotLimits& lim, const float vel[3], const float* sample) {
   auto axis = [&](double lo, double hi, int a) {
     double b = std::max(std::max(fabs(lo), fabs(hi)), fabs((double)vel[a]));
     if (sample) b = std::max(fabs((double)sample[a]), fabs((double)vel[a]));
     return b;
   };
-  const double bx = axis(c.min_vel_x, c.max_vel_x, 0), by = axis(c.min_vel_y, c.max_vel_y, 1);
+  const double bx = axis(lim.min_vel_x, lim.max_vel_x, 0), by = axis(lim.min_vel_y, lim.max_vel_y, 1);
   return hypot(bx, by) * c.sim_time * 1.001 + fabs(c.forward_point_distance);
 }
-static uint32_t bfsReachCells(const navgpu_fleet* f, const navgpu_robot_state& s, double goal_x, double goal_y) {
+static uint32_t bfsReachCells(const navgpu_fleet* f, uint32_t i, const navgpu_robot_state& s, double goal_x, double goal_y) {
   if (!f->bounded_grids) return 0;  // (every wavefront kernel can stop at the robot's box)
   if (f->pl.mg_generic) return 0;  // (a sideways-shifted look-up leaves the box the reach is derived for: whole grids)
-  const double reach = reachMetres(f->pl.cfg, s.vel, nullptr);
+  const double reach = reachMetres(f->pl.cfg, f->h_limits[i], s.vel, nullptr);  // (robot i's own limits, as the k_samples behind this stage reads them)
   const double cells = ceil(reach / f->pl.res) + kBoxMarginCells;
   if (!(cells < 32768.0)) return 0;
   // close to the goal the stop-and-rotate controller may take over and keep checking trajectories against these
@@ -1160,10 +1173,39 @@ extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, uint32_t first, ui
   return checkLaunch();
 }
 
+// Per-robot limits: the records of the set's robots that navgpu_planner_set_limits changed travel to pl.limits as kernel arguments
+// (k_set_limits), in stream order - behind a cycle that is still queued, in front of the launches of the call that flushes.  Every
+// call that stages a robot or probes it flushes that robot first, so the reach it works out from h_limits and the kernels behind
+// it see the same record.
+static int flushLimits(navgpu_fleet* f, const RobotSet& r) {
+  if (!f->n_limits_dirty) return NAVGPU_OK;
+  LimitsChunk ch;
+  ch.limits = f->pl.limits;
+  ch.count = ch.pad = 0;
+  for (uint32_t k = 0; k < r.count && f->n_limits_dirty; ++k) {
+    const uint32_t i = r[k];
+    if (!f->limits_dirty[i]) continue;
+    f->limits_dirty[i] = 0;
+    --f->n_limits_dirty;
+    ch.inst[ch.count] = i;
+    ch.rec[ch.count++] = f->h_limits[i];
+    if (ch.count == kLimitsChunk) {
+      launch_set_limits(ch, f->stream);  // (a robot is dirty only behind navgpu_planner_set_limits, which needs the launcher)
+      ch.count = 0;
+    }
+  }
+  if (ch.count) launch_set_limits(ch, f->stream);
+  return checkLaunch();
+}
+
 // the staged reach depends on the configuration: a reconfigure (or the switch below) between stage and cycle re-derives it
 static int restageReach(navgpu_fleet* f) {
   if (!f->planner_staged) return NAVGPU_OK;
   PlannerDev& pl = f->pl;
+  {  // the reach below follows h_limits: so must the device
+    int rc = flushLimits(f, RobotSet{0, f->desc.n_instances, nullptr});
+    if (rc != NAVGPU_OK) return rc;
+  }
   HIP_TRY(waitStream(f->stream));
   const uint32_t n = f->desc.n_instances;
   for (uint32_t i = 0; i < n; ++i) {
@@ -1173,7 +1215,7 @@ static int restageReach(navgpu_fleet* f) {
       continue;
     }
     const double* last = &f->hp_plan[((size_t)i * pl.max_plan + np - 1) * 2];
-    f->hp_reach[i] = bfsReachCells(f, f->hp_state[i], last[0], last[1]);
+    f->hp_reach[i] = bfsReachCells(f, i, f->hp_state[i], last[0], last[1]);
   }
   HIP_TRY(hipMemcpyAsync(pl.bfs_reach, f->hp_reach, sizeof(uint32_t) * n, hipMemcpyHostToDevice, f->stream));
   f->hp_dma_pending = true;
@@ -1248,6 +1290,11 @@ int navgpu_planner_wavefront_levels(navgpu_fleet* f, uint32_t first, uint32_t co
   return NAVGPU_OK;
 }
 
+// discretize_by_time = 0: the most steps a sample of a robot with these limits can take (simple_trajectory_generator.cpp:202-212)
+static double limitsSteps(const navgpu_dwa_config& cfg, const RobotLimits& lim) {
+  return ceil(std::max(limitsVmax(lim) * cfg.sim_time / cfg.sim_granularity, fabs(lim.max_rot_vel) * cfg.sim_time / cfg.angular_sim_granularity)) + 1;
+}
+
 int navgpu_planner_configure(navgpu_fleet* f, const navgpu_dwa_config* c) {
   if (!f || !c) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
@@ -1265,9 +1312,7 @@ int navgpu_planner_configure(navgpu_fleet* f, const navgpu_dwa_config* c) {
   if (cfg.discretize_by_time)
     steps = ceil(cfg.sim_time / cfg.sim_granularity);
   else {
-    double vmax = cfg.max_trans_vel >= 0 ? cfg.max_trans_vel + 1e-4
-                                         : hypot(std::max(fabs(cfg.min_vel_x), fabs(cfg.max_vel_x)), std::max(fabs(cfg.min_vel_y), fabs(cfg.max_vel_y)));
-    steps = ceil(std::max(vmax * cfg.sim_time / cfg.sim_granularity, fabs(cfg.max_rot_vel) * cfg.sim_time / cfg.angular_sim_granularity)) + 1;
+    steps = limitsSteps(cfg, limitsOf(cfg));
   }
   if (steps > pl.max_sim_steps) {
     g_last_error = "max_sim_steps too small for this sim_time / granularity";
@@ -1317,10 +1362,20 @@ int navgpu_planner_configure(navgpu_fleet* f, const navgpu_dwa_config* c) {
     if (!rc && f->desc.keep_sample_costs) rc = f->alloc(&n_sample_status, (size_t)nI * max_samples);
   }
   if (!rc) {
-    planWindow(f, np, f->h_fp_n, f->h_fp_spec, f->fp_radius);
+    planWindow(f, np, f->h_fp_n, f->h_fp_spec, f->fp_radius, limitsVmax(limitsOf(cfg)));
     rc = allocPrep(f, np, &n_prep, &n_stride);
   }
   if (!rc && waitStream(f->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;  // (also the allocations' memsets; kernels queued before took their PlannerDev by value)
+  // Every robot's record takes the configuration's limits (a caller who slowed one robot sets that robot's again).  The stream is
+  // drained: nothing reads the table while the copy runs.  Should it fail, every robot is dirty: the next call that stages a robot
+  // writes its record - the previous one, still in h_limits - again.
+  const std::vector<RobotLimits> n_limits(nI, limitsOf(cfg));
+  if (!rc && (hipMemcpyAsync(pl.limits, n_limits.data(), sizeof(RobotLimits) * nI, hipMemcpyHostToDevice, f->stream) != hipSuccess || waitStream(f->stream) != hipSuccess)) {
+    g_last_error = "navgpu_planner_configure: upload of the limits table failed";
+    std::fill(f->limits_dirty.begin(), f->limits_dirty.end(), (uint8_t)1);
+    f->n_limits_dirty = nI;
+    rc = NAVGPU_ERR_HIP;
+  }
   if (rc) {
     dropNew();
     return rc;
@@ -1345,11 +1400,100 @@ int navgpu_planner_configure(navgpu_fleet* f, const navgpu_dwa_config* c) {
   }
   pl = np;
   f->planner_configured = true;
+  f->h_limits = n_limits;
+  std::fill(f->limits_dirty.begin(), f->limits_dirty.end(), (uint8_t)0);
+  f->n_limits_dirty = 0;
+  f->env_vmax = limitsVmax(n_limits[0]);  // the window is this configuration's: the envelope starts again
   f->touchInputs(0, nI);  // allow_unknown decides which cells a wavefront may enter
   // new limits, new boxes: the staged reach follows from the configuration (a failure here leaves a complete, consistent new
   // configuration whose boxes are the old ones: searches that are larger or smaller than they need be, never wrong)
   if ((rc = restageReach(f)) != NAVGPU_OK) return rc;
   HIP_TRY(waitStream(f->stream));
+  return NAVGPU_OK;
+}
+
+// Per-robot limits.  The records are checked, the envelope (window / image, step capacity) is raised on the side if it has to be, and
+// only then do the host records change; the device table follows with each robot's next stage or probe call (flushLimits).
+int navgpu_planner_set_limits(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_limits* limits) {
+  if (!f || !limits || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  static_assert(offsetof(navgpu_robot_limits, acc_lim_theta) == offsetof(RobotLimits, acc_lim_theta) && offsetof(navgpu_robot_limits, prune_plan) == 15 * sizeof(double),
+                "eleven planner limits, four of the control cycle, then the switch");
+  for (uint32_t k = 0; k < count; ++k) {
+    const double* d = reinterpret_cast<const double*>(&limits[k]);
+    for (int q = 0; q < 15; ++q)
+      if (!std::isfinite(d[q])) return NAVGPU_ERR_INVALID;
+  }
+  FleetGuard guard_(f);
+  if (!f->planner_configured || !launch_set_limits) return NAVGPU_ERR_STATE;
+  PlannerDev& pl = f->pl;
+  double vmax = f->env_vmax;
+  for (uint32_t k = 0; k < count; ++k) {
+    RobotLimits l;
+    memcpy(&l, &limits[k], sizeof(l));
+    vmax = std::max(vmax, limitsVmax(l));
+    if (!pl.cfg.discretize_by_time && limitsSteps(pl.cfg, l) > pl.max_sim_steps) {
+      g_last_error = "max_sim_steps too small for the limits of instance " + std::to_string(first + k);
+      return NAVGPU_ERR_CAPACITY;
+    }
+  }
+  if (vmax > f->env_vmax) {  // beyond what the window was planned for: re-plan it as navgpu_planner_configure does, all-or-nothing
+    PlannerDev np = pl;
+    uint8_t* n_prep = nullptr;
+    uint32_t n_stride = pl.prep_stride;
+    planWindow(f, np, f->h_fp_n, f->h_fp_spec, f->fp_radius, vmax);
+    int rc = allocPrep(f, np, &n_prep, &n_stride);
+    if (rc != NAVGPU_OK) return rc;
+    if (waitStream(f->stream) != hipSuccess) {  // (queued kernels took their PlannerDev by value: drain before the image they use goes)
+      f->release(n_prep);
+      g_last_error = "navgpu_planner_set_limits: the stream did not drain";
+      return NAVGPU_ERR_HIP;
+    }
+    if (n_prep) {
+      f->release(pl.prep);
+      np.prep = n_prep;
+      np.prep_stride = n_stride;
+    }
+    pl = np;
+    f->env_vmax = vmax;
+  }
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t i = first + k;
+    const navgpu_robot_limits& r = limits[k];
+    memcpy(&f->h_limits[i], &r, sizeof(RobotLimits));
+    if (!f->limits_dirty[i]) {
+      f->limits_dirty[i] = 1;
+      ++f->n_limits_dirty;
+    }
+    navgpu_local_limits& c = f->lp_lim[i];  // the control cycle's half; sim_period and the latch switch stay the fleet's
+    c.xy_goal_tolerance = r.xy_goal_tolerance;
+    c.yaw_goal_tolerance = r.yaw_goal_tolerance;
+    c.trans_stopped_vel = r.trans_stopped_vel;
+    c.rot_stopped_vel = r.rot_stopped_vel;
+    c.max_rot_vel = r.max_rot_vel;
+    c.min_rot_vel = r.min_rot_vel;
+    c.acc_lim_x = r.acc_lim_x;
+    c.acc_lim_y = r.acc_lim_y;
+    c.acc_lim_theta = r.acc_lim_theta;
+    c.prune_plan = r.prune_plan;
+  }
+  return NAVGPU_OK;
+}
+
+int navgpu_planner_get_limits(navgpu_fleet* f, uint32_t first, uint32_t count, navgpu_robot_limits* limits) {
+  if (!f || !limits || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  for (uint32_t k = 0; k < count; ++k) {
+    const uint32_t i = first + k;
+    navgpu_robot_limits& r = limits[k];
+    memcpy(&r, &f->h_limits[i], sizeof(RobotLimits));
+    const navgpu_local_limits& c = f->lp_lim[i];
+    r.xy_goal_tolerance = c.xy_goal_tolerance;
+    r.yaw_goal_tolerance = c.yaw_goal_tolerance;
+    r.trans_stopped_vel = c.trans_stopped_vel;
+    r.rot_stopped_vel = c.rot_stopped_vel;
+    r.prune_plan = c.prune_plan;
+    r.reserved = 0;
+  }
   return NAVGPU_OK;
 }
 
@@ -1384,7 +1528,7 @@ static void stageMirrors(navgpu_fleet* f, uint32_t i, const navgpu_robot_state& 
   f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
   f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
   f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
-  f->hp_reach[i] = bfsReachCells(f, s, gx, gy);
+  f->hp_reach[i] = bfsReachCells(f, i, s, gx, gy);
 }
 
 int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, const double* plan_xy,
@@ -1396,6 +1540,7 @@ int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const 
   int rc = checkStageStates(pl, count, states, n_plan_total);
   if (rc != NAVGPU_OK) return rc;
   HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));  // the pinned mirrors may still feed an earlier copy
+  if ((rc = flushLimits(f, RobotSet{first, count, nullptr})) != NAVGPU_OK) return rc;
   for (uint32_t li = 0; li < count; ++li) stageMirrors(f, first + li, states[li], plan_xy);
   f->touchInputs(first, count);
   if (first == 0 && count == f->desc.n_instances) {  // the whole fleet: one copy of the block
@@ -1453,6 +1598,7 @@ int navgpu_planner_stage_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t
   // the pinned mirrors may still feed an earlier copy, and so may the packed block (the marker of two cycles in flight is recorded
   // behind its copy as well)
   HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
+  if ((rc = flushLimits(f, RobotSet{0, n_robots, instances})) != NAVGPU_OK) return rc;
   StageRec* rec = reinterpret_cast<StageRec*>(f->cl.h_stage);
   double* poses = reinterpret_cast<double*>(f->cl.h_stage + sizeof(StageRec) * n_robots);
   uint32_t n_poses = 0;
@@ -1507,7 +1653,7 @@ static void poseMirrors(navgpu_fleet* f, uint32_t i, const float pos[3], const f
   f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
   f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
   f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
-  f->hp_reach[i] = bfsReachCells(f, s, gx, gy);
+  f->hp_reach[i] = bfsReachCells(f, i, s, gx, gy);
 }
 extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth) {
   if (!f->planner_configured) return NAVGPU_ERR_STATE;
@@ -1520,6 +1666,10 @@ extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, 
   if (f->hp_dma_pending) {  // the host mirrors written below may still feed a full stage's copies
     HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
     f->hp_dma_pending = false;
+  }
+  {
+    int rc = flushLimits(f, RobotSet{first, count, nullptr});
+    if (rc != NAVGPU_OK) return rc;
   }
   for (uint32_t li = 0; li < count; ++li) poseMirrors(f, first + li, pos_xyth + 3 * (size_t)li, vel_xyth + 3 * (size_t)li);
   f->touchInputs(first, count);
@@ -1559,6 +1709,10 @@ extern "C++" int navgpu::stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_r
   if (f->hp_dma_pending) {  // the host mirrors written below may still feed a full stage's copies
     HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
     f->hp_dma_pending = false;
+  }
+  {
+    int rc = flushLimits(f, RobotSet{0, n_robots, instances});
+    if (rc != NAVGPU_OK) return rc;
   }
   PoseChunkList ch;
   ch.state = pl.state;
@@ -1817,9 +1971,13 @@ int navgpu_planner_check_trajectory(navgpu_fleet* f, uint32_t instance, const fl
   FleetGuard guard_(f);
   if (!f->planner_configured || !f->planner_staged) return NAVGPU_ERR_STATE;
   PlannerDev& pl = f->pl;
+  {
+    int rc = flushLimits(f, RobotSet{instance, 1, nullptr});
+    if (rc != NAVGPU_OK) return rc;
+  }
   if (f->grid_partial[instance]) {  // the sample must stay inside the box the last wavefronts settled
     const navgpu_robot_state& st = f->hp_state[instance];
-    const uint32_t need = (uint32_t)std::min(ceil(reachMetres(pl.cfg, st.vel, vs) / pl.res) + 3.0, 32768.0);
+    const uint32_t need = (uint32_t)std::min(ceil(reachMetres(pl.cfg, f->h_limits[instance], st.vel, vs) / pl.res) + 3.0, 32768.0);
     int32_t nb[4];
     const int32_t* hb = &f->h_box[(size_t)4 * instance];
     // (a sideways-shifted look-up - navgpu_planner_set_map_grid_options after the cycle - leaves the box reachMetres
@@ -1859,6 +2017,10 @@ int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const 
   if (!f->planner_configured || !f->planner_staged || !launch_check_traj) return NAVGPU_ERR_STATE;
   if (!total) return NAVGPU_OK;  // no robot has a probe: nobody's flags are reset
   PlannerDev& pl = f->pl;
+  {
+    int rc = flushLimits(f, RobotSet{0, n_robots, instances});
+    if (rc != NAVGPU_OK) return rc;
+  }
   navgpu_fleet::Probes& pb = f->pb;
   const size_t head = 2 * (size_t)n_robots + 1;  // words in front of the samples
   if (total > pb.cap) {  // all four buffers or none; the ones they replace are idle (every call drains the stream)
@@ -1890,7 +2052,7 @@ int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const 
       if (!f->grid_partial[i] || probe_offsets[q + 1] == probe_offsets[q]) return false;
       const navgpu_robot_state& st = f->hp_state[i];
       double reach = 0.0;
-      for (uint32_t p = probe_offsets[q]; p < probe_offsets[q + 1]; ++p) reach = std::max(reach, reachMetres(pl.cfg, st.vel, vel_samples + 3 * (size_t)p));
+      for (uint32_t p = probe_offsets[q]; p < probe_offsets[q + 1]; ++p) reach = std::max(reach, reachMetres(pl.cfg, f->h_limits[i], st.vel, vel_samples + 3 * (size_t)p));
       const uint32_t need = (uint32_t)std::min(ceil(reach / pl.res) + 3.0, 32768.0);
       int32_t nb[4];
       const int32_t* hb = &f->h_box[(size_t)4 * i];

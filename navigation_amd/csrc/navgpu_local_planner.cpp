@@ -77,6 +77,7 @@ int navgpu_local_planner_configure(navgpu_fleet* f, const navgpu_local_limits* l
   if (!f || !lim) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   f->lp_limits = *lim;
+  f->lp_lim.assign(f->desc.n_instances, *lim);  // every robot's record; navgpu_planner_set_limits changes one robot's
   f->lp_configured = true;
   if (f->lp.size() != f->desc.n_instances) f->lp.assign(f->desc.n_instances, navgpu_fleet::LocalPlannerState());
   return NAVGPU_OK;
@@ -137,8 +138,8 @@ int navgpu_local_planner_is_goal_reached(navgpu_fleet* f, uint32_t first, uint32
   if (!f || !in || !reached || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   if (!f->lp_configured) return NAVGPU_ERR_STATE;
-  const navgpu_local_limits& lim = f->lp_limits;
   for (uint32_t k = 0; k < count; ++k) {
+    const navgpu_local_limits& lim = f->lp_lim[first + k];
     navgpu_fleet::LocalPlannerState& st = f->lp[first + k];
     reached[k] = 0;
     double goal[3];
@@ -159,7 +160,6 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
   if (!f || !in || !out || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   if (!f->lp_configured || !f->planner_configured) return NAVGPU_ERR_STATE;
-  const navgpu_local_limits& lim = f->lp_limits;
   const uint32_t max_plan = f->pl.max_plan;
   const double dist_threshold = std::max(f->cm.nx * f->cm.res / 2.0, f->cm.ny * f->cm.res / 2.0);
   std::vector<double> local((size_t)count * max_plan * 3), packed;
@@ -170,7 +170,7 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
   bool any_resident = false;
   for (uint32_t k = 0; k < count; ++k) any_resident = any_resident || f->rp.residentAt(first + k);
   if (any_resident) {
-    int rc = f->rp.window_pass(f, first, count, in, dist_threshold, lim.prune_plan);
+    int rc = f->rp.window_pass(f, first, count, in, dist_threshold);
     if (rc != NAVGPU_OK) return rc;
     // The mirrors follow the device at once, for EVERY robot whose window the kernel emitted - also those behind a robot whose window
     // does not fit (the call then returns before it looks at them): they say what navgpu_planner_stage_poses and restageReach read
@@ -225,7 +225,7 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
     if (!st.have_plan || st.plan.empty()) continue;    // transformGlobalPlan: "Received plan with zero length"
     uint32_t n_loc = 0, n_er = 0;
     int rc = navgpu_local_plan_window(st.plan.data(), (uint32_t)(st.plan.size() / 3), in[k].pose, st.has_T ? st.T : nullptr,
-                                      dist_threshold, lim.prune_plan, &local[(size_t)k * max_plan * 3], max_plan, &n_loc, &n_er);
+                                      dist_threshold, f->lp_lim[first + k].prune_plan, &local[(size_t)k * max_plan * 3], max_plan, &n_loc, &n_er);
     if (rc == NAVGPU_ERR_CAPACITY) {
       st.window.status = NAVGPU_LOCAL_WINDOW_CAPACITY;
       return rc;
@@ -304,6 +304,7 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
   };
   for (uint32_t k = 0; k < count; ++k) {
     if (!valid[k]) continue;
+    const navgpu_local_limits& lim = f->lp_lim[first + k];  // the robot's own LocalPlannerLimits
     navgpu_fleet::LocalPlannerState& st = f->lp[first + k];
     double goal[3];
     bool reached = false;

@@ -51,7 +51,7 @@ void toGlobal(const Robot& R, const navgpu_global_pose& p, double out[3]) {  // 
   }
 }
 
-int windowPass(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_input* in, double dist_threshold, int32_t prune) {
+int windowPass(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_input* in, double dist_threshold) {
   navgpu_fleet::ResidentPlans& rp = f->rp;
   bool any = false;
   for (uint32_t k = 0; k < count; ++k) {
@@ -60,7 +60,7 @@ int windowPass(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_rob
     a = PlanWindowIn{};
     if (!R.resident || !in[k].have_pose || R.len == 0) continue;
     any = true;
-    a.flags = kPwActive | (prune ? kPwPrune : 0u);
+    a.flags = kPwActive | (f->lp_lim[first + k].prune_plan ? kPwPrune : 0u);  // LocalPlannerLimits::prune_plan of this robot
     a.pose[0] = in[k].pose[0];
     a.pose[1] = in[k].pose[1];
     a.robot[0] = in[k].pose[0];

@@ -79,15 +79,16 @@ __global__ __launch_bounds__(kSamplesThreads, 7) void k_samples(PlannerDev pl, R
     }
     // ---- velocity samples, one lane per axis: `next += step_size` is a sequential fp64 accumulation and must stay one
     const navgpu_robot_state st = pl.state[inst];
+    const RobotLimits& lim = pl.limits[inst];
     int32_t* cnt = pl.axis_count + 4 * inst;
     int n = 0;
     if (tid < 3) {
       const int a = tid;
       const float vsamp = a == 0 ? (float)c.vx_samples : (a == 1 ? (float)c.vy_samples : (float)c.vth_samples);
-      const double max_vel_th = c.max_rot_vel, min_vel_th = -1.0 * max_vel_th;
-      double lim_min = a == 0 ? c.min_vel_x : (a == 1 ? c.min_vel_y : min_vel_th);
-      double lim_max = a == 0 ? c.max_vel_x : (a == 1 ? c.max_vel_y : max_vel_th);
-      const float acc = a == 0 ? (float)c.acc_lim_x : (a == 1 ? (float)c.acc_lim_y : (float)c.acc_lim_theta);
+      const double max_vel_th = lim.max_rot_vel, min_vel_th = -1.0 * max_vel_th;
+      double lim_min = a == 0 ? lim.min_vel_x : (a == 1 ? lim.min_vel_y : min_vel_th);
+      double lim_max = a == 0 ? lim.max_vel_x : (a == 1 ? lim.max_vel_y : max_vel_th);
+      const float acc = a == 0 ? (float)lim.acc_lim_x : (a == 1 ? (float)lim.acc_lim_y : (float)lim.acc_lim_theta);
       const float v = st.vel[a];
       float maxv, minv;
       if (!c.use_dwa) {

@@ -72,6 +72,7 @@ __device__ __forceinline__ void addCritic(double& total, bool en, double value, 
 // behind a robot's image in pl.prep (k_score_prep_tab writes them, k_score_sweep reads them): kScoreAuxBytes of per-robot scalars
 // and one byte per (vx, vy) pair, at the END of the robot's slot
 constexpr uint32_t kScoreAuxBytes = 64;
+constexpr uint32_t kSweepAuxMinRot = 10;  // aux[10..11]: the robot's min_rot_vel as a double (aux[0..8]: storeSweepRobotScalars, storeFreeDistance)
 __host__ __device__ inline uint32_t score_prep_reject_bytes(const PlannerDev& pl) { return (pl.max_axis * pl.max_axis + 255u) & ~255u; }
 __host__ __device__ inline uint32_t score_prep_reject_offset(const PlannerDev& pl) { return pl.prep_stride - score_prep_reject_bytes(pl); }
 // a scoring launch with `lds` bytes of dynamic LDS, allowed for the kernel first when there are more than kAllowAbove
@@ -412,7 +413,17 @@ __device__ __forceinline__ void storeFreeDistance(const PlannerDev& pl, const Sc
     aux[8] = start_fail;
   }
 }
-__device__ __forceinline__ void storeSweepRobotScalars(const PlannerDev& pl, const ScoreRobot& r, const float (*s_axis)[kMaxAxis]) {
+// The three limits the sweep's scalars take from the robot's record.  Loaded where a workgroup begins, beside its other per-robot
+// loads, and handed down: read where they are used - at the very end of the image build, which is the tail of the wavefront launch
+// when it runs there (scorePrepFree) - the loads' latency would be that launch's.
+struct SweepLimits {
+  double min_trans_vel, max_trans_vel, min_rot_vel;
+};
+__device__ __forceinline__ SweepLimits sweepLimits(const PlannerDev& pl, uint32_t inst) {
+  const RobotLimits& l = pl.limits[inst];
+  return SweepLimits{l.min_trans_vel, l.max_trans_vel, l.min_rot_vel};
+}
+__device__ __forceinline__ void storeSweepRobotScalars(const PlannerDev& pl, const ScoreRobot& r, const float (*s_axis)[kMaxAxis], const SweepLimits& lim) {
   const uint32_t tid = threadIdx.x;
   const navgpu_dwa_config& c = pl.cfg;
   const Geom& g = r.g;
@@ -439,6 +450,7 @@ __device__ __forceinline__ void storeSweepRobotScalars(const PlannerDev& pl, con
     aux[4] = (int32_t)fwd_ny;
     aux[5] = need_margin ? 1 : 0;
     aux[6] = fwd_screen ? 1 : 0;
+    *reinterpret_cast<double*>(aux + kSweepAuxMinRot) = lim.min_rot_vel;  // the v_theta half of the reject tests, for the sweep's lanes
   }
   // generateTrajectory's reject tests (simple_trajectory_generator.cpp:193-200), the part that depends on (vx, vy) only:
   // bit 0: vmag + eps < min_trans_vel (rejects together with the v_theta half), bit 1: vmag - eps > max_trans_vel
@@ -447,13 +459,13 @@ __device__ __forceinline__ void storeSweepRobotScalars(const PlannerDev& pl, con
     const int ix = i / nyv, iy = i - ix * nyv;
     const double vmag = hyp2((double)s_axis[0][ix], (double)s_axis[1][iy]);
     const double eps = 1e-4;
-    rej[i] = (uint8_t)(((c.min_trans_vel >= 0 && vmag + eps < c.min_trans_vel) ? 1 : 0) | ((c.max_trans_vel >= 0 && vmag - eps > c.max_trans_vel) ? 2 : 0));
+    rej[i] = (uint8_t)(((lim.min_trans_vel >= 0 && vmag + eps < lim.min_trans_vel) ? 1 : 0) | ((lim.max_trans_vel >= 0 && vmag - eps > lim.max_trans_vel) ? 2 : 0));
   }
 }
 __device__ __forceinline__ void storeSweepScalars(const PlannerDev& pl, const ScoreRobot& r, const float (*s_axis)[kMaxAxis], int* s_cnt,
-                                                  const uint8_t* s_dyn) {
+                                                  const uint8_t* s_dyn, const SweepLimits& lim) {
   storeFreeDistance(pl, r, reinterpret_cast<const uint32_t*>(s_dyn + r.win_bytes), s_cnt);
-  storeSweepRobotScalars(pl, r, s_axis);
+  storeSweepRobotScalars(pl, r, s_axis, lim);
 }
 
 // ---- scorePrepFree: the part of k_score_prep_tab's image that reads neither the path nor the goal grid - the window bytes, the
@@ -465,6 +477,7 @@ __device__ __forceinline__ void storeSweepScalars(const PlannerDev& pl, const Sc
 __host__ __device__ inline size_t score_prep_free_tail_bytes() { return 2 * kMaxFootprint * sizeof(double) + 3 * kMaxAxis * sizeof(float) + 16; }
 __device__ __forceinline__ void scorePrepFree(const PlannerDev& pl, uint32_t inst, uint8_t* s_dyn) {
   ScoreRobot r = scoreRobot(pl, inst);
+  const SweepLimits lim = sweepLimits(pl, inst);
   uint32_t* s_ba = reinterpret_cast<uint32_t*>(s_dyn + r.win_bytes + score_bits_bytes(r.win) + pl.tab_bytes);
   double* s_fp = reinterpret_cast<double*>(reinterpret_cast<uint8_t*>(s_ba) + score_scratch_bytes(r.win));
   float(*s_axis)[kMaxAxis] = reinterpret_cast<float(*)[kMaxAxis]>(s_fp + 2 * kMaxFootprint);
@@ -476,7 +489,7 @@ __device__ __forceinline__ void scorePrepFree(const PlannerDev& pl, uint32_t ins
   buildTables(pl, r, s_fp, s_axis, s_dyn);
   __syncthreads();
   storeImage(pl, r, s_dyn);
-  storeSweepRobotScalars(pl, r, s_axis);
+  storeSweepRobotScalars(pl, r, s_axis, lim);
 }
 
 }  // namespace navgpu

@@ -77,6 +77,7 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
   static_assert(!PROBES || (EXPLICIT && !TERMS), "probes are explicit samples");
   const uint32_t tid = threadIdx.x;
   const navgpu_dwa_config& c = pl.cfg;
+  const RobotLimits& lim = pl.limits[r.inst];
   const Geom& g = r.g;
   const navgpu_robot_state& st = r.st;
   const uint8_t* master = r.master;
@@ -133,8 +134,8 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
     const double vmag = hyp2((double)vs[0], (double)vs[1]);
     const double eps = 1e-4;
     bool reject = false;
-    if ((c.min_trans_vel >= 0 && vmag + eps < c.min_trans_vel) && (c.min_rot_vel >= 0 && fabs((double)vs[2]) + eps < c.min_rot_vel)) reject = true;
-    if (c.max_trans_vel >= 0 && vmag - eps > c.max_trans_vel) reject = true;
+    if ((lim.min_trans_vel >= 0 && vmag + eps < lim.min_trans_vel) && (lim.min_rot_vel >= 0 && fabs((double)vs[2]) + eps < lim.min_rot_vel)) reject = true;
+    if (lim.max_trans_vel >= 0 && vmag - eps > lim.max_trans_vel) reject = true;
     int num_steps = 0;
     if (!reject) {
       double ns;
@@ -161,7 +162,7 @@ __device__ __forceinline__ void scoreSamples(const PlannerDev& pl, const ScoreRo
       const bool continued = !c.use_dwa;
       float px = st.pos[0], py = st.pos[1], pth = st.pos[2];
       float lv[3] = {vs[0], vs[1], vs[2]};
-      const float acc[3] = {(float)c.acc_lim_x, (float)c.acc_lim_y, (float)c.acc_lim_theta};
+      const float acc[3] = {(float)lim.acc_lim_x, (float)lim.acc_lim_y, (float)lim.acc_lim_theta};
       auto newVel = [&](const float* vel_in, float* out) {  // computeNewVelocities (:265-276)
         for (int i = 0; i < 3; ++i) {
           if (vel_in[i] < vs[i])
@@ -581,6 +582,7 @@ __global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev
 #endif
   PREP_STAMP(0);
   ScoreRobot r = scoreRobot(pl, robots(blockIdx.y));
+  const SweepLimits lim = sweepLimits(pl, r.inst);
   stageInputs<false>(pl, r, s_fp, s_axis, s_cnt, s_dyn);
   __syncthreads();
   PREP_STAMP(1);
@@ -591,7 +593,7 @@ __global__ __launch_bounds__(kScorePrepThreads) void k_score_prep_tab(PlannerDev
   PREP_STAMP(3);
   storeImage(pl, r, s_dyn);
   PREP_STAMP(4);
-  storeSweepScalars(pl, r, s_axis, s_cnt, s_dyn);
+  storeSweepScalars(pl, r, s_axis, s_cnt, s_dyn, lim);
 #ifdef NAVGPU_PREP_TIMING
   PREP_STAMP(5);
   if (threadIdx.x == 0 && (blockIdx.y & 15u) == 3u) {

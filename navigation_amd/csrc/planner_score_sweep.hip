@@ -125,6 +125,7 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   const uint32_t fwd_lo = (uint32_t)aux[2], fwd_nx = (uint32_t)aux[3], fwd_ny = (uint32_t)aux[4];
   const bool need_margin = aux[5] != 0, fwd_screen = aux[6] != 0;
   const int free_cells = aux[7];  // Euclidean distance (rounded down) from the robot's cell to the nearest cell with a screen set that still counts after step 0 (or the window's edge)
+  const double min_rot_vel = *reinterpret_cast<const double*>(aux + kSweepAuxMinRot);  // the robot's own (navgpu_planner_set_limits), with the image's scalars
   const int start_fail = aux[8];  // 4 / 5: the path / goal critic fails at the robot's own cell, i.e. for every sample at step 0; 0: neither
   const uint32_t osc = pl.osc_flags[inst];
   const int32_t align_on = pl.align_on[inst];
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(kSweepThreads, kSweepWaves) void k_score_sweep(Plan
   const float vs0 = axis[min((uint32_t)s_ix, amax)], vs1 = axis[pl.max_axis + min((uint32_t)s_iy, amax)], vs2 = axis[2u * pl.max_axis + min((uint32_t)t_ith, amax)];
   const uint32_t rej_xy = rej_bytes[in_range ? t_r : 0];  // the (vx, vy) pair's half of the reject tests (k_score_prep_tab)
   // generateTrajectory: reject tests (:193-200); the step count is the tables' (ceil(sim_time / sim_granularity), host)
-  auto rejected = [&]() { return !in_range || ((rej_xy & 1u) && (c.min_rot_vel >= 0 && fabs((double)vs2) + 1e-4 < c.min_rot_vel)) || (rej_xy & 2u) || K <= 0; };  // `return num_steps > 0` (:250)
+  auto rejected = [&]() { return !in_range || ((rej_xy & 1u) && (min_rot_vel >= 0 && fabs((double)vs2) + 1e-4 < min_rot_vel)) || (rej_xy & 2u) || K <= 0; };  // `return num_steps > 0` (:250)
   if constexpr (!KEEP) {
     // ---- the robot-level exit: the path / goal critic fails at the robot's own cell, which is point 0 of every trajectory, and both
     // stop at a failing point wherever it lies (map_grid_cost_function.cpp:106-112) - every accepted sample's total is negative

@@ -1,5 +1,5 @@
 // k_select (first-strict-minimum selection, winner trajectory, oscillation flag update), k_cell_costs, k_stage_poses,
-// k_stage_scatter, k_sincos (gfx950).
+// k_set_limits, k_stage_scatter, k_sincos (gfx950).
 #include "planner_common.h"
 
 namespace navgpu {
@@ -39,6 +39,7 @@ __global__ __launch_bounds__(64) void k_select(PlannerDev pl, Robots robots, uin
   const uint32_t inst = robots(blockIdx.x);
   const uint32_t tid = threadIdx.x;
   const navgpu_dwa_config& c = pl.cfg;
+  const RobotLimits& lim = pl.limits[inst];
   double bc = 1.0e300;
   int bi = 0x7FFFFFFF;
   for (uint32_t k = tid; k < n_blocks; k += 64) {
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(64) void k_select(PlannerDev pl, Robots robots, uin
     if (sel_steps > (int)pl.max_sim_steps) sel_steps = (int)pl.max_sim_steps;
     sel_dt = c.sim_time / sel_steps;
     const bool continued = !c.use_dwa;
-    const float acc[3] = {(float)c.acc_lim_x, (float)c.acc_lim_y, (float)c.acc_lim_theta};
+    const float acc[3] = {(float)lim.acc_lim_x, (float)lim.acc_lim_y, (float)lim.acc_lim_theta};
     auto newVel = [&](const float* vel_in, float* out) {
       for (int i = 0; i < 3; ++i) {
         if (vel_in[i] < sel_vs[i])
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(64) void k_select(PlannerDev pl, Robots robots, uin
       }
     } else {  // (more steps than the shared tables hold: the plain sequential form)
       const bool continued = !c.use_dwa;
-      const float acc[3] = {(float)c.acc_lim_x, (float)c.acc_lim_y, (float)c.acc_lim_theta};
+      const float acc[3] = {(float)lim.acc_lim_x, (float)lim.acc_lim_y, (float)lim.acc_lim_theta};
       float lv[3] = {sel_lv0[0], sel_lv0[1], sel_lv0[2]};
       auto newVel = [&](const float* vel_in, float* out) {
         for (int i = 0; i < 3; ++i) {
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(64) void k_select(PlannerDev pl, Robots robots, uin
       set(NAVGPU_OSC_FORWARD_NEG, false);
       set(NAVGPU_OSC_FORWARD_POS, true);
     }
-    if (fabs(xv) <= c.min_trans_vel) {
+    if (fabs(xv) <= lim.min_trans_vel) {
       if (yv < 0) {
         if (has(NAVGPU_OSC_STRAFING_POS)) {
           set(NAVGPU_OSC_STRAFE_NEG_ONLY, true);
@@ -319,6 +320,17 @@ __global__ __launch_bounds__(64) void k_stage_poses(Chunk c) {
 }
 void launch_stage_poses(const PoseChunk& c, hipStream_t s) { hipLaunchKernelGGL(k_stage_poses<PoseChunk>, dim3(1), dim3(64), 0, s, c); }
 void launch_stage_poses_list(const PoseChunkList& c, hipStream_t s) { hipLaunchKernelGGL(k_stage_poses<PoseChunkList>, dim3(1), dim3(64), 0, s, c); }
+
+// ------------------------------------------------------------------------------------------------
+// k_set_limits (navgpu_planner_set_limits): the records a stage call carries up for robots whose limits changed, as kernel
+// arguments like the poses - in stream order behind the cycle before, in front of this cycle's k_samples.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_set_limits(LimitsChunk c) {
+  const uint32_t li = threadIdx.x;
+  if (li >= c.count) return;
+  c.limits[c.inst[li]] = c.rec[li];
+}
+void launch_set_limits(const LimitsChunk& c, hipStream_t s) { hipLaunchKernelGGL(k_set_limits, dim3(1), dim3(64), 0, s, c); }
 
 // ------------------------------------------------------------------------------------------------
 // k_stage_scatter (navgpu_planner_stage_list): what navgpu_planner_stage copies into the slots of a contiguous range, for

@@ -154,7 +154,8 @@ __global__ __launch_bounds__(kTrajEmitThreads) void k_traj_emit(PlannerDev pl, T
     const int num_steps = my_n;
     const double dt = c.sim_time / num_steps;
     const bool continued = !c.use_dwa;
-    const float acc[3] = {(float)c.acc_lim_x, (float)c.acc_lim_y, (float)c.acc_lim_theta};
+    const RobotLimits& lim = pl.limits[inst];
+    const float acc[3] = {(float)lim.acc_lim_x, (float)lim.acc_lim_y, (float)lim.acc_lim_theta};
     auto newVel = [&](const float* vel_in, float* out) {  // computeNewVelocities (:265-276)
       for (int i = 0; i < 3; ++i) {
         if (vel_in[i] < vs[i])

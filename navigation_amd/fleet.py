@@ -5,6 +5,8 @@ Method names follow the reference interfaces they front:
   add_static_map        StaticLayer::incomingMap             (plugins/static_layer.cpp:167-228)
   set_footprint         LayeredCostmap::setFootprint         (layered_costmap.cpp:164-174)
   set_plan              DWAPlanner::setPlan                  (dwa_local_planner/src/dwa_planner.cpp:204-207)
+  set_limits / limits   LocalPlannerUtil::reconfigureCB / getCurrentLimits per robot (base_local_planner/src/local_planner_util.cpp:59-80),
+                        MoveSlowAndClear::setRobotSpeed for one robot of a fleet (move_slow_and_clear.cpp:188-214)
   find_best_path        DWAPlanner::updatePlanAndLocalCosts + findBestPath (dwa_planner.cpp:240-371)
   check_trajectory      DWAPlanner::checkTrajectory          (dwa_planner.cpp:213-237)
   check_trajectories    a loop of checkTrajectory calls over robots and velocity probes, one launch
@@ -378,6 +380,51 @@ class Fleet:
     def configure_planner(self, cfg):
         self.cfg = cfg
         check(self.L.navgpu_planner_configure(self.h, C.byref(cfg)), "planner_configure")
+
+    @staticmethod
+    def _limit_records(limits):
+        """A list of dicts, a structured array or a (RobotLimits * n) array as a ctypes array; raises before any library call when a
+        record misses a field, names an unknown one or holds something that is no number."""
+        if isinstance(limits, C.Array) and getattr(limits, "_type_", None) is N.RobotLimits:
+            return limits
+        names = N.RobotLimits.FIELDS
+        if isinstance(limits, np.ndarray):
+            if limits.dtype.names is None:
+                raise ValueError("set_limits: an array of limits must be a structured array with the fields of navgpu_robot_limits")
+            rows = [{n: r[n] for n in limits.dtype.names} for r in np.atleast_1d(limits)]
+        elif isinstance(limits, dict):
+            rows = [limits]
+        else:
+            rows = list(limits)
+        if not rows:
+            raise ValueError("set_limits: no record")
+        out = (N.RobotLimits * len(rows))()
+        for k, r in enumerate(rows):
+            if not isinstance(r, dict):
+                raise ValueError(f"set_limits: record {k} is not a dict")
+            missing, unknown = [n for n in names if n not in r], [n for n in r if n not in names and n != "reserved"]
+            if missing or unknown:
+                raise ValueError(f"set_limits: record {k}: missing fields {missing}, unknown fields {unknown}")
+            for n in names:
+                v = r[n]
+                if isinstance(v, (bool, np.bool_)) and n != "prune_plan" or not isinstance(v, (int, float, bool, np.integer, np.floating, np.bool_)):
+                    raise ValueError(f"set_limits: record {k}: {n} = {v!r} is not a number")
+                setattr(out[k], n, int(v) if n == "prune_plan" else float(v))
+        return out
+
+    def set_limits(self, limits, first=0):
+        """LocalPlannerUtil::reconfigureCB / MoveSlowAndClear::setRobotSpeed for the robots first, first + 1, ...: one record of
+        LocalPlannerLimits each (a list of dicts, or a structured array, with the fields of navgpu_robot_limits).  The robots'
+        next staged cycle or probe runs on them; the others stay as they were."""
+        rec = self._limit_records(limits)
+        check(self.L.navgpu_planner_set_limits(self.h, first, len(rec), C.cast(rec, C.c_void_p)), "planner_set_limits")
+
+    def limits(self, first=0, count=None):
+        """LocalPlannerUtil::getCurrentLimits per robot: a list of dicts with the fields of navgpu_robot_limits."""
+        first, count = self._range(first, count)
+        rec = (N.RobotLimits * count)()
+        check(self.L.navgpu_planner_get_limits(self.h, first, count, C.cast(rec, C.c_void_p)), "planner_get_limits")
+        return [r.as_dict() for r in rec]
 
     def set_plan(self, first=0, count=None):
         first, count = self._range(first, count)

@@ -3,6 +3,8 @@
 #include "navgpu_dwa_planner_ros.h"
 
 #include <base_local_planner/goal_functions.h>
+#include <cstddef>
+#include <cstring>
 #include <pluginlib/class_list_macros.h>
 
 PLUGINLIB_EXPORT_CLASS(navgpu::DWAPlannerROS, nav_core::BaseLocalPlanner)  // dwa_planner_ros.cpp:50
@@ -10,7 +12,7 @@ PLUGINLIB_EXPORT_CLASS(navgpu::DWAPlannerROS, nav_core::BaseLocalPlanner)  // dw
 namespace navgpu {
 
 DWAPlannerROS::DWAPlannerROS() : tf_(NULL), costmap_ros_(NULL), odom_helper_("odom"), dsrv_(NULL), setup_(false),
-                                 initialized_(false), publish_traj_pc_(false), fleet_(NULL), sim_period_(0.05) {}
+                                 initialized_(false), publish_traj_pc_(false), fleet_(NULL), configured_(false), sim_period_(0.05) {}
 DWAPlannerROS::~DWAPlannerROS() {
   delete dsrv_;
   if (fleet_) navgpu_fleet_destroy(fleet_);
@@ -90,7 +92,7 @@ void DWAPlannerROS::reconfigureCB(dwa_local_planner::DWAPlannerConfig& config, u
   limits.rot_stopped_vel = config.rot_stopped_vel;
   planner_util_.reconfigureCB(limits, config.restore_defaults);
 
-  navgpu_dwa_config& c = cfg_;  // DWAPlanner::reconfigure (dwa_planner.cpp:52-116)
+  navgpu_dwa_config c = navgpu_dwa_config();  // DWAPlanner::reconfigure (dwa_planner.cpp:52-116); every field is set below
   c.max_trans_vel = config.max_trans_vel;  c.min_trans_vel = config.min_trans_vel;
   c.max_vel_x = config.max_vel_x;          c.min_vel_x = config.min_vel_x;
   c.max_vel_y = config.max_vel_y;          c.min_vel_y = config.min_vel_y;
@@ -112,7 +114,35 @@ void DWAPlannerROS::reconfigureCB(dwa_local_planner::DWAPlannerConfig& config, u
   int rollout_trig = 0;
   nh.param("navgpu_rollout_trig", rollout_trig, 0);       // 0: cos(pos[2]) is ::cos(double) in the reference build being replaced, 1: the float overload
   c.sum_scores = sum_scores;  c.cheat_factor = cheat;  c.allow_unknown = allow_unknown;  c.rollout_trig = rollout_trig;
-  if (navgpu_planner_configure(fleet_, &c) != NAVGPU_OK) ROS_ERROR("navgpu_planner_configure: %s", navgpu_last_error());
+  // Only LocalPlannerLimits fields changed - MoveSlowAndClear::setRobotSpeed (move_slow_and_clear.cpp:188-214), a speed slider: the
+  // robot's limits record alone, without the drain and the reallocation of a full reconfigure.  The limits lead navgpu_dwa_config
+  // (max_trans_vel ... acc_lim_theta); everything behind them is compared as bytes (both structs are filled field by field from
+  // zeroed storage, no padding in between).
+  const size_t limits_bytes = offsetof(navgpu_dwa_config, sim_time);
+  const bool limits_only = configured_ && memcmp(reinterpret_cast<const char*>(&c) + limits_bytes, reinterpret_cast<const char*>(&cfg_) + limits_bytes,
+                                                 sizeof(c) - limits_bytes) == 0;
+  if (limits_only) {
+    navgpu_robot_limits r = {};
+    r.max_trans_vel = c.max_trans_vel;  r.min_trans_vel = c.min_trans_vel;
+    r.max_vel_x = c.max_vel_x;          r.min_vel_x = c.min_vel_x;
+    r.max_vel_y = c.max_vel_y;          r.min_vel_y = c.min_vel_y;
+    r.max_rot_vel = c.max_rot_vel;      r.min_rot_vel = c.min_rot_vel;
+    r.acc_lim_x = c.acc_lim_x;  r.acc_lim_y = c.acc_lim_y;  r.acc_lim_theta = c.acc_lim_theta;
+    r.xy_goal_tolerance = config.xy_goal_tolerance;  r.yaw_goal_tolerance = config.yaw_goal_tolerance;
+    r.trans_stopped_vel = config.trans_stopped_vel;  r.rot_stopped_vel = config.rot_stopped_vel;
+    r.prune_plan = config.prune_plan;
+    if (navgpu_planner_set_limits(fleet_, 0, 1, &r) == NAVGPU_OK) {
+      cfg_ = c;
+      return;
+    }
+    ROS_WARN("navgpu_planner_set_limits: %s; reconfiguring in full", navgpu_last_error());
+  }
+  if (navgpu_planner_configure(fleet_, &c) != NAVGPU_OK) {
+    ROS_ERROR("navgpu_planner_configure: %s", navgpu_last_error());
+    return;  // (the previous configuration stays in force, and cfg_ with it)
+  }
+  cfg_ = c;
+  configured_ = true;
 }
 
 bool DWAPlannerROS::setPlan(const std::vector<geometry_msgs::PoseStamped>& orig_global_plan) {

@@ -71,6 +71,7 @@ class DWAPlannerROS : public nav_core::BaseLocalPlanner {
   boost::mutex configuration_mutex_;
   navgpu_fleet* fleet_;
   navgpu_dwa_config cfg_;
+  bool configured_;  // cfg_ is in force on the fleet (a navgpu_planner_configure has succeeded): a change of limits alone goes through navgpu_planner_set_limits
   navgpu_robot_state staged_;  // pose / velocity of the last stage
   double sim_period_;
   tf::Stamped<tf::Pose> current_pose_;
