@@ -800,6 +800,20 @@ int navgpu_tp_update_plans(navgpu_fleet* fleet, uint32_t first, uint32_t count, 
 int navgpu_tp_score_trajectories(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances,
                                  const uint32_t* probe_offsets /* n_robots + 1 */, const double* probes /* 9 per probe */,
                                  double* costs /* per probe */, int32_t* ok /* per probe, may be NULL */);
+/* navgpu_tp_update_plans / navgpu_tp_find_best_path for a robot list, with the conventions of navgpu_planner_*_list: instances = n_robots
+ * strictly increasing robot indices, each < n_instances (else NAVGPU_ERR_INVALID); plans, offsets, states and results go by position in
+ * the list; an empty list (n_robots = 0) is no work and no error.  What a call leaves - results, navgpu_tp_samples / _trajectory /
+ * _get_state, both MapGrids - is bit-equal to the range calls run contiguous run by contiguous run over the same robots, and every robot
+ * outside the list stays byte for byte as it was.  The cost does not depend on how the robots lie in the fleet: the list, ONE packed
+ * block that holds only what is in use (plan points, samples, the cells under the robots, start states) and one launch that spreads it;
+ * each kernel of the range call once (k_free_bits, k_tp_within, the wavefronts, k_tp_rollout) with the list where that passes `first`;
+ * the listed robots' results packed on the device and read in one copy; the second pass's winners the same way up.
+ * Errors are checked before anything is uploaded or launched, nothing changed for any robot: NAVGPU_ERR_STATE before navgpu_tp_configure
+ * and (find_best_path) for simple_attractor with an empty plan on a listed robot; NAVGPU_ERR_CAPACITY for a plan longer than max_plan. */
+int navgpu_tp_update_plans_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const double* plans_xy,
+                                const uint32_t* offsets /* n_robots + 1 */, int32_t compute_dists);
+int navgpu_tp_find_best_path_list(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_state* states,
+                                  navgpu_tp_result* results);
 
 /* ---- TrajectoryPlannerROS control cycle for a fleet (base_local_planner/src/trajectory_planner_ros.cpp:283-597) ----
  * Host-side mirror, free of ROS types, of TrajectoryPlannerROS::setPlan / computeVelocityCommands / stopWithAccLimits / rotateToGoal /
@@ -831,9 +845,9 @@ int navgpu_tp_ros_set_plans(navgpu_fleet* fleet, uint32_t first, uint32_t count,
  * 3. reached and |shortest_angular_distance(yaw, goal_th)| <= yaw_goal_tolerance: zero command, rotating_to_goal_ and the latch cleared,
  *    reached_goal_ set, ok 1, NAVGPU_BRANCH_AT_GOAL; no updatePlan / findBestPath for this robot.
  * 4. every other robot with a window: updatePlan(transformed_plan) + findBestPath - also the robots whose position is reached (:443-444:
- *    the reference refreshes the grids and advances the planner's oscillation / escape state there and discards the result).  One
- *    navgpu_tp_update_plans + navgpu_tp_find_best_path per CONTIGUOUS RUN of such robots: robots of step 3 split the runs (the limitation
- *    the DWA cycle has for robots without a local plan).
+ *    the reference refreshes the grids and advances the planner's oscillation / escape state there and discards the result).  ONE
+ *    updatePlan and ONE findBestPath for all of them: navgpu_tp_update_plans + navgpu_tp_find_best_path when they form one contiguous
+ *    run, else navgpu_tp_update_plans_list + navgpu_tp_find_best_path_list - robots of step 3 or without a window cost no launch.
  * 5. position reached: stopWithAccLimits' candidate while !rotating_to_goal_ && !stopped(odom) (NAVGPU_BRANCH_STOP), else
  *    rotating_to_goal_ = true and rotateToGoal's (NAVGPU_BRANCH_ROTATE).  All candidates are checked in ONE navgpu_tp_score_trajectories
  *    call behind step 4, so they see this cycle's grids, within_robot included.  Invalid: zero command, ok 0.
@@ -847,7 +861,7 @@ int navgpu_tp_ros_is_goal_reached(navgpu_fleet* fleet, uint32_t first, uint32_t 
 /* replaces: a loop of TrajectoryPlannerROS::checkTrajectory / scoreTrajectory(vx, vy, vtheta, update_map) calls (:528-588) over robots
  * (instances strictly increasing, in[k] the input of robot instances[k]) and velocity samples (3 doubles per probe, probe_offsets as in
  * navgpu_tp_score_trajectories).  With update_map the listed robots first get updatePlan({pose}, true) - the planner's plan and final
- * goal become the robot's pose, as in the reference - in runs of navgpu_tp_update_plans; then one navgpu_tp_score_trajectories call with
+ * goal become the robot's pose, as in the reference - in ONE navgpu_tp_update_plans_list; then one navgpu_tp_score_trajectories call with
  * pose and vel = odom_vel.  A robot without a pose: cost -1.0, ok 0, neither updated nor probed.  ok may be NULL. */
 int navgpu_tp_ros_check_trajectories(navgpu_fleet* fleet, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_input* in,
                                      const uint32_t* probe_offsets, const double* vel_samples, int32_t update_map, double* costs,

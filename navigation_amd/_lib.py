@@ -568,6 +568,8 @@ SYMBOLS = [
     ("navgpu_tp_set_state", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_tp_update_plans", C.c_int, [vp, u32, u32, vp, vp, i32]),
     ("navgpu_tp_score_trajectories", C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
+    ("navgpu_tp_update_plans_list", C.c_int, [vp, u32, vp, vp, vp, i32]),
+    ("navgpu_tp_find_best_path_list", C.c_int, [vp, u32, vp, vp, vp]),
     ("navgpu_tp_ros_configure", C.c_int, [vp, C.POINTER(TpRosParams)]),
     ("navgpu_tp_ros_set_plans", C.c_int, [vp, u32, u32, vp, vp, vp]),
     ("navgpu_tp_ros_compute_velocity_commands", C.c_int, [vp, u32, u32, vp, vp]),

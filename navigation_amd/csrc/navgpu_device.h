@@ -268,6 +268,29 @@ struct TpDev {
 };
 void launch_tp_within(const PlannerDev& pl, const TpDev& tp, uint32_t first, uint32_t count, hipStream_t s);
 void launch_tp_rollout(const PlannerDev& pl, const TpDev& tp, uint32_t first, uint32_t count, int store_points, hipStream_t s);
+// ---- the legacy planner for a robot list (navgpu_tp_update_plans_list, navgpu_tp_find_best_path_list): robot k of a launch is
+// list[k], a device array, strictly increasing.  One robot's record of the packed upload; the block holds the records, then the plan
+// points in use (x, y), then the samples in use (vx, vy, vtheta), then the cells under the robots.
+struct TpStageRec {
+  double start[6];                  // x, y, theta, vx, vy, vtheta
+  uint32_t inst;                    // the robot
+  uint32_t n_plan, plan_off;        // plan points and the first of them among the packed points
+  uint32_t n_samples, samples_off;  // samples and the first of them among the packed samples (and among the packed results coming back)
+  uint32_t n_within, within_off;    // cells under the robot and the first of them among the packed cells
+  uint32_t pad;
+};
+static_assert(sizeof(TpStageRec) == 80, "staged as an array of these in front of the plan points");
+struct TpStageBlock {  // per-launch view of the block on the device
+  const TpStageRec* rec;
+  const double *plan, *samples;
+  const uint32_t* within;
+};
+// Weak for the reason launch_tp_probe (below) is; without them the listed calls answer NAVGPU_ERR_STATE.
+__attribute__((weak)) void launch_tp_stage_scatter(const PlannerDev& pl, const TpDev& tp, const TpStageBlock& b, uint32_t n_robots, int with_rollout, hipStream_t s);
+__attribute__((weak)) void launch_tp_within_list(const PlannerDev& pl, const TpDev& tp, const uint32_t* list, uint32_t count, hipStream_t s);
+__attribute__((weak)) void launch_tp_rollout_list(const PlannerDev& pl, const TpDev& tp, const uint32_t* list, uint32_t count, int store_points, hipStream_t s);
+__attribute__((weak)) void launch_tp_gather_out(const TpDev& tp, const TpStageRec* rec, TpOut* packed, uint32_t n_robots, hipStream_t s);
+__attribute__((weak)) void launch_tp_winner_scatter(const TpDev& tp, const uint32_t* list, const int32_t* winners, uint32_t n_robots, hipStream_t s);
 // batched scoreTrajectory (navgpu_tp_score_trajectories, tp_probe_kernels.hip): per-launch view of the fleet's probe buffers
 struct TpProbeBatch {
   const double* probes;      // [n_probes][9] pose x y theta, velocity x y theta, sample x y theta
@@ -430,7 +453,8 @@ static_assert(sizeof(StageRec) == 64, "staged as an array of these in front of t
 __attribute__((weak)) void launch_stage_poses_list(const PoseChunkList& c, hipStream_t s);
 __attribute__((weak)) void launch_stage_scatter(const PlannerDev& pl, const StageRec* rec, const double* poses, uint32_t n_robots, hipStream_t s);
 __attribute__((weak)) void launch_samples_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);
-__attribute__((weak)) void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order);
+__attribute__((weak)) void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order = nullptr,
+                                           bool free_ready = false);  // as launch_bfs: false = k_free_bits and the work counters are this launch's
 __attribute__((weak)) uint32_t launch_score_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s);  // returns blocks per instance
 __attribute__((weak)) void launch_select_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, uint32_t n_blocks, hipStream_t s);
 // ---- the split image build (navgpu_planner_set_split_prep): the wavefront launch with scorePrepFree workgroups, and the scoring

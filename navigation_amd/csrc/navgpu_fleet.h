@@ -55,6 +55,9 @@ struct RobotSet {
 };
 // instances[0 .. n_robots) strictly increasing, each < n_instances (navgpu_planner_check_trajectories' conventions)
 bool listOk(const navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances);
+// finish the MapGrids of the set's robots whose last wavefronts stopped at their box - one listed launch for all of them, however
+// they lie; fails, before any launch, when their inputs have changed since (ensureCompleteGrids(f, first, count) is the range's set)
+int ensureCompleteGrids(navgpu_fleet* f, const RobotSet& r);
 // what a costmap stage call checks of its observations before it changes anything: every one for a robot of the set, within the
 // fleet's capacities and the caller's points
 int checkStageObservations(navgpu_fleet* f, const RobotSet& r, const navgpu_observation* obs, uint32_t n_obs, uint32_t n_points_total);
@@ -235,6 +238,19 @@ struct navgpu_fleet {
     uint8_t *d_in = nullptr, *h_in = nullptr;     // [cap][9] doubles, [cap] robot indices
     double *d_cost = nullptr, *h_cost = nullptr;  // [cap]
   } tpb;
+  // the legacy planner for a robot list (navgpu_tp_update_plans_list, navgpu_tp_find_best_path_list), allocated by the first listed
+  // call: the list its kernels read, the packed upload (TpStageRec ...) as a pinned block and its device twin, grown on demand, the
+  // packed results coming back and the second pass's winners
+  struct TpList {
+    uint32_t *d_list = nullptr, *h_list = nullptr;   // [n]
+    hipEvent_t ev_list = nullptr;                    // behind the copy out of h_list
+    bool ev_set = false;
+    uint8_t *d_stage = nullptr, *h_stage = nullptr;  // [stage_bytes]
+    size_t stage_bytes = 0;
+    TpOut *d_out = nullptr, *h_out = nullptr;        // [out_cap] results of the listed robots' samples, packed
+    size_t out_cap = 0;
+    int32_t *d_win = nullptr, *h_win = nullptr;      // [n] winners by list position
+  } tpl;
   // TrajectoryPlannerROS mirror (navgpu_tp_ros.cpp): per-instance controller state, host only
   struct TpRosState {
     std::vector<double> plan;      // global_plan_: (x, y, yaw) triples in the plan's frame (prunePlan shrinks it)

@@ -286,7 +286,7 @@ int navgpu_fleet_destroy(navgpu_fleet* f) {
     hipEventDestroy(e.a);
     hipEventDestroy(e.b);
   }
-  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.ev_list, f->cml.ev_list, f->cml.ev_stage})
+  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.ev_list, f->cml.ev_list, f->cml.ev_stage, f->tpl.ev_list})
     if (e) hipEventDestroy(e);
   for (void* p : f->allocs) hipFree(p);
   for (void* p : f->pinned) hipHostFree(p);
@@ -1149,28 +1149,44 @@ static bool robotBox(const navgpu_fleet* f, uint32_t i, const float pos[3], uint
   return true;
 }
 // finish the grids of robots whose last wavefronts stopped early; fails when their inputs have changed since
-extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, uint32_t first, uint32_t count) {
+static int reserveCycleList(navgpu_fleet* f);
+extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, const RobotSet& r) {
   if (NAVGPU_DEBUG_ENV("NAVGPU_DEBUG_RAW_GRIDS")) return NAVGPU_OK;  // tool builds only (tools/probe_levels.py): look at what a bounded search left
-  for (uint32_t i = first; i < first + count; ++i)
-    if (f->grid_partial[i] && f->cycle_gen[i] != f->inputs_gen[i]) {
+  uint32_t n_partial = 0;
+  for (uint32_t k = 0; k < r.count; ++k) {
+    const uint32_t i = r[k];
+    if (!f->grid_partial[i]) continue;
+    ++n_partial;
+    if (f->cycle_gen[i] != f->inputs_gen[i]) {
       g_last_error = "MapGrids of instance " + std::to_string(i) + " were searched inside the robot's box only and the costmap / plan they came from has changed; "
                      "read them before the next update or call navgpu_planner_set_bounded_map_grids(f, 0)";
       return NAVGPU_ERR_STATE;
     }
+  }
+  if (!n_partial) return NAVGPU_OK;
+  if (!launch_bfs_list) return NAVGPU_ERR_STATE;
+  int rc = reserveCycleList(f);
+  if (rc != NAVGPU_OK) return rc;
+  // the partial robots of the set as one list (increasing, as the set is), through the listed cycle's buffers
+  navgpu_fleet::CycleList& cl = f->cl;
+  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));  // the pinned list may still feed the copy of a listed launch before
+  uint32_t n = 0;
+  for (uint32_t k = 0; k < r.count; ++k)
+    if (f->grid_partial[r[k]]) {
+      f->grid_partial[r[k]] = 0;
+      cl.h_list[n++] = r[k];
+    }
+  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
+  cl.ev_set = true;
   PlannerDev pl = f->pl;
   pl.bfs_bounded = 0;
-  pl.bfs_seed_cap = 0;  // (no k_samples in front of these launches: the lists are some earlier cycle's)
-  for (uint32_t i = first; i < first + count;) {
-    if (!f->grid_partial[i]) {
-      ++i;
-      continue;
-    }
-    uint32_t j = i;
-    while (j < first + count && f->grid_partial[j]) f->grid_partial[j++] = 0;
-    launch_bfs(pl, i, j - i, f->stream);
-    i = j;
-  }
+  pl.bfs_seed_cap = 0;  // (no k_samples in front of this launch: the lists are some earlier cycle's)
+  PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n, f->stream, nullptr, false));
   return checkLaunch();
+}
+extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, uint32_t first, uint32_t count) {
+  return ensureCompleteGrids(f, RobotSet{first, count, nullptr});
 }
 
 // Per-robot limits: the records of the set's robots that navgpu_planner_set_limits changed travel to pl.limits as kernel arguments
@@ -1862,7 +1878,7 @@ int navgpu_planner_cycle_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t
   if (split)
     PROFILED(f, NAVGPU_K_BFS, launch_bfs_prep_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
   else
-    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3, true));
   uint32_t n_blocks = 0;
   if (split)
     PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_grids_list(pl, cl.d_list, n_robots, f->stream));
@@ -2045,8 +2061,8 @@ int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const 
     pb = nb;
   }
   // Bounded MapGrids: the single call's test per listed robot, with the largest reach over its probes; the robots that fail it get
-  // complete grids, in contiguous runs
-  for (uint32_t k = 0; k < n_robots;) {
+  // complete grids, in one listed launch
+  {
     auto leavesBox = [&](uint32_t q) {
       const uint32_t i = instances[q];
       if (!f->grid_partial[i] || probe_offsets[q + 1] == probe_offsets[q]) return false;
@@ -2058,15 +2074,13 @@ int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const 
       const int32_t* hb = &f->h_box[(size_t)4 * i];
       return !(!pl.mg_generic && robotBox(f, i, st.pos, need, nb) && nb[0] >= hb[0] && nb[1] <= hb[1] && nb[2] >= hb[2] && nb[3] <= hb[3]);
     };
-    if (!leavesBox(k)) {
-      ++k;
-      continue;
+    std::vector<uint32_t> leaving;
+    for (uint32_t k = 0; k < n_robots; ++k)
+      if (leavesBox(k)) leaving.push_back(instances[k]);
+    if (!leaving.empty()) {
+      int rc = ensureCompleteGrids(f, RobotSet{0, (uint32_t)leaving.size(), leaving.data()});
+      if (rc) return rc;
     }
-    uint32_t e = k + 1;
-    while (e < n_robots && instances[e] == instances[e - 1] + 1 && leavesBox(e)) ++e;
-    int rc = ensureCompleteGrids(f, instances[k], e - k);
-    if (rc) return rc;
-    k = e;
   }
   memcpy(pb.h_in, instances, sizeof(uint32_t) * n_robots);
   memcpy(pb.h_in + n_robots, probe_offsets, sizeof(uint32_t) * (n_robots + 1));

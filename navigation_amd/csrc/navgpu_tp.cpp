@@ -1,6 +1,7 @@
 // Host side of the legacy base_local_planner::TrajectoryPlanner (include/navgpu.h, navgpu_tp_*): footprint cells
 // under the robot, velocity window and sample enumeration, launch of the wavefronts and of k_tp_rollout, and the
-// replay of createTrajectories' sequential, stateful selection over the per-sample results.
+// replay of createTrajectories' sequential, stateful selection over the per-sample results.  updatePlan and findBestPath take a
+// range of robots or a strictly increasing list (navgpu_tp_*_list): one copy of the host logic over a RobotSet, two ways to hand over.
 #include "navgpu_fleet.h"
 
 extern "C" {
@@ -186,30 +187,167 @@ int navgpu_tp_configure(navgpu_fleet* f, const navgpu_tp_config* cfg_in) {
 }
 
 // the wavefront launch of the legacy planner: two grids, path_map_ optionally with within_robot bits
-static int tpLaunchGrids(navgpu_fleet* f, uint32_t first, uint32_t count, bool with_within) {
+// (a listed set's robots are in f->tpl.d_list by then: tpSendList)
+static int tpLaunchGrids(navgpu_fleet* f, const RobotSet& r, bool with_within) {
   PlannerDev pl = f->pl;
   pl.bfs_grids = 2;
   pl.within = with_within ? f->tp.within_bits : nullptr;
   pl.cfg.allow_unknown = f->tp.cfg.allow_unknown;
   pl.bfs_bounded = 0;  // the legacy planner's look-ups are not confined to a box around the robot
   pl.bfs_seed_cap = 0;  // no k_samples in front of this launch: the wavefronts seed from the plan
-  for (uint32_t i = first; i < first + count; ++i) f->grid_partial[i] = 0;
-  PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, first, count, f->stream));
+  for (uint32_t k = 0; k < r.count; ++k) f->grid_partial[r[k]] = 0;
+  if (r.list)
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, f->tpl.d_list, r.count, f->stream, nullptr, false));
+  else
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, r.first, r.count, f->stream));
+  return NAVGPU_OK;
+}
+// the set's plans in the pinned mirrors (what a range call uploads, and what the DWA planner's reach reads of a robot's plan)
+static int tpPlanMirrors(navgpu_fleet* f, const RobotSet& r) {
+  PlannerDev& pl = f->pl;
+  for (uint32_t k = 0; k < r.count; ++k)
+    if (f->tph[r[k]].plan.size() / 2 > pl.max_plan) return NAVGPU_ERR_CAPACITY;
+  for (uint32_t k = 0; k < r.count; ++k) {
+    const uint32_t i = r[k];
+    const std::vector<double>& p = f->tph[i].plan;
+    if (!p.empty()) memcpy(&f->hp_plan[(size_t)i * pl.max_plan * 2], p.data(), sizeof(double) * p.size());
+    f->hp_plan_cnt[i] = (uint32_t)(p.size() / 2);
+  }
   return NAVGPU_OK;
 }
 static int tpUploadPlans(navgpu_fleet* f, uint32_t first, uint32_t count) {
   PlannerDev& pl = f->pl;
-  for (uint32_t i = first; i < first + count; ++i) {
-    const std::vector<double>& p = f->tph[i].plan;
-    const uint32_t np = (uint32_t)(p.size() / 2);
-    if (np > pl.max_plan) return NAVGPU_ERR_CAPACITY;
-    if (np) memcpy(&f->hp_plan[(size_t)i * pl.max_plan * 2], p.data(), sizeof(double) * p.size());
-    f->hp_plan_cnt[i] = np;
-  }
+  int rc = tpPlanMirrors(f, RobotSet{first, count, nullptr});
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(pl.plan + (size_t)first * pl.max_plan * 2, f->hp_plan + (size_t)first * pl.max_plan * 2,
                          sizeof(double) * 2 * (size_t)count * pl.max_plan, hipMemcpyHostToDevice, f->stream));
   HIP_TRY(hipMemcpyAsync(pl.plan_count + first, f->hp_plan_cnt + first, sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
   return NAVGPU_OK;
+}
+
+// ---- a listed call's hand-over (navgpu_tp_update_plans_list, navgpu_tp_find_best_path_list)
+static bool tpListLaunchers() {
+  return launch_bfs_list && launch_tp_stage_scatter && launch_tp_within_list && launch_tp_rollout_list && launch_tp_gather_out && launch_tp_winner_scatter;
+}
+// the buffers of the listed calls: the fixed ones on the first call, all or none; the packed block and the results grow on demand
+static int reserveTpList(navgpu_fleet* f, size_t stage_bytes, size_t out_cap) {
+  navgpu_fleet::TpList& tl = f->tpl;
+  const uint32_t n = f->desc.n_instances;
+  if (!tl.d_list) {
+    navgpu_fleet::TpList nl;
+    int rc = f->alloc(&nl.d_list, n);
+    if (!rc) rc = f->alloc(&nl.d_win, n);
+    if (!rc) rc = f->allocPinned(&nl.h_list, n);
+    if (!rc) rc = f->allocPinned(&nl.h_win, n);
+    if (!rc && hipEventCreateWithFlags(&nl.ev_list, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
+    if (rc) {
+      f->release(nl.d_list);
+      f->release(nl.d_win);
+      f->releasePinned(nl.h_list);
+      f->releasePinned(nl.h_win);
+      return rc;
+    }
+    tl = nl;
+  }
+  if (stage_bytes > tl.stage_bytes) {  // (the block it replaces is idle: every call of the legacy planner drains the stream)
+    const size_t bytes = (stage_bytes + 65535u) & ~(size_t)65535u;
+    uint8_t *d = nullptr, *h = nullptr;
+    int rc = f->alloc(&d, bytes);
+    if (!rc) rc = f->allocPinned(&h, bytes);
+    if (rc) {
+      f->release(d);
+      return rc;
+    }
+    f->release(tl.d_stage);
+    f->releasePinned(tl.h_stage);
+    tl.d_stage = d;
+    tl.h_stage = h;
+    tl.stage_bytes = bytes;
+  }
+  if (out_cap > tl.out_cap) {
+    const size_t cap = (out_cap + 1023u) & ~(size_t)1023u;
+    TpOut *d = nullptr, *h = nullptr;
+    int rc = f->alloc(&d, cap);
+    if (!rc) rc = f->allocPinned(&h, cap);
+    if (rc) {
+      f->release(d);
+      return rc;
+    }
+    f->release(tl.d_out);
+    f->releasePinned(tl.h_out);
+    tl.d_out = d;
+    tl.h_out = h;
+    tl.out_cap = cap;
+  }
+  return NAVGPU_OK;
+}
+// The list and ONE packed block for its robots - records, plan points, and with_rollout the samples, the cells under the robots and the
+// start states, all out of the host mirrors and only what is in use - then k_tp_stage_scatter: two copies and a launch, however the
+// robots lie in the fleet.  The records stay on the device for k_tp_gather_out.
+static int tpSendList(navgpu_fleet* f, const RobotSet& r, bool with_rollout, size_t* n_samples_total) {
+  PlannerDev& pl = f->pl;
+  TpDev& tp = f->tp;
+  const uint32_t ms = tp.max_samples;
+  size_t n_plan = 0, n_smp = 0, n_within = 0;
+  for (uint32_t k = 0; k < r.count; ++k) {
+    n_plan += f->hp_plan_cnt[r[k]];
+    if (with_rollout) {
+      n_smp += f->tp_h_nsamples[r[k]];
+      n_within += f->tp_h_within_count[r[k]];
+    }
+  }
+  const size_t off_plan = sizeof(TpStageRec) * r.count, off_smp = off_plan + sizeof(double) * 2 * n_plan;
+  const size_t off_within = off_smp + sizeof(double) * 3 * n_smp, bytes = off_within + sizeof(uint32_t) * n_within;
+  int rc = reserveTpList(f, bytes, n_smp);
+  if (rc) return rc;
+  navgpu_fleet::TpList& tl = f->tpl;
+  if (tl.ev_set) HIP_TRY(hipEventSynchronize(tl.ev_list));  // the pinned list may still feed the copy of the listed call before
+  memcpy(tl.h_list, r.list, sizeof(uint32_t) * r.count);
+  HIP_TRY(hipMemcpyAsync(tl.d_list, tl.h_list, sizeof(uint32_t) * r.count, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipEventRecord(tl.ev_list, f->stream));
+  tl.ev_set = true;
+  TpStageRec* rec = reinterpret_cast<TpStageRec*>(tl.h_stage);
+  double* plan = reinterpret_cast<double*>(tl.h_stage + off_plan);
+  double* smp = reinterpret_cast<double*>(tl.h_stage + off_smp);
+  uint32_t* within = reinterpret_cast<uint32_t*>(tl.h_stage + off_within);
+  uint32_t at_plan = 0, at_smp = 0, at_within = 0;
+  for (uint32_t k = 0; k < r.count; ++k) {
+    const uint32_t i = r[k];
+    TpStageRec& q = rec[k];
+    q = TpStageRec();
+    q.inst = i;
+    q.n_plan = f->hp_plan_cnt[i];
+    q.plan_off = at_plan;
+    memcpy(plan + 2 * (size_t)at_plan, &f->hp_plan[(size_t)i * pl.max_plan * 2], sizeof(double) * 2 * q.n_plan);
+    at_plan += q.n_plan;
+    if (!with_rollout) continue;
+    memcpy(q.start, &f->tp_h_start[(size_t)i * 6], sizeof(q.start));
+    q.n_samples = f->tp_h_nsamples[i];
+    q.samples_off = at_smp;
+    memcpy(smp + 3 * (size_t)at_smp, &f->tp_h_samples[(size_t)i * ms * 3], sizeof(double) * 3 * q.n_samples);
+    at_smp += q.n_samples;
+    q.n_within = f->tp_h_within_count[i];
+    q.within_off = at_within;
+    memcpy(within + at_within, &f->tp_h_within[(size_t)i * tp.max_within], sizeof(uint32_t) * q.n_within);
+    at_within += q.n_within;
+  }
+  HIP_TRY(hipMemcpyAsync(tl.d_stage, tl.h_stage, bytes, hipMemcpyHostToDevice, f->stream));
+  const TpStageBlock b{reinterpret_cast<const TpStageRec*>(tl.d_stage), reinterpret_cast<const double*>(tl.d_stage + off_plan),
+                       reinterpret_cast<const double*>(tl.d_stage + off_smp), reinterpret_cast<const uint32_t*>(tl.d_stage + off_within)};
+  launch_tp_stage_scatter(pl, tp, b, r.count, with_rollout ? 1 : 0, f->stream);
+  if (n_samples_total) *n_samples_total = n_smp;
+  return NAVGPU_OK;
+}
+// updatePlan's host half for one robot (:480-487)
+static void tpSetPlan(navgpu_fleet::TpHost& h, const double* p, uint32_t n) {
+  h.plan.assign(p, p + 2 * (size_t)n);
+  if (n) {
+    h.final_goal_x = p[2 * (size_t)(n - 1)];
+    h.final_goal_y = p[2 * (size_t)(n - 1) + 1];
+    h.final_goal_position_valid = true;
+  } else {
+    h.final_goal_position_valid = false;
+  }
 }
 
 int navgpu_tp_update_plan(navgpu_fleet* f, uint32_t instance, const double* plan_xy, uint32_t n, int32_t compute_dists) {
@@ -217,19 +355,11 @@ int navgpu_tp_update_plan(navgpu_fleet* f, uint32_t instance, const double* plan
   FleetGuard guard_(f);
   if (!f->tp_configured) return NAVGPU_ERR_STATE;
   if (n > f->pl.max_plan) return NAVGPU_ERR_CAPACITY;
-  navgpu_fleet::TpHost& h = f->tph[instance];
-  h.plan.assign(plan_xy, plan_xy + 2 * (size_t)n);
-  if (n) {  // :480-487
-    h.final_goal_x = plan_xy[2 * (size_t)(n - 1)];
-    h.final_goal_y = plan_xy[2 * (size_t)(n - 1) + 1];
-    h.final_goal_position_valid = true;
-  } else {
-    h.final_goal_position_valid = false;
-  }
+  tpSetPlan(f->tph[instance], plan_xy, n);
   if (compute_dists) {  // :489-499 (resetPathDist clears within_robot)
     int rc = tpUploadPlans(f, instance, 1);
     if (rc) return rc;
-    rc = tpLaunchGrids(f, instance, 1, false);
+    rc = tpLaunchGrids(f, RobotSet{instance, 1, nullptr}, false);
     if (rc) return rc;
     HIP_TRY(waitStream(f->stream));
     return checkLaunch();
@@ -240,26 +370,31 @@ int navgpu_tp_update_plan(navgpu_fleet* f, uint32_t instance, const double* plan
 static inline bool tpFlag(const navgpu_tp_state& s, uint32_t bit) { return (s.flags & bit) != 0; }
 static inline void tpSet(navgpu_tp_state& s, uint32_t bit, bool v) { s.flags = v ? (s.flags | bit) : (s.flags & ~bit); }
 
-int navgpu_tp_find_best_path(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, navgpu_tp_result* results) {
-  if (!f || !states || !results || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
-  if (!f->tp_configured) return NAVGPU_ERR_STATE;
+// findBestPath for the robots of a set - the range of navgpu_tp_find_best_path or the list of navgpu_tp_find_best_path_list; states
+// and results go by position in the set.  One copy of the host logic; the two forms differ in how the inputs travel and the
+// kernels find their robots.
+static int tpFindBestPath(navgpu_fleet* f, const RobotSet& r, const navgpu_robot_state* states, navgpu_tp_result* results) {
   TpDev& tp = f->tp;
   const navgpu_tp_config& c = tp.cfg;
   const CostmapDev& cm = f->cm;
   const uint32_t ms = tp.max_samples;
+  const uint32_t count = r.count;
   std::vector<std::vector<TpPlanned>> planned(count);
   std::vector<double> dvth(count, 0.0);
   std::vector<std::vector<TpCell>> cells(count);
   size_t max_cells = 0;
+  if (c.simple_attractor)  // the reference indexes global_plan_[size() - 1] (:311-314)
+    for (uint32_t k = 0; k < count; ++k)
+      if (f->tph[r[k]].plan.empty()) {
+        g_last_error = "navgpu_tp_find_best_path: simple_attractor needs a plan";
+        return NAVGPU_ERR_STATE;
+      }
+  for (uint32_t k = 0; k < count; ++k)  // (navgpu_tp_update_plan* keeps longer plans out)
+    if (f->tph[r[k]].plan.size() / 2 > f->pl.max_plan) return NAVGPU_ERR_CAPACITY;
   // ---- host: footprint cells under the robot, velocity window, sample enumeration
   for (uint32_t k = 0; k < count; ++k) {
-    const uint32_t inst = first + k;
+    const uint32_t inst = r[k];
     navgpu_fleet::TpHost& h = f->tph[inst];
-    if (c.simple_attractor && h.plan.empty()) {  // the reference indexes global_plan_[size() - 1] (:311-314)
-      g_last_error = "navgpu_tp_find_best_path: simple_attractor needs a plan";
-      return NAVGPU_ERR_STATE;
-    }
     const float* pos = states[k].pos;
     const float* vel = states[k].vel;
     tpFootprintCells(pos, &f->h_fp_spec[(size_t)inst * kMaxFootprint * 2], f->h_fp_n[inst], f->h_origin[2 * inst],
@@ -335,32 +470,50 @@ int navgpu_tp_find_best_path(navgpu_fleet* f, uint32_t first, uint32_t count, co
     f->tp_h_within.assign((size_t)f->desc.n_instances * tp.max_within, 0);
   }
   for (uint32_t k = 0; k < count; ++k) {
-    const uint32_t inst = first + k;
+    const uint32_t inst = r[k];
     f->tp_h_within_count[inst] = (uint32_t)cells[k].size();
     for (size_t q = 0; q < cells[k].size(); ++q)
       f->tp_h_within[(size_t)inst * tp.max_within + q] = (uint32_t)cells[k][q].y * cm.nx + (uint32_t)cells[k][q].x;
   }
   // ---- H2D + wavefronts + rollout of every planned sample
-  int rc = tpUploadPlans(f, first, count);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(tp.within_cells + (size_t)first * tp.max_within, &f->tp_h_within[(size_t)first * tp.max_within],
-                         sizeof(uint32_t) * (size_t)count * tp.max_within, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipMemcpyAsync(tp.within_count + first, &f->tp_h_within_count[first], sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipMemcpyAsync(tp.samples + (size_t)first * ms * 3, &f->tp_h_samples[(size_t)first * ms * 3], sizeof(double) * 3 * (size_t)count * ms,
-                         hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipMemcpyAsync(tp.n_samples + first, &f->tp_h_nsamples[first], sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipMemcpyAsync(tp.start + (size_t)first * 6, &f->tp_h_start[(size_t)first * 6], sizeof(double) * 6 * count, hipMemcpyHostToDevice, f->stream));
-  launch_tp_within(f->pl, tp, first, count, f->stream);
-  rc = tpLaunchGrids(f, first, count, true);
-  if (rc) return rc;
-  PROFILED(f, NAVGPU_K_SCORE, launch_tp_rollout(f->pl, tp, first, count, 0, f->stream));
-  HIP_TRY(hipMemcpyAsync(&f->tp_h_out[(size_t)first * ms], tp.out + (size_t)first * ms, sizeof(TpOut) * (size_t)count * ms, hipMemcpyDeviceToHost, f->stream));
-  HIP_TRY(waitStream(f->stream));
-  rc = checkLaunch();
-  if (rc) return rc;
+  const uint32_t first = r.first;  // (of a range)
+  int rc;
+  if (r.list) {  // one packed block out of the mirrors written above, spread on the device
+    if ((rc = tpPlanMirrors(f, r))) return rc;
+    size_t n_out = 0;
+    if ((rc = tpSendList(f, r, true, &n_out))) return rc;
+    launch_tp_within_list(f->pl, tp, f->tpl.d_list, count, f->stream);
+    if ((rc = tpLaunchGrids(f, r, true))) return rc;
+    PROFILED(f, NAVGPU_K_SCORE, launch_tp_rollout_list(f->pl, tp, f->tpl.d_list, count, 0, f->stream));
+    launch_tp_gather_out(tp, reinterpret_cast<const TpStageRec*>(f->tpl.d_stage), f->tpl.d_out, count, f->stream);
+    HIP_TRY(hipMemcpyAsync(f->tpl.h_out, f->tpl.d_out, sizeof(TpOut) * n_out, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(waitStream(f->stream));
+    if ((rc = checkLaunch())) return rc;
+    size_t at = 0;
+    for (uint32_t k = 0; k < count; ++k) {  // (the order of the upload's samples)
+      const uint32_t n = f->tp_h_nsamples[r[k]];
+      if (n) memcpy(&f->tp_h_out[(size_t)r[k] * ms], f->tpl.h_out + at, sizeof(TpOut) * n);
+      at += n;
+    }
+  } else {
+    if ((rc = tpUploadPlans(f, first, count))) return rc;
+    HIP_TRY(hipMemcpyAsync(tp.within_cells + (size_t)first * tp.max_within, &f->tp_h_within[(size_t)first * tp.max_within],
+                           sizeof(uint32_t) * (size_t)count * tp.max_within, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(tp.within_count + first, &f->tp_h_within_count[first], sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(tp.samples + (size_t)first * ms * 3, &f->tp_h_samples[(size_t)first * ms * 3], sizeof(double) * 3 * (size_t)count * ms,
+                           hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(tp.n_samples + first, &f->tp_h_nsamples[first], sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
+    HIP_TRY(hipMemcpyAsync(tp.start + (size_t)first * 6, &f->tp_h_start[(size_t)first * 6], sizeof(double) * 6 * count, hipMemcpyHostToDevice, f->stream));
+    launch_tp_within(f->pl, tp, first, count, f->stream);
+    if ((rc = tpLaunchGrids(f, r, true))) return rc;
+    PROFILED(f, NAVGPU_K_SCORE, launch_tp_rollout(f->pl, tp, first, count, 0, f->stream));
+    HIP_TRY(hipMemcpyAsync(&f->tp_h_out[(size_t)first * ms], tp.out + (size_t)first * ms, sizeof(TpOut) * (size_t)count * ms, hipMemcpyDeviceToHost, f->stream));
+    HIP_TRY(waitStream(f->stream));
+    if ((rc = checkLaunch())) return rc;
+  }
   // ---- host: the reference's sequential selection (createTrajectories :568-905) over the per-sample results
   for (uint32_t k = 0; k < count; ++k) {
-    const uint32_t inst = first + k;
+    const uint32_t inst = r[k];
     navgpu_fleet::TpHost& h = f->tph[inst];
     navgpu_tp_state& S = h.st;
     const std::vector<TpPlanned>& P = planned[k];
@@ -519,10 +672,33 @@ int navgpu_tp_find_best_path(navgpu_fleet* f, uint32_t first, uint32_t count, co
     f->tp_h_winner[inst] = best;
   }
   // ---- second pass: the winner's points (published as the local plan)
-  HIP_TRY(hipMemcpyAsync(tp.winner + first, &f->tp_h_winner[first], sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
-  launch_tp_rollout(f->pl, tp, first, count, 1, f->stream);
+  if (r.list) {
+    for (uint32_t k = 0; k < count; ++k) f->tpl.h_win[k] = f->tp_h_winner[r[k]];
+    HIP_TRY(hipMemcpyAsync(f->tpl.d_win, f->tpl.h_win, sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
+    launch_tp_winner_scatter(tp, f->tpl.d_list, f->tpl.d_win, count, f->stream);
+    launch_tp_rollout_list(f->pl, tp, f->tpl.d_list, count, 1, f->stream);
+  } else {
+    HIP_TRY(hipMemcpyAsync(tp.winner + first, &f->tp_h_winner[first], sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
+    launch_tp_rollout(f->pl, tp, first, count, 1, f->stream);
+  }
   HIP_TRY(waitStream(f->stream));
   return checkLaunch();
+}
+
+int navgpu_tp_find_best_path(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, navgpu_tp_result* results) {
+  if (!f || !states || !results || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->tp_configured) return NAVGPU_ERR_STATE;
+  return tpFindBestPath(f, RobotSet{first, count, nullptr}, states, results);
+}
+int navgpu_tp_find_best_path_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_state* states,
+                                  navgpu_tp_result* results) {
+  if (!f) return NAVGPU_ERR_INVALID;
+  if (!n_robots) return NAVGPU_OK;  // no work
+  if (!states || !results || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->tp_configured || !tpListLaunchers()) return NAVGPU_ERR_STATE;
+  return tpFindBestPath(f, RobotSet{0, n_robots, instances}, states, results);
 }
 
 int navgpu_tp_trajectory(navgpu_fleet* f, uint32_t instance, double* xyth, uint32_t cap) {
@@ -571,36 +747,45 @@ int navgpu_tp_score_trajectory(navgpu_fleet* f, uint32_t instance, const double 
   return checkLaunch();
 }
 
-int navgpu_tp_update_plans(navgpu_fleet* f, uint32_t first, uint32_t count, const double* plans_xy, const uint32_t* offsets, int32_t compute_dists) {
-  if (!f || !offsets || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
-  for (uint32_t k = 0; k < count; ++k)
-    if (offsets[k + 1] < offsets[k]) return NAVGPU_ERR_INVALID;
-  if (offsets[count] > offsets[0] && !plans_xy) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
-  if (!f->tp_configured) return NAVGPU_ERR_STATE;
-  for (uint32_t k = 0; k < count; ++k)  // before anything changes for any robot
+// updatePlan for the robots of a set (the range of navgpu_tp_update_plans or the list of navgpu_tp_update_plans_list), plans by
+// position in the set; the caller has checked the offsets
+static int tpUpdatePlans(navgpu_fleet* f, const RobotSet& r, const double* plans_xy, const uint32_t* offsets, int32_t compute_dists) {
+  for (uint32_t k = 0; k < r.count; ++k)  // before anything changes for any robot
     if (offsets[k + 1] - offsets[k] > f->pl.max_plan) return NAVGPU_ERR_CAPACITY;
-  for (uint32_t k = 0; k < count; ++k) {
-    navgpu_fleet::TpHost& h = f->tph[first + k];
+  for (uint32_t k = 0; k < r.count; ++k) {
     const uint32_t n = offsets[k + 1] - offsets[k];
-    const double* p = n ? plans_xy + 2 * (size_t)offsets[k] : nullptr;
-    h.plan.assign(p, p + 2 * (size_t)n);
-    if (n) {  // :480-487
-      h.final_goal_x = p[2 * (size_t)(n - 1)];
-      h.final_goal_y = p[2 * (size_t)(n - 1) + 1];
-      h.final_goal_position_valid = true;
-    } else {
-      h.final_goal_position_valid = false;
-    }
+    tpSetPlan(f->tph[r[k]], n ? plans_xy + 2 * (size_t)offsets[k] : nullptr, n);
   }
   if (!compute_dists) return NAVGPU_OK;
-  // :489-499 for the whole range: the plans and their lengths go up together, one wavefront launch covers the range, one wait
-  int rc = tpUploadPlans(f, first, count);
+  // :489-499 for the whole set: the plans and their lengths go up together, one wavefront launch covers the set, one wait
+  int rc = r.list ? tpPlanMirrors(f, r) : tpUploadPlans(f, r.first, r.count);
+  if (!rc && r.list) rc = tpSendList(f, r, false, nullptr);
   if (rc) return rc;
-  rc = tpLaunchGrids(f, first, count, false);
+  rc = tpLaunchGrids(f, r, false);
   if (rc) return rc;
   HIP_TRY(waitStream(f->stream));
   return checkLaunch();
+}
+static bool tpOffsetsOk(uint32_t count, const double* plans_xy, const uint32_t* offsets) {
+  if (!offsets) return false;
+  for (uint32_t k = 0; k < count; ++k)
+    if (offsets[k + 1] < offsets[k]) return false;
+  return !(offsets[count] > offsets[0] && !plans_xy);
+}
+int navgpu_tp_update_plans(navgpu_fleet* f, uint32_t first, uint32_t count, const double* plans_xy, const uint32_t* offsets, int32_t compute_dists) {
+  if (!f || !f->rangeOk(first, count) || !tpOffsetsOk(count, plans_xy, offsets)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->tp_configured) return NAVGPU_ERR_STATE;
+  return tpUpdatePlans(f, RobotSet{first, count, nullptr}, plans_xy, offsets, compute_dists);
+}
+int navgpu_tp_update_plans_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const double* plans_xy, const uint32_t* offsets,
+                                int32_t compute_dists) {
+  if (!f) return NAVGPU_ERR_INVALID;
+  if (!n_robots) return NAVGPU_OK;  // no work
+  if (!listOk(f, n_robots, instances) || !tpOffsetsOk(n_robots, plans_xy, offsets)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  if (!f->tp_configured || !tpListLaunchers()) return NAVGPU_ERR_STATE;
+  return tpUpdatePlans(f, RobotSet{0, n_robots, instances}, plans_xy, offsets, compute_dists);
 }
 
 int navgpu_tp_score_trajectories(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const uint32_t* probe_offsets,

@@ -2,8 +2,9 @@
 // base_local_planner/src/trajectory_planner_ros.cpp:283-597): plan window, goal test on the window's last pose, the stop / rotate
 // candidates and the dispatch to the navgpu_tp_* core - plain host arithmetic in fp64; the grids, the rollout and the candidates' legality
 // run on the GPU through navgpu_tp_update_plans, navgpu_tp_find_best_path and navgpu_tp_score_trajectories.
-// Limitation shared with the DWA cycle: updatePlan + findBestPath run once per CONTIGUOUS run of robots that need them; a
-// robot that is at its goal, or has no window, splits the range into two runs.
+// updatePlan + findBestPath run ONCE per call for the robots that need them: through the range calls when those robots form one
+// contiguous run, else through navgpu_tp_update_plans_list / navgpu_tp_find_best_path_list - a robot that is at its goal, or has no
+// window, costs no launch.
 #include "navgpu_fleet.h"
 
 extern "C" {
@@ -148,37 +149,43 @@ int navgpu_tp_ros_compute_velocity_commands(navgpu_fleet* f, uint32_t first, uin
       }
     }
   }
-  // --- updatePlan(transformed_plan) + findBestPath (:443-444, :475-478) for every robot that is not at its goal, in contiguous runs
-  std::vector<navgpu_robot_state> states(count);
+  // --- updatePlan(transformed_plan) + findBestPath (:443-444, :475-478) for every robot that is not at its goal: one of each
   std::vector<navgpu_tp_result> res(count);
-  std::vector<double> packed;
-  std::vector<uint32_t> offsets;
-  for (uint32_t k = 0; k < count;) {
-    if (kind[k] != ROLLOUT && kind[k] != REACHED) {
-      ++k;
-      continue;
-    }
-    uint32_t e = k;
-    packed.clear();
-    offsets.assign(1, 0u);
-    while (e < count && (kind[e] == ROLLOUT || kind[e] == REACHED)) {
-      const std::vector<double>& t = f->tpr[first + e].transformed;
+  {
+    std::vector<uint32_t> ks, inst, offsets(1, 0u);  // the robots by position in the call / in the fleet
+    std::vector<navgpu_robot_state> states;
+    std::vector<double> packed;
+    for (uint32_t k = 0; k < count; ++k) {
+      if (kind[k] != ROLLOUT && kind[k] != REACHED) continue;
+      const std::vector<double>& t = f->tpr[first + k].transformed;
       for (size_t q = 0; q < t.size() / 3; ++q) {
         packed.push_back(t[3 * q]);
         packed.push_back(t[3 * q + 1]);
       }
       offsets.push_back((uint32_t)(packed.size() / 2));
+      navgpu_robot_state s{};
       for (int a = 0; a < 3; ++a) {  // Eigen::Vector3f pos / vel (trajectory_planner.cpp:911-912)
-        states[e].pos[a] = (float)in[e].pose[a];
-        states[e].vel[a] = (float)in[e].odom_vel[a];
+        s.pos[a] = (float)in[k].pose[a];
+        s.vel[a] = (float)in[k].odom_vel[a];
       }
-      ++e;
+      states.push_back(s);
+      ks.push_back(k);
+      inst.push_back(first + k);
     }
-    int rc = navgpu_tp_update_plans(f, first + k, e - k, packed.data(), offsets.data(), 0);
-    if (rc != NAVGPU_OK) return rc;
-    rc = navgpu_tp_find_best_path(f, first + k, e - k, &states[k], &res[k]);
-    if (rc != NAVGPU_OK) return rc;
-    k = e;
+    if (!ks.empty()) {
+      const uint32_t n = (uint32_t)ks.size();
+      std::vector<navgpu_tp_result> got(n);
+      int rc;
+      if (ks.back() - ks.front() + 1 == n) {  // one contiguous run: the range calls
+        rc = navgpu_tp_update_plans(f, inst[0], n, packed.data(), offsets.data(), 0);
+        if (rc == NAVGPU_OK) rc = navgpu_tp_find_best_path(f, inst[0], n, states.data(), got.data());
+      } else {
+        rc = navgpu_tp_update_plans_list(f, n, inst.data(), packed.data(), offsets.data(), 0);
+        if (rc == NAVGPU_OK) rc = navgpu_tp_find_best_path_list(f, n, inst.data(), states.data(), got.data());
+      }
+      if (rc != NAVGPU_OK) return rc;
+      for (uint32_t q = 0; q < n; ++q) res[ks[q]] = got[q];
+    }
   }
   // --- position reached (:447-464): the stop / rotate candidates, checked in ONE call against the grids findBestPath just made
   std::vector<uint32_t> chk_inst, chk_k, chk_off(1, 0u);
@@ -242,26 +249,17 @@ int navgpu_tp_ros_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const u
   if (!f->tpr_configured || !f->tp_configured) return NAVGPU_ERR_STATE;
   auto probed = [&](uint32_t k) { return in[k].have_pose && probe_offsets[k + 1] > probe_offsets[k]; };
   if (update_map) {  // updatePlan({pose}, true) (:531-539, :563-571): the planner's plan and final goal become the robot's pose
-    std::vector<double> xy;
-    std::vector<uint32_t> off;
-    for (uint32_t k = 0; k < n_robots;) {
-      if (!probed(k)) {
-        ++k;
-        continue;
-      }
-      uint32_t e = k;
-      xy.clear();
-      off.assign(1, 0u);
-      while (e < n_robots && probed(e) && instances[e] == instances[k] + (e - k)) {
-        xy.push_back(in[e].pose[0]);
-        xy.push_back(in[e].pose[1]);
-        off.push_back(e - k + 1);
-        ++e;
-      }
-      const int rc = navgpu_tp_update_plans(f, instances[k], e - k, xy.data(), off.data(), 1);
-      if (rc != NAVGPU_OK) return rc;
-      k = e;
+    std::vector<double> xy;   // one listed updatePlan for the probed robots, however they lie
+    std::vector<uint32_t> who, off(1, 0u);
+    for (uint32_t k = 0; k < n_robots; ++k) {
+      if (!probed(k)) continue;
+      who.push_back(instances[k]);
+      xy.push_back(in[k].pose[0]);
+      xy.push_back(in[k].pose[1]);
+      off.push_back((uint32_t)who.size());
     }
+    const int rc = navgpu_tp_update_plans_list(f, (uint32_t)who.size(), who.data(), xy.data(), off.data(), 1);
+    if (rc != NAVGPU_OK) return rc;
   }
   std::vector<uint32_t> inst, off(1, 0u), where;  // where: the caller's index of each probe sent
   std::vector<double> probes;

@@ -7,9 +7,10 @@ namespace navgpu {
 // k_free_bits: the traversable-cell bitmap of every robot's costmap, [ny][W] words, once per launch for the two or three
 // wavefronts of a robot (each reads its rows twice).  Read inside a sweep, the same 160 KB of cost bytes took 14 wide loads
 // per lane that the register budget of the sweep serialises: 16 us per read, against 7 dword loads now.
-__global__ __launch_bounds__(256) void k_free_bits(PlannerDev pl, uint32_t first) {
+template <class Robots>
+__global__ __launch_bounds__(256) void k_free_bits(PlannerDev pl, Robots robots) {
   const uint32_t W = (pl.nx + 31) >> 5, words = pl.ny * W;
-  const uint32_t inst = first + blockIdx.y;
+  const uint32_t inst = robots(blockIdx.y);
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= words) return;
   const uint32_t row = i / W, wi = i - row * W;
@@ -216,7 +217,7 @@ uint32_t bfs_cu_count() {
 void launch_bfs(const PlannerDev& pl_, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
   PlannerDev pl = pl_;
   if (!free_ready) {  // (a planner cycle has all three done by its k_samples launch)
-    hipLaunchKernelGGL(k_free_bits, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, first);
+    hipLaunchKernelGGL(k_free_bits<RobotRange>, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, RobotRange{first});
     hipMemsetAsync(pl.bfs_next_item, 0, 2 * sizeof(uint32_t), s);
     pl.bfs_seed_cap = 0;  // no seed lists either: the wavefronts walk the plans
   }
@@ -224,9 +225,16 @@ void launch_bfs(const PlannerDev& pl_, uint32_t first, uint32_t count, hipStream
   if (launch_bfs_rows2(pl, first, count, s, order)) return;
   hipLaunchKernelGGL(k_bfs_global<RobotRange>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, RobotRange{first}, pl.bfs_scratch);
 }
-// The wavefronts of a cycle for the robots list[0 .. count): the bitmaps and the zeroed work counters are k_samples' (the
-// free_ready form above), the scratch slots go by position in the launch as they do there.
-void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order) {
+// The wavefronts for the robots list[0 .. count), the scratch slots by position in the launch as above.  free_ready: the bitmaps
+// and the zeroed work counters are k_samples' (a planner cycle); else this launch makes them itself, as launch_bfs does - the
+// legacy planner's listed calls and the completion of bounded grids, which have no k_samples in front of them.
+void launch_bfs_list(const PlannerDev& pl_, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
+  PlannerDev pl = pl_;
+  if (!free_ready) {
+    hipLaunchKernelGGL(k_free_bits<RobotList>, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, RobotList{list});
+    hipMemsetAsync(pl.bfs_next_item, 0, 2 * sizeof(uint32_t), s);
+    pl.bfs_seed_cap = 0;  // no seed lists either: the wavefronts walk the plans
+  }
   if (launch_bfs_rows_list(pl, list, count, s, order)) return;
   if (launch_bfs_rows2_list(pl, list, count, s, order)) return;
   hipLaunchKernelGGL(k_bfs_global<RobotList>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, RobotList{list}, pl.bfs_scratch);

@@ -23,6 +23,7 @@ Method names follow the reference interfaces they front:
                         (costmap_2d/src/observation_buffer.cpp:111-251, plugins/obstacle_layer.cpp:252-338, 466-496)
   tp_update_plans / tp_score_trajectories  TrajectoryPlanner::updatePlan / scoreTrajectory for a range / a list of robots
                         (base_local_planner/src/trajectory_planner.cpp:474-531)
+  tp_update_plans_list / tp_find_best_path_list  updatePlan / findBestPath for a list of robots, one launch set however they lie
   tp_ros_*              TrajectoryPlannerROS::setPlan / computeVelocityCommands / checkTrajectory / isGoalReached for a fleet
                         (base_local_planner/src/trajectory_planner_ros.cpp:283-597)
   trajectory_cloud      DWAPlanner::findBestPath's trajectory_cloud (dwa_planner.cpp:318-348); sample_terms: the breakdown behind it
@@ -850,6 +851,35 @@ class Fleet:
         xy = np.ascontiguousarray(np.concatenate(plans) if plans else np.zeros((0, 2)))
         check(self.L.navgpu_tp_update_plans(self.h, first, len(plans), _ptr(xy) if len(xy) else None, _ptr(offsets), int(compute_dists)),
               "tp_update_plans")
+
+    def tp_update_plans_list(self, instances, plans_xy, compute_dists=False):
+        """tp_update_plans for a list of robots (strictly increasing indices), plans by list position: one packed upload, one wavefront
+        launch, however the robots lie in the fleet."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        plans = [np.ascontiguousarray(p, np.float64).reshape(-1, 2) for p in plans_xy]
+        if len(plans) != len(inst):
+            raise ValueError("one plan per listed robot")
+        offsets = np.zeros(len(plans) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(p) for p in plans])
+        xy = np.ascontiguousarray(np.concatenate(plans) if plans else np.zeros((0, 2)))
+        check(self.L.navgpu_tp_update_plans_list(self.h, len(inst), _ptr(inst) if len(inst) else None, _ptr(xy) if len(xy) else None,
+                                                 _ptr(offsets), int(compute_dists)), "tp_update_plans_list")
+
+    def tp_find_best_path_list(self, instances, pos, vel):
+        """tp_find_best_path for a list of robots (strictly increasing indices), pos / vel by list position -> list of TpResult."""
+        inst = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        pos = np.asarray(pos, np.float32).reshape(-1, 3)
+        vel = np.asarray(vel, np.float32).reshape(-1, 3)
+        if len(pos) != len(inst) or len(vel) != len(inst):
+            raise ValueError("one pose and one velocity per listed robot")
+        n = len(inst)
+        st = (N.RobotState * max(n, 1))()
+        for k in range(n):
+            st[k].pos[:] = [float(v) for v in pos[k]]
+            st[k].vel[:] = [float(v) for v in vel[k]]
+        out = (N.TpResult * max(n, 1))()
+        check(self.L.navgpu_tp_find_best_path_list(self.h, n, _ptr(inst) if n else None, st, out), "tp_find_best_path_list")
+        return list(out)[:n]
 
     @staticmethod
     def _probe_runs(instances, probes, offsets, width):

@@ -6,6 +6,7 @@ cells, against the same work done through the single entry points.
   plans   navgpu_tp_update_plans for 256 robots with compute_dists                        | 256 navgpu_tp_update_plan calls
   stop    navgpu_tp_ros_compute_velocity_commands, every robot on the stop branch         | by hand: window and navgpu_tp_update_plan per robot,
   drive   the same, every robot driving                                                   |   one navgpu_tp_find_best_path, a score call per stopping robot
+  mixed   the same call with no robot, every third and every second robot at its goal     | (none: compare with the commit before the listed calls)
 
 The right-hand column uses nothing but entry points the commit before this feature has: run the tool from a checkout of that commit as well
 (copy this file into its tools/; the left-hand legs are skipped there) and set the two JSON lines side by side - that is the yardstick, the
@@ -146,13 +147,36 @@ def leg_cycle(fl, poses, plans, stop, args, out):
         out[key]["commands_differ"] = int(sum(tuple(g.cmd_vel) != tuple(c) for g, c in zip(cycle.got, by_hand.cmds)))
 
 
+def leg_mixed(fl, poses, plans, args, out):
+    """navgpu_tp_ros_compute_velocity_commands with some robots at their goal (a plan that ends where they stand, heading as they do) and
+    the others driving: none (one contiguous run of driving robots), every third, every second (as many runs as there are driving
+    robots).  The commit before the listed calls ran updatePlan + findBestPath once per run."""
+    n = len(poses)
+    vels = np.tile((0.3, 0.0, 0.1), (n, 1))
+    s = np.arange(-1.0, 0.0001, 0.05)
+    at_goal = [np.ascontiguousarray(np.column_stack([p[0] + s, np.full_like(s, p[1]), np.zeros_like(s)])) for p in poses]
+    drive = [np.ascontiguousarray(p) for p in plans]
+    fl.configure_tp_ros(prune_plan=0)
+    out["mixed"] = {"robots": n}
+    for key, stands in (("goal_0", lambda k: False), ("goal_third", lambda k: k % 3 == 2), ("goal_alternating", lambda k: k % 2 == 1)):
+        fl.tp_ros_set_plans([at_goal[k] if stands(k) else drive[k] for k in range(n)])
+
+        def cycle():
+            cycle.got = fl.tp_ros_compute_velocity_commands(poses, vels)
+        ms = median_ms(cycle, args.steps, args.warmup)
+        runs = sum(1 for k in range(n) if not stands(k) and (k == 0 or stands(k - 1)))
+        out["mixed"][key] = {"fleet_call_wall_ms": ms, "runs": runs,
+                             "driving": int(sum(g.branch == N.BRANCH_ROLLOUT and g.ok == 1 for g in cycle.got)),
+                             "at_goal": int(sum(g.branch == N.BRANCH_AT_GOAL for g in cycle.got))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", type=int, default=256)
     ap.add_argument("--size", type=int, default=400)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--legs", default="probes,plans,stop,drive")
+    ap.add_argument("--legs", default="probes,plans,stop,drive,mixed")
     ap.add_argument("--lib", help="another build of the library")
     ap.add_argument("--ab", action="store_true", help="the probes leg of the shipped library and of libnavgpu_lpp.so (make tp-probe-ab)")
     args = ap.parse_args()
@@ -181,6 +205,8 @@ def main():
         leg_cycle(fl, poses, plans, True, args, out)
     if "drive" in legs:
         leg_cycle(fl, poses, plans, False, args, out)
+    if "mixed" in legs:
+        leg_mixed(fl, poses, plans, args, out)
     fl.close()
     print(json.dumps(out))
 
