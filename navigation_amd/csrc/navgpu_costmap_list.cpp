@@ -10,23 +10,23 @@ namespace navgpu {
 // the buffers of the listed calls, all or none
 int reserveCostmapList(navgpu_fleet* f) {
   navgpu_fleet::CostmapList& cl = f->cml;
-  if (cl.d_list) return NAVGPU_OK;
+  if (cl.list.d) return NAVGPU_OK;
   const uint32_t n = f->desc.n_instances;
   const size_t stage_bytes = (size_t)n * (sizeof(CmStageRec) + sizeof(double) * 2 * kMaxFootprint + sizeof(ObsCsr) * f->cm.max_obs +
                                           sizeof(float) * 3 * (size_t)f->cm.max_points);
   navgpu_fleet::CostmapList nl;
-  int rc = f->alloc(&nl.d_list, n);
+  int rc = f->alloc(&nl.list.d, n);
   if (!rc) rc = f->alloc(&nl.d_stage, stage_bytes);
-  if (!rc) rc = f->allocPinned(&nl.h_list, n);
+  if (!rc) rc = f->allocPinned(&nl.list.h, n);
   if (!rc) rc = f->allocPinned(&nl.h_stage, stage_bytes);
-  if (!rc && hipEventCreateWithFlags(&nl.ev_list, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
+  if (!rc && hipEventCreateWithFlags(&nl.list.ev, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
   if (!rc && hipEventCreateWithFlags(&nl.ev_stage, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
   if (rc) {
-    f->release(nl.d_list);
+    f->release(nl.list.d);
     f->release(nl.d_stage);
-    f->releasePinned(nl.h_list);
+    f->releasePinned(nl.list.h);
     f->releasePinned(nl.h_stage);
-    if (nl.ev_list) (void)hipEventDestroy(nl.ev_list);
+    if (nl.list.ev) (void)hipEventDestroy(nl.list.ev);
     if (nl.ev_stage) (void)hipEventDestroy(nl.ev_stage);
     return rc;
   }
@@ -152,13 +152,8 @@ int navgpu_costmap_update_list(navgpu_fleet* f, uint32_t n_robots, const uint32_
     return NAVGPU_ERR_STATE;
   int rc = reserveCostmapList(f);
   if (rc != NAVGPU_OK) return rc;
-  navgpu_fleet::CostmapList& cl = f->cml;
-  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));  // the pinned list may still feed the copy of the listed update before
-  memcpy(cl.h_list, instances, sizeof(uint32_t) * n_robots);
-  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n_robots, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
-  cl.ev_set = true;
-  const RobotList robots{cl.d_list};
+  if ((rc = f->cml.list.send(f, instances, n_robots)) != NAVGPU_OK) return rc;
+  const RobotList robots{f->cml.list.d};
   for (uint32_t k = 0; k < n_robots; ++k) f->touchInputs(instances[k], 1);
   applyPendingShiftList(f, n_robots, robots);
   PROFILED(f, NAVGPU_K_OBSTACLE, launch_obstacle(cm, robots, n_robots, nullptr, 0, f->stream));

@@ -71,11 +71,18 @@ void stagePoseMirrors(navgpu_fleet* f, const RobotSet& r, const double* poses);
 // behind it, the marker of two cycles in flight, and for a rolling window the pending shift of this list (navgpu_costmap_list.cpp)
 int reserveCostmapList(navgpu_fleet* f);
 int sendCostmapStageList(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, bool with_points);
-// navgpu_planner_stage_poses without its "a plan was staged" check: for robots whose plan is on the device and whose length and last
-// point the pinned mirrors hold (navgpu_host.cpp)
-int stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth);
-// the same for the robots instances[0 .. n_robots) of a valid list (navgpu_planner_stage_poses_list without its check)
-int stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth, const float* vel_xyth);
+// navgpu_planner_stage_poses(_list) without its "a plan was staged" check: for the robots of a range or a valid list whose plan is on
+// the device and whose length and last point the pinned mirrors hold; pos_xyth / vel_xyth [k] belong to robot r[k] (navgpu_host.cpp)
+int stagePoses(navgpu_fleet* f, const RobotSet& r, const float* pos_xyth, const float* vel_xyth);
+// The robot list a listed launch reads: the device array, its pinned source and the marker behind the last copy out of it.
+struct DeviceList {
+  uint32_t *d = nullptr, *h = nullptr;  // [n]
+  hipEvent_t ev = nullptr;              // behind the copy out of h
+  bool set = false;
+  hipError_t wait() { return set ? hipEventSynchronize(ev) : hipSuccess; }  // h may still feed the copy of the listed call before
+  // src[0 .. n) into d on the fleet's stream, through h.  src == h: the caller has waited and written the list in place.
+  int send(navgpu_fleet* f, const uint32_t* src, uint32_t n);
+};
 // device-resident global plans (navgpu_resident_plan.cpp), for the handover of navgpu_move_base.cpp: wait until the last adoption's
 // copies out of ResidentPlans::h_off have run; a robot's slot has just taken a new plan of len poses (DWAPlannerROS::setPlan's host side)
 int waitAdoption(navgpu_fleet* f);
@@ -132,6 +139,9 @@ struct navgpu_fleet {
   std::vector<uint64_t> inputs_gen, cycle_gen;  // [n] bumped by whatever a wavefront reads / value at the last cycle
   void touchInputs(uint32_t first, uint32_t count) {
     for (uint32_t i = first; i < first + count && i < inputs_gen.size(); ++i) ++inputs_gen[i];
+  }
+  void touchInputs(const RobotSet& r) {
+    for (uint32_t k = 0; k < r.count; ++k) ++inputs_gen[r[k]];
   }
   navgpu_robot_state* hp_state = nullptr;
   navgpu_plan_result* hp_result = nullptr;      // [2][n]: the slot a cycle writes alternates while two cycles are in flight
@@ -242,9 +252,7 @@ struct navgpu_fleet {
   // call: the list its kernels read, the packed upload (TpStageRec ...) as a pinned block and its device twin, grown on demand, the
   // packed results coming back and the second pass's winners
   struct TpList {
-    uint32_t *d_list = nullptr, *h_list = nullptr;   // [n]
-    hipEvent_t ev_list = nullptr;                    // behind the copy out of h_list
-    bool ev_set = false;
+    DeviceList list;
     uint8_t *d_stage = nullptr, *h_stage = nullptr;  // [stage_bytes]
     size_t stage_bytes = 0;
     TpOut *d_out = nullptr, *h_out = nullptr;        // [out_cap] results of the listed robots' samples, packed
@@ -332,17 +340,13 @@ struct navgpu_fleet {
   // the planner cycle for a robot list (navgpu_planner_*_list), allocated by the first listed call, sized for the whole fleet:
   // the list the cycle's kernels read, and navgpu_planner_stage_list's packed upload - a pinned block and its device twin
   struct CycleList {
-    uint32_t *d_list = nullptr, *h_list = nullptr;  // [n]
-    hipEvent_t ev_list = nullptr;                   // behind the copy out of h_list
-    bool ev_set = false;
+    DeviceList list;
     uint8_t *d_stage = nullptr, *h_stage = nullptr; // [n] StageRec, then [n][max_plan][2] doubles (only the poses in use travel)
   } cl;
   // the costmap update for a robot list (navgpu_costmap_*_list), allocated by the first listed call, sized for the whole fleet: the
   // list the update's kernels read, and the listed stages' packed upload - a pinned block and its device twin
   struct CostmapList {
-    uint32_t *d_list = nullptr, *h_list = nullptr;  // [n]
-    hipEvent_t ev_list = nullptr;                   // behind the copy out of h_list
-    bool ev_set = false;
+    DeviceList list;
     uint8_t *d_stage = nullptr, *h_stage = nullptr; // [n] CmStageRec, [n][kMaxFootprint][2] doubles, [n][max_obs] ObsCsr, [n][max_points][3] floats (only what is in use travels)
     hipEvent_t ev_stage = nullptr;                  // behind the copy out of h_stage
     bool ev_stage_set = false;
@@ -449,6 +453,17 @@ struct navgpu_fleet {
     return NAVGPU_OK;
   }
 };
+
+inline int navgpu::DeviceList::send(navgpu_fleet* f, const uint32_t* src, uint32_t n) {
+  if (src != h) {
+    HIP_TRY(wait());
+    memcpy(h, src, sizeof(uint32_t) * n);
+  }
+  HIP_TRY(hipMemcpyAsync(d, h, sizeof(uint32_t) * n, hipMemcpyHostToDevice, f->stream));
+  HIP_TRY(hipEventRecord(ev, f->stream));
+  set = true;
+  return NAVGPU_OK;
+}
 
 // lock + "this thread talks to the fleet's GPU" (hipSetDevice is per host thread: a caller's second thread starts on
 // device 0 whatever device the fleet lives on)

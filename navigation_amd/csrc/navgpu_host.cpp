@@ -286,7 +286,7 @@ int navgpu_fleet_destroy(navgpu_fleet* f) {
     hipEventDestroy(e.a);
     hipEventDestroy(e.b);
   }
-  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.ev_list, f->cml.ev_list, f->cml.ev_stage, f->tpl.ev_list})
+  for (hipEvent_t e : {f->ev_cycle[0], f->ev_cycle[1], f->ev_cm_h2d, f->ev_pl_h2d, f->ob.ev_h2d, f->rp.ev_fleet, f->rp.ev_nav, f->cl.list.ev, f->cml.list.ev, f->cml.ev_stage, f->tpl.list.ev})
     if (e) hipEventDestroy(e);
   for (void* p : f->allocs) hipFree(p);
   for (void* p : f->pinned) hipHostFree(p);
@@ -1168,21 +1168,19 @@ extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, const RobotSet& r)
   int rc = reserveCycleList(f);
   if (rc != NAVGPU_OK) return rc;
   // the partial robots of the set as one list (increasing, as the set is), through the listed cycle's buffers
-  navgpu_fleet::CycleList& cl = f->cl;
-  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));  // the pinned list may still feed the copy of a listed launch before
+  DeviceList& list = f->cl.list;
+  HIP_TRY(list.wait());
   uint32_t n = 0;
   for (uint32_t k = 0; k < r.count; ++k)
     if (f->grid_partial[r[k]]) {
       f->grid_partial[r[k]] = 0;
-      cl.h_list[n++] = r[k];
+      list.h[n++] = r[k];
     }
-  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
-  cl.ev_set = true;
+  if ((rc = list.send(f, list.h, n)) != NAVGPU_OK) return rc;
   PlannerDev pl = f->pl;
   pl.bfs_bounded = 0;
   pl.bfs_seed_cap = 0;  // (no k_samples in front of this launch: the lists are some earlier cycle's)
-  PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n, f->stream, nullptr, false));
+  PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, list.d, n, f->stream, nullptr, false));
   return checkLaunch();
 }
 extern "C++" int navgpu::ensureCompleteGrids(navgpu_fleet* f, uint32_t first, uint32_t count) {
@@ -1530,15 +1528,10 @@ static int checkStageStates(const PlannerDev& pl, uint32_t count, const navgpu_r
   }
   return NAVGPU_OK;
 }
-// robot i's pinned mirrors from its staged state and plan
-static void stageMirrors(navgpu_fleet* f, uint32_t i, const navgpu_robot_state& s, const double* plan_xy) {
-  const PlannerDev& pl = f->pl;
-  const navgpu_dwa_config& c = pl.cfg;
-  f->hp_state[i] = s;
-  memcpy(&f->hp_plan[(size_t)i * pl.max_plan * 2], plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
-  f->hp_plan_cnt[i] = s.plan_count;
-  // DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285); pos is the float-narrowed pose
-  const double gx = plan_xy[((size_t)s.plan_first + s.plan_count - 1) * 2], gy = plan_xy[((size_t)s.plan_first + s.plan_count - 1) * 2 + 1];
+// DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285) for robot i: nose goal, alignment switch and wavefront reach from
+// its state (pos is the float-narrowed pose) and the last point of its plan
+static void noseGoal(navgpu_fleet* f, uint32_t i, const navgpu_robot_state& s, double gx, double gy) {
+  const navgpu_dwa_config& c = f->pl.cfg;
   const double sq_dist = (s.pos[0] - gx) * (s.pos[0] - gx) + (s.pos[1] - gy) * (s.pos[1] - gy);
   const double angle_to_goal = atan2(gy - s.pos[1], gx - s.pos[0]);
   f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
@@ -1546,55 +1539,33 @@ static void stageMirrors(navgpu_fleet* f, uint32_t i, const navgpu_robot_state& 
   f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
   f->hp_reach[i] = bfsReachCells(f, i, s, gx, gy);
 }
-
-int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, const double* plan_xy,
-                         uint32_t n_plan_total) {
-  if (!f || !states || !plan_xy || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
-  if (!f->planner_configured) return NAVGPU_ERR_STATE;
-  PlannerDev& pl = f->pl;
-  int rc = checkStageStates(pl, count, states, n_plan_total);
-  if (rc != NAVGPU_OK) return rc;
-  HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));  // the pinned mirrors may still feed an earlier copy
-  if ((rc = flushLimits(f, RobotSet{first, count, nullptr})) != NAVGPU_OK) return rc;
-  for (uint32_t li = 0; li < count; ++li) stageMirrors(f, first + li, states[li], plan_xy);
-  f->touchInputs(first, count);
-  if (first == 0 && count == f->desc.n_instances) {  // the whole fleet: one copy of the block
-    HIP_TRY(hipMemcpyAsync(f->pl_stage_dev, f->pl_stage_host, f->pl_stage_bytes, hipMemcpyHostToDevice, f->stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(pl.state + first, f->hp_state + first, sizeof(navgpu_robot_state) * count, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(hipMemcpyAsync(pl.plan + (size_t)first * pl.max_plan * 2, f->hp_plan + (size_t)first * pl.max_plan * 2, sizeof(double) * 2 * (size_t)count * pl.max_plan, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(hipMemcpyAsync(pl.plan_count + first, f->hp_plan_cnt + first, sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(hipMemcpyAsync(pl.front_last + (size_t)first * 2, f->hp_front + (size_t)first * 2, sizeof(double) * 2 * count, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(hipMemcpyAsync(pl.align_on + first, f->hp_align + first, sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
-    HIP_TRY(hipMemcpyAsync(pl.bfs_reach + first, f->hp_reach + first, sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
-  }
-  if (f->cycles_in_flight > 1) {
-    HIP_TRY(hipEventRecord(f->ev_pl_h2d, f->stream));
-    f->ev_pl_set = true;
-  }
-  f->planner_staged = true;
-  f->hp_dma_pending = true;
-  return NAVGPU_OK;
+// robot i's pinned mirrors from its staged state and plan
+static void stageMirrors(navgpu_fleet* f, uint32_t i, const navgpu_robot_state& s, const double* plan_xy) {
+  const PlannerDev& pl = f->pl;
+  f->hp_state[i] = s;
+  memcpy(&f->hp_plan[(size_t)i * pl.max_plan * 2], plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
+  f->hp_plan_cnt[i] = s.plan_count;
+  const double* last = plan_xy + ((size_t)s.plan_first + s.plan_count - 1) * 2;
+  noseGoal(f, i, s, last[0], last[1]);
 }
 
-// ---- the cycle for a robot list: instances[0 .. n_robots) strictly increasing, each < n_instances (listOk)
-// the buffers of the listed calls, all or none
+// ---- the calls for a robot list: instances[0 .. n_robots) strictly increasing, each < n_instances (listOk)
+// the buffers of the planner's listed calls, all or none
 static int reserveCycleList(navgpu_fleet* f) {
   navgpu_fleet::CycleList& cl = f->cl;
-  if (cl.d_list) return NAVGPU_OK;
+  if (cl.list.d) return NAVGPU_OK;
   const uint32_t n = f->desc.n_instances;
   const size_t stage_bytes = (size_t)n * (sizeof(StageRec) + sizeof(double) * 2 * f->pl.max_plan);
   navgpu_fleet::CycleList nl;
-  int rc = f->alloc(&nl.d_list, n);
+  int rc = f->alloc(&nl.list.d, n);
   if (!rc) rc = f->alloc(&nl.d_stage, stage_bytes);
-  if (!rc) rc = f->allocPinned(&nl.h_list, n);
+  if (!rc) rc = f->allocPinned(&nl.list.h, n);
   if (!rc) rc = f->allocPinned(&nl.h_stage, stage_bytes);
-  if (!rc && hipEventCreateWithFlags(&nl.ev_list, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
+  if (!rc && hipEventCreateWithFlags(&nl.list.ev, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
   if (rc) {
-    f->release(nl.d_list);
+    f->release(nl.list.d);
     f->release(nl.d_stage);
-    f->releasePinned(nl.h_list);
+    f->releasePinned(nl.list.h);
     f->releasePinned(nl.h_stage);
     return rc;
   }
@@ -1602,41 +1573,67 @@ static int reserveCycleList(navgpu_fleet* f) {
   return NAVGPU_OK;
 }
 
-int navgpu_planner_stage_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_state* states,
-                              const double* plan_xy, uint32_t n_plan_total) {
-  if (!f || !states || !plan_xy || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
-  if (!f->planner_configured || !launch_stage_scatter) return NAVGPU_ERR_STATE;
+// navgpu_planner_stage and navgpu_planner_stage_list behind their argument checks: states[k] belongs to robot r[k].  The two differ in how
+// the mirrors travel: a range in block copies out of them, a list as the packed block of its robots with k_stage_scatter behind it.
+static int stagePlans(navgpu_fleet* f, const RobotSet& r, const navgpu_robot_state* states, const double* plan_xy, uint32_t n_plan_total) {
+  if (!f->planner_configured || (r.list && !launch_stage_scatter)) return NAVGPU_ERR_STATE;
   PlannerDev& pl = f->pl;
-  int rc = checkStageStates(pl, n_robots, states, n_plan_total);
-  if (rc == NAVGPU_OK) rc = reserveCycleList(f);
+  int rc = checkStageStates(pl, r.count, states, n_plan_total);
+  if (rc == NAVGPU_OK && r.list) rc = reserveCycleList(f);
   if (rc != NAVGPU_OK) return rc;
-  // the pinned mirrors may still feed an earlier copy, and so may the packed block (the marker of two cycles in flight is recorded
+  // the pinned mirrors may still feed an earlier copy, and so may a list's packed block (the marker of two cycles in flight is recorded
   // behind its copy as well)
   HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
-  if ((rc = flushLimits(f, RobotSet{0, n_robots, instances})) != NAVGPU_OK) return rc;
-  StageRec* rec = reinterpret_cast<StageRec*>(f->cl.h_stage);
-  double* poses = reinterpret_cast<double*>(f->cl.h_stage + sizeof(StageRec) * n_robots);
-  uint32_t n_poses = 0;
-  for (uint32_t k = 0; k < n_robots; ++k) {
-    const uint32_t i = instances[k];
-    const navgpu_robot_state& s = states[k];
-    stageMirrors(f, i, s, plan_xy);
-    f->touchInputs(i, 1);
-    rec[k] = StageRec{s, {f->hp_front[2 * i], f->hp_front[2 * i + 1]}, f->hp_align[i], f->hp_reach[i], i, n_poses};
-    memcpy(poses + 2 * (size_t)n_poses, plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
-    n_poses += s.plan_count;  // (<= n_instances * max_plan: the block holds them)
+  if ((rc = flushLimits(f, r)) != NAVGPU_OK) return rc;
+  for (uint32_t k = 0; k < r.count; ++k) stageMirrors(f, r[k], states[k], plan_xy);
+  f->touchInputs(r);
+  if (r.list) {
+    StageRec* rec = reinterpret_cast<StageRec*>(f->cl.h_stage);
+    double* poses = reinterpret_cast<double*>(f->cl.h_stage + sizeof(StageRec) * r.count);
+    uint32_t n_poses = 0;
+    for (uint32_t k = 0; k < r.count; ++k) {
+      const uint32_t i = r[k];
+      const navgpu_robot_state& s = states[k];
+      rec[k] = StageRec{s, {f->hp_front[2 * i], f->hp_front[2 * i + 1]}, f->hp_align[i], f->hp_reach[i], i, n_poses};
+      memcpy(poses + 2 * (size_t)n_poses, plan_xy + (size_t)s.plan_first * 2, sizeof(double) * 2 * s.plan_count);
+      n_poses += s.plan_count;  // (<= n_instances * max_plan: the block holds them)
+    }
+    const size_t bytes = sizeof(StageRec) * r.count + sizeof(double) * 2 * (size_t)n_poses;
+    HIP_TRY(hipMemcpyAsync(f->cl.d_stage, f->cl.h_stage, bytes, hipMemcpyHostToDevice, f->stream));
+    launch_stage_scatter(pl, reinterpret_cast<const StageRec*>(f->cl.d_stage), reinterpret_cast<const double*>(f->cl.d_stage + sizeof(StageRec) * r.count),
+                         r.count, f->stream);
+  } else {
+    const uint32_t first = r.first, count = r.count;
+    if (first == 0 && count == f->desc.n_instances) {  // the whole fleet: one copy of the block
+      HIP_TRY(hipMemcpyAsync(f->pl_stage_dev, f->pl_stage_host, f->pl_stage_bytes, hipMemcpyHostToDevice, f->stream));
+    } else {
+      HIP_TRY(hipMemcpyAsync(pl.state + first, f->hp_state + first, sizeof(navgpu_robot_state) * count, hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipMemcpyAsync(pl.plan + (size_t)first * pl.max_plan * 2, f->hp_plan + (size_t)first * pl.max_plan * 2, sizeof(double) * 2 * (size_t)count * pl.max_plan, hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipMemcpyAsync(pl.plan_count + first, f->hp_plan_cnt + first, sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipMemcpyAsync(pl.front_last + (size_t)first * 2, f->hp_front + (size_t)first * 2, sizeof(double) * 2 * count, hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipMemcpyAsync(pl.align_on + first, f->hp_align + first, sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
+      HIP_TRY(hipMemcpyAsync(pl.bfs_reach + first, f->hp_reach + first, sizeof(uint32_t) * count, hipMemcpyHostToDevice, f->stream));
+    }
+    f->hp_dma_pending = true;
   }
-  const size_t bytes = sizeof(StageRec) * n_robots + sizeof(double) * 2 * (size_t)n_poses;
-  HIP_TRY(hipMemcpyAsync(f->cl.d_stage, f->cl.h_stage, bytes, hipMemcpyHostToDevice, f->stream));
-  launch_stage_scatter(pl, reinterpret_cast<const StageRec*>(f->cl.d_stage), reinterpret_cast<const double*>(f->cl.d_stage + sizeof(StageRec) * n_robots),
-                       n_robots, f->stream);
   if (f->cycles_in_flight > 1) {
     HIP_TRY(hipEventRecord(f->ev_pl_h2d, f->stream));
     f->ev_pl_set = true;
   }
   f->planner_staged = true;
-  return checkLaunch();
+  return r.list ? checkLaunch() : NAVGPU_OK;  // (only a list has launched anything)
+}
+int navgpu_planner_stage(navgpu_fleet* f, uint32_t first, uint32_t count, const navgpu_robot_state* states, const double* plan_xy,
+                         uint32_t n_plan_total) {
+  if (!f || !states || !plan_xy || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  return stagePlans(f, RobotSet{first, count, nullptr}, states, plan_xy, n_plan_total);
+}
+int navgpu_planner_stage_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const navgpu_robot_state* states,
+                              const double* plan_xy, uint32_t n_plan_total) {
+  if (!f || !states || !plan_xy || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  return stagePlans(f, RobotSet{0, n_robots, instances}, states, plan_xy, n_plan_total);
 }
 
 // A control cycle whose plan has not changed (the plan arrives at ~1 Hz, the pose at controller_frequency): only pose and
@@ -1647,79 +1644,34 @@ int navgpu_planner_stage_poses(navgpu_fleet* f, uint32_t first, uint32_t count, 
   if (!f || !pos_xyth || !vel_xyth || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   if (!f->planner_configured || !f->planner_staged) return NAVGPU_ERR_STATE;
-  return stagePosesFromMirrors(f, first, count, pos_xyth, vel_xyth);
-}
-// The body of navgpu_planner_stage_poses, also what the control cycle runs for robots whose window k_plan_window has just left on the
-// device.  Precondition, checked here: every robot of the range has a plan on the device whose length and last point the pinned
-// mirrors (hp_plan_cnt, hp_plan) hold - after navgpu_planner_stage, or written from k_plan_window's records.
-// robot i's pinned mirrors from a new pose and velocity and the last point of its resident plan
-static void poseMirrors(navgpu_fleet* f, uint32_t i, const float pos[3], const float vel[3]) {
-  const PlannerDev& pl = f->pl;
-  const navgpu_dwa_config& c = pl.cfg;
-  navgpu_robot_state& s = f->hp_state[i];
-  for (int k = 0; k < 3; ++k) {
-    s.pos[k] = pos[k];
-    s.vel[k] = vel[k];
-  }
-  const double* last = &f->hp_plan[((size_t)i * pl.max_plan + f->hp_plan_cnt[i] - 1) * 2];
-  const double gx = last[0], gy = last[1];
-  // DWAPlanner::updatePlanAndLocalCosts (dwa_planner.cpp:254-285), as in navgpu_planner_stage
-  const double sq_dist = (s.pos[0] - gx) * (s.pos[0] - gx) + (s.pos[1] - gy) * (s.pos[1] - gy);
-  const double angle_to_goal = atan2(gy - s.pos[1], gx - s.pos[0]);
-  f->hp_front[2 * i] = gx + c.forward_point_distance * cos(angle_to_goal);
-  f->hp_front[2 * i + 1] = gy + c.forward_point_distance * sin(angle_to_goal);
-  f->hp_align[i] = sq_dist > c.forward_point_distance * c.forward_point_distance * c.cheat_factor ? 1 : 0;
-  f->hp_reach[i] = bfsReachCells(f, i, s, gx, gy);
-}
-extern "C++" int navgpu::stagePosesFromMirrors(navgpu_fleet* f, uint32_t first, uint32_t count, const float* pos_xyth, const float* vel_xyth) {
-  if (!f->planner_configured) return NAVGPU_ERR_STATE;
-  PlannerDev& pl = f->pl;
-  for (uint32_t i = first; i < first + count; ++i)
-    if (!f->hp_plan_cnt[i]) {
-      g_last_error = "navgpu_planner_stage_poses: instance " + std::to_string(i) + " has no staged plan";
-      return NAVGPU_ERR_STATE;
-    }
-  if (f->hp_dma_pending) {  // the host mirrors written below may still feed a full stage's copies
-    HIP_TRY(f->waitMirrors(f->ev_pl_h2d, f->ev_pl_set));
-    f->hp_dma_pending = false;
-  }
-  {
-    int rc = flushLimits(f, RobotSet{first, count, nullptr});
-    if (rc != NAVGPU_OK) return rc;
-  }
-  for (uint32_t li = 0; li < count; ++li) poseMirrors(f, first + li, pos_xyth + 3 * (size_t)li, vel_xyth + 3 * (size_t)li);
-  f->touchInputs(first, count);
-  PoseChunk ch;
-  ch.state = pl.state;
-  ch.front_last = pl.front_last;
-  ch.align_on = pl.align_on;
-  ch.bfs_reach = pl.bfs_reach;
-  for (uint32_t at = 0; at < count; at += kPoseChunk) {
-    ch.first = first + at;
-    ch.count = std::min(kPoseChunk, count - at);
-    memcpy(ch.st, f->hp_state + ch.first, sizeof(navgpu_robot_state) * ch.count);
-    memcpy(ch.front, f->hp_front + (size_t)ch.first * 2, sizeof(double) * 2 * ch.count);
-    memcpy(ch.align, f->hp_align + ch.first, sizeof(int32_t) * ch.count);
-    memcpy(ch.reach, f->hp_reach + ch.first, sizeof(uint32_t) * ch.count);
-    launch_stage_poses(ch, f->stream);
-  }
-  f->planner_staged = true;  // (the device holds a staged state for these robots, however their windows got there)
-  return checkLaunch();
+  return stagePoses(f, RobotSet{first, count, nullptr}, pos_xyth, vel_xyth);
 }
 int navgpu_planner_stage_poses_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth, const float* vel_xyth) {
   if (!f || !pos_xyth || !vel_xyth || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
   if (!f->planner_configured || !f->planner_staged) return NAVGPU_ERR_STATE;
-  return stagePosesListFromMirrors(f, n_robots, instances, pos_xyth, vel_xyth);
+  return stagePoses(f, RobotSet{0, n_robots, instances}, pos_xyth, vel_xyth);
 }
-// stagePosesFromMirrors for a list: the same precondition per listed robot, a chunk entry names its robot
-extern "C++" int navgpu::stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const float* pos_xyth,
-                                                   const float* vel_xyth) {
-  if (!f->planner_configured || !launch_stage_poses_list) return NAVGPU_ERR_STATE;
+// robot i's pinned mirrors from a new pose and velocity and the last point of its resident plan
+static void poseMirrors(navgpu_fleet* f, uint32_t i, const float pos[3], const float vel[3]) {
+  navgpu_robot_state& s = f->hp_state[i];
+  for (int k = 0; k < 3; ++k) {
+    s.pos[k] = pos[k];
+    s.vel[k] = vel[k];
+  }
+  const double* last = &f->hp_plan[((size_t)i * f->pl.max_plan + f->hp_plan_cnt[i] - 1) * 2];
+  noseGoal(f, i, s, last[0], last[1]);
+}
+// The body of both calls, also what the control cycle runs for robots whose window k_plan_window has just left on the device.
+// Precondition, checked here: every robot of the set has a plan on the device whose length and last point the pinned mirrors
+// (hp_plan_cnt, hp_plan) hold - after navgpu_planner_stage, or written from k_plan_window's records.  A chunk of a range says where
+// it starts and is filled in block copies; a chunk of a list names the robot of every entry.
+extern "C++" int navgpu::stagePoses(navgpu_fleet* f, const RobotSet& r, const float* pos_xyth, const float* vel_xyth) {
+  if (!f->planner_configured || (r.list && !launch_stage_poses_list)) return NAVGPU_ERR_STATE;
   PlannerDev& pl = f->pl;
-  for (uint32_t k = 0; k < n_robots; ++k)
-    if (!f->hp_plan_cnt[instances[k]]) {
-      g_last_error = "navgpu_planner_stage_poses_list: instance " + std::to_string(instances[k]) + " has no staged plan";
+  for (uint32_t k = 0; k < r.count; ++k)
+    if (!f->hp_plan_cnt[r[k]]) {
+      g_last_error = "navgpu_planner_stage_poses: instance " + std::to_string(r[k]) + " has no staged plan";
       return NAVGPU_ERR_STATE;
     }
   if (f->hp_dma_pending) {  // the host mirrors written below may still feed a full stage's copies
@@ -1727,21 +1679,29 @@ extern "C++" int navgpu::stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_r
     f->hp_dma_pending = false;
   }
   {
-    int rc = flushLimits(f, RobotSet{0, n_robots, instances});
+    int rc = flushLimits(f, r);
     if (rc != NAVGPU_OK) return rc;
   }
-  PoseChunkList ch;
+  for (uint32_t k = 0; k < r.count; ++k) poseMirrors(f, r[k], pos_xyth + 3 * (size_t)k, vel_xyth + 3 * (size_t)k);
+  f->touchInputs(r);
+  PoseChunkList ch;  // (a range launch takes its PoseChunk)
   ch.state = pl.state;
   ch.front_last = pl.front_last;
   ch.align_on = pl.align_on;
   ch.bfs_reach = pl.bfs_reach;
-  ch.first = 0;
-  for (uint32_t at = 0; at < n_robots; at += kPoseChunk) {
-    ch.count = std::min(kPoseChunk, n_robots - at);
+  for (uint32_t at = 0; at < r.count; at += kPoseChunk) {
+    ch.first = r.list ? 0 : r.first + at;
+    ch.count = std::min(kPoseChunk, r.count - at);
+    if (!r.list) {
+      memcpy(ch.st, f->hp_state + ch.first, sizeof(navgpu_robot_state) * ch.count);
+      memcpy(ch.front, f->hp_front + (size_t)ch.first * 2, sizeof(double) * 2 * ch.count);
+      memcpy(ch.align, f->hp_align + ch.first, sizeof(int32_t) * ch.count);
+      memcpy(ch.reach, f->hp_reach + ch.first, sizeof(uint32_t) * ch.count);
+      launch_stage_poses(ch, f->stream);
+      continue;
+    }
     for (uint32_t q = 0; q < ch.count; ++q) {
-      const uint32_t i = instances[at + q];
-      poseMirrors(f, i, pos_xyth + 3 * (size_t)(at + q), vel_xyth + 3 * (size_t)(at + q));
-      f->touchInputs(i, 1);
+      const uint32_t i = r.list[at + q];
       ch.inst[q] = i;
       ch.st[q] = f->hp_state[i];
       ch.front[2 * q] = f->hp_front[2 * i];
@@ -1751,7 +1711,7 @@ extern "C++" int navgpu::stagePosesListFromMirrors(navgpu_fleet* f, uint32_t n_r
     }
     launch_stage_poses_list(ch, f->stream);
   }
-  f->planner_staged = true;
+  f->planner_staged = true;  // (the device holds a staged state for these robots, however their windows got there)
   return checkLaunch();
 }
 
@@ -1784,23 +1744,35 @@ extern "C" int navgpu_debug_prep_image(navgpu_fleet* f, uint32_t inst, uint8_t* 
   return 0;
 }
 #endif
-int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
-  if (!f || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
-  FleetGuard guard_(f);
+// navgpu_planner_cycle and navgpu_planner_cycle_list behind their argument checks: the same six launches, each once, a list in device
+// memory where a range passes `first`.  With two cycles in flight only the whole fleet cycles: anything else would write into the
+// result slot the cycle before may still be filling.
+static int plannerCycle(navgpu_fleet* f, const RobotSet& r) {
   if (!f->planner_configured || !f->planner_staged) return NAVGPU_ERR_STATE;
+  if (f->cycles_in_flight > 1 && (r.list || r.first != 0 || r.count != f->desc.n_instances)) return NAVGPU_ERR_STATE;
   PlannerDev& pl = f->pl;
-  const int prev_slot = f->res_slot;
-  if (f->cycles_in_flight > 1) {  // the cycle before this one may still run: its results stay where they are
-    if (first != 0 || count != f->desc.n_instances) return NAVGPU_ERR_STATE;
-    pl.result = f->hp_result + (size_t)(prev_slot ^ 1) * f->desc.n_instances;  // (the slot flips once the launches are out)
+  const uint32_t* d_list = nullptr;
+  if (r.list) {
+    if (!launch_samples_list || !launch_bfs_list || !launch_score_list || !launch_select_list) return NAVGPU_ERR_STATE;
+    int rc = reserveCycleList(f);
+    if (rc == NAVGPU_OK) rc = f->cl.list.send(f, r.list, r.count);
+    if (rc != NAVGPU_OK) return rc;
+    d_list = f->cl.list.d;
   }
+  const int prev_slot = f->res_slot;
+  if (f->cycles_in_flight > 1)  // the cycle before this one may still run: its results stay where they are
+    pl.result = f->hp_result + (size_t)(prev_slot ^ 1) * f->desc.n_instances;  // (the slot flips once the launches are out)
   pl.bfs_bounded = 1;  // per robot: bfs_reach (0 = whole grid)
   pl.bfs_seed_cap = seedListCap(f);
-  for (uint32_t i = first; i < first + count; ++i) {
+  for (uint32_t k = 0; k < r.count; ++k) {
+    const uint32_t i = r[k];
     f->grid_partial[i] = robotBox(f, i, f->hp_state[i].pos, f->hp_reach[i], &f->h_box[(size_t)4 * i]) ? 1 : 0;
     f->cycle_gen[i] = f->inputs_gen[i];
   }
-  launch_samples(pl, first, count, f->stream);
+  if (r.list)
+    launch_samples_list(pl, d_list, r.count, f->stream);
+  else
+    launch_samples(pl, r.first, r.count, f->stream);
 #ifdef NAVGPU_DEBUG_SWITCHES  // tool builds only (tools/trace_bfs.py): per-item phase stamps of the wavefront launch, written to the named file
   if (getenv("NAVGPU_DEBUG_BFS_TRACE") && !pl.bfs_trace) f->alloc(&pl.bfs_trace, (size_t)f->desc.n_instances * 3 * 8);
 #endif
@@ -1808,17 +1780,19 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
   // launches complete them.  One image buffer serves two cycles in flight: this launch is behind the k_select of the cycle before on
   // the fleet's stream, and that cycle's k_score_sweep and terms pass, the only readers of its images, come before its k_select.
   const bool split = splitPrep(f);
+  // (a list's dispatch order sits where the range cycle of its first robot would put it: count <= n_instances - r[0])
+  const uint32_t* order = pl.bfs_order + (size_t)r[0] * 3;
   if (split)
-    PROFILED(f, NAVGPU_K_BFS, launch_bfs_prep(pl, first, count, f->stream, pl.bfs_order + (size_t)first * 3));
+    PROFILED(f, NAVGPU_K_BFS, r.list ? launch_bfs_prep_list(pl, d_list, r.count, f->stream, order) : launch_bfs_prep(pl, r.first, r.count, f->stream, order));
   else
-    PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, first, count, f->stream, pl.bfs_order + (size_t)first * 3, true));
+    PROFILED(f, NAVGPU_K_BFS, r.list ? launch_bfs_list(pl, d_list, r.count, f->stream, order, true) : launch_bfs(pl, r.first, r.count, f->stream, order, true));
 #ifdef NAVGPU_DEBUG_SWITCHES
   if (pl.bfs_trace) {
-    std::vector<unsigned long long> h((size_t)count * 24);
+    std::vector<unsigned long long> h((size_t)r.count * 24);
     hipMemcpyAsync(h.data(), pl.bfs_trace, h.size() * 8, hipMemcpyDeviceToHost, f->stream);
     waitStream(f->stream);
     if (FILE* fp = fopen(getenv("NAVGPU_DEBUG_BFS_TRACE"), "w")) {
-      for (size_t i = 0; i < (size_t)count * 3; ++i)
+      for (size_t i = 0; i < (size_t)r.count * 3; ++i)
         fprintf(fp, "%zu %llu %llu %llu %llu %llu %llu %llu %llu\n", i, h[8 * i], h[8 * i + 1] & 0xFFFFFFFFFFFFull, h[8 * i + 1] >> 48, h[8 * i + 2], h[8 * i + 3], h[8 * i + 4], h[8 * i + 5], h[8 * i + 6]);
       fclose(fp);
     }
@@ -1826,14 +1800,18 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
 #endif
   uint32_t n_blocks = 0;
   if (split)
-    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_grids(pl, first, count, f->stream));
+    PROFILED(f, NAVGPU_K_SCORE, n_blocks = r.list ? launch_score_grids_list(pl, d_list, r.count, f->stream) : launch_score_grids(pl, r.first, r.count, f->stream));
   else
-    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score(pl, first, count, nullptr, f->stream));
+    PROFILED(f, NAVGPU_K_SCORE, n_blocks = r.list ? launch_score_list(pl, d_list, r.count, f->stream) : launch_score(pl, r.first, r.count, nullptr, f->stream));
+  // publish_traj_pc robots: their terms, under the oscillation flags the scorer saw (k_select updates them).  The pass takes a range:
+  // once per contiguous run of the set
   int rc_terms = NAVGPU_OK;
-  if (!f->tc.robots.empty()) {  // publish_traj_pc robots: their terms, under the oscillation flags the scorer saw (k_select updates them)
-    rc_terms = f->tc.terms_pass(f, first, count);
-  }
-  PROFILED(f, NAVGPU_K_SELECT, launch_select(pl, first, count, n_blocks, f->stream));
+  if (!f->tc.robots.empty())
+    for (uint32_t k = 0, e; k < r.count && rc_terms == NAVGPU_OK; k = e) {
+      for (e = k + 1; e < r.count && r[e] == r[e - 1] + 1;) ++e;
+      rc_terms = f->tc.terms_pass(f, r[k], e - k);
+    }
+  PROFILED(f, NAVGPU_K_SELECT, r.list ? launch_select_list(pl, d_list, r.count, n_blocks, f->stream) : launch_select(pl, r.first, r.count, n_blocks, f->stream));
   int rc = checkLaunch();
   if (rc == NAVGPU_OK) rc = rc_terms;  // (the cycle itself is complete either way)
   if (f->cycles_in_flight > 1) {
@@ -1848,54 +1826,15 @@ int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
   }
   return rc;
 }
-
-// navgpu_planner_cycle for a robot list: the same launches, each once, with the list in device memory where the range form
-// passes `first`.  One cycle in flight only (a listed cycle writes into the result slot the range cycles of that mode use).
+int navgpu_planner_cycle(navgpu_fleet* f, uint32_t first, uint32_t count) {
+  if (!f || !f->rangeOk(first, count)) return NAVGPU_ERR_INVALID;
+  FleetGuard guard_(f);
+  return plannerCycle(f, RobotSet{first, count, nullptr});
+}
 int navgpu_planner_cycle_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances) {
   if (!f || !listOk(f, n_robots, instances)) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
-  if (!f->planner_configured || !f->planner_staged || f->cycles_in_flight > 1) return NAVGPU_ERR_STATE;
-  if (!launch_samples_list || !launch_bfs_list || !launch_score_list || !launch_select_list) return NAVGPU_ERR_STATE;
-  int rc = reserveCycleList(f);
-  if (rc != NAVGPU_OK) return rc;
-  PlannerDev& pl = f->pl;
-  navgpu_fleet::CycleList& cl = f->cl;
-  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));  // the pinned list may still feed the copy of the listed cycle before
-  memcpy(cl.h_list, instances, sizeof(uint32_t) * n_robots);
-  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n_robots, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
-  cl.ev_set = true;
-  pl.bfs_bounded = 1;  // per robot: bfs_reach (0 = whole grid)
-  pl.bfs_seed_cap = seedListCap(f);
-  for (uint32_t k = 0; k < n_robots; ++k) {
-    const uint32_t i = instances[k];
-    f->grid_partial[i] = robotBox(f, i, f->hp_state[i].pos, f->hp_reach[i], &f->h_box[(size_t)4 * i]) ? 1 : 0;
-    f->cycle_gen[i] = f->inputs_gen[i];
-  }
-  launch_samples_list(pl, cl.d_list, n_robots, f->stream);
-  // (the launch's dispatch order sits where the range cycle of instances[0] .. would put it: n_robots <= n_instances - instances[0])
-  const bool split = splitPrep(f);  // (as in navgpu_planner_cycle)
-  if (split)
-    PROFILED(f, NAVGPU_K_BFS, launch_bfs_prep_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3));
-  else
-    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, cl.d_list, n_robots, f->stream, pl.bfs_order + (size_t)instances[0] * 3, true));
-  uint32_t n_blocks = 0;
-  if (split)
-    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_grids_list(pl, cl.d_list, n_robots, f->stream));
-  else
-    PROFILED(f, NAVGPU_K_SCORE, n_blocks = launch_score_list(pl, cl.d_list, n_robots, f->stream));
-  int rc_terms = NAVGPU_OK;
-  if (!f->tc.robots.empty()) {  // publish_traj_pc robots that are in the list: run by run, the pass takes a range
-    for (uint32_t k = 0; k < n_robots && rc_terms == NAVGPU_OK;) {
-      uint32_t e = k + 1;
-      while (e < n_robots && instances[e] == instances[e - 1] + 1) ++e;
-      rc_terms = f->tc.terms_pass(f, instances[k], e - k);
-      k = e;
-    }
-  }
-  PROFILED(f, NAVGPU_K_SELECT, launch_select_list(pl, cl.d_list, n_robots, n_blocks, f->stream));
-  rc = checkLaunch();
-  return rc == NAVGPU_OK ? rc_terms : rc;  // (the cycle itself is complete either way)
+  return plannerCycle(f, RobotSet{0, n_robots, instances});
 }
 
 int navgpu_planner_results_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, navgpu_plan_result* results) {
@@ -1982,6 +1921,14 @@ int navgpu_planner_samples(navgpu_fleet* f, uint32_t instance, double* costs, in
   return cnt[3];
 }
 
+// does a probe of robot i that reaches `reach` metres stay inside the box its last bounded wavefronts settled?  (a sideways-shifted
+// look-up - navgpu_planner_set_map_grid_options after the cycle - leaves the box reachMetres describes: those always get complete grids)
+static bool staysInBox(const navgpu_fleet* f, uint32_t i, double reach) {
+  const uint32_t need = (uint32_t)std::min(ceil(reach / f->pl.res) + 3.0, 32768.0);
+  int32_t nb[4];
+  const int32_t* hb = &f->h_box[(size_t)4 * i];
+  return !f->pl.mg_generic && robotBox(f, i, f->hp_state[i].pos, need, nb) && nb[0] >= hb[0] && nb[1] <= hb[1] && nb[2] >= hb[2] && nb[3] <= hb[3];
+}
 int navgpu_planner_check_trajectory(navgpu_fleet* f, uint32_t instance, const float vs[3], int32_t* ok) {
   if (!f || !vs || !ok || instance >= f->desc.n_instances) return NAVGPU_ERR_INVALID;
   FleetGuard guard_(f);
@@ -1991,18 +1938,9 @@ int navgpu_planner_check_trajectory(navgpu_fleet* f, uint32_t instance, const fl
     int rc = flushLimits(f, RobotSet{instance, 1, nullptr});
     if (rc != NAVGPU_OK) return rc;
   }
-  if (f->grid_partial[instance]) {  // the sample must stay inside the box the last wavefronts settled
-    const navgpu_robot_state& st = f->hp_state[instance];
-    const uint32_t need = (uint32_t)std::min(ceil(reachMetres(pl.cfg, f->h_limits[instance], st.vel, vs) / pl.res) + 3.0, 32768.0);
-    int32_t nb[4];
-    const int32_t* hb = &f->h_box[(size_t)4 * instance];
-    // (a sideways-shifted look-up - navgpu_planner_set_map_grid_options after the cycle - leaves the box reachMetres
-    // describes: those always get complete grids)
-    const bool inside = !pl.mg_generic && robotBox(f, instance, st.pos, need, nb) && nb[0] >= hb[0] && nb[1] <= hb[1] && nb[2] >= hb[2] && nb[3] <= hb[3];
-    if (!inside) {
-      int rc = ensureCompleteGrids(f, instance, 1);
-      if (rc) return rc;
-    }
+  if (f->grid_partial[instance] && !staysInBox(f, instance, reachMetres(pl.cfg, f->h_limits[instance], f->hp_state[instance].vel, vs))) {
+    int rc = ensureCompleteGrids(f, instance, 1);
+    if (rc) return rc;
   }
   // checkTrajectory resets the oscillation flags first (dwa_planner.cpp:217)
   HIP_TRY(hipMemsetAsync(pl.osc_flags + instance, 0, sizeof(uint32_t), f->stream));
@@ -2021,10 +1959,10 @@ int navgpu_planner_check_trajectory(navgpu_fleet* f, uint32_t instance, const fl
 // buffers of their own (navgpu_fleet::Probes): the cycle's partial argmin, per-sample costs and counters are not touched.
 int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const uint32_t* instances, const uint32_t* probe_offsets,
                                       const float* vel_samples, int32_t* ok, double* costs) {
-  if (!f || !n_robots || !instances || !probe_offsets || n_robots > f->desc.n_instances || probe_offsets[0] != 0) return NAVGPU_ERR_INVALID;
+  if (!f || !listOk(f, n_robots, instances) || !probe_offsets || probe_offsets[0] != 0) return NAVGPU_ERR_INVALID;
   uint32_t max_probes = 0;
   for (uint32_t k = 0; k < n_robots; ++k) {
-    if (instances[k] >= f->desc.n_instances || (k && instances[k] <= instances[k - 1]) || probe_offsets[k + 1] < probe_offsets[k]) return NAVGPU_ERR_INVALID;
+    if (probe_offsets[k + 1] < probe_offsets[k]) return NAVGPU_ERR_INVALID;
     max_probes = std::max(max_probes, probe_offsets[k + 1] - probe_offsets[k]);
   }
   const uint32_t total = probe_offsets[n_robots];
@@ -2066,13 +2004,9 @@ int navgpu_planner_check_trajectories(navgpu_fleet* f, uint32_t n_robots, const 
     auto leavesBox = [&](uint32_t q) {
       const uint32_t i = instances[q];
       if (!f->grid_partial[i] || probe_offsets[q + 1] == probe_offsets[q]) return false;
-      const navgpu_robot_state& st = f->hp_state[i];
       double reach = 0.0;
-      for (uint32_t p = probe_offsets[q]; p < probe_offsets[q + 1]; ++p) reach = std::max(reach, reachMetres(pl.cfg, f->h_limits[i], st.vel, vel_samples + 3 * (size_t)p));
-      const uint32_t need = (uint32_t)std::min(ceil(reach / pl.res) + 3.0, 32768.0);
-      int32_t nb[4];
-      const int32_t* hb = &f->h_box[(size_t)4 * i];
-      return !(!pl.mg_generic && robotBox(f, i, st.pos, need, nb) && nb[0] >= hb[0] && nb[1] <= hb[1] && nb[2] >= hb[2] && nb[3] <= hb[3]);
+      for (uint32_t p = probe_offsets[q]; p < probe_offsets[q + 1]; ++p) reach = std::max(reach, reachMetres(pl.cfg, f->h_limits[i], f->hp_state[i].vel, vel_samples + 3 * (size_t)p));
+      return !staysInBox(f, i, reach);
     };
     std::vector<uint32_t> leaving;
     for (uint32_t k = 0; k < n_robots; ++k)

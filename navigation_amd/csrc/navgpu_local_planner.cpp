@@ -276,18 +276,21 @@ int navgpu_local_planner_compute_velocity_commands(navgpu_fleet* f, uint32_t fir
     if (rc != NAVGPU_OK) return rc;
   }
   if (collect(valid, 2)) {  // resident: the window is on the device already; pose, nose goal, alignment switch and reach through k_stage_poses
-    int rc;
-    if (oneRun()) {
-      rc = stagePosesFromMirrors(f, first + ks.front(), (uint32_t)ks.size(), &res_pos[3 * (size_t)ks.front()], &res_vel[3 * (size_t)ks.front()]);
-    } else {
-      std::vector<float> lp(3 * ks.size()), lv(3 * ks.size());
-      for (size_t q = 0; q < ks.size(); ++q)
-        for (int a = 0; a < 3; ++a) {
-          lp[3 * q + a] = res_pos[3 * (size_t)ks[q] + a];
-          lv[3 * q + a] = res_vel[3 * (size_t)ks[q] + a];
-        }
-      rc = stagePosesListFromMirrors(f, (uint32_t)ks.size(), robotsOf().data(), lp.data(), lv.data());
+    RobotSet set{first + ks.front(), (uint32_t)ks.size(), nullptr};
+    const float *pos = &res_pos[3 * (size_t)ks.front()], *vel = &res_vel[3 * (size_t)ks.front()];  // one run: the range, its part of the arrays
+    std::vector<uint32_t> inst;
+    std::vector<float> lp, lv;
+    if (!oneRun()) {  // any other set: the list, the listed robots' entries gathered
+      inst = robotsOf();
+      set.list = inst.data();
+      for (uint32_t k : ks) {
+        lp.insert(lp.end(), &res_pos[3 * (size_t)k], &res_pos[3 * (size_t)k] + 3);
+        lv.insert(lv.end(), &res_vel[3 * (size_t)k], &res_vel[3 * (size_t)k] + 3);
+      }
+      pos = lp.data();
+      vel = lv.data();
     }
+    int rc = stagePoses(f, set, pos, vel);
     if (rc != NAVGPU_OK) return rc;
   }
   // --- dispatch: isPositionReached (latched_stop_rotate_controller.cpp:37-58).  The stop / rotate candidates are collected here -

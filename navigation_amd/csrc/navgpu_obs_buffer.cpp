@@ -334,13 +334,8 @@ int navgpu_obsbuf_stage_list(navgpu_fleet* f, uint32_t n_robots, const uint32_t*
   stagePoseMirrors(f, set, poses);
   if ((rc = sendCostmapStageList(f, n_robots, instances, false))) return rc;
   // the list the gather reads: the block's records name the robots, the kernel wants them as a plain array
-  navgpu_fleet::CostmapList& cl = f->cml;
-  if (cl.ev_set) HIP_TRY(hipEventSynchronize(cl.ev_list));
-  memcpy(cl.h_list, instances, sizeof(uint32_t) * n_robots);
-  HIP_TRY(hipMemcpyAsync(cl.d_list, cl.h_list, sizeof(uint32_t) * n_robots, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipEventRecord(cl.ev_list, f->stream));
-  cl.ev_set = true;
-  launch_obs_gather(ob.dev, cm, RobotList{cl.d_list}, n_robots, f->stream);
+  if ((rc = f->cml.list.send(f, instances, n_robots))) return rc;
+  launch_obs_gather(ob.dev, cm, RobotList{f->cml.list.d}, n_robots, f->stream);
   return checkLaunch();
 }
 

@@ -187,7 +187,7 @@ int navgpu_tp_configure(navgpu_fleet* f, const navgpu_tp_config* cfg_in) {
 }
 
 // the wavefront launch of the legacy planner: two grids, path_map_ optionally with within_robot bits
-// (a listed set's robots are in f->tpl.d_list by then: tpSendList)
+// (a listed set's robots are in f->tpl.list.d by then: tpSendList)
 static int tpLaunchGrids(navgpu_fleet* f, const RobotSet& r, bool with_within) {
   PlannerDev pl = f->pl;
   pl.bfs_grids = 2;
@@ -197,7 +197,7 @@ static int tpLaunchGrids(navgpu_fleet* f, const RobotSet& r, bool with_within) {
   pl.bfs_seed_cap = 0;  // no k_samples in front of this launch: the wavefronts seed from the plan
   for (uint32_t k = 0; k < r.count; ++k) f->grid_partial[r[k]] = 0;
   if (r.list)
-    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, f->tpl.d_list, r.count, f->stream, nullptr, false));
+    PROFILED(f, NAVGPU_K_BFS, launch_bfs_list(pl, f->tpl.list.d, r.count, f->stream, nullptr, false));
   else
     PROFILED(f, NAVGPU_K_BFS, launch_bfs(pl, r.first, r.count, f->stream));
   return NAVGPU_OK;
@@ -233,17 +233,17 @@ static bool tpListLaunchers() {
 static int reserveTpList(navgpu_fleet* f, size_t stage_bytes, size_t out_cap) {
   navgpu_fleet::TpList& tl = f->tpl;
   const uint32_t n = f->desc.n_instances;
-  if (!tl.d_list) {
+  if (!tl.list.d) {
     navgpu_fleet::TpList nl;
-    int rc = f->alloc(&nl.d_list, n);
+    int rc = f->alloc(&nl.list.d, n);
     if (!rc) rc = f->alloc(&nl.d_win, n);
-    if (!rc) rc = f->allocPinned(&nl.h_list, n);
+    if (!rc) rc = f->allocPinned(&nl.list.h, n);
     if (!rc) rc = f->allocPinned(&nl.h_win, n);
-    if (!rc && hipEventCreateWithFlags(&nl.ev_list, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
+    if (!rc && hipEventCreateWithFlags(&nl.list.ev, hipEventDisableTiming) != hipSuccess) rc = NAVGPU_ERR_HIP;
     if (rc) {
-      f->release(nl.d_list);
+      f->release(nl.list.d);
       f->release(nl.d_win);
-      f->releasePinned(nl.h_list);
+      f->releasePinned(nl.list.h);
       f->releasePinned(nl.h_win);
       return rc;
     }
@@ -301,11 +301,7 @@ static int tpSendList(navgpu_fleet* f, const RobotSet& r, bool with_rollout, siz
   int rc = reserveTpList(f, bytes, n_smp);
   if (rc) return rc;
   navgpu_fleet::TpList& tl = f->tpl;
-  if (tl.ev_set) HIP_TRY(hipEventSynchronize(tl.ev_list));  // the pinned list may still feed the copy of the listed call before
-  memcpy(tl.h_list, r.list, sizeof(uint32_t) * r.count);
-  HIP_TRY(hipMemcpyAsync(tl.d_list, tl.h_list, sizeof(uint32_t) * r.count, hipMemcpyHostToDevice, f->stream));
-  HIP_TRY(hipEventRecord(tl.ev_list, f->stream));
-  tl.ev_set = true;
+  if ((rc = tl.list.send(f, r.list, r.count)) != NAVGPU_OK) return rc;
   TpStageRec* rec = reinterpret_cast<TpStageRec*>(tl.h_stage);
   double* plan = reinterpret_cast<double*>(tl.h_stage + off_plan);
   double* smp = reinterpret_cast<double*>(tl.h_stage + off_smp);
@@ -482,9 +478,9 @@ static int tpFindBestPath(navgpu_fleet* f, const RobotSet& r, const navgpu_robot
     if ((rc = tpPlanMirrors(f, r))) return rc;
     size_t n_out = 0;
     if ((rc = tpSendList(f, r, true, &n_out))) return rc;
-    launch_tp_within_list(f->pl, tp, f->tpl.d_list, count, f->stream);
+    launch_tp_within_list(f->pl, tp, f->tpl.list.d, count, f->stream);
     if ((rc = tpLaunchGrids(f, r, true))) return rc;
-    PROFILED(f, NAVGPU_K_SCORE, launch_tp_rollout_list(f->pl, tp, f->tpl.d_list, count, 0, f->stream));
+    PROFILED(f, NAVGPU_K_SCORE, launch_tp_rollout_list(f->pl, tp, f->tpl.list.d, count, 0, f->stream));
     launch_tp_gather_out(tp, reinterpret_cast<const TpStageRec*>(f->tpl.d_stage), f->tpl.d_out, count, f->stream);
     HIP_TRY(hipMemcpyAsync(f->tpl.h_out, f->tpl.d_out, sizeof(TpOut) * n_out, hipMemcpyDeviceToHost, f->stream));
     HIP_TRY(waitStream(f->stream));
@@ -675,8 +671,8 @@ static int tpFindBestPath(navgpu_fleet* f, const RobotSet& r, const navgpu_robot
   if (r.list) {
     for (uint32_t k = 0; k < count; ++k) f->tpl.h_win[k] = f->tp_h_winner[r[k]];
     HIP_TRY(hipMemcpyAsync(f->tpl.d_win, f->tpl.h_win, sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
-    launch_tp_winner_scatter(tp, f->tpl.d_list, f->tpl.d_win, count, f->stream);
-    launch_tp_rollout_list(f->pl, tp, f->tpl.d_list, count, 1, f->stream);
+    launch_tp_winner_scatter(tp, f->tpl.list.d, f->tpl.d_win, count, f->stream);
+    launch_tp_rollout_list(f->pl, tp, f->tpl.list.d, count, 1, f->stream);
   } else {
     HIP_TRY(hipMemcpyAsync(tp.winner + first, &f->tp_h_winner[first], sizeof(int32_t) * count, hipMemcpyHostToDevice, f->stream));
     launch_tp_rollout(f->pl, tp, first, count, 1, f->stream);

@@ -214,30 +214,31 @@ uint32_t bfs_cu_count() {
 // Every wavefront kernel stops a bounded search at its robot's region (pl.bfs_bounded) and runs the legacy
 // planner's two-grid launches (pl.bfs_grids == 2, pl.within) as well: k_bfs_rows for maps up to 640 x 800, k_bfs_rows2 up to
 // 1024 x 1344, k_bfs_global beyond.  order: the launch's items longest first (k_samples), or null.
-void launch_bfs(const PlannerDev& pl_, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
+// free_ready: the bitmaps and the zeroed work counters are k_samples' (a planner cycle); else this launch makes them itself - the
+// legacy planner's calls and the completion of bounded grids, which have no k_samples in front of them.
+static bool launchRowSweeps(const PlannerDev& pl, RobotRange r, uint32_t count, hipStream_t s, const uint32_t* order) {
+  return launch_bfs_rows(pl, r.first, count, s, order) || launch_bfs_rows2(pl, r.first, count, s, order);
+}
+static bool launchRowSweeps(const PlannerDev& pl, RobotList r, uint32_t count, hipStream_t s, const uint32_t* order) {
+  return launch_bfs_rows_list(pl, r.list, count, s, order) || launch_bfs_rows2_list(pl, r.list, count, s, order);
+}
+template <class Robots>
+static void launchBfs(const PlannerDev& pl_, Robots robots, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
   PlannerDev pl = pl_;
   if (!free_ready) {  // (a planner cycle has all three done by its k_samples launch)
-    hipLaunchKernelGGL(k_free_bits<RobotRange>, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, RobotRange{first});
+    hipLaunchKernelGGL(k_free_bits<Robots>, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, robots);
     hipMemsetAsync(pl.bfs_next_item, 0, 2 * sizeof(uint32_t), s);
     pl.bfs_seed_cap = 0;  // no seed lists either: the wavefronts walk the plans
   }
-  if (launch_bfs_rows(pl, first, count, s, order)) return;
-  if (launch_bfs_rows2(pl, first, count, s, order)) return;
-  hipLaunchKernelGGL(k_bfs_global<RobotRange>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, RobotRange{first}, pl.bfs_scratch);
+  if (launchRowSweeps(pl, robots, count, s, order)) return;
+  hipLaunchKernelGGL(k_bfs_global<Robots>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, robots, pl.bfs_scratch);
 }
-// The wavefronts for the robots list[0 .. count), the scratch slots by position in the launch as above.  free_ready: the bitmaps
-// and the zeroed work counters are k_samples' (a planner cycle); else this launch makes them itself, as launch_bfs does - the
-// legacy planner's listed calls and the completion of bounded grids, which have no k_samples in front of them.
-void launch_bfs_list(const PlannerDev& pl_, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
-  PlannerDev pl = pl_;
-  if (!free_ready) {
-    hipLaunchKernelGGL(k_free_bits<RobotList>, dim3((pl.ny * ((pl.nx + 31) / 32) + 255) / 256, count), dim3(256), 0, s, pl, RobotList{list});
-    hipMemsetAsync(pl.bfs_next_item, 0, 2 * sizeof(uint32_t), s);
-    pl.bfs_seed_cap = 0;  // no seed lists either: the wavefronts walk the plans
-  }
-  if (launch_bfs_rows_list(pl, list, count, s, order)) return;
-  if (launch_bfs_rows2_list(pl, list, count, s, order)) return;
-  hipLaunchKernelGGL(k_bfs_global<RobotList>, dim3(count, pl.bfs_grids), dim3(1024), 0, s, pl, RobotList{list}, pl.bfs_scratch);
+void launch_bfs(const PlannerDev& pl, uint32_t first, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
+  launchBfs(pl, RobotRange{first}, count, s, order, free_ready);
+}
+// the wavefronts for the robots list[0 .. count), the scratch slots by position in the launch as above
+void launch_bfs_list(const PlannerDev& pl, const uint32_t* list, uint32_t count, hipStream_t s, const uint32_t* order, bool free_ready) {
+  launchBfs(pl, RobotList{list}, count, s, order, free_ready);
 }
 
 }  // namespace navgpu

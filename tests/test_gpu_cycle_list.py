@@ -194,6 +194,80 @@ def test_full_list_and_single_robot(nav, robots):
     _twin_cycles(nav, 120, 120, "sweep", robots)
 
 
+def test_result_slots_across_the_in_flight_switch(nav):
+    """Two whole-fleet cycles with two cycles in flight, back to one, then a listed cycle: the listed cycle shares the range cycle's code
+    and must never flip the result slot.  Everything read is byte-equal to a twin that runs the listed step as range calls, and the
+    robots outside the list keep the results of the second whole-fleet cycle."""
+    from navigation_amd import _lib as N
+    masters, sets = _scene(120, 120)
+    robots = [0, 2, 3, 7]
+    A, B = _fleet(nav, 120, 120, "sweep", masters), _fleet(nav, 120, 120, "sweep", masters)
+    try:
+        read = {}
+        for fl in (A, B):
+            fl.set_plan()
+            fl.set_cycles_in_flight(2)
+            for s in (0, 1):
+                fl.stage_planner(np.stack([x[0] for x in sets[s]]), np.stack([x[1] for x in sets[s]]), [x[2] for x in sets[s]])
+                fl.planner_cycle()
+            previous = list(fl.results_previous_into((N.PlanResult * N_ROBOTS)()))
+            latest = fl.results()
+            fl.set_cycles_in_flight(1)
+            pos, vel = np.stack([sets[2][i][0] for i in robots]), np.stack([sets[2][i][1] for i in robots])
+            plans = [sets[2][i][2] for i in robots]
+            if fl is A:
+                fl.stage_planner_list(robots, pos, vel, plans)
+                fl.planner_cycle_list(robots)
+                listed = fl.results_list(robots)
+            else:
+                listed = []
+                for first, count in _runs(robots):
+                    k = robots.index(first)
+                    fl.stage_planner(pos[k:k + count], vel[k:k + count], plans[k:k + count], first=first)
+                    fl.planner_cycle(first, count)
+                    listed += fl.results(first, count)
+            read["A" if fl is A else "B"] = {k: [bytes(r) for r in v] for k, v in dict(previous=previous, latest=latest, listed=listed, after=fl.results()).items()}
+        _assert_same(read["A"], read["B"], "twins")
+        a = read["A"]
+        assert a["previous"] != a["latest"], "both whole-fleet cycles gave the same results: the slots cannot be told apart"
+        for i in range(N_ROBOTS):
+            assert a["after"][i] == (a["listed"][robots.index(i)] if i in robots else a["latest"][i]), i
+    finally:
+        A.close()
+        B.close()
+
+
+def test_pose_stage_across_a_chunk_boundary(nav):
+    """70 robots, more than the 64 a pose chunk holds: stage_poses_list of every robot but 1 and 66 takes two chunks and its runs cross
+    entry 64; the twin's run [2, 66) crosses the range form's chunk boundary as well."""
+    masters, sets = _scene(120, 120)
+    n = 70
+    robots = [i for i in range(n) if i not in (1, 66)]
+    of = lambda s, i: sets[s][i % N_ROBOTS]  # noqa: E731  (the scene's eight robots, over again)
+    many = [masters[i % N_ROBOTS] for i in range(n)]
+    A, B = _fleet(nav, 120, 120, "sweep", many), _fleet(nav, 120, 120, "sweep", many)
+    try:
+        for fl in (A, B):
+            fl.set_plan()
+            fl.find_best_path(np.stack([of(0, i)[0] for i in range(n)]), np.stack([of(0, i)[1] for i in range(n)]), [of(0, i)[2] for i in range(n)])
+        before = {i: _state(A, i) for i in (1, 66)}
+        pos, vel = np.stack([of(1, i)[0] for i in robots]), np.stack([of(1, i)[1] for i in robots])
+        A.stage_poses_list(robots, pos, vel)
+        A.planner_cycle_list(robots)
+        assert _runs(robots) == [(0, 1), (2, 64), (67, 3)]
+        for first, count in _runs(robots):
+            k = robots.index(first)
+            B.stage_poses(pos[k:k + count], vel[k:k + count], first=first)
+            B.planner_cycle(first, count)
+        for i in robots:
+            _assert_same(_state(A, i), _state(B, i), ("robot", i))
+        for i in (1, 66):
+            _assert_same(before[i], _state(A, i), ("unlisted robot", i))
+    finally:
+        A.close()
+        B.close()
+
+
 # ------------------------------------------------------------------------------------------------ c. errors
 def test_errors(nav):
     from navigation_amd import _lib as N
