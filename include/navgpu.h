@@ -1888,6 +1888,115 @@ int navgpu_amcl_node_integrate_odom(navgpu_amcl* amcl, uint32_t first, uint32_t 
 int navgpu_amcl_node_get_state(navgpu_amcl* amcl, uint32_t first, uint32_t count, navgpu_amcl_node_state* states);
 int navgpu_amcl_node_set_state(navgpu_amcl* amcl, uint32_t first, uint32_t count, const navgpu_amcl_node_state* states);
 
+/* ------------------------------------------------------------------------------------------ */
+/* costmap_3d::Costmap3DQuery - batched mesh-vs-occupancy collision and distance queries      */
+/* ------------------------------------------------------------------------------------------ */
+/* A handle of its own (as navgpu_navfn): n_instances resident 3-D occupancy maps of one size and one robot mesh.  A map is a
+ * dense bit volume: one uint64_t per (x, y) column, bit z set when cell (x, y, z) is occupied, in two planes per instance -
+ * LETHAL and NONLETHAL, the reference's "strictly between FREE and LETHAL" (costmap_3d/include/costmap_3d/costmap_3d.h:48-60).
+ * Cell (i, j, k) is the closed cube [origin + (i, j, k) * resolution, origin + (i + 1, j + 1, k + 1) * resolution].
+ * What a query computes is geometry: the robot is the closed solid bounded by the mesh at the pose, the obstacles are
+ * the closed cubes of the occupied cells.  It is what the reference's octree / BVH solver and interior-collision look-up table
+ * approximate (costmap_3d/src/costmap_3d_query.cpp:586-939); FCL's own answers are not pinned.
+ * The device is opened by the first call that needs it (NAVGPU_ERR_NO_DEVICE there, never a CPU fallback): every argument error
+ * below is found before that, and before anything is queued.  Calls on one handle are serialised and ordered on one stream. */
+typedef struct navgpu_costmap3d navgpu_costmap3d;
+#define NAVGPU_C3D_MAX_TRIANGLES 384 /* largest max_triangles: a pose's world triangles live in one workgroup's LDS */
+typedef struct {
+  uint32_t n_instances;
+  uint32_t size_x, size_y; /* columns; size_x * size_y <= 2^26                                                  */
+  uint32_t size_z;         /* levels, 1..64                                                                     */
+  double resolution;       /* edge of a cell, > 0                                                               */
+  uint32_t max_triangles;  /* 1..NAVGPU_C3D_MAX_TRIANGLES                                                       */
+  uint32_t max_boxes;      /* per navgpu_costmap3d_set_boxes call                                               */
+  uint32_t max_poses;      /* per query call (and its runs)                                                     */
+  int32_t device;
+} navgpu_costmap3d_desc;
+typedef struct {
+  double cx, cy, cz; /* centre                                                                                  */
+  double size;       /* edge: resolution * 2^k (an octomap leaf of any depth)                                   */
+  int32_t cls;       /* NAVGPU_C3D_LETHAL | NAVGPU_C3D_NONLETHAL                                                */
+  int32_t reserved;
+} navgpu_c3d_box;
+typedef struct {
+  uint32_t instance;
+  uint32_t first_pose; /* index into the call's pose array                                                      */
+  uint32_t n_poses;
+} navgpu_c3d_run;
+typedef struct {
+  double cost;          /* distance mode: the minimum over the run's poses, from DBL_MAX; else the fold below  */
+  int32_t n_lethal;     /* poses with a negative cost (response.lethal_indices.size())                         */
+  int32_t first_lethal; /* index within the run of the first of them, -1 when there is none                    */
+  int32_t n_done;       /* poses answered: n_poses, or with lazy first_lethal + 1                               */
+  int32_t reserved;
+} navgpu_c3d_run_result;
+enum { NAVGPU_C3D_LETHAL = 0, NAVGPU_C3D_NONLETHAL = 1 };
+enum { NAVGPU_C3D_REPLACE = 0, NAVGPU_C3D_MARK = 1, NAVGPU_C3D_CLEAR = 2 };
+/* GetPlanCost3D.srv's numbers; COST_QUERY_MODE_SIGNED_DISTANCE (3) is NAVGPU_ERR_INVALID: the reference's own README calls it not functional */
+enum { NAVGPU_C3D_COST = 0, NAVGPU_C3D_COLLISION_ONLY = 1, NAVGPU_C3D_DISTANCE = 2 };
+enum { NAVGPU_C3D_REGION_ALL = 0, NAVGPU_C3D_REGION_LEFT = 1, NAVGPU_C3D_REGION_RIGHT = 2, NAVGPU_C3D_REGION_RECTANGULAR_PRISM = 3 };
+
+/* replaces: Costmap3DQuery::Costmap3DQuery / init (costmap_3d/src/costmap_3d_query.cpp:58-126) for n_instances maps.  Host only:
+ * NAVGPU_ERR_INVALID for a NULL argument, a zero count, size_z > 64, size_x * size_y > 2^26, a resolution that is not positive
+ * and finite, max_triangles > NAVGPU_C3D_MAX_TRIANGLES or a negative device.  Origins start at (0, 0, 0), the maps empty. */
+int navgpu_costmap3d_create(const navgpu_costmap3d_desc* desc, navgpu_costmap3d** out);
+int navgpu_costmap3d_destroy(navgpu_costmap3d* c3d);
+/* replaces: the octree's fixed frame (Costmap3DQuery::checkCostmap, costmap_3d_query.cpp:138-287, reads the tree in the costmap's
+ * frame): the world position of the corner of cell (0, 0, 0) of one instance.  Not finite: NAVGPU_ERR_INVALID. */
+int navgpu_costmap3d_set_origin(navgpu_costmap3d* c3d, uint32_t instance, const double origin_xyz[3]);
+int navgpu_costmap3d_get_origin(navgpu_costmap3d* c3d, uint32_t instance, double origin_xyz[3]);
+/* replaces: Costmap3DQuery::updateCostmap (costmap_3d_query.cpp:128-136; mode REPLACE: the boxes are the whole map) and the
+ * deltas of an octomap update that checkCostmap (:138-287) follows (MARK, CLEAR).  A box is an octomap leaf of any depth: size
+ * must be resolution * 2^k and the box aligned to the instance's grid (both to 1e-6 of a cell), else NAVGPU_ERR_INVALID with the
+ * map untouched; so for a cls outside the two, a non-finite field and a bad mode.  n > max_boxes: NAVGPU_ERR_CAPACITY.  A pruned
+ * leaf is rasterised into its finest cells (the union of closed cubes is the same set); cells outside the extents are dropped
+ * and counted in clipped_out (or NULL).  MARK sets the cells in the plane of cls and clears them in the other plane, CLEAR
+ * clears them in both (cls is not looked at); one call must not name a cell in both classes (an octomap leaf has one value).
+ * k_c3d_rasterize: vector atomicOr / atomicAnd on the column words, which commute - the result does not depend on the order. */
+int navgpu_costmap3d_set_boxes(navgpu_costmap3d* c3d, uint32_t instance, int32_t mode, const navgpu_c3d_box* boxes, uint32_t n,
+                               uint32_t* clipped_out);
+/* Raw access to an instance's planes (tests, checkpoints; as navgpu_grid_upload / navgpu_grid_download - no reference lines, the
+ * reference keeps an octomap::OcTree, costmap_3d.h:48-60 names the classes): size_y * size_x words each, word index y * size_x + x.
+ * Either pointer may be NULL (that plane is skipped); a bit at or above size_z in an upload is NAVGPU_ERR_INVALID. */
+int navgpu_costmap3d_columns_upload(navgpu_costmap3d* c3d, uint32_t instance, const uint64_t* lethal, const uint64_t* nonlethal);
+int navgpu_costmap3d_columns_download(navgpu_costmap3d* c3d, uint32_t instance, uint64_t* lethal, uint64_t* nonlethal);
+/* replaces: Costmap3DQuery::updateMeshResource (costmap_3d_query.cpp:413-449) with padPoints (costmap_3d/include/costmap_3d/
+ * costmap_3d_query.h:332-350: every vertex pushed radially in xy by `padding`, the arithmetic in float as written there, the
+ * origin left alone).  vertices = nv x {x, y, z}, triangles = nt x 3 vertex indices.  closed_out (or NULL) says whether the mesh
+ * is closed and consistently oriented - every directed edge has its opposite exactly once.  An open mesh is treated as a
+ * surface: there is no interior test for it.  nt > max_triangles: NAVGPU_ERR_CAPACITY.  NAVGPU_ERR_INVALID for nt == 0, an index
+ * >= nv, a coordinate or padding that is not finite, or a triangle without area.  A call that fails leaves the previous mesh. */
+int navgpu_costmap3d_set_mesh(navgpu_costmap3d* c3d, const double* vertices, uint32_t nv, const uint32_t* triangles, uint32_t nt,
+                              double padding, int32_t* closed_out);
+/* replaces: Costmap3DROS::processPlanCost3D (costmap_3d/src/costmap_3d_ros.cpp:464-616) over Costmap3DQuery::footprintCollision /
+ * footprintCost / footprintDistance (costmap_3d_query.cpp:493-521, 586-970) for n_runs runs of poses, each against one instance:
+ * one upload, one launch set (k_c3d_query: a wave per pose; k_c3d_fold: a lane per run), one read-back.
+ *   runs       any instances in any order, an instance more than once; their pose ranges must not overlap (NAVGPU_ERR_INVALID)
+ *              and must end at or below max_poses, n_runs <= max_poses (NAVGPU_ERR_CAPACITY)
+ *   poses      {x, y, z, qx, qy, qz, qw} per pose; the quaternion is normalised on the device; a pose that is not finite or has
+ *              a zero quaternion is NAVGPU_ERR_INVALID
+ *   mode       NAVGPU_C3D_COST | _COLLISION_ONLY | _DISTANCE
+ *   regions    per pose, or NULL (ALL): the half-spaces of RegionsOfInterestAtPose (costmap_3d_query.h:573-617) at the pose, the
+ *              prism with region_scale[1] and [2].  A cell is considered unless it lies entirely outside some half-space - centre
+ *              distance minus extent > 0, checkROI (costmap_3d/include/costmap_3d/octree_solver.h:248-285) - per finest cell
+ *   obstacles  per pose, or NULL (LETHAL): honoured in distance mode only, as in the reference (costmap_3d_ros.cpp:533-551)
+ * Per pose: it collides iff a considered occupied cell's closed cube intersects a mesh triangle, or - closed mesh - the centre of
+ * one lies inside the solid (winding number from the triangles' solid angles, |w| > 0.5).  COLLISION_ONLY and COST (the
+ * reference's TODO, costmap_3d_query.cpp:493-497): -1.0 | 0.0.  DISTANCE: -1.0 when colliding, else the Euclidean distance between
+ * the mesh and the considered occupied cells closer than distance_limit, else distance_limit as given (DBL_MAX for an empty map,
+ * an empty region, a pose off the extents); a limit <= 0 is raised to DBL_MIN (costmap_3d_query.cpp:632).
+ * Per run: the fold of costmap_3d_ros.cpp:494-609 in results_out (or NULL).  With lazy a run ends at its first lethal pose and
+ * pose_costs_out (or NULL; indexed as poses) behind it is left untouched. */
+int navgpu_costmap3d_query(navgpu_costmap3d* c3d, uint32_t n_runs, const navgpu_c3d_run* runs, const double* poses, int32_t mode,
+                           const uint8_t* regions, const uint8_t* obstacles, const double region_scale[3], double distance_limit,
+                           int32_t lazy, double* pose_costs_out, navgpu_c3d_run_result* results_out);
+/* replaces: base_local_planner::Costmap3DModel::footprintCost(x, y, theta, ...) (base_local_planner/src/costmap_3d_model.cpp:61-79):
+ * the pose is (x, y, 0) with the yaw quaternion, the query the cost mode over ALL.  poses_xyth = {x, y, theta} per pose, indexed by
+ * the runs as above; costs_out one double per pose and first_illegal_out (or NULL) per run the index within it of the first
+ * negative cost, -1 when there is none - navgpu_footprint_cost's layout. */
+int navgpu_costmap3d_footprint_costs(navgpu_costmap3d* c3d, uint32_t n_runs, const navgpu_c3d_run* runs, const double* poses_xyth,
+                                     double* costs_out, int32_t* first_illegal_out);
+
 #ifdef __cplusplus
 }
 #endif

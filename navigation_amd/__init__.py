@@ -6,9 +6,10 @@ imports the CPU oracle and has no CPU fallback: loading fails loudly when libnav
 """
 from ._lib import (TpConfig, TpRosParams, DwaConfig, FleetDesc, InflationParams, NavgpuError, Observation, ObstacleParams, PlanResult,
                    RobotState, build, lib, lib_path)
+from .costmap3d import Costmap3D, load_octomap_bt, load_stl
 from .fleet import Fleet
 from .localization import AmclLaser
 from .navfn import NavFn
 
-__all__ = ["AmclLaser", "Fleet", "NavFn", "TpConfig", "TpRosParams", "DwaConfig", "FleetDesc", "InflationParams", "ObstacleParams", "Observation", "PlanResult",
+__all__ = ["AmclLaser", "Costmap3D", "load_octomap_bt", "load_stl", "Fleet", "NavFn", "TpConfig", "TpRosParams", "DwaConfig", "FleetDesc", "InflationParams", "ObstacleParams", "Observation", "PlanResult",
            "RobotState", "NavgpuError", "build", "lib", "lib_path"]

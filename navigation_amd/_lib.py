@@ -461,6 +461,34 @@ class AmclNodeState(C.Structure):
             "pf_odom_pose", "odom_integrator_absolute_motion", "odom_integrator_last_pose", "latest_tf")]
 
 
+class Costmap3DDesc(C.Structure):
+    """Mirror of navgpu_costmap3d_desc (include/navgpu.h)."""
+    _fields_ = [("n_instances", C.c_uint32), ("size_x", C.c_uint32), ("size_y", C.c_uint32), ("size_z", C.c_uint32), ("resolution", C.c_double),
+                ("max_triangles", C.c_uint32), ("max_boxes", C.c_uint32), ("max_poses", C.c_uint32), ("device", C.c_int32)]
+
+
+class C3dBox(C.Structure):
+    """Mirror of navgpu_c3d_box (include/navgpu.h)."""
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("cz", C.c_double), ("size", C.c_double), ("cls", C.c_int32), ("reserved", C.c_int32)]
+
+
+class C3dRun(C.Structure):
+    """Mirror of navgpu_c3d_run (include/navgpu.h)."""
+    _fields_ = [("instance", C.c_uint32), ("first_pose", C.c_uint32), ("n_poses", C.c_uint32)]
+
+
+class C3dRunResult(C.Structure):
+    """Mirror of navgpu_c3d_run_result (include/navgpu.h)."""
+    _fields_ = [("cost", C.c_double), ("n_lethal", C.c_int32), ("first_lethal", C.c_int32), ("n_done", C.c_int32), ("reserved", C.c_int32)]
+
+
+C3D_MAX_TRIANGLES = 384
+C3D_LETHAL, C3D_NONLETHAL = 0, 1
+C3D_REPLACE, C3D_MARK, C3D_CLEAR = 0, 1, 2
+C3D_COST, C3D_COLLISION_ONLY, C3D_DISTANCE = 0, 1, 2
+C3D_REGION_ALL, C3D_REGION_LEFT, C3D_REGION_RIGHT, C3D_REGION_RECTANGULAR_PRISM = 0, 1, 2, 3
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -656,6 +684,16 @@ SYMBOLS = [
     ("navgpu_amcl_node_integrate_odom", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_amcl_node_get_state", C.c_int, [vp, u32, u32, vp]),
     ("navgpu_amcl_node_set_state", C.c_int, [vp, u32, u32, vp]),
+    ("navgpu_costmap3d_create", C.c_int, [C.POINTER(Costmap3DDesc), C.POINTER(vp)]),
+    ("navgpu_costmap3d_destroy", C.c_int, [vp]),
+    ("navgpu_costmap3d_set_origin", C.c_int, [vp, u32, vp]),
+    ("navgpu_costmap3d_get_origin", C.c_int, [vp, u32, vp]),
+    ("navgpu_costmap3d_set_boxes", C.c_int, [vp, u32, i32, vp, u32, C.POINTER(u32)]),
+    ("navgpu_costmap3d_columns_upload", C.c_int, [vp, u32, vp, vp]),
+    ("navgpu_costmap3d_columns_download", C.c_int, [vp, u32, vp, vp]),
+    ("navgpu_costmap3d_set_mesh", C.c_int, [vp, vp, u32, vp, u32, dbl, C.POINTER(i32)]),
+    ("navgpu_costmap3d_query", C.c_int, [vp, u32, vp, vp, i32, vp, vp, vp, dbl, i32, vp, vp]),
+    ("navgpu_costmap3d_footprint_costs", C.c_int, [vp, u32, vp, vp, vp, vp]),
 ]
 
 

@@ -1,0 +1,193 @@
+"""Costmap3D: thin Python handle over navgpu_costmap3d_* - costmap_3d::Costmap3DQuery for batches of poses on one GPU.
+
+  set_origin / origin     the frame of an instance's grid
+  set_boxes               Costmap3DQuery::updateCostmap and an octomap update's deltas   (costmap_3d/src/costmap_3d_query.cpp:128-287)
+  set_mesh                Costmap3DQuery::updateMeshResource with padPoints              (:413-449; costmap_3d_query.h:332-350)
+  query                   Costmap3DROS::processPlanCost3D over footprintCollision / footprintCost / footprintDistance
+                          (costmap_3d/src/costmap_3d_ros.cpp:464-616; costmap_3d_query.cpp:493-521, 586-970)
+  footprint_costs         base_local_planner::Costmap3DModel::footprintCost              (base_local_planner/src/costmap_3d_model.cpp:61-79)
+  columns / set_columns   the resident bit volumes themselves
+  load_stl                a binary STL as (vertices, triangles), equal corners merged
+  load_octomap_bt         an octomap binary tree (.bt) as its occupied leaves: centres, sizes, classes
+All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers and reads the two file formats.
+"""
+import ctypes as C
+import struct
+
+import numpy as np
+
+from ._lib import (C3D_DISTANCE, C3D_LETHAL, C3D_REPLACE, C3dBox, C3dRun, C3dRunResult, Costmap3DDesc, check, lib)
+
+BOX_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("cz", "<f8"), ("size", "<f8"), ("cls", "<i4"), ("reserved", "<i4")])
+RUN_DTYPE = np.dtype([("instance", "<u4"), ("first_pose", "<u4"), ("n_poses", "<u4")])
+RUN_RESULT_DTYPE = np.dtype([("cost", "<f8"), ("n_lethal", "<i4"), ("first_lethal", "<i4"), ("n_done", "<i4"), ("reserved", "<i4")])
+assert BOX_DTYPE.itemsize == C.sizeof(C3dBox) and RUN_DTYPE.itemsize == C.sizeof(C3dRun) and RUN_RESULT_DTYPE.itemsize == C.sizeof(C3dRunResult)
+DBL_MAX = float(np.finfo(np.float64).max)
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def load_stl(path):
+    """A binary STL -> (vertices (nv, 3) float64, triangles (nt, 3) uint32).  Corners with equal coordinates become one vertex,
+    in order of first appearance; the facet normals are not used (the corner order gives the orientation)."""
+    data = open(path, "rb").read()
+    (nt,) = struct.unpack_from("<I", data, 80)
+    if len(data) != 84 + 50 * nt:
+        raise ValueError(f"{path}: not a binary STL ({len(data)} bytes for {nt} triangles)")
+    rec = np.frombuffer(data, np.dtype([("n", "<f4", 3), ("v", "<f4", (3, 3)), ("attr", "<u2")]), count=nt, offset=84)
+    index, vertices, triangles = {}, [], np.zeros((nt, 3), np.uint32)
+    for t in range(nt):
+        for k in range(3):
+            key = rec["v"][t, k].tobytes()
+            if key not in index:
+                index[key] = len(vertices)
+                vertices.append(rec["v"][t, k].astype(np.float64))
+            triangles[t, k] = index[key]
+    return np.array(vertices, np.float64).reshape(-1, 3), triangles
+
+
+def read_octomap_bt(path):
+    """An octomap binary tree file, whole: dict(res, depth, size, n_nodes, centres, sizes, classes, depths) of its occupied leaves.
+    The text header ends at the `data` line (`depth N` is this fork's line; 16 without it).  Then, depth first, 2 bytes per inner
+    node: child i is the bit pair (2j, 2j + 1) of byte i // 4, j = i & 3, least significant first - (0, 0) absent, (1, 0) free leaf,
+    (0, 1) occupied leaf, (1, 1) inner node, whose record follows in child order.  Child i adds bit 0 of i to the x key, bit 1 to
+    y, bit 2 to z; a leaf at depth d with key k has edge res * 2^(N - d) and centre (k + 0.5) * edge - 2^(N - 1) * res."""
+    data = open(path, "rb").read()
+    at = data.index(b"\ndata\n") + 6
+    header = {}
+    for line in data[:at].decode("ascii", "replace").splitlines():
+        parts = line.split()
+        if len(parts) == 2 and not line.startswith("#"):
+            header[parts[0]] = parts[1]
+    res, depth, size = float(header["res"]), int(header.get("depth", 16)), int(header["size"])
+    payload = data[at:]
+    pos, n_nodes = 0, 1
+    centres, sizes, depths = [], [], []
+    stack = [(0, 0, 0, 0)]  # inner nodes whose record is next, last on top: (depth, kx, ky, kz)
+    while stack:
+        d, kx, ky, kz = stack.pop()
+        if pos + 2 > len(payload):
+            raise ValueError(f"{path}: the tree ends before its payload does")
+        b = payload[pos:pos + 2]
+        pos += 2
+        inner = []
+        for i in range(8):
+            pair = (b[i // 4] >> (2 * (i & 3))) & 3  # bit 2j is the pair's first
+            if pair == 0:
+                continue
+            n_nodes += 1
+            cx, cy, cz = 2 * kx + (i & 1), 2 * ky + ((i >> 1) & 1), 2 * kz + ((i >> 2) & 1)
+            if pair == 3:
+                inner.append((d + 1, cx, cy, cz))
+            elif pair == 2:  # (0, 1): occupied
+                edge = res * 2.0 ** (depth - d - 1)
+                centres.append([(k + 0.5) * edge - 2.0 ** (depth - 1) * res for k in (cx, cy, cz)])
+                sizes.append(edge)
+                depths.append(d + 1)
+        stack.extend(reversed(inner))
+    assert pos == len(payload), f"{path}: {len(payload) - pos} payload bytes left over"
+    assert n_nodes == size, f"{path}: {n_nodes} nodes read, the header says {size}"
+    return dict(res=res, depth=depth, size=size, n_nodes=n_nodes, centres=np.array(centres, np.float64).reshape(-1, 3),
+                sizes=np.array(sizes, np.float64), classes=np.full(len(sizes), C3D_LETHAL, np.int32), depths=np.array(depths, np.int32))
+
+
+def load_octomap_bt(path):
+    """the occupied leaves of a .bt file as set_boxes takes them: (centres (n, 3), sizes (n,), classes (n,))"""
+    t = read_octomap_bt(path)
+    return t["centres"], t["sizes"], t["classes"]
+
+
+class Costmap3D:
+    def __init__(self, n_instances, size_x, size_y, size_z, resolution, max_triangles=64, max_boxes=1 << 16, max_poses=1 << 12, device=0):
+        self.L = lib()
+        self.n, self.size_x, self.size_y, self.size_z, self.resolution = n_instances, size_x, size_y, size_z, float(resolution)
+        desc = Costmap3DDesc(n_instances, size_x, size_y, size_z, resolution, max_triangles, max_boxes, max_poses, device)
+        h = C.c_void_p()
+        check(self.L.navgpu_costmap3d_create(C.byref(desc), C.byref(h)), "navgpu_costmap3d_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.navgpu_costmap3d_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_origin(self, instance, origin_xyz):
+        o = np.ascontiguousarray(origin_xyz, np.float64).reshape(3)
+        check(self.L.navgpu_costmap3d_set_origin(self.h, instance, _ptr(o)), "navgpu_costmap3d_set_origin")
+
+    def origin(self, instance):
+        o = np.zeros(3)
+        check(self.L.navgpu_costmap3d_get_origin(self.h, instance, _ptr(o)), "navgpu_costmap3d_get_origin")
+        return o
+
+    def set_boxes(self, instance, centres, sizes, classes=None, mode=C3D_REPLACE):
+        """centres (n, 3), sizes (n,) or one size, classes (n,) or None (LETHAL).  Returns the number of cells that fell outside the extents."""
+        c = np.asarray(centres, np.float64).reshape(-1, 3)
+        boxes = np.zeros(len(c), BOX_DTYPE)
+        boxes["cx"], boxes["cy"], boxes["cz"] = c[:, 0], c[:, 1], c[:, 2]
+        boxes["size"] = sizes
+        boxes["cls"] = C3D_LETHAL if classes is None else classes
+        clipped = C.c_uint32(0)
+        check(self.L.navgpu_costmap3d_set_boxes(self.h, instance, mode, _ptr(boxes), len(boxes), C.byref(clipped)), "navgpu_costmap3d_set_boxes")
+        return clipped.value
+
+    def set_columns(self, instance, lethal=None, nonlethal=None):
+        planes = [None if p is None else np.ascontiguousarray(p, np.uint64).reshape(self.size_y, self.size_x) for p in (lethal, nonlethal)]
+        check(self.L.navgpu_costmap3d_columns_upload(self.h, instance, _ptr(planes[0]), _ptr(planes[1])), "navgpu_costmap3d_columns_upload")
+
+    def columns(self, instance):
+        """(lethal, nonlethal): (size_y, size_x) uint64 each, bit z of a word is cell (x, y, z)"""
+        lethal, nonlethal = np.zeros((self.size_y, self.size_x), np.uint64), np.zeros((self.size_y, self.size_x), np.uint64)
+        check(self.L.navgpu_costmap3d_columns_download(self.h, instance, _ptr(lethal), _ptr(nonlethal)), "navgpu_costmap3d_columns_download")
+        return lethal, nonlethal
+
+    def set_mesh(self, vertices, triangles, padding=0.0):
+        """Returns whether the mesh is closed and consistently oriented (an open mesh is a surface: no interior test)."""
+        v = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+        closed = C.c_int32(0)
+        check(self.L.navgpu_costmap3d_set_mesh(self.h, _ptr(v), len(v), _ptr(t), len(t), float(padding), C.byref(closed)), "navgpu_costmap3d_set_mesh")
+        return bool(closed.value)
+
+    @staticmethod
+    def _runs(runs, n_poses):
+        if runs is None:
+            runs = [(0, 0, n_poses)]
+        r = np.zeros(len(runs), RUN_DTYPE)
+        for k, (instance, first, count) in enumerate(runs):
+            r[k] = (instance, first, count)
+        return r
+
+    def query(self, poses, runs=None, mode=C3D_DISTANCE, regions=None, obstacles=None, region_scale=(0.0, 0.0, 0.0), distance_limit=DBL_MAX,
+              lazy=False, pose_costs=None):
+        """poses (n, 7) {x, y, z, qx, qy, qz, qw}; runs a list of (instance, first_pose, n_poses), default one run of every pose on
+        instance 0.  Returns (pose_costs (n,), results: RUN_RESULT_DTYPE per run).  pose_costs, when given, is written in place:
+        with lazy the entries behind a run's first lethal pose keep what they held (NaN in a fresh array)."""
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        r = self._runs(runs, len(p))
+        reg = None if regions is None else np.ascontiguousarray(regions, np.uint8)
+        obs = None if obstacles is None else np.ascontiguousarray(obstacles, np.uint8)
+        assert all(a is None or len(a) == len(p) for a in (reg, obs))
+        scale = np.ascontiguousarray(region_scale, np.float64).reshape(3)
+        costs = np.full(len(p), np.nan) if pose_costs is None else pose_costs
+        assert costs.dtype == np.float64 and costs.flags.c_contiguous and len(costs) == len(p)
+        results = np.zeros(len(r), RUN_RESULT_DTYPE)
+        check(self.L.navgpu_costmap3d_query(self.h, len(r), _ptr(r), _ptr(p), mode, _ptr(reg), _ptr(obs), _ptr(scale), float(distance_limit), int(lazy),
+                                            _ptr(costs), _ptr(results)), "navgpu_costmap3d_query")
+        return costs, results
+
+    def footprint_costs(self, poses_xyth, runs=None):
+        """poses (n, 3) {x, y, theta}.  Returns (costs (n,), first_illegal per run)."""
+        p = np.ascontiguousarray(poses_xyth, np.float64).reshape(-1, 3)
+        r = self._runs(runs, len(p))
+        costs, first = np.full(len(p), np.nan), np.zeros(len(r), np.int32)
+        check(self.L.navgpu_costmap3d_footprint_costs(self.h, len(r), _ptr(r), _ptr(p), _ptr(costs), _ptr(first)), "navgpu_costmap3d_footprint_costs")
+        return costs, first
