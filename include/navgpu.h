@@ -1997,6 +1997,10 @@ int navgpu_costmap3d_query(navgpu_costmap3d* c3d, uint32_t n_runs, const navgpu_
 int navgpu_costmap3d_footprint_costs(navgpu_costmap3d* c3d, uint32_t n_runs, const navgpu_c3d_run* runs, const double* poses_xyth,
                                      double* costs_out, int32_t* first_illegal_out);
 
+/* The handle's layered map update from point clouds and its projection into 2-D: configure_layers, layer_set,
+ * buffer_clouds, set_static_grid, update, reset, layer2d_download, layer2d_update_costs and the layers' raw column access. */
+#include "navgpu_costmap3d_layers.h"
+
 #ifdef __cplusplus
 }
 #endif

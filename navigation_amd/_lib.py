@@ -489,6 +489,24 @@ C3D_COST, C3D_COLLISION_ONLY, C3D_DISTANCE = 0, 1, 2
 C3D_REGION_ALL, C3D_REGION_LEFT, C3D_REGION_RIGHT, C3D_REGION_RECTANGULAR_PRISM = 0, 1, 2, 3
 
 
+class C3dLayer(C.Structure):
+    """Mirror of navgpu_c3d_layer (include/navgpu_costmap3d_layers.h)."""
+    _fields_ = [("kind", C.c_int32), ("enabled", C.c_int32), ("combination_method", C.c_int32), ("cloud_has_intensity", C.c_int32),
+                ("free_intensity", C.c_float), ("lethal_intensity", C.c_float), ("lethal_cost_threshold", C.c_int32),
+                ("unknown_to_lethal", C.c_int32), ("height", C.c_double), ("radius", C.c_double), ("max_cloud_points", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class C3dCloud(C.Structure):
+    """Mirror of navgpu_c3d_cloud (include/navgpu_costmap3d_layers.h)."""
+    _fields_ = [("instance", C.c_uint32), ("layer", C.c_uint32), ("first_point", C.c_uint32), ("n_points", C.c_uint32), ("transform", C.c_double * 12)]
+
+
+C3D_MAX_LAYERS = 8
+C3D_LAYER_POINT_CLOUD, C3D_LAYER_STATIC_2D, C3D_LAYER_CYLINDER_CLEARING = 0, 1, 2
+C3D_COMBINE_OVERWRITE, C3D_COMBINE_MAXIMUM, C3D_COMBINE_IF_UNKNOWN, C3D_COMBINE_NOTHING = 0, 1, 2, 99
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -694,6 +712,16 @@ SYMBOLS = [
     ("navgpu_costmap3d_set_mesh", C.c_int, [vp, vp, u32, vp, u32, dbl, C.POINTER(i32)]),
     ("navgpu_costmap3d_query", C.c_int, [vp, u32, vp, vp, i32, vp, vp, vp, dbl, i32, vp, vp]),
     ("navgpu_costmap3d_footprint_costs", C.c_int, [vp, u32, vp, vp, vp, vp]),
+    ("navgpu_costmap3d_configure_layers", C.c_int, [vp, vp, u32, i32]),
+    ("navgpu_costmap3d_layer_set", C.c_int, [vp, u32, i32, i32]),
+    ("navgpu_costmap3d_buffer_clouds", C.c_int, [vp, vp, u32, vp, u32, vp]),
+    ("navgpu_costmap3d_set_static_grid", C.c_int, [vp, u32, u32, vp, u32, u32, dbl, dbl, C.POINTER(u32)]),
+    ("navgpu_costmap3d_update", C.c_int, [vp, u32, vp, vp, vp]),
+    ("navgpu_costmap3d_reset", C.c_int, [vp, u32, vp]),
+    ("navgpu_costmap3d_layer2d_download", C.c_int, [vp, u32, u32, u32, u32, u32, vp]),
+    ("navgpu_costmap3d_layer2d_update_costs", C.c_int, [vp, u32, vp, vp, C.c_size_t, u32, u32, u32, vp, i32]),
+    ("navgpu_costmap3d_layer_columns_download", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
+    ("navgpu_costmap3d_free_columns_download", C.c_int, [vp, u32, vp]),
 ]
 
 

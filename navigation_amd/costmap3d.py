@@ -7,6 +7,9 @@
                           (costmap_3d/src/costmap_3d_ros.cpp:464-616; costmap_3d_query.cpp:493-521, 586-970)
   footprint_costs         base_local_planner::Costmap3DModel::footprintCost              (base_local_planner/src/costmap_3d_model.cpp:61-79)
   columns / set_columns   the resident bit volumes themselves
+  configure_layers, layer_set, buffer_clouds, set_static_grid, update, reset, layer2d, update_costs_2d, layer_columns, free_columns
+                          the layered map update from point clouds and its projection into 2-D (include/navgpu_costmap3d_layers.h):
+                          PointCloudLayer3D, Static2DLayer3D, CylinderClearingLayer3D, LayeredCostmap3D::updateMap, Costmap3DTo2DLayer
   load_stl                a binary STL as (vertices, triangles), equal corners merged
   load_octomap_bt         an octomap binary tree (.bt) as its occupied leaves: centres, sizes, classes
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers and reads the two file formats.
@@ -16,11 +19,14 @@ import struct
 
 import numpy as np
 
-from ._lib import (C3D_DISTANCE, C3D_LETHAL, C3D_REPLACE, C3dBox, C3dRun, C3dRunResult, Costmap3DDesc, check, lib)
+from ._lib import (C3D_DISTANCE, C3D_LETHAL, C3D_REPLACE, GRID_MASTER, C3dBox, C3dCloud, C3dLayer, C3dRun, C3dRunResult, Costmap3DDesc, check, lib)
 
 BOX_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("cz", "<f8"), ("size", "<f8"), ("cls", "<i4"), ("reserved", "<i4")])
 RUN_DTYPE = np.dtype([("instance", "<u4"), ("first_pose", "<u4"), ("n_poses", "<u4")])
 RUN_RESULT_DTYPE = np.dtype([("cost", "<f8"), ("n_lethal", "<i4"), ("first_lethal", "<i4"), ("n_done", "<i4"), ("reserved", "<i4")])
+CLOUD_DTYPE = np.dtype([("instance", "<u4"), ("layer", "<u4"), ("first_point", "<u4"), ("n_points", "<u4"), ("transform", "<f8", 12)])
+IDENTITY_TRANSFORM = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+assert CLOUD_DTYPE.itemsize == C.sizeof(C3dCloud)
 assert BOX_DTYPE.itemsize == C.sizeof(C3dBox) and RUN_DTYPE.itemsize == C.sizeof(C3dRun) and RUN_RESULT_DTYPE.itemsize == C.sizeof(C3dRunResult)
 DBL_MAX = float(np.finfo(np.float64).max)
 
@@ -191,3 +197,80 @@ class Costmap3D:
         costs, first = np.full(len(p), np.nan), np.zeros(len(r), np.int32)
         check(self.L.navgpu_costmap3d_footprint_costs(self.h, len(r), _ptr(r), _ptr(p), _ptr(costs), _ptr(first)), "navgpu_costmap3d_footprint_costs")
         return costs, first
+
+    # ---- the layered map update (include/navgpu_costmap3d_layers.h) ----
+    def configure_layers(self, layers, nonlethal_cost_2d=127):
+        """layers: dicts with the fields of navgpu_c3d_layer (kind and whatever its kind reads; enabled defaults to 1, the method to
+        Maximum, max_cloud_points to 65536), in the order the stack applies them."""
+        recs = (C3dLayer * len(layers))()
+        for k, spec in enumerate(layers):
+            d = dict(enabled=1, combination_method=1, max_cloud_points=1 << 16)
+            d.update(spec)
+            recs[k] = C3dLayer(**d)
+        check(self.L.navgpu_costmap3d_configure_layers(self.h, recs, len(layers), int(nonlethal_cost_2d)), "navgpu_costmap3d_configure_layers")
+
+    def layer_set(self, layer, enabled, combination_method):
+        check(self.L.navgpu_costmap3d_layer_set(self.h, layer, int(enabled), int(combination_method)), "navgpu_costmap3d_layer_set")
+
+    def buffer_clouds(self, clouds, points):
+        """clouds: a list of (instance, layer, first_point, n_points[, transform12]); points (n, 3) or (n, 4) float32 by the layers'
+        format.  Returns the number of points dropped per cloud."""
+        c = np.zeros(len(clouds), CLOUD_DTYPE)
+        for k, rec in enumerate(clouds):
+            c[k] = tuple(rec[:4]) + (tuple(rec[4]) if len(rec) > 4 else IDENTITY_TRANSFORM,)
+        p = np.ascontiguousarray(points, np.float32)
+        assert p.ndim == 2 and p.shape[1] in (3, 4)
+        clipped = np.zeros(len(c), np.uint32)
+        check(self.L.navgpu_costmap3d_buffer_clouds(self.h, _ptr(c), len(c), _ptr(p), len(p), _ptr(clipped)), "navgpu_costmap3d_buffer_clouds")
+        return clipped
+
+    def set_static_grid(self, instance, layer, occupancy, origin_x, origin_y):
+        """occupancy (height, width) int8 at the map's resolution.  Returns the number of cells that fell outside the extents."""
+        g = np.ascontiguousarray(occupancy, np.int8)
+        assert g.ndim == 2
+        clipped = C.c_uint32(0)
+        check(self.L.navgpu_costmap3d_set_static_grid(self.h, instance, layer, _ptr(g), g.shape[1], g.shape[0], float(origin_x), float(origin_y),
+                                                      C.byref(clipped)), "navgpu_costmap3d_set_static_grid")
+        return clipped.value
+
+    def update(self, instances, robot_poses_xyz):
+        """Returns the 2-D bounds (n, 4) = min_x, min_y, max_x, max_y per listed instance ((1e6, 1e6, -1e6, -1e6): none)."""
+        ins = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        poses = np.ascontiguousarray(robot_poses_xyz, np.float64).reshape(-1, 3)
+        assert len(poses) == len(ins)
+        bounds = np.zeros((len(ins), 4))
+        check(self.L.navgpu_costmap3d_update(self.h, len(ins), _ptr(ins), _ptr(poses), _ptr(bounds)), "navgpu_costmap3d_update")
+        return bounds
+
+    def reset(self, instances=None):
+        ins = np.arange(self.n, dtype=np.uint32) if instances is None else np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        check(self.L.navgpu_costmap3d_reset(self.h, len(ins), _ptr(ins)), "navgpu_costmap3d_reset")
+
+    def layer2d(self, instance, x0=0, y0=0, xn=None, yn=None):
+        xn = self.size_x if xn is None else xn
+        yn = self.size_y if yn is None else yn
+        out = np.zeros((max(yn - y0, 0), max(xn - x0, 0)), np.uint8)
+        check(self.L.navgpu_costmap3d_layer2d_download(self.h, instance, x0, y0, xn, yn, _ptr(out)), "navgpu_costmap3d_layer2d_download")
+        return out
+
+    def update_costs_2d(self, fleet, instances, boxes_ij, use_maximum=True):
+        """Costmap3DTo2DLayer::updateCosts into the fleet's master grid: boxes_ij (n, 4) = min_i, min_j, max_i, max_j.  The fleet
+        must be idle meanwhile."""
+        ins = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        boxes = np.ascontiguousarray(boxes_ij, np.int32).reshape(-1, 4)
+        assert len(boxes) == len(ins)
+        ptr, stride = fleet.grid_device(GRID_MASTER)
+        check(self.L.navgpu_costmap3d_layer2d_update_costs(self.h, len(ins), _ptr(ins), ptr, stride, fleet.desc.n_instances, fleet.desc.size_x,
+                                                           fleet.desc.size_y, _ptr(boxes), int(bool(use_maximum))),
+              "navgpu_costmap3d_layer2d_update_costs")
+
+    def layer_columns(self, instance, layer):
+        """(lethal, nonlethal, free, changed) of a costmap layer: (size_y, size_x) uint64 each"""
+        planes = [np.zeros((self.size_y, self.size_x), np.uint64) for _ in range(4)]
+        check(self.L.navgpu_costmap3d_layer_columns_download(self.h, instance, layer, *[_ptr(p) for p in planes]), "navgpu_costmap3d_layer_columns_download")
+        return tuple(planes)
+
+    def free_columns(self, instance):
+        free = np.zeros((self.size_y, self.size_x), np.uint64)
+        check(self.L.navgpu_costmap3d_free_columns_download(self.h, instance, _ptr(free)), "navgpu_costmap3d_free_columns_download")
+        return free

@@ -3,12 +3,34 @@
 #include <cfloat>
 #include <cmath>
 #include <map>
+#include <memory>
+#include <type_traits>
 
 #include "navgpu_costmap3d.h"
 #include "navgpu_fleet.h"
 
+// what navgpu_costmap3d_configure_layers adds to a handle (include/navgpu_costmap3d_layers.h)
+struct C3dLayers {
+  std::vector<navgpu_c3d_layer> layers;
+  std::vector<uint32_t> index;     // per layer: its slot (costmap layers) or its number among the cylinder layers
+  uint32_t n_cyl = 0, max_points = 0;
+  C3dLayersDev ly{};
+  std::vector<uint32_t> cur;       // [n][nc] which plane set is current
+  std::vector<uint32_t> full;      // [n] size_changed_ / copy_full_map_
+  struct Cyl { bool has = false; double x = 0, y = 0; };
+  std::vector<Cyl> prev;           // [n][n_cyl] CylinderClearingLayer3D::clearing_bounds_map_, as the position it was built round
+  std::vector<void*> allocs;
+  uint8_t *d_stage = nullptr, *h_stage = nullptr;  // a call's records: one upload (h_stage pinned); the read-back comes into its tail
+  size_t stage_bytes = 0;
+  float* d_points = nullptr;       // [max_points][4]
+  int8_t* d_grid = nullptr;        // a static grid on its way in; grows on demand
+  size_t grid_bytes = 0;
+  bool resident = false;           // the device buffers exist (openLayers)
+};
+
 struct navgpu_costmap3d {
   navgpu_costmap3d_desc desc{};
+  C3dLayers* layered = nullptr;
   C3dDev dv{};
   bool opened = false;
   std::recursive_mutex mu;  // calls on one handle are serialised inside the library (as on a fleet)
@@ -197,6 +219,15 @@ int runQuery(navgpu_costmap3d* h, uint32_t n_runs, const navgpu_c3d_run* runs, c
   return NAVGPU_OK;
 }
 
+void freeLayers(navgpu_costmap3d* h) {
+  if (!h->layered) return;
+  for (void* p : h->layered->allocs) hipFree(p);
+  if (h->layered->d_grid) hipFree(h->layered->d_grid);
+  if (h->layered->h_stage) hipHostFree(h->layered->h_stage);
+  delete h->layered;
+  h->layered = nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,8 +261,10 @@ int navgpu_costmap3d_destroy(navgpu_costmap3d* h) {
     hipHostFree(h->h_boxes);
     hipHostFree(h->h_in);
     hipHostFree(h->h_out);
+    freeLayers(h);
     hipStreamDestroy(h->stream);
   }
+  delete h->layered;
   delete h;
   return NAVGPU_OK;
 }
@@ -423,6 +456,547 @@ int navgpu_costmap3d_footprint_costs(navgpu_costmap3d* h, uint32_t n_runs, const
   if (rc) return rc;
   if (first_illegal_out)
     for (uint32_t r = 0; r < n_runs; ++r) first_illegal_out[r] = res[r].first_lethal;
+  return NAVGPU_OK;
+}
+
+}  // extern "C"
+
+// ---- the layered map update (include/navgpu_costmap3d_layers.h, costmap3d_layer_kernels.hip) ----
+namespace {
+
+bool costmapLayer(const navgpu_c3d_layer& l) { return l.kind == NAVGPU_C3D_LAYER_POINT_CLOUD || l.kind == NAVGPU_C3D_LAYER_STATIC_2D; }
+bool knownMethod(int32_t m) {
+  return m == NAVGPU_C3D_COMBINE_OVERWRITE || m == NAVGPU_C3D_COMBINE_MAXIMUM || m == NAVGPU_C3D_COMBINE_IF_UNKNOWN || m == NAVGPU_C3D_COMBINE_NOTHING;
+}
+
+// ok = llround(origin / resolution) per axis; false unless the origin is a multiple of the resolution to 1e-6 of a cell
+bool originKeys(const navgpu_costmap3d* h, uint32_t instance, int64_t ok[3]) {
+  for (int a = 0; a < 3; ++a) {
+    const double f = h->origins[3 * (size_t)instance + a] / h->desc.resolution;
+    if (!std::isfinite(f) || std::fabs(f) > 1073741824.0 || std::fabs(f - std::nearbyint(f)) > 1e-6) {
+      g_last_error = "costmap3d layers: the origin of instance " + std::to_string(instance) + " is not a multiple of the resolution";
+      return false;
+    }
+    ok[a] = std::llround(f);
+  }
+  return true;
+}
+
+// octomap's coordToKeyClamped less the origin's key
+int32_t clampedKey(double c, double inv_res, int64_t ok, uint32_t size) {
+  const double k = std::floor(c * inv_res) - (double)ok;
+  return k <= 0.0 ? 0 : k >= (double)(size - 1) ? (int32_t)(size - 1) : (int32_t)k;
+}
+
+// a call's records, packed into the pinned block behind one another (16-byte aligned) for one upload
+struct Stage {
+  C3dLayers* L;
+  size_t at = 0;
+  template <class T>
+  size_t put(const T* src, size_t count) {
+    const size_t o = at;
+    if (count) memcpy(L->h_stage + o, src, sizeof(T) * count);
+    at = (o + sizeof(T) * count + 15) & ~(size_t)15;
+    return o;
+  }
+  template <class T>
+  T* dev(size_t o) const { return reinterpret_cast<T*>(L->d_stage + o); }
+  template <class T>
+  T* host(size_t o) const { return reinterpret_cast<T*>(L->h_stage + o); }
+};
+
+int layeredHandle(navgpu_costmap3d* h, const char* what) {
+  if (h->layered) return NAVGPU_OK;
+  g_last_error = std::string(what) + ": navgpu_costmap3d_configure_layers has not been called";
+  return NAVGPU_ERR_STATE;
+}
+
+// distinct instances below n_instances
+int checkInstanceList(const navgpu_costmap3d* h, uint32_t n, const uint32_t* instances) {
+  if (n && !instances) return NAVGPU_ERR_INVALID;
+  if (n > h->desc.n_instances) return NAVGPU_ERR_INVALID;  // (some instance twice)
+  std::vector<uint8_t> seen(h->desc.n_instances, 0);
+  for (uint32_t k = 0; k < n; ++k) {
+    if (instances[k] >= h->desc.n_instances || seen[instances[k]]) {
+      g_last_error = "costmap3d layers: an instance is out of range or listed twice";
+      return NAVGPU_ERR_INVALID;
+    }
+    seen[instances[k]] = 1;
+  }
+  return NAVGPU_OK;
+}
+
+// the first layer call that needs the device: every buffer of the layered update, all or nothing
+int openLayers(navgpu_costmap3d* h) {
+  int rc = openDevice(h);
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  if (L->resident) return NAVGPU_OK;
+  C3dLayersDev& ly = L->ly;
+  const size_t n = h->desc.n_instances, cols = h->dv.cols, nc = ly.nc;
+  // the staging block holds the largest of: a buffer_clouds call's records, an update's, an update_costs call's
+  const size_t pairs = n * std::max<size_t>(nc, 1);
+  L->stage_bytes = pairs * (sizeof(C3dCloudRec) + 3 * sizeof(uint32_t) + 2 * sizeof(uint32_t)) +
+                   n * (sizeof(uint32_t) * (2 + nc) + 3 * sizeof(int64_t) + sizeof(C3dCylRec) * L->n_cyl + 8 * sizeof(int32_t)) + sizeof(C3dGridRec) + 16 * 16;
+  auto dalloc = [&](auto** p, size_t count) {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(**p), 16);
+    if (rc) return;
+    if (hipMalloc(&q, bytes) != hipSuccess || hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) {
+      if (q) hipFree(q);
+      g_last_error = "hipMalloc failed (costmap3d layers)";
+      rc = NAVGPU_ERR_HIP;
+      return;
+    }
+    L->allocs.push_back(q);
+    *p = static_cast<std::remove_reference_t<decltype(*p)>>(q);
+  };
+  dalloc(&ly.sets, n * nc * 2 * 3 * cols);
+  dalloc(&ly.changed, n * nc * cols);
+  dalloc(&ly.occ, n * nc * 2 * ly.tw);
+  dalloc(&ly.dirty, n * ly.tw);
+  dalloc(&ly.free_plane, n * cols);
+  dalloc(&ly.layer2d, n * cols);
+  dalloc(&L->d_stage, L->stage_bytes);
+  dalloc(&L->d_points, (size_t)L->max_points * 4);
+  if (!rc && hipHostMalloc((void**)&L->h_stage, L->stage_bytes, hipHostMallocDefault) != hipSuccess) {
+    L->h_stage = nullptr;
+    g_last_error = "hipHostMalloc failed (costmap3d layers)";
+    rc = NAVGPU_ERR_HIP;
+  }
+  if (!rc) {
+    launch_c3d_fill_u8(ly.layer2d, 255, n * cols, h->stream);  // NO_INFORMATION
+    rc = checkLaunch();
+  }
+  if (!rc && waitStream(h->stream) != hipSuccess) rc = NAVGPU_ERR_HIP;
+  if (rc) {  // the next call starts over
+    for (void* q : L->allocs) hipFree(q);
+    L->allocs.clear();
+    if (L->h_stage) hipHostFree(L->h_stage);
+    L->h_stage = nullptr;
+    return rc;
+  }
+  L->resident = true;
+  return NAVGPU_OK;
+}
+
+// the swap (mode 0) or the touch (mode 1) of the pairs whose records (instance, slot, next) are staged at o_pairs
+int queueSwap(navgpu_costmap3d* h, const Stage& st, size_t o_pairs, uint32_t n_pairs, int32_t mode) {
+  launch_c3d_layer_swap(h->dv, h->layered->ly, st.dev<uint32_t>(o_pairs), n_pairs, mode, h->stream);
+  return checkLaunch();
+}
+
+}  // namespace
+
+extern "C" {
+
+int navgpu_costmap3d_configure_layers(navgpu_costmap3d* h, const navgpu_c3d_layer* layers, uint32_t n_layers, int32_t nonlethal_cost_2d) {
+  if (!h || !layers || !n_layers || n_layers > NAVGPU_C3D_MAX_LAYERS || nonlethal_cost_2d < 0 || nonlethal_cost_2d > 255) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  std::unique_ptr<C3dLayers> L(new C3dLayers());
+  uint32_t nc = 0;
+  for (uint32_t l = 0; l < n_layers; ++l) {
+    const navgpu_c3d_layer& y = layers[l];
+    bool ok = knownMethod(y.combination_method);
+    switch (y.kind) {
+      case NAVGPU_C3D_LAYER_POINT_CLOUD:
+        ok = ok && y.max_cloud_points > 0 &&
+             (!y.cloud_has_intensity || (std::isfinite(y.free_intensity) && std::isfinite(y.lethal_intensity) && y.free_intensity != y.lethal_intensity));
+        L->max_points = std::max(L->max_points, y.max_cloud_points);
+        L->index.push_back(nc++);
+        break;
+      case NAVGPU_C3D_LAYER_STATIC_2D:
+        ok = ok && y.lethal_cost_threshold >= 0 && y.lethal_cost_threshold <= 255 && std::isfinite(y.height);
+        L->index.push_back(nc++);
+        break;
+      case NAVGPU_C3D_LAYER_CYLINDER_CLEARING:
+        ok = ok && std::isfinite(y.radius);
+        L->index.push_back(L->n_cyl++);
+        break;
+      default: ok = false;
+    }
+    if (!ok) {
+      g_last_error = "navgpu_costmap3d_configure_layers: layer " + std::to_string(l) + " has an unknown kind or method, or a parameter out of range";
+      return NAVGPU_ERR_INVALID;
+    }
+    L->layers.push_back(y);
+    L->layers.back().radius = std::fabs(y.radius);
+  }
+  const size_t n = h->desc.n_instances;
+  if (h->opened) {  // a second call reconfigures from scratch; sizeChange empties the master too (a handle not opened yet has an empty one)
+    HIP_TRY(hipSetDevice(h->desc.device));
+    HIP_TRY(waitStream(h->stream));
+    HIP_TRY(hipMemsetAsync(h->dv.planes, 0, sizeof(uint64_t) * n * 2 * h->dv.cols, h->stream));
+  }
+  freeLayers(h);
+  C3dLayersDev& ly = L->ly;
+  ly.nc = nc;
+  ly.tpr = (h->dv.sx + 63) / 64;
+  ly.tiles = ly.tpr * h->dv.sy;
+  ly.tw = (ly.tiles + 31) / 32;
+  ly.nonlethal_cost_2d = nonlethal_cost_2d;
+  ly.all_tiles = NAVGPU_DEBUG_ENV("NAVGPU_C3D_ALL_TILES") ? 1 : 0;
+  ly.inv_res = 1.0 / h->desc.resolution;
+  L->cur.assign(n * nc, 0);
+  L->full.assign(n, 1);
+  L->prev.assign(n * L->n_cyl, C3dLayers::Cyl());
+  h->layered = L.release();
+  return NAVGPU_OK;  // the buffers come with the first call that needs the device (openLayers)
+}
+
+int navgpu_costmap3d_layer_set(navgpu_costmap3d* h, uint32_t layer, int32_t enabled, int32_t combination_method) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_layer_set");
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  if (layer >= L->layers.size() || !knownMethod(combination_method)) return NAVGPU_ERR_INVALID;
+  navgpu_c3d_layer& y = L->layers[layer];
+  const bool differs = (y.enabled != 0) != (enabled != 0) || y.combination_method != combination_method;
+  if (differs && costmapLayer(y) && L->resident) {  // touch: every present cell of the layer, in every instance (nothing is present before the buffers exist)
+    const uint32_t slot = L->index[layer];
+    std::vector<uint32_t> pairs;
+    for (uint32_t i = 0; i < h->desc.n_instances; ++i) {
+      const uint32_t c = L->cur[(size_t)i * L->ly.nc + slot];
+      pairs.insert(pairs.end(), {i, slot, c ^ 1u});
+    }
+    HIP_TRY(hipSetDevice(h->desc.device));
+    HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+    Stage st{L};
+    const size_t o = st.put(pairs.data(), pairs.size());
+    HIP_TRY(hipMemcpyAsync(L->d_stage, L->h_stage, st.at, hipMemcpyHostToDevice, h->stream));
+    if ((rc = queueSwap(h, st, o, h->desc.n_instances, 1))) return rc;
+  }
+  y.enabled = enabled;
+  y.combination_method = combination_method;
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_buffer_clouds(navgpu_costmap3d* h, const navgpu_c3d_cloud* clouds, uint32_t n_clouds, const float* points, uint32_t n_points,
+                                   uint32_t* clipped_out) {
+  if (!h || (n_clouds && !clouds) || (n_points && !points)) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_buffer_clouds");
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  const uint32_t nc = L->ly.nc;
+  if (n_points > L->max_points) return NAVGPU_ERR_CAPACITY;
+  std::vector<C3dCloudRec> recs(n_clouds);
+  std::vector<uint32_t> pairs(3 * (size_t)n_clouds);
+  std::vector<uint8_t> seen((size_t)h->desc.n_instances * std::max<uint32_t>(nc, 1), 0);
+  uint32_t max_points = 0;
+  int format = -1;
+  for (uint32_t k = 0; k < n_clouds; ++k) {
+    const navgpu_c3d_cloud& c = clouds[k];
+    if (c.instance >= h->desc.n_instances || c.layer >= L->layers.size() || L->layers[c.layer].kind != NAVGPU_C3D_LAYER_POINT_CLOUD) {
+      g_last_error = "navgpu_costmap3d_buffer_clouds: cloud " + std::to_string(k) + " names no instance or no POINT_CLOUD layer";
+      return NAVGPU_ERR_INVALID;
+    }
+    const navgpu_c3d_layer& y = L->layers[c.layer];
+    const uint32_t slot = L->index[c.layer];
+    uint8_t& mark = seen[(size_t)c.instance * nc + slot];
+    const int fmt = y.cloud_has_intensity ? 1 : 0;
+    if (mark || (format >= 0 && fmt != format) || (uint64_t)c.first_point + c.n_points > n_points) {
+      g_last_error = "navgpu_costmap3d_buffer_clouds: cloud " + std::to_string(k) +
+                     " shares its (instance, layer) with another, mixes point formats, or ends beyond n_points";
+      return NAVGPU_ERR_INVALID;
+    }
+    mark = 1;
+    format = fmt;
+    for (double v : c.transform)
+      if (!std::isfinite(v)) return NAVGPU_ERR_INVALID;
+    C3dCloudRec& r = recs[k];
+    if (!originKeys(h, c.instance, r.ok)) return NAVGPU_ERR_INVALID;
+    std::copy_n(c.transform, 12, r.tf);
+    r.instance = c.instance;
+    r.slot = slot;
+    r.next = L->cur[(size_t)c.instance * nc + slot] ^ 1u;
+    r.first_point = c.first_point;
+    r.n_points = c.n_points;
+    r.has_intensity = (uint32_t)fmt;
+    r.free_intensity = y.free_intensity;
+    r.lethal_intensity = y.lethal_intensity;
+    pairs[3 * (size_t)k] = r.instance;
+    pairs[3 * (size_t)k + 1] = r.slot;
+    pairs[3 * (size_t)k + 2] = r.next;
+    max_points = std::max(max_points, c.n_points);
+  }
+  if (!n_clouds) return NAVGPU_OK;
+  if ((rc = openLayers(h))) return rc;
+  HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+  Stage st{L};
+  const size_t o_recs = st.put(recs.data(), recs.size()), o_pairs = st.put(pairs.data(), pairs.size());
+  const std::vector<uint32_t> zeros(n_clouds, 0);
+  const size_t o_clip = st.put(zeros.data(), zeros.size());
+  HIP_TRY(hipMemcpyAsync(L->d_stage, L->h_stage, st.at, hipMemcpyHostToDevice, h->stream));
+  if (n_points) HIP_TRY(hipMemcpyAsync(L->d_points, points, sizeof(float) * (format ? 4 : 3) * (size_t)n_points, hipMemcpyHostToDevice, h->stream));
+  launch_c3d_cloud(h->dv, L->ly, st.dev<C3dCloudRec>(o_recs), n_clouds, max_points, L->d_points, st.dev<uint32_t>(o_clip), h->stream);
+  if ((rc = checkLaunch())) return rc;
+  if ((rc = queueSwap(h, st, o_pairs, n_clouds, 0))) return rc;
+  for (uint32_t k = 0; k < n_clouds; ++k) L->cur[(size_t)recs[k].instance * nc + recs[k].slot] = recs[k].next;
+  HIP_TRY(hipMemcpyAsync(st.host<uint32_t>(o_clip), st.dev<uint32_t>(o_clip), sizeof(uint32_t) * n_clouds, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));  // (the caller's points are free again)
+  if (clipped_out) std::copy_n(st.host<uint32_t>(o_clip), n_clouds, clipped_out);
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_set_static_grid(navgpu_costmap3d* h, uint32_t instance, uint32_t layer, const int8_t* occupancy, uint32_t width, uint32_t height,
+                                     double origin_x, double origin_y, uint32_t* clipped_out) {
+  if (!h || !occupancy) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_set_static_grid");
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  if (instance >= h->desc.n_instances || layer >= L->layers.size() || L->layers[layer].kind != NAVGPU_C3D_LAYER_STATIC_2D || !width || !height ||
+      (uint64_t)width * height > kC3dMaxColumns || !std::isfinite(origin_x) || !std::isfinite(origin_y))
+    return NAVGPU_ERR_INVALID;
+  const navgpu_c3d_layer& y = L->layers[layer];
+  C3dGridRec rec{};
+  if (!originKeys(h, instance, rec.ok)) return NAVGPU_ERR_INVALID;
+  const size_t cells = (size_t)width * height;
+  const uint32_t slot = L->index[layer];
+  rec.origin_x = origin_x;
+  rec.origin_y = origin_y;
+  rec.height = y.height;
+  rec.instance = instance;
+  rec.slot = slot;
+  rec.next = L->cur[(size_t)instance * L->ly.nc + slot] ^ 1u;
+  rec.width = width;
+  rec.rows = height;
+  rec.threshold = y.lethal_cost_threshold;
+  rec.unknown_to_lethal = y.unknown_to_lethal ? 1 : 0;
+  if ((rc = openLayers(h))) return rc;
+  HIP_TRY(waitStream(h->stream));
+  if (L->grid_bytes < cells) {
+    if (L->d_grid) HIP_TRY(hipFree(L->d_grid));
+    L->d_grid = nullptr;
+    L->grid_bytes = 0;
+    HIP_TRY(hipMalloc((void**)&L->d_grid, cells));
+    L->grid_bytes = cells;
+  }
+  Stage st{L};
+  const uint32_t pair[3] = {instance, slot, rec.next}, zero = 0;
+  const size_t o_rec = st.put(&rec, 1), o_pair = st.put(pair, 3), o_clip = st.put(&zero, 1);
+  HIP_TRY(hipMemcpyAsync(L->d_stage, L->h_stage, st.at, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(L->d_grid, occupancy, cells, hipMemcpyHostToDevice, h->stream));
+  launch_c3d_static2d(h->dv, L->ly, st.dev<C3dGridRec>(o_rec), cells, L->d_grid, st.dev<uint32_t>(o_clip), h->stream);
+  if ((rc = checkLaunch())) return rc;
+  if ((rc = queueSwap(h, st, o_pair, 1, 0))) return rc;
+  L->cur[(size_t)instance * L->ly.nc + slot] = rec.next;
+  HIP_TRY(hipMemcpyAsync(st.host<uint32_t>(o_clip), st.dev<uint32_t>(o_clip), sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  if (clipped_out) *clipped_out = *st.host<uint32_t>(o_clip);
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_update(navgpu_costmap3d* h, uint32_t n, const uint32_t* instances, const double* robot_poses_xyz, double* bounds2d_out) {
+  if (!h || (n && !robot_poses_xyz)) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_update");
+  if (rc) return rc;
+  if ((rc = checkInstanceList(h, n, instances))) return rc;
+  C3dLayers* L = h->layered;
+  const uint32_t nc = L->ly.nc, n_cyl = L->n_cyl;
+  std::vector<int64_t> ok(3 * (size_t)n);
+  std::vector<uint32_t> cur((size_t)n * nc), full(n);
+  std::vector<C3dCylRec> cyl((size_t)n * n_cyl);
+  std::vector<C3dLayers::Cyl> prev_after((size_t)n * n_cyl);
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t i = instances[k];
+    const double* pose = robot_poses_xyz + 3 * (size_t)k;
+    if (!finite3(pose)) {
+      g_last_error = "navgpu_costmap3d_update: a robot pose is not finite";
+      return NAVGPU_ERR_INVALID;
+    }
+    if (!originKeys(h, i, ok.data() + 3 * (size_t)k)) return NAVGPU_ERR_INVALID;
+    std::copy_n(L->cur.begin() + (size_t)i * nc, nc, cur.begin() + (size_t)k * nc);
+    full[k] = L->full[i];
+    for (uint32_t l = 0; l < L->layers.size(); ++l) {
+      const navgpu_c3d_layer& y = L->layers[l];
+      if (y.kind != NAVGPU_C3D_LAYER_CYLINDER_CLEARING) continue;
+      const uint32_t c = L->index[l];
+      const C3dLayers::Cyl& was = L->prev[(size_t)i * n_cyl + c];
+      C3dCylRec& r = cyl[(size_t)k * n_cyl + c];
+      const int64_t* o = ok.data() + 3 * (size_t)k;
+      auto keyBox = [&](double x, double yy, int32_t* box) {  // coordToKeyClamped of the corners (cylinder_clearing_layer_3d.cpp:98-109)
+        box[0] = clampedKey(x - y.radius, L->ly.inv_res, o[0], h->dv.sx);
+        box[1] = clampedKey(x + y.radius, L->ly.inv_res, o[0], h->dv.sx);
+        box[2] = clampedKey(yy - y.radius, L->ly.inv_res, o[1], h->dv.sy);
+        box[3] = clampedKey(yy + y.radius, L->ly.inv_res, o[1], h->dv.sy);
+      };
+      r = C3dCylRec{};
+      r.r = y.radius;
+      if (was.has) {
+        r.has_prev = 1;
+        r.px = was.x;
+        r.py = was.y;
+        keyBox(was.x, was.y, r.pbox);
+      }
+      C3dLayers::Cyl& then = prev_after[(size_t)k * n_cyl + c];
+      if (y.enabled) {
+        r.has_cur = 1;
+        r.cx = pose[0];
+        r.cy = pose[1];
+        keyBox(pose[0], pose[1], r.cbox);
+        then.has = true;
+        then.x = pose[0];
+        then.y = pose[1];
+      }  // (else: the previous set is forgotten after it has been added)
+    }
+  }
+  if (!n) return NAVGPU_OK;
+  if ((rc = openLayers(h))) return rc;
+  HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+  Stage st{L};
+  std::vector<int32_t> box(4 * (size_t)n);
+  for (uint32_t k = 0; k < n; ++k) {
+    box[4 * (size_t)k] = box[4 * (size_t)k + 1] = INT32_MAX;
+    box[4 * (size_t)k + 2] = box[4 * (size_t)k + 3] = INT32_MIN;
+  }
+  const size_t o_inst = st.put(instances, n), o_cur = st.put(cur.data(), cur.size()), o_full = st.put(full.data(), n), o_ok = st.put(ok.data(), ok.size()),
+               o_cyl = st.put(cyl.data(), cyl.size()), o_box = st.put(box.data(), box.size());
+  HIP_TRY(hipMemcpyAsync(L->d_stage, L->h_stage, st.at, hipMemcpyHostToDevice, h->stream));
+  C3dUpdate u{};
+  u.instances = st.dev<uint32_t>(o_inst);
+  u.cur = st.dev<uint32_t>(o_cur);
+  u.full = st.dev<uint32_t>(o_full);
+  u.ok = st.dev<int64_t>(o_ok);
+  u.cyl = st.dev<C3dCylRec>(o_cyl);
+  u.box = st.dev<int32_t>(o_box);
+  u.n = n;
+  u.n_cyl = n_cyl;
+  u.n_layers = (uint32_t)L->layers.size();
+  for (uint32_t l = 0; l < u.n_layers; ++l)
+    u.rules[l] = C3dLayerRule{L->layers[l].kind, L->layers[l].enabled ? 1 : 0, L->layers[l].combination_method, (int32_t)L->index[l]};
+  launch_c3d_combine(h->dv, L->ly, u, h->stream);
+  if ((rc = checkLaunch())) return rc;
+  for (uint32_t k = 0; k < n; ++k) {  // queued: the host's view follows
+    L->full[instances[k]] = 0;
+    std::copy_n(prev_after.begin() + (size_t)k * n_cyl, n_cyl, L->prev.begin() + (size_t)instances[k] * n_cyl);
+  }
+  HIP_TRY(hipMemcpyAsync(st.host<int32_t>(o_box), st.dev<int32_t>(o_box), sizeof(int32_t) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  if (bounds2d_out) {
+    const int32_t* got = st.host<int32_t>(o_box);
+    const double res = h->desc.resolution;
+    for (uint32_t k = 0; k < n; ++k) {  // addExtraBounds of the touched columns, then useExtraBounds (costmap_layer.cpp:34-60)
+      const int32_t* b = got + 4 * (size_t)k;
+      const double* org = h->origins.data() + 3 * (size_t)instances[k];
+      double* out = bounds2d_out + 4 * (size_t)k;
+      if (b[0] > b[2]) {
+        out[0] = out[1] = 1e6;
+        out[2] = out[3] = -1e6;
+      } else {
+        out[0] = org[0] + b[0] * res;
+        out[1] = org[1] + b[1] * res;
+        out[2] = org[0] + (b[2] + 1) * res;
+        out[3] = org[1] + (b[3] + 1) * res;
+      }
+    }
+  }
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_reset(navgpu_costmap3d* h, uint32_t n, const uint32_t* instances) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_reset");
+  if (rc) return rc;
+  if ((rc = checkInstanceList(h, n, instances))) return rc;
+  C3dLayers* L = h->layered;
+  const C3dLayersDev& ly = L->ly;
+  const size_t cols = h->dv.cols;
+  if (n && h->opened) HIP_TRY(hipSetDevice(h->desc.device));
+  for (uint32_t k = 0; k < n; ++k) {
+    const size_t i = instances[k];
+    L->full[i] = 1;
+    std::fill_n(L->prev.begin() + i * L->n_cyl, L->n_cyl, C3dLayers::Cyl());
+    if (h->opened) HIP_TRY(hipMemsetAsync(h->dv.planes + i * 2 * cols, 0, sizeof(uint64_t) * 2 * cols, h->stream));
+    if (!L->resident) continue;  // (nothing else exists yet: it is empty when it does)
+    HIP_TRY(hipMemsetAsync(ly.free_plane + i * cols, 0, sizeof(uint64_t) * cols, h->stream));
+    if (ly.nc) {
+      HIP_TRY(hipMemsetAsync(ly.sets + i * ly.nc * 6 * cols, 0, sizeof(uint64_t) * ly.nc * 6 * cols, h->stream));
+      HIP_TRY(hipMemsetAsync(ly.changed + i * ly.nc * cols, 0, sizeof(uint64_t) * ly.nc * cols, h->stream));
+      HIP_TRY(hipMemsetAsync(ly.occ + i * ly.nc * 2 * ly.tw, 0, sizeof(uint32_t) * ly.nc * 2 * ly.tw, h->stream));
+    }
+    HIP_TRY(hipMemsetAsync(ly.dirty + i * ly.tw, 0, sizeof(uint32_t) * ly.tw, h->stream));
+  }
+  return NAVGPU_OK;  // queued
+}
+
+int navgpu_costmap3d_layer2d_download(navgpu_costmap3d* h, uint32_t instance, uint32_t x0, uint32_t y0, uint32_t xn, uint32_t yn, uint8_t* out) {
+  if (!h || !out) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_layer2d_download");
+  if (rc) return rc;
+  if (instance >= h->desc.n_instances || x0 >= xn || y0 >= yn || xn > h->dv.sx || yn > h->dv.sy) return NAVGPU_ERR_INVALID;
+  if ((rc = openLayers(h))) return rc;
+  const uint8_t* src = h->layered->ly.layer2d + (size_t)instance * h->dv.cols + (size_t)y0 * h->dv.sx + x0;
+  HIP_TRY(hipMemcpy2DAsync(out, xn - x0, src, h->dv.sx, xn - x0, yn - y0, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_layer2d_update_costs(navgpu_costmap3d* h, uint32_t n, const uint32_t* instances, void* device_grid, size_t instance_stride_bytes,
+                                          uint32_t grid_instances, uint32_t size_x, uint32_t size_y, const int32_t* boxes_ij, int32_t use_maximum) {
+  if (!h || !device_grid || (n && !boxes_ij)) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_layer2d_update_costs");
+  if (rc) return rc;
+  if (size_x != h->dv.sx || size_y != h->dv.sy || instance_stride_bytes < (size_t)size_x * size_y) {
+    g_last_error = "navgpu_costmap3d_layer2d_update_costs: the grid's size differs from the 3-D map's columns";
+    return NAVGPU_ERR_INVALID;
+  }
+  if ((rc = checkInstanceList(h, n, instances))) return rc;
+  for (uint32_t k = 0; k < n; ++k) {
+    const int32_t* b = boxes_ij + 4 * (size_t)k;
+    if (instances[k] >= grid_instances || b[0] < 0 || b[1] < 0 || b[2] < b[0] || b[3] < b[1] || b[2] > (int32_t)size_x || b[3] > (int32_t)size_y)
+      return NAVGPU_ERR_INVALID;
+  }
+  if (!n) return NAVGPU_OK;
+  C3dLayers* L = h->layered;
+  if ((rc = openLayers(h))) return rc;
+  HIP_TRY(waitStream(h->stream));
+  Stage st{L};
+  const size_t o_inst = st.put(instances, n), o_box = st.put(boxes_ij, 4 * (size_t)n);
+  HIP_TRY(hipMemcpyAsync(L->d_stage, L->h_stage, st.at, hipMemcpyHostToDevice, h->stream));
+  C3dCosts2d c{st.dev<uint32_t>(o_inst), st.dev<int32_t>(o_box), static_cast<uint8_t*>(device_grid), instance_stride_bytes, n, use_maximum ? 1 : 0};
+  launch_c3d_costs2d(h->dv, L->ly, c, h->stream);
+  if ((rc = checkLaunch())) return rc;
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_layer_columns_download(navgpu_costmap3d* h, uint32_t instance, uint32_t layer, uint64_t* lethal, uint64_t* nonlethal,
+                                            uint64_t* free_cells, uint64_t* changed) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_layer_columns_download");
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  if (instance >= h->desc.n_instances || layer >= L->layers.size() || !costmapLayer(L->layers[layer])) return NAVGPU_ERR_INVALID;
+  if ((rc = openLayers(h))) return rc;
+  const size_t cols = h->dv.cols, bytes = sizeof(uint64_t) * cols;
+  const uint32_t slot = L->index[layer];
+  const uint64_t* set = L->ly.set(instance, slot, L->cur[(size_t)instance * L->ly.nc + slot], h->dv.cols);
+  if (lethal) HIP_TRY(hipMemcpyAsync(lethal, set + kC3dL * cols, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (nonlethal) HIP_TRY(hipMemcpyAsync(nonlethal, set + kC3dN * cols, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (free_cells) HIP_TRY(hipMemcpyAsync(free_cells, set + kC3dF * cols, bytes, hipMemcpyDeviceToHost, h->stream));
+  if (changed) HIP_TRY(hipMemcpyAsync(changed, L->ly.changed + ((size_t)instance * L->ly.nc + slot) * cols, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_free_columns_download(navgpu_costmap3d* h, uint32_t instance, uint64_t* free_cells) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_free_columns_download");
+  if (rc) return rc;
+  if (instance >= h->desc.n_instances) return NAVGPU_ERR_INVALID;
+  if ((rc = openLayers(h))) return rc;
+  if (free_cells)
+    HIP_TRY(hipMemcpyAsync(free_cells, h->layered->ly.free_plane + (size_t)instance * h->dv.cols, sizeof(uint64_t) * h->dv.cols, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
   return NAVGPU_OK;
 }
 

@@ -41,6 +41,79 @@ struct C3dQuery {
   double scale_y, scale_z, limit;
 };
 
+// ---- the layered map update (costmap3d_layer_kernels.hip, include/navgpu_costmap3d_layers.h) ----
+// A tile is 64 consecutive column words of a row (a wave's lanes): tpr tiles per row, tiles = tpr * sy per instance, one bit each
+// in bitmaps of tw 32-bit words.  nc costmap layers (POINT_CLOUD, STATIC_2D) have a slot each.
+struct C3dLayersDev {
+  uint64_t* sets = nullptr;     // [n][nc][2][3][cols] a layer's two plane sets (LETHAL, NONLETHAL, FREE): the current one and the next scratch
+  uint64_t* changed = nullptr;  // [n][nc][cols] CostmapLayer3D::changed_cells_
+  uint32_t* occ = nullptr;      // [n][nc][2][tw] tiles a plane set occupies
+  uint32_t* dirty = nullptr;    // [n][tw] tiles with a changed bit in some layer
+  uint64_t* free_plane = nullptr;  // [n][cols] the master's FREE plane
+  uint8_t* layer2d = nullptr;   // [n][cols] Costmap3DTo2DLayer's costmap_
+  uint32_t nc = 0, tpr = 0, tiles = 0, tw = 0;
+  int32_t nonlethal_cost_2d = 127;
+  int32_t all_tiles = 0;        // tool builds: the plain full-volume pass, no tile is skipped
+  double inv_res = 0;           // 1.0 / resolution (octomap's resolution_factor)
+  __host__ __device__ uint64_t* set(uint32_t inst, uint32_t slot, uint32_t which, uint32_t cols) const {
+    return sets + (((size_t)inst * nc + slot) * 2 + which) * 3 * cols;
+  }
+  __host__ __device__ uint32_t* occOf(uint32_t inst, uint32_t slot, uint32_t which) const { return occ + (((size_t)inst * nc + slot) * 2 + which) * tw; }
+};
+enum { kC3dL = 0, kC3dN = 1, kC3dF = 2 };  // plane order inside a set
+
+// one (instance, layer) pair of a buffer_clouds / set_static_grid call
+struct C3dCloudRec {
+  double tf[12];
+  int64_t ok[3];        // llround(origin / resolution)
+  uint32_t instance, slot, next;  // next: the set that receives the new cells (the other one is current)
+  uint32_t first_point, n_points, has_intensity;
+  float free_intensity, lethal_intensity;
+};
+struct C3dGridRec {
+  int64_t ok[3];
+  double origin_x, origin_y, height;
+  uint32_t instance, slot, next, width, rows;
+  int32_t threshold, unknown_to_lethal;
+};
+// one cylinder layer of one listed instance of an update
+struct C3dCylRec {
+  double cx, cy, px, py, r;  // current and previous robot position, the radius
+  int32_t cbox[4], pbox[4];  // clamped key boxes x0, x1, y0, y1 (inclusive)
+  int32_t has_cur, has_prev;
+};
+struct C3dLayerRule {  // one layer of the stack, in order
+  int32_t kind, enabled, method, index;  // index: the slot of a costmap layer, the number of a cylinder layer
+};
+struct C3dUpdate {
+  const uint32_t* instances;  // [n]
+  const uint32_t* cur;        // [n][nc] the current set of each slot
+  const uint32_t* full;       // [n]
+  const int64_t* ok;          // [n][3]
+  const C3dCylRec* cyl;       // [n][n_cyl]
+  int32_t* box;               // [n][4] x0, y0, x1, y1 of the columns with a bounds bit: min, min, max, max
+  uint32_t n, n_cyl, n_layers;
+  C3dLayerRule rules[8];
+};
+struct C3dCosts2d {
+  const uint32_t* instances;
+  const int32_t* boxes;  // [n][4] min_i, min_j, max_i, max_j
+  uint8_t* grid;
+  size_t stride;
+  uint32_t n;
+  int32_t use_maximum;
+};
+
+void launch_c3d_cloud(const C3dDev& d, const C3dLayersDev& ly, const C3dCloudRec* clouds, uint32_t n_clouds, uint32_t max_points, const float* points,
+                      uint32_t* clipped, hipStream_t stream);
+void launch_c3d_static2d(const C3dDev& d, const C3dLayersDev& ly, const C3dGridRec* rec, size_t cells, const int8_t* grid, uint32_t* clipped,
+                         hipStream_t stream);
+// mode 0: the swap of every listed pair; mode 1: touch (changed |= present) of the pairs' current sets (next names the other one)
+void launch_c3d_layer_swap(const C3dDev& d, const C3dLayersDev& ly, const uint32_t* pairs3, uint32_t n_pairs, int32_t mode, hipStream_t stream);
+void launch_c3d_combine(const C3dDev& d, const C3dLayersDev& ly, const C3dUpdate& u, hipStream_t stream);
+void launch_c3d_costs2d(const C3dDev& d, const C3dLayersDev& ly, const C3dCosts2d& c, hipStream_t stream);
+void launch_c3d_fill_u8(uint8_t* p, uint8_t v, size_t n, hipStream_t stream);
+
 void launch_c3d_rasterize(const C3dDev& d, uint32_t instance, int32_t mode, const C3dBoxCells* boxes, uint32_t n_boxes,
                           uint32_t max_columns, hipStream_t stream);
 void launch_c3d_query(const C3dDev& d, const C3dQuery& q, hipStream_t stream);
