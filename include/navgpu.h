@@ -2000,6 +2000,8 @@ int navgpu_costmap3d_footprint_costs(navgpu_costmap3d* c3d, uint32_t n_runs, con
 /* The handle's layered map update from point clouds and its projection into 2-D: configure_layers, layer_set,
  * buffer_clouds, set_static_grid, update, reset, layer2d_download, layer2d_update_costs and the layers' raw column access. */
 #include "navgpu_costmap3d_layers.h"
+/* Rolling 3-D maps and the reset of a bounding box: the two calls that move or clear what the layers hold. */
+#include "navgpu_costmap3d_rolling.h"
 
 #ifdef __cplusplus
 }

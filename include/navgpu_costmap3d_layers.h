@@ -87,7 +87,7 @@ int navgpu_costmap3d_buffer_clouds(navgpu_costmap3d* c3d, const navgpu_c3d_cloud
  * origin that is not finite or an unaligned instance origin. */
 int navgpu_costmap3d_set_static_grid(navgpu_costmap3d* c3d, uint32_t instance, uint32_t layer, const int8_t* occupancy, uint32_t width,
                                      uint32_t height, double origin_x, double origin_y, uint32_t* clipped_out);
-/* replaces: LayeredCostmap3D::updateMap (layered_costmap_3d.cpp:60-165), non-rolling, for a list of distinct instances in one
+/* replaces: LayeredCostmap3D::updateMap (layered_costmap_3d.cpp:60-165; its rolling part is navgpu_costmap3d_roll), for a list of distinct instances in one
  * launch set (k_c3d_combine: a lane per column word), with CostmapLayer3D::updateBounds / updateCosts (costmap_layer_3d.cpp:
  * 51-108), CylinderClearingLayer3D::updateBounds / updateCosts (cylinder_clearing_layer_3d.cpp:78-160) and
  * Costmap3DTo2DLayer::updateFrom3D / updateBounds (costmap_3d_to_2d_layer.cpp:114-277).  robot_poses_xyz = {x, y, z} per listed
@@ -102,8 +102,9 @@ int navgpu_costmap3d_set_static_grid(navgpu_costmap3d* c3d, uint32_t instance, u
  * re-projects a bounding box; the projection is a function of the master column, so the results are equal), and the 2-D bounds
  * are extended by origin + x0*res, origin + y0*res, origin + (x1+1)*res, origin + (y1+1)*res.  bounds2d_out (or NULL) holds
  * {min_x, min_y, max_x, max_y} per listed instance, {1e6, 1e6, -1e6, -1e6} when empty (costmap_2d/src/costmap_layer.cpp:55-58);
- * the pending bounds are consumed (useExtraBounds).  NAVGPU_ERR_INVALID for an instance out of range or listed twice, a pose
- * that is not finite or an unaligned origin. */
+ * the pending bounds are consumed (useExtraBounds).  An instance whose window moved since its last update (navgpu_costmap3d_roll's
+ * moved mark, which this call consumes) reports the whole window, {ox, oy, ox + size_x * res, oy + size_y * res}.
+ * NAVGPU_ERR_INVALID for an instance out of range or listed twice, a pose that is not finite or an unaligned origin. */
 int navgpu_costmap3d_update(navgpu_costmap3d* c3d, uint32_t n, const uint32_t* instances, const double* robot_poses_xyz, double* bounds2d_out);
 /* replaces: LayeredCostmap3D::reset (layered_costmap_3d.cpp:183-194) for the listed instances: the master and every costmap
  * layer are cleared with their changed planes, cylinder layers forget their previous set, the full flag is set. */

@@ -505,6 +505,7 @@ class C3dCloud(C.Structure):
 C3D_MAX_LAYERS = 8
 C3D_LAYER_POINT_CLOUD, C3D_LAYER_STATIC_2D, C3D_LAYER_CYLINDER_CLEARING = 0, 1, 2
 C3D_COMBINE_OVERWRITE, C3D_COMBINE_MAXIMUM, C3D_COMBINE_IF_UNKNOWN, C3D_COMBINE_NOTHING = 0, 1, 2, 99
+C3D_ROLL_CENTRE, C3D_ROLL_ORIGIN = 0, 1  # include/navgpu_costmap3d_rolling.h
 
 
 def lib_path():
@@ -722,6 +723,8 @@ SYMBOLS = [
     ("navgpu_costmap3d_layer2d_update_costs", C.c_int, [vp, u32, vp, vp, C.c_size_t, u32, u32, u32, vp, i32]),
     ("navgpu_costmap3d_layer_columns_download", C.c_int, [vp, u32, u32, vp, vp, vp, vp]),
     ("navgpu_costmap3d_free_columns_download", C.c_int, [vp, u32, vp]),
+    ("navgpu_costmap3d_roll", C.c_int, [vp, u32, vp, i32, vp, vp]),
+    ("navgpu_costmap3d_reset_bounding_box", C.c_int, [vp, u32, vp, vp, u32]),
 ]
 
 

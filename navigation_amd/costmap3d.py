@@ -10,6 +10,9 @@
   configure_layers, layer_set, buffer_clouds, set_static_grid, update, reset, layer2d, update_costs_2d, layer_columns, free_columns
                           the layered map update from point clouds and its projection into 2-D (include/navgpu_costmap3d_layers.h):
                           PointCloudLayer3D, Static2DLayer3D, CylinderClearingLayer3D, LayeredCostmap3D::updateMap, Costmap3DTo2DLayer
+  roll, reset_bounding_box
+                          rolling windows and Costmap3DROS::resetBoundingBox (include/navgpu_costmap3d_rolling.h):
+                          LayeredCostmap3D::updateMap's rolling part, CostmapLayer3D::resetBoundingBox
   load_stl                a binary STL as (vertices, triangles), equal corners merged
   load_octomap_bt         an octomap binary tree (.bt) as its occupied leaves: centres, sizes, classes
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers and reads the two file formats.
@@ -19,7 +22,7 @@ import struct
 
 import numpy as np
 
-from ._lib import (C3D_DISTANCE, C3D_LETHAL, C3D_REPLACE, GRID_MASTER, C3dBox, C3dCloud, C3dLayer, C3dRun, C3dRunResult, Costmap3DDesc, check, lib)
+from ._lib import (C3D_DISTANCE, C3D_LETHAL, C3D_REPLACE, C3D_ROLL_CENTRE, C3D_ROLL_ORIGIN, GRID_MASTER, C3dBox, C3dCloud, C3dLayer, C3dRun, C3dRunResult, Costmap3DDesc, check, lib)
 
 BOX_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("cz", "<f8"), ("size", "<f8"), ("cls", "<i4"), ("reserved", "<i4")])
 RUN_DTYPE = np.dtype([("instance", "<u4"), ("first_pose", "<u4"), ("n_poses", "<u4")])
@@ -274,3 +277,28 @@ class Costmap3D:
         free = np.zeros((self.size_y, self.size_x), np.uint64)
         check(self.L.navgpu_costmap3d_free_columns_download(self.h, instance, _ptr(free)), "navgpu_costmap3d_free_columns_download")
         return free
+
+    # ---- rolling maps and resetBoundingBox (include/navgpu_costmap3d_rolling.h) ----
+    def roll(self, instances, robot_xy=None, origin_xy=None):
+        """Moves the listed instances' windows: round the robots' positions robot_xy (n, 2), or to the origins origin_xy (n, 2) - exactly
+        one of the two.  Returns the shifts (n, 2) = dx, dy in cells.  A cycle is roll, then buffer_clouds, then update."""
+        assert (robot_xy is None) != (origin_xy is None), "give robot_xy or origin_xy"
+        ins = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        targets = np.ascontiguousarray(origin_xy if robot_xy is None else robot_xy, np.float64).reshape(-1, 2)
+        assert len(targets) == len(ins)
+        shifts = np.zeros((len(ins), 2), np.int32)
+        check(self.L.navgpu_costmap3d_roll(self.h, len(ins), _ptr(ins), C3D_ROLL_ORIGIN if robot_xy is None else C3D_ROLL_CENTRE, _ptr(targets),
+                                           _ptr(shifts)), "navgpu_costmap3d_roll")
+        return shifts
+
+    def reset_bounding_box(self, instances, boxes, layers):
+        """boxes (n, 6) = min x, y, z, max x, y, z per listed instance; layers: the indices of the layers to clear inside them (only
+        POINT_CLOUD layers hold anything the call deletes)."""
+        ins = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        b = np.ascontiguousarray(boxes, np.float64).reshape(-1, 6)
+        assert len(b) == len(ins)
+        mask = 0
+        for l in layers:
+            assert 0 <= int(l) < 32
+            mask |= 1 << int(l)
+        check(self.L.navgpu_costmap3d_reset_bounding_box(self.h, len(ins), _ptr(ins), _ptr(b), mask), "navgpu_costmap3d_reset_bounding_box")

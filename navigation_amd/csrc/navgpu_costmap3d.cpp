@@ -17,6 +17,7 @@ struct C3dLayers {
   C3dLayersDev ly{};
   std::vector<uint32_t> cur;       // [n][nc] which plane set is current
   std::vector<uint32_t> full;      // [n] size_changed_ / copy_full_map_
+  std::vector<uint8_t> moved;      // [n] the window moved since the last update (navgpu_costmap3d_roll): its 2-D bounds are the window
   struct Cyl { bool has = false; double x = 0, y = 0; };
   std::vector<Cyl> prev;           // [n][n_cyl] CylinderClearingLayer3D::clearing_bounds_map_, as the position it was built round
   std::vector<void*> allocs;
@@ -41,6 +42,7 @@ struct navgpu_costmap3d {
   C3dBoxCells* h_boxes = nullptr;       // pinned: a set_boxes call's records until its copy has run
   uint8_t *d_in = nullptr, *d_out = nullptr;  // a query call's upload and read-back
   uint8_t *h_in = nullptr, *h_out = nullptr;  // pinned
+  uint8_t *d_roll = nullptr, *h_roll = nullptr;  // a roll's or a reset_bounding_box call's records (h_roll pinned); come with the first such call
   bool have_mesh = false;
   template <class T>
   int alloc(T** p, size_t count) {
@@ -261,6 +263,7 @@ int navgpu_costmap3d_destroy(navgpu_costmap3d* h) {
     hipHostFree(h->h_boxes);
     hipHostFree(h->h_in);
     hipHostFree(h->h_out);
+    if (h->h_roll) hipHostFree(h->h_roll);
     freeLayers(h);
     hipStreamDestroy(h->stream);
   }
@@ -639,6 +642,7 @@ int navgpu_costmap3d_configure_layers(navgpu_costmap3d* h, const navgpu_c3d_laye
   ly.inv_res = 1.0 / h->desc.resolution;
   L->cur.assign(n * nc, 0);
   L->full.assign(n, 1);
+  L->moved.assign(n, 0);
   L->prev.assign(n * L->n_cyl, C3dLayers::Cyl());
   h->layered = L.release();
   return NAVGPU_OK;  // the buffers come with the first call that needs the device (openLayers)
@@ -870,8 +874,11 @@ int navgpu_costmap3d_update(navgpu_costmap3d* h, uint32_t n, const uint32_t* ins
     u.rules[l] = C3dLayerRule{L->layers[l].kind, L->layers[l].enabled ? 1 : 0, L->layers[l].combination_method, (int32_t)L->index[l]};
   launch_c3d_combine(h->dv, L->ly, u, h->stream);
   if ((rc = checkLaunch())) return rc;
+  std::vector<uint8_t> moved(n);
   for (uint32_t k = 0; k < n; ++k) {  // queued: the host's view follows
     L->full[instances[k]] = 0;
+    moved[k] = L->moved[instances[k]];
+    L->moved[instances[k]] = 0;
     std::copy_n(prev_after.begin() + (size_t)k * n_cyl, n_cyl, L->prev.begin() + (size_t)instances[k] * n_cyl);
   }
   HIP_TRY(hipMemcpyAsync(st.host<int32_t>(o_box), st.dev<int32_t>(o_box), sizeof(int32_t) * 4 * n, hipMemcpyDeviceToHost, h->stream));
@@ -883,7 +890,12 @@ int navgpu_costmap3d_update(navgpu_costmap3d* h, uint32_t n, const uint32_t* ins
       const int32_t* b = got + 4 * (size_t)k;
       const double* org = h->origins.data() + 3 * (size_t)instances[k];
       double* out = bounds2d_out + 4 * (size_t)k;
-      if (b[0] > b[2]) {
+      if (moved[k]) {  // the window itself (costmap_3d_to_2d_layer.cpp:120-127, with maxima where it passes sizes)
+        out[0] = org[0];
+        out[1] = org[1];
+        out[2] = org[0] + h->dv.sx * res;
+        out[3] = org[1] + h->dv.sy * res;
+      } else if (b[0] > b[2]) {
         out[0] = out[1] = 1e6;
         out[2] = out[3] = -1e6;
       } else {
@@ -910,6 +922,7 @@ int navgpu_costmap3d_reset(navgpu_costmap3d* h, uint32_t n, const uint32_t* inst
   for (uint32_t k = 0; k < n; ++k) {
     const size_t i = instances[k];
     L->full[i] = 1;
+    L->moved[i] = 0;  // (the full flag implies it)
     std::fill_n(L->prev.begin() + i * L->n_cyl, L->n_cyl, C3dLayers::Cyl());
     if (h->opened) HIP_TRY(hipMemsetAsync(h->dv.planes + i * 2 * cols, 0, sizeof(uint64_t) * 2 * cols, h->stream));
     if (!L->resident) continue;  // (nothing else exists yet: it is empty when it does)
@@ -998,6 +1011,177 @@ int navgpu_costmap3d_free_columns_download(navgpu_costmap3d* h, uint32_t instanc
     HIP_TRY(hipMemcpyAsync(free_cells, h->layered->ly.free_plane + (size_t)instance * h->dv.cols, sizeof(uint64_t) * h->dv.cols, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(waitStream(h->stream));
   return NAVGPU_OK;
+}
+
+}  // extern "C"
+
+// ---- rolling maps and resetBoundingBox (include/navgpu_costmap3d_rolling.h, costmap3d_roll_kernels.hip) ----
+namespace {
+
+static_assert(sizeof(C3dRollRec) == 32 && sizeof(C3dResetRec) == 32, "one staging block serves both record types");
+
+// the records of a roll or a reset_bounding_box call: a device block and its pinned twin, one record per instance
+int openRollStage(navgpu_costmap3d* h) {
+  if (h->d_roll) return NAVGPU_OK;
+  const size_t bytes = sizeof(C3dRollRec) * h->desc.n_instances;
+  if (hipHostMalloc((void**)&h->h_roll, bytes, hipHostMallocDefault) != hipSuccess) {
+    h->h_roll = nullptr;
+    g_last_error = "hipHostMalloc failed (costmap3d roll)";
+    return NAVGPU_ERR_HIP;
+  }
+  const int rc = h->alloc(&h->d_roll, bytes);
+  if (rc) {
+    hipHostFree(h->h_roll);
+    h->h_roll = nullptr;
+  }
+  return rc;
+}
+
+// bit s: the current plane set of slot s
+uint32_t currentSets(const C3dLayers* L, uint32_t instance) {
+  uint32_t bits = 0;
+  for (uint32_t s = 0; L && s < L->ly.nc; ++s) bits |= (L->cur[(size_t)instance * L->ly.nc + s] & 1u) << s;
+  return bits;
+}
+
+}  // namespace
+
+extern "C" {
+
+int navgpu_costmap3d_roll(navgpu_costmap3d* h, uint32_t n, const uint32_t* instances, int32_t mode, const double* targets_xy, int32_t* shifts_out) {
+  if (!h || (n && !targets_xy) || (mode != NAVGPU_C3D_ROLL_CENTRE && mode != NAVGPU_C3D_ROLL_ORIGIN)) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = checkInstanceList(h, n, instances);
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  const double res = h->desc.resolution;
+  const uint32_t size[2] = {h->dv.sx, h->dv.sy};
+  std::vector<C3dRollRec> recs;
+  std::vector<int32_t> shifts(2 * (size_t)n);
+  bool any_y = false, any_x = false;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t i = instances[k];
+    const double* t = targets_xy + 2 * (size_t)k;
+    if (!std::isfinite(t[0]) || !std::isfinite(t[1])) {
+      g_last_error = "navgpu_costmap3d_roll: a target is not finite";
+      return NAVGPU_ERR_INVALID;
+    }
+    int64_t ok[3], shift[2];
+    if (!originKeys(h, i, ok)) return NAVGPU_ERR_INVALID;
+    double key[2];
+    for (int a = 0; a < 2; ++a) {
+      if (mode == NAVGPU_C3D_ROLL_CENTRE) {  // LayeredCostmap3D::updateMap with octomap::point3d's floats (layered_costmap_3d.cpp:78-92)
+        const double w = (double)(float)(size[a] * res);
+        const float m = (float)(t[a] - w / 2.0);
+        key[a] = std::floor((double)m * (1.0 / res));
+      } else {
+        const double f = t[a] / res;
+        key[a] = std::nearbyint(f);
+        if (!std::isfinite(f) || std::fabs(f - key[a]) > 1e-6) {
+          g_last_error = "navgpu_costmap3d_roll: the new origin of instance " + std::to_string(i) + " is not a multiple of the resolution";
+          return NAVGPU_ERR_INVALID;
+        }
+      }
+      if (!(std::fabs(key[a]) <= 1073741824.0)) {
+        g_last_error = "navgpu_costmap3d_roll: the new window of instance " + std::to_string(i) + " lies beyond the keys an origin may have";
+        return NAVGPU_ERR_INVALID;
+      }
+      shift[a] = (int64_t)key[a] - ok[a];
+      shifts[2 * (size_t)k + a] = (int32_t)std::max<int64_t>(std::min<int64_t>(shift[a], INT32_MAX), INT32_MIN);
+    }
+    if (!shift[0] && !shift[1]) continue;  // not touched, no moved mark
+    C3dRollRec r{};
+    r.ox = key[0] * res;
+    r.oy = key[1] * res;
+    r.instance = i;
+    r.cur_bits = currentSets(L, i);
+    if (std::llabs(shift[0]) >= (int64_t)size[0] || std::llabs(shift[1]) >= (int64_t)size[1]) {
+      r.cur_bits |= kC3dRollEmpty;
+      any_x = true;  // (the fill goes by rows)
+    } else {
+      r.dx = (int32_t)shift[0];
+      r.dy = (int32_t)shift[1];
+      any_x = any_x || r.dx;
+      any_y = any_y || r.dy;
+    }
+    recs.push_back(r);
+  }
+  if (!recs.empty()) {
+    if ((rc = L ? openLayers(h) : openDevice(h))) return rc;
+    if ((rc = openRollStage(h))) return rc;
+    HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+    memcpy(h->h_roll, recs.data(), sizeof(C3dRollRec) * recs.size());
+    HIP_TRY(hipMemcpyAsync(h->d_roll, h->h_roll, sizeof(C3dRollRec) * recs.size(), hipMemcpyHostToDevice, h->stream));
+    launch_c3d_roll(h->dv, L ? L->ly : C3dLayersDev{}, L ? 1 : 0, reinterpret_cast<const C3dRollRec*>(h->d_roll), (uint32_t)recs.size(), any_y, any_x,
+                    h->stream);
+    if ((rc = checkLaunch())) return rc;
+    for (const C3dRollRec& r : recs) {  // queued: the host's view follows
+      h->origins[3 * (size_t)r.instance] = r.ox;
+      h->origins[3 * (size_t)r.instance + 1] = r.oy;
+      if (L) L->moved[r.instance] = 1;
+    }
+  }
+  if (shifts_out) std::copy(shifts.begin(), shifts.end(), shifts_out);
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_reset_bounding_box(navgpu_costmap3d* h, uint32_t n, const uint32_t* instances, const double* boxes, uint32_t layer_mask) {
+  if (!h || (n && !boxes)) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_reset_bounding_box");
+  if (rc) return rc;
+  if ((rc = checkInstanceList(h, n, instances))) return rc;
+  C3dLayers* L = h->layered;
+  if (L->layers.size() < 32 && (layer_mask >> L->layers.size())) {
+    g_last_error = "navgpu_costmap3d_reset_bounding_box: layer_mask names a layer that is not configured";
+    return NAVGPU_ERR_INVALID;
+  }
+  C3dResetSlots slots{};
+  for (uint32_t l = 0; l < L->layers.size(); ++l)  // a STATIC_2D layer ignores the call (static_2d_layer_3d.cpp:153-158); a cylinder layer keeps its set
+    if (((layer_mask >> l) & 1u) && L->layers[l].kind == NAVGPU_C3D_LAYER_POINT_CLOUD) slots.slot[slots.n++] = L->index[l];
+  const uint32_t size[3] = {h->dv.sx, h->dv.sy, h->dv.sz};
+  std::vector<C3dResetRec> recs;
+  uint32_t max_tiles = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const double* b = boxes + 6 * (size_t)k;
+    if (!finite3(b) || !finite3(b + 3)) {
+      g_last_error = "navgpu_costmap3d_reset_bounding_box: a box is not finite";
+      return NAVGPU_ERR_INVALID;
+    }
+    int64_t ok[3];
+    if (!originKeys(h, instances[k], ok)) return NAVGPU_ERR_INVALID;
+    uint32_t lo[3], hi[3];
+    bool empty = false;
+    for (int a = 0; a < 3; ++a) {  // the keys of the corners, both ends inclusive (costmap_layer_3d.cpp:149-191), clipped to the window
+      const double k0 = std::floor(b[a] * L->ly.inv_res) - (double)ok[a], k1 = std::floor(b[3 + a] * L->ly.inv_res) - (double)ok[a];
+      if (b[a] > b[3 + a] || k1 < 0.0 || k0 > (double)(size[a] - 1)) {
+        empty = true;
+        break;
+      }
+      lo[a] = k0 <= 0.0 ? 0u : (uint32_t)k0;
+      hi[a] = k1 >= (double)(size[a] - 1) ? size[a] - 1 : (uint32_t)k1;
+    }
+    if (empty) continue;
+    C3dResetRec r{};
+    const uint32_t levels = hi[2] - lo[2] + 1;
+    r.zmask = (levels >= 64 ? ~0ull : ((uint64_t)1 << levels) - 1) << lo[2];
+    r.instance = instances[k];
+    r.cur_bits = currentSets(L, instances[k]);
+    r.x0 = lo[0];
+    r.x1 = hi[0];
+    r.y0 = lo[1];
+    r.y1 = hi[1];
+    max_tiles = std::max(max_tiles, ((r.x1 >> 6) - (r.x0 >> 6) + 1) * (r.y1 - r.y0 + 1));
+    recs.push_back(r);
+  }
+  if (recs.empty() || !slots.n) return NAVGPU_OK;
+  if ((rc = openLayers(h))) return rc;
+  if ((rc = openRollStage(h))) return rc;
+  HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+  memcpy(h->h_roll, recs.data(), sizeof(C3dResetRec) * recs.size());
+  HIP_TRY(hipMemcpyAsync(h->d_roll, h->h_roll, sizeof(C3dResetRec) * recs.size(), hipMemcpyHostToDevice, h->stream));
+  launch_c3d_reset_box(h->dv, L->ly, reinterpret_cast<const C3dResetRec*>(h->d_roll), (uint32_t)recs.size(), max_tiles, slots, h->stream);
+  return checkLaunch();  // queued
 }
 
 }  // extern "C"

@@ -114,6 +114,31 @@ void launch_c3d_combine(const C3dDev& d, const C3dLayersDev& ly, const C3dUpdate
 void launch_c3d_costs2d(const C3dDev& d, const C3dLayersDev& ly, const C3dCosts2d& c, hipStream_t stream);
 void launch_c3d_fill_u8(uint8_t* p, uint8_t v, size_t n, hipStream_t stream);
 
+// ---- rolling maps and resetBoundingBox (costmap3d_roll_kernels.hip, include/navgpu_costmap3d_rolling.h) ----
+constexpr uint32_t kC3dRollRow = 2048;  // columns of a row that k_c3d_roll_x holds in registers at a time (256 lanes x 8)
+// one moved instance of a roll: dst(x, y) = src(x + dx, y + dy), or empty off the window
+struct C3dRollRec {
+  double ox, oy;      // the new origin
+  uint32_t instance;
+  int32_t dx, dy;     // cells; both inside (-size, size) unless empty
+  uint32_t cur_bits;  // bit s: the current plane set of slot s; bit 31: |dx| >= size_x or |dy| >= size_y, everything leaves
+};
+constexpr uint32_t kC3dRollEmpty = 1u << 31;
+// one listed instance of a reset_bounding_box call whose clipped box is not empty
+struct C3dResetRec {
+  uint64_t zmask;
+  uint32_t instance, cur_bits;
+  uint32_t x0, x1, y0, y1;  // inclusive
+};
+struct C3dResetSlots {
+  uint32_t n, slot[8];  // the POINT_CLOUD slots the mask names
+};
+// layered: 0 shifts the master's LETHAL and NONLETHAL planes only (ly is not read)
+void launch_c3d_roll(const C3dDev& d, const C3dLayersDev& ly, int32_t layered, const C3dRollRec* recs, uint32_t n, bool any_y, bool any_x,
+                     hipStream_t stream);
+void launch_c3d_reset_box(const C3dDev& d, const C3dLayersDev& ly, const C3dResetRec* recs, uint32_t n, uint32_t max_tiles, const C3dResetSlots& slots,
+                          hipStream_t stream);
+
 void launch_c3d_rasterize(const C3dDev& d, uint32_t instance, int32_t mode, const C3dBoxCells* boxes, uint32_t n_boxes,
                           uint32_t max_columns, hipStream_t stream);
 void launch_c3d_query(const C3dDev& d, const C3dQuery& q, hipStream_t stream);
