@@ -2002,6 +2002,8 @@ int navgpu_costmap3d_footprint_costs(navgpu_costmap3d* c3d, uint32_t n_runs, con
 #include "navgpu_costmap3d_layers.h"
 /* Rolling 3-D maps and the reset of a bounding box: the two calls that move or clear what the layers hold. */
 #include "navgpu_costmap3d_rolling.h"
+/* The maps' way out of a handle and into a layer: pruned octree leaves, Costmap3DPublisher and updateCells. */
+#include "navgpu_costmap3d_publish.h"
 
 #ifdef __cplusplus
 }

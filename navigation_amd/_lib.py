@@ -508,6 +508,24 @@ C3D_COMBINE_OVERWRITE, C3D_COMBINE_MAXIMUM, C3D_COMBINE_IF_UNKNOWN, C3D_COMBINE_
 C3D_ROLL_CENTRE, C3D_ROLL_ORIGIN = 0, 1  # include/navgpu_costmap3d_rolling.h
 
 
+class C3dLeaf(C.Structure):
+    """Mirror of navgpu_c3d_leaf (include/navgpu_costmap3d_publish.h)."""
+    _fields_ = [("key", C.c_int32 * 3), ("level", C.c_uint16), ("cls", C.c_uint16)]
+
+
+class C3dUpdateMsg(C.Structure):
+    """Mirror of navgpu_c3d_update_msg (include/navgpu_costmap3d_publish.h)."""
+    _fields_ = [("instance", C.c_uint32), ("update_seq", C.c_uint32), ("bounds_seq", C.c_uint32), ("universe", C.c_int32), ("plain_map", C.c_int32),
+                ("first_value", C.c_uint32), ("n_values", C.c_uint32), ("first_bound", C.c_uint32), ("n_bounds", C.c_uint32),
+                ("n_forgotten", C.c_uint32), ("forgotten", (C.c_int32 * 6) * 2)]
+
+
+C3D_FREE = 2  # include/navgpu_costmap3d_publish.h
+C3D_EXPORT_FULL, C3D_EXPORT_DELTA = 0, 1
+C3D_CELLS_BINARY, C3D_CELLS_AS_GIVEN = 0, 1
+C3D_APPLIED, C3D_IGNORED, C3D_RESYNC = 0, 1, 2
+
+
 def lib_path():
     return os.path.join(_HERE, "libnavgpu.so")
 
@@ -725,6 +743,10 @@ SYMBOLS = [
     ("navgpu_costmap3d_free_columns_download", C.c_int, [vp, u32, vp]),
     ("navgpu_costmap3d_roll", C.c_int, [vp, u32, vp, i32, vp, vp]),
     ("navgpu_costmap3d_reset_bounding_box", C.c_int, [vp, u32, vp, vp, u32]),
+    ("navgpu_costmap3d_publisher_configure", C.c_int, [vp, i32]),
+    ("navgpu_costmap3d_export", C.c_int, [vp, u32, vp, i32, u32, vp, u32, vp, vp]),
+    ("navgpu_costmap3d_layer_update_cells", C.c_int, [vp, u32, vp, vp, i32, vp, u32, vp, u32, vp]),
+    ("navgpu_costmap3d_layer_resubscribe", C.c_int, [vp, u32, u32]),
 ]
 
 

@@ -13,6 +13,11 @@
   roll, reset_bounding_box
                           rolling windows and Costmap3DROS::resetBoundingBox (include/navgpu_costmap3d_rolling.h):
                           LayeredCostmap3D::updateMap's rolling part, CostmapLayer3D::resetBoundingBox
+  configure_publisher, export, update_cells, resubscribe
+                          the maps' way out of a handle and into a layer as pruned octree leaves (include/navgpu_costmap3d_publish.h):
+                          Costmap3DPublisher, CostmapLayer3D::updateCells, OctomapServerLayer3D's subscription
+  leaves_to_boxes, boxes_to_leaves
+                          leaves as set_boxes takes them, and back
   load_stl                a binary STL as (vertices, triangles), equal corners merged
   load_octomap_bt         an octomap binary tree (.bt) as its occupied leaves: centres, sizes, classes
 All compute happens in libnavgpu.so on the GPU; this file only marshals numpy buffers and reads the two file formats.
@@ -22,7 +27,8 @@ import struct
 
 import numpy as np
 
-from ._lib import (C3D_DISTANCE, C3D_LETHAL, C3D_REPLACE, C3D_ROLL_CENTRE, C3D_ROLL_ORIGIN, GRID_MASTER, C3dBox, C3dCloud, C3dLayer, C3dRun, C3dRunResult, Costmap3DDesc, check, lib)
+from ._lib import (C3D_CELLS_BINARY, C3D_DISTANCE, C3D_EXPORT_FULL, C3D_LETHAL, C3D_REPLACE, C3D_ROLL_CENTRE, C3D_ROLL_ORIGIN, GRID_MASTER, C3dBox, C3dCloud, C3dLayer,
+                   C3dLeaf, C3dRun, C3dRunResult, C3dUpdateMsg, Costmap3DDesc, check, lib)
 
 BOX_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("cz", "<f8"), ("size", "<f8"), ("cls", "<i4"), ("reserved", "<i4")])
 RUN_DTYPE = np.dtype([("instance", "<u4"), ("first_pose", "<u4"), ("n_poses", "<u4")])
@@ -31,6 +37,11 @@ CLOUD_DTYPE = np.dtype([("instance", "<u4"), ("layer", "<u4"), ("first_point", "
 IDENTITY_TRANSFORM = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
 assert CLOUD_DTYPE.itemsize == C.sizeof(C3dCloud)
 assert BOX_DTYPE.itemsize == C.sizeof(C3dBox) and RUN_DTYPE.itemsize == C.sizeof(C3dRun) and RUN_RESULT_DTYPE.itemsize == C.sizeof(C3dRunResult)
+LEAF_DTYPE = np.dtype([("key", "<i4", 3), ("level", "<u2"), ("cls", "<u2")])
+UPDATE_MSG_DTYPE = np.dtype([("instance", "<u4"), ("update_seq", "<u4"), ("bounds_seq", "<u4"), ("universe", "<i4"), ("plain_map", "<i4"), ("first_value", "<u4"),
+                             ("n_values", "<u4"), ("first_bound", "<u4"), ("n_bounds", "<u4"), ("n_forgotten", "<u4"), ("forgotten", "<i4", (2, 6))])
+assert LEAF_DTYPE.itemsize == C.sizeof(C3dLeaf) == 16 and UPDATE_MSG_DTYPE.itemsize == C.sizeof(C3dUpdateMsg) == 88
+NAVGPU_ERR_CAPACITY = -4
 DBL_MAX = float(np.finfo(np.float64).max)
 
 
@@ -106,6 +117,25 @@ def load_octomap_bt(path):
     """the occupied leaves of a .bt file as set_boxes takes them: (centres (n, 3), sizes (n,), classes (n,))"""
     t = read_octomap_bt(path)
     return t["centres"], t["sizes"], t["classes"]
+
+
+def leaves_to_boxes(leaves, resolution):
+    """leaves (LEAF_DTYPE) -> (centres (n, 3), sizes (n,), classes (n,)) as set_boxes takes them (which knows LETHAL and NONLETHAL only)"""
+    l = np.asarray(leaves, LEAF_DTYPE).reshape(-1)
+    edge = np.ldexp(float(resolution), l["level"].astype(np.int32))
+    return l["key"].astype(np.float64) * float(resolution) + 0.5 * edge[:, None], edge, l["cls"].astype(np.int32)
+
+
+def boxes_to_leaves(centres, sizes, classes, resolution):
+    """the inverse of leaves_to_boxes: boxes whose size is resolution * 2^k and whose lower corner lies on the lattice"""
+    c = np.asarray(centres, np.float64).reshape(-1, 3)
+    size = np.broadcast_to(np.asarray(sizes, np.float64), (len(c),))
+    level = np.rint(np.log2(size / float(resolution))).astype(np.int64)
+    key = (c - 0.5 * size[:, None]) / float(resolution)
+    assert np.all(np.abs(size - np.ldexp(float(resolution), level.astype(np.int32))) <= 1e-9) and np.all(np.abs(key - np.rint(key)) <= 1e-6), "not leaves of the lattice"
+    out = np.zeros(len(c), LEAF_DTYPE)
+    out["key"], out["level"], out["cls"] = np.rint(key), level, np.broadcast_to(np.asarray(classes), (len(c),))
+    return out
 
 
 class Costmap3D:
@@ -302,3 +332,46 @@ class Costmap3D:
             assert 0 <= int(l) < 32
             mask |= 1 << int(l)
         check(self.L.navgpu_costmap3d_reset_bounding_box(self.h, len(ins), _ptr(ins), _ptr(b), mask), "navgpu_costmap3d_reset_bounding_box")
+
+    # ---- publishing: pruned octree leaves out of the handle and into a layer (include/navgpu_costmap3d_publish.h) ----
+    def configure_publisher(self, enabled=True):
+        check(self.L.navgpu_costmap3d_publisher_configure(self.h, int(bool(enabled))), "navgpu_costmap3d_publisher_configure")
+
+    def export(self, instances, mode=C3D_EXPORT_FULL):
+        """Returns (msgs: UPDATE_MSG_DTYPE per listed instance, values, bounds: LEAF_DTYPE arrays the messages' ranges index).  The
+        arrays have the capacity of the last export; a call they are too small for commits nothing, says how many leaves there are
+        and is repeated with room."""
+        ins = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        msgs = np.zeros(len(ins), UPDATE_MSG_DTYPE)
+        cap_v, cap_b = getattr(self, "_export_capacity", (0, 0))
+        for _ in range(2):
+            values, bounds = np.zeros(max(cap_v, 1), LEAF_DTYPE), np.zeros(max(cap_b, 1), LEAF_DTYPE)
+            rc = self.L.navgpu_costmap3d_export(self.h, len(ins), _ptr(ins), int(mode), cap_v, _ptr(values), cap_b, _ptr(bounds), _ptr(msgs))
+            if rc != NAVGPU_ERR_CAPACITY:
+                break
+            cap_v, cap_b = max(cap_v, int(msgs["n_values"].sum())), max(cap_b, int(msgs["n_bounds"].sum()))
+        check(rc, "navgpu_costmap3d_export")
+        self._export_capacity = (cap_v, cap_b)
+        return msgs, values[:int(msgs["n_values"].sum())].copy(), bounds[:int(msgs["n_bounds"].sum())].copy()
+
+    def export_counts(self, instances, mode=C3D_EXPORT_FULL):
+        """the messages with their counts alone; nothing is committed"""
+        ins = np.ascontiguousarray(instances, np.uint32).reshape(-1)
+        msgs = np.zeros(len(ins), UPDATE_MSG_DTYPE)
+        check(self.L.navgpu_costmap3d_export(self.h, len(ins), _ptr(ins), int(mode), 0, None, 0, None, _ptr(msgs)), "navgpu_costmap3d_export")
+        return msgs
+
+    def update_cells(self, msgs, layers, values, bounds=None, cell_mode=C3D_CELLS_BINARY):
+        """msgs (UPDATE_MSG_DTYPE; instance is the destination) into the layers layers[i]; returns the verdict per message."""
+        m = np.ascontiguousarray(msgs, UPDATE_MSG_DTYPE).reshape(-1)
+        lay = np.ascontiguousarray(layers, np.uint32).reshape(-1)
+        assert len(lay) == len(m)
+        v = np.ascontiguousarray(values, LEAF_DTYPE).reshape(-1)
+        b = np.zeros(0, LEAF_DTYPE) if bounds is None else np.ascontiguousarray(bounds, LEAF_DTYPE).reshape(-1)
+        verdicts = np.zeros(len(m), np.int32)
+        check(self.L.navgpu_costmap3d_layer_update_cells(self.h, len(m), _ptr(m), _ptr(lay), int(cell_mode), _ptr(v) if len(v) else None, len(v),
+                                                         _ptr(b) if len(b) else None, len(b), _ptr(verdicts)), "navgpu_costmap3d_layer_update_cells")
+        return verdicts
+
+    def resubscribe(self, instance, layer):
+        check(self.L.navgpu_costmap3d_layer_resubscribe(self.h, instance, layer), "navgpu_costmap3d_layer_resubscribe")

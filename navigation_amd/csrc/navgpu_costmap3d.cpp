@@ -29,9 +29,33 @@ struct C3dLayers {
   bool resident = false;           // the device buffers exist (openLayers)
 };
 
+// what navgpu_costmap3d_publisher_configure, _export and _layer_update_cells add to a handle (include/navgpu_costmap3d_publish.h)
+struct C3dPublish {
+  bool enabled = false;             // publisher_configure: the three vectors below exist
+  std::vector<uint32_t> seq;        // [n] Costmap3DPublisher::update_seq_
+  std::vector<int64_t> window;      // [n][3] the lattice origin a shadow was taken at
+  std::vector<uint8_t> has_window;  // [n]
+  uint64_t* d_shadow = nullptr;     // [n][shadow_planes][cols] the master as last published; comes with the first DELTA
+  uint32_t shadow_planes = 0;
+  struct Sub { bool first_full = false, using_updates = false; uint32_t n_updates = 0, last_seq = 0; };
+  std::vector<Sub> subs;            // [n][nc] OctomapServerLayer3D's subscription state; sized by the first update_cells after a configure_layers
+  const void* subs_of = nullptr;    // the C3dLayers the states belong to
+  // a call's device blocks, grown on demand
+  uint8_t *d_stage = nullptr, *h_stage = nullptr;  // records up, counts down (h_stage pinned)
+  size_t stage_bytes = 0;
+  uint32_t* d_counts = nullptr;     // counts, offsets, totals
+  size_t count_words = 0;
+  navgpu_c3d_leaf *d_values = nullptr, *d_bounds = nullptr;
+  size_t value_capacity = 0, bounds_capacity = 0;
+  uint64_t* d_scratch = nullptr;    // [scratch_msgs][4][cols]; all zero between calls
+  uint32_t* d_touched = nullptr;    // [scratch_msgs][tw]
+  size_t scratch_msgs = 0;
+};
+
 struct navgpu_costmap3d {
   navgpu_costmap3d_desc desc{};
   C3dLayers* layered = nullptr;
+  C3dPublish* pub = nullptr;
   C3dDev dv{};
   bool opened = false;
   std::recursive_mutex mu;  // calls on one handle are serialised inside the library (as on a fleet)
@@ -264,10 +288,17 @@ int navgpu_costmap3d_destroy(navgpu_costmap3d* h) {
     hipHostFree(h->h_in);
     hipHostFree(h->h_out);
     if (h->h_roll) hipHostFree(h->h_roll);
+    if (h->pub) {
+      for (void* p : {(void*)h->pub->d_shadow, (void*)h->pub->d_stage, (void*)h->pub->d_counts, (void*)h->pub->d_values, (void*)h->pub->d_bounds,
+                      (void*)h->pub->d_scratch, (void*)h->pub->d_touched})
+        if (p) hipFree(p);
+      if (h->pub->h_stage) hipHostFree(h->pub->h_stage);
+    }
     freeLayers(h);
     hipStreamDestroy(h->stream);
   }
   delete h->layered;
+  delete h->pub;
   delete h;
   return NAVGPU_OK;
 }
@@ -632,6 +663,7 @@ int navgpu_costmap3d_configure_layers(navgpu_costmap3d* h, const navgpu_c3d_laye
     HIP_TRY(hipMemsetAsync(h->dv.planes, 0, sizeof(uint64_t) * n * 2 * h->dv.cols, h->stream));
   }
   freeLayers(h);
+  if (h->pub) h->pub->subs.clear();  // every (instance, layer) subscription starts over (include/navgpu_costmap3d_publish.h)
   C3dLayersDev& ly = L->ly;
   ly.nc = nc;
   ly.tpr = (h->dv.sx + 63) / 64;
@@ -1182,6 +1214,409 @@ int navgpu_costmap3d_reset_bounding_box(navgpu_costmap3d* h, uint32_t n, const u
   HIP_TRY(hipMemcpyAsync(h->d_roll, h->h_roll, sizeof(C3dResetRec) * recs.size(), hipMemcpyHostToDevice, h->stream));
   launch_c3d_reset_box(h->dv, L->ly, reinterpret_cast<const C3dResetRec*>(h->d_roll), (uint32_t)recs.size(), max_tiles, slots, h->stream);
   return checkLaunch();  // queued
+}
+
+}  // extern "C"
+
+// ---- publishing: pruned octree leaves out of a handle and into a layer (include/navgpu_costmap3d_publish.h, costmap3d_publish_kernels.hip) ----
+namespace {
+
+static_assert(sizeof(navgpu_c3d_leaf) == 16 && sizeof(navgpu_c3d_update_msg) == 88, "the records of include/navgpu_costmap3d_publish.h");
+
+C3dPublish* publishState(navgpu_costmap3d* h) {
+  if (!h->pub) h->pub = new C3dPublish();
+  return h->pub;
+}
+
+// a device block of at least `want` items; a block that grows is new and, with zero, all zero
+template <class T>
+int growDevice(navgpu_costmap3d* h, T** p, size_t* have, size_t want, bool zero) {
+  if (*have >= want && *p) return NAVGPU_OK;
+  if (*p) {
+    HIP_TRY(waitStream(h->stream));
+    HIP_TRY(hipFree(*p));
+  }
+  *p = nullptr;
+  *have = 0;
+  void* q = nullptr;
+  const size_t bytes = std::max<size_t>(want * sizeof(T), 16);
+  if (hipMalloc(&q, bytes) != hipSuccess) {
+    g_last_error = "hipMalloc failed (costmap3d publish)";
+    return NAVGPU_ERR_HIP;
+  }
+  if (zero && hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) {
+    hipFree(q);
+    return NAVGPU_ERR_HIP;
+  }
+  *p = static_cast<T*>(q);
+  *have = want;
+  return NAVGPU_OK;
+}
+
+int growStage(navgpu_costmap3d* h, size_t bytes) {
+  C3dPublish* P = h->pub;
+  if (P->stage_bytes >= bytes && P->d_stage) return NAVGPU_OK;
+  HIP_TRY(waitStream(h->stream));
+  if (P->h_stage) hipHostFree(P->h_stage);
+  P->h_stage = nullptr;
+  size_t have = P->d_stage ? P->stage_bytes : 0;
+  P->stage_bytes = 0;
+  int rc = growDevice(h, &P->d_stage, &have, bytes, false);
+  if (rc) return rc;
+  if (hipHostMalloc((void**)&P->h_stage, std::max<size_t>(bytes, 16), hipHostMallocDefault) != hipSuccess) {
+    P->h_stage = nullptr;
+    hipFree(P->d_stage);
+    P->d_stage = nullptr;
+    g_last_error = "hipHostMalloc failed (costmap3d publish)";
+    return NAVGPU_ERR_HIP;
+  }
+  P->stage_bytes = bytes;
+  return NAVGPU_OK;
+}
+
+int64_t floorDiv64(int64_t v) { return v >= 0 ? v / 64 : -((-v + 63) / 64); }
+
+// shadow window \ current window as at most two lattice boxes: the x strip over the old y range, the y strip over the remaining x range
+uint32_t forgottenBoxes(const int64_t* was, const int64_t* now, const int64_t* size, int32_t out[2][6]) {
+  uint32_t n = 0;
+  const int64_t x_end = was[0] + size[0] - 1, y_end = was[1] + size[1] - 1;
+  auto put = [&](int64_t x0, int64_t x1, int64_t y0, int64_t y1) {
+    const int64_t box[6] = {x0, y0, was[2], x1, y1, was[2] + size[2] - 1};
+    for (int a = 0; a < 6; ++a) out[n][a] = (int32_t)box[a];
+    ++n;
+  };
+  if (now[0] > was[0]) put(was[0], std::min(now[0] - 1, x_end), was[1], y_end);
+  else if (now[0] < was[0]) put(std::max(now[0] + size[0], was[0]), x_end, was[1], y_end);
+  const int64_t x0 = std::max(was[0], now[0]), x1 = std::min(was[0], now[0]) + size[0] - 1;  // the x range both windows hold
+  if (x0 <= x1) {
+    if (now[1] > was[1]) put(x0, x1, was[1], std::min(now[1] - 1, y_end));
+    else if (now[1] < was[1]) put(x0, x1, std::max(now[1] + size[1], was[1]), y_end);
+  }
+  return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int navgpu_costmap3d_publisher_configure(navgpu_costmap3d* h, int32_t enabled) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  C3dPublish* P = publishState(h);
+  const size_t n = h->desc.n_instances;
+  if (P->d_shadow) {  // shadows start empty
+    HIP_TRY(hipSetDevice(h->desc.device));
+    HIP_TRY(hipMemsetAsync(P->d_shadow, 0, sizeof(uint64_t) * n * P->shadow_planes * h->dv.cols, h->stream));
+  }
+  P->enabled = enabled != 0;
+  P->seq.assign(P->enabled ? n : 0, 0);
+  P->window.assign(P->enabled ? 3 * n : 0, 0);
+  P->has_window.assign(P->enabled ? n : 0, 0);
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_export(navgpu_costmap3d* h, uint32_t n, const uint32_t* instances, int32_t mode, uint32_t value_capacity, navgpu_c3d_leaf* values,
+                            uint32_t bounds_capacity, navgpu_c3d_leaf* bounds, navgpu_c3d_update_msg* msgs) {
+  if (!h || !msgs || (mode != NAVGPU_C3D_EXPORT_FULL && mode != NAVGPU_C3D_EXPORT_DELTA) || (value_capacity && !values) || (bounds_capacity && !bounds))
+    return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = checkInstanceList(h, n, instances);
+  if (rc) return rc;
+  const bool delta = mode == NAVGPU_C3D_EXPORT_DELTA, layered = h->layered != nullptr;
+  const int64_t size[3] = {h->dv.sx, h->dv.sy, h->dv.sz};
+  std::vector<C3dExportRec> recs(n);
+  std::vector<int64_t> ok(3 * (size_t)n);
+  uint32_t blocks = 0, max_blocks = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    int64_t* o = ok.data() + 3 * (size_t)k;
+    if (!originKeys(h, instances[k], o)) return NAVGPU_ERR_INVALID;  // (|key| <= 2^30 and size < 2^26: the window fits int32_t)
+    C3dExportRec& r = recs[k];
+    r = C3dExportRec{};
+    for (int a = 0; a < 3; ++a) r.ok[a] = (int32_t)o[a];
+    r.bx0 = (int32_t)floorDiv64(o[0]);
+    r.by0 = (int32_t)floorDiv64(o[1]);
+    r.nbx = (uint32_t)(floorDiv64(o[0] + size[0] - 1) - r.bx0 + 1);
+    r.nby = (uint32_t)(floorDiv64(o[1] + size[1] - 1) - r.by0 + 1);
+    r.instance = instances[k];
+    r.first_block = blocks;
+    blocks += r.nbx * r.nby;
+    max_blocks = std::max(max_blocks, r.nbx * r.nby);
+  }
+  if (delta && !(h->pub && h->pub->enabled)) {
+    g_last_error = "navgpu_costmap3d_export: DELTA needs navgpu_costmap3d_publisher_configure";
+    return NAVGPU_ERR_STATE;
+  }
+  if (!n) return NAVGPU_OK;
+  C3dPublish* P = publishState(h);
+  const bool sequenced = P->enabled;
+  for (uint32_t k = 0; k < n && delta; ++k) {  // where the shadow lies; one without a window is empty, wherever it is read
+    const uint32_t i = instances[k];
+    for (int a = 0; a < 3; ++a) {
+      const int64_t d = P->has_window[i] ? ok[3 * (size_t)k + a] - P->window[3 * (size_t)i + a] : 0;
+      recs[k].sd[a] = (int32_t)std::max<int64_t>(std::min<int64_t>(d, INT32_MAX / 2), INT32_MIN / 2);  // (beyond the window either way)
+    }
+  }
+  if ((rc = layered ? openLayers(h) : openDevice(h))) return rc;
+  const uint32_t np = layered ? 3u : 2u;
+  const size_t cols = h->dv.cols, n_all = h->desc.n_instances;
+  if (delta && (!P->d_shadow || P->shadow_planes != np)) {  // (configure_layers since: the master was emptied with it)
+    size_t have = 0;
+    if (P->d_shadow) {
+      HIP_TRY(waitStream(h->stream));
+      HIP_TRY(hipFree(P->d_shadow));
+      P->d_shadow = nullptr;
+    }
+    if ((rc = growDevice(h, &P->d_shadow, &have, n_all * np * cols, true))) return rc;
+    P->shadow_planes = np;
+  }
+  const size_t o_totals = (sizeof(C3dExportRec) * n + 15) & ~(size_t)15;
+  if ((rc = growStage(h, o_totals + sizeof(uint32_t) * 4 * n))) return rc;
+  if ((rc = growDevice(h, &P->d_counts, &P->count_words, 4 * (size_t)blocks + 4 * (size_t)n, false))) return rc;
+  HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+  memcpy(P->h_stage, recs.data(), sizeof(C3dExportRec) * n);
+  HIP_TRY(hipMemcpyAsync(P->d_stage, P->h_stage, sizeof(C3dExportRec) * n, hipMemcpyHostToDevice, h->stream));
+  C3dExport e{};
+  e.recs = reinterpret_cast<const C3dExportRec*>(P->d_stage);
+  e.shadow = P->d_shadow;
+  e.counts = P->d_counts;
+  e.offsets = P->d_counts + 2 * (size_t)blocks;
+  e.totals = P->d_counts + 4 * (size_t)blocks;
+  e.n = n;
+  e.blocks = blocks;
+  e.max_blocks = max_blocks;
+  e.np = np;
+  e.delta = delta ? 1 : 0;
+  const C3dLayersDev ly = layered ? h->layered->ly : C3dLayersDev{};
+  launch_c3d_export_count(h->dv, ly, e, h->stream);
+  if ((rc = checkLaunch())) return rc;
+  uint32_t* totals = reinterpret_cast<uint32_t*>(P->h_stage + o_totals);
+  HIP_TRY(hipMemcpyAsync(totals, e.totals, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  uint64_t n_values = 0, n_bounds = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t i = instances[k];
+    navgpu_c3d_update_msg& m = msgs[k];
+    m = navgpu_c3d_update_msg{};
+    m.instance = i;
+    m.update_seq = sequenced ? P->seq[i] : 0u;
+    m.bounds_seq = delta || !sequenced ? m.update_seq : m.update_seq - 1u;  // (the sentinel of a first map, costmap_3d_publisher.cpp:139-143)
+    m.universe = delta ? 0 : 1;
+    m.first_value = totals[4 * k];
+    m.n_values = totals[4 * k + 1];
+    m.first_bound = totals[4 * k + 2];
+    m.n_bounds = totals[4 * k + 3];
+    if (delta && P->has_window[i]) m.n_forgotten = forgottenBoxes(P->window.data() + 3 * (size_t)i, ok.data() + 3 * (size_t)k, size, m.forgotten);
+    n_values += m.n_values;
+    n_bounds += m.n_bounds;
+  }
+  if (!values && !bounds) return NAVGPU_OK;  // counted only: nothing is committed
+  if (n_values > value_capacity || n_bounds > bounds_capacity) {
+    g_last_error = "navgpu_costmap3d_export: " + std::to_string(n_values) + " value and " + std::to_string(n_bounds) + " bounds leaves exceed the capacities";
+    return NAVGPU_ERR_CAPACITY;
+  }
+  if ((rc = growDevice(h, &P->d_values, &P->value_capacity, (size_t)n_values, false))) return rc;
+  if ((rc = growDevice(h, &P->d_bounds, &P->bounds_capacity, (size_t)n_bounds, false))) return rc;
+  e.values = P->d_values;
+  e.bounds = P->d_bounds;
+  e.value_capacity = (uint32_t)n_values;
+  e.bounds_capacity = (uint32_t)n_bounds;
+  if (n_values || n_bounds) {
+    launch_c3d_export_emit(h->dv, ly, e, h->stream);
+    if ((rc = checkLaunch())) return rc;
+  }
+  if (delta) {
+    launch_c3d_shadow_copy(h->dv, ly, e, P->d_shadow, h->stream);
+    if ((rc = checkLaunch())) return rc;
+  }
+  if (n_values) HIP_TRY(hipMemcpyAsync(values, P->d_values, sizeof(navgpu_c3d_leaf) * (size_t)n_values, hipMemcpyDeviceToHost, h->stream));
+  if (n_bounds) HIP_TRY(hipMemcpyAsync(bounds, P->d_bounds, sizeof(navgpu_c3d_leaf) * (size_t)n_bounds, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(waitStream(h->stream));
+  for (uint32_t k = 0; k < n && delta; ++k) {  // published: the host's view follows
+    const uint32_t i = instances[k];
+    ++P->seq[i];
+    P->has_window[i] = 1;
+    std::copy_n(ok.begin() + 3 * (size_t)k, 3, P->window.begin() + 3 * (size_t)i);
+  }
+  return NAVGPU_OK;
+}
+
+int navgpu_costmap3d_layer_resubscribe(navgpu_costmap3d* h, uint32_t instance, uint32_t layer) {
+  if (!h) return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_layer_resubscribe");
+  if (rc) return rc;
+  C3dLayers* L = h->layered;
+  if (instance >= h->desc.n_instances || layer >= L->layers.size() || !costmapLayer(L->layers[layer])) return NAVGPU_ERR_INVALID;
+  C3dPublish* P = publishState(h);
+  if (P->subs_of == L && !P->subs.empty()) P->subs[(size_t)instance * L->ly.nc + L->index[layer]] = C3dPublish::Sub();
+  return NAVGPU_OK;  // (states that do not exist yet start over by themselves)
+}
+
+int navgpu_costmap3d_layer_update_cells(navgpu_costmap3d* h, uint32_t n_msgs, const navgpu_c3d_update_msg* msgs, const uint32_t* layers, int32_t cell_mode,
+                                        const navgpu_c3d_leaf* values, uint32_t n_values, const navgpu_c3d_leaf* bounds, uint32_t n_bounds,
+                                        int32_t* verdicts_out) {
+  if (!h || !msgs || !layers || (cell_mode != NAVGPU_C3D_CELLS_BINARY && cell_mode != NAVGPU_C3D_CELLS_AS_GIVEN) || (n_values && !values) ||
+      (n_bounds && !bounds))
+    return NAVGPU_ERR_INVALID;
+  C3dGuard guard_(h);
+  int rc = layeredHandle(h, "navgpu_costmap3d_layer_update_cells");
+  if (rc) return rc;
+  if ((uint64_t)n_values + n_bounds > h->desc.max_boxes) {
+    g_last_error = "navgpu_costmap3d_layer_update_cells: " + std::to_string((uint64_t)n_values + n_bounds) + " leaves exceed max_boxes";
+    return NAVGPU_ERR_CAPACITY;
+  }
+  C3dLayers* L = h->layered;
+  C3dPublish* P = publishState(h);
+  const uint32_t nc = L->ly.nc;
+  std::vector<C3dPublish::Sub> subs = P->subs_of == L && P->subs.size() == (size_t)h->desc.n_instances * nc
+                                          ? P->subs
+                                          : std::vector<C3dPublish::Sub>((size_t)h->desc.n_instances * nc);  // (a configure_layers resets them all)
+  std::vector<uint8_t> seen(subs.size(), 0);
+  std::vector<int32_t> verdicts(n_msgs);
+  std::vector<C3dCellsMsg> applied;
+  std::vector<C3dBoxCells> leaves;
+  const int64_t size[3] = {h->dv.sx, h->dv.sy, h->dv.sz};
+  uint32_t max_columns = 0;
+  auto bad = [&](uint32_t k, const char* why) {
+    g_last_error = "navgpu_costmap3d_layer_update_cells: message " + std::to_string(k) + ": " + why;
+    return NAVGPU_ERR_INVALID;
+  };
+  // the clipped cells of a lattice box [lo, lo + cnt) per axis; false: none inside the window
+  auto clip = [&](const int64_t* ok, const int64_t* lo, const int64_t* cnt, C3dBoxCells* c) {
+    int64_t first[3], count[3];
+    for (int a = 0; a < 3; ++a) {
+      first[a] = std::max<int64_t>(lo[a] - ok[a], 0);
+      count[a] = std::min<int64_t>(lo[a] - ok[a] + cnt[a], size[a]) - first[a];
+      if (count[a] <= 0) return false;
+    }
+    c->zmask = (count[2] >= 64 ? ~0ull : (((uint64_t)1 << count[2]) - 1)) << first[2];
+    c->x0 = (uint32_t)first[0];
+    c->y0 = (uint32_t)first[1];
+    c->nx = (uint32_t)count[0];
+    c->ny = (uint32_t)count[1];
+    return true;
+  };
+  for (uint32_t k = 0; k < n_msgs; ++k) {
+    const navgpu_c3d_update_msg& m = msgs[k];
+    if (m.instance >= h->desc.n_instances || layers[k] >= L->layers.size() || !costmapLayer(L->layers[layers[k]])) return bad(k, "names no instance or no costmap layer");
+    const uint32_t slot = L->index[layers[k]];
+    const size_t pair = (size_t)m.instance * nc + slot;
+    if (seen[pair]) return bad(k, "shares its (instance, layer) with another");
+    seen[pair] = 1;
+    if ((uint64_t)m.first_value + m.n_values > n_values || (uint64_t)m.first_bound + m.n_bounds > n_bounds) return bad(k, "a range ends beyond its array");
+    if (m.n_forgotten > 2) return bad(k, "n_forgotten > 2");
+    for (uint32_t f = 0; f < m.n_forgotten; ++f)
+      for (int a = 0; a < 3; ++a)
+        if (m.forgotten[f][3 + a] < m.forgotten[f][a]) return bad(k, "a forgotten box is inverted");
+    auto leafOk = [](const navgpu_c3d_leaf& l) {
+      if (l.level > 6 || l.cls > NAVGPU_C3D_FREE) return false;
+      const int32_t mask = (1 << l.level) - 1;
+      return !((l.key[0] | l.key[1] | l.key[2]) & mask);  // (two's complement: a multiple of 2^level, floor-mod)
+    };
+    for (uint32_t j = 0; j < m.n_values; ++j)
+      if (!leafOk(values[m.first_value + j])) return bad(k, "a value leaf has a key not aligned to its level, a level > 6 or an unknown class");
+    for (uint32_t j = 0; j < m.n_bounds; ++j)
+      if (!leafOk(bounds[m.first_bound + j])) return bad(k, "a bounds leaf has a key not aligned to its level, a level > 6 or an unknown class");
+    int64_t ok[3];
+    if (!originKeys(h, m.instance, ok)) return NAVGPU_ERR_INVALID;
+    // mapCallback / mapUpdateCallback (octomap_server_layer_3d.cpp:281-350)
+    C3dPublish::Sub& s = subs[pair];
+    if (m.plain_map) {
+      if (s.using_updates) {
+        verdicts[k] = NAVGPU_C3D_IGNORED;
+        continue;
+      }
+    } else {
+      ++s.n_updates;
+      if (!s.first_full) {
+        if (s.n_updates == 1 && m.bounds_seq == m.update_seq) {
+          verdicts[k] = NAVGPU_C3D_IGNORED;
+          continue;
+        }
+        if (s.n_updates > 1) {  // the first full map was lost: subscribeUpdatesUnlocked (:179-186)
+          s.first_full = false;
+          s.n_updates = 0;
+          verdicts[k] = NAVGPU_C3D_RESYNC;
+          continue;
+        }
+        s.first_full = true;
+      } else if ((uint32_t)(s.last_seq + 1u) < m.bounds_seq) {
+        s.first_full = false;
+        s.n_updates = 0;
+        verdicts[k] = NAVGPU_C3D_RESYNC;
+        continue;
+      }
+      s.last_seq = m.bounds_seq;
+      s.using_updates = true;
+    }
+    verdicts[k] = NAVGPU_C3D_APPLIED;
+    C3dCellsMsg rec{};
+    rec.instance = m.instance;
+    rec.slot = slot;
+    rec.cur = L->cur[pair];
+    const bool universe = m.universe || m.plain_map;
+    uint32_t n_forgotten = 0;
+    for (uint32_t f = 0; f < m.n_forgotten && !universe; ++f) {
+      int64_t lo[3], cnt[3];
+      for (int a = 0; a < 3; ++a) {
+        lo[a] = m.forgotten[f][a];
+        cnt[a] = (int64_t)m.forgotten[f][3 + a] - m.forgotten[f][a] + 1;
+      }
+      C3dBoxCells c{};
+      if (!clip(ok, lo, cnt, &c)) continue;
+      rec.fz[n_forgotten] = c.zmask;
+      const int32_t box[4] = {(int32_t)c.x0, (int32_t)(c.x0 + c.nx - 1), (int32_t)c.y0, (int32_t)(c.y0 + c.ny - 1)};
+      std::copy_n(box, 4, rec.fbox[n_forgotten]);
+      ++n_forgotten;
+    }
+    rec.flags = (universe ? 1u : 0u) | (n_forgotten << 1);
+    const size_t leaves_before = leaves.size();
+    auto put = [&](const navgpu_c3d_leaf& l, int32_t plane) {
+      const int64_t lo[3] = {l.key[0], l.key[1], l.key[2]}, edge = (int64_t)1 << l.level, cnt[3] = {edge, edge, edge};
+      C3dBoxCells c{};
+      if (!clip(ok, lo, cnt, &c)) return;
+      c.cls = plane;
+      c.reserved = (int32_t)applied.size();
+      max_columns = std::max(max_columns, c.nx * c.ny);
+      leaves.push_back(c);
+    };
+    for (uint32_t j = 0; j < m.n_bounds && !universe; ++j) put(bounds[m.first_bound + j], 0);
+    for (uint32_t j = 0; j < m.n_values; ++j) {
+      const navgpu_c3d_leaf& l = values[m.first_value + j];
+      put(l, 1 + (cell_mode == NAVGPU_C3D_CELLS_BINARY && l.cls == NAVGPU_C3D_NONLETHAL ? (int32_t)NAVGPU_C3D_LETHAL : (int32_t)l.cls));
+    }
+    if (rec.flags || leaves.size() != leaves_before) applied.push_back(rec);  // (an empty delta, or one wholly off the window, queues nothing)
+  }
+  if (!applied.empty()) {
+    if ((rc = openLayers(h))) return rc;
+    const size_t o_leaves = sizeof(C3dCellsMsg) * applied.size(), bytes = o_leaves + sizeof(C3dBoxCells) * leaves.size();
+    if ((rc = growStage(h, bytes))) return rc;
+    if (P->scratch_msgs < applied.size() || !P->d_scratch || !P->d_touched) {
+      size_t a = P->d_scratch ? P->scratch_msgs : 0, b = P->d_touched ? P->scratch_msgs : 0;
+      P->scratch_msgs = 0;
+      if ((rc = growDevice(h, &P->d_scratch, &a, applied.size() * 4 * h->dv.cols, true))) return rc;
+      if ((rc = growDevice(h, &P->d_touched, &b, applied.size() * L->ly.tw, true))) return rc;
+      P->scratch_msgs = applied.size();
+    }
+    HIP_TRY(waitStream(h->stream));  // (the staging block is free)
+    memcpy(P->h_stage, applied.data(), o_leaves);
+    if (!leaves.empty()) memcpy(P->h_stage + o_leaves, leaves.data(), sizeof(C3dBoxCells) * leaves.size());
+    HIP_TRY(hipMemcpyAsync(P->d_stage, P->h_stage, bytes, hipMemcpyHostToDevice, h->stream));
+    C3dCells c{};
+    c.msgs = reinterpret_cast<const C3dCellsMsg*>(P->d_stage);
+    c.leaves = reinterpret_cast<const C3dBoxCells*>(P->d_stage + o_leaves);
+    c.scratch = P->d_scratch;
+    c.touched = P->d_touched;
+    c.n_msgs = (uint32_t)applied.size();
+    c.n_leaves = (uint32_t)leaves.size();
+    c.max_columns = max_columns;
+    launch_c3d_cells(h->dv, L->ly, c, h->stream);
+    if ((rc = checkLaunch())) return rc;
+  }
+  P->subs.swap(subs);
+  P->subs_of = L;
+  if (verdicts_out) std::copy(verdicts.begin(), verdicts.end(), verdicts_out);
+  return NAVGPU_OK;  // queued
 }
 
 }  // extern "C"

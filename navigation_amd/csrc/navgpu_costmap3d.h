@@ -139,6 +139,46 @@ void launch_c3d_roll(const C3dDev& d, const C3dLayersDev& ly, int32_t layered, c
 void launch_c3d_reset_box(const C3dDev& d, const C3dLayersDev& ly, const C3dResetRec* recs, uint32_t n, uint32_t max_tiles, const C3dResetSlots& slots,
                           hipStream_t stream);
 
+// ---- publishing: pruned octree leaves out of a handle and into a layer (costmap3d_publish_kernels.hip, include/navgpu_costmap3d_publish.h) ----
+// An export works by 64 x 64-column blocks aligned to the lattice, so that a block holds whole octree nodes up to level 6.
+struct C3dExportRec {     // one listed instance
+  int32_t ok[3];          // the window's lattice origin
+  int32_t sd[3];          // shadow column = window column + (sd[0], sd[1]); shadow level = window level + sd[2]
+  int32_t bx0, by0;       // the first block: floor(ok / 64)
+  uint32_t nbx, nby;      // blocks the window meets
+  uint32_t instance, first_block;  // first_block: the instance's first entry in counts / offsets
+};
+struct C3dExport {
+  const C3dExportRec* recs;  // [n]
+  const uint64_t* shadow;    // [n_instances][np][cols] the master as last published (DELTA)
+  uint32_t* counts;          // [blocks][2] leaves of a block: values, bounds
+  uint32_t* offsets;         // [blocks][2] their exclusive prefix over the whole list
+  uint32_t* totals;          // [n][4] first_value, n_values, first_bound, n_bounds
+  navgpu_c3d_leaf *values, *bounds;
+  uint32_t value_capacity, bounds_capacity;
+  uint32_t n, blocks, max_blocks;  // max_blocks: the most blocks one listed instance has
+  uint32_t np;               // planes of the master: 3 layered, 2 not
+  int32_t delta;
+};
+// one applied message of a layer_update_cells call
+struct C3dCellsMsg {
+  uint64_t fz[2];        // the forgotten boxes' levels
+  int32_t fbox[2][4];    // their columns x0, x1, y0, y1 (inclusive), clipped to the window
+  uint32_t instance, slot, cur;
+  uint32_t flags;        // bit 0: universe; bits 1..2: the number of forgotten boxes that meet the window
+};
+struct C3dCells {
+  const C3dCellsMsg* msgs;    // [n_msgs]
+  const C3dBoxCells* leaves;  // [n_leaves]: cls is the scratch plane (0 E, 1 + class), reserved the message
+  uint64_t* scratch;          // [n_msgs][4][cols] E and the value leaves' cells by class; all zero between calls
+  uint32_t* touched;          // [n_msgs][tw] tiles with a scratch bit; all zero between calls
+  uint32_t n_msgs, n_leaves, max_columns;
+};
+void launch_c3d_export_count(const C3dDev& d, const C3dLayersDev& ly, const C3dExport& e, hipStream_t stream);  // count, scan, totals
+void launch_c3d_export_emit(const C3dDev& d, const C3dLayersDev& ly, const C3dExport& e, hipStream_t stream);
+void launch_c3d_shadow_copy(const C3dDev& d, const C3dLayersDev& ly, const C3dExport& e, uint64_t* shadow, hipStream_t stream);
+void launch_c3d_cells(const C3dDev& d, const C3dLayersDev& ly, const C3dCells& c, hipStream_t stream);
+
 void launch_c3d_rasterize(const C3dDev& d, uint32_t instance, int32_t mode, const C3dBoxCells* boxes, uint32_t n_boxes,
                           uint32_t max_columns, hipStream_t stream);
 void launch_c3d_query(const C3dDev& d, const C3dQuery& q, hipStream_t stream);
